@@ -5,7 +5,8 @@ One "step" = one tick of every env of the batch, on synthetic input: the fixed-t
 (cygym_amd/topology.py) and the alternating defender/attacker action script, pre-generated
 on device so that all inputs are resident in HBM when a timed region starts.
 
-Two ways of issuing the same K ticks are timed, from the same state, and must end with the same rewards:
+Two ways of issuing the same K ticks are timed under `--full` (a plain run times the headline one only), from the same
+state, and must end with the same rewards:
 
   * `per_tick_stepping` -- K x cygym_step: one launch per tick (per sub-batch), i.e. what `env.step()` drives and
     what a closed-loop policy can use.  THIS is `value` / `roofline` (the reference's callers are closed-loop:
@@ -17,9 +18,16 @@ Two ways of issuing the same K ticks are timed, from the same state, and must en
   * `fused_rollout` -- cygym_rollout: K ticks in ONE launch (open-loop scripts only; state on chip between ticks;
     every tick's observation / reward / done still written to HBM).  `--headline rollout` swaps the two.
 
-Every timed region times exactly K steps and is repeated `--reps` times from the same state (restored, untimed,
-between repetitions); the MEDIAN repetition is reported (max over ranks first).  HIP events on the launch stream
-give `roofline.launch_us`.
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it sets up, warms
+up, times ONE region of exactly K steps of the headline way of issuing them, and prints the result line (`value`,
+`ms_per_step` = that region's wall time / K).  `--full` adds everything else, as described below: the other way of
+issuing the ticks, `--reps` (11) repetitions of every timed region with the MEDIAN reported (max over ranks first) and
+HIP-event repetitions for `roofline` (`launch_us`), the measured device-copy bandwidth, the CPU baseline, the
+closed-loop and IPPO consumers, the other BASELINE configs and, for N > 1, the gathered-returns check.
+
+`--dump-outputs DIR` writes what the headline path returned for the last timed tick (obs, raw, shaped, done of rank 0's
+shard) as DIR/<name>.npy in float32 / float64; above 64 MB in all, a fixed seeded sample of env rows is written.  The
+inputs depend only on the arguments, so two builds can be compared output for output.
 
 Contract (see the task description): `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver
 launches one rank per GPU with torch.distributed.run.  Envs are independent, so ranks shard the batch by env id
@@ -160,18 +168,19 @@ class Dist:
             self.dist.destroy_process_group()
 
 
-def timed_reps(D: Dist, env, keep, reps, issue):
+def timed_reps(D: Dist, env, keep, reps, issue, events=True):
     """`reps` repetitions of one timed region: restore the state (untimed), barrier + synchronize, issue, barrier +
-    synchronize.  Returns (median wall seconds, median HIP-event seconds), each the max over ranks per repetition.
-    The wall clock and the HIP events are taken in SEPARATE repetitions (`reps` of each): the two event records are
-    stream operations of their own, and inside the wall-clocked region they cost ~0.2 us per step at K = 20."""
+    synchronize.  Returns (median wall seconds, median HIP-event seconds or None, wall seconds per repetition), each the
+    max over ranks per repetition.  The wall clock and the HIP events are taken in SEPARATE repetitions (`reps` of each,
+    the event ones only with `events`): the two event records are stream operations of their own, and inside the
+    wall-clocked region they cost ~0.2 us per step at K = 20."""
     torch = D.torch
     walls, evs = [], []
-    for i in range(2 * reps):
+    for i in range(2 * reps if events else reps):
         for k, v in keep.items():
             env.state[k].copy_(v)
         D.barrier()
-        if i & 1:
+        if events and i & 1:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()                # HIP events on the stream the kernels are launched on (torch's current stream)
             issue()
@@ -187,12 +196,17 @@ def timed_reps(D: Dist, env, keep, reps, issue):
         D.barrier()
         walls.append(time.perf_counter() - t0)
     walls = D.max_over_ranks(walls)
+    if not events:
+        return float(np.median(walls)), None, walls
     evs = D.max_over_ranks(evs)
     return float(np.median(walls)), float(np.median(evs)), walls
 
 
-def run_workload(D: Dist, name, n_per_gpu, K, W, reps, sub, fused_T, seed, max_extra, want_rollout=True):
-    """All legs of one workload on this rank's shard.  Returns (record, env-side objects for the CPU baseline)."""
+def run_workload(D: Dist, name, n_per_gpu, K, W, reps, sub, fused_T, seed, max_extra, want_rollout=True, full=True,
+                 headline="per_tick"):
+    """All legs of one workload on this rank's shard; without `full` only the `headline` leg, timed on the wall clock
+    alone (no HIP-event repetitions, no roofline).  Returns (record, env-side objects for the CPU baseline, {leg: copies
+    of what that leg returned for the last timed tick})."""
     import torch
     from cygym_amd import abi
     from cygym_amd import spec as S
@@ -206,24 +220,28 @@ def run_workload(D: Dist, name, n_per_gpu, K, W, reps, sub, fused_T, seed, max_e
     L = max(1, M // 8)
     env = BatchedCyberDefenseEnv(topo, cfg, n_per_gpu, init, device=dev, max_groups=1, max_devs=L)
     N = n_per_gpu
-    scripts = []   # the action script of every tick, generated on device: inputs resident in HBM before timing
+    # the action script of every tick, generated on device: inputs resident in HBM before timing.  One zeroed tensor per
+    # field with a leading tick dimension (the generator leaves the unused tail of dev_idx alone), one view per tick.
+    block = {k: torch.zeros((W + K,) + tuple(v.shape), dtype=v.dtype, device=dev) for k, v in env.act.items()}
+    scripts = [{k: v[t] for k, v in block.items()} for t in range(W + K)]
     for t in range(W + K):
-        act = {k: torch.empty_like(v) for k, v in env.act.items()}
-        env.gen_actions(t, act)
-        scripts.append(act)
-    # clock ramp: a quarter of a second of untimed stepping first (a workload that follows an idle stretch -- the CPU
-    # baseline, a process start -- otherwise runs its few hundred microseconds of timed region at idle clocks: the
-    # short cfg2 legs came out up to 2x low), then back to the initial state
-    t_end = time.perf_counter() + 0.25
-    while time.perf_counter() < t_end:
-        for t in range(W + K):
-            env.step(scripts[t])
-        torch.cuda.synchronize(dev)
+        env.gen_actions(t, scripts[t])
     env.load_state(init)
     for t in range(W):
         env.step(scripts[t])
     torch.cuda.synchronize(dev)
     keep = {k: env.state[k].clone() for k in abi.BUFFER_FIELDS}   # the state at tick W: every timed region starts here
+    # clock ramp: a quarter of a second of untimed stepping right before the first timed region (a workload that follows
+    # an idle stretch -- the CPU baseline, a process start, the host-side state load -- otherwise runs its few hundred
+    # microseconds of timed region at idle clocks: the short cfg2 legs came out up to 2x low); every timed region then
+    # restores the state at tick W.  Chunks of at most 256 ticks, so that a long script does not stretch the ramp.
+    t_end = time.perf_counter() + 0.25
+    t = 0
+    while time.perf_counter() < t_end:
+        for _ in range(min(W + K, 256)):
+            env.step(scripts[t])
+            t = (t + 1) % (W + K)
+        torch.cuda.synchronize(dev)
     B = algorithmic_bytes(M, topo.E)
     total_envs = N * D.world
     main = torch.cuda.current_stream(dev)
@@ -255,65 +273,87 @@ def run_workload(D: Dist, name, n_per_gpu, K, W, reps, sub, fused_T, seed, max_e
         graph = torch.cuda.CUDAGraph()
 
     def leg(issue, launches_per_tick, what):
-        wall, ev, walls = timed_reps(D, env, keep, reps, issue)
-        r = roofline_block(N * B, ev / K, "step_kernel<WPB, M, FUSED=0, ..>", 1, wall / K)
-        r["launches_per_tick"] = launches_per_tick
-        return {"what": what, "value": total_envs * K / wall, "unit": "env-steps/s", "ms_per_step": wall / K * 1e3,
-                "sub_batches": launches_per_tick, "reps": reps, "rep_spread": [min(walls) / K * 1e3, max(walls) / K * 1e3],
-                "roofline": r, "last_raw_reward_sum": float(env.raw.sum())}
+        wall, ev, walls = timed_reps(D, env, keep, reps, issue, events=full)
+        rec = {"what": what, "value": total_envs * K / wall, "unit": "env-steps/s", "ms_per_step": wall / K * 1e3,
+               "sub_batches": launches_per_tick, "reps": reps, "rep_spread": [min(walls) / K * 1e3, max(walls) / K * 1e3],
+               "last_raw_reward_sum": float(env.raw.sum())}
+        if full:
+            r = roofline_block(N * B, ev / K, "step_kernel<WPB, M, FUSED=0, ..>", 1, wall / K)
+            r["launches_per_tick"] = launches_per_tick
+            rec["roofline"] = r
+        return rec
 
-    # (plain env.step() calls: the same K launches replayed from one HIP graph measured the same -- 15.44-15.45 against 15.39-15.50 us
-    # per step at K = 20 -- the host enqueues a step in less time than the GPU runs one)
-    one = leg(single, 1, "K launches of cygym_step, one full-batch launch per tick")
-    if sub > 1:
-        with torch.cuda.stream(cap):
-            _pipelined(cap)                     # warm-up outside the capture
+    want_rollout = want_rollout and fused_T != 0 and (full or headline == "rollout")
+    outputs = {}
+    per_tick, same_sub = None, True
+    if full or not want_rollout:
+        # (plain env.step() calls: the same K launches replayed from one HIP graph measured the same -- 15.44-15.45 against 15.39-15.50 us
+        # per step at K = 20 -- the host enqueues a step in less time than the GPU runs one)
+        one = leg(single, 1, "K launches of cygym_step, one full-batch launch per tick") if full or sub == 1 else None
+        if sub > 1:
+            with torch.cuda.stream(cap):
+                _pipelined(cap)                     # warm-up outside the capture
+                torch.cuda.synchronize(dev)
+                with torch.cuda.graph(graph, stream=cap):
+                    _pipelined(cap)
             torch.cuda.synchronize(dev)
-            with torch.cuda.graph(graph, stream=cap):
-                _pipelined(cap)
-        torch.cuda.synchronize(dev)
-        per_tick = leg(pipelined, sub, f"K ticks of cygym_step_range on {sub} sub-batches of {per} envs, one HIP stream each, replayed "
-                       "from one HIP graph (closed-loop capable: every tick of every sub-batch is its own launch)")
-        per_tick["single_launch"] = {k: one[k] for k in ("value", "ms_per_step", "roofline", "rep_spread")}
-        same_sub = per_tick["last_raw_reward_sum"] == one["last_raw_reward_sum"]
-    else:
-        per_tick, same_sub = one, True
+            per_tick = leg(pipelined, sub, f"K ticks of cygym_step_range on {sub} sub-batches of {per} envs, one HIP stream each, replayed "
+                           "from one HIP graph (closed-loop capable: every tick of every sub-batch is its own launch)")
+            if one is not None:
+                per_tick["single_launch"] = {k: one[k] for k in ("value", "ms_per_step", "roofline", "rep_spread")}
+                same_sub = per_tick["last_raw_reward_sum"] == one["last_raw_reward_sum"]
+        else:
+            per_tick = one
+        outputs["per_tick"] = {"obs": env.obs.clone(), "raw": env.raw.clone(), "shaped": env.shaped.clone(), "done": env.done.clone()}
 
     rollout = None
-    if want_rollout and fused_T != 0:
+    if want_rollout:
         T = K if fused_T < 0 else min(fused_T, K)
+        shared = None
+        if fused_T < 0:
+            # all K ticks in one launch -- unless their outputs would take more than half the free device memory (a long
+            # --steps): then launches of as many ticks as fit, all writing one output buffer
+            fit = int(torch.cuda.mem_get_info(dev)[0] // 2 // (N * (M * 6 * 4 + 8 + 8 + 1)))
+            if fit < K:
+                T = max(1, fit)
+                _, shared = env.alloc_rollout(T)
         chunks = []
         for c in range((K + T - 1) // T):
             lo, hi = W + c * T, min(W + K, W + (c + 1) * T)
             act = {k: torch.stack([scripts[t][k] for t in range(lo, hi)]).contiguous() for k in scripts[0]}
-            _, out = env.alloc_rollout(hi - lo)
+            out = env.alloc_rollout(hi - lo)[1] if shared is None else {k: v[:hi - lo] for k, v in shared.items()}
             chunks.append((act, out))
 
         def fused():
             for act, out in chunks:
                 env.rollout(act, out, check=False)    # asynchronous form; the status word is read once, after the timed region
-        wall, ev, walls = timed_reps(D, env, keep, reps, fused)
+        wall, ev, walls = timed_reps(D, env, keep, reps, fused, events=full)
         n_launch = len(chunks)
-        r = roofline_block(N * B * K / n_launch, ev / n_launch, "step_kernel<WPB, M, FUSED=1, ..>", K / n_launch, wall / n_launch)
-        r["frac_without_state_term"] = (N * (B - state_term_bytes(M)) * K / n_launch) / (max(ev, wall) / n_launch) / 1e9 / HBM_PEAK_GBS
         rollout = {"what": f"cygym_rollout: {T} ticks per launch (open loop, pre-staged action script; state on chip between "
                            "ticks; every tick's obs / reward / done written to HBM)",
                    "value": total_envs * K / wall, "unit": "env-steps/s", "ms_per_step": wall / K * 1e3, "reps": reps,
-                   "rep_spread": [min(walls) / K * 1e3, max(walls) / K * 1e3], "roofline": r,
+                   "rep_spread": [min(walls) / K * 1e3, max(walls) / K * 1e3],
                    "last_raw_reward_sum": float(chunks[-1][1]["raw"][-1].sum())}
+        if full:
+            r = roofline_block(N * B * K / n_launch, ev / n_launch, "step_kernel<WPB, M, FUSED=1, ..>", K / n_launch, wall / n_launch)
+            r["frac_without_state_term"] = (N * (B - state_term_bytes(M)) * K / n_launch) / (max(ev, wall) / n_launch) / 1e9 / HBM_PEAK_GBS
+            rollout["roofline"] = r
+        outputs["rollout"] = {k: v[-1].clone() for k, v in chunks[-1][1].items()}
         del chunks
 
+    check = {"last_raw_reward_sum": (per_tick if per_tick is not None else rollout)["last_raw_reward_sum"]}
+    if full:
+        check["same_trajectory_all_ways"] = same_sub and (rollout is None or rollout["last_raw_reward_sum"] == per_tick["last_raw_reward_sum"])
+    # the fixed-topology run must never have wanted an edge it could not add (CG_E_TOPO_OVF)
+    check["envs_that_needed_an_unavailable_edge"] = int(((env.state["ienv"][:, S.I_FLAGS] & S.E_TOPO_OVF) != 0).sum())
     x_used = (env.state["ienv"][:, S.I_FLAGS].to(torch.int64) & 0xFFFFFFFF) >> 16   # live entries of the extra-edge lists
     rec = {"workload": f"{name}: {desc}", "envs_per_gpu": N, "devices": M, "edges": topo.E, "exploits": topo.X,
            "max_extra_edges": topo.max_extra, "envs_with_added_edges": int((x_used > 0).sum()),
            "bytes_per_env_step": B, "layout_bytes_per_env_step": layout_bytes(M, topo.E),
-           "per_tick_stepping": per_tick, "fused_rollout": rollout,
-           "check": {"last_raw_reward_sum": per_tick["last_raw_reward_sum"],
-                     "same_trajectory_all_ways": same_sub and (rollout is None or rollout["last_raw_reward_sum"] == per_tick["last_raw_reward_sum"]),
-                     # the fixed-topology run must never have wanted an edge it could not add (CG_E_TOPO_OVF)
-                     "envs_that_needed_an_unavailable_edge": int(((env.state["ienv"][:, S.I_FLAGS] & S.E_TOPO_OVF) != 0).sum())}}
-    attach_traffic(rec, name, N)
-    return rec, (env, topo, init, cfg, M, L, scripts)
+           "per_tick_stepping": per_tick, "fused_rollout": rollout, "check": check}
+    if full:
+        attach_traffic(rec, name, N)
+    return rec, (env, topo, init, cfg, M, L, scripts), outputs
 
 
 def attach_traffic(rec, name, n_envs):
@@ -687,6 +727,29 @@ def brief(rec):
     return out
 
 
+DUMP_BUDGET = 60 * 10**6   # bytes of --dump-outputs in all: under 64 MB with the .npy headers
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(dirname, outputs):
+    """Write each output of the last timed tick as `dirname`/<name>.npy: float64 stays float64, everything else becomes
+    float32.  If they hold more than DUMP_BUDGET bytes together, the same fixed seeded sample of env rows (leading
+    dimension, sorted) is taken from every array."""
+    arrays = {}
+    for k, v in outputs.items():
+        a = v.cpu().numpy()
+        arrays[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        keep = max(1, int(n * DUMP_BUDGET // total))
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[rows]) for k, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+
+
 def spin_wait():
     """Host wait policy: spin instead of sleeping in hipDeviceSynchronize (hipDeviceScheduleSpin; must be set before the
     runtime creates its context, i.e. before torch touches the GPU).  A sleeping wait wakes up tens of microseconds after a
@@ -709,13 +772,20 @@ def main():
     ap.add_argument("--workload", default="target", choices=sorted(WORKLOADS))
     ap.add_argument("--envs", type=int, default=0, help="override envs per GPU")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--reps", type=int, default=11, help="repetitions of every timed K-step region (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the other way of issuing the steps, repeated "
+                         "timed regions and HIP-event roofline figures, device-copy bandwidth, CPU baseline, closed-loop and IPPO "
+                         "consumers, the other BASELINE configs, the gathered-returns check for N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline path returned for the last timed tick (rank 0's shard) as DIR/<name>.npy")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of every timed K-step region (median reported; default 1, with --full 11)")
     ap.add_argument("--sub-batches", type=int, default=0,
                     help="per-tick stepping: sub-batches / HIP streams the batch is pipelined over (0 = the workload's default, "
                          "1 = one full-batch launch per tick only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-closed-loop", action="store_true", help="skip the closed-loop grid consumer leg")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short runs of the other single-GPU BASELINE configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-closed-loop", action="store_true", help="with --full: skip the closed-loop grid consumer leg")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the short runs of the other single-GPU BASELINE configs")
     ap.add_argument("--max-extra", type=int, default=None,
                     help="capacity of the per-env list of edges evolve_network may add.  0: no list -- the fixed-topology run "
                          "of SURVEY.md 8d (with lambda_events = 0 only the attacker-star check can want an edge; bench.py "
@@ -728,8 +798,10 @@ def main():
     ap.add_argument("--fused", type=int, default=-1,
                     help="ticks per cygym_rollout launch (-1 = all K steps in one launch, 0 = skip the rollout leg)")
     ap.add_argument("--headline", default="per_tick", choices=["per_tick", "rollout"],
-                    help="which way of issuing the K steps fills value / roofline (the other one is reported beside it)")
+                    help="which way of issuing the K steps fills value / roofline (with --full the other one is reported beside it)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 11 if args.full else 1
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus != world_env:
@@ -744,11 +816,14 @@ def main():
     n_per_gpu = args.envs or WORKLOADS[name][0]
     sub = args.sub_batches or DEFAULT_SUB[name]
     max_extra_of = lambda w: DEFAULT_MAX_EXTRA[w] if args.max_extra is None else args.max_extra
-    rec, (env, topo, init, cfg, M, L, scripts) = run_workload(D, name, n_per_gpu, K, W, args.reps, sub, args.fused, args.seed,
-                                                               max_extra_of(name))
+    rec, (env, topo, init, cfg, M, L, scripts), outputs = run_workload(D, name, n_per_gpu, K, W, args.reps, sub, args.fused, args.seed,
+                                                                        max_extra_of(name), full=args.full, headline=args.headline)
     per_tick, rollout = rec["per_tick_stepping"], rec["fused_rollout"]
-    head = rollout if (rollout is not None and args.headline == "rollout") else per_tick
+    head = rollout if (rollout is not None and (args.headline == "rollout" or per_tick is None)) else per_tick
     other_key, other = ("per_tick_stepping", per_tick) if head is rollout else ("fused_rollout", rollout)
+    if args.dump_outputs and D.rank == 0:
+        dump_outputs(args.dump_outputs, outputs["rollout" if head is rollout else "per_tick"])
+    del outputs
 
     out = {
         "metric": "env-steps/sec", "value": head["value"], "unit": "env-steps/s", "n_gpus": D.world, "steps": K, "warmup": W,
@@ -757,16 +832,18 @@ def main():
         "config": {"workload": rec["workload"], "envs_per_gpu": n_per_gpu, "devices": M, "edges": topo.E,
                    "exploits": topo.X, "lambda_events": 0.0, "max_extra_edges": topo.max_extra,
                    "stepping": head["what"], "reps": args.reps, "host_wait": wait_policy,
-                   "parallelism": f"env-batch split x{D.world}, no step-path collective"},
-        "roofline": dict(head["roofline"]),
-        "check": rec["check"],
+                   "parallelism": f"env-batch split x{D.world}, no step-path collective", "full": args.full},
     }
-    out["roofline"].update({"bytes_per_env_step": rec["bytes_per_env_step"], "layout_bytes_per_env_step": rec["layout_bytes_per_env_step"]})
-    if head is per_tick and "single_launch" in per_tick:
-        out["single_launch_per_tick"] = per_tick["single_launch"]
-    if other is not None:
-        out[other_key] = other
-    if D.rank == 0:
+    if args.full:
+        out["roofline"] = dict(head["roofline"])
+        out["roofline"].update({"bytes_per_env_step": rec["bytes_per_env_step"], "layout_bytes_per_env_step": rec["layout_bytes_per_env_step"]})
+    out["check"] = rec["check"]
+    if args.full:
+        if head is per_tick and "single_launch" in per_tick:
+            out["single_launch_per_tick"] = per_tick["single_launch"]
+        if other is not None:
+            out[other_key] = other
+    if args.full and D.rank == 0:
         # also price the kernel against a device-copy bandwidth measured on this box
         bw = measured_copy_gbs(D.dev)
         out["roofline"]["measured_copy_peak"] = bw
@@ -774,7 +851,7 @@ def main():
     ident = D.identity()       # (a collective when N > 1: every rank calls it)
     if D.world > 1:
         out["ranks"] = ident
-    if D.world > 1:
+    if args.full and D.world > 1:
         # end-of-rollout gather of per-env returns over RCCL, checked against a single-rank recomputation:
         # restart from the initial state and run the first W + 4 ticks on every rank
         n_ticks = min(len(scripts), W + 4)
@@ -782,25 +859,25 @@ def main():
         for t in range(n_ticks):
             env.step(scripts[t])
         out["check"]["gathered_returns_match_single_rank"] = gathered_returns_check(D, env, scripts[:n_ticks], topo, init, cfg, L)
-    if D.rank == 0 and D.world == 1 and not args.no_cpu_baseline:
+    if args.full and D.rank == 0 and D.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(topo, init, cfg, M, L, scripts, W, args.cpu_seconds, args.cpu_threads)
     st = env.take_status()
     out["check"]["status_word"] = {"unpinned_scan": bool(st & 0x200), "busy_saturated": bool(st & 0x40)}
     env.close()
     del env, scripts
-    if not args.no_closed_loop and name == "target" and not args.envs:
+    if args.full and not args.no_closed_loop and name == "target" and not args.envs:
         per_tick_one = per_tick["single_launch"]["value"] if "single_launch" in per_tick else per_tick["value"]
         out["closed_loop_grid"] = closed_loop_block(D, per_tick_one, args.seed, n_per_gpu)
         out["ippo_rollout_collect"] = ippo_collect_block(D, args.seed, n_per_gpu)
 
     # the other BASELINE configs as short sub-records (parity-test sizes, here timed on the current kernels):
     # N = 1: cfg2 / cfg3 / cfg5; N > 1: cfg4 = the per-GPU shard of the 131072-env config
-    if not args.no_configs and not args.envs and name == "target":
+    if args.full and not args.no_configs and not args.envs and name == "target":
         others = ["cfg2", "cfg3", "cfg5"] if D.world == 1 else ["cfg4"]
         out["configs"] = {}
         for w in others:
             kk = min(K, 20 if w != "cfg5" else 10)
-            r, objs = run_workload(D, w, WORKLOADS[w][0], kk, min(W, 5), min(args.reps, 5), DEFAULT_SUB[w], -1, args.seed, max_extra_of(w))
+            r, objs, _ = run_workload(D, w, WORKLOADS[w][0], kk, min(W, 5), min(args.reps, 5), DEFAULT_SUB[w], -1, args.seed, max_extra_of(w))
             objs[0].close()
             del objs
             b = brief(r)

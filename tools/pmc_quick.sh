@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for set in "$@"; do
   i=$((i+1))
-  rocprofv3 --pmc $set --output-format csv -d "$OUT/p$i" -- python3 $REPO/bench.py --workload ${PMC_WORKLOAD:-target} --steps 20 --warmup 5 --reps 3 --no-cpu-baseline --no-configs --no-closed-loop > /dev/null 2> "$OUT/p$i.err"
+  rocprofv3 --pmc $set --output-format csv -d "$OUT/p$i" -- python3 $REPO/bench.py --full --workload ${PMC_WORKLOAD:-target} --steps 20 --warmup 5 --reps 3 --no-cpu-baseline --no-configs --no-closed-loop > /dev/null 2> "$OUT/p$i.err"
 done
 cd "$REPO"
 python3 - "$OUT" <<'PY'

@@ -5,7 +5,7 @@ Recipe (on the GPU box; counters in their own passes, never together with a trac
 for every single-GPU workload:
 
   cd /tmp && export TMPDIR=/tmp
-  B="python3 $REPO/bench.py --workload W --steps 20 --warmup 5 --reps 3 --no-cpu-baseline --no-configs"
+  B="python3 $REPO/bench.py --full --workload W --steps 20 --warmup 5 --reps 3 --no-cpu-baseline --no-configs"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/W/kt        -- $B
   rocprofv3 --pmc FETCH_SIZE       --output-format csv -d $OUT/W/pmc_fetch -- $B
   rocprofv3 --pmc WRITE_SIZE       --output-format csv -d $OUT/W/pmc_write -- $B

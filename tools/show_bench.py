@@ -9,7 +9,8 @@ def leg(name, v):
     if "single_launch" in v:
         sl = v["single_launch"]; s += f"  | single launch {sl['value']:.3e} frac {(sl['roofline'] if 'roofline' in sl else sl)['frac']:.3f}"
     print(s)
-print(d["config"]["workload"] if "config" in d else "", "| value", f"{d['value']:.3e}", "ms_per_step", d["ms_per_step"], "frac", d["roofline"]["frac"])
+print(d["config"]["workload"] if "config" in d else "", "| value", f"{d['value']:.3e}", "ms_per_step", d["ms_per_step"],
+      "frac", (d.get("roofline") or {}).get("frac", "n/a (a line of bench.py --full has it)"))
 leg("per_tick", d.get("per_tick_stepping")); leg("fused_rollout", d.get("fused_rollout"))
 for k, v in (d.get("configs") or {}).items():
     print(k); leg("per_tick", v.get("per_tick_stepping")); leg("fused_rollout", v.get("fused_rollout"))
