@@ -186,7 +186,7 @@ static size_t wave_lds_bytes(const DevTopo& t, int max_devs) {
 #define CG_RT_REG_CAP 20
 #endif
 static int choose_launch_with(cygym_handle* h, int max_devs, int* waves_out);
-static int choose_launch(cygym_handle* h, int max_devs) {
+static int plan_launch(cygym_handle* h, int max_devs) {
   // comp_by in LDS (as ever), or -- run-time sizes with M % 4 == 0 -- in global memory when that frees enough LDS for
   // another resident wave per CU (2048 devices without an extra-edge list: 4 -> 5)
   DevTopo& t = h->t;
@@ -211,6 +211,19 @@ static int choose_launch(cygym_handle* h, int max_devs) {
     return choose_launch_with(h, max_devs, &w_lds);
   }
   return rc;
+}
+// Transactional: the plan is made on a copy of the handle and committed only when it succeeds.  plan_launch clears the
+// placement flags before it tries the layouts, while choose_launch_with writes the LDS sizes only on success: a failed
+// re-plan (a longer device list that does not fit) must not leave the old sizes under the new flags.
+static int choose_launch(cygym_handle* h, int max_devs) {
+  cygym_handle p = *h;
+  const int rc = plan_launch(&p, max_devs);
+  if (rc != 0) return rc;
+  h->t.cby_global = p.t.cby_global; h->t.lists_global = p.t.lists_global; h->t.x_bytes = p.t.x_bytes;
+  h->t.lds_bytes = p.t.lds_bytes; h->t.in_lds = p.t.in_lds;
+  h->wpb = p.wpb; h->wpb_fused = p.wpb_fused; h->wave_lds = p.wave_lds; h->shared_lds = p.shared_lds;
+  h->max_devs = p.max_devs; h->wide = p.wide;
+  return 0;
 }
 static int choose_launch_with(cygym_handle* h, int max_devs, int* waves_out) {
   DevTopo& t = h->t;

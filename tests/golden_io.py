@@ -206,7 +206,9 @@ def compare_state(got: dict, exp: dict, label: str, ring_total=None):
     # ring: only the valid window (last min(total, R) entries) is defined
     gr = np.asarray(got["ring"]).astype(np.int64).reshape(gi.shape[0], S.LOG_RING, 2)
     xr = np.asarray(exp["ring"]).astype(np.int64).reshape(gi.shape[0], S.LOG_RING, 2)
-    for e in range(gi.shape[0]):
+    # (the window of total entries covers slots [0, min(total, R)); compared at once, reported per env in window order)
+    valid = np.arange(S.LOG_RING)[None, :] < np.minimum(xi[:, S.I_LOG_TOTAL], S.LOG_RING)[:, None]
+    for e in np.flatnonzero(((gr != xr).any(axis=2) & valid).any(axis=1)):
         tot = int(xi[e, S.I_LOG_TOTAL])
         n = min(tot, S.LOG_RING)
         for j in range(tot - n, tot):

@@ -471,13 +471,15 @@ def test_every_workgroup_shape(M, wpb, monkeypatch):
         env.close()
 
 
-def test_long_device_lists_replan_the_launch():
+@pytest.mark.parametrize("max_extra", [None, 0])
+def test_long_device_lists_replan_the_launch(max_extra):
     """Device lists as long as the network (max_devs = M, longer than the M/8 the handle was created for): the library
-    re-plans its LDS layout at the first step (cygym_step: max_devs > planned) -- also for the WIDE per-tick kernel, which
-    keeps the in-CSR maps in LDS -- and block / unblock / clean over whole-network lists match the oracle."""
+    re-plans its LDS layout at the first step (cygym_step: max_devs > planned) -- with the generator's extra-edge list for
+    the full-feature per-tick kernel, without one (max_extra = 0) for the WIDE per-tick kernel, which keeps the in-CSR maps
+    in LDS and still fits with a 256-entry list -- and block / unblock / clean over whole-network lists match the oracle."""
     from oracle import driver as od
     M, N = 256, 128
-    topo, init, ck = make_topology(M, 1, seed=4, n_active=240)
+    topo, init, ck = make_topology(M, 1, seed=4, n_active=240, max_extra=max_extra)
     cfg = abi.EnvConfig(seed=4, **ck)
     small = _env(topo, cfg, N, init, max_groups=1, max_devs=M // 8)
     small.gen_actions(0)
@@ -498,6 +500,11 @@ def test_long_device_lists_replan_the_launch():
             act["dev_idx"][e, :k] = rs.permutation(M)[:k]
         env.set_actions_numpy(act)
         obs, raw, shaped, done = env.step()
+        if t == 0:   # re-planned for lists of M entries, on the kernel this network selects
+            plan = env.launch_plan()
+            assert plan["wide"] == (1 if max_extra == 0 else 0), plan
+            if max_extra == 0:
+                assert plan["waves_per_workgroup"] == 16, plan
         o_obs, o_raw, _, _ = ob.step(act)
         got = env.state_numpy()
         got["ienv"] = got["ienv"].copy()

@@ -515,7 +515,9 @@ def test_tick_and_next_actor_as_one_launch_equals_two_launches():
     """cygym_step_actor (merge_launches: a tick and the next role's whole-actor launch as ONE kernel, the actor reading the flag
     planes the tick left in LDS) against the two-launch loop on the same strategies -- float weights, epsilon-greedy action
     types (the addressed Philox draw reads the rng tick the tick has just written back), a 2 x 2 population grid in env order
-    and a 1 x 1 grid, eager and graph replay: identical payoffs and final state, and the merged entry point really ran."""
+    and a 1 x 1 grid, eager and graph replay: identical payoffs and final state, and the merged entry point really ran.
+    Also at the bench's batch of 4096 envs (16 per CU: the largest batch the merged launch takes), as 2 x 2 x 1024 and
+    1 x 1 x 4096 from graph replay, and with an episode cap at that size."""
     from cygym_amd.batched_env import BatchedCyberDefenseEnv
     from cygym_amd.policies import ActorPolicy, mlp_actor
     from cygym_amd.rollout_grid import simulate_grid
@@ -525,7 +527,8 @@ def test_tick_and_next_actor_as_one_launch_equals_two_launches():
     X = abi.EnvConfig(seed=11, **ck).max_exploits
     dt, at = [1, 4, 5, 6, 7, 8, 9, 11, 12, 13, 2], [1, 2, 3]
     # (the last case: episodes end inside the run -- the tick reloads the snapshot into LDS and the actor behind it must see that)
-    for (nD, nA, n_mc), graph, cap in (((2, 2, 16), True, 1000), ((1, 1, 48), False, 1000), ((3, 2, 32), False, 1000), ((1, 2, 16), False, 9)):
+    for (nD, nA, n_mc), graph, cap in (((2, 2, 16), True, 1000), ((1, 1, 48), False, 1000), ((3, 2, 32), False, 1000), ((1, 2, 16), False, 9),
+                                       ((2, 2, 1024), True, 1000), ((1, 1, 4096), True, 1000), ((1, 2, 2048), True, 9)):
         N = nD * nA * n_mc
         cfg = abi.EnvConfig(seed=11, lambda_events=0.0, auto_reset=int(cap < 1000), episode_limit=cap, **ck)
 
