@@ -269,16 +269,13 @@ __device__ __forceinline__ void attacker_spread(Env& e, const KP& P, const int32
     for (int sweep = 0; sweep <= M + 1; ++sweep) {
       ++n_rounds;
       bool lost_any = false;    // some pick is not settled yet: another sweep is needed
-#ifndef CG_SPREAD_PRECHECK
-#define CG_SPREAD_PRECHECK 1
-#endif
       // Sweeps >= 1 first ask, for ALL blocks with the loads of four blocks in flight together, which sources lost their pick
       // (bit b of `need` <-> block b: at most 32 blocks); the block loop below then runs only for blocks that hold one.  A
       // verification sweep used to walk every block through its four dependent round trips -- 14 blocks, ~40 k cycles at 2048
       // devices -- to find the three or four sources that have to resume (profiles/r04_tail_hist_cfg5.txt).  A resumed source's
       // take that reaches a LATER source's target is reported as a conflict by the take itself, so the next sweep re-checks.
       uint32_t need = 0xFFFFFFFFu;
-      if (CG_SPREAD_PRECHECK && sweep > 0) {
+      if (sweep > 0) {
         need = 0u;
         constexpr int PB = 4;
 #pragma nounroll
@@ -331,15 +328,12 @@ __device__ __forceinline__ void attacker_spread(Env& e, const KP& P, const int32
             rescan = !spread_ok(T, vc, s);
           }
           if (rescan && !xrow) {
-#ifndef CG_LONG_PREFIX
-#define CG_LONG_PREFIX 1
-#endif
             // A long row that is not "full" (a hub's 47 slots at 2048 devices) first has its next four slots scanned by its own lane,
             // with -- and by the same instructions as -- the short rows of the block; only if none of them is a pick does the rest
             // of the row take a cooperative step.  (Those steps, four rows each and ~90 rows per exploit, were 40 us of a 165 us
             // tick at 4096 x 2048: timing ablation, PERFLOG.md; the usual pick is among a hub's first neighbours.)
             const int from = sweep == 0 ? o0 : k0 + 1;
-            const bool prefix = CG_LONG_PREFIX && CR > 1 && !shortrow && !full;
+            const bool prefix = CR > 1 && !shortrow && !full;
             if (shortrow || full || prefix) {
               const int lim1 = prefix ? (from + 4 < o1 ? from + 4 : o1) : o1;
               uint32_t low = 0;
@@ -353,17 +347,13 @@ __device__ __forceinline__ void attacker_spread(Env& e, const KP& P, const int32
                 if (k < o1) { v = (k - o0) + ((k - o0) >= s ? 1 : 0); low = T[v] & 3u; }
               }
               if (prefix && k >= lim1 && lim1 < o1) {
-#ifndef CG_ABL_NO_COOP_ROWS
                 coop = true; k0 = lim1;   // the rest of the row, cooperatively, from here
-#endif
               } else {
                 cur[s] = (uint16_t)k;
                 if (k < o1 && spread_take_c(T, v, s, low)) lost_any = true;
               }
             } else {
-#ifndef CG_ABL_NO_COOP_ROWS
               coop = true; k0 = from;
-#endif
             }
 #ifdef CG_STAMPS
             if (sweep == 0) { dg_full += full ? 1 : 0; dg_coop += coop ? 1 : 0; } else dg_resc += 1;
@@ -457,10 +447,7 @@ __device__ __forceinline__ void attacker_spread(Env& e, const KP& P, const int32
     // log entries of every source: unblocked out-entries up to and including its pick
     // ... and, in the same pass, the domain-controller attribution (:1163-1185): a DC source marks its pick
     int total_new = 0;
-#ifndef CG_COUNTS_STAGED
-#define CG_COUNTS_STAGED 1
-#endif
-    if constexpr (CG_COUNTS_STAGED && CR > 1) {
+    if constexpr (CR > 1) {
       // four blocks of sources per step, each stage's loads in flight together (source id -> row bounds + pick + static byte ->
       // the blocked-word pair of the prefix): three round trips per FOUR blocks where the loop below pays five per block; a prefix
       // of more than 33 slots (a hub without a target) takes the rolled count, only when some lane of the step has one.  One
@@ -834,9 +821,6 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
 #pragma unroll
     for (int b = 0; b < MCT; ++b) {
       cnt[b] = 0;
-#ifdef CG_ABL_NO_CNT
-      continue;
-#endif
       if (b * WAVE >= n_src) continue;   // (uniform)
       const int o0 = (int)(row[b] & 0xFFFFu), o1 = (int)(row[b] >> 16), k = (int)(pkv[b] & 0xFFFFu);
       int n = 0;
@@ -859,12 +843,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
     wsync();
     SUBSTAMP(12);
     // ring: only the last CG_LOG_RING entries (global order: source id, then row order) matter
-#ifdef CG_ABL_NO_RING
-    e.log_total += total_new;   // (timing ablation: the counts stay alive, the ring is not written)
-    if (false) {
-#else
     if (total_new > 0) {
-#endif
       const uint32_t base = (uint32_t)e.log_total;
       const uint32_t end = base + (uint32_t)total_new;
       const uint32_t lo = end > CG_LOG_RING ? end - CG_LOG_RING : 0;
@@ -884,11 +863,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
         // (cooperative only for sources with many entries or a pick far into the row: a hub whose pick is among its first neighbours --
         // the usual case -- goes with the short rows, one step per ENTRY on the bits of its blocked-word pair)
         const bool is_long = mine && (last - o0 >= 33 || n > LONG_ROW);
-#ifdef CG_ABL_RING_NOLANE
-        if (false) {
-#else
         if (mine && !is_long) {
-#endif
           // a short row's entries = the clear bits of its blocked-word pair below the pick: one read of the pair, then one step per
           // ENTRY (not per slot, and no blocked-bit read inside the loop)
           const int w0 = o0 >> 5, wl = ((P.t.EW + 3) & ~3) - 1;
@@ -902,11 +877,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
             ++idx;
           }
         }
-#ifdef CG_ABL_RING_NOCOOP
-        uint64_t lm = 0;
-#else
         uint64_t lm = ballot(is_long);
-#endif
         while (lm) {
           const int ll = __builtin_ctzll(lm);
           lm &= lm - 1;

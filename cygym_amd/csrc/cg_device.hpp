@@ -12,16 +12,12 @@
 #include <new>
 #include "cygym_abi.h"
 
-#ifndef CG_FUSED_LB
-#define CG_FUSED_LB 4   // rollout kernels: 4 waves per SIMD (128 VGPRs); see the tick-loop note in cg_tick.hpp
-#endif
-#ifndef CG_LB
+constexpr int CG_FUSED_LB = 4;   // rollout kernels: 4 waves per SIMD (128 VGPRs); see the tick-loop note in cg_tick.hpp
 // Full-feature per-tick kernels: 4 waves per SIMD (128 VGPRs).  At 6 (80 VGPRs) they spilled 5-11 VGPRs on top of
 // ~150 SGPRs kept in VGPR lanes, and with the parameter block read through the laundered kernarg pointer that
 // combination miscompiled: a spilled SGPR pair (an f64 env accumulator) came back clobbered after the divergent
 // block / unblock code at run-time sizes (caught by every full-feature fixture test).  No VGPR spills, no problem.
-#define CG_LB 4
-#endif
+constexpr int CG_LB = 4;
 #define CG_E_STAR_OK 0x80  // kernel-private: star edges verified for the current owned set
 
 namespace cygym_k {

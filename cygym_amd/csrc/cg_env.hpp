@@ -100,9 +100,7 @@ __device__ __forceinline__ int range_popc(const uint32_t* blk, int a, int b) {
 // wait out the longest row, one word per trip.  Every kernel of a compile-time size uses these forms (pool_pick<NW>); rows longer
 // than W words cannot occur there: cygym_create sends such a topology to the run-time-size kernels (DevTopo::ct), so there is no
 // fallback loop.
-#ifndef CG_WIDE_W
-#define CG_WIDE_W 9
-#endif
+constexpr int CG_WIDE_W = 9;
 // W words read at once: 9 covers any row of <= 256 slots (256 devices), 3 any row of <= 64 slots (64 devices).
 // Nine (W) clamped reads, W popcount-accumulates, then arithmetic instead of per-word masks and selects: the last word was read
 // (W - words) times and counts once; the first word's bits below a and the last word's bits from b on are taken off.  (Half the

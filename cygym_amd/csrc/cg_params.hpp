@@ -79,11 +79,6 @@ inline void fill_hot(KParams& P) {   // host side, once the rest of P is complet
   h.env_begin = P.env_begin; h.env_end = P.env_end; h.wave_lds = P.wave_lds; h.shared_lds = P.shared_lds;
 }
 
-// how a kernel sees its parameters: as the by-value kernel argument (per-tick kernel), or through a constant-
-// address-space pointer to the kernarg segment itself, re-read at the top of every tick (rollout kernel)
-template <bool FUSED> struct KParamsOf { using type = const KParams; };
-template <> struct KParamsOf<true> { using type = const __attribute__((address_space(4))) KParams; };
-
 #define CG_DBG_W 28   // uint64 slots per env in the stamp buffer of diagnostic builds
 #ifdef CG_STAMPS
 #define SUBSTAMP(k) do { if (P.dbg && e.lane == 0) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); P.dbg[(size_t)e.env * CG_DBG_W + (k)] = _t; } } while (0)

@@ -19,28 +19,11 @@ __device__ __forceinline__ float2 ld_ano2(const float2* p, bool vol) {
   return make_float2(q[0], q[1]);
 }
 __device__ __forceinline__ float ld_ano(const float* p, bool vol) { return vol ? *(const volatile float*)p : *p; }
-// How the observation leaves the chip.  0: plain stores (lines stay dirty in the XCD's L2 and are written back when the
-// launch ends: ~1.5 us of a one-tick launch's 3.2 us gap to the next launch, tools/exp_gap.py); 1: non-temporal; 2: sc1
-// (written through as the kernel runs).
-#ifndef CG_OBS_STORE
-#define CG_OBS_STORE 0
-#endif
+// How the observation leaves the chip: plain stores (lines stay dirty in the XCD's L2 and are written back when the launch
+// ends: ~1.5 us of a one-tick launch's 3.2 us gap to the next launch, tools/exp_gap.py), or written through as whole lines
+// by write_obs_staged below.
 typedef float cg_f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void obs_store4(float4* p, float4 v) {
-  [[maybe_unused]] const cg_f4v vv = {v.x, v.y, v.z, v.w};
-  [[maybe_unused]] const uint64_t pa = (uint64_t)p;
-#if CG_OBS_STORE == 1
-  __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y); __builtin_nontemporal_store(v.z, &p->z); __builtin_nontemporal_store(v.w, &p->w);
-#elif CG_OBS_STORE == 2
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(pa), "v"(vv) : "memory");
-#elif CG_OBS_STORE == 3
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(pa), "v"(vv) : "memory");
-#elif CG_OBS_STORE == 4
-  asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(pa), "v"(vv) : "memory");
-#else
-  *p = v;
-#endif
-}
+__device__ __forceinline__ void obs_store4(float4* p, float4 v) { *p = v; }
 template <int GP>   // pairs per lane and step
 __device__ __forceinline__ void write_obs(const uint8_t* flags, const float* osv, const float* ver, const float* ano,
                                           float* obs, int M, int lane, bool vol = false) {
@@ -180,11 +163,11 @@ __device__ __forceinline__ void write_obs_att(const uint8_t* flags, const float*
 }
 
 #define CG_OBS_STAGE_BYTES 3072   // 64 pairs x 48 bytes
-struct WaveAux { uint64_t* srcb; int32_t* park; };
-// MAPS: the in-CSR columns and slot maps are staged in LDS too (the WIDE per-tick kernel, one 16-wave workgroup per CU)
+// MAPS: the in-CSR columns and slot maps are staged in LDS too (the WIDE per-tick kernel, one 16-wave workgroup per CU).
+// Returns the spread's per-chunk source masks (srcb: [MC] words of this wave's block).
 template <bool MAPS, bool RT, class KP>   // RT: run-time size (comp_by may stay in global memory: one plane less in LDS)
-__device__ __forceinline__ WaveAux env_setup(Env& e, uint8_t* smem, const KP& P, int M, int MC, int Mp, int MS,
-                                             int wave, int lane, int env) {
+__device__ __forceinline__ uint64_t* env_setup(Env& e, uint8_t* smem, const KP& P, int M, int MC, int Mp, int MS,
+                                               int wave, int lane, int env) {
   uint8_t* wb = smem + P.shared_lds + (size_t)wave * P.wave_lds;
   e.flags = wb; e.busy = wb + MS; e.wl = wb + 2 * MS; e.cby = wb + 3 * MS;
   const int n_planes = (RT && P.t.cby_global) ? 3 : 4;   // (comp_by left in global memory: Env::cby_g)
@@ -195,11 +178,11 @@ __device__ __forceinline__ WaveAux env_setup(Env& e, uint8_t* smem, const KP& P,
   e.bin = e.blk + ((P.t.EW + 3) & ~3);
   e.ring = (uint16_t*)(e.bin + ((P.t.EW + 3) & ~3));
   e.marks = (uint32_t*)(e.ring + 2 * CG_LOG_RING);
-  WaveAux x;
-  x.srcb = (uint64_t*)(e.marks + ((Mp / 32 + 2) & ~1));
-  e.lsrc = (uint16_t*)(x.srcb + MC);
+  uint64_t* const srcb = (uint64_t*)(e.marks + ((Mp / 32 + 2) & ~1));
+  e.lsrc = (uint16_t*)(srcb + MC);
   e.devl = (int16_t*)(e.lsrc + Mp);
-  x.park = (int32_t*)(wb + P.wave_lds - 128);   // [16 i32 + 3 f64] per-env scalars between fused ticks
+  // (the last 128 bytes of the block are reserved and unused: they once parked the rollout kernel's scalars between ticks, and
+  // are kept so that every launch plan stays as it was -- wave_lds_bytes on the host)
   e.xk = (uint32_t*)(wb + P.wave_lds - 128 - P.t.x_bytes);
   // (below the extra-edge section; the host adds the bytes: 3 KB for the WIDE kernel, 1.5 KB -- all 32 pairs -- at 64 devices)
   e.obs_stage = (float4*)(wb + P.wave_lds - 128 - P.t.x_bytes - (M == 64 ? CG_OBS_STAGE_BYTES / 2 : CG_OBS_STAGE_BYTES));
@@ -209,10 +192,7 @@ __device__ __forceinline__ WaveAux env_setup(Env& e, uint8_t* smem, const KP& P,
   if (lists_global) { e.xmo = (uint64_t*)e.xk; e.xk = nullptr; e.xb = nullptr; e.devl = nullptr; }   // (the tick body points them at the env's global rows)
   e.xmi = e.xmo + MC;
   e.K = P.t.K;
-#ifndef CG_AFFINE_BLOB
-#define CG_AFFINE_BLOB 1
-#endif
-  if constexpr (CG_AFFINE_BLOB && !RT) {
+  if constexpr (!RT) {
     // Compile-time device count: the blob's twelve section offsets (cygym_create: every section padded to 16 bytes) are all
     // "o_dst + constant" or "+ k * padded column bytes" -- two run-time scalars instead of twelve kept (spilled, restored) for the
     // whole kernel, and the constants fold into the instructions' offset fields.
@@ -244,30 +224,24 @@ __device__ __forceinline__ WaveAux env_setup(Env& e, uint8_t* smem, const KP& P,
   e.multi = P.t.multi != 0;
   e.stash = P.b.stash + (size_t)env * 4 * M;
   e.cby_g = (RT && P.t.cby_global) ? P.b.live + (size_t)env * 4 * M + 3 * (size_t)M : nullptr;
-  return x;
+  return srcb;
 }
 
-// FUSED: cygym_rollout (n_ticks > 1).  The per-env scalars are parked in LDS between ticks so that they are
-// not loop-carried registers; the single-tick instantiation has a compile-time trip count of 1.
+constexpr int CG_WGP0 = 4;      // run-time sizes: words / observation pairs per lane and staged step
+constexpr int CG_OBS_GP0 = 4;
+constexpr int CG_WIDE_CR = 1;   // rows per cooperative step of the generic spread (attacker_spread's CR): the WIDE kernel ...
+constexpr int CG_RT_CR = 4;     // ... and the run-time-size kernels in workgroups of up to 8 waves
+constexpr int CG_LEAN_LB = 6;   // waves per SIMD of the lean per-tick kernel at a compile-time size (below; choose_launch_with plans by it)
+
+// FUSED: cygym_rollout (n_ticks > 1): the tick loop runs inside the launch; the single-tick instantiation has a
+// compile-time trip count of 1.
 template <int WPB, int MT, bool FUSED, bool XE, bool WIDE>
-#ifndef CG_WGP0
-#define CG_WGP0 4   // run-time sizes: words / observation pairs per lane and staged step
-#endif
-#ifndef CG_OBS_GP0
-#define CG_OBS_GP0 4
-#endif
-#ifndef CG_LEAN_LB
-#define CG_LEAN_LB 6
-#endif
-#ifndef CG_WIDE_CR
-#define CG_WIDE_CR 1
-#endif
 // (a one-wave workgroup at a run-time size is only chosen when LDS, not registers, limits residency: 3 there.)
 // Register budget (second launch-bound = minimum waves per SIMD): the fused kernel and the WIDE per-tick kernel must keep 4 waves per SIMD (16 per CU: with one wave
 // per env and <= 16 envs per CU that is the whole batch in ONE residency round -- at 3 per SIMD a quarter of the
 // batch would wait for a second round).  The lean per-tick kernel at a compile-time size is capped for 6 waves per SIMD
 // (80 VGPRs, no spills): batches that oversubscribe the chip (16384 envs) step 9 % faster than at 5.
-__global__ __launch_bounds__(WPB * WAVE, FUSED ? CG_FUSED_LB : (XE ? (WPB == 1 && MT == 0 ? 3 : CG_LB) : (WIDE ? 4 : (MT && MT <= 256 ? (WPB > 1 && WPB <= 8 ? CG_LEAN_LB : CG_LEAN_LB - 1) : 1)))) void step_kernel(const KParams P0) {
+__global__ __launch_bounds__(WPB * WAVE, FUSED ? CG_FUSED_LB : (XE ? (WPB == 1 && MT == 0 ? 3 : CG_LB) : (WIDE ? 4 : (MT && MT <= 256 ? (WPB > 1 && WPB <= 8 ? CG_LEAN_LB : CG_LEAN_LB - 1) : 1)))) void step_kernel([[maybe_unused]] const KParams P0) {   // (read through the kernarg pointer, cg_tick_body.inc)
 #include "cg_tick_body.inc"
 }
 

@@ -7,41 +7,27 @@
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry) :: "memory");
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_entry) :: "memory");   // 100 MHz, one counter for the whole chip: launch spans across XCDs
 #endif
-  // every use below goes through `P`: the by-value argument for the single-tick kernel; for the fused one a
-  // pointer to the kernarg segment itself (the struct is the only argument, so it sits at offset 0), so that it
-  // can be re-read, opaquely, at the top of every tick.  That pointer is in the CONSTANT address space: LLVM then
-  // knows that the pointers it loads from there are global ones (not LDS / scratch) and emits global_* instead
-  // of flat_* memory instructions (a flat access also ticks the LDS counter, so every LDS wait would queue
-  // behind it).  No device copy of the parameters, hence no upload before the launch and nothing shared
-  // between launches of one handle.
-#ifndef CG_KARG_PTR
-#define CG_KARG_PTR 1
-#endif
-  using KPT = typename KParamsOf<FUSED || CG_KARG_PTR>::type;
+  // every use below goes through `P`: a pointer to the kernarg segment itself (the struct is the first argument, so it sits
+  // at offset 0), which the rollout kernel re-reads, opaquely, at the top of every tick.  That pointer is in the CONSTANT
+  // address space: LLVM then knows that the pointers it loads from there are global ones (not LDS / scratch) and emits
+  // global_* instead of flat_* memory instructions (a flat access also ticks the LDS counter, so every LDS wait would queue
+  // behind it).  No device copy of the parameters, hence no upload before the launch and nothing shared between launches
+  // of one handle.
+  using KPT = const __attribute__((address_space(4))) KParams;
   KPT* pk;
-  if constexpr (FUSED || CG_KARG_PTR) {
+  {
     // laundered: loads through it are not known dereferenceable at kernel entry, so the compiler leaves each one
     // next to its use instead of hoisting ~150 scalars to the top and spilling them into VGPR lanes
     const uint64_t pv = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
     uint32_t plo = (uint32_t)pv, phi = (uint32_t)(pv >> 32);
     asm volatile("" : "+s"(plo), "+s"(phi));
     pk = (KPT*)(((uint64_t)phi << 32) | plo);
-  } else pk = &P0;
+  }
 #define P (*pk)
   // the prologue's own fields: one batch of scalar loads at kernel entry (KHot, cg_params.hpp)
   using KHT = const __attribute__((address_space(4))) KHot;
   KHT* const hk = (KHT*)__builtin_amdgcn_kernarg_segment_ptr();
-#ifndef CG_KARG_HOT
-#define CG_KARG_HOT 1
-#endif
-#if CG_KARG_HOT
 #define H (*hk)
-#else
-#define H (P.h)
-#endif
-#ifndef CG_KARG_PREFETCH
-#define CG_KARG_PREFETCH 1
-#endif
   // ... and every OTHER 64-byte line of the argument is requested right here as well (one dword each, results unused): the
   // tick body reads its ~150 scalars through the laundered pointer next to their uses, and the first touch of each of
   // the block's ~20 lines was a cold miss of the scalar cache in the middle of some phase (observation pointers, config
@@ -49,21 +35,17 @@
   // hot batch; their destination registers stay allocated until the prologue's loads have been waited for (scalar loads
   // return out of order, so every wait on them is a wait for all of them).
   // (compile-time sizes only: at run-time sizes the fifteen registers held through the prologue cost more than the misses -- 4096 x 2048: +5 % without)
-  constexpr int KARG_LINES = (CG_KARG_PREFETCH && MT != 0) ? (int)((sizeof(KParams) + 63) / 64) : 0;
+  constexpr int KARG_LINES = MT != 0 ? (int)((sizeof(KParams) + 63) / 64) : 0;
   uint32_t kpf[KARG_LINES > 0 ? KARG_LINES : 1];
   if constexpr (KARG_LINES > 0) {
     const uint64_t kb = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
     // (lines 0..3 are the hot block itself; lines that hold only what a common tick never reads -- the topology's host-side
     // views, the tails of the Poisson / triangular tables, the turbo knobs, the snapshot's other planes -- are left out:
     // fewer requests in front of the first wait)
-#ifndef CG_KARG_SPARSE
-#define CG_KARG_SPARSE 1
-#endif
     auto karg_line_needed = [](int i) constexpr {
       const size_t lo = 64 * (size_t)i, hi = lo + 64;
       auto hit = [&](size_t a, size_t b) constexpr { return lo < b && a < hi; };
-      return !CG_KARG_SPARSE
-          || hit(offsetof(KParams, t), offsetof(KParams, t) + offsetof(DevTopo, dstatic))
+      return hit(offsetof(KParams, t), offsetof(KParams, t) + offsetof(DevTopo, dstatic))
           || hit(offsetof(KParams, c), offsetof(KParams, c) + offsetof(cygym_config, poisson_thr) + 8)
           || hit(offsetof(KParams, b), offsetof(KParams, snap) + 8)
           || hit(offsetof(KParams, a), sizeof(KParams));
@@ -75,55 +57,32 @@
   }
   const int M = MT ? MT : H.t.M, MC = MT ? (MT + WAVE - 1) / WAVE : H.t.MC, Mp = MC * WAVE, MS = (M + 3) & ~3;
   // (the wave id as a scalar: the per-wave LDS pointers derived from it then live in SGPRs -- 5 VGPRs less in the WIDE kernel, 14 in the rollout kernels)
-#ifndef CG_UNI_WAVE
-#define CG_UNI_WAVE 1
-#endif
-  int wave = CG_UNI_WAVE ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;   // (run-time-size rollout kernel: laundered per tick, below)
+  int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;   // (run-time-size rollout kernel: laundered per tick, below)
   const int env = uni(H.env_begin + blockIdx.x * WPB + wave);
   const bool live = env < H.env_end;
   const int G = H.a.max_groups, L = H.a.max_devs;
 
   Env e;
-  WaveAux aux = env_setup<WIDE, MT == 0>(e, smem, H, M, MC, Mp, MS, wave, lane, live ? env : 0);
-  uint64_t* srcb = aux.srcb;
-  int32_t* park = aux.park;
+  uint64_t* srcb = env_setup<WIDE, MT == 0>(e, smem, H, M, MC, Mp, MS, wave, lane, live ? env : 0);
   e.env = env;
   e.blk_dirty = e.ring_dirty = e.x_dirty = false;
 
-#ifndef CG_PIN_PTRS
-#define CG_PIN_PTRS 0
-#endif
-  if constexpr (CG_PIN_PTRS && MT != 0 && !FUSED) {
-    // every pointer the prologue's loads start from, materialised HERE: left alone the compiler sinks each pointer's scalar load
-    // into the exec-masked region that uses it, with its own s_waitcnt (~15 scalar-cache round trips in a row)
-    asm volatile("" :: "s"(H.b.live), "s"(H.b.blocked), "s"(H.b.blocked_in), "s"(H.b.ring), "s"(H.b.ienv), "s"(H.b.fenv), "s"(H.t.blob),
-                 "s"(H.a.mode), "s"(H.a.n_groups), "s"(H.a.atype), "s"(H.a.n_exploit), "s"(H.a.exploit), "s"(H.a.app), "s"(H.a.dev_cnt), "s"(H.a.dev_idx));
-  }
   STAMP(0);
   // ---- issue every global load of this tick up front (one memory latency, not a chain) ----
   const size_t so = (size_t)(live ? env : 0) * 4 * M;
   const uint8_t* g_live = H.b.live + so;
-#ifndef CG_HDR_GATHER
-#define CG_HDR_GATHER 1
-#endif
-#ifndef CG_LANE_SCALARS
-#define CG_LANE_SCALARS 1
-#endif
-  // (CG_LANE_SCALARS: the 16 + 3 env scalars stay in the lanes of `hv`, the register the gathered load filled, for the whole kernel:
-  // EnvI / EnvF, cg_wave.hpp)
-  constexpr bool LS = CG_LANE_SCALARS && CG_HDR_GATHER;
+  // the 16 + 3 env scalars stay in the lanes of `hv`, the register the gathered load below fills, for the whole kernel
+  // (EnvI / EnvF, cg_wave.hpp)
   uint32_t hv = 0;
-  int32_t ie_a[LS ? 1 : CG_I_COUNT];
-  double fe_a[LS ? 1 : CG_D_COUNT];
-  auto ie = scalars_i<LS>(hv, ie_a);
-  auto fe = scalars_f<LS>(hv, fe_a);
+  EnvI ie{hv};
+  EnvF fe{hv};
   int mode = 0, ng = 0, at0 = 8, cnt0 = 0, nexp0 = 0, app0 = -1;
   int ex0 = -1;   // first exploit id of an attacker spread: fetched as soon as the header says so (its latency hides
                   // behind the staging), not inside the spread where the heaviest envs would wait a full round trip
-  // Prefetch depths (items per lane held in registers between the load and the LDS store): at a compile-time size
-  // the whole state is one item per lane; at run-time sizes (up to 2048 devices: 8 items of the live block, 5
-  // blocked words, 8 KB of topology per wave) deep enough that the prologue stays ONE memory round trip instead of
-  // a load -> wait -> store chain per item.
+  // Prefetch depths (items per lane): at a compile-time size the whole state is one item per lane, copied by LDS-DMA (below);
+  // at run-time sizes the items are held in registers between the load and the LDS store (up to 2048 devices: 8 items of
+  // the live block, 5 blocked words), deep enough that the prologue stays ONE memory round trip instead of a load -> wait
+  // -> store chain per item.
   constexpr int PF_LIVE = MT ? (MT / 4 + WAVE - 1) / WAVE : 8;
   uint4 rl[PF_LIVE];
 #pragma unroll
@@ -146,54 +105,25 @@
   // otherwise SUNK into that block, next to its s_waitcnt, and the staging runs as a chain of 8-16 dependent
   // round trips.  (At the compile-time sizes, with 4+ waves per SIMD, the pinned form measured +-2 % and costs
   // registers: not applied there.)
-#ifndef CG_SCALAR_HDR
-#define CG_SCALAR_HDR 0
-#endif
-  // (CG_SCALAR_HDR: the env's 16 + 3 scalars and its action header are read through the scalar cache -- `s_load` into SGPRs, one
-  // x16, one x4 + x2 and seven single dwords -- instead of ~30 same-address vector loads followed by as many v_readfirstlane.
-  // They were written by the PREVIOUS launch (the write-back of this very wave's env, the host or the actor kernel), the
-  // scalar cache is invalidated at every dispatch, and nothing reads them again after this wave's own write-back.
-  // Measured at 4096 x 256 (profiles/r04_spread_block_experiments.txt, r0/r1): staging -650 cycles per env, but the 26 values are
-  // then live in SGPRs across the prologue, 190 -> 302 spilled SGPRs, every later phase +10-30 %: launch +0.3 us.  Off.)
-#if CG_SCALAR_HDR
-#define CG_KS(T, p) ((const __attribute__((address_space(4))) T*)(p))
-#else
-#define CG_KS(T, p) ((const T*)(p))
-#endif
+  // (the env's scalars and action header through the scalar cache: measured slower, profiles/r04_spread_block_experiments.txt)
 #define KEEP4(r) asm volatile("" :: "v"((r).x), "v"((r).y), "v"((r).z), "v"((r).w))
-  constexpr int PF_BLOB = MT ? 4 : (WPB >= 16 ? 2 : WPB >= 8 ? 4 : 8);   // 16-byte items per lane: 32 KB per workgroup in the pinned round
   const uint4* blob_src = (const uint4*)H.t.blob;
   const int n16 = H.t.lds_bytes >> 4;
   constexpr int stride = WPB * WAVE;
-#ifndef CG_BLOB_DMA
-#define CG_BLOB_DMA 1
-#endif
-  // (CG_BLOB_DMA: the blob goes global -> LDS directly, `global_load_lds_dwordx4`: 1 KB per wave-instruction lands at a wave-uniform
-  // LDS base + 16 * lane -- no register staging, no ds_write pass; the compiler waits for them in front of the staging barrier)
-#ifndef CG_BLOB_DMA_RT
-#define CG_BLOB_DMA_RT 1
-#endif
-  constexpr bool BLOB_DMA = CG_BLOB_DMA && (MT != 0 || CG_BLOB_DMA_RT);
-#ifndef CG_STATE_DMA
-#define CG_STATE_DMA 1
-#endif
-  // (CG_STATE_DMA: the same for the env's own state: the [4][M] byte planes as 16-byte items, the blocked-edge words and the
-  // log ring as dwords -- each a wave-instruction into this wave's LDS block)
-  constexpr bool STATE_DMA = CG_STATE_DMA && MT != 0;
+  // The blob goes global -> LDS directly, `global_load_lds_dwordx4`: 1 KB per wave-instruction lands at a wave-uniform LDS
+  // base + 16 * lane -- no register staging, no ds_write pass; the compiler waits for them in front of the staging barrier.
+  // At the compile-time sizes the same goes for the env's own state: the [4][M] byte planes as 16-byte items, the
+  // blocked-edge words and the log ring as dwords -- each a wave-instruction into this wave's LDS block.
+  constexpr bool STATE_DMA = MT != 0;
 #define CG_DMA(src, dst, bytes) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), \
                                                                  (__attribute__((address_space(3))) void*)(dst), bytes, 0, 0)
-  uint4 br[BLOB_DMA ? 1 : PF_BLOB];
-  if constexpr (!BLOB_DMA) {
-#pragma unroll
-    for (int j = 0; j < PF_BLOB; ++j) { const int i = threadIdx.x + j * stride; br[j] = blob_src[i < n16 ? i : n16 - 1]; }
-  }
-  // (CG_HDR_GATHER: the env's 16 + 3 scalars and the seven words of its action header come back from ONE vector load -- lane l
-  // reads word l of {ienv[16], fenv[3] as 6 words, mode, n_groups, atype, dev_cnt, n_exploit, app, exploit[0]} -- and are moved to
-  // SGPRs with v_readlane behind the barrier.  As 26 same-address loads per wave they cost the CU's one texture-address unit
-  // 4 cycles each, 16 waves at once: 1.7 k of the 3.2 k cycles the prologue spent ISSUING its loads (stage sub-stamps,
-  // profiles/r04_stage_substamps.txt); the first exploit id no longer waits for the header either.)
+  // The env's 16 + 3 scalars and the seven words of its action header come back from ONE vector load -- lane l reads word l
+  // of {ienv[16], fenv[3] as 6 words, mode, n_groups, atype, dev_cnt, n_exploit, app, exploit[0]} -- and the header words are
+  // moved to SGPRs with v_readlane behind the barrier.  As 26 same-address loads per wave they cost the CU's one
+  // texture-address unit 4 cycles each, 16 waves at once: 1.7 k of the 3.2 k cycles the prologue spent ISSUING its loads
+  // (stage sub-stamps, profiles/r04_stage_substamps.txt); the first exploit id no longer waits for the header either.
   static_assert(CG_I_COUNT == 16 && CG_D_COUNT == 3, "header gather layout");
-  if constexpr (CG_HDR_GATHER) {
+  {
     const size_t envc = live ? (size_t)env : 0;
     const uint32_t* pa = (const uint32_t*)(H.b.ienv + envc * CG_I_COUNT) + (lane & 15);
     if (lane >= 16) pa = (const uint32_t*)(H.b.fenv + envc * CG_D_COUNT) + (lane < 22 ? lane - 16 : 0);
@@ -226,68 +156,23 @@
     for (int j = 0; j < PF_BLK; ++j) { int w = lane + j * WAVE; w = w < EW ? w : EW - 1; bw[j] = gb0[w]; bwi[j] = gbi0[w]; }
 #pragma unroll
     for (int j = 0; j < PF_DEV; ++j) { const int q = lane + j * WAVE; dv[j] = H.a.dev_idx[(size_t)envc * L + (q < L ? q : L - 1)]; }
-    if constexpr (!CG_HDR_GATHER) {
-    if constexpr (!FUSED) {   // (the rollout kernel loads each tick's header at the top of its tick loop)
-      mode = CG_KS(int32_t, H.a.mode)[envc];
-      ng = CG_KS(int32_t, H.a.n_groups)[envc];
-      at0 = CG_KS(int32_t, H.a.atype)[(size_t)envc * G];
-      cnt0 = CG_KS(int32_t, H.a.dev_cnt)[(size_t)envc * G];
-      nexp0 = CG_KS(int32_t, H.a.n_exploit)[(size_t)envc * G];
-      app0 = CG_KS(int32_t, H.a.app)[(size_t)envc * G];
-      ex0 = CG_KS(int32_t, H.a.exploit)[(size_t)envc * G * CG_MAX_EXPLOITS];
-    }
-    const auto* g = CG_KS(int32_t, H.b.ienv) + (size_t)envc * CG_I_COUNT;
-#pragma unroll
-    for (int i = 0; i < CG_I_COUNT; ++i) ie[i] = g[i];
-    const auto* gf = CG_KS(double, H.b.fenv) + (size_t)envc * CG_D_COUNT;
-#pragma unroll
-    for (int i = 0; i < CG_D_COUNT; ++i) fe[i] = gf[i];
-    } else asm volatile("" :: "v"(hv));
+    asm volatile("" :: "v"(hv));
 #pragma unroll
     for (int j = 0; j < PF_LIVE; ++j) KEEP4(rl[j]);
 #pragma unroll
     for (int j = 0; j < PF_BLK; ++j) asm volatile("" :: "v"(bw[j]), "v"(bwi[j]));
     asm volatile("" :: "v"(ringw), "v"((int)dv[0]));
-  } else if (live) {
-    if constexpr (!CG_HDR_GATHER) {
-    const auto* g = CG_KS(int32_t, H.b.ienv) + (size_t)env * CG_I_COUNT;
+  } else if (live) {   // (STATE_DMA)
 #pragma unroll
-    for (int i = 0; i < CG_I_COUNT; ++i) ie[i] = g[i];
-    const auto* gf = CG_KS(double, H.b.fenv) + (size_t)env * CG_D_COUNT;
-#pragma unroll
-    for (int i = 0; i < CG_D_COUNT; ++i) fe[i] = gf[i];
-    mode = CG_KS(int32_t, H.a.mode)[env];
-    ng = CG_KS(int32_t, H.a.n_groups)[env];
-    at0 = CG_KS(int32_t, H.a.atype)[(size_t)env * G];
-    cnt0 = CG_KS(int32_t, H.a.dev_cnt)[(size_t)env * G];
-    nexp0 = CG_KS(int32_t, H.a.n_exploit)[(size_t)env * G];
-    app0 = CG_KS(int32_t, H.a.app)[(size_t)env * G];
-    if (CG_SCALAR_HDR || ((mode & 0xFF) == CG_MODE_ATTACKER && at0 == 1 && ng == 0)) ex0 = CG_KS(int32_t, H.a.exploit)[(size_t)env * G * CG_MAX_EXPLOITS];
-    }
-    if constexpr (STATE_DMA) {
-#pragma unroll
-      for (int j = 0; j < PF_LIVE; ++j) { const int i = lane + j * WAVE; if (i < items) CG_DMA((const uint4*)g_live + i, (uint4*)e.flags + j * WAVE, 16); }
-      if (lane < CG_LOG_RING) CG_DMA((const uint32_t*)(H.b.ring + (size_t)env * CG_LOG_RING * 2) + lane, e.ring, 4);
-#pragma unroll
-      for (int j = 0; j < PF_BLK; ++j) {
-        const int w = lane + j * WAVE;
-        if (w < H.t.EW) {
-          CG_DMA(H.b.blocked + (size_t)env * H.t.EW + w, e.blk + j * WAVE, 4);
-          CG_DMA(H.b.blocked_in + (size_t)env * H.t.EW + w, e.bin + j * WAVE, 4);
-        }
-      }
-    } else {
-    if (vec) {
-#pragma unroll
-      for (int j = 0; j < PF_LIVE; ++j) { const int i = lane + j * WAVE; rl[j] = ((const uint4*)g_live)[i < items ? i : 0]; }
-    }
-    if (lane < CG_LOG_RING) ringw = ((const uint32_t*)(H.b.ring + (size_t)env * CG_LOG_RING * 2))[lane];
+    for (int j = 0; j < PF_LIVE; ++j) { const int i = lane + j * WAVE; if (i < items) CG_DMA((const uint4*)g_live + i, (uint4*)e.flags + j * WAVE, 16); }
+    if (lane < CG_LOG_RING) CG_DMA((const uint32_t*)(H.b.ring + (size_t)env * CG_LOG_RING * 2) + lane, e.ring, 4);
 #pragma unroll
     for (int j = 0; j < PF_BLK; ++j) {
-      int w = lane + j * WAVE;
-      bw[j] = w < H.t.EW ? H.b.blocked[(size_t)env * H.t.EW + w] : 0u;
-      bwi[j] = w < H.t.EW ? H.b.blocked_in[(size_t)env * H.t.EW + w] : 0u;
-    }
+      const int w = lane + j * WAVE;
+      if (w < H.t.EW) {
+        CG_DMA(H.b.blocked + (size_t)env * H.t.EW + w, e.blk + j * WAVE, 4);
+        CG_DMA(H.b.blocked_in + (size_t)env * H.t.EW + w, e.bin + j * WAVE, 4);
+      }
     }
 #pragma unroll
     for (int j = 0; j < PF_DEV; ++j) { int q = lane + j * WAVE; dv[j] = q < L ? H.a.dev_idx[(size_t)env * L + q] : (int16_t)0; }
@@ -298,40 +183,31 @@
 #endif
   // ---- workgroup-shared topology blob -> LDS ----
   {
-    if constexpr (MT == 0 && !BLOB_DMA) {
-#pragma unroll
-      for (int j = 0; j < PF_BLOB; ++j) KEEP4(br[j]);
-    }
     uint4* dstp = (uint4*)smem;
-    if constexpr (BLOB_DMA) {
-      for (int i0 = (threadIdx.x & ~63); i0 < n16; i0 += stride) {   // (i0: wave-uniform first item of this wave's 1 KB piece)
-        const int i = i0 + (threadIdx.x & 63);
-        if (i < n16)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(blob_src + i),
-                                           (__attribute__((address_space(3))) void*)(dstp + __builtin_amdgcn_readfirstlane(i0)), 16, 0, 0);
-      }
-    } else {
-#pragma unroll
-    for (int j = 0; j < PF_BLOB; ++j) { const int i = threadIdx.x + j * stride; if (i < n16) dstp[i] = br[j]; }
-    for (int i = threadIdx.x + PF_BLOB * stride; i < n16; i += stride) dstp[i] = blob_src[i];
+    for (int i0 = (threadIdx.x & ~63); i0 < n16; i0 += stride) {   // (i0: wave-uniform first item of this wave's 1 KB piece)
+      const int i = i0 + (threadIdx.x & 63);
+      if (i < n16)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(blob_src + i),
+                                         (__attribute__((address_space(3))) void*)(dstp + __builtin_amdgcn_readfirstlane(i0)), 16, 0, 0);
     }
   }
 #undef KEEP4
   if (live) {
-    if constexpr (STATE_DMA) {
-    } else if (vec) {
+    if constexpr (!STATE_DMA) {   // the registers the loads above filled -> LDS
+      if (vec) {
 #pragma unroll
-      for (int j = 0; j < PF_LIVE; ++j) { const int i = lane + j * WAVE; if (i < items) ((uint4*)e.flags)[i] = rl[j]; }
-      for (int i = lane + PF_LIVE * WAVE; i < items; i += WAVE) ((uint4*)e.flags)[i] = ((const uint4*)g_live)[i];
-    } else {
-      for (int pl = 0; pl < 4; ++pl)
-        for (int i = lane; i < MS; i += WAVE) e.flags[pl * MS + i] = i < M ? g_live[pl * M + i] : (pl == 0 ? (uint8_t)CG_F_NYA : (uint8_t)0);
+        for (int j = 0; j < PF_LIVE; ++j) { const int i = lane + j * WAVE; if (i < items) ((uint4*)e.flags)[i] = rl[j]; }
+        for (int i = lane + PF_LIVE * WAVE; i < items; i += WAVE) ((uint4*)e.flags)[i] = ((const uint4*)g_live)[i];
+      } else {
+        for (int pl = 0; pl < 4; ++pl)
+          for (int i = lane; i < MS; i += WAVE) e.flags[pl * MS + i] = i < M ? g_live[pl * M + i] : (pl == 0 ? (uint8_t)CG_F_NYA : (uint8_t)0);
+      }
     }
     const uint32_t* gb = H.b.blocked + (size_t)env * H.t.EW;
     if constexpr (!STATE_DMA) {
-    if (lane < CG_LOG_RING) ((uint32_t*)e.ring)[lane] = ringw;
+      if (lane < CG_LOG_RING) ((uint32_t*)e.ring)[lane] = ringw;
 #pragma unroll
-    for (int j = 0; j < PF_BLK; ++j) { int w = lane + j * WAVE; if (w < H.t.EW) { e.blk[w] = bw[j]; e.bin[w] = bwi[j]; } }
+      for (int j = 0; j < PF_BLK; ++j) { int w = lane + j * WAVE; if (w < H.t.EW) { e.blk[w] = bw[j]; e.bin[w] = bwi[j]; } }
     }
     for (int w = lane + PF_BLK * WAVE; w < H.t.EW; w += WAVE) { e.blk[w] = gb[w]; e.bin[w] = H.b.blocked_in[(size_t)env * H.t.EW + w]; }
     const int16_t* gd = H.a.dev_idx + (size_t)env * L;
@@ -355,50 +231,12 @@
 #ifdef CG_STAMPS
   if (P.dbg && lane == 0) { P.dbg[(size_t)env * CG_DBG_W + 24] = st_issued; P.dbg[(size_t)env * CG_DBG_W + 25] = st_back; }
 #endif
-  if constexpr (CG_HDR_GATHER) {
-    if constexpr (!LS) {
-#pragma unroll
-    for (int i = 0; i < CG_I_COUNT; ++i) ie[i] = __builtin_amdgcn_readlane((int)hv, i);
-#pragma unroll
-    for (int i = 0; i < CG_D_COUNT; ++i)
-      fe[i] = __hiloint2double(__builtin_amdgcn_readlane((int)hv, 16 + 2 * i + 1), __builtin_amdgcn_readlane((int)hv, 16 + 2 * i));
-    }
-    if constexpr (!FUSED) {
-      mode = __builtin_amdgcn_readlane((int)hv, 22); ng = __builtin_amdgcn_readlane((int)hv, 23); at0 = __builtin_amdgcn_readlane((int)hv, 24);
-      cnt0 = __builtin_amdgcn_readlane((int)hv, 25); nexp0 = __builtin_amdgcn_readlane((int)hv, 26); app0 = __builtin_amdgcn_readlane((int)hv, 27);
-      ex0 = __builtin_amdgcn_readlane((int)hv, 28);
-    }
+  if constexpr (!FUSED) {
+    mode = __builtin_amdgcn_readlane((int)hv, 22); ng = __builtin_amdgcn_readlane((int)hv, 23); at0 = __builtin_amdgcn_readlane((int)hv, 24);
+    cnt0 = __builtin_amdgcn_readlane((int)hv, 25); nexp0 = __builtin_amdgcn_readlane((int)hv, 26); app0 = __builtin_amdgcn_readlane((int)hv, 27);
+    ex0 = __builtin_amdgcn_readlane((int)hv, 28);
   }
-#ifndef CG_NO_UNIFORM_SCALARS
-  if constexpr (!FUSED && !CG_HDR_GATHER) {
-    // The 16 + 3 per-env scalars were fetched with vector loads (a uniform address into memory the kernel also
-    // writes is not eligible for the scalar cache), i.e. into 22 VGPRs that stay live to the write-back.  Telling
-    // the compiler they are uniform moves them to SGPRs: the VGPRs go back to the per-lane work (the WIDE kernel
-    // spilled 7 of them, an f64 accumulator among them), and a spilled SGPR costs a v_writelane, not scratch traffic.
-#pragma unroll
-    for (int i = 0; i < CG_I_COUNT; ++i) ie[i] = __builtin_amdgcn_readfirstlane(ie[i]);
-#pragma unroll
-    for (int i = 0; i < CG_D_COUNT; ++i)
-      fe[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(fe[i])), __builtin_amdgcn_readfirstlane(__double2loint(fe[i])));
-    mode = __builtin_amdgcn_readfirstlane(mode); ng = __builtin_amdgcn_readfirstlane(ng); at0 = __builtin_amdgcn_readfirstlane(at0);
-    cnt0 = __builtin_amdgcn_readfirstlane(cnt0); nexp0 = __builtin_amdgcn_readfirstlane(nexp0); app0 = __builtin_amdgcn_readfirstlane(app0);
-    ex0 = __builtin_amdgcn_readfirstlane(ex0);   // (the tick's action header: uniform as well)
-  }
-#endif
 
-#ifndef CG_OBS_STAGED
-#define CG_OBS_STAGED 1
-#endif
-#ifndef CG_EARLY_PRIO
-#define CG_EARLY_PRIO 0
-#endif
-  if constexpr (CG_EARLY_PRIO && !FUSED) {
-    // The envs that bound a launch (attacker spread; block / unblock lists) are known as soon as the action header is
-    // back: they win issue arbitration from here on, not only inside their long phase -- while every env of the batch
-    // is still alive the SIMD's issue slots are what an env waits for (four waves per SIMD, all in their early phases).
-    const int m0 = mode & 0xFF;
-    if (ng == 0 && ((m0 == CG_MODE_ATTACKER && at0 == 1) || (m0 == CG_MODE_DEFENDER && (at0 == 6 || at0 == 9)))) __builtin_amdgcn_s_setprio(CG_EARLY_PRIO);
-  }
   const int NW = MS >> 2;
   // word loops run in groups of WGP words per lane, loads first (see the chunk loops of the spread): one LDS round trip
   // per group instead of one per word; a single word per lane at the compile-time sizes
@@ -408,22 +246,13 @@
   // ---- ticks of this launch: 1 for cygym_step, T for cygym_rollout (state stays in LDS / registers;
   // no cross-env synchronisation between ticks) ----
   const int n_ticks = FUSED ? P.n_ticks : 1;
-  // Rollout kernel: EVERY tick, the first one included, starts from the same point -- scalars parked in LDS, the
+  // Rollout kernel: EVERY tick, the first one included, starts from the same point -- the env's scalars in `hv`, the
   // env view re-derived through a laundered parameter pointer, the tick's header and device list loaded here.
   // With tick 0 special-cased (its header prefetched with the state) every per-env value reached the loop as a
   // phi of "prologue version" and "re-derived version" and stayed live across the whole body: the full-feature
   // rollout kernels spilled 10-47 VGPRs at the 128 cap; now none does.  (Laundering the lane / wave ids per tick as
   // well stops the hoisting of per-lane addresses and fits 96 VGPRs = 5 waves per SIMD, but the recomputation costs
   // 3-4 % per tick: +6 % at 16384 envs, -3 % at 4096 and 65536 -- measured, not adopted.)
-  if constexpr (FUSED && !LS) {
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < CG_I_COUNT; ++i) park[i] = ie[i];
-#pragma unroll
-      for (int i = 0; i < CG_D_COUNT; ++i) ((double*)(park + CG_I_COUNT))[i] = fe[i];
-    }
-    wsync();
-  }
   // (the scalars of a tick's last phases and of the write-back, filled in one batch at the top of those phases: see STAMP(5))
   struct { int32_t episode_limit, evolve_period, auto_reset; double *raw, *shaped; uint8_t* done; double* ret; uint8_t* alive;
            const uint8_t* snap_live; float *obs_def, *obs_att; uint8_t* b_live; uint32_t* status; int32_t* b_ienv; double* b_fenv; } EP;
@@ -444,18 +273,7 @@
       asm volatile("" : "+s"(plo), "+s"(phi));   // opaque: nothing derived from it is hoisted out of the tick loop
       pk = (KPT*)(((uint64_t)phi << 32) | plo);
     }
-    aux = env_setup<WIDE, MT == 0>(e, smem, P, M, MC, Mp, MS, wave, lane, env);
-    srcb = aux.srcb; park = aux.park;
-    // parked in LDS: an LDS load lands in a VGPR; readfirstlane tells the compiler the value is uniform, so the
-    // 22 per-env scalars live in SGPRs across the tick body instead of 22 of the 128 VGPRs
-    if constexpr (!LS) {   // (lane scalars: they never left `hv`)
-#pragma unroll
-    for (int i = 0; i < CG_I_COUNT; ++i) ie[i] = __builtin_amdgcn_readfirstlane(park[i]);
-#pragma unroll
-    for (int i = 0; i < CG_D_COUNT; ++i)
-      fe[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(park[CG_I_COUNT + 2 * i + 1]),
-                               __builtin_amdgcn_readfirstlane(park[CG_I_COUNT + 2 * i]));
-    }
+    srcb = env_setup<WIDE, MT == 0>(e, smem, P, M, MC, Mp, MS, wave, lane, env);
     mode = P.a.mode[te];
     ng = P.a.n_groups[te];
     at0 = P.a.atype[te * G];
@@ -469,7 +287,7 @@
     wsync();
   }
   if (FUSED && tk > 0) STAMP(1);
-  if (ng < 0) continue;   // n_groups < 0: this env does not tick (per-env stepping inside a batch); its parked scalars stand
+  if (ng < 0) continue;   // n_groups < 0: this env does not tick (per-env stepping inside a batch); its scalars stand
   const int16_t* devs = e.devl;
   uint32_t* const F = (uint32_t*)e.flags;
   uint32_t* const Bz = (uint32_t*)e.busy;
@@ -523,10 +341,7 @@
         if (Ld > 0) def_per_device<XE, WIDE, XE && !FUSED, MT == 256 ? 9 : (MT == 64 ? 3 : 0)>(e, P, at, devs, Ld, app0, cost, dirty, ie, fe);
     } else if (baseline != 3 && (at == 1 || at == 2)) {
       // The spread at a compile-time size without added edges: device-major, its state in registers (attacker_spread_ct).
-#ifndef CG_SPREAD_CT
-#define CG_SPREAD_CT 1
-#endif
-      constexpr bool SPREAD_CT = CG_SPREAD_CT && MT != 0 && !XE;
+      constexpr bool SPREAD_CT = MT != 0 && !XE;
       if (SPREAD_CT && at == 1) {
         if constexpr (SPREAD_CT) {
           int ne = nexp0;
@@ -555,9 +370,6 @@
         int ne = nexp0;
         if (ne > CG_MAX_EXPLOITS) ne = CG_MAX_EXPLOITS;
         __builtin_amdgcn_s_setprio(3);   // the spread bounds the launch: win issue arbitration over short envs
-#ifndef CG_RT_CR
-#define CG_RT_CR 4
-#endif
         attacker_spread<XE, (MT == 0 && WPB <= 8) ? CG_RT_CR : (WIDE ? CG_WIDE_CR : 1), CGP, WIDE, typename TWord<MT == 0>::type>(e, P, P.a.exploit + te * G * CG_MAX_EXPLOITS, ex0, ne, srcb);
         __builtin_amdgcn_s_setprio(0);
       } else {
@@ -661,18 +473,14 @@
   // ---- observation (_get_state CyberDefenseEnv.py:146-191), before evolve.  The static float columns come from
   // LDS, or (large M, where leaving them out of LDS buys resident waves) from the L2-resident blob.
   constexpr int OBS_GP = MT ? ((MT / 2 + WAVE - 1) / WAVE < 4 ? (MT / 2 + WAVE - 1) / WAVE : 4) : CG_OBS_GP0;
-#ifdef CG_ABL_NO_OBS
-  if (false) {
-#else
   if (P.o.obs) {
-#endif
     bool dyn_ano = false;
     if constexpr (XE && !FUSED) dyn_ano = COLD(P.b.anomaly != nullptr);   // this env's own Device.anomaly_score plane (slow scan path; per-tick kernels only)
     if (dyn_ano) write_obs<OBS_GP>(e.flags, P.t.in_lds ? e.osv : (const float*)(P.t.blob + P.t.o_os), P.t.in_lds ? e.ver : (const float*)(P.t.blob + P.t.o_ver),
                                    P.b.anomaly + (size_t)env * M, P.o.obs + te * M * 6, M, lane, true);
-    else if (CG_OBS_STAGED && WIDE && !(M & 1))   // written through, as whole lines, via LDS (cg_tick.hpp: write_obs_staged)
+    else if (WIDE && !(M & 1))   // written through, as whole lines, via LDS (cg_tick.hpp: write_obs_staged)
       write_obs_staged(e.flags, e.osv, e.ver, e.ano, P.o.obs + te * M * 6, M, lane, e.obs_stage, WAVE);
-    else if (CG_OBS_STAGED && !FUSED && !XE && MT == 64 && P.t.in_lds)   // 64 devices: the 32 pairs in one step (4096 x 64: -0.3 us of the gap)
+    else if (!FUSED && !XE && MT == 64 && P.t.in_lds)   // 64 devices: the 32 pairs in one step (4096 x 64: -0.3 us of the gap)
       write_obs_staged(e.flags, e.osv, e.ver, e.ano, P.o.obs + te * M * 6, M, lane, e.obs_stage, 32);
     else if (P.t.in_lds) write_obs<OBS_GP>(e.flags, e.osv, e.ver, e.ano, P.o.obs + te * M * 6, M, lane);
     else write_obs<OBS_GP>(e.flags, (const float*)(P.t.blob + P.t.o_os), (const float*)(P.t.blob + P.t.o_ver),
@@ -680,9 +488,6 @@
   }
 
   STAMP(5);
-#ifndef CG_EPI_BATCH
-#define CG_EPI_BATCH 1
-#endif
   // The scalars of the tick's last phases, requested TOGETHER: read next to their uses (the laundered pointer keeps them from
   // being hoisted, which is right for the body as a whole) they were a dozen dependent scalar-cache hits, one after the other,
   // on every env's chain -- episode limit, evolve period, the output pointers, the snapshot pointer, the state pointers of the
@@ -690,23 +495,15 @@
   EP.episode_limit = P.c.episode_limit; EP.evolve_period = P.c.evolve_period; EP.auto_reset = P.c.auto_reset;
   EP.raw = P.o.raw; EP.shaped = P.o.shaped; EP.done = P.o.done; EP.ret = P.o.ret; EP.alive = P.o.alive; EP.snap_live = P.snap.live;
   EP.obs_def = P.o.obs_def; EP.obs_att = P.o.obs_att; EP.b_live = P.b.live; EP.status = P.o.status; EP.b_ienv = P.b.ienv; EP.b_fenv = P.b.fenv;
-  if constexpr (CG_EPI_BATCH) {
-    asm volatile("" :: "s"(EP.episode_limit), "s"(EP.evolve_period), "s"(EP.auto_reset), "s"(EP.raw), "s"(EP.shaped), "s"(EP.done), "s"(EP.ret), "s"(EP.alive));
-    asm volatile("" :: "s"(EP.snap_live), "s"(EP.obs_def), "s"(EP.obs_att), "s"(EP.b_live), "s"(EP.status), "s"(EP.b_ienv), "s"(EP.b_fenv));
-  }
+  asm volatile("" :: "s"(EP.episode_limit), "s"(EP.evolve_period), "s"(EP.auto_reset), "s"(EP.raw), "s"(EP.shaped), "s"(EP.done), "s"(EP.ret), "s"(EP.alive));
+  asm volatile("" :: "s"(EP.snap_live), "s"(EP.obs_def), "s"(EP.obs_att), "s"(EP.b_live), "s"(EP.status), "s"(EP.b_ienv), "s"(EP.b_fenv));
   if (!partial) {   // :1307-1312
     ie[CG_I_STEP_NUM] += 1;
     if (mode == CG_MODE_ATTACKER) ie[CG_I_ATT_STEP] += 1; else ie[CG_I_DEF_STEP] += 1;
   }
   const bool done = ie[CG_I_STEP_NUM] > EP.episode_limit;
-#ifndef CG_ABL_NO_EVOLVE
   if (dirty || umod(ie[CG_I_STEP_NUM], EP.evolve_period) == 0) evolve<XE>(e, P);
-#endif
-#ifdef CG_ABL_NO_BUSYC
-  if (false) {
-#else
   if (ng == 0) {   // :1330 rebuild of the cached busy set
-#endif
     for (int w0 = lane; w0 < NW; w0 += WGP * WAVE) {
       uint32_t fj[WGP], bj[WGP];
 #pragma unroll
@@ -796,17 +593,10 @@
       e.x_dirty = true;
     }
     const int32_t keep_tick = ie[CG_I_RNG_TICK];
-    if constexpr (LS) {   // the snapshot's scalars: the same gathered load as the prologue's
+    {   // the snapshot's scalars: the same gathered load as the prologue's
       const uint32_t* ps = (const uint32_t*)(P.snap.ienv + (size_t)si * CG_I_COUNT) + (lane & 15);
       if (lane >= 16) ps = (const uint32_t*)(P.snap.fenv + (size_t)si * CG_D_COUNT) + (lane < 22 ? lane - 16 : 0);
       hv = lane < 22 ? *ps : 0u;
-    } else {
-    const int32_t* g = P.snap.ienv + (size_t)si * CG_I_COUNT;
-#pragma unroll
-    for (int i = 0; i < CG_I_COUNT; ++i) ie[i] = g[i];
-    const double* gf = P.snap.fenv + (size_t)si * CG_D_COUNT;
-#pragma unroll
-    for (int i = 0; i < CG_D_COUNT; ++i) fe[i] = gf[i];
     }
     ie[CG_I_RNG_TICK] = keep_tick;
     if (!(P.t.K > 0 && P.snap.extra)) ie[CG_I_FLAGS] &= 0xFFFF;
@@ -823,15 +613,6 @@
     if (dyn_ano) ano = P.b.anomaly + (size_t)env * M;
     if (EP.obs_def) write_obs_def(e.flags, osv, ver, ano, EP.obs_def + te * M * 6, M, lane, dyn_ano);
     if (EP.obs_att) write_obs_att(e.flags, osv, ver, EP.obs_att + te * (size_t)(4 * M + P.c.max_exploits), M, P.t.X, P.c.max_exploits, lane);
-  }
-  if (FUSED && !LS && tk + 1 < n_ticks) {   // park the scalars for the next tick
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < CG_I_COUNT; ++i) park[i] = ie[i];
-#pragma unroll
-      for (int i = 0; i < CG_D_COUNT; ++i) ((double*)(park + CG_I_COUNT))[i] = fe[i];
-    }
-    wsync();
   }
   if (FUSED) STAMP(6);
   }   // for tk
@@ -867,16 +648,8 @@
   if (lane == 0) {
     const uint32_t sticky = (uint32_t)ie[CG_I_FLAGS] & (CG_E_TOPO_OVF | CG_E_BUSY_SAT | CG_E_DET_PENDING | CG_E_UNPINNED);
     if (COLD(sticky != 0u) && EP.status) atomicOr(EP.status, sticky);
-    if constexpr (!LS) {
-    int32_t* g = EP.b_ienv + (size_t)env * CG_I_COUNT;
-#pragma unroll
-    for (int i = 0; i < CG_I_COUNT; ++i) g[i] = ie[i];
-    double* gf = EP.b_fenv + (size_t)env * CG_D_COUNT;
-#pragma unroll
-    for (int i = 0; i < CG_D_COUNT; ++i) gf[i] = fe[i];
-    }
   }
-  if constexpr (LS) {   // the scalars go back as they came: lane l writes word l (one store)
+  {   // the scalars go back as they came: lane l writes word l (one store)
     uint32_t* pw = (uint32_t*)(EP.b_ienv + (size_t)env * CG_I_COUNT) + (lane & 15);
     if (lane >= 16) pw = (uint32_t*)(EP.b_fenv + (size_t)env * CG_D_COUNT) + (lane < 22 ? lane - 16 : 0);
     if (lane < 22) *pw = hv;

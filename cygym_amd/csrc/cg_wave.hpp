@@ -45,8 +45,6 @@ struct EnvF {
   uint32_t& hv;
   __device__ __forceinline__ LaneD operator[](int i) const { return LaneD{hv, 16 + 2 * i}; }
 };
-template <bool LS> __device__ __forceinline__ auto scalars_i(uint32_t& hv, int32_t* a) { if constexpr (LS) return EnvI{hv}; else return a; }
-template <bool LS> __device__ __forceinline__ auto scalars_f(uint32_t& hv, double* a) { if constexpr (LS) return EnvF{hv}; else return a; }
 __device__ __forceinline__ uint64_t ballot(bool p) { return __ballot(p); }
 __device__ __forceinline__ int below(uint64_t m) {  // set bits of m below this lane
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));

@@ -175,16 +175,14 @@ static size_t wave_lds_bytes(const DevTopo& t, int max_devs) {
   const bool rt = !t.ct;   // run-time size: 4 bytes of scratch per device (16-bit T table), else 6 (env_setup)
   size_t w = align_up((size_t)(t.cby_global ? 3 : 4) * ((t.M + 3) & ~3), 16) + (size_t)t.Mp * (rt ? 4 : 6) + (size_t)((t.EW + 3) & ~3) * 4 * 2 + CG_LOG_RING * 4 +
              (size_t)((t.Mp / 32 + 2) & ~1) * 4 + (size_t)t.MC * 8 + (size_t)t.Mp * 2 +
-             (t.lists_global ? 0 : align_up((size_t)max_devs * 2, 16)) + (size_t)x_section_bytes(t, t.lists_global) + 128 /* scalar parking of the fused kernel */ +
+             (t.lists_global ? 0 : align_up((size_t)max_devs * 2, 16)) + (size_t)x_section_bytes(t, t.lists_global) + 128 /* reserved, unused: kept so that every launch plan stays as it was */ +
              (t.ct && t.M == 64 ? CG_OBS_STAGE_BYTES / 2 : 0) /* the observation's LDS stage at 64 devices (write_obs_staged) */;
   return align_up(w, 16);
 }
 // The in-CSR columns and slot maps (icol/ieid/oeid, ~2/3 of the blob) are read by block/unblock only (~9 % of
 // env-ticks): they stay in global memory (L2-resident); the staged prefix ends before them (o_icol), or already
 // before the float columns (o_os).
-#ifndef CG_RT_REG_CAP
-#define CG_RT_REG_CAP 20
-#endif
+constexpr int CG_RT_REG_CAP = 20;   // resident waves per CU of the per-tick kernels at run-time sizes (choose_launch_with)
 static int choose_launch_with(cygym_handle* h, int max_devs, int* waves_out);
 static int plan_launch(cygym_handle* h, int max_devs) {
   // comp_by in LDS (as ever), or -- run-time sizes with M % 4 == 0 -- in global memory when that frees enough LDS for
@@ -193,7 +191,7 @@ static int plan_launch(cygym_handle* h, int max_devs) {
   int w_lds = 0, w_glob = 0;
   t.cby_global = 0; t.lists_global = 0;
   const int rc = choose_launch_with(h, max_devs, &w_lds);
-  const bool can = !t.ct && (t.M & 3) == 0 && !getenv("CYGYM_CBY_LDS");
+  const bool can = !t.ct && (t.M & 3) == 0;
   if (can) {
     t.cby_global = 1;
     if (choose_launch_with(h, max_devs, &w_glob) == 0 && (rc != 0 || w_glob > w_lds || getenv("CYGYM_CBY_GLOBAL"))) {   // (env: test aid)
@@ -203,7 +201,7 @@ static int plan_launch(cygym_handle* h, int max_devs) {
       int w_lists = 0;
       // (the rollout kernels share the plan: 4096 x 2048, 20 ticks per launch: roofline fraction 0.311 -> 0.332 on one box)
       t.lists_global = 1;
-      if (!getenv("CYGYM_LISTS_LDS") && choose_launch_with(h, max_devs, &w_lists) == 0 && (w_lists > w_glob || getenv("CYGYM_LISTS_GLOBAL"))) return 0;
+      if (choose_launch_with(h, max_devs, &w_lists) == 0 && (w_lists > w_glob || getenv("CYGYM_LISTS_GLOBAL"))) return 0;
       t.lists_global = 0;
       return choose_launch_with(h, max_devs, &w_glob);
     }
@@ -253,7 +251,7 @@ static int choose_launch_with(cygym_handle* h, int max_devs, int* waves_out) {
       // tests/test_host_cpu.py holds them to that)
       // (run-time sizes, per-tick kernels: <= 81 VGPRs since the topology blob is staged by LDS-DMA instead of through registers:
       // five waves per SIMD; tests/test_host_cpu.py holds them to that)
-      const int reg_cap = ct_lean ? ((wpb > 1 && wpb <= 8) ? 24 : 20) : (ct ? 20 : CG_RT_REG_CAP);
+      const int reg_cap = ct_lean ? ((wpb > 1 && wpb <= 8) ? 4 * CG_LEAN_LB : 4 * (CG_LEAN_LB - 1)) : (ct ? 20 : CG_RT_REG_CAP);   // (4 SIMDs per CU)
       if (waves > reg_cap / wpb * wpb) waves = reg_cap / wpb * wpb;
       // ties: two 8-wave workgroups per CU beat one 16-wave workgroup (their phases interleave)
       const bool better = waves > best_waves || (waves == best_waves && floats == best_floats && wpb == 8);
@@ -805,7 +803,7 @@ int cygym_actor_head_decode(cygym_handle* h, const cygym_actor_head* head, const
     return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: rows_per_group must be a multiple of 16 and the groups must cover the rows%s", "");
   size_t lds = (size_t)n_out_p * HEAD_KC * sizeof(float);
   const void* k = nullptr;
-  const bool mfma = (head->H & 3) == 0 && !getenv("CYGYM_HEAD_SCALAR");   // matrix-core variant: 16 rows per workgroup
+  const bool mfma = (head->H & 3) == 0;   // matrix-core variant: 16 rows per workgroup
   if (mfma) {
     lds = ((size_t)16 * n_out_p + (size_t)16 * (head->H + 1)) * sizeof(float);   // outputs + the hidden tile
     switch (n_out_p / WAVE) {
@@ -938,7 +936,6 @@ int cygym_fit_forests(const uint16_t* rows, const int64_t* row_ptr, const uint32
   return total;
 }
 
-/* diagnostic builds only (-DCG_STAMPS): per-env phase stamps, [N][16] uint64 device buffer (NULL to disable) */
 int cygym_launch_plan(const cygym_handle* h, int32_t* out) {
   if (!h || !out) return fail(nullptr, CYGYM_EINVAL, "cygym_launch_plan: null argument%s", "");
   out[0] = h->wpb; out[1] = h->wpb_fused; out[2] = h->wave_lds; out[3] = h->shared_lds;
@@ -946,6 +943,7 @@ int cygym_launch_plan(const cygym_handle* h, int32_t* out) {
   return CYGYM_OK;
 }
 
+/* diagnostic builds only (-DCG_STAMPS): per-env phase stamps, int64 [N][28] device buffer (CG_DBG_W, cg_params.hpp; NULL to disable) */
 int cygym_set_debug(cygym_handle* h, void* buf) {
   if (!h) return fail(h, CYGYM_EINVAL, "null handle%s", "");
   h->dbg = (unsigned long long*)buf;

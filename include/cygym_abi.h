@@ -454,8 +454,9 @@ int cygym_timer_stop(cygym_handle* h, void* stream, float* ms);
  *    reserved (0), one 16-wave workgroup per CU with the in-CSR maps in LDS (0/1)} */
 int cygym_launch_plan(const cygym_handle* h, int32_t* out);
 
-/* Diagnostic builds only (-DCG_STAMPS, tools/stamps.py): `stamps` = DEVICE int64 [N][16] receiving per-phase
- * s_memtime stamps of every env's last tick, or NULL to switch them off.  Ignored by the product build. */
+/* Diagnostic builds only (-DCG_STAMPS, tools/stamps.py): `stamps` = DEVICE int64 [N][28] (CG_DBG_W in
+ * cygym_amd/csrc/cg_params.hpp) receiving per-phase s_memtime stamps of every env's last tick, or NULL to switch them
+ * off.  Ignored by the product build. */
 int cygym_set_debug(cygym_handle* h, void* stamps);
 
 #ifdef __cplusplus

@@ -201,6 +201,24 @@ def test_every_shipped_kernel_is_free_of_spilled_vgprs():
     assert {"actor_mlp_kernel", "tick_actor_kernel", "actor_head", "sample_group_actions_kernel", "group_actions_kernel", "step_kernel"} <= families
 
 
+def test_kernel_sources_carry_no_tuning_switches():
+    """The native sources build one configuration: no CG_ compile switch besides the header guards and the build's own
+    (diagnostic stamps, instantiation groups, subset builds, the C-ABI unit), and no environment hook besides the four the
+    GPU tests force.  A tuning override is a constant; its measurements live in PERFLOG.md and profiles/."""
+    keep = {"CG_STAMPS", "CG_INST_GROUP", "CG_CBY_GLOBAL", "CG_DEV_MT", "CG_HAS_MT", "CG_MAIN_UNIT"}
+    hooks = {"CYGYM_WPB", "CYGYM_NO_WIDE", "CYGYM_CBY_GLOBAL", "CYGYM_LISTS_GLOBAL"}
+    src = os.path.join(ROOT, "cygym_amd", "csrc")
+    bad = []
+    for fn in sorted(os.listdir(src)):
+        for i, line in enumerate(open(os.path.join(src, fn), errors="replace"), 1):
+            m = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)", line)
+            names = re.findall(r"\bCG_\w+", m.group(1)) if m else []
+            names += re.findall(r"\bdefined\s*\(?\s*(CG_\w+)", line)
+            bad += [f"{fn}:{i}: {n}" for n in names if n not in keep and not n.endswith("_HPP")]
+            bad += [f"{fn}:{i}: getenv({a})" for a in re.findall(r"getenv\s*\(([^)]*)\)", line) if a.strip().strip('"') not in hooks]
+    assert not bad, bad
+
+
 def _create(topo, cfg, n=4):
     from cygym_amd import _lib
     lib = _lib.load()

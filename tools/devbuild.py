@@ -4,7 +4,7 @@ compiler's resource report (VGPRs / spills / scratch / occupancy).
     python tools/devbuild.py 256                 # the 256-device kernels only -> /tmp/cygym_dev.so  (about 40 s)
     python tools/devbuild.py 0 "" path/lib.so    # run-time sizes, named output   (second argument: unused, kept for old habits)
     CYGYM_SO=/tmp/cygym_dev.so python bench.py ...       # run against it (cygym_amd/_lib.py honours CYGYM_SO)
-Extra compiler flags: CYGYM_BUILD_FLAGS="-DCG_LEAN_LB=5 ...".
+Extra compiler flags: CYGYM_BUILD_FLAGS="-DCG_STAMPS ..." (the diagnostic build, tools/stamps.py).
 """
 import json
 import os
