@@ -18,6 +18,7 @@ constexpr int CG_FUSED_LB = 4;   // rollout kernels: 4 waves per SIMD (128 VGPRs
 // combination miscompiled: a spilled SGPR pair (an f64 env accumulator) came back clobbered after the divergent
 // block / unblock code at run-time sizes (caught by every full-feature fixture test).  No VGPR spills, no problem.
 constexpr int CG_LB = 4;
+#include "cg_plan.hpp"   // the constants host and device share (CG_LEAN_LB, CG_OBS_STAGE_BYTES, ...) and the launch planner
 #define CG_E_STAR_OK 0x80  // kernel-private: star edges verified for the current owned set
 
 namespace cygym_k {

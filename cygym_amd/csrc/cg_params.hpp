@@ -11,7 +11,7 @@ constexpr int WAVE = 64;
 //   [optr u16 M+1][ocol u16 E][dst u8 M][vul u8 M][nap u8 M][iptr u16 M+1] | [os f32 M][ver f32 M][ano f32 M] | [icol u16 E][ieid u16 E][oeid u16 E]
 //   (ieid: out-slot of an in-entry; oeid: in-entry of an out-slot)
 // The first `lds_bytes` bytes are staged in LDS: up to and including the float columns (in_lds), or without them
-// when that buys more resident waves (choose_launch); the in-CSR columns are read from the L2-resident blob.
+// when that buys more resident waves (plan_layout, cg_plan.hpp); the in-CSR columns are read from the L2-resident blob.
 struct DevTopo {
   int M, X, E, EW, MC, Mp;
   const uint8_t* blob;
@@ -20,7 +20,7 @@ struct DevTopo {
   int K, KW, x_bytes;   // extra-edge list: capacity, blocked-bit words, bytes of its per-wave LDS section
   int cby_global;       // run-time sizes with M % 4 == 0: the comp_by plane stays in global memory (3 planes staged, Env::cby_g)
   int ct;               // 64 or 256 devices AND no row longer than the device count: the compile-time-size kernels apply (else the run-time ones)
-  int lists_global;     // ... and so do the tick's device list, the extra-edge list and the in-row bounds (choose_launch: where that buys a resident wave)
+  int lists_global;     // ... and so do the tick's device list, the extra-edge list and the in-row bounds (plan_launch: where that buys a resident wave)
   const double* apl;    // [CG_DET_APL_N] leaf-term table of the trained detector (global; tail of the blob), or nullptr
   // global views (host-side convenience; kernels outside the tick use them)
   const uint8_t *dstatic, *vuln, *napps;

@@ -162,7 +162,6 @@ __device__ __forceinline__ void write_obs_att(const uint8_t* flags, const float*
   if (lane < max_exploits) out[4 * M + lane] = lane < X ? 1.f : 0.f;
 }
 
-#define CG_OBS_STAGE_BYTES 3072   // 64 pairs x 48 bytes
 // MAPS: the in-CSR columns and slot maps are staged in LDS too (the WIDE per-tick kernel, one 16-wave workgroup per CU).
 // Returns the spread's per-chunk source masks (srcb: [MC] words of this wave's block).
 template <bool MAPS, bool RT, class KP>   // RT: run-time size (comp_by may stay in global memory: one plane less in LDS)
@@ -188,7 +187,7 @@ __device__ __forceinline__ uint64_t* env_setup(Env& e, uint8_t* smem, const KP& 
   e.obs_stage = (float4*)(wb + P.wave_lds - 128 - P.t.x_bytes - (M == 64 ? CG_OBS_STAGE_BYTES / 2 : CG_OBS_STAGE_BYTES));
   e.xb = e.xk + P.t.K;
   e.xmo = (uint64_t*)(e.xb + ((P.t.KW + 1) & ~1));
-  const bool lists_global = RT && P.t.lists_global;   // device list / extra-edge list / in-row bounds read where they lie (see choose_launch)
+  const bool lists_global = RT && P.t.lists_global;   // device list / extra-edge list / in-row bounds read where they lie (see plan_launch, cg_plan.hpp)
   if (lists_global) { e.xmo = (uint64_t*)e.xk; e.xk = nullptr; e.xb = nullptr; e.devl = nullptr; }   // (the tick body points them at the env's global rows)
   e.xmi = e.xmo + MC;
   e.K = P.t.K;
@@ -231,7 +230,6 @@ constexpr int CG_WGP0 = 4;      // run-time sizes: words / observation pairs per
 constexpr int CG_OBS_GP0 = 4;
 constexpr int CG_WIDE_CR = 1;   // rows per cooperative step of the generic spread (attacker_spread's CR): the WIDE kernel ...
 constexpr int CG_RT_CR = 4;     // ... and the run-time-size kernels in workgroups of up to 8 waves
-constexpr int CG_LEAN_LB = 6;   // waves per SIMD of the lean per-tick kernel at a compile-time size (below; choose_launch_with plans by it)
 
 // FUSED: cygym_rollout (n_ticks > 1): the tick loop runs inside the launch; the single-tick instantiation has a
 // compile-time trip count of 1.

@@ -211,7 +211,7 @@
     }
     for (int w = lane + PF_BLK * WAVE; w < H.t.EW; w += WAVE) { e.blk[w] = gb[w]; e.bin[w] = H.b.blocked_in[(size_t)env * H.t.EW + w]; }
     const int16_t* gd = H.a.dev_idx + (size_t)env * L;
-    if (MT == 0 && H.t.lists_global) e.devl = (int16_t*)gd;   // (read where it lies: see choose_launch; never written through this pointer)
+    if (MT == 0 && H.t.lists_global) e.devl = (int16_t*)gd;   // (read where it lies: see plan_launch, cg_plan.hpp; never written through this pointer)
     else {
 #pragma unroll
     for (int j = 0; j < PF_DEV; ++j) { int q = lane + j * WAVE; if (q < L) e.devl[q] = dv[j]; }

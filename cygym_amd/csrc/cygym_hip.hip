@@ -34,6 +34,7 @@
 #include "cg_iforest.hpp"
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 using namespace cygym_k;
 
@@ -57,19 +58,15 @@ extern template __global__ void tick_actor_kernel<6>(const KParams, cygym_actor_
 struct cygym_handle {
   int device_id;
   int n_envs;
-  DevTopo t;
+  DevTopo t;            // the topology layout; its five plan fields are stamped from `plan` by make_params
   cygym_config c;
   cygym_buffers b;
   cygym_buffers snap;
   bool bound, has_snap;
   void* dev_blob;       // one allocation holding the topology copies (+ the detector's leaf-term table)
-  int wpb, max_devs;
-  int wpb_fused;        // shape of the rollout kernels (register-capped at 16 waves per CU: a single 16-wave workgroup where it fits)
+  LaunchPlan plan;      // which kernel shape runs with which LDS carve-up (cg_plan.hpp); written by replan() only
   bool few_waves;       // n_envs <= 16 per CU: one wave per env cannot use more than 4 waves per SIMD
-  bool wide;            // the WIDE per-tick kernel runs: one 16-wave workgroup per CU with the WHOLE blob (in-CSR maps too) in LDS
-  int o_maps_end;       // blob offset just past the in-CSR maps
   int max_row;          // longest out- or in-row of the shared CSR, in slots
-  int wave_lds, shared_lds;
   hipEvent_t ev0, ev1;
   unsigned long long* dbg;
   char err[256];
@@ -92,7 +89,7 @@ static int fail(cygym_handle* h, int code, const char* fmt, const char* detail) 
 template <int MT, bool FUSED, bool XE, bool WIDE>
 static const void* kernel_for(int wpb) {
   if constexpr (!CG_HAS_MT(MT)) return nullptr;
-  else if constexpr (WIDE) {   // the WIDE kernel only ever runs as one 16-wave workgroup per CU (choose_launch)
+  else if constexpr (WIDE) {   // the WIDE kernel only ever runs as one 16-wave workgroup per CU (plan_layout)
     return wpb == 16 ? (const void*)step_kernel<16, MT, FUSED, XE, WIDE> : nullptr;
   } else
   switch (wpb) {
@@ -112,7 +109,7 @@ static const void* kernel_for(int wpb) {
 }
 template <bool FUSED, bool XE, bool WIDE>
 static const void* kernel_for_m(const cygym_handle* h) {
-  const int wpb = FUSED ? h->wpb_fused : h->wpb;
+  const int wpb = FUSED ? h->plan.wpb_fused : h->plan.wpb;
   if (h->t.ct && h->t.M == 256) return kernel_for<256, FUSED, XE, WIDE>(wpb);
   if (h->t.ct && h->t.M == 64) return kernel_for<64, FUSED, XE, false>(wpb);   // rows of <= 3 words: nothing to gain (measured: -9 %)
   return kernel_for<0, FUSED, XE, false>(wpb);   // run-time M: the wide variant would spill
@@ -127,18 +124,46 @@ static const void* pick_kernel(const cygym_handle* h, bool fused, int full = -1)
   const bool xe = full < 0 ? full_feature(h) : full != 0;
   if (fused) return xe ? kernel_for_m<true, true, false>(h) : kernel_for_m<true, false, false>(h);
   if (xe) return kernel_for_m<false, true, false>(h);
-  return h->wide ? kernel_for_m<false, false, true>(h) : kernel_for_m<false, false, false>(h);
+  return h->plan.wide ? kernel_for_m<false, false, true>(h) : kernel_for_m<false, false, false>(h);
 }
 static hipError_t set_lds_attr(cygym_handle* h) {   // every instantiation this handle may launch (lean and full-feature)
   for (int full = (h->t.K > 0 ? 1 : 0); full < 2; ++full)
     for (int fused = 0; fused < 2; ++fused) {
-      const int lds = h->shared_lds + h->wave_lds * (fused ? h->wpb_fused : h->wpb);
+      const int lds = h->plan.shared_lds + h->plan.wave_lds * (fused ? h->plan.wpb_fused : h->plan.wpb);
       const void* k = pick_kernel(h, fused != 0, full);
       if (!k) return hipErrorInvalidDeviceFunction;   // development subset build (CG_DEV_MT)
       hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       if (e != hipSuccess) return e;
     }
   return hipSuccess;
+}
+// What the planner reads of a handle.  The environment hooks (test / tuning aids) are read here, once per plan.
+static PlanInput plan_input(const cygym_handle* h, int max_devs) {
+  PlanInput in = plan_shape(h->t.M, h->t.E, h->t.K, h->max_row);
+  in.few_waves = h->few_waves; in.full_feature = full_feature(h); in.max_devs = max_devs;
+  const char* force = getenv("CYGYM_WPB"); in.forced_wpb = force ? atoi(force) : 0;
+  in.force_cby_global = getenv("CYGYM_CBY_GLOBAL") != nullptr; in.force_lists_global = getenv("CYGYM_LISTS_GLOBAL") != nullptr;
+  return in;
+}
+// Plan the launch for device lists of up to max_devs entries and opt in to its dynamic LDS.  Transactional: a plan that
+// does not fit (a longer device list) leaves the handle as it was -- the old sizes never end up under new placement flags.
+static int replan(cygym_handle* h, int max_devs, const char* what) {
+  const LaunchPlan p = plan_launch(plan_input(h, max_devs));
+  if (!p.fits()) return fail(h, CYGYM_EUNSUPPORTED, "%s does not fit in LDS", what);
+  h->plan = p;
+  HIPCHK(h, hipSetDevice(h->device_id));   // (the attribute belongs to the HANDLE's device, whatever the caller's current one is)
+  HIPCHK(h, set_lds_attr(h));              // every instantiation we may launch
+  return CYGYM_OK;
+}
+// The actor kernels are instantiated per outputs-per-lane count: f(integral_constant<n>) names kernel<n> for n in LO..8 (else 8).
+template <int LO, class F>
+static const void* kernel_by_opl(int n, F f) {
+  switch (n) {
+#define CG_OPL_CASE(O) case O: if constexpr (O >= LO) return f(std::integral_constant<int, O>{}); else break;
+    CG_OPL_CASE(0) CG_OPL_CASE(1) CG_OPL_CASE(2) CG_OPL_CASE(3) CG_OPL_CASE(4) CG_OPL_CASE(5) CG_OPL_CASE(6) CG_OPL_CASE(7)
+#undef CG_OPL_CASE
+  }
+  return f(std::integral_constant<int, 8>{});
 }
 
 extern "C" {
@@ -161,127 +186,6 @@ int cygym_sizeof(int32_t which) {
   }
 }
 const char* cygym_last_error(const cygym_handle* h) { return h ? h->err : g_err; }
-
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// LDS budget: shared blob prefix + WPB per-wave regions.  Prefers staging the in-CSR too.
-// Bytes of the extra-edge section of a wave's LDS block: keys + blocked bits + the per-chunk in / out masks, or -- lists_global --
-// the masks alone (the list itself is then read and edited in its global row)
-static int x_section_bytes(const DevTopo& t, bool lists_global) {
-  if (t.K <= 0) return 0;
-  return (int)align_up((lists_global ? 0 : (size_t)4 * (t.K + ((t.KW + 1) & ~1))) + (size_t)16 * t.MC, 16);
-}
-static size_t wave_lds_bytes(const DevTopo& t, int max_devs) {
-  const bool rt = !t.ct;   // run-time size: 4 bytes of scratch per device (16-bit T table), else 6 (env_setup)
-  size_t w = align_up((size_t)(t.cby_global ? 3 : 4) * ((t.M + 3) & ~3), 16) + (size_t)t.Mp * (rt ? 4 : 6) + (size_t)((t.EW + 3) & ~3) * 4 * 2 + CG_LOG_RING * 4 +
-             (size_t)((t.Mp / 32 + 2) & ~1) * 4 + (size_t)t.MC * 8 + (size_t)t.Mp * 2 +
-             (t.lists_global ? 0 : align_up((size_t)max_devs * 2, 16)) + (size_t)x_section_bytes(t, t.lists_global) + 128 /* reserved, unused: kept so that every launch plan stays as it was */ +
-             (t.ct && t.M == 64 ? CG_OBS_STAGE_BYTES / 2 : 0) /* the observation's LDS stage at 64 devices (write_obs_staged) */;
-  return align_up(w, 16);
-}
-// The in-CSR columns and slot maps (icol/ieid/oeid, ~2/3 of the blob) are read by block/unblock only (~9 % of
-// env-ticks): they stay in global memory (L2-resident); the staged prefix ends before them (o_icol), or already
-// before the float columns (o_os).
-constexpr int CG_RT_REG_CAP = 20;   // resident waves per CU of the per-tick kernels at run-time sizes (choose_launch_with)
-static int choose_launch_with(cygym_handle* h, int max_devs, int* waves_out);
-static int plan_launch(cygym_handle* h, int max_devs) {
-  // comp_by in LDS (as ever), or -- run-time sizes with M % 4 == 0 -- in global memory when that frees enough LDS for
-  // another resident wave per CU (2048 devices without an extra-edge list: 4 -> 5)
-  DevTopo& t = h->t;
-  int w_lds = 0, w_glob = 0;
-  t.cby_global = 0; t.lists_global = 0;
-  const int rc = choose_launch_with(h, max_devs, &w_lds);
-  const bool can = !t.ct && (t.M & 3) == 0;
-  if (can) {
-    t.cby_global = 1;
-    if (choose_launch_with(h, max_devs, &w_glob) == 0 && (rc != 0 || w_glob > w_lds || getenv("CYGYM_CBY_GLOBAL"))) {   // (env: test aid)
-      // ... and, if THAT buys yet another one, the tick's device list, the extra-edge list and the in-row bounds too: they are read
-      // where they lie in global memory (2048 devices with a 416-entry extra-edge list: 24.2 -> 22.0 KB per env and 4 KB less of
-      // shared topology: 5 -> 6 waves per CU, i.e. 4096 envs in three residency rounds instead of four)
-      int w_lists = 0;
-      // (the rollout kernels share the plan: 4096 x 2048, 20 ticks per launch: roofline fraction 0.311 -> 0.332 on one box)
-      t.lists_global = 1;
-      if (choose_launch_with(h, max_devs, &w_lists) == 0 && (w_lists > w_glob || getenv("CYGYM_LISTS_GLOBAL"))) return 0;
-      t.lists_global = 0;
-      return choose_launch_with(h, max_devs, &w_glob);
-    }
-    t.cby_global = 0;
-    return choose_launch_with(h, max_devs, &w_lds);
-  }
-  return rc;
-}
-// Transactional: the plan is made on a copy of the handle and committed only when it succeeds.  plan_launch clears the
-// placement flags before it tries the layouts, while choose_launch_with writes the LDS sizes only on success: a failed
-// re-plan (a longer device list that does not fit) must not leave the old sizes under the new flags.
-static int choose_launch(cygym_handle* h, int max_devs) {
-  cygym_handle p = *h;
-  const int rc = plan_launch(&p, max_devs);
-  if (rc != 0) return rc;
-  h->t.cby_global = p.t.cby_global; h->t.lists_global = p.t.lists_global; h->t.x_bytes = p.t.x_bytes;
-  h->t.lds_bytes = p.t.lds_bytes; h->t.in_lds = p.t.in_lds;
-  h->wpb = p.wpb; h->wpb_fused = p.wpb_fused; h->wave_lds = p.wave_lds; h->shared_lds = p.shared_lds;
-  h->max_devs = p.max_devs; h->wide = p.wide;
-  return 0;
-}
-static int choose_launch_with(cygym_handle* h, int max_devs, int* waves_out) {
-  DevTopo& t = h->t;
-  const size_t lds_cap = 160 * 1024;
-  const size_t wave = wave_lds_bytes(t, max_devs);
-  const char* force = getenv("CYGYM_WPB");   // tuning aid: force the waves-per-workgroup choice
-  const int forced = force ? atoi(force) : 0;
-  int best = 0, best_waves = 0, best_floats = 1;
-  // The three static float columns (os / version / anomaly, 12 bytes per device) feed only the observation
-  // writer: they ride in LDS unless leaving them in the L2-resident blob buys more resident waves (M >= 1024).
-  for (int floats = t.lists_global ? 0 : 1; floats >= 0; --floats) {
-    const size_t shared = (size_t)(t.lists_global ? t.o_iptr : floats ? t.o_icol : t.o_os);   // (lists_global: the staged prefix ends before the in-row bounds)
-    static const int shapes[] = {16, 12, 8, 6, 5, 4, 3, 2, 1};
-    for (int wpb : shapes) {
-      if (forced && wpb != forced) continue;
-      if ((wpb & (wpb - 1)) != 0 && t.ct) continue;   // the compile-time sizes come in powers of two only
-      const size_t per_wg = shared + wave * wpb;
-      if (per_wg > lds_cap) continue;
-      int waves = (int)(lds_cap / per_wg) * wpb;
-      if (waves > 32) waves = 32;
-      // ... of which the register file keeps this many resident (whole workgroups): the lean per-tick kernel at a
-      // compile-time size is built for 6 waves per SIMD in workgroups of 2-8 waves and 5 otherwise, everything else
-      // for 4 (launch bounds of step_kernel).  Without this a 16-wave shape that LDS would hold twice won over three
-      // 8-wave workgroups although only one of the two ever runs (16384 x 256: -11 %).
-      const bool ct = t.ct != 0, ct_lean = ct && !full_feature(h);
-      // (the full-feature per-tick kernels at a compile-time size need <= 102 VGPRs: 5 waves per SIMD;
-      // tests/test_host_cpu.py holds them to that)
-      // (run-time sizes, per-tick kernels: <= 81 VGPRs since the topology blob is staged by LDS-DMA instead of through registers:
-      // five waves per SIMD; tests/test_host_cpu.py holds them to that)
-      const int reg_cap = ct_lean ? ((wpb > 1 && wpb <= 8) ? 4 * CG_LEAN_LB : 4 * (CG_LEAN_LB - 1)) : (ct ? 20 : CG_RT_REG_CAP);   // (4 SIMDs per CU)
-      if (waves > reg_cap / wpb * wpb) waves = reg_cap / wpb * wpb;
-      // ties: two 8-wave workgroups per CU beat one 16-wave workgroup (their phases interleave)
-      const bool better = waves > best_waves || (waves == best_waves && floats == best_floats && wpb == 8);
-      if (better) { best_waves = waves; best = wpb; best_floats = floats; }
-    }
-  }
-  if (!best) return -1;
-  *waves_out = best_waves;
-  const size_t shared = (size_t)(t.lists_global ? t.o_iptr : best_floats ? t.o_icol : t.o_os);
-  t.x_bytes = x_section_bytes(t, t.lists_global);
-  h->wpb = best; h->wave_lds = (int)wave; h->shared_lds = (int)shared;
-  // The rollout kernels are built for 4 waves per SIMD whatever the size: 16 resident waves per CU at most, and one
-  // 16-wave workgroup measured 4 % faster than two of 8 (16384 x 256).  Otherwise they share the per-tick shape.
-  h->wpb_fused = best;
-  if (!forced && t.ct && best < 16 && shared + wave * 16 <= lds_cap) h->wpb_fused = 16;
-  t.lds_bytes = (int)shared; t.in_lds = best_floats;   // in_lds: the float columns are staged too
-  h->max_devs = max_devs;
-  // Few envs per CU (<= 16: every env has its own resident wave and a launch lasts as long as its slowest env, which
-  // on defender ticks is a block / unblock list): one 16-wave workgroup per CU leaves room for the in-CSR columns and
-  // slot maps in LDS as well, so a speculation pass no longer waits on global memory.  Compile-time size 256, lean only.
-  h->wide = false;
-  // (its nine-word pool reads cover rows of at most 256 slots: max_row is checked here, there is no fallback in the kernel)
-  if (h->few_waves && t.ct && t.M == 256 && !full_feature(h) && !forced && h->max_row <= 256 && (size_t)h->o_maps_end + (wave + CG_OBS_STAGE_BYTES) * 16 <= lds_cap) {
-    h->wide = true;
-    h->wave_lds = (int)wave + CG_OBS_STAGE_BYTES;   // + the observation's LDS stage (write_obs_staged)
-    h->wpb = 16; h->wpb_fused = 16; h->shared_lds = h->o_maps_end;
-    t.lds_bytes = h->o_maps_end; t.in_lds = 1;
-  }
-  return 0;
-}
 
 int cygym_create(const cygym_topology* topo, const cygym_config* cfg, int32_t n_envs, int32_t device_id,
                  cygym_handle** out) {
@@ -339,49 +243,33 @@ int cygym_create(const cygym_topology* topo, const cygym_config* cfg, int32_t n_
     h->few_waves = (long long)n_envs <= 16LL * cus && !getenv("CYGYM_NO_WIDE");
   }
   DevTopo& t = h->t;
-  t.M = M; t.X = X; t.E = E; t.EW = (E + 31) / 32 > 0 ? (E + 31) / 32 : 1;
-  t.MC = (M + WAVE - 1) / WAVE; t.Mp = t.MC * WAVE;
-  t.K = topo->max_extra_edges; t.KW = (t.K + 31) / 32;
-  // Run-time sizes (not one of the compile-time device counts), M % 4 == 0: Device.compromised_by is not staged -- the few
-  // actions that touch it go to global memory -- which buys LDS: at 2048 devices 2 KB per env, the difference between four
-  // and five resident waves per CU (the lean kernels; with an extra-edge list four either way)
-  // (decided in choose_launch: only where it buys a resident wave -- the global-memory accesses cost 3-6 % otherwise)
-  t.cby_global = 0;
-  t.lists_global = 0;
-  t.x_bytes = x_section_bytes(t, false);   // (choose_launch sets the one in effect)
-  // one blob, laid out exactly as the LDS-shared section (see DevTopo)
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 16); return (int)o; };
-  t.o_optr = take((size_t)(M + 1) * 2); t.o_ocol = take((size_t)(E > 0 ? E : 1) * 2);
-  t.o_dst = take(M); t.o_vul = take(M); t.o_nap = take(M);
-  t.o_iptr = take((size_t)(M + 1) * 2);   // in-row bounds: always staged (block / unblock and evolve read them per lane)
-  t.o_os = take((size_t)M * 4); t.o_ver = take((size_t)M * 4); t.o_ano = take((size_t)M * 4);   // LDS only when that is free
-  t.o_icol = take((size_t)(E > 0 ? E : 1) * 2); t.o_ieid = take((size_t)(E > 0 ? E : 1) * 2);
-  t.o_oeid = take((size_t)(E > 0 ? E : 1) * 2);
-  h->o_maps_end = (int)off;
-  {  // env_setup (cg_tick.hpp) derives every section offset from o_dst at the compile-time sizes: hold the layout to that
-    const int A_M = (M + 15) & ~15, A_P = (2 * (M + 1) + 15) & ~15, A_F = (4 * M + 15) & ~15, a_e = t.o_dst - A_P;
-    if (t.o_optr != 0 || t.o_ocol != A_P || t.o_vul != t.o_dst + A_M || t.o_nap != t.o_dst + 2 * A_M || t.o_iptr != t.o_dst + 3 * A_M ||
-        t.o_os != t.o_iptr + A_P || t.o_ver != t.o_os + A_F || t.o_ano != t.o_ver + A_F || t.o_icol != t.o_ano + A_F ||
-        t.o_ieid != t.o_icol + a_e || t.o_oeid != t.o_ieid + a_e) { delete h; return fail(nullptr, CYGYM_EINVAL, "internal: blob layout%s", ""); }
-  }
-  const int o_apl = take(topo->det_apl ? (size_t)CG_DET_APL_N * 8 : 0);   // global only: read by trained scans
-  t.blob_bytes = (int)off;
-  t.multi = 0;   // duplicate (u,v) out-entries? (env._blocked holds pairs, so duplicates share their state)
-  for (int u = 0; u < M && !t.multi; ++u)
-    for (int k = topo->out_ptr[u]; k < topo->out_ptr[u + 1] && !t.multi; ++k)
-      for (int k2 = k + 1; k2 < topo->out_ptr[u + 1]; ++k2)
-        if (topo->out_col[k2] == topo->out_col[k]) { t.multi = 1; break; }
   h->max_row = 0;
   for (int u = 0; u < M; ++u) {
     const int lo = topo->out_ptr[u + 1] - topo->out_ptr[u], li = topo->in_ptr[u + 1] - topo->in_ptr[u];
     if (lo > h->max_row) h->max_row = lo;
     if (li > h->max_row) h->max_row = li;
   }
-  // A compile-time size whose longest row exceeds the device count (duplicate edges) runs on the run-time-size kernels: the
-  // compile-time ones count and select a row's bits in a fixed number of words (pool_pick<NW>, cg_defender.hpp).
-  t.ct = ((M == 64 && h->max_row <= 64) || (M == 256 && h->max_row <= 256)) ? 1 : 0;
-  if (choose_launch(h, M > 8 ? M / 8 : 1) != 0) { delete h; return fail(nullptr, CYGYM_EUNSUPPORTED, "topology does not fit in LDS%s", ""); }
+  const PlanInput sz = plan_shape(M, E, topo->max_extra_edges, h->max_row);   // (t.ct: the compile-time-size kernels apply)
+  t.M = M; t.X = X; t.E = E; t.EW = sz.EW; t.MC = sz.MC; t.Mp = sz.Mp; t.K = sz.K; t.KW = sz.KW; t.ct = sz.ct;
+  // one blob, laid out exactly as the LDS-shared section (see DevTopo)
+  const BlobLayout L = blob_layout(M, E);
+  t.o_optr = L.o_optr; t.o_ocol = L.o_ocol; t.o_dst = L.o_dst; t.o_vul = L.o_vul; t.o_nap = L.o_nap; t.o_iptr = L.o_iptr;
+  t.o_os = L.o_os; t.o_ver = L.o_ver; t.o_ano = L.o_ano; t.o_icol = L.o_icol; t.o_ieid = L.o_ieid; t.o_oeid = L.o_oeid;
+  {  // env_setup (cg_tick.hpp) derives every section offset from o_dst at the compile-time sizes: hold the layout to that
+    const int A_M = (M + 15) & ~15, A_P = (2 * (M + 1) + 15) & ~15, A_F = (4 * M + 15) & ~15, a_e = t.o_dst - A_P;
+    if (t.o_optr != 0 || t.o_ocol != A_P || t.o_vul != t.o_dst + A_M || t.o_nap != t.o_dst + 2 * A_M || t.o_iptr != t.o_dst + 3 * A_M ||
+        t.o_os != t.o_iptr + A_P || t.o_ver != t.o_os + A_F || t.o_ano != t.o_ver + A_F || t.o_icol != t.o_ano + A_F ||
+        t.o_ieid != t.o_icol + a_e || t.o_oeid != t.o_ieid + a_e) { delete h; return fail(nullptr, CYGYM_EINVAL, "internal: blob layout%s", ""); }
+  }
+  const int o_apl = L.maps_end;   // the detector's leaf-term table follows the maps (global only: read by trained scans)
+  const size_t off = cg_align_up((size_t)o_apl + (topo->det_apl ? (size_t)CG_DET_APL_N * 8 : 0), 16);
+  t.blob_bytes = (int)off;
+  t.multi = 0;   // duplicate (u,v) out-entries? (env._blocked holds pairs, so duplicates share their state)
+  for (int u = 0; u < M && !t.multi; ++u)
+    for (int k = topo->out_ptr[u]; k < topo->out_ptr[u + 1] && !t.multi; ++k)
+      for (int k2 = k + 1; k2 < topo->out_ptr[u + 1]; ++k2)
+        if (topo->out_col[k2] == topo->out_col[k]) { t.multi = 1; break; }
+  if (const int rc = replan(h, M > 8 ? M / 8 : 1, "topology")) { delete h; return rc; }
   uint8_t* host = (uint8_t*)calloc(1, off);
   if (!host) { delete h; return fail(nullptr, CYGYM_EINVAL, "out of host memory%s", ""); }
   memcpy(host + t.o_dst, topo->dstatic, M); memcpy(host + t.o_vul, topo->vuln, M); memcpy(host + t.o_nap, topo->napps, M);
@@ -415,9 +303,6 @@ int cygym_create(const cygym_topology* topo, const cygym_config* cfg, int32_t n_
   t.out_ptr = (const uint16_t*)(d + t.o_optr); t.out_col = (const uint16_t*)(d + t.o_ocol);
   t.in_ptr = (const uint16_t*)(d + t.o_iptr); t.in_col = (const uint16_t*)(d + t.o_icol); t.in_eid = (const uint16_t*)(d + t.o_ieid);
   t.apl = topo->det_apl ? (const double*)(d + o_apl) : nullptr;
-  // opt in to large dynamic LDS for every instantiation we may launch
-  hipError_t e2 = set_lds_attr(h);
-  if (e2 != hipSuccess) { fail(nullptr, CYGYM_EHIP, "hipFuncSetAttribute: %s", hipGetErrorString(e2)); cygym_destroy(h); return CYGYM_EHIP; }
   *out = h;
   return CYGYM_OK;
 }
@@ -449,8 +334,7 @@ static int check_buffers(cygym_handle* h, const cygym_buffers* b, bool snapshot)
 
 int cygym_bind(cygym_handle* h, const cygym_buffers* state) {
   if (!h) return fail(h, CYGYM_EINVAL, "cygym_bind: null handle%s", "");
-  int rc = check_buffers(h, state, false);
-  if (rc) return rc;
+  if (const int rc = check_buffers(h, state, false)) return rc;
   if (!h->c.fast_scan && (!state->hist || !state->anomaly))
     return fail(h, CYGYM_EINVAL, "fast_scan=False (per-log scan path) needs the `hist` and `anomaly` planes bound%s", "");
   const bool was_full = full_feature(h);
@@ -458,32 +342,60 @@ int cygym_bind(cygym_handle* h, const cygym_buffers* state) {
   h->bound = true;
   // The launch was planned at cygym_create, before it was known whether a forest / history buffer would select the
   // full-feature kernels (other register budget, no WIDE shape): re-plan now that it is.
-  if (full_feature(h) != was_full) {
-    if (choose_launch(h, h->max_devs) != 0) return fail(h, CYGYM_EUNSUPPORTED, "topology does not fit in LDS%s", "");
-    HIPCHK(h, hipSetDevice(h->device_id));
-    HIPCHK(h, set_lds_attr(h));
-  }
+  if (full_feature(h) != was_full)
+    if (const int rc = replan(h, h->plan.max_devs, "topology")) return rc;
   return CYGYM_OK;
 }
 
-static KParams make_params(cygym_handle* h) {
+static KParams make_params(const cygym_handle* h) {
   KParams P;
   memset(&P, 0, sizeof(P));
   P.t = h->t; P.c = h->c; P.b = h->b; P.n_envs = h->n_envs;
   P.env_begin = 0; P.env_end = h->n_envs;
-  P.wave_lds = h->wave_lds; P.shared_lds = h->shared_lds;
+  const LaunchPlan& p = h->plan;   // the one place the plan enters the kernel argument
+  P.t.lds_bytes = p.lds_bytes; P.t.in_lds = p.in_lds; P.t.x_bytes = p.x_bytes; P.t.cby_global = p.cby_global; P.t.lists_global = p.lists_global;
+  P.wave_lds = p.wave_lds; P.shared_lds = p.shared_lds;
   P.dbg = h->dbg;
   return P;
 }
+// The kernel argument of a tick launch (per-tick, rollout, tick + actor), complete.
+static KParams tick_params(const cygym_handle* h, const cygym_actions* a, const cygym_outputs* o, int n_ticks, int env_begin, int env_end) {
+  KParams P = make_params(h);
+  P.a = *a; P.o = *o;
+  P.n_ticks = n_ticks; P.snap = h->snap;
+  P.env_begin = env_begin; P.env_end = env_end;
+  fill_hot(P);
+  return P;
+}
+static bool step_io_ok(const cygym_actions* a, const cygym_outputs* o) {   // every array a tick reads / writes unconditionally
+  return a && o && a->mode && a->n_groups && a->atype && a->n_exploit && a->exploit && a->app && a->dev_cnt && a->dev_idx && o->raw && o->shaped && o->done;
+}
+// The destination of the action writers must be complete (n_groups too where the writer sets it).
+static int check_dst(cygym_handle* h, const cygym_actions* dst, const char* who, bool needs_n_groups) {
+  if ((needs_n_groups && !dst->n_groups) || !dst->atype || !dst->n_exploit || !dst->exploit || !dst->app || !dst->dev_cnt || !dst->dev_idx || dst->max_groups < 1 || dst->max_devs < 1)
+    return fail(h, CYGYM_EINVAL, "%s: bad destination", who);
+  return CYGYM_OK;
+}
+// Raise a kernel's dynamic-LDS limit once per variant and device (not per launch: this sits in a closed loop's tick).
+static int raise_lds_once(cygym_handle* h, const void* k) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> raised;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!raised.count({k, h->device_id})) {
+    HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, CG_LDS_BYTES));
+    raised.insert({k, h->device_id});
+  }
+  return CYGYM_OK;
+}
+constexpr int ROW_THREADS = 256;   // launch geometry of the auxiliary kernels: 256 threads, one wave per row
+static dim3 row_grid(int rows) { return dim3((rows + ROW_THREADS / WAVE - 1) / (ROW_THREADS / WAVE)); }
 
 int cygym_derive(cygym_handle* h, const cygym_buffers* bufs, void* stream) {
   if (!h) return fail(h, CYGYM_EINVAL, "cygym_derive: null handle%s", "");
-  int rc = check_buffers(h, bufs, true);
-  if (rc) return rc;
+  if (const int rc = check_buffers(h, bufs, true)) return rc;
   HIPCHK(h, hipSetDevice(h->device_id));
   KParams P = make_params(h);
-  const int threads = 256, waves_per_block = threads / WAVE;
-  hipLaunchKernelGGL(derive_kernel, dim3((bufs->n_envs + waves_per_block - 1) / waves_per_block), dim3(threads), 0,
+  hipLaunchKernelGGL(derive_kernel, row_grid(bufs->n_envs), dim3(ROW_THREADS), 0,
                      (hipStream_t)stream, P, *bufs);
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
@@ -495,16 +407,14 @@ int cygym_reset(cygym_handle* h, const cygym_buffers* snapshot, const int32_t* e
     if (!h->has_snap) return fail(h, CYGYM_EINVAL, "cygym_reset: no snapshot given or registered%s", "");
     snapshot = &h->snap;
   }
-  int rc = check_buffers(h, snapshot, true);
-  if (rc) return rc;
+  if (const int rc = check_buffers(h, snapshot, true)) return rc;
   if (!env_ids) n = h->n_envs;
   if (n <= 0) return CYGYM_OK;
   if (n > h->n_envs) return fail(h, CYGYM_EINVAL, "cygym_reset: more ids than envs%s", "");
   HIPCHK(h, hipSetDevice(h->device_id));
   KParams P = make_params(h);
   P.snap = *snapshot;
-  const int threads = 256, waves_per_block = threads / WAVE;
-  hipLaunchKernelGGL(reset_kernel, dim3((n + waves_per_block - 1) / waves_per_block), dim3(threads), 0,
+  hipLaunchKernelGGL(reset_kernel, row_grid(n), dim3(ROW_THREADS), 0,
                      (hipStream_t)stream, P, env_ids, n);
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
@@ -518,8 +428,7 @@ int cygym_randomize(cygym_handle* h, const int32_t* env_ids, int32_t n, uint32_t
   if (n > h->n_envs) return fail(h, CYGYM_EINVAL, "cygym_randomize: more ids than envs%s", "");
   HIPCHK(h, hipSetDevice(h->device_id));
   KParams P = make_params(h);
-  const int threads = 256, waves_per_block = threads / WAVE;
-  hipLaunchKernelGGL(randomize_kernel, dim3((n + waves_per_block - 1) / waves_per_block), dim3(threads), 0,
+  hipLaunchKernelGGL(randomize_kernel, row_grid(n), dim3(ROW_THREADS), 0,
                      (hipStream_t)stream, P, env_ids, n, scratch);
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
@@ -528,8 +437,7 @@ int cygym_randomize(cygym_handle* h, const int32_t* env_ids, int32_t n, uint32_t
 int cygym_set_snapshot(cygym_handle* h, const cygym_buffers* snapshot) {
   if (!h) return fail(h, CYGYM_EINVAL, "cygym_set_snapshot: null handle%s", "");
   if (!snapshot) { h->has_snap = false; memset(&h->snap, 0, sizeof(h->snap)); return CYGYM_OK; }
-  int rc = check_buffers(h, snapshot, true);
-  if (rc) return rc;
+  if (const int rc = check_buffers(h, snapshot, true)) return rc;
   h->snap = *snapshot;
   h->has_snap = true;
   return CYGYM_OK;
@@ -569,37 +477,24 @@ static int launch_ticks(cygym_handle* h, int32_t n_ticks, int32_t env_begin, int
   }
   if (n_ticks < 1) return fail(h, CYGYM_EINVAL, "cygym_rollout: n_ticks must be >= 1%s", "");
   if (env_begin < 0 || n < 0 || env_begin > h->n_envs - n) return fail(h, CYGYM_EINVAL, "cygym_step_range: env range outside [0, n_envs)%s", "");
-  if (!a || !o || !a->mode || !a->n_groups || !a->atype || !a->n_exploit || !a->exploit || !a->app ||
-      !a->dev_cnt || !a->dev_idx || !o->raw || !o->shaped || !o->done)
-    return fail(h, CYGYM_EINVAL, "cygym_step: null action / output pointer%s", "");
+  if (!step_io_ok(a, o)) return fail(h, CYGYM_EINVAL, "cygym_step: null action / output pointer%s", "");
   if (a->max_groups < 1 || a->max_devs < 1) return fail(h, CYGYM_EINVAL, "cygym_step: max_groups / max_devs must be >= 1%s", "");
   if (a->max_devs > 32767) return fail(h, CYGYM_EINVAL, "cygym_step: max_devs too large%s", "");
-  if (a->max_devs > h->max_devs) {   // the device list lives in LDS: re-plan the launch for a longer list
-    if (choose_launch(h, a->max_devs) != 0) return fail(h, CYGYM_EUNSUPPORTED, "device list does not fit in LDS%s", "");
-    HIPCHK(h, hipSetDevice(h->device_id));   // (the attribute belongs to the HANDLE's device, whatever the caller's current one is)
-    HIPCHK(h, set_lds_attr(h));
-  }
+  if (a->max_devs > h->plan.max_devs)   // the device list lives in LDS: re-plan the launch for a longer list
+    if (const int rc = replan(h, a->max_devs, "device list")) return rc;
   if (h->c.auto_reset && !h->has_snap) return fail(h, CYGYM_EINVAL, "auto_reset needs cygym_set_snapshot first%s", "");
   if (n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  KParams P = make_params(h);
-  P.a = *a; P.o = *o;
-  P.n_ticks = n_ticks;
-  P.snap = h->snap;
-  P.env_begin = env_begin; P.env_end = env_begin + n;
+  KParams P = tick_params(h, a, o, n_ticks, env_begin, env_begin + n);
   // The parameter block travels as the kernel argument only (the rollout kernel re-reads it from the kernarg
   // segment): nothing is uploaded or shared between launches, so launches of one handle on different streams
   // are independent as long as their env ranges are disjoint.  hipGetLastError below reports launch-time errors;
   // a fault inside the kernel surfaces at the caller's next synchronisation.
-  const int wpb = n_ticks > 1 ? h->wpb_fused : h->wpb;
-  const int lds = h->shared_lds + h->wave_lds * wpb;
+  const int wpb = n_ticks > 1 ? h->plan.wpb_fused : h->plan.wpb;
+  const int lds = h->plan.shared_lds + h->plan.wave_lds * wpb;
   const dim3 grid((n + wpb - 1) / wpb), block(wpb * WAVE);
-  hipStream_t s = (hipStream_t)stream;
-  {
-    fill_hot(P);
-    void* args[] = {(void*)&P};
-    HIPCHK(h, hipLaunchKernel(pick_kernel(h, n_ticks > 1), grid, block, args, (size_t)lds, s));
-  }
+  void* args[] = {(void*)&P};
+  HIPCHK(h, hipLaunchKernel(pick_kernel(h, n_ticks > 1), grid, block, args, (size_t)lds, (hipStream_t)stream));
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
 }
@@ -621,19 +516,14 @@ int cygym_step_actor(cygym_handle* h, const cygym_actions* a, const cygym_output
                      const cygym_action_vectors* layout, const cygym_actions* next, void* stream) {
   if (!h || !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_step_actor: handle not bound%s", "");
   if (!a || !o || !mlp || !layout || !next) return fail(h, CYGYM_EINVAL, "cygym_step_actor: null argument%s", "");
-  if (!a->mode || !a->n_groups || !a->atype || !a->n_exploit || !a->exploit || !a->app || !a->dev_cnt || !a->dev_idx || !o->raw || !o->shaped || !o->done ||
-      a->max_groups < 1 || a->max_devs < 1 || a->max_devs > 32767)
+  if (!step_io_ok(a, o) || a->max_groups < 1 || a->max_devs < 1 || a->max_devs > 32767)
     return fail(h, CYGYM_EINVAL, "cygym_step_actor: bad action / output tensors%s", "");
-  if (a->max_devs > h->max_devs) {   // the device list lives in LDS: re-plan the launch for a longer list (as cygym_step does)
-    if (choose_launch(h, a->max_devs) != 0) return fail(h, CYGYM_EUNSUPPORTED, "device list does not fit in LDS%s", "");
-    HIPCHK(h, hipSetDevice(h->device_id));
-    HIPCHK(h, set_lds_attr(h));
-  }
+  if (a->max_devs > h->plan.max_devs)   // the device list lives in LDS: re-plan the launch for a longer list (as cygym_step does)
+    if (const int rc = replan(h, a->max_devs, "device list")) return rc;
   // the shape both halves share: the lean WIDE per-tick kernel (256 devices, one 16-wave workgroup per CU = 16 envs) over the whole batch
-  if (h->t.M != 256 || !h->wide || h->wpb != 16 || full_feature(h) || (h->n_envs & 15))
+  if (h->t.M != 256 || !h->plan.wide || h->plan.wpb != 16 || full_feature(h) || (h->n_envs & 15))
     return fail(h, CYGYM_EUNSUPPORTED, "cygym_step_actor: 256 devices, a fixed topology without detector buffers, a multiple of 16 envs and at most 16 envs per CU%s", "");
-  if (!next->atype || !next->n_exploit || !next->exploit || !next->app || !next->dev_cnt || !next->dev_idx || next->max_groups < 1 || next->max_devs < 1)
-    return fail(h, CYGYM_EINVAL, "cygym_step_actor: bad destination%s", "");
+  if (const int rc = check_dst(h, next, "cygym_step_actor", false)) return rc;
   if (h->c.auto_reset && !h->has_snap) return fail(h, CYGYM_EINVAL, "auto_reset needs cygym_set_snapshot first%s", "");
   if (mlp->obs_role < 1 || mlp->obs_role > 2 || !mlp->w_head || mlp->n_hidden < 1 || mlp->n_hidden > CG_MLP_MAX_HIDDEN ||
       mlp->K != (mlp->obs_role == 1 ? 6 * h->t.M : 4 * h->t.M + h->c.max_exploits))
@@ -649,33 +539,20 @@ int cygym_step_actor(cygym_handle* h, const cygym_actions* a, const cygym_output
   const int opl = (int)((n_out + 63) / 64);
   if (opl != 5 && opl != 6) return fail(h, CYGYM_EUNSUPPORTED, "cygym_step_actor: action vectors of 257 to 384 entries%s", "");
   HIPCHK(h, hipSetDevice(h->device_id));
-  KParams P = make_params(h);
-  P.a = *a; P.o = *o;
-  P.n_ticks = 1;
-  P.snap = h->snap;
-  P.env_begin = 0; P.env_end = h->n_envs;
+  KParams P = tick_params(h, a, o, 1, 0, h->n_envs);
   const MlpPlan pl = mlp_plan(mlp->K, mlp->n_hidden, mlp->width, opl * 64);
   size_t lds = (size_t)pl.total * sizeof(float);
-  const size_t lds_tick = (size_t)h->shared_lds + (size_t)h->wave_lds * 16;
+  const size_t lds_tick = (size_t)h->plan.shared_lds + (size_t)h->plan.wave_lds * 16;
   if (lds_tick > lds) lds = lds_tick;
-  if (lds > 160 * 1024) return fail(h, CYGYM_EUNSUPPORTED, "cygym_step_actor: the layer shapes do not fit in LDS%s", "");
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_step_actor: the layer shapes do not fit in LDS%s", "");
 #if CG_HAS_MT(256)
   const void* k = opl == 5 ? (const void*)tick_actor_kernel<5> : (const void*)tick_actor_kernel<6>;
 #else
   const void* k = nullptr;   // development subset build without the 256-device kernels
   if (!k) return fail(h, CYGYM_EUNSUPPORTED, "cygym_step_actor: not in this build%s", "");
 #endif
-  {
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> raised;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!raised.count({k, h->device_id})) {
-      HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      raised.insert({k, h->device_id});
-    }
-  }
+  if (const int rc = raise_lds_once(h, k)) return rc;
   MlpView view = {h->b.live, h->t.os_val, h->t.version, h->t.anomaly, h->b.anomaly, h->t.M, h->t.X, h->c.max_exploits, mlp->obs_role};
-  fill_hot(P);
   void* args[] = {(void*)&P, (void*)mlp, (void*)layout, (void*)next, &view};
   HIPCHK(h, hipLaunchKernel(k, dim3(h->n_envs / 16), dim3(16 * WAVE), args, lds, (hipStream_t)stream));
   HIPCHK(h, hipGetLastError());
@@ -687,8 +564,7 @@ int cygym_observe(cygym_handle* h, int32_t role, float* out, void* stream) {
   if (!out || role < 0 || role > 2) return fail(h, CYGYM_EINVAL, "cygym_observe: bad argument%s", "");
   HIPCHK(h, hipSetDevice(h->device_id));
   KParams P = make_params(h);
-  const int threads = 256, waves_per_block = threads / WAVE;
-  hipLaunchKernelGGL(observe_kernel, dim3((h->n_envs + waves_per_block - 1) / waves_per_block), dim3(threads), 0,
+  hipLaunchKernelGGL(observe_kernel, row_grid(h->n_envs), dim3(ROW_THREADS), 0,
                      (hipStream_t)stream, P, role, out);
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
@@ -712,14 +588,11 @@ int cygym_write_actions(cygym_handle* h, const cygym_action_rows* src, const cyg
   if (!h) return fail(h, CYGYM_EINVAL, "cygym_write_actions: null handle%s", "");
   if (!src || !dst || !src->atype || !src->exploit || !src->app || (!src->dev_mask && (!src->dev_idx || !src->dev_cnt)))
     return fail(h, CYGYM_EINVAL, "cygym_write_actions: null source pointer%s", "");
-  if (!dst->atype || !dst->n_exploit || !dst->exploit || !dst->app || !dst->dev_cnt || !dst->dev_idx || dst->max_groups < 1 ||
-      dst->max_devs < 1)
-    return fail(h, CYGYM_EINVAL, "cygym_write_actions: bad destination%s", "");
+  if (const int rc = check_dst(h, dst, "cygym_write_actions", false)) return rc;
   if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_write_actions: bad row count%s", "");
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  const int threads = 256, waves_per_block = threads / WAVE;
-  hipLaunchKernelGGL(write_actions_kernel, dim3((src->n + waves_per_block - 1) / waves_per_block), dim3(threads), 0,
+  hipLaunchKernelGGL(write_actions_kernel, row_grid(src->n), dim3(ROW_THREADS), 0,
                      (hipStream_t)stream, *src, *dst, h->t.M, h->n_envs);
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
@@ -728,9 +601,7 @@ int cygym_write_actions(cygym_handle* h, const cygym_action_rows* src, const cyg
 int cygym_decode_actions(cygym_handle* h, const cygym_action_vectors* src, const cygym_actions* dst, void* stream) {
   if (!h) return fail(h, CYGYM_EINVAL, "cygym_decode_actions: null handle%s", "");
   if (!src || !dst || !src->vec) return fail(h, CYGYM_EINVAL, "cygym_decode_actions: null source pointer%s", "");
-  if (!dst->atype || !dst->n_exploit || !dst->exploit || !dst->app || !dst->dev_cnt || !dst->dev_idx || dst->max_groups < 1 ||
-      dst->max_devs < 1)
-    return fail(h, CYGYM_EINVAL, "cygym_decode_actions: bad destination%s", "");
+  if (const int rc = check_dst(h, dst, "cygym_decode_actions", false)) return rc;
   if (src->n_types < 0 || src->n_exploits < 0 || src->n_apps < 0 || src->n_devices != h->t.M ||
       (long long)src->stride < (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps)
     return fail(h, CYGYM_EINVAL, "cygym_decode_actions: row layout does not fit the stride / the handle's device count%s", "");
@@ -738,8 +609,7 @@ int cygym_decode_actions(cygym_handle* h, const cygym_action_vectors* src, const
   if (src->epsilon_thr && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_decode_actions: epsilon > 0 needs a bound handle%s", "");
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  const int threads = 256, waves_per_block = threads / WAVE;
-  hipLaunchKernelGGL(decode_actions_kernel, dim3((src->n + waves_per_block - 1) / waves_per_block), dim3(threads), 0,
+  hipLaunchKernelGGL(decode_actions_kernel, row_grid(src->n), dim3(ROW_THREADS), 0,
                      (hipStream_t)stream, *src, *dst, h->n_envs, h->b.ienv, h->c.seed, h->c.env_id_base);
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
@@ -748,16 +618,13 @@ int cygym_decode_actions(cygym_handle* h, const cygym_action_vectors* src, const
 int cygym_group_actions(cygym_handle* h, const cygym_device_types* src, const cygym_actions* dst, void* stream) {
   if (!h || !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_group_actions: handle not bound%s", "");
   if (!src || !dst || !src->types) return fail(h, CYGYM_EINVAL, "cygym_group_actions: null source pointer%s", "");
-  if (!dst->n_groups || !dst->atype || !dst->n_exploit || !dst->exploit || !dst->app || !dst->dev_cnt || !dst->dev_idx || dst->max_groups < 1 ||
-      dst->max_devs < 1)
-    return fail(h, CYGYM_EINVAL, "cygym_group_actions: bad destination%s", "");
+  if (const int rc = check_dst(h, dst, "cygym_group_actions", true)) return rc;
   if (src->n_types < 1 || src->n_types > 32 || (!src->visible && src->role != 1 && src->role != 2))
     return fail(h, CYGYM_EINVAL, "cygym_group_actions: 1 to 32 action types; role 1 or 2 when no visibility mask is given%s", "");
   if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_group_actions: bad row count%s", "");
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  const int threads = 256, waves_per_block = threads / WAVE;
-  hipLaunchKernelGGL(group_actions_kernel, dim3((src->n + waves_per_block - 1) / waves_per_block), dim3(threads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(group_actions_kernel, row_grid(src->n), dim3(ROW_THREADS), 0, (hipStream_t)stream,
                      *src, *dst, h->t.M, h->n_envs, (const uint8_t*)h->b.live, h->b.ienv, h->c.seed, h->c.env_id_base);
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
@@ -766,9 +633,7 @@ int cygym_group_actions(cygym_handle* h, const cygym_device_types* src, const cy
 int cygym_sample_group_actions(cygym_handle* h, const cygym_device_logits* src, const cygym_actions* dst, void* stream) {
   if (!h || !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_sample_group_actions: handle not bound%s", "");
   if (!src || !dst || !src->logits || !src->types_out) return fail(h, CYGYM_EINVAL, "cygym_sample_group_actions: null source pointer%s", "");
-  if (!dst->n_groups || !dst->atype || !dst->n_exploit || !dst->exploit || !dst->app || !dst->dev_cnt || !dst->dev_idx || dst->max_groups < 1 ||
-      dst->max_devs < 1)
-    return fail(h, CYGYM_EINVAL, "cygym_sample_group_actions: bad destination%s", "");
+  if (const int rc = check_dst(h, dst, "cygym_sample_group_actions", true)) return rc;
   if (src->n_types < 1 || src->n_types > 32 || src->n_exp < 0 || src->n_exp > 32 || src->n_app < 0 || src->n_app > 32 || (src->role != 1 && src->role != 2))
     return fail(h, CYGYM_EINVAL, "cygym_sample_group_actions: 1 to 32 action types, at most 32 exploit / app logits, role 1 or 2%s", "");
   if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_sample_group_actions: bad row count%s", "");
@@ -785,9 +650,7 @@ int cygym_actor_head_decode(cygym_handle* h, const cygym_actor_head* head, const
                             const cygym_actions* dst, void* stream) {
   if (!h) return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: null handle%s", "");
   if (!head || !src || !dst || !head->hidden || !head->weight_t) return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: null source pointer%s", "");
-  if (!dst->atype || !dst->n_exploit || !dst->exploit || !dst->app || !dst->dev_cnt || !dst->dev_idx || dst->max_groups < 1 ||
-      dst->max_devs < 1)
-    return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: bad destination%s", "");
+  if (const int rc = check_dst(h, dst, "cygym_actor_head_decode", false)) return rc;
   if (src->n_types < 0 || src->n_exploits < 0 || src->n_apps < 0 || src->n_devices != h->t.M || head->H < 1 || head->hidden_stride < head->H)
     return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: bad layout%s", "");
   const long long n_out = (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps;
@@ -802,31 +665,10 @@ int cygym_actor_head_decode(cygym_handle* h, const cygym_actor_head* head, const
   if (head->n_groups > 1 && (head->rows_per_group < 16 || (head->rows_per_group & 15) || (long long)head->n_groups * head->rows_per_group < src->n))
     return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: rows_per_group must be a multiple of 16 and the groups must cover the rows%s", "");
   size_t lds = (size_t)n_out_p * HEAD_KC * sizeof(float);
-  const void* k = nullptr;
   const bool mfma = (head->H & 3) == 0;   // matrix-core variant: 16 rows per workgroup
-  if (mfma) {
-    lds = ((size_t)16 * n_out_p + (size_t)16 * (head->H + 1)) * sizeof(float);   // outputs + the hidden tile
-    switch (n_out_p / WAVE) {
-      case 1: k = (const void*)actor_head_mfma_kernel<1>; break;
-      case 2: k = (const void*)actor_head_mfma_kernel<2>; break;
-      case 3: k = (const void*)actor_head_mfma_kernel<3>; break;
-      case 4: k = (const void*)actor_head_mfma_kernel<4>; break;
-      case 5: k = (const void*)actor_head_mfma_kernel<5>; break;
-      case 6: k = (const void*)actor_head_mfma_kernel<6>; break;
-      case 7: k = (const void*)actor_head_mfma_kernel<7>; break;
-      default: k = (const void*)actor_head_mfma_kernel<8>; break;
-    }
-  } else
-  switch (n_out_p / WAVE) {   // outputs per lane
-    case 1: k = (const void*)actor_head_kernel<1>; break;
-    case 2: k = (const void*)actor_head_kernel<2>; break;
-    case 3: k = (const void*)actor_head_kernel<3>; break;
-    case 4: k = (const void*)actor_head_kernel<4>; break;
-    case 5: k = (const void*)actor_head_kernel<5>; break;
-    case 6: k = (const void*)actor_head_kernel<6>; break;
-    case 7: k = (const void*)actor_head_kernel<7>; break;
-    default: k = (const void*)actor_head_kernel<8>; break;
-  }
+  if (mfma) lds = ((size_t)16 * n_out_p + (size_t)16 * (head->H + 1)) * sizeof(float);   // outputs + the hidden tile
+  const void* k = mfma ? kernel_by_opl<1>(n_out_p / WAVE, [](auto O) { return (const void*)actor_head_mfma_kernel<decltype(O)::value>; })
+                       : kernel_by_opl<1>(n_out_p / WAVE, [](auto O) { return (const void*)actor_head_kernel<decltype(O)::value>; });
   if (!mfma) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, HEAD_OPL_MAX * WAVE * HEAD_KC * (int)sizeof(float)));
   const int rows_per_wg = 16;   // (both variants: 16 waves, one row each to decode)
   int n_envs = h->n_envs;
@@ -843,9 +685,7 @@ int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cy
                            void* stream) {
   if (!h) return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: null handle%s", "");
   if (!mlp || !src || !dst || (!mlp->obs && !mlp->obs_role) || !mlp->w_head) return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: null source pointer%s", "");
-  if (!dst->atype || !dst->n_exploit || !dst->exploit || !dst->app || !dst->dev_cnt || !dst->dev_idx || dst->max_groups < 1 ||
-      dst->max_devs < 1)
-    return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: bad destination%s", "");
+  if (const int rc = check_dst(h, dst, "cygym_actor_mlp_decode", false)) return rc;
   if (src->n_types < 0 || src->n_exploits < 0 || src->n_apps < 0 || src->n_devices != h->t.M || mlp->K < 1 || (!mlp->obs_role && mlp->obs_stride < mlp->K))
     return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: bad layout%s", "");
   if (mlp->obs_role) {
@@ -874,26 +714,15 @@ int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cy
   const int n_out_p = wide_out ? HEAD_OPL_MAX * WAVE : (((int)n_out + 63) & ~63);
   const MlpPlan pl = mlp_plan(mlp->K, mlp->n_hidden, mlp->width, n_out_p);
   const size_t lds = (size_t)pl.total * sizeof(float);
-  if (lds > 160 * 1024) return fail(h, CYGYM_EUNSUPPORTED, "cygym_actor_mlp_decode: the layer shapes do not fit in LDS%s", "");
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_actor_mlp_decode: the layer shapes do not fit in LDS%s", "");
   // widest vector the observation rows allow (base address and row stride)
   const uintptr_t al = mlp->obs_role ? 0 : ((uintptr_t)mlp->obs | ((uintptr_t)mlp->obs_stride * 4));   // (K itself may be anything <= obs_stride)
   const int vw = mlp->obs_role ? 0 : (al & 15) == 0 ? 4 : (al & 7) == 0 ? 2 : 1;   // (0: the role view built on chip)
-  const void* k = nullptr;
-#define CG_MLP_CASE(O) case O: k = vw == 0 ? (const void*)actor_mlp_kernel<O, 0> : vw == 4 ? (const void*)actor_mlp_kernel<O, 4> : vw == 2 ? (const void*)actor_mlp_kernel<O, 2> : (const void*)actor_mlp_kernel<O, 1>; break;
-  switch (wide_out ? 0 : n_out_p / WAVE) {
-    CG_MLP_CASE(0) CG_MLP_CASE(1) CG_MLP_CASE(2) CG_MLP_CASE(3) CG_MLP_CASE(4) CG_MLP_CASE(5) CG_MLP_CASE(6) CG_MLP_CASE(7)
-    default: k = vw == 0 ? (const void*)actor_mlp_kernel<8, 0> : vw == 4 ? (const void*)actor_mlp_kernel<8, 4> : vw == 2 ? (const void*)actor_mlp_kernel<8, 2> : (const void*)actor_mlp_kernel<8, 1>; break;
-  }
-#undef CG_MLP_CASE
-  {   // raise the kernel's dynamic-LDS limit once per variant and device (not per launch: this sits in a closed loop's tick)
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> raised;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!raised.count({k, h->device_id})) {
-      HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      raised.insert({k, h->device_id});
-    }
-  }
+  const void* k = kernel_by_opl<0>(wide_out ? 0 : n_out_p / WAVE, [vw](auto O) {
+    constexpr int o = decltype(O)::value;
+    return vw == 0 ? (const void*)actor_mlp_kernel<o, 0> : vw == 4 ? (const void*)actor_mlp_kernel<o, 4> : vw == 2 ? (const void*)actor_mlp_kernel<o, 2> : (const void*)actor_mlp_kernel<o, 1>;
+  });
+  if (const int rc = raise_lds_once(h, k)) return rc;
   int n_envs = h->n_envs;
   const int32_t* ienv = h->b.ienv;
   uint64_t seed = h->c.seed;
@@ -938,8 +767,9 @@ int cygym_fit_forests(const uint16_t* rows, const int64_t* row_ptr, const uint32
 
 int cygym_launch_plan(const cygym_handle* h, int32_t* out) {
   if (!h || !out) return fail(nullptr, CYGYM_EINVAL, "cygym_launch_plan: null argument%s", "");
-  out[0] = h->wpb; out[1] = h->wpb_fused; out[2] = h->wave_lds; out[3] = h->shared_lds;
-  out[4] = h->t.cby_global; out[5] = h->t.lists_global; out[6] = 0; out[7] = h->wide ? 1 : 0;
+  const LaunchPlan& p = h->plan;
+  out[0] = p.wpb; out[1] = p.wpb_fused; out[2] = p.wave_lds; out[3] = p.shared_lds;
+  out[4] = p.cby_global; out[5] = p.lists_global; out[6] = 0; out[7] = p.wide ? 1 : 0;
   return CYGYM_OK;
 }
 

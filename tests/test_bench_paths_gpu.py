@@ -305,7 +305,7 @@ def _dense_topology(M, E, seed):
 
 def test_failed_replan_keeps_the_launch_plan(monkeypatch):
     """A step whose device list does not fit in LDS fails with CYGYM_EUNSUPPORTED and must leave the handle as it was:
-    choose_launch clears the placement flags before it plans, so an untransactional failure left the old LDS sizes under
+    the planner once cleared the placement flags before it planned, so an untransactional failure left the old LDS sizes under
     new flags (comp_by back in LDS: four planes carved out of a block sized for three).  The plan is checked BEFORE any
     further launch; then the handle steps normally against the oracle.  2048 devices, 40 000 edges, no extra-edge list,
     comp_by in global memory (CYGYM_CBY_GLOBAL: at this edge count the natural plan keeps it in LDS).  Measured on the

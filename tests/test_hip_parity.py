@@ -408,7 +408,7 @@ def test_long_rows_at_a_compile_time_size_run_on_the_run_time_kernels(M):
 
 def test_lists_read_from_global_memory(monkeypatch):
     """Run-time sizes where it buys a resident wave (4096 x 2048 with its extra-edge list: 5 -> 6 per CU) leave the tick's
-    device list, the extra-edge list and the in-row bounds in global memory (choose_launch, cygym_hip.hip).  No network that
+    device list, the extra-edge list and the in-row bounds in global memory (plan_launch, csrc/cg_plan.hpp).  No network that
     fits a test picks that plan by itself: force it (CYGYM_CBY_GLOBAL + CYGYM_LISTS_GLOBAL) and run the added-edge scenarios --
     per tick with aimed block / unblock lists, and as a rollout -- against the oracle."""
     monkeypatch.setenv("CYGYM_CBY_GLOBAL", "1")
@@ -430,7 +430,7 @@ def test_lists_read_from_global_memory(monkeypatch):
 def test_every_workgroup_shape(M, wpb, monkeypatch):
     """cygym_create picks the waves-per-workgroup shape from the LDS and register budgets, so a given network only ever
     exercises one of the shapes compiled for its size class (nine at run-time sizes, five at 64 and 256 devices): force
-    each (CYGYM_WPB, the tuning hook of choose_launch) and check lean and full-feature kernels, per tick and as a
+    each (CYGYM_WPB, the tuning hook of the launch planner) and check lean and full-feature kernels, per tick and as a
     rollout, against the oracle."""
     from oracle import driver as od
     monkeypatch.setenv("CYGYM_WPB", str(wpb))

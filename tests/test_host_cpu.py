@@ -165,7 +165,7 @@ def test_tick_kernels_do_not_spill():
         # instructions), so the size alone is not a spill.
         assert r.get("vgpr_spill", 0) == 0 and r["scratch"] <= 64, (name, r)
         assert r["vgprs"] <= (132 if mt == 0 and not fused and not xe else 128), (name, r)
-        if mt and xe and not fused:       # choose_launch counts on 5 resident waves per SIMD for these
+        if mt and xe and not fused:       # plan_layout (cg_plan.hpp) counts on 5 resident waves per SIMD for these
             assert r["vgprs"] <= 102, (name, r)
         if mt == 0 and not fused:         # ... and for the per-tick kernels at run-time sizes (CG_RT_REG_CAP: the topology blob is
             assert r["vgprs"] <= 102, (name, r)   # staged by LDS-DMA, not through registers: 75-81 VGPRs)
@@ -217,6 +217,187 @@ def test_kernel_sources_carry_no_tuning_switches():
             bad += [f"{fn}:{i}: {n}" for n in names if n not in keep and not n.endswith("_HPP")]
             bad += [f"{fn}:{i}: getenv({a})" for a in re.findall(r"getenv\s*\(([^)]*)\)", line) if a.strip().strip('"') not in hooks]
     assert not bad, bad
+
+
+# The launch planner (csrc/cg_plan.hpp) is integer arithmetic over a dozen sizes: it is checked here, without a GPU, through
+# tests/plan_probe.cpp.  Each entry: the probe's input line
+#   [+] M E K max_row few_waves full_feature max_devs forced_wpb force_cby_global force_lists_global
+# ('+': a re-plan of the previous entry's handle) and its answer
+#   fits wpb wpb_fused wave_lds shared_lds lds_bytes in_lds x_bytes cby_global lists_global wide max_devs resident_waves
+# E, K and max_row of the named networks are what topology.make_topology gives for them (bench.WORKLOADS with
+# DEFAULT_MAX_EXTRA; the networks of the GPU tests named).  The expected plans were NOT written by hand and not taken from
+# cg_plan.hpp: they were recorded from the planner as it stood before it became a header (choose_launch in cygym_hip.hip, lifted
+# verbatim into a host harness), as part of a differential sweep of 322 461 inputs on which old and new planner agreed in
+# every field.
+PLAN_TABLE = [
+    # bench target/cfg3, lean, few_waves=1
+    ('256 3798 0 255 1 0 32 0 0 0', '1 16 16 7504 35296 35296 1 0 0 0 1 32 24'),
+    # bench target/cfg3, lean, few_waves=0
+    ('256 3798 0 255 0 0 32 0 0 0', '1 8 16 4432 12496 12496 1 0 0 0 0 32 24'),
+    # bench target/cfg3, full-feature, few_waves=1
+    ('256 3798 0 255 1 1 32 0 0 0', '1 4 16 4432 12496 12496 1 0 0 0 0 32 20'),
+    # bench target/cfg3, full-feature, few_waves=0
+    ('256 3798 0 255 0 1 32 0 0 0', '1 4 16 4432 12496 12496 1 0 0 0 0 32 20'),
+    # bench cfg2, lean, few_waves=1
+    ('64 306 0 63 1 0 8 0 0 0', '1 8 16 2704 1872 1872 1 0 0 0 0 8 24'),
+    # bench cfg2, lean, few_waves=0
+    ('64 306 0 63 0 0 8 0 0 0', '1 8 16 2704 1872 1872 1 0 0 0 0 8 24'),
+    # bench cfg2, full-feature, few_waves=1
+    ('64 306 0 63 1 1 8 0 0 0', '1 4 16 2704 1872 1872 1 0 0 0 0 8 20'),
+    # bench cfg2, full-feature, few_waves=0
+    ('64 306 0 63 0 1 8 0 0 0', '1 4 16 2704 1872 1872 1 0 0 0 0 8 20'),
+    # bench cfg5 without its extra-edge list, lean, few_waves=1
+    ('2048 9193 0 147 1 0 256 0 0 0', '1 5 5 24080 32768 32768 0 0 0 0 0 256 5'),
+    # bench cfg5 without its extra-edge list, lean, few_waves=0
+    ('2048 9193 0 147 0 0 256 0 0 0', '1 5 5 24080 32768 32768 0 0 0 0 0 256 5'),
+    # bench cfg5 without its extra-edge list, full-feature, few_waves=1
+    ('2048 9193 0 147 1 1 256 0 0 0', '1 5 5 24080 32768 32768 0 0 0 0 0 256 5'),
+    # bench cfg5 without its extra-edge list, full-feature, few_waves=0
+    ('2048 9193 0 147 0 1 256 0 0 0', '1 5 5 24080 32768 32768 0 0 0 0 0 256 5'),
+    # bench cfg5 (416-entry extra-edge list: lists in global memory), few_waves=1
+    ('2048 9193 416 147 1 1 256 0 0 0', '1 6 6 22032 28656 28656 0 512 1 1 0 256 6'),
+    # bench cfg5 (416-entry extra-edge list: lists in global memory), few_waves=0
+    ('2048 9193 416 147 0 1 256 0 0 0', '1 6 6 22032 28656 28656 0 512 1 1 0 256 6'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=1
+    ('100 689 0 99 1 0 12 1 0 0', '1 1 1 1696 3344 3344 1 0 0 0 0 12 20'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=2
+    ('100 689 0 99 1 0 12 2 0 0', '1 2 2 1696 3344 3344 1 0 0 0 0 12 20'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=3
+    ('100 689 0 99 1 0 12 3 0 0', '1 3 3 1696 3344 3344 1 0 0 0 0 12 18'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=4
+    ('100 689 0 99 1 0 12 4 0 0', '1 4 4 1696 3344 3344 1 0 0 0 0 12 20'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=5
+    ('100 689 0 99 1 0 12 5 0 0', '1 5 5 1696 3344 3344 1 0 0 0 0 12 20'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=6
+    ('100 689 0 99 1 0 12 6 0 0', '1 6 6 1696 3344 3344 1 0 0 0 0 12 18'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=8
+    ('100 689 0 99 1 0 12 8 0 0', '1 8 8 1696 3344 3344 1 0 0 0 0 12 16'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=12
+    ('100 689 0 99 1 0 12 12 0 0', '1 12 12 1696 3344 3344 1 0 0 0 0 12 12'),
+    # test_every_workgroup_shape M=100 K=0 CYGYM_WPB=16
+    ('100 689 0 99 1 0 12 16 0 0', '1 16 16 1696 3344 3344 1 0 0 0 0 12 16'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=1
+    ('100 689 48 99 1 1 12 1 0 0', '1 1 1 1936 3344 3344 1 240 0 0 0 12 20'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=2
+    ('100 689 48 99 1 1 12 2 0 0', '1 2 2 1936 3344 3344 1 240 0 0 0 12 20'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=3
+    ('100 689 48 99 1 1 12 3 0 0', '1 3 3 1936 3344 3344 1 240 0 0 0 12 18'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=4
+    ('100 689 48 99 1 1 12 4 0 0', '1 4 4 1936 3344 3344 1 240 0 0 0 12 20'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=5
+    ('100 689 48 99 1 1 12 5 0 0', '1 5 5 1936 3344 3344 1 240 0 0 0 12 20'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=6
+    ('100 689 48 99 1 1 12 6 0 0', '1 6 6 1936 3344 3344 1 240 0 0 0 12 18'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=8
+    ('100 689 48 99 1 1 12 8 0 0', '1 8 8 1936 3344 3344 1 240 0 0 0 12 16'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=12
+    ('100 689 48 99 1 1 12 12 0 0', '1 12 12 1936 3344 3344 1 240 0 0 0 12 12'),
+    # test_every_workgroup_shape M=100 K=48 CYGYM_WPB=16
+    ('100 689 48 99 1 1 12 16 0 0', '1 16 16 1936 3344 3344 1 240 0 0 0 12 16'),
+    # test_every_workgroup_shape M=64 K=0 CYGYM_WPB=1
+    ('64 313 0 63 1 0 12 1 0 0', '1 1 1 2720 1888 1888 1 0 0 0 0 12 20'),
+    # test_every_workgroup_shape M=64 K=0 CYGYM_WPB=2
+    ('64 313 0 63 1 0 12 2 0 0', '1 2 2 2720 1888 1888 1 0 0 0 0 12 24'),
+    # test_every_workgroup_shape M=64 K=0 CYGYM_WPB=4
+    ('64 313 0 63 1 0 12 4 0 0', '1 4 4 2720 1888 1888 1 0 0 0 0 12 24'),
+    # test_every_workgroup_shape M=64 K=0 CYGYM_WPB=8
+    ('64 313 0 63 1 0 12 8 0 0', '1 8 8 2720 1888 1888 1 0 0 0 0 12 24'),
+    # test_every_workgroup_shape M=64 K=0 CYGYM_WPB=16
+    ('64 313 0 63 1 0 12 16 0 0', '1 16 16 2720 1888 1888 1 0 0 0 0 12 16'),
+    # test_every_workgroup_shape M=64 K=48 CYGYM_WPB=1
+    ('64 313 48 63 1 1 12 1 0 0', '1 1 1 2944 1888 1888 1 224 0 0 0 12 20'),
+    # test_every_workgroup_shape M=64 K=48 CYGYM_WPB=2
+    ('64 313 48 63 1 1 12 2 0 0', '1 2 2 2944 1888 1888 1 224 0 0 0 12 20'),
+    # test_every_workgroup_shape M=64 K=48 CYGYM_WPB=4
+    ('64 313 48 63 1 1 12 4 0 0', '1 4 4 2944 1888 1888 1 224 0 0 0 12 20'),
+    # test_every_workgroup_shape M=64 K=48 CYGYM_WPB=8
+    ('64 313 48 63 1 1 12 8 0 0', '1 8 8 2944 1888 1888 1 224 0 0 0 12 16'),
+    # test_every_workgroup_shape M=64 K=48 CYGYM_WPB=16
+    ('64 313 48 63 1 1 12 16 0 0', '1 16 16 2944 1888 1888 1 224 0 0 0 12 16'),
+    # test_every_workgroup_shape M=256 K=0 CYGYM_WPB=1
+    ('256 3798 0 255 1 0 12 1 0 0', '1 1 1 4400 9424 9424 0 0 0 0 0 12 11'),
+    # test_every_workgroup_shape M=256 K=0 CYGYM_WPB=2
+    ('256 3798 0 255 1 0 12 2 0 0', '1 2 2 4400 9424 9424 0 0 0 0 0 12 16'),
+    # test_every_workgroup_shape M=256 K=0 CYGYM_WPB=4
+    ('256 3798 0 255 1 0 12 4 0 0', '1 4 4 4400 9424 9424 0 0 0 0 0 12 24'),
+    # test_every_workgroup_shape M=256 K=0 CYGYM_WPB=8
+    ('256 3798 0 255 1 0 12 8 0 0', '1 8 8 4400 12496 12496 1 0 0 0 0 12 24'),
+    # test_every_workgroup_shape M=256 K=0 CYGYM_WPB=16
+    ('256 3798 0 255 1 0 12 16 0 0', '1 16 16 4400 12496 12496 1 0 0 0 0 12 16'),
+    # test_every_workgroup_shape M=256 K=48 CYGYM_WPB=1
+    ('256 3798 48 255 1 1 12 1 0 0', '1 1 1 4672 9424 9424 0 272 0 0 0 12 11'),
+    # test_every_workgroup_shape M=256 K=48 CYGYM_WPB=2
+    ('256 3798 48 255 1 1 12 2 0 0', '1 2 2 4672 9424 9424 0 272 0 0 0 12 16'),
+    # test_every_workgroup_shape M=256 K=48 CYGYM_WPB=4
+    ('256 3798 48 255 1 1 12 4 0 0', '1 4 4 4672 12496 12496 1 272 0 0 0 12 20'),
+    # test_every_workgroup_shape M=256 K=48 CYGYM_WPB=8
+    ('256 3798 48 255 1 1 12 8 0 0', '1 8 8 4672 12496 12496 1 272 0 0 0 12 16'),
+    # test_every_workgroup_shape M=256 K=48 CYGYM_WPB=16
+    ('256 3798 48 255 1 1 12 16 0 0', '1 16 16 4672 12496 12496 1 272 0 0 0 12 16'),
+    # test_lists_read_from_global_memory: both hooks
+    ('600 1801 192 84 1 1 75 0 1 1', '1 5 5 6720 6656 6656 0 160 1 1 0 75 20'),
+    # ... comp_by hook alone
+    ('600 1801 192 84 1 1 75 0 1 0', '1 5 5 6720 6656 6656 0 160 1 1 0 75 20'),
+    # ... lists hook alone (no effect without comp_by in global memory)
+    ('600 1801 192 84 1 1 75 0 0 1', '1 5 5 6720 6656 6656 0 160 1 1 0 75 20'),
+    # ... no hook
+    ('600 1801 192 84 1 1 75 0 0 0', '1 5 5 6720 6656 6656 0 160 1 1 0 75 20'),
+    # 2048 devices, 14000 edges, no extra-edge list: comp_by in global memory buys the fifth wave
+    ('2048 14000 0 147 0 0 256 0 0 0', '1 5 5 23248 42368 42368 0 0 1 0 0 256 5'),
+    # hooks on a network that gains nothing from them: none
+    ('100 689 48 99 1 1 12 0 0 0', '1 5 5 1936 3344 3344 1 240 0 0 0 12 20'),
+    # ... comp_by hook
+    ('100 689 48 99 1 1 12 0 1 0', '1 5 5 1840 3344 3344 1 240 1 0 0 12 20'),
+    # ... both hooks
+    ('100 689 48 99 1 1 12 0 1 1', '1 5 5 1600 1936 1936 0 32 1 1 0 12 20'),
+    # 256 devices, a row of 257 slots: run-time kernels
+    ('256 3798 0 257 1 0 32 0 0 0', '1 5 5 3920 12496 12496 1 0 0 0 0 32 20'),
+    # 64 devices, a row of 65 slots: run-time kernels
+    ('64 306 0 65 1 0 8 0 0 0', '1 5 5 1040 1872 1872 1 0 0 0 0 8 20'),
+    # run-time size, M % 4 != 0
+    ('2047 9193 0 147 0 0 255 0 0 0', '1 5 5 24080 32736 32736 0 0 0 0 0 255 5'),
+    # run-time size, M % 4 != 0, comp_by hook set (not applicable)
+    ('257 3798 0 256 1 0 32 0 1 0', '1 5 5 4336 12592 12592 1 0 0 0 0 32 20'),
+    # one device
+    ('1 0 0 0 1 0 1 0 0 0', '1 5 5 736 144 144 1 0 0 0 0 1 20'),
+    # fits no layout
+    ('2048 65535 0 2047 0 0 32767 0 0 0', '0'),
+    # fits no layout (4096-entry extra-edge list, whole-network device lists)
+    ('2048 61000 4096 2047 0 1 32767 0 0 0', '0'),
+    # test_long_device_lists_replan_the_launch: created for M/8
+    ('256 3798 0 255 1 0 32 0 0 0', '1 16 16 7504 35296 35296 1 0 0 0 1 32 24'),
+    # ... re-planned for M: still WIDE
+    ('+256 3798 0 255 1 0 256 0 0 0', '1 16 16 7952 35296 35296 1 0 0 0 1 256 24'),
+    # ... with an extra-edge list: created for M/8
+    ('256 3798 48 255 1 1 32 0 0 0', '1 4 16 4704 12496 12496 1 272 0 0 0 32 20'),
+    # ... re-planned for M
+    ('+256 3798 48 255 1 1 256 0 0 0', '1 4 16 5152 9424 9424 0 272 0 0 0 256 20'),
+    # cygym_bind with detector buffers: lean plan at create
+    ('256 3798 0 255 1 0 32 0 0 0', '1 16 16 7504 35296 35296 1 0 0 0 1 32 24'),
+    # ... re-planned full-feature
+    ('+256 3798 0 255 1 1 32 0 0 0', '1 4 16 4432 12496 12496 1 0 0 0 0 32 20'),
+    # test_failed_replan_keeps_the_launch_plan: max_devs = 256 plans
+    ('2048 40000 0 2048 1 0 256 0 1 0', '1 2 2 29744 94368 94368 0 0 1 0 0 256 2'),
+    # ... max_devs = 32767 does not; the plan stays
+    ('+2048 40000 0 2048 1 0 32767 0 1 0', '0 2 2 29744 94368 94368 0 0 1 0 0 256 2'),
+]
+
+
+def test_launch_planner_without_a_gpu(tmp_path):
+    """The complete launch plan for a fixed table of inputs: the bench workloads (lean / full-feature, few_waves on / off),
+    2048 devices with and without an extra-edge list, every forced workgroup shape and both placement hooks, the fall
+    to the run-time kernels, M % 4 != 0, one device, inputs that fit no layout, and re-plans -- among them the failed
+    re-plan of test_failed_replan_keeps_the_launch_plan, after which the old plan must still be in place."""
+    import subprocess
+    exe = str(tmp_path / "plan_probe")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "cygym_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "plan_probe.cpp")])
+    out = subprocess.run([exe], input="".join(line + "\n" for line, _ in PLAN_TABLE), capture_output=True, text=True, check=True).stdout
+    got = out.splitlines()
+    assert len(got) == len(PLAN_TABLE)
+    for (line, want), have in zip(PLAN_TABLE, got):
+        print(line, "->", have)
+        assert have == want, (line, have, want)
 
 
 def _create(topo, cfg, n=4):
