@@ -30,12 +30,13 @@ struct DevTopo {
 };
 
 // The fields the tick kernel's PROLOGUE reads (env range, the pointers of every load it issues, the LDS carve-up), gathered
-// at the head of the kernel argument: four 64-byte lines instead of fifteen.  The prologue reads them through the plain
-// (not laundered) kernarg pointer, so the compiler fetches them in ONE batch of scalar loads at kernel entry; read next
-// to their uses through the laundered pointer -- which is right for the ~150 scalars of the tick body, see cg_tick_body.inc
-// -- they formed a chain of a dozen dependent scalar-cache round trips, three of them cold misses, in front of the first
-// global load (profiles/r04_*: ~3 k of the 6.7 k cycles every env spent staging).  Same member names as KParams, so that
-// env_setup() takes either.  Filled by fill_hot() on the host from the complete KParams.
+// at the head of the kernel argument: four 64-byte lines instead of fifteen.  Read next to their uses through the laundered
+// pointer -- which is right for the ~150 scalars of the tick body, see cg_tick_body.inc -- they formed a chain of a dozen
+// dependent scalar-cache round trips, three of them cold misses, in front of the first global load (profiles/r04_*: ~3 k of
+// the 6.7 k cycles every env spent staging).  The compile-time-size kernels fetch what they need of the block themselves, as
+// one batch of scalar loads in front of one wait (hot_batch, cg_tick.hpp: by offset, pinned below); the run-time-size kernels
+// read it by name through the plain (not laundered) kernarg pointer.  Same member names as KParams, so that env_setup()
+// takes either.  Filled by fill_hot() on the host from the complete KParams.
 struct KHot {
   struct {
     int M, MC, EW, K, KW, x_bytes, cby_global, multi, lds_bytes, lists_global;
@@ -47,6 +48,13 @@ struct KHot {
   struct { const int32_t *mode, *n_groups, *atype, *n_exploit, *exploit, *app, *dev_cnt; const int16_t* dev_idx; int max_groups, max_devs; } a;
   int env_begin, env_end, wave_lds, shared_lds;
 };
+
+static_assert(offsetof(KHot, t.EW) == 0x8 && offsetof(KHot, t.K) == 0xc && offsetof(KHot, t.KW) == 0x10 && offsetof(KHot, t.x_bytes) == 0x14 &&
+              offsetof(KHot, t.multi) == 0x1c && offsetof(KHot, t.lds_bytes) == 0x20 && offsetof(KHot, t.blob) == 0x28 && offsetof(KHot, t.o_dst) == 0x44 &&
+              offsetof(KHot, c) == 0x60 && offsetof(KHot, b.live) == 0x70 && offsetof(KHot, b.blocked) == 0x80 && offsetof(KHot, b.fenv) == 0xa0 &&
+              offsetof(KHot, a.mode) == 0xa8 && offsetof(KHot, a.n_exploit) == 0xc0 && offsetof(KHot, a.dev_idx) == 0xe0 &&
+              offsetof(KHot, a.max_groups) == 0xe8 && offsetof(KHot, env_begin) == 0xf0 && offsetof(KHot, shared_lds) == 0xfc && sizeof(KHot) == 0x100,
+              "KHot layout: the compile-time-size prologue fetches and unpacks it by dword (hot_batch, cg_tick.hpp)");
 
 struct KParams {
   KHot h;               // FIRST: the prologue reads it at kernarg offset 0

@@ -81,31 +81,47 @@ __device__ __forceinline__ void write_obs(const uint8_t* flags, const float* osv
 // pairs: one pair per lane and step).  (Measured and dropped for the other per-tick kernels, which would have to borrow the
 // env's 1.5 KB scratch area -- 32 pairs per step, four steps: 16384 x 256 +-0, 4096 x 64 -3 %, 4096 x 2048 -4 %: their launches are
 // longer or their observations smaller, so the end-of-launch write-back weighs less than the extra LDS passes.)
+// Each step's LDS reads are issued together, in front of one wait: the 16-byte items of the stage before the first store (the
+// stores are asm statements the compiler moves no load across: as a loop that was one LDS round trip per store), and the
+// NEXT step's flag and column reads before this step's stores as well.
+template <int PS>
 __device__ __forceinline__ void write_obs_staged(const uint8_t* flags, const float* osv, const float* ver, const float* ano,
-                                                 float* obs, int M, int lane, float4* stage, int PS) {
+                                                 float* obs, int M, int lane, float4* stage) {
+  static_assert(PS <= WAVE, "one pair per lane and step");
+  constexpr int NT = (3 * PS + WAVE - 1) / WAVE;   // 16-byte items per lane and step
   const int npairs = M >> 1;   // (M even: checked by the caller)
   const uint16_t* F2 = (const uint16_t*)flags;
   const float2* os2 = (const float2*)osv;
   const float2* ve2 = (const float2*)ver;
   const float2* an2 = (const float2*)ano;
+  uint32_t f2; float2 o, v, a;
+  auto fetch = [&](int p0) {
+    const int p = p0 + lane, pc = p < npairs ? p : npairs - 1;
+    f2 = F2[pc]; o = os2[pc]; v = ve2[pc]; a = an2[pc];
+  };
+  fetch(0);
   for (int p0 = 0; p0 < npairs; p0 += PS) {
-    for (int q = lane; q < PS; q += WAVE) {
-      const int p = p0 + q, pc = p < npairs ? p : npairs - 1;
-      const uint32_t f2 = F2[pc];
-      const float2 o = os2[pc], v = ve2[pc], a = an2[pc];
+    if (PS == WAVE || lane < PS) {
       const uint32_t fa = f2 & 0xFFu, fb = f2 >> 8;
-      stage[3 * q + 0] = make_float4(o.x, v.x, (float)(fa & 1u), a.x);
-      stage[3 * q + 1] = make_float4((float)((fa >> 2) & 1u), (float)((fa >> 4) & 1u), o.y, v.y);
-      stage[3 * q + 2] = make_float4((float)(fb & 1u), a.y, (float)((fb >> 2) & 1u), (float)((fb >> 4) & 1u));
+      stage[3 * lane + 0] = make_float4(o.x, v.x, (float)(fa & 1u), a.x);
+      stage[3 * lane + 1] = make_float4((float)((fa >> 2) & 1u), (float)((fa >> 4) & 1u), o.y, v.y);
+      stage[3 * lane + 2] = make_float4((float)(fb & 1u), a.y, (float)((fb >> 2) & 1u), (float)((fb >> 4) & 1u));
     }
     wsync();
     const int n16 = (npairs - p0 < PS ? npairs - p0 : PS) * 3;   // 16-byte items of this step
     float4* out4 = (float4*)obs + 3 * p0;
-    for (int i = lane; i < n16; i += WAVE) {
-      const float4 w = stage[i];
-      const cg_f4v wv = {w.x, w.y, w.z, w.w};
-      const uint64_t pa = (uint64_t)(out4 + i);
-      asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(pa), "v"(wv) : "memory");
+    float4 w[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) { const int i = lane + j * WAVE; w[j] = i < n16 ? stage[i] : make_float4(0.f, 0.f, 0.f, 0.f); }
+    if (p0 + PS < npairs) fetch(p0 + PS);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int i = lane + j * WAVE;
+      if (i < n16) {
+        const cg_f4v wv = {w[j].x, w[j].y, w[j].z, w[j].w};
+        const uint64_t pa = (uint64_t)(out4 + i);
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(pa), "v"(wv) : "memory");
+      }
     }
     wsync();
   }
@@ -230,6 +246,82 @@ constexpr int CG_WGP0 = 4;      // run-time sizes: words / observation pairs per
 constexpr int CG_OBS_GP0 = 4;
 constexpr int CG_WIDE_CR = 1;   // rows per cooperative step of the generic spread (attacker_spread's CR): the WIDE kernel ...
 constexpr int CG_RT_CR = 4;     // ... and the run-time-size kernels in workgroups of up to 8 waves
+
+// ---- the compile-time-size prologue's scalar batch (cg_tick_body.inc) ----
+// Which 64-byte lines of the kernel argument a common tick reads behind the hot block (lines 0..3).  Lines that hold only what
+// it never reads -- the topology's host-side views, the tails of the Poisson / triangular tables, the turbo knobs, the
+// snapshot's other planes -- are left out: fewer requests in front of the first wait.
+constexpr bool karg_line_needed(int i) {
+  const size_t lo = 64 * (size_t)i, hi = lo + 64;
+  auto hit = [&](size_t a, size_t b) constexpr { return lo < b && a < hi; };
+  return hit(offsetof(KParams, t), offsetof(KParams, t) + offsetof(DevTopo, dstatic))
+      || hit(offsetof(KParams, c), offsetof(KParams, c) + offsetof(cygym_config, poisson_thr) + 8)
+      || hit(offsetof(KParams, b), offsetof(KParams, snap) + 8)
+      || hit(offsetof(KParams, a), sizeof(KParams));
+}
+// One dword of every needed line from I on, requested (results unused) / their registers named as still in use.
+template <int I, int N>
+__device__ __forceinline__ void karg_prefetch(uint64_t kb, uint32_t* kpf) {
+  if constexpr (I < N) {
+    if constexpr (karg_line_needed(I)) asm volatile("s_load_dword %0, %1, %2" : "=&s"(kpf[I]) : "s"(kb), "n"(64 * I));
+    karg_prefetch<I + 1, N>(kb, kpf);
+  }
+}
+template <int I, int N>
+__device__ __forceinline__ void karg_prefetch_done(const uint32_t* kpf) {
+  if constexpr (I < N) {
+    if constexpr (karg_line_needed(I)) asm volatile("" :: "s"(kpf[I]));
+    karg_prefetch_done<I + 1, N>(kpf);
+  }
+}
+typedef uint32_t cg_s16v __attribute__((ext_vector_type(16)));
+typedef uint32_t cg_s2v __attribute__((ext_vector_type(2)));
+// What the compile-time-size prologue reads of the hot block (KHot, cg_params.hpp) -- bytes 0x60..0xff whole, and the six
+// fields of its first 0x60 bytes it needs (K / KW in the full-feature kernels only) -- requested together in front of ONE
+// wait, in a single asm statement: read by name the compiler split them into load / wait pairs next to their uses, most
+// of them inside single-lane regions of the gather's address code (18 full waits before the barrier).  Nothing else can
+// run in front of that wait anyway: every address of the prologue starts from env_begin.
+template <bool XE>
+__device__ __forceinline__ void hot_batch(uint64_t kb, KHot& h) {
+  typedef uint32_t s8v __attribute__((ext_vector_type(8)));
+  uint32_t ew, xb, od;
+  cg_s2v ml, bl;
+  s8v q1;
+  cg_s16v q2, q3;
+#define CG_HOT_LOADS "s_load_dword %[ew], %[kb], 0x8\n\ts_load_dword %[xb], %[kb], 0x14\n\ts_load_dwordx2 %[ml], %[kb], 0x1c\n\t" \
+                     "s_load_dwordx2 %[bl], %[kb], 0x28\n\ts_load_dword %[od], %[kb], 0x44\n\ts_load_dwordx8 %[q1], %[kb], 0x60\n\t" \
+                     "s_load_dwordx16 %[q2], %[kb], 0x80\n\ts_load_dwordx16 %[q3], %[kb], 0xc0\n\t"
+#define CG_HOT_OUTS [ew] "=&s"(ew), [xb] "=&s"(xb), [ml] "=&s"(ml), [bl] "=&s"(bl), [od] "=&s"(od), [q1] "=&s"(q1), [q2] "=&s"(q2), [q3] "=&s"(q3)
+  if constexpr (XE) {
+    cg_s2v qk;
+    asm volatile(CG_HOT_LOADS "s_load_dwordx2 %[qk], %[kb], 0xc\n\ts_waitcnt lgkmcnt(0)" : CG_HOT_OUTS, [qk] "=&s"(qk) : [kb] "s"(kb) : "memory");
+    h.t.K = (int)qk.x; h.t.KW = (int)qk.y;
+  } else {
+    asm volatile(CG_HOT_LOADS "s_waitcnt lgkmcnt(0)" : CG_HOT_OUTS : [kb] "s"(kb) : "memory");
+    h.t.K = 0; h.t.KW = 0;   // (the lean kernels carry no extra-edge code)
+  }
+#undef CG_HOT_OUTS
+#undef CG_HOT_LOADS
+  auto p64 = [](uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; };
+  // (pointers rebuilt from dwords are cast through the global address space: loaded by name from the constant-space argument
+  // they were known to be global ones, and everything derived from them must stay global_*, not flat_*)
+#define CG_GP(T, lo, hi) ((T*)(__attribute__((address_space(1))) T*)p64(lo, hi))
+  h.t.o_dst = (int)od; h.t.EW = (int)ew; h.t.x_bytes = (int)xb; h.t.multi = (int)ml.x; h.t.lds_bytes = (int)ml.y;
+  h.t.blob = CG_GP(const uint8_t, bl.x, bl.y);
+  h.c.seed = p64(q1.s0, q1.s1); h.c.env_id_base = (int64_t)p64(q1.s2, q1.s3);
+  h.b.live = CG_GP(uint8_t, q1.s4, q1.s5); h.b.stash = CG_GP(uint8_t, q1.s6, q1.s7);
+  h.b.blocked = CG_GP(uint32_t, q2.s0, q2.s1); h.b.blocked_in = CG_GP(uint32_t, q2.s2, q2.s3); h.b.ring = CG_GP(uint16_t, q2.s4, q2.s5);
+  h.b.ienv = CG_GP(int32_t, q2.s6, q2.s7); h.b.fenv = CG_GP(double, q2.s8, q2.s9);
+  h.a.mode = CG_GP(const int32_t, q2.sa, q2.sb); h.a.n_groups = CG_GP(const int32_t, q2.sc, q2.sd); h.a.atype = CG_GP(const int32_t, q2.se, q2.sf);
+  h.a.n_exploit = CG_GP(const int32_t, q3.s0, q3.s1); h.a.exploit = CG_GP(const int32_t, q3.s2, q3.s3); h.a.app = CG_GP(const int32_t, q3.s4, q3.s5);
+  h.a.dev_cnt = CG_GP(const int32_t, q3.s6, q3.s7); h.a.dev_idx = CG_GP(const int16_t, q3.s8, q3.s9);
+  h.a.max_groups = (int)q3.sa; h.a.max_devs = (int)q3.sb; h.env_begin = (int)q3.sc; h.env_end = (int)q3.sd;
+  h.wave_lds = (int)q3.se; h.shared_lds = (int)q3.sf;
+#undef CG_GP
+}
+// The hot block as the prologue sees it: the unpacked batch (compile-time sizes) or the argument itself (run-time sizes).
+template <bool CT, class A, class B>
+__device__ __forceinline__ decltype(auto) hot_sel(A& a, B& b) { if constexpr (CT) return (a); else return (b); }
 
 // FUSED: cygym_rollout (n_ticks > 1): the tick loop runs inside the launch; the single-tick instantiation has a
 // compile-time trip count of 1.

@@ -24,37 +24,26 @@
     pk = (KPT*)(((uint64_t)phi << 32) | plo);
   }
 #define P (*pk)
-  // the prologue's own fields: one batch of scalar loads at kernel entry (KHot, cg_params.hpp)
+  // the prologue's own fields (KHot, cg_params.hpp).  Compile-time sizes: every OTHER 64-byte line of the argument that a
+  // common tick reads is requested first (one dword each, results unused): the tick body reads its ~150 scalars through the
+  // laundered pointer next to their uses, and the first touch of each of the block's ~20 lines was a cold miss of the
+  // scalar cache in the middle of some phase (observation pointers, config doubles, ...: ~700 cycles each, for every wave of
+  // the batch at once).  Then the hot block itself, and one wait for all of it (hot_batch, cg_tick.hpp): scalar loads
+  // return out of order, so every wait on them is a wait for all of them.
+  // (run-time sizes read the block by name through the plain kernarg pointer: the registers of the line requests, held
+  // through the prologue, cost more there than the misses -- 4096 x 2048: +5 % without)
   using KHT = const __attribute__((address_space(4))) KHot;
   KHT* const hk = (KHT*)__builtin_amdgcn_kernarg_segment_ptr();
-#define H (*hk)
-  // ... and every OTHER 64-byte line of the argument is requested right here as well (one dword each, results unused): the
-  // tick body reads its ~150 scalars through the laundered pointer next to their uses, and the first touch of each of
-  // the block's ~20 lines was a cold miss of the scalar cache in the middle of some phase (observation pointers, config
-  // doubles, ...: ~700 cycles each, for every wave of the batch at once).  The requests are in flight together with the
-  // hot batch; their destination registers stay allocated until the prologue's loads have been waited for (scalar loads
-  // return out of order, so every wait on them is a wait for all of them).
-  // (compile-time sizes only: at run-time sizes the fifteen registers held through the prologue cost more than the misses -- 4096 x 2048: +5 % without)
-  constexpr int KARG_LINES = MT != 0 ? (int)((sizeof(KParams) + 63) / 64) : 0;
-  uint32_t kpf[KARG_LINES > 0 ? KARG_LINES : 1];
-  if constexpr (KARG_LINES > 0) {
+  KHot hp;
+  if constexpr (MT != 0) {
+    constexpr int KARG_LINES = (int)((sizeof(KParams) + 63) / 64);
     const uint64_t kb = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-    // (lines 0..3 are the hot block itself; lines that hold only what a common tick never reads -- the topology's host-side
-    // views, the tails of the Poisson / triangular tables, the turbo knobs, the snapshot's other planes -- are left out:
-    // fewer requests in front of the first wait)
-    auto karg_line_needed = [](int i) constexpr {
-      const size_t lo = 64 * (size_t)i, hi = lo + 64;
-      auto hit = [&](size_t a, size_t b) constexpr { return lo < b && a < hi; };
-      return hit(offsetof(KParams, t), offsetof(KParams, t) + offsetof(DevTopo, dstatic))
-          || hit(offsetof(KParams, c), offsetof(KParams, c) + offsetof(cygym_config, poisson_thr) + 8)
-          || hit(offsetof(KParams, b), offsetof(KParams, snap) + 8)
-          || hit(offsetof(KParams, a), sizeof(KParams));
-    };
-#pragma unroll
-    for (int i = 4; i < KARG_LINES; ++i)
-      if (karg_line_needed(i)) asm volatile("s_load_dword %0, %1, %2" : "=&s"(kpf[i]) : "s"(kb), "s"(64 * i));
-      else kpf[i] = 0;
+    uint32_t kpf[KARG_LINES];
+    karg_prefetch<4, KARG_LINES>(kb, kpf);   // (lines 0..3 are the hot block)
+    hot_batch<XE>(kb, hp);
+    karg_prefetch_done<4, KARG_LINES>(kpf);   // (their registers were reserved up to here)
   }
+#define H (hot_sel<MT != 0>(hp, *hk))
   const int M = MT ? MT : H.t.M, MC = MT ? (MT + WAVE - 1) / WAVE : H.t.MC, Mp = MC * WAVE, MS = (M + 3) & ~3;
   // (the wave id as a scalar: the per-wave LDS pointers derived from it then live in SGPRs -- 5 VGPRs less in the WIDE kernel, 14 in the rollout kernels)
   int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;   // (run-time-size rollout kernel: laundered per tick, below)
@@ -115,15 +104,44 @@
   // At the compile-time sizes the same goes for the env's own state: the [4][M] byte planes as 16-byte items, the
   // blocked-edge words and the log ring as dwords -- each a wave-instruction into this wave's LDS block.
   constexpr bool STATE_DMA = MT != 0;
-#define CG_DMA(src, dst, bytes) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), \
-                                                                 (__attribute__((address_space(3))) void*)(dst), bytes, 0, 0)
+#define CG_DMA(src, dst, bytes, off) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), \
+                                                                      (__attribute__((address_space(3))) void*)(dst), bytes, off, 0)
   // The env's 16 + 3 scalars and the seven words of its action header come back from ONE vector load -- lane l reads word l
   // of {ienv[16], fenv[3] as 6 words, mode, n_groups, atype, dev_cnt, n_exploit, app, exploit[0]} -- and the header words are
   // moved to SGPRs with v_readlane behind the barrier.  As 26 same-address loads per wave they cost the CU's one
   // texture-address unit 4 cycles each, 16 waves at once: 1.7 k of the 3.2 k cycles the prologue spent ISSUING its loads
   // (stage sub-stamps, profiles/r04_stage_substamps.txt); the first exploit id no longer waits for the header either.
   static_assert(CG_I_COUNT == 16 && CG_D_COUNT == 3, "header gather layout");
-  {
+  using GU32 = const __attribute__((address_space(1))) uint32_t;
+  using GI16 = const __attribute__((address_space(1))) int16_t;
+  [[maybe_unused]] uint64_t s_blk = 0, s_bin = 0, s_dev = 0;   // this env's rows of blocked / blocked_in / dev_idx (compile-time sizes; dead at the barrier)
+  if constexpr (MT != 0) {
+    // The addresses are formed without a branch: the bases are wave-uniform, so they are scalar arithmetic (env * max_groups
+    // once); lanes 0..21 pick ienv or fenv and add their word, and the seven header addresses are placed into lanes 22..28
+    // with v_writelane, as EnvI does for the values.  (As `if (lane == k) pa = ...` each arm was compiled into an exec-mask
+    // region of its own with the load of that array's pointer, a full wait and a fresh 64-bit product inside.)
+    const uint32_t envu = live ? (uint32_t)env : 0u;
+    const uint64_t a_i = (uint64_t)H.b.ienv + (uint64_t)envu * (CG_I_COUNT * 4);
+    const uint64_t a_f = (uint64_t)H.b.fenv + (uint64_t)envu * (CG_D_COUNT * 8) - 16 * 4;   // (lane l reads fenv word l - 16)
+    uint64_t pa = (lane < 16 ? a_i : a_f) + (uint32_t)(lane * 4);
+    if constexpr (!FUSED) {
+      const uint64_t eg = (uint64_t)envu * (uint32_t)G * 4;   // byte offset of row [env][0] in the [N][max_groups] arrays
+      uint32_t plo = (uint32_t)pa, phi = (uint32_t)(pa >> 32);
+      auto put = [&](int l, uint64_t a) {
+        plo = (uint32_t)cg_writelane((int)(uint32_t)a, l, (int)plo);
+        phi = (uint32_t)cg_writelane((int)(uint32_t)(a >> 32), l, (int)phi);
+      };
+      put(22, (uint64_t)H.a.mode + (uint64_t)envu * 4);
+      put(23, (uint64_t)H.a.n_groups + (uint64_t)envu * 4);
+      put(24, (uint64_t)H.a.atype + eg);
+      put(25, (uint64_t)H.a.dev_cnt + eg);
+      put(26, (uint64_t)H.a.n_exploit + eg);
+      put(27, (uint64_t)H.a.app + eg);
+      put(28, (uint64_t)H.a.exploit + eg * CG_MAX_EXPLOITS);
+      pa = ((uint64_t)phi << 32) | plo;
+    }
+    if (lane < (FUSED ? 22 : 29) && live) hv = *(GU32*)pa;
+  } else {
     const size_t envc = live ? (size_t)env : 0;
     const uint32_t* pa = (const uint32_t*)(H.b.ienv + envc * CG_I_COUNT) + (lane & 15);
     if (lane >= 16) pa = (const uint32_t*)(H.b.fenv + envc * CG_D_COUNT) + (lane < 22 ? lane - 16 : 0);
@@ -136,7 +154,7 @@
       if (lane == 27) pa = (const uint32_t*)(H.a.app + envc * G);
       if (lane == 28) pa = (const uint32_t*)(H.a.exploit + envc * G * CG_MAX_EXPLOITS);
     }
-    if (lane < (FUSED ? 22 : 29) && (MT == 0 || live)) hv = *pa;
+    if (lane < (FUSED ? 22 : 29)) hv = *pa;
   }
   if constexpr (MT == 0) {
     // straight-line: every load unconditional at a clamped (always valid) address, the per-lane state before the
@@ -163,26 +181,35 @@
     for (int j = 0; j < PF_BLK; ++j) asm volatile("" :: "v"(bw[j]), "v"(bwi[j]));
     asm volatile("" :: "v"(ringw), "v"((int)dv[0]));
   } else if (live) {   // (STATE_DMA)
+    // every source is "scalar base of this env's row + 4 or 16 bytes per lane"; a second 64-word chunk is the same base and LDS
+    // block with the instruction's immediate offset, which moves both ends (env * EW once)
+    const int EW = H.t.EW;
+    const uint64_t ew4 = (uint64_t)(uint32_t)env * (uint32_t)EW * 4;
+    s_blk = (uint64_t)H.b.blocked + ew4; s_bin = (uint64_t)H.b.blocked_in + ew4;
+    s_dev = (uint64_t)H.a.dev_idx + (uint64_t)(uint32_t)env * (uint32_t)L * 2;
+    static_assert(!STATE_DMA || (PF_LIVE == 1 && PF_BLK == 2), "state DMA: one item of the planes and two blocked words per lane");
+    if (lane < items) CG_DMA((const uint4*)g_live + lane, (uint4*)e.flags, 16, 0);
+    if (lane < CG_LOG_RING) CG_DMA((const uint32_t*)(H.b.ring + (size_t)env * CG_LOG_RING * 2) + lane, e.ring, 4, 0);
+    if (lane < EW) { CG_DMA((GU32*)s_blk + lane, e.blk, 4, 0); CG_DMA((GU32*)s_bin + lane, e.bin, 4, 0); }
+    if (lane + WAVE < EW) { CG_DMA((GU32*)s_blk + lane, e.blk, 4, WAVE * 4); CG_DMA((GU32*)s_bin + lane, e.bin, 4, WAVE * 4); }
 #pragma unroll
-    for (int j = 0; j < PF_LIVE; ++j) { const int i = lane + j * WAVE; if (i < items) CG_DMA((const uint4*)g_live + i, (uint4*)e.flags + j * WAVE, 16); }
-    if (lane < CG_LOG_RING) CG_DMA((const uint32_t*)(H.b.ring + (size_t)env * CG_LOG_RING * 2) + lane, e.ring, 4);
-#pragma unroll
-    for (int j = 0; j < PF_BLK; ++j) {
-      const int w = lane + j * WAVE;
-      if (w < H.t.EW) {
-        CG_DMA(H.b.blocked + (size_t)env * H.t.EW + w, e.blk + j * WAVE, 4);
-        CG_DMA(H.b.blocked_in + (size_t)env * H.t.EW + w, e.bin + j * WAVE, 4);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < PF_DEV; ++j) { int q = lane + j * WAVE; dv[j] = q < L ? H.a.dev_idx[(size_t)env * L + q] : (int16_t)0; }
+    for (int j = 0; j < PF_DEV; ++j) { int q = lane + j * WAVE; dv[j] = q < L ? ((GI16*)s_dev)[q] : (int16_t)0; }
   }
 #ifdef CG_STAMPS
   unsigned long long st_issued = 0, st_back = 0;   // stage sub-stamps, held in SGPRs and stored behind the barrier (slots 24 / 25)
   asm volatile("s_memtime %0" : "=s"(st_issued) :: "memory");
 #endif
   // ---- workgroup-shared topology blob -> LDS ----
-  {
+  if constexpr (MT != 0) {
+    // wave w copies the 1 KB pieces w, w + WPB, ...: a scalar loop over a scalar base and LDS offset, no exec mask and no
+    // per-lane 64-bit address; the last, partial piece is the only one that masks lanes
+    const int nfull = n16 >> 6, tail = n16 & 63;
+    const uint64_t bs = (uint64_t)blob_src;
+    for (int pc = wave; pc < nfull; pc += WPB)
+      CG_DMA((const __attribute__((address_space(1))) uint4*)(bs + ((uint64_t)(uint32_t)pc << 10)) + lane, smem + (pc << 10), 16, 0);
+    if (tail != 0 && wave == (int)((uint32_t)nfull % WPB) && lane < tail)
+      CG_DMA((const __attribute__((address_space(1))) uint4*)(bs + ((uint64_t)(uint32_t)nfull << 10)) + lane, smem + (nfull << 10), 16, 0);
+  } else {
     uint4* dstp = (uint4*)smem;
     for (int i0 = (threadIdx.x & ~63); i0 < n16; i0 += stride) {   // (i0: wave-uniform first item of this wave's 1 KB piece)
       const int i = i0 + (threadIdx.x & 63);
@@ -193,7 +220,17 @@
   }
 #undef KEEP4
   if (live) {
-    if constexpr (!STATE_DMA) {   // the registers the loads above filled -> LDS
+    if constexpr (STATE_DMA) {
+      // what the DMA / prefetch depth does not cover (more than 128 blocked words, more than 64 listed devices): rare, and
+      // kept rolled -- at the common sizes every wave only jumps over this code
+      const int EW = H.t.EW;
+#pragma nounroll
+      for (int w = lane + PF_BLK * WAVE; w < EW; w += WAVE) { e.blk[w] = ((GU32*)s_blk)[w]; e.bin[w] = ((GU32*)s_bin)[w]; }
+#pragma unroll
+      for (int j = 0; j < PF_DEV; ++j) { int q = lane + j * WAVE; if (q < L) e.devl[q] = dv[j]; }
+#pragma nounroll
+      for (int q = lane + PF_DEV * WAVE; q < L; q += WAVE) e.devl[q] = ((GI16*)s_dev)[q];
+    } else {   // the registers the loads above filled -> LDS
       if (vec) {
 #pragma unroll
         for (int j = 0; j < PF_LIVE; ++j) { const int i = lane + j * WAVE; if (i < items) ((uint4*)e.flags)[i] = rl[j]; }
@@ -202,25 +239,19 @@
         for (int pl = 0; pl < 4; ++pl)
           for (int i = lane; i < MS; i += WAVE) e.flags[pl * MS + i] = i < M ? g_live[pl * M + i] : (pl == 0 ? (uint8_t)CG_F_NYA : (uint8_t)0);
       }
-    }
-    const uint32_t* gb = H.b.blocked + (size_t)env * H.t.EW;
-    if constexpr (!STATE_DMA) {
+      const uint32_t* gb = H.b.blocked + (size_t)env * H.t.EW;
       if (lane < CG_LOG_RING) ((uint32_t*)e.ring)[lane] = ringw;
 #pragma unroll
       for (int j = 0; j < PF_BLK; ++j) { int w = lane + j * WAVE; if (w < H.t.EW) { e.blk[w] = bw[j]; e.bin[w] = bwi[j]; } }
-    }
-    for (int w = lane + PF_BLK * WAVE; w < H.t.EW; w += WAVE) { e.blk[w] = gb[w]; e.bin[w] = H.b.blocked_in[(size_t)env * H.t.EW + w]; }
-    const int16_t* gd = H.a.dev_idx + (size_t)env * L;
-    if (MT == 0 && H.t.lists_global) e.devl = (int16_t*)gd;   // (read where it lies: see plan_launch, cg_plan.hpp; never written through this pointer)
-    else {
+      for (int w = lane + PF_BLK * WAVE; w < H.t.EW; w += WAVE) { e.blk[w] = gb[w]; e.bin[w] = H.b.blocked_in[(size_t)env * H.t.EW + w]; }
+      const int16_t* gd = H.a.dev_idx + (size_t)env * L;
+      if (H.t.lists_global) e.devl = (int16_t*)gd;   // (read where it lies: see plan_launch, cg_plan.hpp; never written through this pointer)
+      else {
 #pragma unroll
-    for (int j = 0; j < PF_DEV; ++j) { int q = lane + j * WAVE; if (q < L) e.devl[q] = dv[j]; }
-    for (int q = lane + PF_DEV * WAVE; q < L; q += WAVE) e.devl[q] = gd[q];
+        for (int j = 0; j < PF_DEV; ++j) { int q = lane + j * WAVE; if (q < L) e.devl[q] = dv[j]; }
+        for (int q = lane + PF_DEV * WAVE; q < L; q += WAVE) e.devl[q] = gd[q];
+      }
     }
-  }
-  if constexpr (KARG_LINES > 0) {
-#pragma unroll
-    for (int i = 4; i < KARG_LINES; ++i) asm volatile("" :: "s"(kpf[i]));   // (their registers were reserved up to here)
   }
 #ifdef CG_STAMPS
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_back) :: "memory");
@@ -479,9 +510,9 @@
     if (dyn_ano) write_obs<OBS_GP>(e.flags, P.t.in_lds ? e.osv : (const float*)(P.t.blob + P.t.o_os), P.t.in_lds ? e.ver : (const float*)(P.t.blob + P.t.o_ver),
                                    P.b.anomaly + (size_t)env * M, P.o.obs + te * M * 6, M, lane, true);
     else if (WIDE && !(M & 1))   // written through, as whole lines, via LDS (cg_tick.hpp: write_obs_staged)
-      write_obs_staged(e.flags, e.osv, e.ver, e.ano, P.o.obs + te * M * 6, M, lane, e.obs_stage, WAVE);
+      write_obs_staged<WAVE>(e.flags, e.osv, e.ver, e.ano, P.o.obs + te * M * 6, M, lane, e.obs_stage);
     else if (!FUSED && !XE && MT == 64 && P.t.in_lds)   // 64 devices: the 32 pairs in one step (4096 x 64: -0.3 us of the gap)
-      write_obs_staged(e.flags, e.osv, e.ver, e.ano, P.o.obs + te * M * 6, M, lane, e.obs_stage, 32);
+      write_obs_staged<32>(e.flags, e.osv, e.ver, e.ano, P.o.obs + te * M * 6, M, lane, e.obs_stage);
     else if (P.t.in_lds) write_obs<OBS_GP>(e.flags, e.osv, e.ver, e.ano, P.o.obs + te * M * 6, M, lane);
     else write_obs<OBS_GP>(e.flags, (const float*)(P.t.blob + P.t.o_os), (const float*)(P.t.blob + P.t.o_ver),
                            (const float*)(P.t.blob + P.t.o_ano), P.o.obs + te * M * 6, M, lane);
@@ -626,6 +657,10 @@
     EP.b_live = P.b.live; EP.status = P.o.status; EP.b_ienv = P.b.ienv; EP.b_fenv = P.b.fenv;
   }
   if (vec) {
+    if constexpr (MT != 0) {   // (a compile-time trip count: the laundered lane id hides that one trip covers the block)
+#pragma unroll
+      for (int j = 0; j < PF_LIVE; ++j) { const int i = lane + j * WAVE; if (i < items_wb) ((uint4*)(EP.b_live + so))[i] = ((const uint4*)e.flags)[i]; }
+    } else
     for (int i = lane; i < items_wb; i += WAVE) ((uint4*)(EP.b_live + so))[i] = ((const uint4*)e.flags)[i];
     if (lane < tail_wb) ((uint32_t*)(EP.b_live + so))[items_wb * 4 + lane] = ((const uint32_t*)e.flags)[items_wb * 4 + lane];
   } else {
