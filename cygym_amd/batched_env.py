@@ -24,6 +24,75 @@ _BUF_DTYPES = {"live": torch.uint8, "stash": torch.uint8, "blocked": torch.int32
 _STATE_KEYS = abi.STATE_PLANES + ("blocked", "ring", "ienv", "fenv")
 _NP_VIEW = {"blocked": np.uint32, "ring": np.uint16, "extra": np.uint32, "forest": np.uint32, "hist": np.uint16}
 
+# What the action writers and observers know about a role: its code in the C ABI, its no-op action type, and how many action
+# types it has (get_num_action_types, volt_typhoon_env.py:514-520: the attacker's no-op (3) lies outside its range).
+# The width of a role's view is role_width().
+_ROLES = {"defender": dict(code=1, noop=8, n_types=14), "attacker": dict(code=2, noop=3, n_types=3)}
+_ROLE_OF_CODE = {facts["code"]: name for name, facts in _ROLES.items()}
+
+
+def _role(role: str) -> dict:
+    if role not in _ROLES:
+        raise ValueError("role must be 'attacker' or 'defender'")
+    return _ROLES[role]
+
+
+def _pad64(n: int) -> int:
+    return (int(n) + 63) // 64 * 64
+
+
+# ---- marshalling of the action writers' arguments -------------------------------------------------------------------
+# The writers hand raw pointers to kernels, so every tensor passes through here first: a malformed one is a ValueError
+# and never an out-of-bounds access on the GPU.  `env` needs N, M, device, cfg.max_exploits and status only.
+
+def _on_device(t: torch.Tensor, dtype, device, what: str) -> torch.Tensor:
+    """`t` as a contiguous `dtype` tensor on `device`: `t` itself when it already is one (no copy, no launch -- a per-tick
+    loop passes the same precomputed tensors over and over), a converted temporary otherwise.  The caller keeps what it
+    gets in a local until the library call has returned; it need not live longer, since the caching allocator reuses a
+    freed block only for work enqueued later on the same stream."""
+    if t.device != device:
+        raise ValueError(f"{what} must live on {device}, not on {t.device}")
+    return t if (t.dtype == dtype and t.is_contiguous()) else t.to(dtype).contiguous()
+
+
+def _exactly(n: int, t: torch.Tensor, dtype, device, what: str) -> torch.Tensor:
+    """_on_device for an array the kernel reads n entries of (a column of a source struct: one per source row; the type
+    map: one per action type): exactly n."""
+    if int(t.numel()) != n:
+        raise ValueError(f"{what} must hold exactly {n} entries (it has {int(t.numel())})")
+    return _on_device(t, dtype, device, what)
+
+
+def _bind_rows(env, src, rows, n: int):
+    """Set `n` and `rows` of a source struct (ActionRows, ActionVectors, DeviceTypes, DeviceLogits): `rows` = the env id
+    each of the n source rows is written to, None = source row r goes to env r.  Returns the tensor to keep alive."""
+    src.n = n
+    if rows is None:
+        if n > env.N:
+            raise ValueError(f"rows is None, so source row r goes to env r: {n} source rows, but the batch has {env.N} envs")
+        return None
+    r = _exactly(n, rows, torch.int32, env.device, "rows")
+    src.rows = r.data_ptr()
+    return r
+
+
+def _action_vectors(env, rows, n: int, n_types: int, n_exploits, n_apps: int, type_map, epsilon: float):
+    """The ActionVectors of decode_actions / actor_head_decode / actor_mlp_decode, all but `vec`: the layout of an action
+    vector (type logits | device values | exploit values | app values), the rows it is written to, the type map and the
+    epsilon-greedy threshold.  Returns (struct, width of an action vector, tensors to keep alive)."""
+    src = abi.ActionVectors()
+    src.n_types, src.n_devices, src.n_apps = int(n_types), env.M, int(n_apps)
+    src.n_exploits = env.cfg.max_exploits if n_exploits is None else int(n_exploits)
+    src.status = env.status.data_ptr()
+    if epsilon > 0.0:
+        from . import rng as R
+        src.epsilon_thr = R.bernoulli_threshold(float(epsilon))
+    keep = [_bind_rows(env, src, rows, n)]
+    if type_map is not None:
+        keep.append(_exactly(src.n_types, type_map, torch.int32, env.device, "type_map"))
+        src.type_map = keep[-1].data_ptr()
+    return src, src.n_types + src.n_devices + src.n_exploits + src.n_apps, keep
+
 
 def _alloc_state(n, M, EW, device, K=0, detector=False, anomaly=False):
     """`live` / `stash` are the [N][4][M] buffers of the ABI; flags/busy/... are VIEWS into them.
@@ -244,28 +313,34 @@ class BatchedCyberDefenseEnv:
 
     def reset(self, env_ids=None):
         """reset(from_init=True) (volt_typhoon_env.py:1904): restore the initial snapshot."""
-        if env_ids is None:
-            rc = self.lib.cygym_reset(self._h, None, None, self.N, self._stream())
-        else:
-            ids = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).contiguous()
-            rc = self.lib.cygym_reset(self._h, None, C.c_void_p(ids.data_ptr()), int(ids.numel()), self._stream())
-            torch.cuda.current_stream(self.device).synchronize()  # keep `ids` alive until consumed
+        ids, ptr, n = self._env_ids(env_ids)
+        rc = self.lib.cygym_reset(self._h, None, ptr, n, self._stream())
+        self._env_ids_done(ids)
         _lib.check(rc, self._h, "cygym_reset")
 
     def randomize(self, env_ids=None):
         """randomize_compromise_and_ownership() (volt_typhoon_env.py:330) for the given envs."""
         if self._scratch is None:   # caller-owned scratch of cygym_randomize: u32 [N][ceil(M/64)*64]
-            self._scratch = torch.empty((self.N, (self.M + 63) // 64 * 64), dtype=torch.int32, device=self.device)
+            self._scratch = torch.empty((self.N, _pad64(self.M)), dtype=torch.int32, device=self.device)
         sc = C.c_void_p(self._scratch.data_ptr())
-        if env_ids is None:
-            rc = self.lib.cygym_randomize(self._h, None, self.N, sc, self._stream())
-        else:
-            ids = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).contiguous()
-            if ids.numel() > self.N:
-                raise ValueError("more env ids than envs")
-            rc = self.lib.cygym_randomize(self._h, C.c_void_p(ids.data_ptr()), int(ids.numel()), sc, self._stream())
-            torch.cuda.current_stream(self.device).synchronize()
+        ids, ptr, n = self._env_ids(env_ids)
+        if n > self.N:
+            raise ValueError("more env ids than envs")
+        rc = self.lib.cygym_randomize(self._h, ptr, n, sc, self._stream())
+        self._env_ids_done(ids)
         _lib.check(rc, self._h, "cygym_randomize")
+
+    def _env_ids(self, env_ids):
+        """The env-id argument of a library call as (tensor, pointer, count): (None, None, N) for every env, else an
+        int32 device copy of `env_ids`; hand the tensor to _env_ids_done() after the call."""
+        if env_ids is None:
+            return None, None, self.N
+        ids = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).contiguous()
+        return ids, C.c_void_p(ids.data_ptr()), int(ids.numel())
+
+    def _env_ids_done(self, ids):
+        if ids is not None:   # made for this call alone: keep it alive until the stream has consumed it
+            torch.cuda.current_stream(self.device).synchronize()
 
     _ACT_DTYPES = {"mode": torch.int32, "n_groups": torch.int32, "atype": torch.int32, "n_exploit": torch.int32,
                    "exploit": torch.int32, "app": torch.int32, "dev_cnt": torch.int32, "dev_idx": torch.int16}
@@ -310,11 +385,13 @@ class BatchedCyberDefenseEnv:
         return a
 
     def role_width(self, role: str) -> int:
-        if role == "defender":
-            return 6 * self.M
-        if role == "attacker":
-            return 4 * self.M + self.cfg.max_exploits
-        raise ValueError("role must be 'attacker' or 'defender'")
+        """Width of the role's view of a state: [6M] for _get_defender_state, [4M + MaxExploits] for _get_attacker_state."""
+        _role(role)
+        return 6 * self.M if role == "defender" else 4 * self.M + self.cfg.max_exploits
+
+    def _out_for(self, view, full_obs, returns) -> abi.Outputs:
+        """The outputs struct of a tick: the default combination without a lookup, every other one through _outputs()."""
+        return self._out if (view is None and full_obs and not returns) else self._outputs(view, full_obs, returns)
 
     def _outputs(self, view, full_obs, returns=False) -> abi.Outputs:
         """The cygym_outputs struct for one (role view, full observation, return accumulation) combination; cached."""
@@ -357,7 +434,7 @@ class BatchedCyberDefenseEnv:
         returns=True: the tick also adds its raw reward to self.ret[:, role] for every env that has not reported done
         since reset_returns() (the `def_total` / `att_total` sums of the reference's loop), in the kernel."""
         a = self.actions_struct(act)
-        o = self._out if (view is None and full_obs and not returns) else self._outputs(view, full_obs, returns)
+        o = self._out_for(view, full_obs, returns)
         _lib.check(self.lib.cygym_step(self._h, C.byref(a), C.byref(o), self._stream()), self._h, "cygym_step")
         return self.obs, self.raw, self.shaped, self.done
 
@@ -366,44 +443,26 @@ class BatchedCyberDefenseEnv:
         of the action tensors `act` (default self.act), group 0: ONE launch (cygym_write_actions).  `a`: device
         tensors atype [n], exploit [n] (one index, -1 = none), app [n], and either dev_mask [n, M] (bool / uint8,
         compacted in the kernel to the ascending id list, first max_devs) or dev_idx [n, L] + dev_cnt [n]."""
-        act = self.act if act is None else act
         dst = self.actions_struct(act)
-        i32 = lambda t: t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous()  # noqa: E731
-        keep = [i32(a["atype"]), i32(a["exploit"]), i32(a["app"])]
-        n = int(keep[0].shape[0])
+        n = int(a["atype"].shape[0])
         src = abi.ActionRows()
+        keep = [_exactly(n, a[k], torch.int32, self.device, k) for k in ("atype", "exploit", "app")]
         src.atype, src.exploit, src.app = (t.data_ptr() for t in keep)
-        if rows is not None:
-            r = i32(rows)
-            if int(r.shape[0]) != n:
-                raise ValueError("rows and action tensors differ in length")
-            keep.append(r)
-            src.rows = r.data_ptr()
-        elif n > self.N:
-            raise ValueError("more action rows than envs")
+        keep.append(_bind_rows(self, src, rows, n))
         if "dev_mask" in a:
             m = a["dev_mask"]
-            if m.dtype not in (torch.bool, torch.uint8):
-                m = m != 0
-            m = m.contiguous()
             if tuple(m.shape) != (n, self.M):
                 raise ValueError(f"dev_mask must have shape {(n, self.M)}")
-            keep.append(m)
+            m = m if m.dtype in (torch.bool, torch.uint8) else m != 0
+            m = _on_device(m, m.dtype, self.device, "dev_mask")
             src.dev_mask = m.data_ptr()
         else:
-            di = a["dev_idx"]
-            di = di if (di.dtype == torch.int16 and di.is_contiguous()) else di.to(torch.int16).contiguous()
-            if tuple(di.shape) != (n, dst.max_devs):
+            if tuple(a["dev_idx"].shape) != (n, dst.max_devs):
                 raise ValueError(f"dev_idx must have shape {(n, dst.max_devs)}")
-            dc = i32(a["dev_cnt"])
-            keep += [di, dc]
+            di = _on_device(a["dev_idx"], torch.int16, self.device, "dev_idx")
+            dc = _exactly(n, a["dev_cnt"], torch.int32, self.device, "dev_cnt")
             src.dev_idx, src.dev_cnt = di.data_ptr(), dc.data_ptr()
-        for t in keep:
-            if t.device != self.device:
-                raise ValueError("action rows must live on the batch's device")
-        src.n = n
         _lib.check(self.lib.cygym_write_actions(self._h, C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_write_actions")
-        # (`keep` may die here: the caching allocator only reuses the blocks for work enqueued later on this stream)
 
     def decode_actions(self, rows, vec: torch.Tensor, n_types: int, n_exploits: int | None = None, n_apps: int = 0,
                        type_map: torch.Tensor | None = None, act=None, epsilon: float = 0.0):
@@ -415,36 +474,13 @@ class BatchedCyberDefenseEnv:
         max_devs ids and raises abi.DECODE_TRUNCATED in the batch's status word.  epsilon > 0: with that probability
         an env's action type is uniformly random instead (the reference's epsilon-greedy, do_agent.py:972-973; the draw
         is addressed by the env's current rng tick, site CG_SITE_EPS_TYPE)."""
-        act = self.act if act is None else act
         dst = self.actions_struct(act)
         if vec.dtype != torch.float32 or vec.dim() != 2 or vec.device != self.device or vec.stride(1) != 1:
             raise ValueError("vec must be a [n, width] float32 tensor on the batch's device with unit inner stride")
-        n_exploits = self.cfg.max_exploits if n_exploits is None else int(n_exploits)
-        n = int(vec.shape[0])
-        if int(vec.shape[1]) < n_types + self.M + n_exploits + n_apps:
+        src, n_out, keep = _action_vectors(self, rows, int(vec.shape[0]), n_types, n_exploits, n_apps, type_map, epsilon)
+        if int(vec.shape[1]) < n_out:
             raise ValueError("vec rows are narrower than n_types + n_devices + n_exploits + n_apps")
-        src = abi.ActionVectors()
         src.vec, src.stride = vec.data_ptr(), int(vec.stride(0))
-        src.n_types, src.n_devices, src.n_exploits, src.n_apps, src.n = int(n_types), self.M, n_exploits, int(n_apps), n
-        src.status = self.status.data_ptr()
-        if epsilon > 0.0:
-            from . import rng as R
-            src.epsilon_thr = R.bernoulli_threshold(float(epsilon))
-        keep = [vec]
-        if rows is not None:
-            r = rows if (rows.dtype == torch.int32 and rows.is_contiguous()) else rows.to(torch.int32).contiguous()
-            if int(r.shape[0]) != n or r.device != self.device:
-                raise ValueError("rows must be a device tensor as long as vec")
-            keep.append(r)
-            src.rows = r.data_ptr()
-        elif n > self.N:
-            raise ValueError("more action rows than envs")
-        if type_map is not None:
-            tm = type_map if (type_map.dtype == torch.int32 and type_map.is_contiguous()) else type_map.to(torch.int32).contiguous()
-            if int(tm.numel()) != int(n_types) or tm.device != self.device:
-                raise ValueError("type_map must hold n_types int32 entries on the batch's device")
-            keep.append(tm)
-            src.type_map = tm.data_ptr()
         _lib.check(self.lib.cygym_decode_actions(self._h, C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_decode_actions")
 
     def actor_head_decode(self, rows, hidden: torch.Tensor, weight_t: torch.Tensor, bias, n_types: int,
@@ -455,49 +491,25 @@ class BatchedCyberDefenseEnv:
         -- the [n, n_out] vectors never reach HBM.  Limits: H <= 256, n_out = n_types + M + n_exploits + n_apps <= 512.
         n_groups = S > 1: a population of S same-shaped actors in one launch -- row r is multiplied with the matrix of actor
         r // (n / S); weight_t [S, H, pitch], bias [S, n_out], n / S a multiple of 16."""
-        act = self.act if act is None else act
         dst = self.actions_struct(act)
-        n_exploits = self.cfg.max_exploits if n_exploits is None else int(n_exploits)
-        n_out = int(n_types) + self.M + n_exploits + int(n_apps)
-        H = int(hidden.shape[1])
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
         if not ok(hidden) or hidden.dim() != 2 or hidden.stride(1) != 1:
             raise ValueError("hidden must be a [n, H] float32 tensor on the batch's device with unit inner stride")
-        pitch = (n_out + 63) // 64 * 64
+        n, H = int(hidden.shape[0]), int(hidden.shape[1])
+        src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, epsilon)
+        pitch = _pad64(n_out)
         S_ = int(n_groups)
         wshape, bshape = ((H, pitch), (n_out,)) if S_ <= 1 else ((S_, H, pitch), (S_, n_out))
         if not ok(weight_t) or tuple(weight_t.shape) != wshape or not weight_t.is_contiguous():
             raise ValueError(f"weight_t must be a contiguous float32 {list(wshape)} tensor (see head_weights())")
         if bias is not None and (not ok(bias) or tuple(bias.shape) != bshape or not bias.is_contiguous()):
             raise ValueError(f"bias must be a contiguous float32 {list(bshape)} tensor")
-        n = int(hidden.shape[0])
         if S_ > 1 and (n % S_ or (n // S_) % 16):
             raise ValueError("a population launch needs the same number of rows per actor, a multiple of 16")
         hd = abi.ActorHead()
         hd.hidden, hd.weight_t, hd.bias = hidden.data_ptr(), weight_t.data_ptr(), (bias.data_ptr() if bias is not None else None)
         hd.H, hd.hidden_stride, hd.tanh_out, hd.weight_pitch = H, int(hidden.stride(0)), int(bool(tanh)), pitch
         hd.n_groups, hd.rows_per_group = (S_, n // S_) if S_ > 1 else (1, 0)
-        src = abi.ActionVectors()
-        src.n_types, src.n_devices, src.n_exploits, src.n_apps, src.n = int(n_types), self.M, n_exploits, int(n_apps), n
-        src.status = self.status.data_ptr()
-        if epsilon > 0.0:
-            from . import rng as R
-            src.epsilon_thr = R.bernoulli_threshold(float(epsilon))
-        keep = [hidden]
-        if rows is not None:
-            r = rows if (rows.dtype == torch.int32 and rows.is_contiguous()) else rows.to(torch.int32).contiguous()
-            if int(r.shape[0]) != n or r.device != self.device:
-                raise ValueError("rows must be a device tensor as long as hidden")
-            keep.append(r)
-            src.rows = r.data_ptr()
-        elif n > self.N:
-            raise ValueError("more action rows than envs")
-        if type_map is not None:
-            tm = type_map if (type_map.dtype == torch.int32 and type_map.is_contiguous()) else type_map.to(torch.int32).contiguous()
-            if int(tm.numel()) != int(n_types) or tm.device != self.device:
-                raise ValueError("type_map must hold n_types int32 entries on the batch's device")
-            keep.append(tm)
-            src.type_map = tm.data_ptr()
         _lib.check(self.lib.cygym_actor_head_decode(self._h, C.byref(hd), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_actor_head_decode")
 
@@ -505,7 +517,7 @@ class BatchedCyberDefenseEnv:
     def head_weights(weight: torch.Tensor) -> torch.Tensor:
         """nn.Linear.weight [n_out, H] -> the k-major, row-padded copy actor_head_decode reads: [H, n_out rounded up to 64]."""
         n_out, H = weight.shape
-        out = torch.zeros((H, (n_out + 63) // 64 * 64), dtype=torch.float32, device=weight.device)
+        out = torch.zeros((H, _pad64(n_out)), dtype=torch.float32, device=weight.device)
         out[:, :n_out] = weight.detach().t()
         return out
 
@@ -539,27 +551,28 @@ class BatchedCyberDefenseEnv:
         the grid layouts of rollout_grid in env order are (nA * n_mc, nD) for the defender and (n_mc, nA) for the attacker.
         step = {"act": tensors of the tick to run FIRST, "view", "full_obs", "returns" as in step()}: cygym_step_actor -- the
         tick and this actor (on the state the tick leaves behind) as ONE launch; needs can_step_actor(...)."""
-        act = self.act if act is None else act
         dst = self.actions_struct(act)
-        n_exploits = self.cfg.max_exploits if n_exploits is None else int(n_exploits)
-        n_out = int(n_types) + self.M + n_exploits + int(n_apps)
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
         if not 1 <= len(hidden_layers) <= abi.MLP_MAX_HIDDEN:
             raise ValueError(f"1 to {abi.MLP_MAX_HIDDEN} hidden layers")
         S_ = max(1, int(n_groups))
         ml = abi.ActorMlp()
         if obs_role is not None:
-            if obs_role not in ("defender", "attacker") or self.M % 2:
+            if obs_role not in _ROLES or self.M % 2:
                 raise ValueError("obs_role is 'defender' or 'attacker', on batches with an even device count")
             K = self.role_width(obs_role)
-            ml.obs, ml.obs_stride, ml.K, ml.obs_role = None, K, K, (1 if obs_role == "defender" else 2)
+            ml.obs, ml.obs_stride, ml.K, ml.obs_role = None, K, K, _role(obs_role)["code"]
             obs_by_env = True
         else:
             if not ok(obs) or obs.dim() != 2 or obs.stride(1) != 1:
                 raise ValueError("obs must be a [n, K] float32 tensor on the batch's device with unit inner stride")
             K = int(obs.shape[1])
             ml.obs, ml.obs_stride, ml.K = obs.data_ptr(), int(obs.stride(0)), K
+            if obs_by_env and int(obs.shape[0]) < self.N:
+                raise ValueError("obs_by_env needs the batch's [N, K] role view")
         ml.n_hidden, ml.tanh_out, ml.obs_by_env = len(hidden_layers), int(bool(tanh)), int(bool(obs_by_env))
+        n = int(rows.shape[0]) if (obs_by_env and rows is not None) else (self.N if obs_role is not None else int(obs.shape[0]))
+        src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, epsilon)
         kin = (K + 15) // 16
         for l, (w, b, width) in enumerate(hidden_layers):
             width = int(width)
@@ -572,44 +585,19 @@ class BatchedCyberDefenseEnv:
             ml.w[l], ml.b[l], ml.width[l] = w.data_ptr(), (b.data_ptr() if b is not None else None), width
             kin = width // 16
         wh, bh = head
-        n_out_p = (n_out + 63) // 64 * 64
+        n_out_p = _pad64(n_out)
         if not ok(wh) or not wh.is_contiguous() or wh.numel() != S_ * (n_out_p // 16) * kin * 256:
             raise ValueError("head: packed weights have the wrong size (pack_linear(weight, 64))")
         if bh is not None and (not ok(bh) or not bh.is_contiguous() or bh.numel() != S_ * n_out):
             raise ValueError(f"head: bias must hold {S_ * n_out} float32 values")
         ml.w_head, ml.b_head = wh.data_ptr(), (bh.data_ptr() if bh is not None else None)
-        n = int(rows.shape[0]) if (obs_by_env and rows is not None) else (self.N if obs_role is not None else int(obs.shape[0]))
         rpg = (n // S_ if rows_per_group is None else int(rows_per_group)) if S_ > 1 else 0
         if S_ > 1 and (rpg < 16 or rpg % 16 or (rows_per_group is None and n % S_)):
             raise ValueError("a population launch needs the same number of rows per actor, a multiple of 16")
         ml.n_groups, ml.rows_per_group = (S_, rpg) if S_ > 1 else (1, 0)
-        src = abi.ActionVectors()
-        src.n_types, src.n_devices, src.n_exploits, src.n_apps, src.n = int(n_types), self.M, n_exploits, int(n_apps), n
-        src.status = self.status.data_ptr()
-        if epsilon > 0.0:
-            from . import rng as R
-            src.epsilon_thr = R.bernoulli_threshold(float(epsilon))
-        keep = [obs]
-        if rows is not None:
-            r = rows if (rows.dtype == torch.int32 and rows.is_contiguous()) else rows.to(torch.int32).contiguous()
-            if int(r.shape[0]) != n or r.device != self.device:
-                raise ValueError("rows must be a device tensor with one entry per source row")
-            keep.append(r)
-            src.rows = r.data_ptr()
-        elif n > self.N:
-            raise ValueError("more action rows than envs")
-        if obs_role is None and obs_by_env and int(obs.shape[0]) < self.N:
-            raise ValueError("obs_by_env needs the batch's [N, K] role view")
-        if type_map is not None:
-            tm = type_map if (type_map.dtype == torch.int32 and type_map.is_contiguous()) else type_map.to(torch.int32).contiguous()
-            if int(tm.numel()) != int(n_types) or tm.device != self.device:
-                raise ValueError("type_map must hold n_types int32 entries on the batch's device")
-            keep.append(tm)
-            src.type_map = tm.data_ptr()
         if step is not None:
             a = self.actions_struct(step.get("act"))
-            view, full_obs, returns = step.get("view"), bool(step.get("full_obs", False)), bool(step.get("returns", False))
-            o = self._out if (view is None and full_obs and not returns) else self._outputs(view, full_obs, returns)
+            o = self._out_for(step.get("view"), bool(step.get("full_obs", False)), bool(step.get("returns", False)))
             _lib.check(self.lib.cygym_step_actor(self._h, C.byref(a), C.byref(o), C.byref(ml), C.byref(src), C.byref(dst), self._stream()),
                        self._h, "cygym_step_actor")
             return
@@ -623,6 +611,15 @@ class BatchedCyberDefenseEnv:
         return (self.M == 256 and not getattr(self, "detector", False) and not self.slow_scan and int(self.topo.max_extra) == 0
                 and self.N % 16 == 0 and self.N <= 16 * cus and 257 <= int(n_out) <= 384)
 
+    def _group_rule(self, src, role, noop, single_types) -> dict:
+        """The grouping rule of a DeviceTypes / DeviceLogits: role code, the type that forms no group (default: the role's
+        no-op), the types that pick a single device, the status word.  Returns the role's entry of _ROLES."""
+        facts = _role(role)
+        src.role, src.noop = facts["code"], (facts["noop"] if noop is None else int(noop))
+        src.single_mask = sum(1 << int(t) for t in single_types if 0 <= int(t) < 32)
+        src.status = self.status.data_ptr()
+        return facts
+
     def group_actions(self, rows, types: torch.Tensor, exploit=None, app=None, role: str = "defender", n_types: int | None = None,
                       noop: int | None = None, single_types=(11, 12), visible: torch.Tensor | None = None, act=None):
         """The grouping of per-device decisions into `env.step(groups)` (IPPO.py:560-572 / MAPPO.py) for a batch, ONE launch
@@ -633,42 +630,26 @@ class BatchedCyberDefenseEnv:
         `visible` [n, M] overrides the role's visibility mask (build_visibility_mask, IPPO.py:74-96), which the kernel
         otherwise reads off the flag plane.  Writes n_groups and the groups of rows `rows` of `act`; needs max_groups >=
         the number of groups a row can have and max_devs >= M (else the row is cut and abi.DECODE_TRUNCATED raised)."""
-        act = self.act if act is None else act
         dst = self.actions_struct(act)
-        if role not in ("defender", "attacker"):
-            raise ValueError("role must be 'attacker' or 'defender'")
-        n_types = (14 if role == "defender" else 3) if n_types is None else int(n_types)   # get_num_action_types (volt_typhoon_env.py:514-520): the attacker's no-op (3) lies outside its range
-        noop = (8 if role == "defender" else 3) if noop is None else int(noop)
-        if types.dim() != 2 or int(types.shape[1]) != self.M or types.device != self.device:
-            raise ValueError("types must be an [n, M] integer tensor on the batch's device")
-        t8 = types if (types.dtype == torch.uint8 and types.is_contiguous()) else types.to(torch.uint8).contiguous()
-        n = int(t8.shape[0])
         src = abi.DeviceTypes()
-        src.types, src.n, src.n_types, src.noop, src.role = t8.data_ptr(), n, n_types, noop, (1 if role == "defender" else 2)
-        src.single_mask = sum(1 << int(t) for t in single_types if 0 <= int(t) < 32)
-        src.status = self.status.data_ptr()
-        keep = [t8]
-
-        def i32(x, what):
-            x = x if (x.dtype == torch.int32 and x.is_contiguous()) else x.to(torch.int32).contiguous()
-            if int(x.numel()) != n or x.device != self.device:
-                raise ValueError(f"{what} must hold one entry per row on the batch's device")
-            keep.append(x)
-            return x.data_ptr()
-
-        if rows is not None:
-            src.rows = i32(rows, "rows")
-        elif n > self.N:
-            raise ValueError("more rows than envs")
-        if exploit is not None:
-            src.exploit = i32(exploit, "exploit")
-        if app is not None:
-            src.app = i32(app, "app")
+        facts = self._group_rule(src, role, noop, single_types)
+        src.n_types = facts["n_types"] if n_types is None else int(n_types)
+        if types.dim() != 2 or int(types.shape[1]) != self.M:
+            raise ValueError(f"types must be an [n, {self.M}] integer tensor")
+        t8 = _on_device(types, torch.uint8, self.device, "types")
+        n = int(t8.shape[0])
+        src.types = t8.data_ptr()
+        keep = [t8, _bind_rows(self, src, rows, n)]
+        for name, t in (("exploit", exploit), ("app", app)):
+            if t is not None:
+                keep.append(_exactly(n, t, torch.int32, self.device, name))
+                setattr(src, name, keep[-1].data_ptr())
         if visible is not None:
-            v8 = visible if (visible.dtype == torch.uint8 and visible.is_contiguous()) else (visible != 0).to(torch.uint8).contiguous()
-            if tuple(v8.shape) != (n, self.M) or v8.device != self.device:
-                raise ValueError("visible must be [n, M] on the batch's device")
-            keep.append(v8)
+            if tuple(visible.shape) != (n, self.M):
+                raise ValueError(f"visible must have shape {(n, self.M)}")
+            if not (visible.dtype == torch.uint8 and visible.is_contiguous()):
+                visible = visible != 0
+            v8 = _on_device(visible, torch.uint8, self.device, "visible")
             src.visible = v8.data_ptr()
         _lib.check(self.lib.cygym_group_actions(self._h, C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_group_actions")
 
@@ -680,25 +661,19 @@ class BatchedCyberDefenseEnv:
         log-probabilities, and the groups written into rows `rows` of `act` like group_actions.  Samples walk the inverse CDF
         with addressed Philox draws (env, rng tick, CG_SITE_SAMPLE, device / head); greedy=True takes the arg-max instead.
         Returns (types [n, M] uint8 -- 0 where invisible --, exploit [n] int32, app [n] int32, logp [n] float32)."""
-        act = self.act if act is None else act
         dst = self.actions_struct(act)
-        if role not in ("defender", "attacker"):
-            raise ValueError("role must be 'attacker' or 'defender'")
+        src = abi.DeviceLogits()
+        self._group_rule(src, role, noop, single_types)
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()  # noqa: E731
         if not ok(logits) or logits.dim() != 3 or int(logits.shape[1]) != self.M or not 1 <= int(logits.shape[2]) <= 32:
             raise ValueError("logits must be a contiguous [n, M, K <= 32] float32 tensor on the batch's device")
         n, K = int(logits.shape[0]), int(logits.shape[2])
-        src = abi.DeviceLogits()
         types = torch.empty((n, self.M), dtype=torch.uint8, device=self.device)
         exp_o = torch.empty((n,), dtype=torch.int32, device=self.device)
         app_o = torch.empty((n,), dtype=torch.int32, device=self.device)
         logp = torch.empty((n,), dtype=torch.float32, device=self.device)
         src.logits, src.types_out, src.exp_out, src.app_out, src.logp_out = logits.data_ptr(), types.data_ptr(), exp_o.data_ptr(), app_o.data_ptr(), logp.data_ptr()
-        src.n, src.n_types, src.role, src.greedy = n, K, (1 if role == "defender" else 2), int(bool(greedy))
-        src.noop = (8 if role == "defender" else 3) if noop is None else int(noop)
-        src.single_mask = sum(1 << int(t) for t in single_types if 0 <= int(t) < 32)
-        src.status = self.status.data_ptr()
-        keep = [logits]
+        src.n_types, src.greedy = K, int(bool(greedy))
         for name, t in (("exp", exp_logits), ("app", app_logits)):
             if t is None or int(t.shape[-1]) == 0:
                 continue
@@ -706,15 +681,7 @@ class BatchedCyberDefenseEnv:
                 raise ValueError(f"{name}_logits must be a contiguous [n, <= 32] float32 tensor on the batch's device")
             setattr(src, name + "_logits", t.data_ptr())
             setattr(src, "n_" + name, int(t.shape[1]))
-            keep.append(t)
-        if rows is not None:
-            r = rows if (rows.dtype == torch.int32 and rows.is_contiguous()) else rows.to(torch.int32).contiguous()
-            if int(r.numel()) != n or r.device != self.device:
-                raise ValueError("rows must hold one env id per row on the batch's device")
-            keep.append(r)
-            src.rows = r.data_ptr()
-        elif n > self.N:
-            raise ValueError("more rows than envs")
+        r = _bind_rows(self, src, rows, n)   # noqa: F841 (alive until the call has returned)
         _lib.check(self.lib.cygym_sample_group_actions(self._h, C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_sample_group_actions")
         return types, exp_o, app_o, logp
 
@@ -730,7 +697,7 @@ class BatchedCyberDefenseEnv:
         """Fill self.role_obs[role] with the role's view of the CURRENT state (one cygym_observe launch): the first
         observation of a closed loop; every later one is written by step(view=...) itself."""
         self._outputs(role, False)
-        self.role_obs[role].copy_(self.observe(1 if role == "defender" else 2))
+        self.role_obs[role].copy_(self.observe(_role(role)["code"]))
         return self.role_obs[role]
 
     def step_range(self, begin: int, n: int, act=None, view: str | None = None, full_obs: bool = True, returns: bool = False):
@@ -739,7 +706,7 @@ class BatchedCyberDefenseEnv:
         sub-batch on its own stream, so that its policy evaluation and the tail of its slowest env overlap the other
         sub-batches' ticks (see bench.py, leg `per_tick_stepping`)."""
         a = self.actions_struct(act)
-        o = self._out if (view is None and full_obs and not returns) else self._outputs(view, full_obs, returns)
+        o = self._out_for(view, full_obs, returns)
         _lib.check(self.lib.cygym_step_range(self._h, int(begin), int(n), C.byref(a), C.byref(o), self._stream()),
                    self._h, "cygym_step_range")
         return self.obs, self.raw, self.shaped, self.done
@@ -750,13 +717,24 @@ class BatchedCyberDefenseEnv:
         CG_E_DET_PENDING.  `words`: u32 [FOREST_WORDS] from detector.fit_forest / flatten_forest."""
         if not self.detector:
             raise _lib.CygymError("this batch was created without detector=True")
-        w = torch.from_numpy(np.ascontiguousarray(np.asarray(words, np.uint32)).view(np.int32)).to(self.device)
-        f = self.state["forest"][env]
-        f[0:3] = w[0:3]
-        f[5] = f[3]
-        f[7] = w[7]
-        f[S.FOREST_HDR:] = w[S.FOREST_HDR:]
-        self.state["ienv"][env, S.I_FLAGS] &= ~S.E_DET_PENDING
+        env = int(env)
+        if not -self.N <= env < self.N:   # (the id becomes a device index tensor, whose values nobody checks)
+            raise IndexError(f"env {env} is out of range for a batch of {self.N} envs")
+        self._install_forests(torch.tensor([env % self.N], device=self.device), np.asarray(words, np.uint32)[None])
+
+    def _install_forests(self, ids: torch.Tensor, words):
+        """Install the fitted forests `words` (u32 [n, FOREST_WORDS]) of the envs `ids` (int64 device tensor [n]) and
+        clear their CG_E_DET_PENDING.  Header words 0..2 and 7 and everything from FOREST_HDR on come from the fit;
+        the request the tick recorded stays (words 3, 4, 6), and word 5 takes the request tick recorded in word 3."""
+        w = torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(self.device)
+        st = self.state
+        cur = st["forest"][ids]                      # [n, FOREST_WORDS]
+        cur[:, 0:3] = w[:, 0:3]
+        cur[:, 5] = cur[:, 3]
+        cur[:, 7] = w[:, 7]
+        cur[:, S.FOREST_HDR:] = w[:, S.FOREST_HDR:]
+        st["forest"][ids] = cur
+        st["ienv"][ids, S.I_FLAGS] &= ~S.E_DET_PENDING
 
     def pending_detectors(self, env_ids=None) -> torch.Tensor:
         """Env ids (int64 device tensor, ascending) whose Detector.train request is still unanswered
@@ -804,15 +782,7 @@ class BatchedCyberDefenseEnv:
              for j in range(n)],
             [D.fit_seed(cfg.seed, cfg.env_id_base + int(ids[j]), int(req_tick[j])) for j in range(n)],
             [int(v) for v in n_fits])
-        w = torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(self.device)
-        f = st["forest"]
-        cur = f[pend]                                # [n, FOREST_WORDS]: keep the request the tick recorded (words 3, 4, 6)
-        cur[:, 0:3] = w[:, 0:3]
-        cur[:, 5] = cur[:, 3]
-        cur[:, 7] = w[:, 7]
-        cur[:, S.FOREST_HDR:] = w[:, S.FOREST_HDR:]
-        f[pend] = cur
-        st["ienv"][pend, S.I_FLAGS] &= ~S.E_DET_PENDING
+        self._install_forests(pend, words)
         return n
 
     def unpinned_envs(self) -> int:
@@ -858,7 +828,7 @@ class BatchedCyberDefenseEnv:
         T = int(act["mode"].shape[0])
         G, L = self._check_actions(act, (T, self.N))
         odt = {"obs": (torch.float32, (self.M, 6)), "raw": (torch.float64, ()), "shaped": (torch.float64, ()), "done": (torch.uint8, ()),
-               "obs_def": (torch.float32, (6 * self.M,)), "obs_att": (torch.float32, (4 * self.M + self.cfg.max_exploits,))}
+               "obs_def": (torch.float32, (self.role_width("defender"),)), "obs_att": (torch.float32, (self.role_width("attacker"),))}
         optional = ("obs", "obs_def", "obs_att")
         for k, (dt, tail) in odt.items():
             t = out.get(k)
@@ -914,7 +884,7 @@ class BatchedCyberDefenseEnv:
 
     def observe(self, role: int) -> torch.Tensor:
         """role 0: _get_state, 1: _get_defender_state, 2: _get_attacker_state (CyberDefenseEnv.py:146-257)."""
-        width = 6 * self.M if role in (0, 1) else 4 * self.M + self.cfg.max_exploits
+        width = self.role_width(_ROLE_OF_CODE.get(role, "defender"))   # (role 0, _get_state, is as wide as the defender's view)
         out = torch.empty((self.N, width), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.cygym_observe(self._h, int(role), C.c_void_p(out.data_ptr()), self._stream()),
                    self._h, "cygym_observe")
@@ -925,13 +895,8 @@ class BatchedCyberDefenseEnv:
         [N, M] float32, 1 where the device is visible to the role -- attacker: Known_to_attacker and attacker_owned and
         not Not_yet_added; defender: attacker_owned and not Not_yet_added.  Pure tensor ops on the flag plane (no
         launch of this library, no host round trip), for closed-loop policies that mask their per-device heads."""
+        want = S.F_OWNED if _role(role) is _ROLES["defender"] else S.F_KNOWN | S.F_OWNED
         f = self.state["flags"]
-        if role == "attacker":
-            want = S.F_KNOWN | S.F_OWNED
-        elif role == "defender":
-            want = S.F_OWNED
-        else:
-            raise ValueError("role must be 'attacker' or 'defender'")
         return ((f & (want | S.F_NYA)) == want).to(torch.float32)
 
     def launch_plan(self) -> dict:

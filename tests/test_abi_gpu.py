@@ -147,6 +147,71 @@ def test_malformed_action_tensors_are_python_errors():
         env.rollout({**act, "n_groups": act["n_groups"][:2].contiguous()}, out)
     with pytest.raises(ValueError):
         env.rollout(act, {**out, "obs": out["obs"][:, :4].contiguous()})
+
+    # the six action writers: one well-formed call each, then malformed source tensors -- every one a ValueError on the host
+    dev, N, M, X, L = "cuda:0", env.N, env.M, env.cfg.max_exploits, env.L
+    n_types, n_apps, H, KL = 4, 2, 16, 14
+    n_out, K = n_types + M + X + n_apps, 6 * M
+    g = torch.Generator().manual_seed(5)
+    rnd = lambda *shape: torch.randn(shape, generator=g).to(dev)  # noqa: E731
+    ints = lambda hi, *shape: torch.randint(0, hi, shape, generator=g).to(dev, torch.int32)  # noqa: E731
+    ids = torch.tensor([0, 2, 3, 5, 6, 7], dtype=torch.int32, device=dev)
+    tm = torch.tensor([1, 4, 8, 13], dtype=torch.int32, device=dev)
+    W1, b1, Wh, bh = rnd(H, K), rnd(H), rnd(n_out, H), rnd(n_out)
+    hidden, head = [(env.pack_linear(W1), b1, H)], (env.pack_linear(Wh, 64), bh)
+    wt = env.head_weights(Wh)
+
+    def rejected(match, call, *args, **kw):   # `match`: the argument the message has to name
+        with pytest.raises(ValueError, match=match):
+            call(*args, **kw)
+
+    writers = {   # name -> call(rows, n source rows, overrides of single arguments)
+        "write_actions": lambda rows, n, **o: env.write_actions(rows, {"atype": ints(9, n), "exploit": ints(X, n), "app": ints(3, n), **o.get("dev", {"dev_mask": rnd(n, M) > 0}), **o.get("cols", {})}),
+        "decode_actions": lambda rows, n, **o: env.decode_actions(rows, o.get("vec", rnd(n, n_out)), n_types, X, n_apps, o.get("tm", tm)),
+        "actor_head_decode": lambda rows, n, **o: env.actor_head_decode(rows, rnd(n, H), o.get("wt", wt), o.get("bias", bh), n_types, X, n_apps, o.get("tm", tm), n_groups=o.get("groups", 1)),
+        "actor_mlp_decode": lambda rows, n, **o: env.actor_mlp_decode(rows, rnd(n, K), o.get("hidden", hidden), o.get("head", head), n_types, X, n_apps, o.get("tm", tm), n_groups=o.get("groups", 1)),
+        "group_actions": lambda rows, n, **o: env.group_actions(rows, o.get("types", ints(14, n, M)), ints(X, n), ints(3, n), o.get("role", "defender"), visible=o.get("visible")),
+        "sample_group_actions": lambda rows, n, **o: env.sample_group_actions(rows, o.get("logits", rnd(n, M, KL)), o.get("exp", rnd(n, X)), rnd(n, 3), o.get("role", "defender")),
+    }
+    for name, call in writers.items():
+        call(ids, 6)
+        call(ids.long(), 6)                      # (ids of another integer type are converted, not refused)
+        call(None, N)
+        rejected("rows", call, ids.cpu(), 6)             # rows on the CPU
+        rejected("rows", call, torch.cat([ids, ids[:1]]), 6)   # rows one too long
+        rejected("rows", call, ids[:5], 6)
+        rejected("rows", call, None, N + 1)              # no rows: source row r goes to env r, and there is no env 8
+    for name in ("decode_actions", "actor_head_decode", "actor_mlp_decode"):
+        rejected("type_map", writers[name], ids, 6, tm=tm[:3])
+        rejected("type_map", writers[name], ids, 6, tm=torch.cat([tm, tm[:1]]))
+        rejected("type_map", writers[name], ids, 6, tm=tm.cpu())
+    rejected("vec", writers["decode_actions"], ids, 6, vec=rnd(6, n_out).double())
+    rejected("vec", writers["decode_actions"], ids, 6, vec=rnd(6, n_out - 1))
+    writers["write_actions"](ids, 6, dev={"dev_idx": ints(M, 6, L).to(torch.int16), "dev_cnt": ints(L + 1, 6)})
+    rejected("dev_mask", writers["write_actions"], ids, 6, dev={"dev_mask": rnd(6, M - 1) > 0})
+    rejected("dev_idx", writers["write_actions"], ids, 6, dev={"dev_idx": ints(M, 6, L + 1).to(torch.int16), "dev_cnt": ints(L + 1, 6)})
+    rejected("exploit", writers["write_actions"], ids, 6, cols={"exploit": ints(X, 5)})   # (checked since the writers share one marshalling path)
+    rejected("app", writers["write_actions"], ids, 6, cols={"app": ints(3, 7)})   # (checked since the writers share one marshalling path)
+    rejected("dev_cnt", writers["write_actions"], ids, 6, dev={"dev_idx": ints(M, 6, L).to(torch.int16), "dev_cnt": ints(L + 1, 5)})   # (checked since the writers share one marshalling path)
+    writers["group_actions"](ids, 6, visible=torch.ones((6, M), dtype=torch.uint8, device=dev))
+    rejected("types", writers["group_actions"], ids, 6, types=ints(14, 6, M - 1))
+    rejected("visible", writers["group_actions"], ids, 6, visible=torch.ones((6, M - 1), dtype=torch.uint8, device=dev))
+    rejected("visible", writers["group_actions"], ids, 6, visible=torch.ones((5, M), dtype=torch.uint8, device=dev))
+    rejected("role", writers["group_actions"], ids, 6, role="observer")
+    rejected("logits", writers["sample_group_actions"], ids, 6, logits=rnd(6, M, 33))
+    rejected("exp_logits", writers["sample_group_actions"], ids, 6, exp=rnd(7, X))
+    rejected("role", writers["sample_group_actions"], ids, 6, role="observer")
+    rejected("weight_t", writers["actor_head_decode"], ids, 6, wt=wt[:, :-1].contiguous())
+    rejected("weight_t", writers["actor_head_decode"], ids, 6, wt=wt[:-1].contiguous())
+    rejected("population", writers["actor_head_decode"], None, N, groups=2, wt=torch.stack([wt, wt]), bias=torch.stack([bh, bh]))   # 4 rows per actor: no multiple of 16
+    rejected("hidden layer 0", writers["actor_mlp_decode"], ids, 6, hidden=[(hidden[0][0][:-1].contiguous(), b1, H)])
+    rejected("head", writers["actor_mlp_decode"], ids, 6, head=(head[0][:-1].contiguous(), bh))
+    two = lambda t: torch.cat([t, t])  # noqa: E731
+    rejected("population", writers["actor_mlp_decode"], None, N, groups=2, hidden=[(two(hidden[0][0]), two(b1), H)], head=(two(head[0]), two(bh)))
+    env.actor_mlp_decode(ids, None, hidden, head, n_types, X, n_apps, tm, obs_role="defender")   # the view built on chip: M is even here
+    rejected("obs_role", env.actor_mlp_decode, ids, None, hidden, head, n_types, X, n_apps, tm, obs_role="observer")
+    rejected("rows", env.actor_mlp_decode, torch.cat([ids, ids[:1]]).cpu(), None, hidden, head, n_types, X, n_apps, tm, obs_role="defender")
+    env.take_status()   # (rows cut to max_devs = 4 devices / max_groups = 2 groups raise DECODE_TRUNCATED: expected here)
     # raw ABI: more ids than envs, missing scratch
     ids = torch.zeros(9, dtype=torch.int32, device="cuda:0")
     assert env.lib.cygym_reset(env._h, None, C.c_void_p(ids.data_ptr()), 9, None) == EINVAL

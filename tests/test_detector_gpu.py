@@ -76,6 +76,11 @@ def test_scan_without_current_forest_is_flagged(detector):
             assert env.service_detectors() == N
             for e in range(N):
                 ob.install_forest(e, env.state["forest"][e].cpu().numpy().view(np.uint32))
+            words = env.state["forest"][N - 1].cpu().numpy().view(np.uint32)
+            env.install_forest(-1, words)    # the last env's own forest once more, by negative id: the state stays as it is
+            for bad in (N, -N - 1):          # an env id outside the batch is refused on the host
+                with pytest.raises(IndexError):
+                    env.install_forest(bad, words)
         got = env.state_numpy()
         got["ienv"] = got["ienv"].copy()
         got["ienv"][:, S.I_FLAGS] &= ~0x80

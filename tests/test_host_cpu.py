@@ -88,6 +88,66 @@ def test_batched_env_refuses_cpu_device():
         BatchedCyberDefenseEnv(topo, abi.EnvConfig(**ck), 2, init, device="cpu")
 
 
+def test_action_writer_marshalling_on_cpu_tensors():
+    """The one coercion helper, the one `rows` binder and the one ActionVectors builder of the batch's action writers
+    (cygym_amd/batched_env.py), on CPU tensors and a stand-in batch: they are what stands between a malformed tensor and
+    a kernel that indexes it by raw pointer."""
+    import types
+    import torch
+    from cygym_amd import batched_env as BE
+    from cygym_amd import rng as R
+    cpu = torch.device("cpu")
+    right = torch.arange(6, dtype=torch.int32)
+    assert BE._on_device(right, torch.int32, cpu, "t") is right            # no copy, no launch
+    for dt in (torch.uint8, torch.int16):
+        t = right.to(dt)
+        assert BE._on_device(t, dt, cpu, "t") is t
+    for t in (torch.arange(6), torch.arange(12, dtype=torch.int32)[::2], torch.arange(12, dtype=torch.int64).reshape(6, 2).t()):
+        got = BE._on_device(t, torch.int32, cpu, "t")
+        assert got.dtype == torch.int32 and got.is_contiguous() and got.shape == t.shape and torch.equal(got.to(t.dtype), t)
+    with pytest.raises(ValueError, match="elsewhere"):
+        BE._on_device(torch.empty(6, dtype=torch.int32, device="meta"), torch.int32, cpu, "elsewhere")
+
+    env = types.SimpleNamespace(N=8, M=16, device=cpu, cfg=types.SimpleNamespace(max_exploits=5), status=torch.zeros(1, dtype=torch.int32))
+    n = 6
+    for struct in (abi.ActionRows, abi.ActionVectors, abi.DeviceTypes, abi.DeviceLogits):
+        src = struct()
+        rows = torch.arange(n, dtype=torch.int32)
+        assert BE._bind_rows(env, src, rows, n) is rows and src.rows == rows.data_ptr() and src.n == n
+        kept = BE._bind_rows(env, struct(), torch.arange(n), n)               # int64 ids: converted, and returned to be kept alive
+        assert kept.dtype == torch.int32 and kept.tolist() == list(range(n))
+        for bad in (n - 1, n + 1):
+            with pytest.raises(ValueError, match="rows"):
+                BE._bind_rows(env, struct(), torch.arange(bad, dtype=torch.int32), n)
+        with pytest.raises(ValueError, match="rows"):
+            BE._bind_rows(env, struct(), torch.empty(n, dtype=torch.int32, device="meta"), n)
+        src = struct()
+        assert BE._bind_rows(env, src, None, env.N) is None and not src.rows and src.n == env.N
+        with pytest.raises(ValueError, match="rows"):
+            BE._bind_rows(env, struct(), None, env.N + 1)
+
+    n_types = 4
+    tm = torch.tensor([3, 1, 2, 0], dtype=torch.int32)
+    src, n_out, keep = BE._action_vectors(env, None, env.N, n_types, None, 2, tm, 0.0)
+    assert (src.n_types, src.n_devices, src.n_exploits, src.n_apps, src.n) == (n_types, env.M, 5, 2, env.N)
+    assert n_out == n_types + env.M + 5 + 2 and src.status == env.status.data_ptr() and src.epsilon_thr == 0
+    assert src.type_map == tm.data_ptr() and any(k is tm for k in keep) and not src.rows
+    rows = torch.arange(n, dtype=torch.int32)
+    src, n_out, keep = BE._action_vectors(env, rows, n, n_types, 3, 0, None, 0.25)
+    assert src.rows == rows.data_ptr() and src.n == n and src.n_exploits == 3 and n_out == n_types + env.M + 3 and not src.type_map
+    assert src.epsilon_thr == R.bernoulli_threshold(0.25) > 0
+    for bad in (n_types - 1, n_types + 1):
+        with pytest.raises(ValueError, match="type_map"):
+            BE._action_vectors(env, None, n, n_types, None, 0, torch.zeros(bad, dtype=torch.int32), 0.0)
+    with pytest.raises(ValueError, match="type_map"):
+        BE._action_vectors(env, None, n, n_types, None, 0, torch.zeros(n_types, dtype=torch.int32, device="meta"), 0.0)
+    with pytest.raises(ValueError, match="rows"):
+        BE._action_vectors(env, rows, n + 1, n_types, None, 0, None, 0.0)
+    with pytest.raises(ValueError, match="rows"):
+        BE._action_vectors(env, None, env.N + 1, n_types, None, 0, None, 0.0)
+    BE._action_vectors(env, None, env.N, n_types, None, 0, None, 0.0)
+
+
 def test_default_actions_and_validation():
     f = np.zeros(6, np.uint8)
     f[1] = S.F_OWNED
