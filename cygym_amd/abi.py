@@ -13,7 +13,7 @@ import numpy as np
 from . import rng as R
 from . import spec as S
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
@@ -115,6 +115,12 @@ class DeviceLogits(C.Structure):
                 ("types_out", C.c_void_p), ("exp_out", C.c_void_p), ("app_out", C.c_void_p), ("logp_out", C.c_void_p),
                 ("n", C.c_int32), ("n_types", C.c_int32), ("n_exp", C.c_int32), ("n_app", C.c_int32), ("noop", C.c_int32),
                 ("role", C.c_int32), ("single_mask", C.c_uint32), ("greedy", C.c_int32), ("status", C.c_void_p)]
+
+
+class Critic(C.Structure):
+    _fields_ = [("h_state", C.c_void_p), ("w1a_t", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
+                ("pick_out", C.c_void_p), ("q_out", C.c_void_p), ("tau", C.c_double), ("b3", C.c_float), ("H1", C.c_int32),
+                ("H2", C.c_int32), ("h_stride", C.c_int32), ("top_k", C.c_int32), ("reserved", C.c_int32)]
 
 
 DECODE_TRUNCATED = 0x10000

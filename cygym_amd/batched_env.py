@@ -604,6 +604,45 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_actor_mlp_decode(self._h, C.byref(ml), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_actor_mlp_decode")
 
+    def coord_ascent_decode(self, rows, h_state: torch.Tensor, critic_pack, n_types: int, n_exploits: int | None = None,
+                            n_apps: int = 0, type_map=None, act=None, top_k: int = 5, tau: float = 0.5, pick_out=None, q_out=None):
+        """DoubleOracle.greedy_device_coord_ascent (do_agent.py:2137-2219: decode_action in the reference's default
+        best-response mode `Cord_asc`) for a batch, fused with the scatter into rows `rows` of `act` (group 0): ONE launch
+        (cygym_coord_ascent_decode; include/cygym_abi.h states the candidates, the pick and the merge).
+          h_state      [n, H1] float32 (unit inner stride): fc1.bias + fc1.weight[:, :W] @ state of source row r
+          critic_pack  (w1a_t, w2, b2, w3, b3): w1a_t [n_out, H1] = fc1.weight[:, W:].t() contiguous, w2 = pack_linear(fc2.weight),
+                       b2 [H2] or None, w3 [H2] = fc3.weight, b3 = float(fc3.bias); n_out = n_types + M + n_exploits + n_apps
+          top_k, tau   coord_K, coord_tau (do_agent.py:526-527); top_k = 1: the arg-max candidate, no draw
+          pick_out     optional [n, M] int16: receives the candidate chosen per device;  q_out optional [n, M] float32: its Q
+        Limits: H1, H2 multiples of 16 in 16..128, n_types <= 32, top_k <= 8 (the library answers CYGYM_EUNSUPPORTED)."""
+        dst = self.actions_struct(act)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not ok(h_state) or h_state.dim() != 2 or h_state.stride(1) != 1:
+            raise ValueError("h_state must be a [n, H1] float32 tensor on the batch's device with unit inner stride")
+        n, H1 = int(h_state.shape[0]), int(h_state.shape[1])
+        src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, 0.0)
+        w1a_t, w2, b2, w3, b3 = critic_pack
+        H2 = int(w3.numel())
+        if not ok(w1a_t) or tuple(w1a_t.shape) != (n_out, H1) or not w1a_t.is_contiguous():
+            raise ValueError(f"critic_pack: w1a_t must be a contiguous float32 {[n_out, H1]} tensor (fc1.weight[:, W:].t())")
+        if not ok(w3) or not w3.is_contiguous() or H2 < 1:
+            raise ValueError("critic_pack: w3 must be a contiguous float32 [H2] tensor")
+        if not ok(w2) or not w2.is_contiguous() or w2.numel() != ((H2 + 15) // 16) * ((H1 + 15) // 16) * 256:
+            raise ValueError("critic_pack: packed fc2 weights have the wrong size (see pack_linear)")
+        if b2 is not None and (not ok(b2) or not b2.is_contiguous() or b2.numel() != H2):
+            raise ValueError(f"critic_pack: b2 must hold {H2} float32 values")
+        cr = abi.Critic()
+        cr.h_state, cr.h_stride, cr.w1a_t, cr.w2, cr.w3 = h_state.data_ptr(), int(h_state.stride(0)), w1a_t.data_ptr(), w2.data_ptr(), w3.data_ptr()
+        cr.b2 = b2.data_ptr() if b2 is not None else None
+        cr.b3, cr.H1, cr.H2, cr.top_k, cr.tau = float(b3), H1, H2, int(top_k), float(tau)
+        for name, t, dt in (("pick_out", pick_out, torch.int16), ("q_out", q_out, torch.float32)):
+            if t is not None:
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n, self.M):
+                    raise ValueError(f"{name} must be a contiguous {dt} {[n, self.M]} tensor on {self.device}")
+                setattr(cr, name, t.data_ptr())
+        _lib.check(self.lib.cygym_coord_ascent_decode(self._h, C.byref(cr), C.byref(src), C.byref(dst), self._stream()),
+                   self._h, "cygym_coord_ascent_decode")
+
     def can_step_actor(self, n_out: int) -> bool:
         """May a tick and the next actor run as ONE launch (cygym_step_actor)?  Where both kernels share their launch shape: 256
         devices, a fixed topology without detector buffers, a multiple of 16 envs and at most 16 envs per CU, 257..384 outputs."""

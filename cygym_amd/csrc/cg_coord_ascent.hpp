@@ -1,0 +1,268 @@
+// cg_coord_ascent.hpp -- cygym_coord_ascent_decode: DoubleOracle.greedy_device_coord_ascent (do_agent.py:2137-2219, the decode of
+// the reference's default best-response mode `Cord_asc`) for a batch, in ONE launch.  Included through cg_decode.hpp; instantiated
+// in cg_inst_coord.hip.
+//
+// ONE workgroup of 16 waves per env row; wave w owns the devices w, w + 16, ...  Per device d the critic
+//   Q(s, a) = fc3(relu(fc2(relu(fc1([s, a])))))                                                    (do_agent.py:373-388)
+// scores the candidates c = 0 (no-op) and c = 1 + t E + x (type t, exploit x) -- cygym_abi.h has the encodings, quirks included.
+//   * Layer 1 is no GEMM: a candidate's action vector has four ones, so its pre-activation is
+//       ((h_state + app column) + device column) + type column + exploit column,
+//     h_state = b1 + W1[:, :W] s from the caller.  The type columns, the exploit columns and the first E device columns (the
+//     `d < E` quirk swaps device and exploit) live in LDS (rows padded by four floats: rows of one 16-row tile sit in different
+//     16-byte bank slots); the device's own base row is staged per wave.
+//   * Layer 2 is the GEMM, on the matrix cores in fp32 (v_mfma_f32_16x16x4_f32): a tile is 16 candidates of one device, its A
+//     fragments are built IN REGISTERS from the three rows above (lane = (row r = lane % 16, kk = lane / 16) holds
+//     k = 16 g + 4 kk + i, the pack_linear fragment order), packed W2 stays in LDS for the workgroup's life.  Output tiles go in
+//     pairs: two independent accumulator chains per pair (a dependent 16x16x4 would wait 8 of 40 cycles).
+//   * relu(. + b2), the fc3 dot and + b3 are the epilogue on the D fragments (rows 4 kk + v, column r: a 16-lane sum).
+//   * The device's <= 193 Q values pass through a per-wave LDS row; top-K' by K' wave-wide arg-max rounds on (order bits of Q,
+//     ~c) -- descending Q, ascending c among equals: the reference's stable sort --, the softmax pick in f64 from ONE exp per
+//     lane, the addressed Philox draw.  Neither candidate rows nor Q values reach HBM.
+//   * Wave 0 merges the per-device picks (LDS) into the row's action and writes group 0 like cygym_decode_actions.
+constexpr int CA_WAVES = 16, CA_THREADS = CA_WAVES * WAVE, CA_QROW = 256, CA_MAX_H = 128, CA_MAX_TYPES = 32, CA_MAX_TOPK = 8;
+static_assert(CA_MAX_TYPES * CG_MAX_EXPLOITS + 1 <= CA_QROW, "a device's candidates fit the per-wave Q row (four per lane)");
+
+// LDS plan (offsets in floats), the same arithmetic on both sides of the launch
+struct CaPlan {
+  int hp;                  // pitch of a column row: H1 + 4
+  int w2, col_t, col_x, col_d, hs, noop, b2, w3;   // packed W2 | type rows | exploit rows | first E device rows | h_state + app | no-op base | b2 | w3
+  int wave0, wave_pitch;   // per wave: base row [hp] + Q row [CA_QROW]
+  int q, pick;             // per device: picked Q (float), picked c (int16)
+  int total;
+};
+__host__ __device__ inline CaPlan ca_plan(int H1, int H2, int T, int E, int M) {
+  CaPlan p;
+  p.hp = H1 + 4;
+  int o = 0;
+  p.w2 = o; o += H1 * H2;
+  p.col_t = o; o += T * p.hp;
+  p.col_x = o; o += E * p.hp;
+  p.col_d = o; o += E * p.hp;
+  p.hs = o; o += p.hp;
+  p.noop = o; o += p.hp;
+  p.b2 = o; o += H2;
+  p.w3 = o; o += H2;
+  p.wave0 = o; p.wave_pitch = p.hp + CA_QROW; o += CA_WAVES * p.wave_pitch;
+  p.q = o; o += M;
+  p.pick = o; o += (M + 1) / 2;
+  p.total = o;
+  return p;
+}
+
+__device__ __forceinline__ float ca_nan_to_num(float q) {   // np.nan_to_num(qv, nan=-1e9, posinf=1e9, neginf=-1e9), do_agent.py:2163
+  return q != q ? -1e9f : q > 3.4028234e38f ? 1e9f : q < -3.4028234e38f ? -1e9f : q;
+}
+
+// SAMPLE = false: top_k == 1 (the arg-max candidate, no draw, no f64)
+template <bool SAMPLE>
+__global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic cr, cygym_action_vectors src, cygym_actions dst, int n_envs,
+                                                                  const int32_t* ienv, uint64_t seed, int64_t env_id_base) {
+  extern __shared__ __align__(16) uint8_t smem[];
+  float* lds = reinterpret_cast<float*>(smem);
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int r = lane & 15, kk = lane >> 4;
+  const int srow = blockIdx.x;
+  const int row = src.rows ? src.rows[srow] : srow;
+  if (row < 0 || row >= n_envs) return;   // (uniform: before any barrier)
+  const int T = src.n_types, M = src.n_devices, E = src.n_exploits, H1 = cr.H1, H2 = cr.H2;
+  const int TE = T * E, G1 = H1 >> 4, nt2 = H2 >> 4;
+  const CaPlan pl = ca_plan(H1, H2, T, E, M);
+  const int hp = pl.hp;
+  const float* w1a = cr.w1a_t;
+  // ---------------- stage: packed W2, the column rows, h_state ----------------
+  {
+    const float4* s = reinterpret_cast<const float4*>(cr.w2);
+    float4* d = reinterpret_cast<float4*>(lds + pl.w2);
+    for (int i = tid; i < (H1 * H2) >> 2; i += CA_THREADS) d[i] = s[i];
+    for (int i = tid; i < T * H1; i += CA_THREADS) {
+      const int t = i / H1, k = i - t * H1;
+      lds[pl.col_t + t * hp + k] = w1a[i];
+    }
+    for (int i = tid; i < E * H1; i += CA_THREADS) {
+      const int e = i / H1, k = i - e * H1;
+      lds[pl.col_d + e * hp + k] = w1a[(size_t)T * H1 + i];
+      lds[pl.col_x + e * hp + k] = w1a[(size_t)(T + M) * H1 + i];
+    }
+    if (tid < H1) {
+      float hs = cr.h_state[(size_t)srow * cr.h_stride + tid];
+      if (src.n_apps > 0) hs += w1a[(size_t)(T + M + E) * H1 + tid];   // app index 0 (A = 0: no app term)
+      lds[pl.hs + tid] = hs;
+      lds[pl.noop + tid] = hs + w1a[(size_t)T * H1 + tid];             // the no-op's device bit 0
+    }
+    if (tid < H2) {
+      lds[pl.b2 + tid] = cr.b2 ? cr.b2[tid] : 0.f;
+      lds[pl.w3 + tid] = cr.w3[tid];
+    }
+  }
+  uint32_t tick = 0;
+  if constexpr (SAMPLE) tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];
+  __syncthreads();
+  float* bw = lds + pl.wave0 + wave * pl.wave_pitch;   // this wave's base row, then its Q row
+  float* qb = bw + hp;
+  float* q_dev = lds + pl.q;
+  int16_t* pick_dev = reinterpret_cast<int16_t*>(lds + pl.pick);
+  const float4* w2l = reinterpret_cast<const float4*>(lds + pl.w2) + lane;
+  const int top_k = cr.top_k;
+  const int Kp = top_k < TE + 1 ? top_k : TE + 1;
+  // ---------------- this wave's devices ----------------
+  for (int d = wave; d < M; d += CA_WAVES) {
+    const bool swapped = d < E;   // (uniform) encode_action leaves (exploit, device) swapped: device bit x, exploit one-hot d
+    for (int k = lane; k < H1; k += WAVE) bw[k] = lds[pl.hs + k] + (swapped ? lds[pl.col_x + d * hp + k] : w1a[(size_t)(T + d) * H1 + k]);
+    __builtin_amdgcn_wave_barrier();
+    const float* ytab = lds + (swapped ? pl.col_d : pl.col_x);
+    for (int j = 0; 16 * j <= TE; ++j) {
+      // row r of the tile: candidate c = 16 j + r (past the end: the last one again, never stored)
+      const int c = 16 * j + r, cc = c < TE ? c : TE;
+      const int t = cc ? (cc - 1) / E : T - 1, x = cc ? (cc - 1) - t * E : 0;
+      const float* p0 = (cc ? bw : lds + pl.noop) + 4 * kk;
+      const float* p1 = lds + pl.col_t + t * hp + 4 * kk;
+      const float* p2 = (cc ? ytab : lds + pl.col_x) + x * hp + 4 * kk;
+      cg_floatx4 acc[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] = cg_floatx4{0.f, 0.f, 0.f, 0.f};
+      for (int g = 0; g < G1; ++g) {
+        const float4 a0 = *reinterpret_cast<const float4*>(p0 + 16 * g), a1 = *reinterpret_cast<const float4*>(p1 + 16 * g),
+                     a2 = *reinterpret_cast<const float4*>(p2 + 16 * g);
+        float4 a = make_float4((a0.x + a1.x) + a2.x, (a0.y + a1.y) + a2.y, (a0.z + a1.z) + a2.z, (a0.w + a1.w) + a2.w);
+        a.x = a.x > 0.f ? a.x : 0.f; a.y = a.y > 0.f ? a.y : 0.f; a.z = a.z > 0.f ? a.z : 0.f; a.w = a.w > 0.f ? a.w : 0.f;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          if (2 * p < nt2) {   // (uniform) output tiles 2 p and 2 p + 1 (an odd tile count: the last tile twice, its second copy unused)
+            const int ta = 2 * p, tb = 2 * p + 1 < nt2 ? 2 * p + 1 : nt2 - 1;
+            const float4 b0 = w2l[(size_t)(ta * G1 + g) * WAVE], b1 = w2l[(size_t)(tb * G1 + g) * WAVE];
+            acc[2 * p] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0.x, acc[2 * p], 0, 0, 0);
+            acc[2 * p + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b1.x, acc[2 * p + 1], 0, 0, 0);
+            acc[2 * p] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b0.y, acc[2 * p], 0, 0, 0);
+            acc[2 * p + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1.y, acc[2 * p + 1], 0, 0, 0);
+            acc[2 * p] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b0.z, acc[2 * p], 0, 0, 0);
+            acc[2 * p + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b1.z, acc[2 * p + 1], 0, 0, 0);
+            acc[2 * p] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b0.w, acc[2 * p], 0, 0, 0);
+            acc[2 * p + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b1.w, acc[2 * p + 1], 0, 0, 0);
+          }
+        }
+      }
+      // epilogue: D fragment = rows 4 kk + v, column 16 t2 + r  ->  Q(row) = b3 + sum over columns of w3 relu(. + b2)
+      float part[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t2 = 0; t2 < 8; ++t2) {
+        if (t2 < nt2) {
+          const float bb = lds[pl.b2 + 16 * t2 + r], ww = lds[pl.w3 + 16 * t2 + r];
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const float h = acc[t2][v] + bb;
+            part[v] += ww * (h > 0.f ? h : 0.f);
+          }
+        }
+      }
+#pragma unroll
+      for (int m = 1; m < 16; m <<= 1) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) part[v] += __shfl_xor(part[v], m);
+      }
+      const int co = 16 * j + 4 * kk + r;   // lanes r < 4 store row 4 kk + r
+      const float qv = r == 0 ? part[0] : r == 1 ? part[1] : r == 2 ? part[2] : part[3];
+      if (r < 4 && co <= TE) qb[co] = ca_nan_to_num(qv + cr.b3);
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ---- top-K': K' rounds of a wave-wide arg-max over (order bits of Q, ~c); four candidates per lane ----
+    uint32_t kh[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = lane + WAVE * i;
+      kh[i] = c <= TE ? float_order_bits(qb[c <= TE ? c : 0]) : 0u;
+    }
+    constexpr int NK = SAMPLE ? CA_MAX_TOPK : 1;
+    float sq[NK];
+    int sc[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      sq[k] = 0.f; sc[k] = 0;
+      if (k < Kp) {   // (uniform)
+        uint32_t bh = 0u, bl = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (kh[i] > bh) { bh = kh[i]; bl = ~(uint32_t)(lane + WAVE * i); }   // (equal Q: the lane's smaller c stays)
+        dpp_pair_max(bh, bl);
+        const int cw = (int)~(uint32_t)__builtin_amdgcn_readlane((int)bl, 63);
+        sc[k] = cw;
+        sq[k] = qb[cw];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) kh[i] = cw == lane + WAVE * i ? 0u : kh[i];
+      }
+    }
+    int pc = sc[0];
+    float pq = sq[0];
+    if constexpr (SAMPLE) {
+      if (Kp > 1) {
+        // p_i = exp(q_i / tau - q_0 / tau) / sum (f64, max-subtracted); the pick is the first i whose normalised running sum
+        // exceeds u = draw / 2^32 (np.random.choice).  Lane i evaluates exp i.
+        float mq = sq[0];
+#pragma unroll
+        for (int k = 1; k < CA_MAX_TOPK; ++k) mq = lane == k ? sq[k] : mq;
+        const double el = lane < Kp ? exp((double)mq / cr.tau - (double)sq[0] / cr.tau) : 0.0;
+        double e[CA_MAX_TOPK], sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < CA_MAX_TOPK; ++k) { e[k] = __shfl(el, k); sum += e[k]; }
+        const uint32_t draw = cg_philox4x32_10((uint32_t)(env_id_base + row), tick, CG_SITE_COORD_PICK, (uint32_t)d & 0xFFFFu, (uint32_t)seed,
+                                               (uint32_t)(seed >> 32)).v[0];
+        const double u = (double)draw * (1.0 / 4294967296.0);
+        double run = 0.0;
+        bool found = false;
+        pc = sc[0]; pq = sq[0];
+#pragma unroll
+        for (int k = 0; k < CA_MAX_TOPK; ++k) {
+          if (k < Kp) {
+            run += e[k];
+            const bool take = !found && (run / sum > u || k == Kp - 1);
+            pc = take ? sc[k] : pc; pq = take ? sq[k] : pq;
+            found = found || take;
+          }
+        }
+      }
+    }
+    if (lane == 0) {
+      q_dev[d] = pq;
+      pick_dev[d] = (int16_t)pc;
+      if (cr.pick_out) cr.pick_out[(size_t)srow * M + d] = (int16_t)pc;
+      if (cr.q_out) cr.q_out[(size_t)srow * M + d] = pq;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  // ---------------- merge (`best_q`, do_agent.py:2190-2203) and the row's action, group 0 ----------------
+  const int G = dst.max_groups, L = dst.max_devs;
+  int16_t* out = const_cast<int16_t*>(dst.dev_idx) + (size_t)row * L;
+  int base = 0, ex = -1;
+  uint32_t bh = 0u, bl = 0u;
+  for (int d0 = 0; d0 < M; d0 += WAVE) {
+    const int d = d0 + lane;
+    const int c = d < M ? (int)pick_dev[d] : 0;
+    const int t = c > 0 ? (c - 1) / E : T - 1, x = c > 0 ? (c - 1) - t * E : 0;
+    const bool on = d < M && t != T - 1;   // a pick is a no-op iff its type is T - 1
+    const uint64_t m = __ballot(on);
+    const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (on && pos < L) out[pos] = (int16_t)d;
+    if (ex < 0 && m) ex = __shfl(x, __ffsll((unsigned long long)m) - 1);   // the exploit of the lowest acting device
+    if (on) {
+      const uint32_t ob = float_order_bits(q_dev[d]);
+      if (ob > bh) { bh = ob; bl = ~(uint32_t)d; }
+    }
+    base += __popcll(m);
+  }
+  dpp_pair_max(bh, bl);   // the acting device with the largest Q, the lowest id among equals
+  const uint32_t rh = (uint32_t)__builtin_amdgcn_readlane((int)bh, 63), rl = (uint32_t)__builtin_amdgcn_readlane((int)bl, 63);
+  int at = T - 1;
+  if (rh != 0u) at = ((int)pick_dev[(int)~rl] - 1) / E;
+  if (src.type_map) at = src.type_map[at];
+  const int cnt = base < L ? base : L;
+  for (int q = cnt + lane; q < L; q += WAVE) out[q] = 0;
+  if (lane == 0) {
+    const_cast<int32_t*>(dst.atype)[(size_t)row * G] = at;
+    const_cast<int32_t*>(dst.exploit)[(size_t)row * G * CG_MAX_EXPLOITS] = ex < 0 ? 0 : ex;
+    const_cast<int32_t*>(dst.n_exploit)[(size_t)row * G] = 1;
+    const_cast<int32_t*>(dst.app)[(size_t)row * G] = 0;
+    const_cast<int32_t*>(dst.dev_cnt)[(size_t)row * G] = cnt;
+    if (base > L && src.status) atomicOr(src.status, CG_DECODE_TRUNCATED);
+  }
+}

@@ -82,4 +82,5 @@ __device__ __forceinline__ void head_decode_row(const float* outs_row, const flo
 }
 
 #include "cg_actor_mlp.hpp"
+#include "cg_coord_ascent.hpp"
 #endif  // CG_DECODE_HPP

@@ -52,6 +52,12 @@ extern template __global__ void tick_actor_kernel<5>(const KParams, cygym_actor_
 extern template __global__ void tick_actor_kernel<6>(const KParams, cygym_actor_mlp, cygym_action_vectors, cygym_actions, MlpView);
 }  // namespace cygym_k
 
+// the coordinate-ascent decode lives in its own unit (cg_inst_coord.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void coord_ascent_kernel<false>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+}  // namespace cygym_k
+
 // =====================================================================
 // C ABI
 // =====================================================================
@@ -182,6 +188,7 @@ int cygym_sizeof(int32_t which) {
     case 8: return (int)sizeof(cygym_actor_mlp);
     case 9: return (int)sizeof(cygym_device_types);
     case 10: return (int)sizeof(cygym_device_logits);
+    case 11: return (int)sizeof(cygym_critic);
     default: return -1;
   }
 }
@@ -731,6 +738,37 @@ int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cy
   MlpView view = {h->b.live, h->t.os_val, h->t.version, h->t.anomaly, h->b.anomaly, h->t.M, h->t.X, h->c.max_exploits, mlp->obs_role};
   void* args[] = {(void*)mlp, (void*)src, (void*)dst, &n_envs, &ienv, &seed, &base, &st, &view};
   HIPCHK(h, hipLaunchKernel(k, dim3((src->n + 15) / 16), dim3(MLP_THREADS), args, lds, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* src, const cygym_actions* dst,
+                              void* stream) {
+  if (!h) return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: null handle%s", "");
+  if (!h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_coord_ascent_decode: handle not bound (the picks are drawn at the envs' rng ticks)%s", "");
+  if (!c || !src || !dst || !c->h_state || !c->w1a_t || !c->w2 || !c->w3) return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: null source pointer%s", "");
+  if (const int rc = check_dst(h, dst, "cygym_coord_ascent_decode", false)) return rc;
+  if (src->n_types < 1 || src->n_exploits < 1 || src->n_apps < 0 || src->n_devices != h->t.M || c->h_stride < c->H1 || c->top_k < 1 ||
+      !(c->tau > 0.0) || !(c->tau < 1e300))
+    return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: bad layout (types, exploits >= 1, the handle's device count, h_stride >= H1, top_k >= 1, tau > 0)%s", "");
+  if (c->H1 < 16 || c->H1 > CA_MAX_H || (c->H1 & 15) || c->H2 < 16 || c->H2 > CA_MAX_H || (c->H2 & 15))
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: critic widths H1, H2 must be multiples of 16 in 16 .. 128%s", "");
+  if (src->n_types > CA_MAX_TYPES || src->n_exploits > CG_MAX_EXPLOITS || src->n_exploits > src->n_devices || c->top_k > CA_MAX_TOPK)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: at most 32 action types, CG_MAX_EXPLOITS exploits (and no more than devices), top_k <= 8%s", "");
+  if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: bad row count%s", "");
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const CaPlan pl = ca_plan(c->H1, c->H2, src->n_types, src->n_exploits, src->n_devices);
+  const size_t lds = (size_t)pl.total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: the critic does not fit in LDS%s", "");
+  const void* k = c->top_k > 1 ? (const void*)coord_ascent_kernel<true> : (const void*)coord_ascent_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  int n_envs = h->n_envs;
+  const int32_t* ienv = h->b.ienv;
+  uint64_t seed = h->c.seed;
+  int64_t base = h->c.env_id_base;
+  void* args[] = {(void*)c, (void*)src, (void*)dst, &n_envs, &ienv, &seed, &base};
+  HIPCHK(h, hipLaunchKernel(k, dim3(src->n), dim3(CA_THREADS), args, lds, (hipStream_t)stream));   // one workgroup per row
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
 }

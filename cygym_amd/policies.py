@@ -6,6 +6,11 @@ actor maps the role observation to an action vector [type logits | device values
 module evaluated on all the cells that play the strategy at once, and the decoding + scatter into the batch's
 action tensors is ONE launch of the library (cygym_decode_actions).  `reference_actor` builds the reference's own
 architecture (do_agent.py:357-370); `mlp_actor` a smaller one.
+
+`CoordAscentPolicy` is the same loop in the reference's DEFAULT best-response mode (`--BR_type Cord_asc`): there
+decode_action does not read the actor at all but scores one-device candidate actions with the CRITIC
+(`DoubleOracle.greedy_device_coord_ascent`, do_agent.py:2137-2219); the batch does that in one launch
+(cygym_coord_ascent_decode).  `reference_critic` builds the reference's critic (do_agent.py:373-388).
 """
 from __future__ import annotations
 
@@ -293,6 +298,165 @@ def mlp_actor(state_dim: int, action_dim: int, hidden=(64,), seed: int = 0, devi
 def reference_actor(state_dim: int, action_dim: int, seed: int = 0, device="cpu") -> nn.Module:
     """The reference's DDPG actor (do_agent.py:357-370): state -> 256 -> 256 -> action_dim, ReLU, tanh."""
     return mlp_actor(state_dim, action_dim, hidden=(256, 256), seed=seed, device=device, tanh=True)
+
+
+class Critic(nn.Module):
+    """Q(s, a) = fc3(relu(fc2(relu(fc1([s, a]))))) -- the reference's critic (do_agent.py:373-388) with free widths."""
+
+    def __init__(self, state_dim: int, action_dim: int, hidden=(128, 128)):
+        super().__init__()
+        self.fc1 = nn.Linear(int(state_dim) + int(action_dim), int(hidden[0]))
+        self.fc2 = nn.Linear(int(hidden[0]), int(hidden[1]))
+        self.fc3 = nn.Linear(int(hidden[1]), 1)
+
+    def forward(self, state, action):
+        x = torch.relu(self.fc1(torch.cat([state, action], 1)))
+        return self.fc3(torch.relu(self.fc2(x)))
+
+
+def reference_critic(state_dim: int, action_dim: int, seed: int = 0, device="cpu", hidden=(128, 128)) -> nn.Module:
+    """The reference's DDPG critic (do_agent.py:373-388): [state, action] -> 128 -> 128 -> 1, ReLU; default-initialised
+    from `seed` (uniform +- 1/sqrt(fan_in), like nn.Linear)."""
+    net = Critic(state_dim, action_dim, hidden)
+    g = torch.Generator().manual_seed(int(seed))
+    with torch.no_grad():
+        for lin in (net.fc1, net.fc2, net.fc3):
+            bound = 1.0 / (lin.in_features ** 0.5)
+            for p in (lin.weight, lin.bias):
+                p.copy_((torch.rand(p.shape, generator=g) * 2 - 1) * bound)
+    return net.to(device).eval()
+
+
+def coord_ascent_candidates(T: int, D: int, E: int, device="cpu"):
+    """Index tensors [D, T E + 1] (type, device bit, exploit one-hot) of the candidates greedy_device_coord_ascent scores for
+    every device (do_agent.py:2152, :2170-2173, as encode_action :910-933 sees them): c = 0 is the no-op (T - 1, 0, 0) -- its tuple
+    reaches encode_action with the exploit and device fields swapped --, c = 1 + t E + x is (t, d, x) for d >= E and (t, x, d)
+    for d < E (the swapped tuple is un-swapped only when d >= E, :919-920)."""
+    c = torch.arange(T * E, device=device)
+    t, x = c // E, c % E
+    d = torch.arange(D, device=device)[:, None]
+    swapped = d < E
+    ti = torch.cat([torch.full((D, 1), T - 1, device=device), t[None, :].expand(D, -1)], 1)
+    di = torch.cat([torch.zeros((D, 1), dtype=torch.long, device=device), torch.where(swapped, x[None, :], d.expand(-1, T * E))], 1)
+    xi = torch.cat([torch.zeros((D, 1), dtype=torch.long, device=device), torch.where(swapped, d.expand(-1, T * E), x[None, :])], 1)
+    return ti, di, xi
+
+
+@torch.no_grad()
+def coord_ascent_q(obs, fc1, fc2, fc3, T: int, D: int, E: int, A: int, dtype=torch.float64, max_bytes: int = 1 << 28):
+    """Q of every candidate of every device, [n, D, T E + 1], with torch ops in `dtype` (float64: the restatement the kernel
+    is checked against; float32: the torch path the kernel is timed against): fc1's pre-activation of a candidate is
+    h_state + the action columns of its four ones (no app column when A = 0).  Chunked over devices and rows so that the
+    activations stay under `max_bytes`."""
+    n, W = obs.shape[0], fc1.in_features - (T + D + E + A)
+    w1, H1 = fc1.weight.detach().to(dtype), fc1.out_features
+    hs = obs.to(dtype) @ w1[:, :W].t() + fc1.bias.detach().to(dtype)
+    wa = w1[:, W:].t().contiguous()                                   # [n_out, H1]
+    if A > 0:
+        hs = hs + wa[T + D + E]
+    w2t, b2 = fc2.weight.detach().to(dtype).t().contiguous(), fc2.bias.detach().to(dtype)
+    w3, b3 = fc3.weight.detach().to(dtype).reshape(-1), fc3.bias.detach().to(dtype).reshape(())
+    ti, di, xi = coord_ascent_candidates(T, D, E, obs.device)
+    C = T * E + 1
+    item = torch.empty((), dtype=dtype).element_size()
+    dchunk = max(1, min(D, max_bytes // (4 * C * H1 * item)))
+    q = torch.empty((n, D, C), dtype=dtype, device=obs.device)
+    for d0 in range(0, D, dchunk):
+        d1 = min(D, d0 + dchunk)
+        cols = wa[ti[d0:d1]] + wa[T + di[d0:d1]] + wa[T + D + xi[d0:d1]]      # [dc, C, H1]
+        nchunk = max(1, max_bytes // ((d1 - d0) * C * max(H1, fc2.out_features) * item * 2))
+        for n0 in range(0, n, nchunk):
+            h1 = torch.relu(hs[n0:n0 + nchunk, None, None, :] + cols[None])
+            h2 = torch.relu(h1.reshape(-1, H1) @ w2t + b2)
+            q[n0:n0 + nchunk, d0:d1] = (h2 @ w3 + b3).reshape(h1.shape[0], d1 - d0, C)
+    return q
+
+
+def coord_ascent_merge(pick, q, T: int, E: int):
+    """The `best_q` merge of the per-device picks (do_agent.py:2190-2203): pick [n, D] candidate index, q [n, D] its Q ->
+    (action type before the type map, exploit, device mask).  A pick is a no-op iff its type is T - 1."""
+    t = torch.where(pick > 0, (pick - 1) // E, torch.full_like(pick, T - 1))
+    x = torch.where(pick > 0, (pick - 1) % E, torch.zeros_like(pick))
+    on = t != T - 1
+    any_on = on.any(dim=1)
+    first = torch.argmax(on.to(torch.int8), dim=1)                           # lowest acting device
+    ex = torch.where(any_on, x.gather(1, first[:, None])[:, 0], torch.zeros_like(first))
+    qm = torch.where(on, q, torch.full_like(q, -float("inf")))
+    best = torch.argmax(qm, dim=1)                                            # first maximum in ascending d
+    at = torch.where(any_on, t.gather(1, best[:, None])[:, 0], torch.full_like(best, T - 1))
+    return at, ex, on
+
+
+class CoordAscentPolicy:
+    """A strategy of the reference's default best-response mode (`--BR_type Cord_asc`, volt_typhoon_do.py:1237): every decision
+    is DoubleOracle.greedy_device_coord_ascent (do_agent.py:2137-2219) on the critic -- per device the candidates (type, exploit)
+    and the no-op are scored, one of the top `top_k` is drawn from their softmax at temperature `tau`, and the per-device
+    picks are merged into one action tuple (`best_q`).  include/cygym_abi.h (cygym_coord_ascent_decode) states it in full.
+    `critic`: a module with fc1 / fc2 / fc3 (policies.Critic, the reference's Critic) or a sequence of three nn.Linear.
+    write() is one addmm (the state part of fc1) plus ONE launch; __call__ is the same decode with torch ops in float64, for
+    top_k = 1 only (a sampled pick needs the envs' rng ticks).  Not restated: the training-mode noise on Q (:2177-2178) and
+    exploit_override."""
+
+    tick_free = True
+
+    def __init__(self, critic, n_types: int, n_exploits: int, n_apps: int, type_map=None, top_k: int = 5, tau: float = 0.5):
+        lins = [critic.fc1, critic.fc2, critic.fc3] if hasattr(critic, "fc1") else list(critic)
+        if len(lins) != 3 or not all(isinstance(m, nn.Linear) and m.bias is not None and m.weight.dtype == torch.float32 for m in lins):
+            raise ValueError("critic: a module with fc1 / fc2 / fc3 or three nn.Linear layers (float32, with biases)")
+        self.critic, (self.fc1, self.fc2, self.fc3) = critic, lins
+        self.n_types, self.n_exploits, self.n_apps = int(n_types), int(n_exploits), int(n_apps)
+        self.top_k, self.tau = int(top_k), float(tau)
+        H1, H2 = self.fc1.out_features, self.fc2.out_features
+        if H1 % 16 or H2 % 16 or not (16 <= H1 <= 128 and 16 <= H2 <= 128) or self.fc2.in_features != H1 \
+                or self.fc3.in_features != H2 or self.fc3.out_features != 1:
+            raise ValueError("critic widths: fc1 -> H1 -> H2 -> 1 with H1, H2 multiples of 16 in 16..128")
+        if not (1 <= self.n_types <= 32 and 1 <= self.n_exploits <= 6 and self.n_apps >= 0 and 1 <= self.top_k <= 8 and self.tau > 0.0):
+            raise ValueError("1..32 action types, 1..6 exploits, n_apps >= 0, top_k in 1..8, tau > 0")
+        self.type_map = None if type_map is None else torch.as_tensor(type_map, dtype=torch.int32)
+        self.action_types = list(range(self.n_types)) if type_map is None else sorted({int(x) for x in self.type_map.tolist()})
+
+    _map = ActorPolicy._map
+
+    def n_out(self, M):
+        return self.n_types + M + self.n_exploits + self.n_apps
+
+    def _packed(self, batch, M):
+        """(state part of fc1 transposed, its bias, critic pack of coord_ascent_decode), redone when a parameter changes."""
+        ver = (int(M),) + tuple((m.weight._version, m.weight.data_ptr(), m.bias._version) for m in (self.fc1, self.fc2, self.fc3))
+        if getattr(self, "_pk_ver", None) != ver:
+            W = self.fc1.in_features - self.n_out(M)
+            if W < 1:
+                raise ValueError(f"fc1 takes {self.fc1.in_features} inputs: fewer than the {self.n_out(M)} of an action vector at {M} devices")
+            w1 = self.fc1.weight.detach()
+            self._pk = (w1[:, :W].t().contiguous(), self.fc1.bias.detach().contiguous(),
+                        (w1[:, W:].t().contiguous(), batch.pack_linear(self.fc2.weight), self.fc2.bias.detach().contiguous(),
+                         self.fc3.weight.detach().reshape(-1).contiguous(), float(self.fc3.bias.detach().reshape(-1)[0])))
+            self._pk_ver = ver
+        return self._pk
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, pick_out=None, q_out=None):
+        """h_state = one addmm, then the whole decode + scatter into rows `rows` of the action tensors in ONE launch."""
+        w1s_t, b1, pack = self._packed(batch, batch.M)
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != int(w1s_t.shape[0]):
+            raise ValueError(f"obs must be a float32 [n, {int(w1s_t.shape[0])}] role view")
+        h_state = torch.addmm(b1, obs, w1s_t)
+        batch.coord_ascent_decode(rows, h_state, pack, self.n_types, self.n_exploits, self.n_apps, self._map(obs.device), act,
+                                  top_k=self.top_k, tau=self.tau, pick_out=pick_out, q_out=q_out)
+
+    @torch.no_grad()
+    def __call__(self, obs, t, M, L):
+        """The same decode with torch ops in float64 (batch-likes without cygym_coord_ascent_decode: the tests' oracle harness)."""
+        if self.top_k != 1:
+            raise NotImplementedError("a pick among the top K is drawn in cygym_coord_ascent_decode (needs the envs' rng ticks)")
+        T, E = self.n_types, self.n_exploits
+        q = coord_ascent_q(obs, self.fc1, self.fc2, self.fc3, T, M, E, self.n_apps)
+        q = torch.nan_to_num(q.to(torch.float32), nan=-1e9, posinf=1e9, neginf=-1e9)     # Q is an fp32 value (do_agent.py:2163)
+        pick = torch.argmax(q, dim=2)                                        # first maximum: the stable sort's head
+        at, ex, on = coord_ascent_merge(pick, q.gather(2, pick[:, :, None])[:, :, 0], T, E)
+        tm = self._map(obs.device)
+        at = at.to(torch.int32) if tm is None else tm[at]
+        return {"atype": at, "exploit": ex.to(torch.int32), "dev_mask": on, "app": torch.zeros_like(at)}
 
 
 @torch.no_grad()

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CYGYM_ABI_VERSION 4
+#define CYGYM_ABI_VERSION 5
 
 #define CYGYM_OK            0
 #define CYGYM_EINVAL       -1  /* bad argument / shape                       */
@@ -191,7 +191,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits; -1 for anything else): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic; -1 for anything else): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -290,8 +290,8 @@ typedef struct cygym_action_vectors {
 } cygym_action_vectors;
 #define CG_DECODE_TRUNCATED 0x10000u
 
-/* Replaces: DoubleOracle.decode_action (do_agent.py:935-998, the plain branch :970-998) for a batch, fused with the
- * scatter into the action tensors: action_type = argmax of the type logits (first maximum, like np.argmax),
+/* Replaces: DoubleOracle.decode_action (do_agent.py:935-998, the plain branch :970-998; the `Cord_asc` branch :952-968 is
+ * cygym_coord_ascent_decode below) for a batch, fused with the scatter into the action tensors: action_type = argmax of the type logits (first maximum, like np.argmax),
  * device_indices = ascending ids whose value is > 0, exploit_indices = [argmax of the exploit values] ([0] when
  * n_exploits == 0), app_index = argmax of the app values (0 when n_apps == 0).  Values must be finite.  Writes group 0
  * of the rows like cygym_write_actions; n_devices must equal the handle's device count. */
@@ -407,6 +407,54 @@ typedef struct cygym_actor_mlp {
 } cygym_actor_mlp;
 int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cygym_action_vectors* layout,
                            const cygym_actions* dst, void* stream);
+
+/* The critic of the reference's actor-critic strategies (do_agent.py:373-388), all fp32:
+ *   Q(s, a) = fc3(relu(fc2(relu(fc1([s, a]))))),  fc1: W + n_out -> H1,  fc2: H1 -> H2,  fc3: H2 -> 1,
+ * W = width of the role view, n_out = n_types + n_devices + n_exploits + n_apps, handed over in the pieces the decode below
+ * reads.  DEVICE pointers. */
+typedef struct cygym_critic {
+  const float* h_state;    /* [n][h_stride] state part of fc1 per SOURCE row: b1 + W1[:, :W] s (any GEMM; under 0.1 % of the work) */
+  const float* w1a_t;      /* [n_out][H1] action part of fc1, transposed (k-major): w1a_t[j][k] = fc1.weight[k][W + j]           */
+  const float* w2;         /* fc2.weight PACKED like a hidden layer of cygym_actor_mlp: [H2 / 16][H1 / 16][64][4]                */
+  const float* b2;         /* [H2] or NULL                                                                                     */
+  const float* w3;         /* [H2] fc3.weight                                                                                  */
+  int16_t* pick_out;       /* optional [n][M]: the candidate c chosen for every device of source row r (tests; learners that
+                              store per-device choices)                                                                        */
+  float*   q_out;          /* optional [n][M]: its Q                                                                           */
+  double   tau;            /* softmax temperature of the pick (coord_tau, do_agent.py:527: 0.5), > 0                            */
+  float    b3;             /* fc3.bias                                                                                         */
+  int32_t  H1, H2;         /* multiples of 16, 16 .. 128                                                                       */
+  int32_t  h_stride;       /* floats per row of h_state, >= H1                                                                 */
+  int32_t  top_k;          /* coord_K (do_agent.py:526: 5), 1 .. 8; 1 = the arg-max candidate, no draw                          */
+  int32_t  reserved;
+} cygym_critic;
+
+/* Replaces: DoubleOracle.greedy_device_coord_ascent (do_agent.py:2137-2219) -- what decode_action returns in the reference's
+ * DEFAULT best-response mode `--BR_type Cord_asc` (do_agent.py:952-968; the actor's output is not read) -- for a batch, in ONE
+ * launch, fused with the scatter into the action tensors.  With T = n_types, D = n_devices, E = n_exploits and enc(t, dd, xx) the
+ * vector encode_action builds (:910-933: ones at t, T + dd, T + D + xx and, when n_apps > 0, T + D + E + 0; the reference
+ * raises for n_apps == 0, here: no app term), the candidates of device d are, in this order (the order is the tie-break):
+ *   c = 0                the no-op, enc(T - 1, 0, 0): the reference's tuple (T - 1, [], [0], 0) reaches encode_action with its
+ *                        exploit and device fields in swapped positions -- device bit 0 set, exploit one-hot 0
+ *   c = 1 + t E + x      (t outer, x inner) the tuple (t, [d], [x], 0), swapped as well; encode_action un-swaps it only when
+ *                        d >= E (:919-920): enc(t, d, x) for d >= E, enc(t, x, d) for d < E (device bit x, exploit one-hot d)
+ * Per device: Q in fp32 (layer 1 as four column adds onto h_state, fc2 on the matrix cores with fp32 inputs and accumulators);
+ * nan_to_num (NaN -> -1e9, +-inf -> +-1e9); stable descending sort (equal Q keeps ascending c); the first K' = min(top_k,
+ * T E + 1); p_i = exp(q_i / tau - q_0 / tau) / sum in f64 (the max-subtracted form: equal to the reference's exp(q_i / tau) / sum
+ * wherever that is finite; for |q / tau| > 700 the reference overflows to its uniform / nan_to_num fallbacks, this does not);
+ * the pick is the first i whose normalised running sum exceeds u = draw / 2^32 (np.random.choice), draw = the Philox word
+ * addressed (global env id, the env's current rng tick, CG_SITE_COORD_PICK, a = d).  top_k == 1 needs no draw.
+ * Merge (`best_q`, :2190-2203 -- the only branch of the reference that runs: the other one dies on an undefined name at :2214):
+ * a pick is a no-op iff its type is T - 1; device_indices = the ascending d with another pick; exploit_indices = [x of the lowest
+ * such d], else [0]; action_type = t of the acting pick with the largest Q (first maximum in ascending d), else T - 1, through
+ * `type_map`; app_index = 0.  Written as group 0 of the rows exactly like cygym_decode_actions, CG_DECODE_TRUNCATED included.
+ * From `layout`: rows, type_map, n_types, n_devices (= the handle's), n_exploits, n_apps, n, status.  Needs a bound handle (the
+ * rng ticks).  Limits (CYGYM_EUNSUPPORTED beyond): H1, H2 multiples of 16 in 16 .. 128, 1 <= n_types <= 32,
+ * 1 <= n_exploits <= CG_MAX_EXPLOITS (and <= n_devices), top_k <= 8.
+ * Out of scope: the training-mode noise coord_noise_std * randn (:2177-2178, only when critic.training), exploit_override
+ * (:2147-2149), and building the observation on chip (h_state comes from the caller). */
+int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* layout,
+                              const cygym_actions* dst, void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`

@@ -190,9 +190,12 @@ enum {
   CG_SITE_GROUP_PICK = 66,   /* IPPO.py:566-567 / MAPPO.py: random.choice(devs) of a single-device action type when
                                 per-device types are grouped (cygym_group_actions): a = action type; addressed by the
                                 env's rng tick like CG_SITE_EPS_TYPE                                              */
-  CG_SITE_SAMPLE = 67        /* IPPO.py:524-555 Categorical(logits).sample() of cygym_sample_group_actions: a = device id,
+  CG_SITE_SAMPLE = 67,       /* IPPO.py:524-555 Categorical(logits).sample() of cygym_sample_group_actions: a = device id,
                                 b = 0 (per-device type) / a = 0, b = 1 (exploit) / b = 2 (app); u = word 0 / 2^32 walks
                                 the inverse CDF of softmax(logits); same addressing                               */
+  CG_SITE_COORD_PICK = 68    /* do_agent.py:2185 np.random.choice(len(topk), p=probs) of greedy_device_coord_ascent
+                                (cygym_coord_ascent_decode): a = device id; u = word 0 / 2^32 walks the inverse CDF of the
+                                top-K softmax; same addressing                                                     */
 };
 
 /* ---- Philox4x32-10 (Salmon et al., SC'11), counter-based ----

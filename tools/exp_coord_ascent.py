@@ -1,0 +1,78 @@
+"""Microbenchmark: cygym_coord_ascent_decode (the coordinate-ascent decode through the critic, one launch) at 4096 envs x 256
+devices with the reference's critic (T = 14, E = 6, 128 x 128), HIP events after warm-up: us per decision and the fraction of
+the 155 TF the fp32 matrix instructions reach (layer 2 alone: 2 * M * T * E * H1 * H2 FLOP per env, 2.9 TFLOP per launch) --
+and, at a size the torch path can hold (256 envs, chunked), the same decode with torch ops in float32 on the device.
+One JSON line per measurement."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+from cygym_amd import abi  # noqa: E402
+from cygym_amd.batched_env import BatchedCyberDefenseEnv  # noqa: E402
+from cygym_amd.policies import CoordAscentPolicy, coord_ascent_merge, coord_ascent_q, reference_critic  # noqa: E402
+from cygym_amd.topology import make_topology  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=4096)
+ap.add_argument("--torch-envs", type=int, default=256)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--warmup", type=int, default=2)
+args = ap.parse_args()
+
+M, T, E, A, H = 256, 14, 6, 3, 128
+PEAK = 155e12
+dev = "cuda:0"
+topo, init, ck = make_topology(M, 1, seed=0, max_extra=0)
+cfg = abi.EnvConfig(seed=0, lambda_events=0.0, **ck)
+env = BatchedCyberDefenseEnv(topo, cfg, args.envs, init, device=dev, max_groups=1, max_devs=M)
+env.randomize()
+obs = env.observe(1)                                  # [N, 6 M] defender views
+critic = reference_critic(6 * M, T + M + E + A, seed=1, device=dev, hidden=(H, H))
+flop = 2.0 * M * T * E * H * H                        # layer 2 per env: the rows the reference evaluates (no padding, no no-op)
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return sorted(ms)
+
+
+for top_k in (5, 1):
+    pol = CoordAscentPolicy(critic, T, E, A, top_k=top_k)
+    w1s_t, b1, pack = pol._packed(env, M)
+    h_state = torch.addmm(b1, obs, w1s_t)
+    ms = timed(lambda: env.coord_ascent_decode(None, h_state, pack, T, E, A, None, top_k=top_k, tau=0.5), args.reps, args.warmup)
+    med = ms[len(ms) // 2]
+    print(json.dumps({"what": "cygym_coord_ascent_decode", "envs": args.envs, "devices": M, "types": T, "exploits": E, "H1": H, "H2": H,
+                      "top_k": top_k, "ms_per_launch": round(med, 3), "ms_min_max": [round(ms[0], 3), round(ms[-1], 3)],
+                      "us_per_decision": round(med * 1e3 / args.envs, 3), "tflop_per_launch": round(flop * args.envs / 1e12, 3),
+                      "fraction_of_155TF": round(flop * args.envs / (med * 1e-3) / PEAK, 4)}))
+    ms = timed(lambda: pol.write(env, env.act, None, obs), args.reps, args.warmup)
+    print(json.dumps({"what": "CoordAscentPolicy.write (addmm + launch)", "top_k": top_k, "ms": round(ms[len(ms) // 2], 3)}))
+assert env.take_status() & abi.DECODE_TRUNCATED == 0
+
+n = min(args.torch_envs, args.envs)
+o = obs[:n].contiguous()
+
+
+def torch_path():
+    q = coord_ascent_q(o, critic.fc1, critic.fc2, critic.fc3, T, M, E, A, dtype=torch.float32)
+    q = torch.nan_to_num(q, nan=-1e9, posinf=1e9, neginf=-1e9)
+    pick = torch.argmax(q, dim=2)
+    return coord_ascent_merge(pick, q.gather(2, pick[:, :, None])[:, :, 0], T, E)
+
+
+ms = timed(torch_path, max(2, args.reps // 2), 1)
+med = ms[len(ms) // 2]
+print(json.dumps({"what": "torch ops, float32, top_k = 1 (chunked)", "envs": n, "ms": round(med, 3), "us_per_decision": round(med * 1e3 / n, 3),
+                  "fraction_of_155TF": round(flop * n / (med * 1e-3) / PEAK, 4)}))

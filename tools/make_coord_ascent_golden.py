@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""Record tests/golden/coord_ascent/*.npz from the REFERENCE's own DoubleOracle.greedy_device_coord_ascent
+(do_agent.py:2137-2219) -- for a machine that has the reference checkout (REFERENCE_DIR, default ../reference next to the
+repository); exits with a message where it is absent.
+
+The method is called unbound on a stub that holds what it reads of `self`: encode_action / one_hot_encode bound from the
+class, coord_K, coord_tau and merge_rule_atype = "best_q".  The critic is this script's own small module with the
+reference's forward(state, action) (widths 32, default-initialised, .eval()), so the fixtures hold no reference weights.
+np.random.choice is swapped for the inverse CDF on the addressed Philox draws (cygym_amd/rng.py, site COORD_PICK, a = device),
+and the critic's forward is wrapped to record Q.
+
+A fixture holds arrays only:
+  fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b   the critic
+  dims = (M, T, E, A, W, top_k), tau, seed, env_ids [n] (global ids), ticks [n] (the envs' rng ticks), draws [n, M] u32 (u = draws / 2^32)
+  states [n, W] f32
+  top_c [n, M, K' + 1] u8, top_q [n, M, K' + 1] f32   the reference's candidates in ITS sorted order (stable, descending) with the
+                                                      Q its critic returned: the first K' + 1 (the K' it samples from, and the
+                                                      next one, whose gap decides whether the cut is clear)
+  choice [n, M] u8, pick [n, M] u8                    the index np.random.choice returned, and the candidate it stands for
+  q_err_f64 [2]                                       max |Q_reference - Q_f64| over ALL candidates, and max |Q_f64|
+  atype [n], exploit [n], dev_mask [n, M] u8          the merged tuple the reference returned (app index is 0)
+(The reference's Q of every candidate would be 260 KB for the defender fixture; the pick depends on the sorted head only.)
+"""
+import os
+import sys
+import tempfile
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF = os.environ.get("REFERENCE_DIR", os.path.join(os.path.dirname(ROOT), "reference"))
+
+# name: (M, T, E, A, W, states, seed).  The seed initialises the critic too, and how many devices have a near-tie among their
+# best six candidates depends on it: 3 % to 17 % at a margin of 1e-4 over the seeds 0xC0DE70..77 at the attacker shape (about 1 % at
+# 1e-5 for all of them).  The seeds below are ones at which the cap asserted further down holds.
+FIXTURES = {
+    "def12": (12, 14, 6, 3, 72, 64, 0xC0DE12),
+    "att70": (70, 3, 6, 2, 286, 16, 0xC0DE72),
+}
+TOP_K, TAU, GEN_MARGIN = 5, 0.5, 1e-4
+
+
+def main():
+    if not os.path.exists(os.path.join(REF, "do_agent.py")):
+        sys.exit(f"the reference checkout is not at {REF} (set REFERENCE_DIR): nothing recorded")
+    sys.dont_write_bytecode = True
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle", "harness", "standins"), REF]
+    sys.modules.setdefault("nashpy", types.ModuleType("nashpy"))
+    import numpy as np
+    import torch
+    from torch import nn
+    from cygym_amd import rng as R
+    from cygym_amd import spec as S
+    from cygym_amd.policies import coord_ascent_q
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)            # importing the reference writes cyberdefense_debug.log into the cwd
+        try:
+            import do_agent
+        finally:
+            os.chdir(cwd)
+    DO = do_agent.DoubleOracle
+
+    class SmallCritic(nn.Module):   # the reference's forward(state, action), widths 32
+        def __init__(self, sd, ad):
+            super().__init__()
+            self.fc1, self.fc2, self.fc3 = nn.Linear(sd + ad, 32), nn.Linear(32, 32), nn.Linear(32, 1)
+
+        def forward(self, state, action):
+            x = torch.relu(self.fc1(torch.cat([state, action], 1)))
+            return self.fc3(torch.relu(self.fc2(x)))
+
+    stub = types.SimpleNamespace(coord_K=TOP_K, coord_tau=TAU, merge_rule_atype="best_q", coord_noise_std=0.0)
+    stub.encode_action = types.MethodType(DO.encode_action, stub)
+    stub.one_hot_encode = types.MethodType(DO.one_hot_encode, stub)
+
+    for name, (M, T, E, A, W, n, seed) in FIXTURES.items():
+        torch.manual_seed(seed)
+        critic = SmallCritic(W, T + M + E + A).eval()
+        with torch.no_grad():      # the low 12 mantissa bits of every weight cleared: the fixtures then compress to under 80 KB
+            for p in critic.parameters():
+                p.copy_((p.view(torch.int32) & -4096).view(torch.float32))
+        rs = np.random.RandomState(seed)
+        # role-view-like states: the values a view holds (-1 hidden, flags 0 / 1, small version / OS numbers)
+        states = rs.choice(np.array([-1.0, 0.0, 0.25, 0.5, 1.0, 2.0], np.float32), size=(n, W)).astype(np.float32)
+        env_ids = (1000 + rs.permutation(4 * n)[:n]).astype(np.int64)
+        ticks = rs.randint(0, 500, size=n).astype(np.int32)
+        draws = np.stack([R.draw_np(seed, int(env_ids[i]), int(ticks[i]), S.SITE_COORD_PICK, np.arange(M), 0) for i in range(n)]).astype(np.uint32)
+        C, K1 = T * E + 1, min(TOP_K, T * E + 1) + 1
+        top_c, top_q = np.zeros((n, M, K1), np.uint8), np.zeros((n, M, K1), np.float32)
+        choice, pick = np.zeros((n, M), np.uint8), np.zeros((n, M), np.uint8)
+        atype, exploit, dev_mask = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, M), np.uint8)
+        q_all = np.zeros((n, M, C), np.float32)
+        real_forward, real_choice = critic.forward, np.random.choice
+        for i in range(n):
+            rec, ch = [], []
+
+            def forward(state, action):
+                out = real_forward(state, action)
+                rec.append(out.detach().squeeze(1).numpy().copy())
+                return out
+
+            def addressed_choice(k, p=None):
+                cdf = np.cumsum(np.asarray(p, np.float64))
+                cdf /= cdf[-1]
+                ch.append(int(np.searchsorted(cdf, float(draws[i, len(ch)]) / 4294967296.0, side="right")))
+                return ch[-1]
+
+            critic.forward, np.random.choice = forward, addressed_choice
+            try:
+                res = DO.greedy_device_coord_ascent(stub, T, M, E, A, torch.from_numpy(states[i:i + 1]), None, None, critic)
+            finally:
+                critic.forward, np.random.choice = real_forward, real_choice
+            assert len(ch) == M and len(rec) == 1 + 2 * M and rec[0].shape == (1,) and all(r.shape == (T * E,) for r in rec[1:1 + M])
+            for d in range(M):
+                q = np.concatenate([rec[0], rec[1 + d]])
+                q_all[i, d] = q
+                order = np.argsort(-q.astype(np.float64), kind="stable")          # list.sort(reverse=True) is stable
+                top_c[i, d], top_q[i, d] = order[:K1], q[order[:K1]]
+                choice[i, d], pick[i, d] = ch[d], order[ch[d]]
+            atype[i], exploit[i] = int(res[0]), int(res[1][0])
+            dev_mask[i, np.asarray(res[2], int)] = 1
+            assert int(res[3]) == 0
+            # the picks explain the merged tuple (best_q): acting devices, first exploit, type of the best acting pick
+            t_of = np.where(pick[i] > 0, (pick[i].astype(int) - 1) // E, T - 1)
+            on = t_of != T - 1
+            assert (dev_mask[i] == on).all()
+            assert exploit[i] == ((pick[i, on.argmax()] - 1) % E if on.any() else 0)
+        q64 = coord_ascent_q(torch.from_numpy(states), critic.fc1, critic.fc2, critic.fc3, T, M, E, A).numpy()
+        qmax = float(np.abs(q64).max())
+        err = float(np.abs(q_all.astype(np.float64) - q64).max())
+        # the reference alone must leave the tests' cap (10 % of the devices unclear) room at a margin of 1e-4
+        Kp = K1 - 1
+        gaps = (top_q[:, :, :-1].astype(np.float64) - top_q[:, :, 1:]).min(axis=2)
+        e = np.exp((top_q[:, :, :Kp].astype(np.float64) - top_q[:, :, :1]) / TAU)
+        cdf = np.cumsum(e, axis=2) / e.sum(axis=2, keepdims=True)
+        u = draws.astype(np.float64) / 4294967296.0
+        near = np.abs(cdf[:, :, :-1] - u[:, :, None]).min(axis=2)
+        unclear = float(((gaps <= GEN_MARGIN * qmax) | (near <= GEN_MARGIN)).mean())
+        assert err <= GEN_MARGIN / 8 * qmax, (name, err, qmax)
+        assert unclear <= 0.10, (name, unclear)
+        sd = {k: v.detach().numpy() for k, v in critic.state_dict().items()}
+        os.makedirs(os.path.join(ROOT, "tests", "golden", "coord_ascent"), exist_ok=True)
+        path = os.path.join(ROOT, "tests", "golden", "coord_ascent", name + ".npz")
+        np.savez_compressed(path, fc1_w=sd["fc1.weight"], fc1_b=sd["fc1.bias"], fc2_w=sd["fc2.weight"], fc2_b=sd["fc2.bias"],
+                            fc3_w=sd["fc3.weight"], fc3_b=sd["fc3.bias"], dims=np.array([M, T, E, A, W, TOP_K], np.int32),
+                            tau=np.array(TAU), seed=np.array(seed, np.int64), env_ids=env_ids, ticks=ticks, draws=draws, states=states,
+                            top_c=top_c, top_q=top_q, choice=choice, pick=pick, q_err_f64=np.array([err, qmax]),
+                            atype=atype, exploit=exploit, dev_mask=dev_mask)
+        print(f"{name}: {os.path.getsize(path)} bytes, max |Q_ref - Q_f64| = {err:.3g} (max |Q| = {qmax:.3g}), "
+              f"{100 * unclear:.1f} % of the devices unclear at a margin of {GEN_MARGIN:g}, "
+              f"{int((choice > 0).sum())} of {n * M} picks are not the arg-max, {int(dev_mask.sum())} acting devices")
+
+
+if __name__ == "__main__":
+    main()
