@@ -27,6 +27,7 @@ class CygymError(RuntimeError):
     code = None
 
 
+EINVAL = -1
 EUNSUPPORTED = -3
 
 

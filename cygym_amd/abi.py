@@ -13,7 +13,7 @@ import numpy as np
 from . import rng as R
 from . import spec as S
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
@@ -119,8 +119,8 @@ class DeviceLogits(C.Structure):
 
 class Critic(C.Structure):
     _fields_ = [("h_state", C.c_void_p), ("w1a_t", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
-                ("pick_out", C.c_void_p), ("q_out", C.c_void_p), ("tau", C.c_double), ("b3", C.c_float), ("H1", C.c_int32),
-                ("H2", C.c_int32), ("h_stride", C.c_int32), ("top_k", C.c_int32), ("reserved", C.c_int32)]
+                ("pick_out", C.c_void_p), ("q_out", C.c_void_p), ("vec_out", C.c_void_p), ("tau", C.c_double), ("noise_std", C.c_double),
+                ("b3", C.c_float), ("H1", C.c_int32), ("H2", C.c_int32), ("h_stride", C.c_int32), ("top_k", C.c_int32), ("vec_stride", C.c_int32)]
 
 
 DECODE_TRUNCATED = 0x10000

@@ -605,7 +605,8 @@ class BatchedCyberDefenseEnv:
                    self._h, "cygym_actor_mlp_decode")
 
     def coord_ascent_decode(self, rows, h_state: torch.Tensor, critic_pack, n_types: int, n_exploits: int | None = None,
-                            n_apps: int = 0, type_map=None, act=None, top_k: int = 5, tau: float = 0.5, pick_out=None, q_out=None):
+                            n_apps: int = 0, type_map=None, act=None, top_k: int = 5, tau: float = 0.5, pick_out=None, q_out=None,
+                            noise_std: float = 0.0, vec_out=None):
         """DoubleOracle.greedy_device_coord_ascent (do_agent.py:2137-2219: decode_action in the reference's default
         best-response mode `Cord_asc`) for a batch, fused with the scatter into rows `rows` of `act` (group 0): ONE launch
         (cygym_coord_ascent_decode; include/cygym_abi.h states the candidates, the pick and the merge).
@@ -614,6 +615,12 @@ class BatchedCyberDefenseEnv:
                        b2 [H2] or None, w3 [H2] = fc3.weight, b3 = float(fc3.bias); n_out = n_types + M + n_exploits + n_apps
           top_k, tau   coord_K, coord_tau (do_agent.py:526-527); top_k = 1: the arg-max candidate, no draw
           pick_out     optional [n, M] int16: receives the candidate chosen per device;  q_out optional [n, M] float32: its Q
+                       (the critic's own, also with noise)
+          noise_std    coord_noise_std (do_agent.py:528) while the critic trains: the sort, the top K and the pick run on
+                       Q + noise_std * z, z the normal addressed (env, rng tick, SITE_COORD_NOISE, device, candidate); the
+                       no-op gets none; the merge takes the clean Q.  0: eval mode, no noise
+          vec_out      optional [n, >= n_out] float32 (unit inner stride): row r receives encode_action of the merged tuple
+                       (what the reference's replay buffer stores in this mode, :1424); columns past n_out stay untouched
         Limits: H1, H2 multiples of 16 in 16..128, n_types <= 32, top_k <= 8 (the library answers CYGYM_EUNSUPPORTED)."""
         dst = self.actions_struct(act)
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
@@ -640,6 +647,12 @@ class BatchedCyberDefenseEnv:
                 if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n, self.M):
                     raise ValueError(f"{name} must be a contiguous {dt} {[n, self.M]} tensor on {self.device}")
                 setattr(cr, name, t.data_ptr())
+        cr.noise_std = float(noise_std)
+        if vec_out is not None:
+            if not ok(vec_out) or vec_out.dim() != 2 or int(vec_out.shape[0]) != n or int(vec_out.shape[1]) < n_out or vec_out.stride(1) != 1 \
+                    or (n > 1 and vec_out.stride(0) < int(vec_out.shape[1])):
+                raise ValueError(f"vec_out must be a float32 [{n}, >= {n_out}] tensor on {self.device} with unit inner stride")
+            cr.vec_out, cr.vec_stride = vec_out.data_ptr(), int(vec_out.stride(0)) if n > 1 else int(vec_out.shape[1])
         _lib.check(self.lib.cygym_coord_ascent_decode(self._h, C.byref(cr), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_coord_ascent_decode")
 

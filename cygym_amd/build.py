@@ -26,7 +26,7 @@ RESOURCES = os.path.join(HERE, "build_resources.json")
 
 
 def _parse_resources(text: str) -> dict:
-    """kernel name -> {vgprs, sgpr_spill, vgpr_spill, scratch} from -Rpass-analysis=kernel-resource-usage."""
+    """kernel name -> {vgprs, sgprs, sgpr_spill, vgpr_spill, scratch, lds, occupancy} from -Rpass-analysis=kernel-resource-usage."""
     out, cur = {}, None
     for line in text.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
@@ -37,7 +37,8 @@ def _parse_resources(text: str) -> dict:
             continue
         for key, pat in (("vgprs", r"\bVGPRs: (\d+)"), ("sgpr_spill", r"SGPRs Spill: (\d+)"),
                          ("vgpr_spill", r"VGPRs Spill: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
+                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)"), ("sgprs", r"\bTotalSGPRs: (\d+)"),
+                         ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
             m = re.search(pat, line)
             if m:
                 cur[key] = int(m.group(1))

@@ -19,6 +19,12 @@
 //     ~c) -- descending Q, ascending c among equals: the reference's stable sort --, the softmax pick in f64 from ONE exp per
 //     lane, the addressed Philox draw.  Neither candidate rows nor Q values reach HBM.
 //   * Wave 0 merges the per-device picks (LDS) into the row's action and writes group 0 like cygym_decode_actions.
+// Training mode (NOISE; do_agent.py:2177-2178, cygym_critic.noise_std > 0): in the top-K' phase lane l draws the normals of its own
+// candidates l + 64 i (CG_SITE_COORD_NOISE, one Philox call and one f64 Box-Muller each) and keeps the noisy scores
+//   s_c = (float)((double)q_c + noise_std z(d, c)),  c >= 1;   s_0 = q_0
+// in registers: the arg-max rounds, the softmax and the pick run on s, the merge on the CLEAN q of the picked candidate, read from
+// the wave's Q row as before.  No additional LDS.  VEC (cygym_critic.vec_out): wave 0 also writes encode_action of the merged
+// tuple.  The instantiations <SAMPLE, false, false> are the eval-mode kernels and hold none of this.
 constexpr int CA_WAVES = 16, CA_THREADS = CA_WAVES * WAVE, CA_QROW = 256, CA_MAX_H = 128, CA_MAX_TYPES = 32, CA_MAX_TOPK = 8;
 static_assert(CA_MAX_TYPES * CG_MAX_EXPLOITS + 1 <= CA_QROW, "a device's candidates fit the per-wave Q row (four per lane)");
 
@@ -53,8 +59,51 @@ __device__ __forceinline__ float ca_nan_to_num(float q) {   // np.nan_to_num(qv,
   return q != q ? -1e9f : q > 3.4028234e38f ? 1e9f : q < -3.4028234e38f ? -1e9f : q;
 }
 
-// SAMPLE = false: top_k == 1 (the arg-max candidate, no draw, no f64)
-template <bool SAMPLE>
+// A f64 constant that is made where it is used: the compiler otherwise hoists every polynomial coefficient of the normal out of
+// the device loop into a VGPR pair of its own (about 25 pairs), which the matrix-core phase has no room for.  Scalar moves instead.
+__device__ __forceinline__ double ca_k(double c) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, c);
+  uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
+  asm volatile("" : "+s"(lo), "+s"(hi));
+  return __hiloint2double((int)hi, (int)lo);
+}
+// z(d, c): the standard normal addressed (env, tick, CG_SITE_COORD_NOISE, a = d, b = c), cygym_spec.h:
+//   u1 = (word 0 + 1) / 2^32, u2 = word 1 / 2^32, z = sqrt(-2 ln u1) cos(2 pi u2)   in f64.
+// Both transcendentals are evaluated from the integer words with the reduced-argument polynomials of fdlibm, so neither needs a
+// general argument reduction: z agrees with the f64 library value of the formula to a few 1e-16.
+__device__ __forceinline__ double ca_normal(uint32_t env, uint32_t tick, int d, int c, uint64_t seed) {
+  const cg_u32x4 w = cg_philox4x32_10(env, tick, CG_SITE_COORD_NOISE, ((uint32_t)d & 0xFFFFu) | ((uint32_t)c << 16), (uint32_t)seed,
+                                      (uint32_t)(seed >> 32));
+  // ln u1 = ln(n) - 32 ln 2, n = word 0 + 1 = 2^e m exactly, m in [sqrt(1/2), sqrt(2)): ln m = f - hfsq + s (hfsq + R(s^2)), f = m - 1, s = f / (2 + f)
+  const double n = (double)w.v[0] + 1.0;
+  int e = __builtin_amdgcn_frexp_exp(n);
+  double m = __builtin_amdgcn_frexp_mant(n);            // [1/2, 1)
+  const bool low = m < ca_k(7.07106781186547524401e-01);
+  m = low ? m + m : m;
+  e = low ? e - 1 : e;
+  const double dk = (double)(e - 32), f = m - 1.0, s = f / (2.0 + f), z2 = s * s, w4 = z2 * z2, hfsq = 0.5 * f * f;
+  const double t1 = w4 * (ca_k(3.999999999940941908e-01) + w4 * (ca_k(2.222219843214978396e-01) + w4 * ca_k(1.531383769920937332e-01)));
+  const double t2 = z2 * (ca_k(6.666666666666735130e-01) + w4 * (ca_k(2.857142874366239149e-01) + w4 * (ca_k(1.818357216161805012e-01) +
+                    w4 * ca_k(1.479819860511658591e-01))));
+  const double ln_u1 = dk * ca_k(6.93147180369123816490e-01) - ((hfsq - (s * (hfsq + (t2 + t1)) + dk * ca_k(1.90821492927058770002e-10))) - f);
+  // cos(2 pi u2): the word's top three bits are the octant, so the angle is reduced exactly in integers to y = 2 pi g, |g| <= 1/8,
+  // around the nearest multiple k of pi / 2
+  const uint32_t oct = w.v[1] >> 29, k = ((oct + 1u) >> 1) & 3u;
+  const int32_t gi = (int32_t)(w.v[1] & 0x1FFFFFFFu) - ((oct & 1u) ? (1 << 29) : 0);
+  const double y = ca_k(6.283185307179586) * ldexp((double)gi, -32), z = y * y;
+  const double sn = y + y * z * (ca_k(-1.66666666666666324348e-01) + z * (ca_k(8.33333333332248946124e-03) + z * (ca_k(-1.98412698298579493134e-04) +
+                    z * (ca_k(2.75573137070700676789e-06) + z * (ca_k(-2.50507602534068634195e-08) + z * ca_k(1.58969099521155010221e-10))))));
+  const double cs = 1.0 - (0.5 * z - z * z * (ca_k(4.16666666666666019037e-02) + z * (ca_k(-1.38888888888741095749e-03) + z * (ca_k(2.48015872894767294178e-05) +
+                    z * (ca_k(-2.75573143513906633035e-07) + z * (ca_k(2.08757232129817482790e-09) + z * ca_k(-1.13596475577881948265e-11)))))));
+  const double c2 = k == 0u ? cs : k == 1u ? -sn : k == 2u ? -cs : sn;
+  return sqrt(-2.0 * ln_u1) * c2;
+}
+__device__ __forceinline__ float ca_order_bits_float(uint32_t b) {   // the inverse of float_order_bits
+  return __uint_as_float((b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b);
+}
+
+// SAMPLE = false: top_k == 1 (the arg-max candidate, no draw; no f64 unless NOISE).  NOISE: noise on the scores.  VEC: vec_out.
+template <bool SAMPLE, bool NOISE, bool VEC>
 __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic cr, cygym_action_vectors src, cygym_actions dst, int n_envs,
                                                                   const int32_t* ienv, uint64_t seed, int64_t env_id_base) {
   extern __shared__ __align__(16) uint8_t smem[];
@@ -95,7 +144,7 @@ __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic c
     }
   }
   uint32_t tick = 0;
-  if constexpr (SAMPLE) tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];
+  if constexpr (SAMPLE || NOISE) tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];
   __syncthreads();
   float* bw = lds + pl.wave0 + wave * pl.wave_pitch;   // this wave's base row, then its Q row
   float* qb = bw + hp;
@@ -166,10 +215,22 @@ __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic c
     __builtin_amdgcn_wave_barrier();
     // ---- top-K': K' rounds of a wave-wide arg-max over (order bits of Q, ~c); four candidates per lane ----
     uint32_t kh[4];
+    if constexpr (NOISE) {
+      kh[0] = kh[1] = kh[2] = kh[3] = 0u;
+#pragma unroll 1
+      for (int i = 0; WAVE * i <= TE; ++i) {   // (uniform; one normal at a time: four interleaved f64 chains would not fit the registers)
+        const int c = lane + WAVE * i;      // the lane's own normal; the no-op (c = 0) and the lanes past the end take none
+        const float qc = qb[c <= TE ? c : 0];
+        const float sv = (float)((double)qc + cr.noise_std * ca_normal((uint32_t)(env_id_base + row), tick, d, c >= 1 && c <= TE ? c : 1, seed));
+        const uint32_t ob = c <= TE ? float_order_bits(c >= 1 ? sv : qc) : 0u;
+        kh[0] = i == 0 ? ob : kh[0]; kh[1] = i == 1 ? ob : kh[1]; kh[2] = i == 2 ? ob : kh[2]; kh[3] = i == 3 ? ob : kh[3];
+      }
+    } else {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane + WAVE * i;
-      kh[i] = c <= TE ? float_order_bits(qb[c <= TE ? c : 0]) : 0u;
+      for (int i = 0; i < 4; ++i) {
+        const int c = lane + WAVE * i;
+        kh[i] = c <= TE ? float_order_bits(qb[c <= TE ? c : 0]) : 0u;
+      }
     }
     constexpr int NK = SAMPLE ? CA_MAX_TOPK : 1;
     float sq[NK];
@@ -185,7 +246,8 @@ __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic c
         dpp_pair_max(bh, bl);
         const int cw = (int)~(uint32_t)__builtin_amdgcn_readlane((int)bl, 63);
         sc[k] = cw;
-        sq[k] = qb[cw];
+        if constexpr (NOISE) sq[k] = ca_order_bits_float((uint32_t)__builtin_amdgcn_readlane((int)bh, 63));   // the winner's noisy score
+        else sq[k] = qb[cw];
 #pragma unroll
         for (int i = 0; i < 4; ++i) kh[i] = cw == lane + WAVE * i ? 0u : kh[i];
       }
@@ -220,6 +282,7 @@ __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic c
         }
       }
     }
+    if constexpr (NOISE) pq = qb[pc];   // the merge and q_out take the CLEAN Q of the pick (do_agent.py:2196-2198)
     if (lane == 0) {
       q_dev[d] = pq;
       pick_dev[d] = (int16_t)pc;
@@ -254,6 +317,22 @@ __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic c
   const uint32_t rh = (uint32_t)__builtin_amdgcn_readlane((int)bh, 63), rl = (uint32_t)__builtin_amdgcn_readlane((int)bl, 63);
   int at = T - 1;
   if (rh != 0u) at = ((int)pick_dev[(int)~rl] - 1) / E;
+  if constexpr (VEC) {
+    // encode_action of the merged tuple (do_agent.py:910-933 as :1424 calls it), every element from the picks in LDS: the type
+    // INDEX (before type_map), the whole device mask (also where the list is cut at max_devs), the exploit, app 0
+    const int n_out = T + M + E + src.n_apps, xe = ex < 0 ? 0 : ex;
+    float* vo = cr.vec_out + (size_t)srow * cr.vec_stride;
+    for (int j = lane; j < n_out; j += WAVE) {
+      bool one;
+      if (j < T) one = j == at;
+      else if (j < T + M) {
+        const int c = (int)pick_dev[j - T];
+        one = c > 0 && (c - 1) / E != T - 1;
+      } else if (j < T + M + E) one = j - T - M == xe;
+      else one = j == T + M + E;
+      vo[j] = one ? 1.f : 0.f;
+    }
+  }
   if (src.type_map) at = src.type_map[at];
   const int cnt = base < L ? base : L;
   for (int q = cnt + lane; q < L; q += WAVE) out[q] = 0;

@@ -54,8 +54,14 @@ extern template __global__ void tick_actor_kernel<6>(const KParams, cygym_actor_
 
 // the coordinate-ascent decode lives in its own unit (cg_inst_coord.hip): declared, not instantiated, here
 namespace cygym_k {
-extern template __global__ void coord_ascent_kernel<false>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
-extern template __global__ void coord_ascent_kernel<true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<false, false, false>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<true, false, false>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<false, false, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<true, false, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<false, true, false>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<true, true, false>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<false, true, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_ascent_kernel<true, true, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
 }  // namespace cygym_k
 
 // =====================================================================
@@ -756,12 +762,22 @@ int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygy
   if (src->n_types > CA_MAX_TYPES || src->n_exploits > CG_MAX_EXPLOITS || src->n_exploits > src->n_devices || c->top_k > CA_MAX_TOPK)
     return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: at most 32 action types, CG_MAX_EXPLOITS exploits (and no more than devices), top_k <= 8%s", "");
   if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: bad row count%s", "");
+  if (!(c->noise_std >= 0.0) || !(c->noise_std < 1e300))
+    return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: noise_std must be finite and >= 0%s", "");
+  if (c->vec_out && c->vec_stride < src->n_types + src->n_devices + src->n_exploits + src->n_apps)
+    return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: vec_stride is smaller than n_out = n_types + n_devices + n_exploits + n_apps%s", "");
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   const CaPlan pl = ca_plan(c->H1, c->H2, src->n_types, src->n_exploits, src->n_devices);
   const size_t lds = (size_t)pl.total * sizeof(float);
   if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: the critic does not fit in LDS%s", "");
-  const void* k = c->top_k > 1 ? (const void*)coord_ascent_kernel<true> : (const void*)coord_ascent_kernel<false>;
+  // <SAMPLE, NOISE, VEC>: noise_std == 0 and vec_out == NULL select the eval-mode kernels
+  static const void* const kernels[8] = {
+      (const void*)coord_ascent_kernel<false, false, false>, (const void*)coord_ascent_kernel<true, false, false>,
+      (const void*)coord_ascent_kernel<false, true, false>,  (const void*)coord_ascent_kernel<true, true, false>,
+      (const void*)coord_ascent_kernel<false, false, true>,  (const void*)coord_ascent_kernel<true, false, true>,
+      (const void*)coord_ascent_kernel<false, true, true>,   (const void*)coord_ascent_kernel<true, true, true>};
+  const void* k = kernels[(c->top_k > 1 ? 1 : 0) | (c->noise_std > 0.0 ? 2 : 0) | (c->vec_out ? 4 : 0)];
   if (const int rc = raise_lds_once(h, k)) return rc;
   int n_envs = h->n_envs;
   const int32_t* ienv = h->b.ienv;

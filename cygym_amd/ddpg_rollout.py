@@ -13,6 +13,12 @@ at once, all tensors on the device:
 Here the actor runs once for all envs, the noise is one batched draw, decode_action + the scatter into the action tensors is
 ONE launch (cygym_decode_actions: the action vectors have to exist in HBM anyway -- the replay buffer stores them) and the
 tick writes the learner's next view itself.  `train_ddpg` (the update on the replay buffer) is the caller's.
+
+In the reference's DEFAULT mode (`--BR_type Cord_asc`) decode_action does not read `vec`: it is greedy_device_coord_ascent on the
+critic (:1375-1380 -> :952-968), in training mode with noise on Q (:2177-2178), and the replay buffer stores
+encode_action(action) of the merged tuple instead (:1421-1425).  collect(decoder=CoordAscentPolicy) runs that: one launch decodes,
+scatters and writes the encoded action (cygym_coord_ascent_decode with vec_out); the actor is not evaluated (the reference
+computes raw + noise there and never reads it), the sigma schedule still advances once per decision (:1372).
 """
 from __future__ import annotations
 
@@ -28,7 +34,8 @@ from . import spec as S
 class Transitions:
     """What the loop pushes into the replay buffer (do_agent.py:1424), stacked: [T, N, ...] device tensors."""
     state: torch.Tensor        # [T, N, W] the learner's view at the decision
-    action_vec: torch.Tensor   # [T, N, n_out] the clipped noisy action vector that was decoded
+    action_vec: torch.Tensor   # [T, N, n_out] the clipped noisy action vector that was decoded; with a `decoder` (Cord_asc mode):
+                               # encode_action of the action that was stepped (do_agent.py:1424)
     reward: torch.Tensor       # [T, N] float64 shaped reward (the third return of env.step)
     raw_reward: torch.Tensor   # [T, N] float64
     next_state: torch.Tensor   # [T, N, W] the learner's view right after its own step.  On a row whose step reported `done` (batches
@@ -41,18 +48,28 @@ class Transitions:
 @torch.no_grad()
 def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n_exploits: int | None = None, n_apps: int = 0, *,
             type_map=None, noise_std: float = 0.0, sigma_min: float = 0.0, decay_rate: float = 1.0, clip=(-1.0, 1.0), generator=None,
-            t0: int = 0) -> Transitions:
+            t0: int = 0, decoder=None) -> Transitions:
     """Collect `n_decisions` transitions of `role` in every env of `batch` (the for-loop of do_agent.py:1334-1460 without the
     update).  actor(state [N, W]) -> [N, n_types + M + n_exploits + n_apps] action vectors; opponent: a baseline name / fixed
     sequence, a policy(obs, t, M, L) -> action tensors, or an object with write(batch, act, rows, obs).  The loop's tick
     counter starts at `t0` (turns follow t % 2 like the reference's, not the envs' step_num).  The reference leaves its loop
-    at the first done (:1439); a batch goes on: with auto_reset the env restarts from its snapshot, and `done` marks the row."""
+    at the first done (:1439); a batch goes on: with auto_reset the env restarts from its snapshot, and `done` marks the row.
+    decoder: a policies.CoordAscentPolicy -- the reference's `Cord_asc` mode: on the learner's turn decoder.write(batch, act, rows,
+    state, vec_out=...) decodes through the critic (with the policy's training-mode noise) and `action_vec` records the encoded
+    action; `actor` may be None and is not evaluated; n_types / n_exploits / n_apps (and type_map, when given) must be the decoder's own
+    (ValueError otherwise)."""
     from .rollout_grid import SequencePolicy, _baseline_code
     if role not in (HL.DEFENDER, HL.ATTACKER):
         raise ValueError("role must be 'attacker' or 'defender'")
     other = HL.ATTACKER if role == HL.DEFENDER else HL.DEFENDER
     N, M, L, dev = batch.N, batch.M, batch.L, batch.device
     n_exploits = batch.cfg.max_exploits if n_exploits is None else int(n_exploits)
+    n_out = int(n_types) + M + n_exploits + int(n_apps)
+    if decoder is not None:
+        dtm = None if decoder.type_map is None else [int(x) for x in decoder.type_map.tolist()]
+        if (decoder.n_types, decoder.n_exploits, decoder.n_apps) != (int(n_types), n_exploits, int(n_apps)) or decoder.n_out(M) != n_out \
+                or (type_map is not None and [int(x) for x in torch.as_tensor(type_map).tolist()] != dtm):
+            raise ValueError("decoder: its n_types / n_exploits / n_apps / type_map differ from the ones collect() was called with")
     opp = opponent if (callable(opponent) or hasattr(opponent, "write")) else SequencePolicy(opponent, other)
     bl_code = _baseline_code(opponent, other)      # a baseline opponent: env.base_line stays set from its first turn on
     cur_bl = None
@@ -74,14 +91,18 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
             act["mode"] |= (cur_bl + 1) << S.MODE_BASELINE_SHIFT
         act["n_groups"].zero_()
         if turn == role:
-            vec = actor(state).float()
-            if sigma > 0.0:
-                vec = vec + torch.randn(vec.shape, generator=generator, device=dev, dtype=torch.float32) * sigma
-            if clip is not None:
-                vec = vec.clamp(clip[0], clip[1])
-            sigma = max(float(sigma_min), sigma * float(decay_rate))
-            vec = vec.contiguous()
-            batch.decode_actions(None, vec, n_types, n_exploits, n_apps, tm, act)
+            if decoder is not None:      # Cord_asc: the decode through the critic writes the action and its encoding; `raw + noise` is never read
+                vec = torch.empty((N, n_out), dtype=torch.float32, device=dev)
+                decoder.write(batch, act, rows_all, state, vec_out=vec)
+            else:
+                vec = actor(state).float()
+                if sigma > 0.0:
+                    vec = vec + torch.randn(vec.shape, generator=generator, device=dev, dtype=torch.float32) * sigma
+                if clip is not None:
+                    vec = vec.clamp(clip[0], clip[1])
+                vec = vec.contiguous()
+                batch.decode_actions(None, vec, n_types, n_exploits, n_apps, tm, act)
+            sigma = max(float(sigma_min), sigma * float(decay_rate))       # once per decision in both modes (:1372)
             _, raw, shaped, done = batch.step(act, view=role, full_obs=False)
             nxt = batch.role_obs[role].clone()
             rec["state"].append(state); rec["action_vec"].append(vec); rec["reward"].append(shaped.clone()); rec["raw_reward"].append(raw.clone())

@@ -394,18 +394,27 @@ class CoordAscentPolicy:
     picks are merged into one action tuple (`best_q`).  include/cygym_abi.h (cygym_coord_ascent_decode) states it in full.
     `critic`: a module with fc1 / fc2 / fc3 (policies.Critic, the reference's Critic) or a sequence of three nn.Linear.
     write() is one addmm (the state part of fc1) plus ONE launch; __call__ is the same decode with torch ops in float64, for
-    top_k = 1 only (a sampled pick needs the envs' rng ticks).  Not restated: the training-mode noise on Q (:2177-2178) and
-    exploit_override."""
+    top_k = 1 and without noise only (a sampled pick and the noise need the envs' rng ticks).
+    Training mode (:2177-2178): while the reference's critic is in train() it adds coord_noise_std * randn to the Q of every
+    candidate but the no-op before the sort.  `noise_std` is that coord_noise_std (do_agent.py:528: 0.1); it applies while
+    train_mode(True) -- mirror `critic.training` with train_mode(critic.training) -- and write() then decodes on the noisy scores
+    (addressed normals, SITE_COORD_NOISE) and merges on the clean Q.  write(vec_out=...) also returns encode_action of the merged
+    tuple, what the reference's replay buffer stores in this mode (:1424).  Not restated: exploit_override."""
 
     tick_free = True
 
-    def __init__(self, critic, n_types: int, n_exploits: int, n_apps: int, type_map=None, top_k: int = 5, tau: float = 0.5):
+    def __init__(self, critic, n_types: int, n_exploits: int, n_apps: int, type_map=None, top_k: int = 5, tau: float = 0.5,
+                 noise_std: float = 0.0):
         lins = [critic.fc1, critic.fc2, critic.fc3] if hasattr(critic, "fc1") else list(critic)
         if len(lins) != 3 or not all(isinstance(m, nn.Linear) and m.bias is not None and m.weight.dtype == torch.float32 for m in lins):
             raise ValueError("critic: a module with fc1 / fc2 / fc3 or three nn.Linear layers (float32, with biases)")
         self.critic, (self.fc1, self.fc2, self.fc3) = critic, lins
         self.n_types, self.n_exploits, self.n_apps = int(n_types), int(n_exploits), int(n_apps)
         self.top_k, self.tau = int(top_k), float(tau)
+        self.noise_std = float(noise_std)
+        if not (0.0 <= self.noise_std < float("inf")):
+            raise ValueError("noise_std must be finite and >= 0")
+        self.training = self.noise_std > 0.0      # a policy built with noise starts in training mode
         H1, H2 = self.fc1.out_features, self.fc2.out_features
         if H1 % 16 or H2 % 16 or not (16 <= H1 <= 128 and 16 <= H2 <= 128) or self.fc2.in_features != H1 \
                 or self.fc3.in_features != H2 or self.fc3.out_features != 1:
@@ -416,6 +425,15 @@ class CoordAscentPolicy:
         self.action_types = list(range(self.n_types)) if type_map is None else sorted({int(x) for x in self.type_map.tolist()})
 
     _map = ActorPolicy._map
+
+    def train_mode(self, critic_training: bool = True):
+        """Mirror `critic.training` (do_agent.py:2166): the noise of `noise_std` applies only while True.  Returns self."""
+        self.training = bool(critic_training)
+        return self
+
+    @property
+    def active_noise_std(self) -> float:
+        return self.noise_std if self.training else 0.0
 
     def n_out(self, M):
         return self.n_types + M + self.n_exploits + self.n_apps
@@ -435,20 +453,23 @@ class CoordAscentPolicy:
         return self._pk
 
     @torch.no_grad()
-    def write(self, batch, act, rows, obs, pick_out=None, q_out=None):
-        """h_state = one addmm, then the whole decode + scatter into rows `rows` of the action tensors in ONE launch."""
+    def write(self, batch, act, rows, obs, pick_out=None, q_out=None, vec_out=None):
+        """h_state = one addmm, then the whole decode + scatter into rows `rows` of the action tensors in ONE launch; vec_out
+        [n, >= n_out] float32 receives the encoded merged action of every source row."""
         w1s_t, b1, pack = self._packed(batch, batch.M)
         if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != int(w1s_t.shape[0]):
             raise ValueError(f"obs must be a float32 [n, {int(w1s_t.shape[0])}] role view")
         h_state = torch.addmm(b1, obs, w1s_t)
         batch.coord_ascent_decode(rows, h_state, pack, self.n_types, self.n_exploits, self.n_apps, self._map(obs.device), act,
-                                  top_k=self.top_k, tau=self.tau, pick_out=pick_out, q_out=q_out)
+                                  top_k=self.top_k, tau=self.tau, pick_out=pick_out, q_out=q_out, noise_std=self.active_noise_std, vec_out=vec_out)
 
     @torch.no_grad()
     def __call__(self, obs, t, M, L):
         """The same decode with torch ops in float64 (batch-likes without cygym_coord_ascent_decode: the tests' oracle harness)."""
         if self.top_k != 1:
             raise NotImplementedError("a pick among the top K is drawn in cygym_coord_ascent_decode (needs the envs' rng ticks)")
+        if self.active_noise_std > 0.0:
+            raise NotImplementedError("the training-mode noise is drawn in cygym_coord_ascent_decode (needs the envs' rng ticks)")
         T, E = self.n_types, self.n_exploits
         q = coord_ascent_q(obs, self.fc1, self.fc2, self.fc3, T, M, E, self.n_apps)
         q = torch.nan_to_num(q.to(torch.float32), nan=-1e9, posinf=1e9, neginf=-1e9)     # Q is an fp32 value (do_agent.py:2163)

@@ -59,6 +59,28 @@ def draw_np(seed: int, env, tick, site, a=0, b=0) -> np.ndarray:
     return philox4x32_10_np(env, tick, site, c3, seed & MASK, (seed >> 32) & MASK)[0]
 
 
+def draw_words_np(seed: int, env, tick, site, a=0, b=0):
+    """All four 32-bit words of the draw addressed (env, tick, site, a, b), as four uint64 arrays; word 0 is draw_np's."""
+    a = np.asarray(a, dtype=np.uint64); b = np.asarray(b, dtype=np.uint64)
+    c3 = (a & np.uint64(0xFFFF)) | ((b & np.uint64(0xFFFF)) << np.uint64(16))
+    return philox4x32_10_np(env, tick, site, c3, seed & MASK, (seed >> 32) & MASK)
+
+
+def normal_from_words(w0, w1) -> np.ndarray:
+    """The contract's standard normal from words 0 and 1 of ONE draw, in float64 (include/cygym_spec.h, CG_SITE_COORD_NOISE):
+    u1 = (w0 + 1) / 2^32 in (0, 1], u2 = w1 / 2^32, z = sqrt(-2 ln u1) cos(2 pi u2)."""
+    u1 = (np.asarray(w0, dtype=np.float64) + 1.0) / 4294967296.0
+    u2 = np.asarray(w1, dtype=np.float64) / 4294967296.0
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def normal_np(seed: int, env, tick, site, a=0, b=0) -> np.ndarray:
+    """Standard normal (float64) addressed (env, tick, site, a, b), vectorised over a / b: the contract's mapping of
+    np.random.randn -- addressed like every other draw, never sequenced."""
+    w = draw_words_np(seed, env, tick, site, a, b)
+    return normal_from_words(w[0], w[1])
+
+
 def index(u: int, n: int) -> int:
     """Index in [0, n) by multiply-high."""
     return (u * n) >> 32

@@ -51,6 +51,7 @@ SITE_EPS_TYPE = 65
 SITE_GROUP_PICK = 66
 SITE_SAMPLE = 67
 SITE_COORD_PICK = 68
+SITE_COORD_NOISE = 69
 
 POISSON_TABLE = 16
 TRI_TABLE = 8

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CYGYM_ABI_VERSION 5
+#define CYGYM_ABI_VERSION 6
 
 #define CYGYM_OK            0
 #define CYGYM_EINVAL       -1  /* bad argument / shape                       */
@@ -420,13 +420,17 @@ typedef struct cygym_critic {
   const float* w3;         /* [H2] fc3.weight                                                                                  */
   int16_t* pick_out;       /* optional [n][M]: the candidate c chosen for every device of source row r (tests; learners that
                               store per-device choices)                                                                        */
-  float*   q_out;          /* optional [n][M]: its Q                                                                           */
+  float*   q_out;          /* optional [n][M]: its Q (the critic's own, without the training-mode noise)                       */
+  float*   vec_out;        /* optional [n][vec_stride]: encode_action of the merged tuple of source row r (what the reference's
+                              replay buffer stores in this mode, do_agent.py:1424); the first n_out floats of a row are written */
   double   tau;            /* softmax temperature of the pick (coord_tau, do_agent.py:527: 0.5), > 0                            */
+  double   noise_std;      /* coord_noise_std (do_agent.py:528: 0.1) while the critic trains (:2177-2178), >= 0; 0 = eval mode:
+                              no noise, the kernels without it                                                                 */
   float    b3;             /* fc3.bias                                                                                         */
   int32_t  H1, H2;         /* multiples of 16, 16 .. 128                                                                       */
   int32_t  h_stride;       /* floats per row of h_state, >= H1                                                                 */
   int32_t  top_k;          /* coord_K (do_agent.py:526: 5), 1 .. 8; 1 = the arg-max candidate, no draw                          */
-  int32_t  reserved;
+  int32_t  vec_stride;     /* floats per row of vec_out, >= n_out (read only when vec_out is set)                               */
 } cygym_critic;
 
 /* Replaces: DoubleOracle.greedy_device_coord_ascent (do_agent.py:2137-2219) -- what decode_action returns in the reference's
@@ -444,15 +448,28 @@ typedef struct cygym_critic {
  * wherever that is finite; for |q / tau| > 700 the reference overflows to its uniform / nan_to_num fallbacks, this does not);
  * the pick is the first i whose normalised running sum exceeds u = draw / 2^32 (np.random.choice), draw = the Philox word
  * addressed (global env id, the env's current rng tick, CG_SITE_COORD_PICK, a = d).  top_k == 1 needs no draw.
+ * Training mode (noise_std > 0; :2177-2178, what the reference does while critic.training): the sort, the top K' and the softmax
+ * pick run on the scores  s_c = (float)((double)q_c + noise_std z(d, c)) for c >= 1,  s_0 = q_0 (the no-op gets no noise, :2166),
+ * q_c the fp32 Q after nan_to_num, z(d, c) the standard normal addressed (global env id, the env's current rng tick,
+ * CG_SITE_COORD_NOISE, a = d, b = c) -- the tick the pick reads; the decode does not advance it; top_k == 1 is then the arg-max of
+ * s.  Rounding the score to fp32 is a deliberate deviation: the reference keeps the f64 sum; the two differ by at most half an
+ * fp32 ulp of the score, less than the fp32 critic's own error, and the 32-bit order-bit selection stays what it is.  Equal s keeps
+ * ascending c.  The merge, q_out and the Q compared between devices are the CLEAN q of the picked candidate: the reference
+ * re-evaluates Q_of(best_map[d]) without noise (:2196-2198).
  * Merge (`best_q`, :2190-2203 -- the only branch of the reference that runs: the other one dies on an undefined name at :2214):
  * a pick is a no-op iff its type is T - 1; device_indices = the ascending d with another pick; exploit_indices = [x of the lowest
  * such d], else [0]; action_type = t of the acting pick with the largest Q (first maximum in ascending d), else T - 1, through
  * `type_map`; app_index = 0.  Written as group 0 of the rows exactly like cygym_decode_actions, CG_DECODE_TRUNCATED included.
+ * vec_out (with or without noise): row r receives encode_action of the merged tuple (:910-933 as :1424 calls it; its exploit index
+ * is < E, so no field swap occurs): 1.0 at t*, the merged type INDEX (before type_map: the critic's input uses the index), at T + d
+ * for EVERY acting device (the whole mask, also where the device list is cut at max_devs and CG_DECODE_TRUNCATED is raised), at
+ * T + D + x (x = the exploit above) and, when n_apps > 0, at T + D + E; 0.0 elsewhere among the first n_out floats; floats past n_out
+ * are not written.
  * From `layout`: rows, type_map, n_types, n_devices (= the handle's), n_exploits, n_apps, n, status.  Needs a bound handle (the
  * rng ticks).  Limits (CYGYM_EUNSUPPORTED beyond): H1, H2 multiples of 16 in 16 .. 128, 1 <= n_types <= 32,
  * 1 <= n_exploits <= CG_MAX_EXPLOITS (and <= n_devices), top_k <= 8.
- * Out of scope: the training-mode noise coord_noise_std * randn (:2177-2178, only when critic.training), exploit_override
- * (:2147-2149), and building the observation on chip (h_state comes from the caller). */
+ * CYGYM_EINVAL for a negative or non-finite noise_std and for vec_out with vec_stride < n_out.
+ * Out of scope: exploit_override (:2147-2149), and building the observation on chip (h_state comes from the caller). */
 int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* layout,
                               const cygym_actions* dst, void* stream);
 

@@ -193,9 +193,15 @@ enum {
   CG_SITE_SAMPLE = 67,       /* IPPO.py:524-555 Categorical(logits).sample() of cygym_sample_group_actions: a = device id,
                                 b = 0 (per-device type) / a = 0, b = 1 (exploit) / b = 2 (app); u = word 0 / 2^32 walks
                                 the inverse CDF of softmax(logits); same addressing                               */
-  CG_SITE_COORD_PICK = 68    /* do_agent.py:2185 np.random.choice(len(topk), p=probs) of greedy_device_coord_ascent
+  CG_SITE_COORD_PICK = 68,   /* do_agent.py:2185 np.random.choice(len(topk), p=probs) of greedy_device_coord_ascent
                                 (cygym_coord_ascent_decode): a = device id; u = word 0 / 2^32 walks the inverse CDF of the
                                 top-K softmax; same addressing                                                     */
+  CG_SITE_COORD_NOISE = 69   /* do_agent.py:2178 coord_noise_std * np.random.randn(T E) on the Q of a device's candidates while
+                                the critic trains (cygym_critic.noise_std > 0): a = device id, b = candidate c = 1 .. T E (the
+                                no-op, c = 0, gets none); the rng tick CG_SITE_COORD_PICK reads, not advanced.  The contract's
+                                mapping of randn -- addressed, not sequenced, like every other site: a standard normal from ONE
+                                call, in f64: u1 = (word 0 + 1) / 2^32 in (0, 1], u2 = word 1 / 2^32,
+                                z = sqrt(-2 ln u1) cos(2 pi u2)                                                    */
 };
 
 /* ---- Philox4x32-10 (Salmon et al., SC'11), counter-based ----

@@ -2,7 +2,9 @@
 devices with the reference's critic (T = 14, E = 6, 128 x 128), HIP events after warm-up: us per decision and the fraction of
 the 155 TF the fp32 matrix instructions reach (layer 2 alone: 2 * M * T * E * H1 * H2 FLOP per env, 2.9 TFLOP per launch) --
 and, at a size the torch path can hold (256 envs, chunked), the same decode with torch ops in float32 on the device.
-One JSON line per measurement."""
+--noise-std S: the training-mode launch (noise on the scores, do_agent.py:2177-2178) instead of the eval-mode one; --vec-out: with
+the encoded action written; --collect K: decisions per second of ddpg_rollout.collect(decoder=...) over K decisions of the
+defender against a fixed attacker sequence; --no-torch skips the torch path.  One JSON line per measurement."""
 import argparse
 import json
 import os
@@ -20,6 +22,11 @@ ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--torch-envs", type=int, default=256)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=2)
+ap.add_argument("--noise-std", type=float, default=0.0)
+ap.add_argument("--vec-out", action="store_true")
+ap.add_argument("--collect", type=int, default=0)
+ap.add_argument("--no-torch", action="store_true")
+ap.add_argument("--label", default="")
 args = ap.parse_args()
 
 M, T, E, A, H = 256, 14, 6, 3, 128
@@ -47,13 +54,18 @@ def timed(fn, reps, warmup):
     return sorted(ms)
 
 
+extra = {}
+if args.noise_std > 0.0:
+    extra["noise_std"] = args.noise_std
+if args.vec_out:
+    extra["vec_out"] = torch.empty((args.envs, T + M + E + A), dtype=torch.float32, device=dev)
 for top_k in (5, 1):
-    pol = CoordAscentPolicy(critic, T, E, A, top_k=top_k)
+    pol = CoordAscentPolicy(critic, T, E, A, top_k=top_k, **({"noise_std": args.noise_std} if args.noise_std > 0.0 else {}))
     w1s_t, b1, pack = pol._packed(env, M)
     h_state = torch.addmm(b1, obs, w1s_t)
-    ms = timed(lambda: env.coord_ascent_decode(None, h_state, pack, T, E, A, None, top_k=top_k, tau=0.5), args.reps, args.warmup)
+    ms = timed(lambda: env.coord_ascent_decode(None, h_state, pack, T, E, A, None, top_k=top_k, tau=0.5, **extra), args.reps, args.warmup)
     med = ms[len(ms) // 2]
-    print(json.dumps({"what": "cygym_coord_ascent_decode", "envs": args.envs, "devices": M, "types": T, "exploits": E, "H1": H, "H2": H,
+    print(json.dumps({"what": "cygym_coord_ascent_decode", "label": args.label, "noise_std": args.noise_std, "vec_out": args.vec_out, "envs": args.envs, "devices": M, "types": T, "exploits": E, "H1": H, "H2": H,
                       "top_k": top_k, "ms_per_launch": round(med, 3), "ms_min_max": [round(ms[0], 3), round(ms[-1], 3)],
                       "us_per_decision": round(med * 1e3 / args.envs, 3), "tflop_per_launch": round(flop * args.envs / 1e12, 3),
                       "fraction_of_155TF": round(flop * args.envs / (med * 1e-3) / PEAK, 4)}))
@@ -61,6 +73,25 @@ for top_k in (5, 1):
     print(json.dumps({"what": "CoordAscentPolicy.write (addmm + launch)", "top_k": top_k, "ms": round(ms[len(ms) // 2], 3)}))
 assert env.take_status() & abi.DECODE_TRUNCATED == 0
 
+if args.collect > 0:
+    import time
+    from cygym_amd.ddpg_rollout import collect
+    def_types = [1, 4, 5, 6, 7, 9, 13, 2, 12, 11, 3, 1, 4, 8][:T]       # the defender's no-op (8) last (two types twice: no detector batch here)
+    pol = CoordAscentPolicy(critic, T, E, A, type_map=def_types, top_k=5, **({"noise_std": args.noise_std} if args.noise_std > 0.0 else {}))
+    opp = [(1, [0], [], 0), (2, [1], [], 0), (3, [0], [], 0)]
+    collect(env, "defender", None, opp, 2, T, E, A, decoder=pol)            # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tr = collect(env, "defender", None, opp, args.collect, T, E, A, decoder=pol)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(json.dumps({"what": "ddpg_rollout.collect(decoder=CoordAscentPolicy)", "label": args.label, "noise_std": args.noise_std, "envs": args.envs,
+                      "decisions": args.collect, "seconds": round(dt, 4), "ms_per_decision_step": round(dt / args.collect * 1e3, 3),
+                      "env_decisions_per_s": round(args.collect * args.envs / dt, 1)}))
+    del tr
+
+if args.no_torch:
+    sys.exit(0)
 n = min(args.torch_envs, args.envs)
 o = obs[:n].contiguous()
 

@@ -20,6 +20,16 @@ A fixture holds arrays only:
   q_err_f64 [2]                                       max |Q_reference - Q_f64| over ALL candidates, and max |Q_f64|
   atype [n], exploit [n], dev_mask [n, M] u8          the merged tuple the reference returned (app index is 0)
 (The reference's Q of every candidate would be 260 KB for the defender fixture; the pick depends on the sorted head only.)
+
+*_train: the same recipe in TRAINING mode (do_agent.py:2166, :2177-2178): critic.train(), coord_noise_std = 0.1 on the stub, and
+np.random.randn swapped for the addressed normals (cygym_amd/rng.normal_np, site COORD_NOISE, a = device = the call's ordinal, b =
+candidate c = 1 .. T E).  They hold what the others hold, with
+  noise_std                                           coord_noise_std
+  top_q [n, M, K' + 1] f64                            the NOISY scores the reference sorted (the no-op's is its clean Q)
+  top_q_clean [n, M, K' + 1] f32                      its critic's clean Q of those candidates
+  s_err_f64 [2]                                       max |score_reference - score_f64| over all candidates (score_f64 = Q_f64 +
+                                                      noise_std z), and max |score_f64|
+The normals are not stored: tests recompute them.
 """
 import os
 import sys
@@ -35,7 +45,10 @@ REF = os.environ.get("REFERENCE_DIR", os.path.join(os.path.dirname(ROOT), "refer
 FIXTURES = {
     "def12": (12, 14, 6, 3, 72, 64, 0xC0DE12),
     "att70": (70, 3, 6, 2, 286, 16, 0xC0DE72),
+    "def12_train": (12, 14, 6, 3, 72, 64, 0xC0DE1A),
+    "att70_train": (70, 3, 6, 2, 286, 10, 0xC0DE7A),   # (10 states, not 16: the f64 scores do not compress, and a fixture stays under 100 KB)
 }
+NOISE_STD = 0.1      # coord_noise_std, do_agent.py:528
 TOP_K, TAU, GEN_MARGIN = 5, 0.5, 1e-4
 
 
@@ -74,8 +87,12 @@ def main():
     stub.one_hot_encode = types.MethodType(DO.one_hot_encode, stub)
 
     for name, (M, T, E, A, W, n, seed) in FIXTURES.items():
+        train = name.endswith("_train")
+        stub.coord_noise_std = NOISE_STD if train else 0.0
         torch.manual_seed(seed)
         critic = SmallCritic(W, T + M + E + A).eval()
+        if train:
+            critic.train()
         with torch.no_grad():      # the low 12 mantissa bits of every weight cleared: the fixtures then compress to under 80 KB
             for p in critic.parameters():
                 p.copy_((p.view(torch.int32) & -4096).view(torch.float32))
@@ -90,9 +107,11 @@ def main():
         choice, pick = np.zeros((n, M), np.uint8), np.zeros((n, M), np.uint8)
         atype, exploit, dev_mask = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, M), np.uint8)
         q_all = np.zeros((n, M, C), np.float32)
-        real_forward, real_choice = critic.forward, np.random.choice
+        s_all, top_s = np.zeros((n, M, C), np.float64), np.zeros((n, M, K1), np.float64)
+        z_all = np.zeros((n, M, C), np.float64)
+        real_forward, real_choice, real_randn = critic.forward, np.random.choice, np.random.randn
         for i in range(n):
-            rec, ch = [], []
+            rec, ch, zs = [], [], []
 
             def forward(state, action):
                 out = real_forward(state, action)
@@ -105,17 +124,28 @@ def main():
                 ch.append(int(np.searchsorted(cdf, float(draws[i, len(ch)]) / 4294967296.0, side="right")))
                 return ch[-1]
 
-            critic.forward, np.random.choice = forward, addressed_choice
+            def addressed_randn(*shape):
+                assert shape == (T * E,)
+                zs.append(R.normal_np(seed, int(env_ids[i]), int(ticks[i]), S.SITE_COORD_NOISE, len(zs), np.arange(1, T * E + 1)))
+                return zs[-1]
+
+            critic.forward, np.random.choice, np.random.randn = forward, addressed_choice, addressed_randn
             try:
                 res = DO.greedy_device_coord_ascent(stub, T, M, E, A, torch.from_numpy(states[i:i + 1]), None, None, critic)
             finally:
-                critic.forward, np.random.choice = real_forward, real_choice
+                critic.forward, np.random.choice, np.random.randn = real_forward, real_choice, real_randn
+            assert len(zs) == (M if train else 0)
             assert len(ch) == M and len(rec) == 1 + 2 * M and rec[0].shape == (1,) and all(r.shape == (T * E,) for r in rec[1:1 + M])
             for d in range(M):
                 q = np.concatenate([rec[0], rec[1 + d]])
                 q_all[i, d] = q
-                order = np.argsort(-q.astype(np.float64), kind="stable")          # list.sort(reverse=True) is stable
-                top_c[i, d], top_q[i, d] = order[:K1], q[order[:K1]]
+                sc = q.astype(np.float64)
+                if train:           # what the reference sorted: qv + coord_noise_std * randn (:2178), the no-op's Q as it is
+                    sc[1:] = rec[1 + d] + stub.coord_noise_std * zs[d]
+                    z_all[i, d, 1:] = zs[d]
+                s_all[i, d] = sc
+                order = np.argsort(-sc, kind="stable")          # list.sort(reverse=True) is stable
+                top_c[i, d], top_q[i, d], top_s[i, d] = order[:K1], q[order[:K1]], sc[order[:K1]]
                 choice[i, d], pick[i, d] = ch[d], order[ch[d]]
             atype[i], exploit[i] = int(res[0]), int(res[1][0])
             dev_mask[i, np.asarray(res[2], int)] = 1
@@ -128,15 +158,17 @@ def main():
         q64 = coord_ascent_q(torch.from_numpy(states), critic.fc1, critic.fc2, critic.fc3, T, M, E, A).numpy()
         qmax = float(np.abs(q64).max())
         err = float(np.abs(q_all.astype(np.float64) - q64).max())
+        s64 = q64 + stub.coord_noise_std * z_all
+        smax, s_err = float(np.abs(s64).max()), float(np.abs(s_all - s64).max())
         # the reference alone must leave the tests' cap (10 % of the devices unclear) room at a margin of 1e-4
         Kp = K1 - 1
-        gaps = (top_q[:, :, :-1].astype(np.float64) - top_q[:, :, 1:]).min(axis=2)
-        e = np.exp((top_q[:, :, :Kp].astype(np.float64) - top_q[:, :, :1]) / TAU)
+        gaps = (top_s[:, :, :-1] - top_s[:, :, 1:]).min(axis=2)
+        e = np.exp((top_s[:, :, :Kp] - top_s[:, :, :1]) / TAU)
         cdf = np.cumsum(e, axis=2) / e.sum(axis=2, keepdims=True)
         u = draws.astype(np.float64) / 4294967296.0
         near = np.abs(cdf[:, :, :-1] - u[:, :, None]).min(axis=2)
-        unclear = float(((gaps <= GEN_MARGIN * qmax) | (near <= GEN_MARGIN)).mean())
-        assert err <= GEN_MARGIN / 8 * qmax, (name, err, qmax)
+        unclear = float(((gaps <= GEN_MARGIN * (smax if train else qmax)) | (near <= GEN_MARGIN)).mean())
+        assert err <= GEN_MARGIN / 8 * qmax and s_err <= GEN_MARGIN / 8 * smax, (name, err, qmax, s_err, smax)
         assert unclear <= 0.10, (name, unclear)
         sd = {k: v.detach().numpy() for k, v in critic.state_dict().items()}
         os.makedirs(os.path.join(ROOT, "tests", "golden", "coord_ascent"), exist_ok=True)
@@ -144,10 +176,12 @@ def main():
         np.savez_compressed(path, fc1_w=sd["fc1.weight"], fc1_b=sd["fc1.bias"], fc2_w=sd["fc2.weight"], fc2_b=sd["fc2.bias"],
                             fc3_w=sd["fc3.weight"], fc3_b=sd["fc3.bias"], dims=np.array([M, T, E, A, W, TOP_K], np.int32),
                             tau=np.array(TAU), seed=np.array(seed, np.int64), env_ids=env_ids, ticks=ticks, draws=draws, states=states,
-                            top_c=top_c, top_q=top_q, choice=choice, pick=pick, q_err_f64=np.array([err, qmax]),
-                            atype=atype, exploit=exploit, dev_mask=dev_mask)
+                            top_c=top_c, top_q=top_s if train else top_q, choice=choice, pick=pick, q_err_f64=np.array([err, qmax]),
+                            atype=atype, exploit=exploit, dev_mask=dev_mask,
+                            **({"noise_std": np.array(stub.coord_noise_std), "top_q_clean": top_q, "s_err_f64": np.array([s_err, smax])} if train else {}))
         print(f"{name}: {os.path.getsize(path)} bytes, max |Q_ref - Q_f64| = {err:.3g} (max |Q| = {qmax:.3g}), "
               f"{100 * unclear:.1f} % of the devices unclear at a margin of {GEN_MARGIN:g}, "
+              + (f"max |score_ref - score_f64| = {s_err:.3g} (max |score| = {smax:.3g}), " if train else "") +
               f"{int((choice > 0).sum())} of {n * M} picks are not the arg-max, {int(dev_mask.sum())} acting devices")
 
 
