@@ -480,11 +480,10 @@ __device__ __forceinline__ void actor_mlp_body(cygym_actor_mlp ml, const cygym_a
     MSTAMP(11);
   } else {
     // ---- STREAM: chunks of 512 outputs through the same LDS tile; a wave keeps its row's running arg-maxima and list length ----
-    const int M = src.n_devices, G = dst.max_groups, L = dst.max_devs;
+    const int M = src.n_devices;
     const int lo1 = nt + M, lo2 = nt + M + src.n_exploits;
     uint32_t bh0 = 0u, bl0 = 0u, bh1 = 0u, bl1 = 0u, bh2 = 0u, bl2 = 0u;   // (order bits, ~index) of types / exploit / app so far, per lane
-    int base = 0;
-    int16_t* out = const_cast<int16_t*>(dst.dev_idx) + (size_t)(row >= 0 ? row : 0) * L;
+    RowList list(dst, row >= 0 ? row : 0);
     const float* a_row = hin + r * hp;
     const int n_chunks = (n_tiles_tot + 31) >> 5;
     for (int c = 0; c < n_chunks; ++c) {
@@ -522,40 +521,19 @@ __device__ __forceinline__ void actor_mlp_body(cygym_actor_mlp ml, const cygym_a
           if (j >= lo1 && j < lo2 && ob > bh1) { bh1 = ob; bl1 = ~(uint32_t)(j - lo1); }
           if (j >= lo2 && j < n_out && ob > bh2) { bh2 = ob; bl2 = ~(uint32_t)(j - lo2); }
           const int d = j - nt;
-          const bool on = d >= 0 && d < M && v > 0.f;
-          const uint64_t m = __ballot(on);
-          const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-          if (on && pos < L) out[pos] = (int16_t)d;
-          base += __popcll(m);
+          list.push(d >= 0 && d < M && v > 0.f, d);
         }
       }
       if (c + 1 < n_chunks) __syncthreads();   // the next chunk overwrites the tile
     }
     MSTAMP(10);
     if (row < 0) return;
-    auto wave_best = [&](uint32_t h, uint32_t l) -> int {
-      dpp_pair_max(h, l);
-      const uint32_t rl = (uint32_t)__builtin_amdgcn_readlane((int)l, 63), rh = (uint32_t)__builtin_amdgcn_readlane((int)h, 63);
-      return rh == 0u ? 0 : (int)~rl;
-    };
-    int at = nt > 0 ? wave_best(bh0, bl0) : 0;
-    if (src.epsilon_thr && nt > 0) {   // epsilon-greedy (do_agent.py:972-973)
-      const cg_u32x4 rr = cg_philox4x32_10((uint32_t)(env_id_base + row), tick, CG_SITE_EPS_TYPE, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-      if ((uint64_t)rr.v[0] < src.epsilon_thr) at = (int)cg_index(rr.v[1], (uint32_t)nt);
-    }
+    int at = nt > 0 ? wave_first_max(bh0, bl0) : 0;
+    at = eps_greedy_type(at, src, row, tick, seed, env_id_base);
     if (nt > 0) at = nt <= WAVE ? __shfl(tmap, at) : (src.type_map ? src.type_map[at] : at);
-    const int cnt = base < L ? base : L;
-    for (int q = cnt + lane; q < L; q += WAVE) out[q] = 0;
-    const int ex = src.n_exploits > 0 ? wave_best(bh1, bl1) : 0;
-    const int app = src.n_apps > 0 ? wave_best(bh2, bl2) : 0;
-    if (lane == 0) {
-      const_cast<int32_t*>(dst.atype)[(size_t)row * G] = at;
-      const_cast<int32_t*>(dst.exploit)[(size_t)row * G * CG_MAX_EXPLOITS] = ex;
-      const_cast<int32_t*>(dst.n_exploit)[(size_t)row * G] = 1;
-      const_cast<int32_t*>(dst.app)[(size_t)row * G] = app;
-      const_cast<int32_t*>(dst.dev_cnt)[(size_t)row * G] = cnt;
-      if (base > L && src.status) atomicOr(src.status, CG_DECODE_TRUNCATED);
-    }
+    const int ex = src.n_exploits > 0 ? wave_first_max(bh1, bl1) : 0;
+    const int app = src.n_apps > 0 ? wave_first_max(bh2, bl2) : 0;
+    list.finish(dst, row, lane, at, ex, 1, app, src.status);
     MSTAMP(11);
   }
 #undef MSTAMP

@@ -145,44 +145,30 @@ __global__ void observe_kernel(KParams P, int role, float* out) {
 
 #include "cg_decode.hpp"      // decode of one row by one wave + the whole-actor kernel (templates: also used by cg_inst_actor.hip)
 
-// cygym_write_actions: one wave per source row.  A device mask is compacted to the ascending id list with ballots
-// (rank of a chosen device = chosen devices below it), the first max_devs of them; entries past the count are zeroed.
+// cygym_write_actions: one wave per source row.  A device mask goes through the row writer of cg_decode.hpp (RowList), a given
+// list is copied; no status word, and n_exploit = 0 for "no exploit" (-1).
 __global__ void write_actions_kernel(cygym_action_rows src, cygym_actions dst, int M, int n_envs) {
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (wave >= src.n) return;
   const int row = src.rows ? src.rows[wave] : wave;
   if (row < 0 || row >= n_envs) return;
-  const int G = dst.max_groups, L = dst.max_devs;
-  int16_t* out = const_cast<int16_t*>(dst.dev_idx) + (size_t)row * L;
-  int cnt;
+  RowList list(dst, row);
   if (src.dev_mask) {
     const uint8_t* mk = src.dev_mask + (size_t)wave * M;
-    int base = 0;
     for (int d0 = 0; d0 < M; d0 += WAVE) {
       const int d = d0 + lane;
-      const bool on = d < M && mk[d] != 0;
-      const uint64_t m = __ballot(on);
-      const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      if (on && pos < L) out[pos] = (int16_t)d;
-      base += __popcll(m);
+      list.push(d < M && mk[d] != 0, d);
     }
-    cnt = base < L ? base : L;
   } else {
-    cnt = src.dev_cnt[wave];
-    if (cnt > L) cnt = L;
+    int cnt = src.dev_cnt[wave];
+    if (cnt > list.L) cnt = list.L;
     if (cnt < 0) cnt = 0;
-    const int16_t* in = src.dev_idx + (size_t)wave * L;
-    for (int q = lane; q < cnt; q += WAVE) out[q] = in[q];
+    const int16_t* in = src.dev_idx + (size_t)wave * list.L;
+    for (int q = lane; q < cnt; q += WAVE) list.out[q] = in[q];
+    list.n = cnt;
   }
-  for (int q = cnt + lane; q < L; q += WAVE) out[q] = 0;
-  if (lane == 0) {
-    const int ex = src.exploit[wave];
-    const_cast<int32_t*>(dst.atype)[(size_t)row * G] = src.atype[wave];
-    const_cast<int32_t*>(dst.exploit)[(size_t)row * G * CG_MAX_EXPLOITS] = ex;
-    const_cast<int32_t*>(dst.n_exploit)[(size_t)row * G] = ex >= 0 ? 1 : 0;
-    const_cast<int32_t*>(dst.app)[(size_t)row * G] = src.app[wave];
-    const_cast<int32_t*>(dst.dev_cnt)[(size_t)row * G] = cnt;
-  }
+  const int ex = src.exploit[wave];
+  list.finish(dst, row, lane, src.atype[wave], ex, ex >= 0 ? 1 : 0, src.app[wave], nullptr);
 }
 
 // cygym_group_actions (IPPO.py:560-572 for a batch): one wave per row.  For every action type in ascending order the
@@ -342,7 +328,8 @@ __global__ __launch_bounds__(SAMPLE_WPB * WAVE) void sample_group_actions_kernel
   group_row(ty, nullptr, fl, want, M, K, src.noop, src.single_mask, ex, app, dst, row, tick, seed, env_id_base, src.status, lane);
 }
 
-// cygym_decode_actions (do_agent.py:970-998 for a batch): one wave per row.  argmax = first maximum (np.argmax).
+// cygym_decode_actions (do_agent.py:970-998 for a batch): one wave per row.  argmax = first maximum (np.argmax), over memory;
+// the type step, the device list and the row's scalars are the shared pieces of cg_decode.hpp.
 __device__ __forceinline__ int wave_argmax(const float* v, int n, int lane) {
   float best = -__builtin_inff();
   int bi = 0x7FFFFFFF;
@@ -361,38 +348,22 @@ __global__ void decode_actions_kernel(cygym_action_vectors src, cygym_actions ds
   if (wave >= src.n) return;
   const int row = src.rows ? src.rows[wave] : wave;
   if (row < 0 || row >= n_envs) return;
-  const int G = dst.max_groups, L = dst.max_devs, M = src.n_devices;
+  const int M = src.n_devices;
   const float* v = src.vec + (size_t)wave * src.stride;
   int at = src.n_types > 0 ? wave_argmax(v, src.n_types, lane) : 0;
-  if (src.epsilon_thr && src.n_types > 0) {   // epsilon-greedy (do_agent.py:972-973)
-    const uint32_t tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];
-    const cg_u32x4 r = cg_philox4x32_10((uint32_t)(env_id_base + row), tick, CG_SITE_EPS_TYPE, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    if ((uint64_t)r.v[0] < src.epsilon_thr) at = (int)cg_index(r.v[1], (uint32_t)src.n_types);
-  }
+  uint32_t tick = 0;
+  if (src.epsilon_thr) tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];
+  at = eps_greedy_type(at, src, row, tick, seed, env_id_base);
   if (src.type_map && src.n_types > 0) at = src.type_map[at];
   const float* dv = v + src.n_types;
-  int16_t* out = const_cast<int16_t*>(dst.dev_idx) + (size_t)row * L;
-  int base = 0;
+  RowList list(dst, row);
   for (int d0 = 0; d0 < M; d0 += WAVE) {
     const int d = d0 + lane;
-    const bool on = d < M && dv[d] > 0.f;
-    const uint64_t m = __ballot(on);
-    const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (on && pos < L) out[pos] = (int16_t)d;
-    base += __popcll(m);
+    list.push(d < M && dv[d] > 0.f, d);
   }
-  const int cnt = base < L ? base : L;
-  for (int q = cnt + lane; q < L; q += WAVE) out[q] = 0;
   const int ex = src.n_exploits > 0 ? wave_argmax(dv + M, src.n_exploits, lane) : 0;
   const int app = src.n_apps > 0 ? wave_argmax(dv + M + src.n_exploits, src.n_apps, lane) : 0;
-  if (lane == 0) {
-    const_cast<int32_t*>(dst.atype)[(size_t)row * G] = at;
-    const_cast<int32_t*>(dst.exploit)[(size_t)row * G * CG_MAX_EXPLOITS] = ex;
-    const_cast<int32_t*>(dst.n_exploit)[(size_t)row * G] = 1;
-    const_cast<int32_t*>(dst.app)[(size_t)row * G] = app;
-    const_cast<int32_t*>(dst.dev_cnt)[(size_t)row * G] = cnt;
-    if (base > L && src.status) atomicOr(src.status, CG_DECODE_TRUNCATED);
-  }
+  list.finish(dst, row, lane, at, ex, 1, app, src.status);
 }
 
 // cygym_actor_head_decode: last Linear layer of the actor + decode_action, fused.  A workgroup of HEAD_WAVES waves stages
@@ -400,7 +371,7 @@ __global__ void decode_actions_kernel(cygym_action_vectors src, cygym_actions ds
 // every wave owns ONE row (16 waves per workgroup = 4 per SIMD: the LDS and reduction latencies of one row hide behind the
 // other rows'); lane j accumulates outputs j, j + 64, ... (HEAD_OPL per lane) with the hidden activation of step k
 // broadcast from the lane that holds it (v_readlane: an SGPR operand, no LDS traffic).  The action vector of a row lives
-// in registers only; its arg-maxima are wave reductions on the DPP path over (order-preserving value bits, ~index) pairs.
+// in registers only and is decoded from them (decode_row_regs, cg_decode.hpp); the type-map entry is read from memory.
 template <int HEAD_OPL>
 __global__ __launch_bounds__(HEAD_WAVES * WAVE) void actor_head_kernel(cygym_actor_head hd, cygym_action_vectors src, cygym_actions dst,
                                                                         int n_envs, const int32_t* ienv, uint64_t seed, int64_t env_id_base) {
@@ -451,53 +422,12 @@ __global__ __launch_bounds__(HEAD_WAVES * WAVE) void actor_head_kernel(cygym_act
   if (!have) return;
   const int row = src.rows ? src.rows[srow] : srow;
   if (row < 0 || row >= n_envs) return;
-  const int G = dst.max_groups, L = dst.max_devs, M = src.n_devices, nt = src.n_types;
   float v[HEAD_OPL];
 #pragma unroll
   for (int i = 0; i < HEAD_OPL; ++i) v[i] = hd.tanh_out ? tanhf(acc[i]) : acc[i];
-  // argmax of the outputs in [lo, hi) (first maximum, like np.argmax): per lane over its registers, then across the wave
-  auto range_argmax = [&](int lo, int hi) -> int {
-    uint32_t bh = 0u, bl = 0u;   // (0, 0): below every real candidate (order bits of a finite float are >= 0x00800000)
-#pragma unroll
-    for (int i = 0; i < HEAD_OPL; ++i) {
-      const int j = lane + i * WAVE;
-      const uint32_t ob = float_order_bits(v[i]);
-      if (j >= lo && j < hi && ob > bh) { bh = ob; bl = ~(uint32_t)(j - lo); }   // ascending j per lane: first maximum
-    }
-    dpp_pair_max(bh, bl);
-    const uint32_t rl = (uint32_t)__builtin_amdgcn_readlane((int)bl, 63), rh = (uint32_t)__builtin_amdgcn_readlane((int)bh, 63);
-    return rh == 0u ? 0 : (int)~rl;
-  };
-  int at = nt > 0 ? range_argmax(0, nt) : 0;
-  if (src.epsilon_thr && nt > 0) {   // epsilon-greedy (do_agent.py:972-973)
-    const uint32_t tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];
-    const cg_u32x4 rr = cg_philox4x32_10((uint32_t)(env_id_base + row), tick, CG_SITE_EPS_TYPE, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    if ((uint64_t)rr.v[0] < src.epsilon_thr) at = (int)cg_index(rr.v[1], (uint32_t)nt);
-  }
-  if (src.type_map && nt > 0) at = src.type_map[at];
-  int16_t* out = const_cast<int16_t*>(dst.dev_idx) + (size_t)row * L;
-  int base = 0;
-#pragma unroll
-  for (int i = 0; i < HEAD_OPL; ++i) {   // (i, lane) ascending == output index ascending == device id ascending
-    const int d = lane + i * WAVE - nt;
-    const bool on = d >= 0 && d < M && v[i] > 0.f;
-    const uint64_t m = __ballot(on);
-    const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (on && pos < L) out[pos] = (int16_t)d;
-    base += __popcll(m);
-  }
-  const int cnt = base < L ? base : L;
-  for (int q = cnt + lane; q < L; q += WAVE) out[q] = 0;
-  const int ex = src.n_exploits > 0 ? range_argmax(nt + M, nt + M + src.n_exploits) : 0;
-  const int app = src.n_apps > 0 ? range_argmax(nt + M + src.n_exploits, n_out) : 0;
-  if (lane == 0) {
-    const_cast<int32_t*>(dst.atype)[(size_t)row * G] = at;
-    const_cast<int32_t*>(dst.exploit)[(size_t)row * G * CG_MAX_EXPLOITS] = ex;
-    const_cast<int32_t*>(dst.n_exploit)[(size_t)row * G] = 1;
-    const_cast<int32_t*>(dst.app)[(size_t)row * G] = app;
-    const_cast<int32_t*>(dst.dev_cnt)[(size_t)row * G] = cnt;
-    if (base > L && src.status) atomicOr(src.status, CG_DECODE_TRUNCATED);
-  }
+  uint32_t tick = 0;
+  if (src.epsilon_thr) tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];
+  decode_row_regs<HEAD_OPL>(v, row, tick, [&](int at) { return src.type_map ? src.type_map[at] : at; }, src, dst, lane, seed, env_id_base);
 }
 
 // The same on the matrix cores (H % 4 == 0): a workgroup of 16 waves owns 16 rows; the [16 x H] x [H x n_out_p] product

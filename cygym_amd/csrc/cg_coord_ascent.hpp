@@ -243,10 +243,10 @@ __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic c
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           if (kh[i] > bh) { bh = kh[i]; bl = ~(uint32_t)(lane + WAVE * i); }   // (equal Q: the lane's smaller c stays)
-        dpp_pair_max(bh, bl);
-        const int cw = (int)~(uint32_t)__builtin_amdgcn_readlane((int)bl, 63);
+        uint32_t wh;
+        const int cw = wave_first_max(bh, bl, &wh);   // (never empty: k < K' <= the candidates left)
         sc[k] = cw;
-        if constexpr (NOISE) sq[k] = ca_order_bits_float((uint32_t)__builtin_amdgcn_readlane((int)bh, 63));   // the winner's noisy score
+        if constexpr (NOISE) sq[k] = ca_order_bits_float(wh);   // the winner's noisy score
         else sq[k] = qb[cw];
 #pragma unroll
         for (int i = 0; i < 4; ++i) kh[i] = cw == lane + WAVE * i ? 0u : kh[i];
@@ -294,29 +294,23 @@ __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic c
   __syncthreads();
   if (wave != 0) return;
   // ---------------- merge (`best_q`, do_agent.py:2190-2203) and the row's action, group 0 ----------------
-  const int G = dst.max_groups, L = dst.max_devs;
-  int16_t* out = const_cast<int16_t*>(dst.dev_idx) + (size_t)row * L;
-  int base = 0, ex = -1;
+  RowList list(dst, row);
+  int ex = -1;
   uint32_t bh = 0u, bl = 0u;
   for (int d0 = 0; d0 < M; d0 += WAVE) {
     const int d = d0 + lane;
     const int c = d < M ? (int)pick_dev[d] : 0;
     const int t = c > 0 ? (c - 1) / E : T - 1, x = c > 0 ? (c - 1) - t * E : 0;
     const bool on = d < M && t != T - 1;   // a pick is a no-op iff its type is T - 1
-    const uint64_t m = __ballot(on);
-    const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (on && pos < L) out[pos] = (int16_t)d;
+    const uint64_t m = list.push(on, d);
     if (ex < 0 && m) ex = __shfl(x, __ffsll((unsigned long long)m) - 1);   // the exploit of the lowest acting device
     if (on) {
       const uint32_t ob = float_order_bits(q_dev[d]);
       if (ob > bh) { bh = ob; bl = ~(uint32_t)d; }
     }
-    base += __popcll(m);
   }
-  dpp_pair_max(bh, bl);   // the acting device with the largest Q, the lowest id among equals
-  const uint32_t rh = (uint32_t)__builtin_amdgcn_readlane((int)bh, 63), rl = (uint32_t)__builtin_amdgcn_readlane((int)bl, 63);
-  int at = T - 1;
-  if (rh != 0u) at = ((int)pick_dev[(int)~rl] - 1) / E;
+  const int dbest = wave_first_max(bh, bl);   // the acting device with the largest Q, the lowest id among equals
+  int at = list.n > 0 ? ((int)pick_dev[dbest] - 1) / E : T - 1;   // (no acting device: the no-op type)
   if constexpr (VEC) {
     // encode_action of the merged tuple (do_agent.py:910-933 as :1424 calls it), every element from the picks in LDS: the type
     // INDEX (before type_map), the whole device mask (also where the list is cut at max_devs), the exploit, app 0
@@ -334,14 +328,5 @@ __global__ __launch_bounds__(CA_THREADS) void coord_ascent_kernel(cygym_critic c
     }
   }
   if (src.type_map) at = src.type_map[at];
-  const int cnt = base < L ? base : L;
-  for (int q = cnt + lane; q < L; q += WAVE) out[q] = 0;
-  if (lane == 0) {
-    const_cast<int32_t*>(dst.atype)[(size_t)row * G] = at;
-    const_cast<int32_t*>(dst.exploit)[(size_t)row * G * CG_MAX_EXPLOITS] = ex < 0 ? 0 : ex;
-    const_cast<int32_t*>(dst.n_exploit)[(size_t)row * G] = 1;
-    const_cast<int32_t*>(dst.app)[(size_t)row * G] = 0;
-    const_cast<int32_t*>(dst.dev_cnt)[(size_t)row * G] = cnt;
-    if (base > L && src.status) atomicOr(src.status, CG_DECODE_TRUNCATED);
-  }
+  list.finish(dst, row, lane, at, ex < 0 ? 0 : ex, 1, 0, src.status);
 }

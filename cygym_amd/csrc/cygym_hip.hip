@@ -403,6 +403,42 @@ static int raise_lds_once(cygym_handle* h, const void* k) {
 constexpr int ROW_THREADS = 256;   // launch geometry of the auxiliary kernels: 256 threads, one wave per row
 static dim3 row_grid(int rows) { return dim3((rows + ROW_THREADS / WAVE - 1) / (ROW_THREADS / WAVE)); }
 
+// What the decodes of action vectors (cygym_decode_actions, cygym_actor_head_decode, cygym_actor_mlp_decode,
+// cygym_coord_ascent_decode) check alike.  Two steps, because each function has checks of its own between them and a caller sees
+// which of two failing checks wins.  check_vectors: the handle, the pointers (own_ptrs: the function's own are there), the
+// destination, the row layout against the handle's device count (at least min_te action types and exploits; the function tests
+// its own layout conditions next, under the same message bad_layout).  check_rows (the other action writers too): the row count,
+// and epsilon-greedy needs the rng ticks of a bound handle.
+static int check_vectors(cygym_handle* h, const cygym_action_vectors* src, const cygym_actions* dst, const char* who, bool own_ptrs, int min_te,
+                         const char* bad_layout) {
+  if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
+  if (!src || !dst || !own_ptrs) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (const int rc = check_dst(h, dst, who, false)) return rc;
+  if (src->n_types < min_te || src->n_exploits < min_te || src->n_apps < 0 || src->n_devices != h->t.M) return fail(h, CYGYM_EINVAL, bad_layout, "");
+  return CYGYM_OK;
+}
+static int check_rows(cygym_handle* h, int32_t n, const int32_t* rows, uint64_t epsilon_thr, const char* who) {
+  if (n < 0 || (!rows && n > h->n_envs)) return fail(h, CYGYM_EINVAL, "%s: bad row count", who);
+  if (epsilon_thr && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: epsilon > 0 needs a bound handle", who);
+  return CYGYM_OK;
+}
+// Launch a row decode: its kernel takes (front..., n_envs, ienv, seed, env_id_base, back...).
+static int launch_decode(cygym_handle* h, const void* k, dim3 grid, dim3 block, size_t lds, void* stream, std::initializer_list<const void*> front,
+                         std::initializer_list<const void*> back = {}) {
+  int n_envs = h->n_envs;
+  const int32_t* ienv = h->b.ienv;
+  uint64_t seed = h->c.seed;
+  int64_t base = h->c.env_id_base;
+  void* args[12];
+  int n = 0;
+  for (const void* a : front) args[n++] = const_cast<void*>(a);
+  for (void* a : {(void*)&n_envs, (void*)&ienv, (void*)&seed, (void*)&base}) args[n++] = a;
+  for (const void* a : back) args[n++] = const_cast<void*>(a);
+  HIPCHK(h, hipLaunchKernel(k, grid, block, args, lds, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
 int cygym_derive(cygym_handle* h, const cygym_buffers* bufs, void* stream) {
   if (!h) return fail(h, CYGYM_EINVAL, "cygym_derive: null handle%s", "");
   if (const int rc = check_buffers(h, bufs, true)) return rc;
@@ -602,7 +638,7 @@ int cygym_write_actions(cygym_handle* h, const cygym_action_rows* src, const cyg
   if (!src || !dst || !src->atype || !src->exploit || !src->app || (!src->dev_mask && (!src->dev_idx || !src->dev_cnt)))
     return fail(h, CYGYM_EINVAL, "cygym_write_actions: null source pointer%s", "");
   if (const int rc = check_dst(h, dst, "cygym_write_actions", false)) return rc;
-  if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_write_actions: bad row count%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, "cygym_write_actions")) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   hipLaunchKernelGGL(write_actions_kernel, row_grid(src->n), dim3(ROW_THREADS), 0,
@@ -612,20 +648,14 @@ int cygym_write_actions(cygym_handle* h, const cygym_action_rows* src, const cyg
 }
 
 int cygym_decode_actions(cygym_handle* h, const cygym_action_vectors* src, const cygym_actions* dst, void* stream) {
-  if (!h) return fail(h, CYGYM_EINVAL, "cygym_decode_actions: null handle%s", "");
-  if (!src || !dst || !src->vec) return fail(h, CYGYM_EINVAL, "cygym_decode_actions: null source pointer%s", "");
-  if (const int rc = check_dst(h, dst, "cygym_decode_actions", false)) return rc;
-  if (src->n_types < 0 || src->n_exploits < 0 || src->n_apps < 0 || src->n_devices != h->t.M ||
-      (long long)src->stride < (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps)
-    return fail(h, CYGYM_EINVAL, "cygym_decode_actions: row layout does not fit the stride / the handle's device count%s", "");
-  if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_decode_actions: bad row count%s", "");
-  if (src->epsilon_thr && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_decode_actions: epsilon > 0 needs a bound handle%s", "");
+  const char* const who = "cygym_decode_actions";
+  const char* const bad_layout = "cygym_decode_actions: row layout does not fit the stride / the handle's device count%s";
+  if (const int rc = check_vectors(h, src, dst, who, src && src->vec, 0, bad_layout)) return rc;
+  if ((long long)src->stride < (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps) return fail(h, CYGYM_EINVAL, bad_layout, "");
+  if (const int rc = check_rows(h, src->n, src->rows, src->epsilon_thr, who)) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  hipLaunchKernelGGL(decode_actions_kernel, row_grid(src->n), dim3(ROW_THREADS), 0,
-                     (hipStream_t)stream, *src, *dst, h->n_envs, h->b.ienv, h->c.seed, h->c.env_id_base);
-  HIPCHK(h, hipGetLastError());
-  return CYGYM_OK;
+  return launch_decode(h, (const void*)decode_actions_kernel, row_grid(src->n), dim3(ROW_THREADS), 0, stream, {src, dst});
 }
 
 int cygym_group_actions(cygym_handle* h, const cygym_device_types* src, const cygym_actions* dst, void* stream) {
@@ -634,7 +664,7 @@ int cygym_group_actions(cygym_handle* h, const cygym_device_types* src, const cy
   if (const int rc = check_dst(h, dst, "cygym_group_actions", true)) return rc;
   if (src->n_types < 1 || src->n_types > 32 || (!src->visible && src->role != 1 && src->role != 2))
     return fail(h, CYGYM_EINVAL, "cygym_group_actions: 1 to 32 action types; role 1 or 2 when no visibility mask is given%s", "");
-  if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_group_actions: bad row count%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, "cygym_group_actions")) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   hipLaunchKernelGGL(group_actions_kernel, row_grid(src->n), dim3(ROW_THREADS), 0, (hipStream_t)stream,
@@ -649,7 +679,7 @@ int cygym_sample_group_actions(cygym_handle* h, const cygym_device_logits* src, 
   if (const int rc = check_dst(h, dst, "cygym_sample_group_actions", true)) return rc;
   if (src->n_types < 1 || src->n_types > 32 || src->n_exp < 0 || src->n_exp > 32 || src->n_app < 0 || src->n_app > 32 || (src->role != 1 && src->role != 2))
     return fail(h, CYGYM_EINVAL, "cygym_sample_group_actions: 1 to 32 action types, at most 32 exploit / app logits, role 1 or 2%s", "");
-  if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_sample_group_actions: bad row count%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, "cygym_sample_group_actions")) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   const size_t lds = (size_t)SAMPLE_WPB * ((size_t)((h->t.M + 63) & ~63) + (size_t)WAVE * src->n_types * sizeof(float));
@@ -661,16 +691,14 @@ int cygym_sample_group_actions(cygym_handle* h, const cygym_device_logits* src, 
 
 int cygym_actor_head_decode(cygym_handle* h, const cygym_actor_head* head, const cygym_action_vectors* src,
                             const cygym_actions* dst, void* stream) {
-  if (!h) return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: null handle%s", "");
-  if (!head || !src || !dst || !head->hidden || !head->weight_t) return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: null source pointer%s", "");
-  if (const int rc = check_dst(h, dst, "cygym_actor_head_decode", false)) return rc;
-  if (src->n_types < 0 || src->n_exploits < 0 || src->n_apps < 0 || src->n_devices != h->t.M || head->H < 1 || head->hidden_stride < head->H)
-    return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: bad layout%s", "");
+  const char* const who = "cygym_actor_head_decode";
+  const char* const bad_layout = "cygym_actor_head_decode: bad layout%s";
+  if (const int rc = check_vectors(h, src, dst, who, head && head->hidden && head->weight_t, 0, bad_layout)) return rc;
+  if (head->H < 1 || head->hidden_stride < head->H) return fail(h, CYGYM_EINVAL, bad_layout, "");
   const long long n_out = (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps;
   if (head->H > 256 || n_out > (long long)HEAD_OPL_MAX * WAVE)
     return fail(h, CYGYM_EUNSUPPORTED, "cygym_actor_head_decode: H > 256 or more than 512 outputs%s", "");
-  if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_actor_head_decode: bad row count%s", "");
-  if (src->epsilon_thr && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_actor_head_decode: epsilon > 0 needs a bound handle%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, src->epsilon_thr, who)) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   const int n_out_p = ((int)n_out + 63) & ~63;
@@ -684,23 +712,15 @@ int cygym_actor_head_decode(cygym_handle* h, const cygym_actor_head* head, const
                        : kernel_by_opl<1>(n_out_p / WAVE, [](auto O) { return (const void*)actor_head_kernel<decltype(O)::value>; });
   if (!mfma) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, HEAD_OPL_MAX * WAVE * HEAD_KC * (int)sizeof(float)));
   const int rows_per_wg = 16;   // (both variants: 16 waves, one row each to decode)
-  int n_envs = h->n_envs;
-  const int32_t* ienv = h->b.ienv;
-  uint64_t seed = h->c.seed;
-  int64_t base = h->c.env_id_base;
-  void* args[] = {(void*)head, (void*)src, (void*)dst, &n_envs, &ienv, &seed, &base};
-  HIPCHK(h, hipLaunchKernel(k, dim3((src->n + rows_per_wg - 1) / rows_per_wg), dim3(16 * WAVE), args, lds, (hipStream_t)stream));
-  HIPCHK(h, hipGetLastError());
-  return CYGYM_OK;
+  return launch_decode(h, k, dim3((src->n + rows_per_wg - 1) / rows_per_wg), dim3(16 * WAVE), lds, stream, {head, src, dst});
 }
 
 int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cygym_action_vectors* src, const cygym_actions* dst,
                            void* stream) {
-  if (!h) return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: null handle%s", "");
-  if (!mlp || !src || !dst || (!mlp->obs && !mlp->obs_role) || !mlp->w_head) return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: null source pointer%s", "");
-  if (const int rc = check_dst(h, dst, "cygym_actor_mlp_decode", false)) return rc;
-  if (src->n_types < 0 || src->n_exploits < 0 || src->n_apps < 0 || src->n_devices != h->t.M || mlp->K < 1 || (!mlp->obs_role && mlp->obs_stride < mlp->K))
-    return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: bad layout%s", "");
+  const char* const who = "cygym_actor_mlp_decode";
+  const char* const bad_layout = "cygym_actor_mlp_decode: bad layout%s";
+  if (const int rc = check_vectors(h, src, dst, who, mlp && (mlp->obs || mlp->obs_role) && mlp->w_head, 0, bad_layout)) return rc;
+  if (mlp->K < 1 || (!mlp->obs_role && mlp->obs_stride < mlp->K)) return fail(h, CYGYM_EINVAL, bad_layout, "");
   if (mlp->obs_role) {
     if (!h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_actor_mlp_decode: obs_role needs a bound handle%s", "");
     if (mlp->obs_role < 1 || mlp->obs_role > 2 || (h->t.M & 1) ||
@@ -715,8 +735,7 @@ int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cy
   }
   const long long n_out = (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps;
   if (n_out > 8192) return fail(h, CYGYM_EUNSUPPORTED, "cygym_actor_mlp_decode: more than 8192 outputs%s", "");
-  if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: bad row count%s", "");
-  if (src->epsilon_thr && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_actor_mlp_decode: epsilon > 0 needs a bound handle%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, src->epsilon_thr, who)) return rc;
   if (mlp->n_groups > 1 && (mlp->rows_per_group < 16 || (mlp->rows_per_group & 15)))   // (row r: actor (r / rows_per_group) % n_groups)
     return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: rows_per_group must be a multiple of 16%s", "");
   if (!mlp->obs_role && (unsigned long long)(mlp->obs_by_env ? h->n_envs : src->n) * (unsigned long long)mlp->obs_stride >= (1ull << 32))
@@ -736,32 +755,23 @@ int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cy
     return vw == 0 ? (const void*)actor_mlp_kernel<o, 0> : vw == 4 ? (const void*)actor_mlp_kernel<o, 4> : vw == 2 ? (const void*)actor_mlp_kernel<o, 2> : (const void*)actor_mlp_kernel<o, 1>;
   });
   if (const int rc = raise_lds_once(h, k)) return rc;
-  int n_envs = h->n_envs;
-  const int32_t* ienv = h->b.ienv;
-  uint64_t seed = h->c.seed;
-  int64_t base = h->c.env_id_base;
   unsigned long long* st = h->dbg;   // (diagnostic builds: cygym_set_debug)
   MlpView view = {h->b.live, h->t.os_val, h->t.version, h->t.anomaly, h->b.anomaly, h->t.M, h->t.X, h->c.max_exploits, mlp->obs_role};
-  void* args[] = {(void*)mlp, (void*)src, (void*)dst, &n_envs, &ienv, &seed, &base, &st, &view};
-  HIPCHK(h, hipLaunchKernel(k, dim3((src->n + 15) / 16), dim3(MLP_THREADS), args, lds, (hipStream_t)stream));
-  HIPCHK(h, hipGetLastError());
-  return CYGYM_OK;
+  return launch_decode(h, k, dim3((src->n + 15) / 16), dim3(MLP_THREADS), lds, stream, {mlp, src, dst}, {&st, &view});
 }
 
 int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* src, const cygym_actions* dst,
                               void* stream) {
-  if (!h) return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: null handle%s", "");
-  if (!h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_coord_ascent_decode: handle not bound (the picks are drawn at the envs' rng ticks)%s", "");
-  if (!c || !src || !dst || !c->h_state || !c->w1a_t || !c->w2 || !c->w3) return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: null source pointer%s", "");
-  if (const int rc = check_dst(h, dst, "cygym_coord_ascent_decode", false)) return rc;
-  if (src->n_types < 1 || src->n_exploits < 1 || src->n_apps < 0 || src->n_devices != h->t.M || c->h_stride < c->H1 || c->top_k < 1 ||
-      !(c->tau > 0.0) || !(c->tau < 1e300))
-    return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: bad layout (types, exploits >= 1, the handle's device count, h_stride >= H1, top_k >= 1, tau > 0)%s", "");
+  const char* const who = "cygym_coord_ascent_decode";
+  const char* const bad_layout = "cygym_coord_ascent_decode: bad layout (types, exploits >= 1, the handle's device count, h_stride >= H1, top_k >= 1, tau > 0)%s";
+  if (h && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_coord_ascent_decode: handle not bound (the picks are drawn at the envs' rng ticks)%s", "");
+  if (const int rc = check_vectors(h, src, dst, who, c && c->h_state && c->w1a_t && c->w2 && c->w3, 1, bad_layout)) return rc;
+  if (c->h_stride < c->H1 || c->top_k < 1 || !(c->tau > 0.0) || !(c->tau < 1e300)) return fail(h, CYGYM_EINVAL, bad_layout, "");
   if (c->H1 < 16 || c->H1 > CA_MAX_H || (c->H1 & 15) || c->H2 < 16 || c->H2 > CA_MAX_H || (c->H2 & 15))
     return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: critic widths H1, H2 must be multiples of 16 in 16 .. 128%s", "");
   if (src->n_types > CA_MAX_TYPES || src->n_exploits > CG_MAX_EXPLOITS || src->n_exploits > src->n_devices || c->top_k > CA_MAX_TOPK)
     return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: at most 32 action types, CG_MAX_EXPLOITS exploits (and no more than devices), top_k <= 8%s", "");
-  if (src->n < 0 || (!src->rows && src->n > h->n_envs)) return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: bad row count%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
   if (!(c->noise_std >= 0.0) || !(c->noise_std < 1e300))
     return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: noise_std must be finite and >= 0%s", "");
   if (c->vec_out && c->vec_stride < src->n_types + src->n_devices + src->n_exploits + src->n_apps)
@@ -779,14 +789,7 @@ int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygy
       (const void*)coord_ascent_kernel<false, true, true>,   (const void*)coord_ascent_kernel<true, true, true>};
   const void* k = kernels[(c->top_k > 1 ? 1 : 0) | (c->noise_std > 0.0 ? 2 : 0) | (c->vec_out ? 4 : 0)];
   if (const int rc = raise_lds_once(h, k)) return rc;
-  int n_envs = h->n_envs;
-  const int32_t* ienv = h->b.ienv;
-  uint64_t seed = h->c.seed;
-  int64_t base = h->c.env_id_base;
-  void* args[] = {(void*)c, (void*)src, (void*)dst, &n_envs, &ienv, &seed, &base};
-  HIPCHK(h, hipLaunchKernel(k, dim3(src->n), dim3(CA_THREADS), args, lds, (hipStream_t)stream));   // one workgroup per row
-  HIPCHK(h, hipGetLastError());
-  return CYGYM_OK;
+  return launch_decode(h, k, dim3(src->n), dim3(CA_THREADS), lds, stream, {c, src, dst});   // one workgroup per row
 }
 
 int cygym_fit_forests(const uint16_t* rows, const int64_t* row_ptr, const uint32_t* seeds, const int32_t* n_fits,

@@ -279,6 +279,23 @@ def test_kernel_sources_carry_no_tuning_switches():
     assert not bad, bad
 
 
+def test_group_zero_of_an_action_row_has_one_writer():
+    """The kernels that write group 0 of an action row share ONE ending (RowList in csrc/cg_decode.hpp: compaction, cut at
+    max_devs, zero fill, the row's scalars, CG_DECODE_TRUNCATED); only group_row (several groups per row) keeps its own.  A new
+    decode mode that writes the count or raises the bit by hand shows up here."""
+    src = os.path.join(ROOT, "cygym_amd", "csrc")
+    raised, counts = [], []
+    for fn in sorted(os.listdir(src)):
+        text = open(os.path.join(src, fn), errors="replace").read()
+        raised += [fn] * len(re.findall(r"atomicOr\([^;]*CG_DECODE_TRUNCATED", text))
+        counts += [fn] * text.count("const_cast<int32_t*>(dst.dev_cnt)")
+    assert raised == ["cg_aux_kernels.hpp", "cg_decode.hpp"], raised
+    assert counts == ["cg_aux_kernels.hpp", "cg_decode.hpp"], counts
+    aux = open(os.path.join(src, "cg_aux_kernels.hpp")).read()
+    group_row = aux[aux.index("void group_row("):aux.index("__global__ void group_actions_kernel(")]
+    assert "CG_DECODE_TRUNCATED" in group_row and "const_cast<int32_t*>(dst.dev_cnt)" in group_row
+
+
 # The launch planner (csrc/cg_plan.hpp) is integer arithmetic over a dozen sizes: it is checked here, without a GPU, through
 # tests/plan_probe.cpp.  Each entry: the probe's input line
 #   [+] M E K max_row few_waves full_feature max_devs forced_wpb force_cby_global force_lists_global
