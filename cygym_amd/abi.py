@@ -123,6 +123,13 @@ class Critic(C.Structure):
                 ("b3", C.c_float), ("H1", C.c_int32), ("H2", C.c_int32), ("h_stride", C.c_int32), ("top_k", C.c_int32), ("vec_stride", C.c_int32)]
 
 
+class CommActor(C.Structure):
+    _fields_ = [("tok_base", C.c_void_p), ("tok_dev", C.c_void_p), ("w_type", C.c_void_p), ("b_type", C.c_void_p), ("w_ctx", C.c_void_p),
+                ("b_ctx", C.c_void_p), ("w_v2", C.c_void_p), ("value_out", C.c_void_p), ("logits_out", C.c_void_p),
+                ("exp_logits_out", C.c_void_p), ("app_logits_out", C.c_void_p), ("b_v2", C.c_float), ("H", C.c_int32),
+                ("tok_stride", C.c_int32), ("reserved", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

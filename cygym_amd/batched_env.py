@@ -737,6 +737,55 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_sample_group_actions(self._h, C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_sample_group_actions")
         return types, exp_o, app_o, logp
 
+    def comm_actor_decode(self, rows, tok_base: torch.Tensor, pack, role: str = "defender", noop: int | None = None, single_types=(11, 12),
+                          greedy: bool = False, act=None, logits_out=None, exp_logits_out=None, app_logits_out=None):
+        """The per-device actor-critic of IPPO / MAPPO (CommActorCritic.forward with USE_GAT off, IPPO.py:135-196), the sampling
+        (:524-557) and the grouping (:560-572) for a batch in ONE launch (cygym_comm_actor_decode; include/cygym_abi.h states the
+        arithmetic): tokens, pooled context, heads, value, one Categorical per VISIBLE device (the role's mask, read off the flag
+        plane), exploit and app, their summed log-probability, and the groups written into rows `rows` of `act` -- the decision
+        of sample_group_actions on the same logits, draw for draw.
+          tok_base     [n, H] float32 (unit inner stride): merge.bias + merge.weight[:, :H] @ relu(state_proj(state)) of source row r
+          pack         policies.CommActorCritic.packed(batch): dict with tok_dev [M, H], w_type / w_ctx (pack_linear), b_type [K],
+                       b_ctx [E + A + H], w_v2 [H], b_v2 (float) and the head sizes K, E, A
+          logits_out   optional [n, M, K] float32: receives the type logits of EVERY device (the kernel then computes them all);
+                       exp_logits_out [n, E], app_logits_out [n, A] likewise
+        Returns (types [n, M] uint8 -- 0 where invisible --, exploit [n] int32, app [n] int32, logp [n] float32, value [n] float32).
+        Limits: H a multiple of 16 in 16..128, K, E, A <= 32, E >= 1 (the library answers CYGYM_EUNSUPPORTED / CYGYM_EINVAL)."""
+        dst = self.actions_struct(act)
+        src = abi.DeviceLogits()
+        self._group_rule(src, role, noop, single_types)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not ok(tok_base) or tok_base.dim() != 2 or tok_base.stride(1) != 1:
+            raise ValueError("tok_base must be a [n, H] float32 tensor on the batch's device with unit inner stride")
+        n, H = int(tok_base.shape[0]), int(tok_base.shape[1])
+        K, E, A = int(pack["K"]), int(pack["E"]), int(pack["A"])
+        sizes = {"tok_dev": self.M * H, "w_type": (K + 15) // 16 * 16 * H, "b_type": K, "w_ctx": (E + A + H + 15) // 16 * 16 * H,
+                 "b_ctx": E + A + H, "w_v2": H}
+        if H % 16:
+            sizes["w_type"] = sizes["w_ctx"] = -1   # (pack_linear pads the inner dimension: the library refuses such an H anyway)
+        net = abi.CommActor()
+        for name, want in sizes.items():
+            t = pack[name]
+            if not ok(t) or not t.is_contiguous() or (want >= 0 and int(t.numel()) != want):
+                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device} (CommActorCritic.packed)")
+            setattr(net, name, t.data_ptr())
+        net.tok_base, net.tok_stride, net.H, net.b_v2 = tok_base.data_ptr(), int(tok_base.stride(0)) if n > 1 else H, H, float(pack["b_v2"])
+        types = torch.empty((n, self.M), dtype=torch.uint8, device=self.device)
+        exp_o = torch.empty((n,), dtype=torch.int32, device=self.device)
+        app_o = torch.empty((n,), dtype=torch.int32, device=self.device)
+        logp = torch.empty((n,), dtype=torch.float32, device=self.device)
+        value = torch.empty((n,), dtype=torch.float32, device=self.device)
+        src.types_out, src.exp_out, src.app_out, src.logp_out, net.value_out = (t.data_ptr() for t in (types, exp_o, app_o, logp, value))
+        src.n_types, src.n_exp, src.n_app, src.greedy = K, E, A, int(bool(greedy))
+        for name, t, shape in (("logits_out", logits_out, (n, self.M, K)), ("exp_logits_out", exp_logits_out, (n, E)), ("app_logits_out", app_logits_out, (n, A))):
+            if t is not None:
+                if not ok(t) or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {self.device}")
+                setattr(net, name, t.data_ptr())
+        r = _bind_rows(self, src, rows, n)   # noqa: F841 (alive until the call has returned)
+        _lib.check(self.lib.cygym_comm_actor_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_actor_decode")
+        return types, exp_o, app_o, logp, value
+
     def take_status(self) -> int:
         """Read and clear the batch's status word: the OR of CG_E_TOPO_OVF | CG_E_BUSY_SAT | CG_E_DET_PENDING |
         CG_E_UNPINNED over the envs ticked since the last call (one 4-byte device-to-host copy; synchronises)."""

@@ -1,7 +1,12 @@
 // cg_aux_kernels.hpp -- reset / randomize / derive / observe kernels and the synthetic action script of bench.py.
 // Part of the device code gathered by cg_device.hpp (included inside namespace cygym_k, in order); not a standalone header.
+// The plain (non-template) kernels are defined in the C-ABI unit only (CG_MAIN_UNIT).  group_row and sample_head are force-inlined
+// device functions that comm_actor_kernel (cg_comm_actor.hpp, included at the end) shares with the kernels here: its instantiation
+// unit (cg_inst_comm.hip) includes this file without CG_MAIN_UNIT and sees those two and the template only.
 #ifndef CG_AUX_KERNELS_HPP
 #define CG_AUX_KERNELS_HPP
+
+#ifdef CG_MAIN_UNIT
 
 // ---------------- reset / randomize / observe / action script ----------------
 __global__ void reset_kernel(KParams P, const int32_t* env_ids, int n) {
@@ -143,8 +148,11 @@ __global__ void observe_kernel(KParams P, int role, float* out) {
   }
 }
 
+#endif  // CG_MAIN_UNIT
+
 #include "cg_decode.hpp"      // decode of one row by one wave + the whole-actor kernel (templates: also used by cg_inst_actor.hip)
 
+#ifdef CG_MAIN_UNIT
 // cygym_write_actions: one wave per source row.  A device mask goes through the row writer of cg_decode.hpp (RowList), a given
 // list is copied; no status word, and n_exploit = 0 for "no exploit" (-1).
 __global__ void write_actions_kernel(cygym_action_rows src, cygym_actions dst, int M, int n_envs) {
@@ -170,6 +178,8 @@ __global__ void write_actions_kernel(cygym_action_rows src, cygym_actions dst, i
   const int ex = src.exploit[wave];
   list.finish(dst, row, lane, src.atype[wave], ex, ex >= 0 ? 1 : 0, src.app[wave], nullptr);
 }
+
+#endif  // CG_MAIN_UNIT
 
 // cygym_group_actions (IPPO.py:560-572 for a batch): one wave per row.  For every action type in ascending order the
 // devices that sampled it are ranked with ballots (ascending id = list order); a single-device type keeps the r-th of
@@ -230,6 +240,7 @@ __device__ __forceinline__ void group_row(const uint8_t* ty, const uint8_t* vis,
     if (cut && status) atomicOr(status, CG_DECODE_TRUNCATED);
   }
 }
+#ifdef CG_MAIN_UNIT
 __global__ void group_actions_kernel(cygym_device_types src, cygym_actions dst, int M, int n_envs, const uint8_t* live,
                                      const int32_t* ienv, uint64_t seed, int64_t env_id_base) {
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
@@ -246,6 +257,7 @@ __global__ void group_actions_kernel(cygym_device_types src, cygym_actions dst, 
 // cygym_sample_group_actions (IPPO.py:524-572 for a batch): one wave per row, a lane per device.  Sampling = the inverse CDF
 // of softmax(logits) walked with u = addressed Philox draw / 2^32; the sampled types stay in LDS for the grouping.
 constexpr int SAMPLE_WPB = 4;
+#endif  // CG_MAIN_UNIT
 __device__ __forceinline__ int sample_head(const float* l, const int K, const uint32_t u32, const bool greedy, float& logp) {
   float mx = -__builtin_inff();
   int am = 0;
@@ -262,6 +274,7 @@ __device__ __forceinline__ int sample_head(const float* l, const int K, const ui
   logp = l[pick] - mx - __logf(S);
   return pick;
 }
+#ifdef CG_MAIN_UNIT
 __global__ __launch_bounds__(SAMPLE_WPB * WAVE) void sample_group_actions_kernel(cygym_device_logits src, cygym_actions dst, int M, int n_envs,
                                                                                  const uint8_t* live, const int32_t* ienv, uint64_t seed,
                                                                                  int64_t env_id_base) {
@@ -523,5 +536,8 @@ __global__ void gen_actions_kernel(KParams P, int tick, int32_t* mode, int32_t* 
   }
   dev_cnt[env] = k;
 }
+#endif  // CG_MAIN_UNIT
+
+#include "cg_comm_actor.hpp"   // cygym_comm_actor_decode (a template: instantiated in cg_inst_comm.hip)
 
 #endif  // CG_AUX_KERNELS_HPP

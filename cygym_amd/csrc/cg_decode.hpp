@@ -7,7 +7,7 @@
 //   eps_greedy_type                  the epsilon-greedy type draw: decode_actions_kernel, decode_row_regs, the chunked decode
 //   RowList                          compaction of the ascending device list, cut at max_devs, zero fill, the row's scalars and
 //                                    CG_DECODE_TRUNCATED: write_actions_kernel, decode_actions_kernel, decode_row_regs, the chunked
-//                                    decode, the merge of coord_ascent_kernel (group_row writes several groups: its own code)
+//                                    decode, the merge of coord_ascent_kernel (group_row writes several groups: its own code, cg_aux_kernels.hpp)
 //   decode_row_regs                  decode of a row held in registers: actor_head_kernel, and through head_decode_row (row from LDS)
 //                                    actor_head_mfma_kernel, actor_mlp_kernel, tick_actor_kernel
 #ifndef CG_DECODE_HPP

@@ -1,0 +1,9 @@
+// cg_inst_comm.hip -- the instantiation unit of comm_actor_kernel (cg_comm_actor.hpp): the per-device actor-critic of IPPO / MAPPO,
+// its sampling and its grouping in one launch, <ALL>: with every device's type logits computed and stored (logits_out) and with the
+// logits of the visible devices only.
+#include "cg_device.hpp"
+namespace cygym_k {
+#include "cg_aux_kernels.hpp"   // (without CG_MAIN_UNIT: group_row, sample_head and the template, none of the plain kernels)
+template __global__ void comm_actor_kernel<false>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+template __global__ void comm_actor_kernel<true>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+}  // namespace cygym_k

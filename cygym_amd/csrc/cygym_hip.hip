@@ -64,6 +64,12 @@ extern template __global__ void coord_ascent_kernel<false, true, true>(cygym_cri
 extern template __global__ void coord_ascent_kernel<true, true, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
 }  // namespace cygym_k
 
+// the per-device actor-critic decode lives in its own unit (cg_inst_comm.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void comm_actor_kernel<false>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+extern template __global__ void comm_actor_kernel<true>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+}  // namespace cygym_k
+
 // =====================================================================
 // C ABI
 // =====================================================================
@@ -195,6 +201,7 @@ int cygym_sizeof(int32_t which) {
     case 9: return (int)sizeof(cygym_device_types);
     case 10: return (int)sizeof(cygym_device_logits);
     case 11: return (int)sizeof(cygym_critic);
+    case 12: return (int)sizeof(cygym_comm_actor);
     default: return -1;
   }
 }
@@ -790,6 +797,37 @@ int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygy
   const void* k = kernels[(c->top_k > 1 ? 1 : 0) | (c->noise_std > 0.0 ? 2 : 0) | (c->vec_out ? 4 : 0)];
   if (const int rc = raise_lds_once(h, k)) return rc;
   return launch_decode(h, k, dim3(src->n), dim3(CA_THREADS), lds, stream, {c, src, dst});   // one workgroup per row
+}
+
+int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst,
+                            void* stream) {
+  const char* const who = "cygym_comm_actor_decode";
+  const char* const bad_layout = "cygym_comm_actor_decode: bad layout (types, exploit logits >= 1, tok_stride >= H, role 1 or 2, 16-byte aligned tok_dev / w_type / w_ctx)%s";
+  if (h && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_comm_actor_decode: handle not bound (the visibility mask is read off the flag plane, the draws at the envs' rng ticks)%s", "");
+  // the checks the decodes share, on this call's layout: K types, the handle's devices, E exploit and A app logits
+  cygym_action_vectors lay;
+  memset(&lay, 0, sizeof(lay));
+  if (h && src) { lay.n_types = src->n_types; lay.n_devices = h->t.M; lay.n_exploits = src->n_exp; lay.n_apps = src->n_app; }
+  const bool own = net && src && net->tok_base && net->tok_dev && net->w_type && net->b_type && net->w_ctx && net->b_ctx && net->w_v2 &&
+                   net->value_out && src->types_out;
+  if (const int rc = check_vectors(h, src ? &lay : nullptr, dst, who, own, 1, bad_layout)) return rc;
+  if (const int rc = check_dst(h, dst, who, true)) return rc;
+  if (net->H < 1 || net->tok_stride < net->H || (src->role != 1 && src->role != 2) ||
+      (((uintptr_t)net->tok_dev | (uintptr_t)net->w_type | (uintptr_t)net->w_ctx) & 15))
+    return fail(h, CYGYM_EINVAL, bad_layout, "");
+  if (net->H < 16 || net->H > CM_MAX_H || (net->H & 15) || src->n_types > CM_MAX_HEAD || src->n_exp > CM_MAX_HEAD || src->n_app > CM_MAX_HEAD)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_actor_decode: H must be a multiple of 16 in 16 .. 128, at most 32 action types, exploit and app logits%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const CmPlan pl = cm_plan(net->H, src->n_types, src->n_exp, src->n_app, h->t.M);
+  const size_t lds = (size_t)pl.total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_actor_decode: the per-row buffers do not fit in LDS%s", "");
+  const void* k = net->logits_out ? (const void*)comm_actor_kernel<true> : (const void*)comm_actor_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const uint8_t* live = h->b.live;
+  int M = h->t.M;
+  return launch_decode(h, k, dim3((src->n + CM_WAVES - 1) / CM_WAVES), dim3(CM_THREADS), lds, stream, {net, src, dst}, {&live, &M});   // 16 rows per workgroup
 }
 
 int cygym_fit_forests(const uint16_t* rows, const int64_t* row_ptr, const uint32_t* seeds, const int32_t* n_fits,

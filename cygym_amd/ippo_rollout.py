@@ -91,7 +91,7 @@ def _sample(logits: torch.Tensor, greedy: bool, generator):
 
 @torch.no_grad()
 def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool = False, generator=None, n_types: int | None = None,
-            randomize_on_reset: bool = True, max_ticks: int | None = None, fused_sampling: bool = True) -> Rollout:
+            randomize_on_reset: bool = True, max_ticks: int | None = None, fused_sampling: bool = True, fused_net: bool | None = None) -> Rollout:
     """Collect `n_decisions` decisions of `role` in every env of `batch` (the while-loop of IPPO.py:503-611).
 
     net(state [N, W], vis [N, M]) -> dict with "per_dev_type_logits" [N, M, K], "value" [N] (or [N, 1]), optional
@@ -102,7 +102,16 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
     The batch must have been created with max_groups >= the role's action types and max_devs >= M, and auto_reset on.
     fused_sampling (default): the Categoricals are sampled inside the grouping launch (cygym_sample_group_actions: addressed
     Philox draws, log-probabilities summed in the kernel); False: torch.multinomial with `generator`, then cygym_group_actions.
+    fused_net (default: when `net` is a policies.CommActorCritic): the network itself runs inside that launch as well -- a decision
+    is two addmm plus ONE launch (cygym_comm_actor_decode), tokens and logits never reach HBM, and `value` comes from the kernel.
+    The decisions are those of the torch forward + fused sampling wherever the fp32 logits agree (the draws are the same).
     """
+    from .policies import CommActorCritic
+    fused = isinstance(net, CommActorCritic) if fused_net is None else bool(fused_net)
+    if fused and not isinstance(net, CommActorCritic):
+        raise ValueError("fused_net needs a policies.CommActorCritic")
+    if fused and n_types is not None and int(n_types) != net.n_types:
+        raise ValueError(f"the net has {net.n_types} action types, n_types = {n_types}")
     from .rollout_grid import SequencePolicy, _baseline_code
     if role not in (HL.DEFENDER, HL.ATTACKER):
         raise ValueError("role must be 'attacker' or 'defender'")
@@ -140,10 +149,19 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
             act["mode"] |= (cur_bl + 1) << S.MODE_BASELINE_SHIFT
         if turn == role:
             vis = batch.visibility_mask(role)
-            out = net(obs, vis)
-            pdt = out["per_dev_type_logits"]
-            K = int(pdt.shape[-1]) if n_types is None else int(n_types)
-            if fused_sampling and K == int(pdt.shape[-1]) <= 32:
+            if fused:
+                pk = net.packed(batch)
+                t8, e32, a32, logp, value = batch.comm_actor_decode(None, net.tok_base(obs, pk), pk, role, noop=noop, single_types=SINGLE_DEVICE_TYPES,
+                                                                    greedy=greedy, act=act)
+                types, exp_i, app_i, out = t8.to(torch.int64), e32.to(torch.int64), a32.to(torch.int64), {"value": value}
+                pdt = None
+            else:
+                out = net(obs, vis)
+                pdt = out["per_dev_type_logits"]
+                K = int(pdt.shape[-1]) if n_types is None else int(n_types)
+            if pdt is None:
+                pass
+            elif fused_sampling and K == int(pdt.shape[-1]) <= 32:
                 # sampling, log-probabilities and grouping in ONE launch (addressed Philox draws instead of torch's generator)
                 t8, e32, a32, logp = batch.sample_group_actions(None, pdt.float().contiguous(), _opt(out.get("exp_logits")), _opt(out.get("app_logits")),
                                                                 role, noop=noop, single_types=SINGLE_DEVICE_TYPES, greedy=greedy, act=act)

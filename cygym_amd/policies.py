@@ -11,6 +11,11 @@ architecture (do_agent.py:357-370); `mlp_actor` a smaller one.
 decode_action does not read the actor at all but scores one-device candidate actions with the CRITIC
 (`DoubleOracle.greedy_device_coord_ascent`, do_agent.py:2137-2219); the batch does that in one launch
 (cygym_coord_ascent_decode).  `reference_critic` builds the reference's critic (do_agent.py:373-388).
+
+`CommActorCritic` / `CommActorPolicy` are the third family: the per-device actor-critic of the reference's IPPO / MAPPO agents
+(IPPO.py:135-196 with USE_GAT off, as shipped) and its greedy executor (IPPOCommPolicy.select_action, IPPO.py:237-284), which
+answers with GROUPS of devices per action type; the batch evaluates the network, samples and groups in one launch
+(cygym_comm_actor_decode).
 """
 from __future__ import annotations
 
@@ -478,6 +483,121 @@ class CoordAscentPolicy:
         tm = self._map(obs.device)
         at = at.to(torch.int32) if tm is None else tm[at]
         return {"atype": at, "exploit": ex.to(torch.int32), "dev_mask": on, "app": torch.zeros_like(at)}
+
+
+class CommActorCritic(nn.Module):
+    """The per-device actor-critic of the reference's IPPO / MAPPO agents as it runs with USE_GAT = False (IPPO.py:21, :135-196;
+    MAPPO.py the same), with the reference's parameter names, so that a state dict saved there loads here:
+        hs = relu(state_proj(state));  tok[d] = relu(merge([hs, id_emb[d]]));  ctx = mean over all D tokens
+        per_dev_type_logits = dev_type_head(tok);  exp_logits = exp_head(ctx);  app_logits = app_head(ctx) (A > 0)
+        value = v_head(ctx) (Linear - ReLU - Linear);  every output through nan_to_num(0, 0, 0)
+    The attention layers (`gats.*`) never influence these outputs while USE_GAT is off: they are not built, and their entries of
+    a state dict are accepted and ignored.
+    forward() is the unfactorised network in torch -- the restatement the fused kernel is tested against (dtype=torch.float64)
+    and the torch path of ippo_rollout.collect.  factors() / packed() give the form cygym_comm_actor_decode reads:
+    tok[d] = relu(a + P[d]) with a = merge.bias + merge.weight[:, :H] hs (one vector per env) and the env-independent table
+    P[d] = merge.weight[:, H:] id_emb[d]."""
+
+    def __init__(self, state_dim: int, n_types: int, D: int, E: int, A: int, hidden: int = 128):
+        super().__init__()
+        self.state_dim, self.n_types, self.D, self.E, self.A, self.hidden = int(state_dim), int(n_types), int(D), int(E), int(A), int(hidden)
+        self.state_proj = nn.Linear(self.state_dim, self.hidden)
+        self.id_emb = nn.Embedding(self.D, self.hidden)
+        self.merge = nn.Linear(2 * self.hidden, self.hidden)
+        self.dev_type_head = nn.Linear(self.hidden, self.n_types)
+        self.exp_head = nn.Linear(self.hidden, self.E)
+        self.app_head = nn.Linear(self.hidden, self.A) if self.A > 0 else None
+        self.v_head = nn.Sequential(nn.Linear(self.hidden, self.hidden), nn.ReLU(), nn.Linear(self.hidden, 1))
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("gats.")}, *args, **kwargs)
+
+    @staticmethod
+    def _lin(m, x, dtype):
+        return torch.nn.functional.linear(x, m.weight.to(dtype), m.bias.to(dtype))
+
+    def forward(self, state, vis=None, dtype=None):
+        """state [B, state_dim] -> the reference's dict: per_dev_type_logits [B, D, K], exp_logits [B, E], app_logits [B, A] or
+        None, value [B].  `vis` (the role's visibility mask, what a GAT would read) is accepted and unused.  dtype: evaluate in
+        that precision from the same fp32 parameters (float64: the restatement)."""
+        dt = state.dtype if dtype is None else dtype
+        B = state.shape[0]
+        hs = torch.relu(self._lin(self.state_proj, state.to(dt), dt))
+        tok = torch.relu(self._lin(self.merge, torch.cat([hs[:, None, :].expand(B, self.D, -1), self.id_emb.weight.to(dt)[None].expand(B, -1, -1)], -1), dt))
+        ctx = tok.mean(dim=1)
+        clean = lambda t: torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0)  # noqa: E731
+        return {"per_dev_type_logits": clean(self._lin(self.dev_type_head, tok, dt)),
+                "exp_logits": clean(self._lin(self.exp_head, ctx, dt)),
+                "app_logits": clean(self._lin(self.app_head, ctx, dt)) if self.app_head is not None else None,
+                "value": clean(self._lin(self.v_head[2], torch.relu(self._lin(self.v_head[0], ctx, dt)), dt).squeeze(-1))}
+
+    def factors(self, state, dtype=None):
+        """(tok_base [B, H], tok_dev [D, H]) of the factorised form, in `dtype` (default: the state's)."""
+        dt = state.dtype if dtype is None else dtype
+        H, w = self.hidden, self.merge.weight.to(dt)
+        hs = torch.relu(self._lin(self.state_proj, state.to(dt), dt))
+        return hs @ w[:, :H].t() + self.merge.bias.to(dt), self.id_emb.weight.to(dt) @ w[:, H:].t()
+
+    def packed(self, batch=None):
+        """What cygym_comm_actor_decode reads, as a dict (BatchedCyberDefenseEnv.comm_actor_decode): the table tok_dev, the packed
+        heads, and the transposed matrices of the two addmm of tok_base().  Built once per parameter version."""
+        mods = [self.state_proj, self.merge, self.dev_type_head, self.exp_head, self.v_head[0], self.v_head[2]] + ([self.app_head] if self.app_head is not None else [])
+        ver = tuple((m.weight._version, m.weight.data_ptr(), m.bias._version) for m in mods) + ((self.id_emb.weight._version, self.id_emb.weight.data_ptr()),)
+        if getattr(self, "_pk_ver", None) != ver:
+            from .batched_env import BatchedCyberDefenseEnv as B
+            H = self.hidden
+            with torch.no_grad():
+                wm = self.merge.weight.detach()
+                heads = [self.exp_head] + ([self.app_head] if self.app_head is not None else []) + [self.v_head[0]]
+                self._pk = {
+                    "K": self.n_types, "E": self.E, "A": self.A,
+                    "w_sp_t": self.state_proj.weight.detach().t().contiguous(), "b_sp": self.state_proj.bias.detach().contiguous(),
+                    "w_m_t": wm[:, :H].t().contiguous(), "b_m": self.merge.bias.detach().contiguous(),
+                    "tok_dev": (self.id_emb.weight.detach() @ wm[:, H:].t()).contiguous(),
+                    "w_type": B.pack_linear(self.dev_type_head.weight), "b_type": self.dev_type_head.bias.detach().contiguous(),
+                    "w_ctx": B.pack_linear(torch.cat([m.weight.detach() for m in heads])), "b_ctx": torch.cat([m.bias.detach() for m in heads]).contiguous(),
+                    "w_v2": self.v_head[2].weight.detach().reshape(-1).contiguous(), "b_v2": float(self.v_head[2].bias.detach().reshape(-1)[0]),
+                }
+            self._pk_ver = ver
+        return self._pk
+
+    @torch.no_grad()
+    def tok_base(self, state, pack=None):
+        """a = merge.bias + merge.weight[:, :H] relu(state_proj(state)) for a batch: two addmm."""
+        pk = self.packed() if pack is None else pack
+        return torch.addmm(pk["b_m"], torch.relu_(torch.addmm(pk["b_sp"], state, pk["w_sp_t"])), pk["w_m_t"])
+
+
+class CommActorPolicy:
+    """A trained IPPO / MAPPO strategy in the closed loop: IPPOCommPolicy.select_action (IPPO.py:237-284) for a batch -- the
+    network, one arg-max (greedy) or sample per visible device, the exploit and the app, and the grouping into env.step(groups) --
+    as two addmm plus ONE launch (cygym_comm_actor_decode).  It writes GROUPS (`writes_groups`): simulate_grid gives its role an
+    n_groups tensor of its own; the batch needs max_groups >= n_types - 1 and max_devs >= M.  A single-device type (11, 12) keeps
+    the device the addressed Philox draw picks (the reference: random.choice)."""
+
+    tick_free = True
+    writes_groups = True
+
+    def __init__(self, net: CommActorCritic, role: str, greedy: bool = True):
+        if role not in ("defender", "attacker"):
+            raise ValueError("role must be 'attacker' or 'defender'")
+        self.net, self.role, self.greedy = net, role, bool(greedy)
+        self.noop = 8 if role == "defender" else 3      # DEFENDER_NOOP, ATTACKER_NOOP (IPPO.py:25-26)
+        self.n_types = net.n_types
+        self.action_types = [t for t in range(net.n_types) if t != self.noop]
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs):
+        pk = self.net.packed(batch)
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != self.net.state_dim:
+            raise ValueError(f"obs must be a float32 [n, {self.net.state_dim}] role view")
+        if batch.M != self.net.D:
+            raise ValueError(f"the net was built for {self.net.D} devices, the batch has {batch.M}")
+        batch.comm_actor_decode(rows, self.net.tok_base(obs, pk), pk, self.role, noop=self.noop, greedy=self.greedy, act=act)
+
+    def __call__(self, obs, t, M, L):
+        raise NotImplementedError("a CommActorPolicy answers with groups of devices per action type: a dict of single actions cannot "
+                                  "carry them (it runs through write(), on a batch with cygym_comm_actor_decode)")
 
 
 @torch.no_grad()

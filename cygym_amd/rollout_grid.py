@@ -225,6 +225,26 @@ def _group_actors(batch, items, M, env_order_rpg=None):
     return [(grp, r64, r64.to(torch.int32), sl, rpg)]
 
 
+def _role_actions(batch, pol, M, L):
+    """One action dict per role: the roles share every tensor but the mode words (no per-tick copy in steady state).  A role
+    with a strategy that writes groups (`writes_groups`: policies.CommActorPolicy) also gets an n_groups tensor of its own: the
+    rows its ordinary strategies play stay at 0, and the other role's ticks never see its group counts."""
+    acts = {r: dict(batch.act) for r in pol}
+    for r in acts:
+        acts[r]["mode"] = torch.zeros_like(batch.act["mode"])
+    batch.act["n_groups"].zero_()
+    batch.act["n_exploit"].zero_()
+    for r in pol:
+        grouping = [p for p in pol[r] if getattr(p, "writes_groups", False)]
+        if grouping:
+            K, G = max(int(p.n_types) for p in grouping), int(batch.act["atype"].shape[1])
+            if G < K - 1 or L < M:
+                raise ValueError(f"a {r} strategy writes groups: the batch needs max_groups >= {K - 1} and max_devs >= {M} "
+                                 f"(it has max_groups = {G}, max_devs = {L})")
+            acts[r]["n_groups"] = torch.zeros_like(batch.act["n_groups"])
+    return acts
+
+
 def simulate_grid(batch, def_policies, att_policies, n_mc: int, T: int, randomize: bool = True,
                   group=None, n_total: int | None = None, cell_offset: int = 0, timers: dict | None = None,
                   graph: bool = False, streams: int = 1, merge_launches: bool | None = None, local_only: bool = False):
@@ -238,7 +258,9 @@ def simulate_grid(batch, def_policies, att_policies, n_mc: int, T: int, randomiz
       returns  atype [n] i32, exploit [n] i32 (one exploit index, -1 = none), dev_idx [n, L] i16 + dev_cnt [n] i32
                (or `dev_mask` [n, M] bool instead of the two), app [n] i32 -- device tensors
     or an object with `write(batch, act, rows, obs)` that fills the rows itself (cygym_amd.policies.ActorPolicy: actor
-    forward + ONE fused decode-and-scatter launch).  A policy may declare `action_types` (iterable of the action
+    forward + ONE fused decode-and-scatter launch).  A policy that declares `writes_groups = True` (policies.CommActorPolicy: the
+    per-device actor-critic of IPPO / MAPPO) fills GROUPS and their count; its role then steps from an n_groups tensor of its own,
+    and the batch must have max_groups >= its action types - 1 and max_devs >= M.  A policy may declare `action_types` (iterable of the action
     types it can emit) and `tick_free = True` (its action does not depend on t).  Baseline names and fixed sequences
     are accepted too (wrapped in SequencePolicy; they follow the global tick like the reference).
 
@@ -313,12 +335,7 @@ def simulate_grid(batch, def_policies, att_policies, n_mc: int, T: int, randomiz
     batch.reset()
     if randomize:
         batch.randomize()                                  # do_agent.py:189-190
-    # one action dict per role: the roles share every tensor but the mode words (no per-tick copy in steady state)
-    acts = {r: dict(batch.act) for r in ROLES}
-    for r in acts:
-        acts[r]["mode"] = torch.zeros_like(batch.act["mode"])
-    batch.act["n_groups"].zero_()
-    batch.act["n_exploit"].zero_()
+    acts = _role_actions(batch, pol, M, L)
     # a role whose strategies all build their observation on chip from the state (policies.ActorPolicy.reads_state) needs no
     # role-view tensor: the tick then does not write one
     needs_view = {r: not fused or any(not (hasattr(p, "reads_state") and p.reads_state(batch)) for items in plan[r] for p, _, _, _, _ in items)

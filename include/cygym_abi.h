@@ -191,7 +191,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic; -1 for anything else): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor; -1 for anything else): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -472,6 +472,62 @@ typedef struct cygym_critic {
  * Out of scope: exploit_override (:2147-2149), and building the observation on chip (h_state comes from the caller). */
 int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* layout,
                               const cygym_actions* dst, void* stream);
+
+/* The per-device actor-critic of the reference's IPPO / MAPPO agents with USE_GAT off, as the reference ships it (IPPO.py:21,
+ * MAPPO.py:21): CommActorCritic (IPPO.py:135-196, MAPPO.py the same) in the pieces the decode below reads, all fp32, DEVICE
+ * pointers.  With s the role observation, hs = relu(state_proj(s)) and e_d = id_emb.weight[d] the network is
+ *   tok[d] = relu(merge([hs, e_d])) = relu(a + P[d]),   a = merge.bias + merge.weight[:, :H] hs  (one vector per env: tok_base),
+ *                                                       P[d] = merge.weight[:, H:] e_d           (the same for every env: tok_dev)
+ *   per_dev_type_logits[d] = dev_type_head(tok[d]);  ctx = mean over ALL M devices of tok[d] (the net does not mask);
+ *   exp_logits = exp_head(ctx);  app_logits = app_head(ctx) (A > 0);  value = v_head.2(relu(v_head.0(ctx)));
+ *   each output through nan_to_num(nan = 0, posinf = 0, neginf = 0) (:185-189).
+ * Packed matrices are in the fragment order the whole-actor decode reads (cygym_amd.batched_env.pack_linear):
+ *   packed[t][g][lane][i] = W[16 t + lane % 16][16 g + 4 (lane / 16) + i], zero rows past the last. */
+typedef struct cygym_comm_actor {
+  const float* tok_base;      /* [n][tok_stride] a of SOURCE row r (two addmm of the caller, like h_state of cygym_critic)                */
+  const float* tok_dev;       /* [M][H] the table P, 16-byte aligned                                                                   */
+  const float* w_type;        /* dev_type_head.weight [K][H] packed: [ceil(K / 16)][H / 16][64][4], 16-byte aligned                    */
+  const float* b_type;        /* [K] dev_type_head.bias                                                                                */
+  const float* w_ctx;         /* the heads of ctx as ONE matrix, rows exp_head.weight [E][H] | app_head.weight [A][H] (none when A = 0) |
+                                 v_head.0.weight [H][H], packed: [ceil((E + A + H) / 16)][H / 16][64][4], 16-byte aligned              */
+  const float* b_ctx;         /* [E + A + H] their biases in that order                                                                */
+  const float* w_v2;          /* [H] v_head.2.weight                                                                                   */
+  float* value_out;           /* [n] value of source row r                                                                             */
+  float* logits_out;          /* optional [n][M][K]: the type logits of EVERY device (tests; learners that want the behaviour logits).
+                                 NULL: only the visible devices' logits are computed, none is stored -- the action rows are the same   */
+  float* exp_logits_out;      /* optional [n][E]                                                                                       */
+  float* app_logits_out;      /* optional [n][A]                                                                                       */
+  float   b_v2;               /* v_head.2.bias                                                                                         */
+  int32_t H;                  /* hidden width: a multiple of 16, 16 .. 128 (the reference: 128)                                        */
+  int32_t tok_stride;         /* floats per row of tok_base, >= H                                                                      */
+  int32_t reserved;
+} cygym_comm_actor;
+
+/* Replaces: CommActorCritic.forward (IPPO.py:135-196 with USE_GAT = False), the sampling of the decision (:524-557) and its grouping
+ * into env.step(groups) (:560-572) -- what IPPOCommPolicy.select_action (:237-284) and the collection loop (:503-611) do per
+ * decision -- for a batch, in ONE launch.  `src` is the struct of cygym_sample_group_actions: its logits / exp_logits / app_logits
+ * are NOT read (the logits are computed here); rows, types_out (mandatory), exp_out, app_out, logp_out, n, n_types = K, n_exp = E,
+ * n_app = A, noop, role, single_mask, greedy, status mean what they mean there.
+ * Arithmetic, fp32 throughout (u = 2^-24 per operation):
+ *   ctx[h]      = (sum over d = 0 .. M-1, ascending, one running sum, of 2 relu(a[h] + P[d][h]), halved) / M -- doubling and halving
+ *                 are exact; 2 relu(x) is evaluated as x + |x|: NaN stays NaN as in torch, x = -inf gives NaN where torch gives 0
+ *   a head y    = bias + sum_k W[.][k] x[k] on the matrix cores (v_mfma_f32_16x16x4_f32): ONE fused-multiply-add chain per output that
+ *                 starts at 0 and takes k in the order g = 0 .. H/16-1, i = 0 .. 3, j = 0 .. 3 with k = 16 g + 4 j + i; the bias is added
+ *                 last.  dev_type_head reads tok[d] = relu(a + P[d]) (x < 0 ? 0 : x), the heads of ctx read ctx.
+ *   value       = b_v2 + (lane l of 64 sums w_v2[h] relu(hid[h]) over h = l, l + 64 by fma, then an xor butterfly 32, 16, .., 1)
+ *   nan_to_num  NaN, +inf, -inf -> 0 on the type logits, exp_logits, app_logits and value, before they are stored or sampled.
+ * The decision IS cygym_sample_group_actions on those logits: the same addressed Philox draws (CG_SITE_SAMPLE with a = device,
+ * 1 << 16 for the exploit, 2 << 16 for the app; CG_SITE_GROUP_PICK), the same inverse-CDF walk and arg-max (`greedy`), invisible
+ * devices (the role's mask off the bound flag plane) get label 0 and no log-probability, the log-probabilities are added in that
+ * kernel's order (logp_out agrees bit for bit), then cygym_group_actions: n_groups and the groups of the rows, CG_DECODE_TRUNCATED when
+ * max_groups or max_devs cut a row.  The rng tick is read, not advanced.
+ * Limits (CYGYM_EUNSUPPORTED beyond): H a multiple of 16 in 16 .. 128; K, E, A <= 32; any M of the handle whose per-row buffers fit in
+ * LDS (every M <= 2048 does).  CYGYM_EINVAL (the argument check the decodes share): NULL mandatory pointers, K < 1, E < 1, A < 0,
+ * tok_stride < H, a role other than 1 / 2, a packed matrix or tok_dev off 16-byte alignment.  CYGYM_ENOTBOUND without cygym_bind.
+ * Out of scope: USE_GAT = True (the attention layers over masked_adjacency), populations of nets in one launch, the PPO update, and
+ * building the observation on chip (tok_base comes from the caller). */
+int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst,
+                            void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`
