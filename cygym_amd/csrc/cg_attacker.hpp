@@ -818,6 +818,12 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
     // attribution of that pick, :1163-1168); the counts stay in registers
     int cnt[MCT];
     int total_new = 0;
+    // the blocked-word pair of a source's row, shifted to its first slot: read for the counts, kept for the ring (nothing writes
+    // blk in between) -- for the two blocks that up to 128 sources fill; later blocks read it again
+    constexpr int KB = MCT < 2 ? MCT : 2;
+    uint64_t bitsv[KB];
+#pragma unroll
+    for (int b = 0; b < KB; ++b) bitsv[b] = 0ull;
 #pragma unroll
     for (int b = 0; b < MCT; ++b) {
       cnt[b] = 0;
@@ -834,6 +840,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
         const uint64_t bits = ((uint64_t)e.blk[w0] | ((uint64_t)e.blk[w0 < wl ? w0 + 1 : w0] << 32)) >> (o0 & 31);
         const int len = end - o0;   // 0..33
         n = len - __popcll(len > 0 ? bits & (~0ull >> (64 - len)) : 0ull);
+        if (b < KB) bitsv[b < KB ? b : 0] = bits;
       }
       if (__any(far)) { if (far) n = (end - o0) - (WIDE ? range_popc_wide(e.blk, o0, end) : range_popc(e.blk, o0, end)); }
       if (mine && ((sst[b] >> 16) & CG_D_DC) && k < o1) cby_or(e, (int)(pkv[b] >> 16), ebit);
@@ -864,10 +871,14 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
         // the usual case -- goes with the short rows, one step per ENTRY on the bits of its blocked-word pair)
         const bool is_long = mine && (last - o0 >= 33 || n > LONG_ROW);
         if (mine && !is_long) {
-          // a short row's entries = the clear bits of its blocked-word pair below the pick: one read of the pair, then one step per
-          // ENTRY (not per slot, and no blocked-bit read inside the loop)
-          const int w0 = o0 >> 5, wl = ((P.t.EW + 3) & ~3) - 1;
-          const uint64_t bits = ((uint64_t)e.blk[w0] | ((uint64_t)e.blk[w0 < wl ? w0 + 1 : w0] << 32)) >> (o0 & 31);
+          // a short row's entries = the clear bits of its blocked-word pair below the pick: the pair (kept from the counts, or one
+          // read), then one step per ENTRY (not per slot, and no blocked-bit read inside the loop)
+          uint64_t bits;
+          if (b < KB) bits = bitsv[b < KB ? b : 0];   // (not long => not `far` in the counts: the pair was read there)
+          else {
+            const int w0 = o0 >> 5, wl = ((P.t.EW + 3) & ~3) - 1;
+            bits = ((uint64_t)e.blk[w0] | ((uint64_t)e.blk[w0 < wl ? w0 + 1 : w0] << 32)) >> (o0 & 31);
+          }
           uint64_t z = ~bits & (~0ull >> (63 - (last - o0)));   // slots o0 .. last (rows of <= LONG_ROW slots)
           uint32_t idx = off;
           while (z) {

@@ -142,11 +142,14 @@ struct PoolPtrs {
 // NW: words a row's bits can span, known at compile time (9 at 256 devices, 3 at 64: cygym_create sends a topology with a longer
 // row -- duplicate edges -- to the run-time-size kernels), or 0: run-time sizes, the rolled per-lane loops (both forms in one kernel
 // cost it a wave per SIMD: 114 VGPRs).
+// At a compile-time size the counts leave their packed running popcounts behind (cg_select.hpp) and the select finds its word
+// from them: one read, on ONE side -- range_select_words read the row again, and lanes picking from different sides ran both arms.
 template <int NW>
 __device__ __forceinline__ Pick pool_pick(const PoolPtrs q, bool want, uint32_t u, int o0, int o1, int i0, int i1) {
   Pick p; p.slot = -1; p.j = -1; p.x = -1;
   int nbo, nbi;
-  if constexpr (NW > 0) { nbo = range_popc_words<NW>(q.blk, o0, o1); nbi = range_popc_words<NW>(q.bin, i0, i1); }
+  [[maybe_unused]] uint32_t pko[cg_pk_regs(NW > 0 ? NW : 1)], pki[cg_pk_regs(NW > 0 ? NW : 1)];
+  if constexpr (NW > 0) { nbo = range_popc_prefix<NW>(q.blk, o0, o1, pko); nbi = range_popc_prefix<NW>(q.bin, i0, i1, pki); }
   else { nbo = range_popc(q.blk, o0, o1); nbi = range_popc(q.bin, i0, i1); }
   const int n_out = want ? nbo : (o1 - o0) - nbo;
   const int n_in = want ? nbi : (i1 - i0) - nbi;
@@ -156,8 +159,10 @@ __device__ __forceinline__ Pick pool_pick(const PoolPtrs q, bool want, uint32_t 
   const bool from_out = r < n_out;
   int slot = -1, j = -1;
   if constexpr (NW > 0) {
-    if (from_out) slot = range_select_words<NW>(q.blk, o0, o1, want, r);
-    else          j = range_select_words<NW>(q.bin, i0, i1, want, r - n_out);
+    uint32_t pk[cg_pk_regs(NW > 0 ? NW : 1)];
+#pragma unroll
+    for (int i = 0; i < cg_pk_regs(NW); ++i) pk[i] = from_out ? pko[i] : pki[i];
+    slot = j = range_select_prefix<NW>(from_out ? q.blk : q.bin, pk, from_out ? o0 : i0, want, from_out ? r : r - n_out);
   } else {
     if (from_out) slot = range_select(q.blk, o0, o1, want, r);
     else          j = range_select(q.bin, i0, i1, want, r - n_out);

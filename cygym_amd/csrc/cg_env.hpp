@@ -3,6 +3,8 @@
 #ifndef CG_ENV_HPP
 #define CG_ENV_HPP
 
+#include "cg_select.hpp"   // packed running popcounts of a bit range: plain host-and-device integer code (tests/select_probe.cpp)
+
 // ---------------- per-wave environment view ----------------
 struct Env {
   // LDS, planes at stride MS = round_up(M, 4); padding bytes of `flags` hold CG_F_NYA
@@ -121,6 +123,30 @@ __device__ __forceinline__ int range_popc_words(const uint32_t* blk, int a, int 
   return n;
 }
 __device__ __forceinline__ int range_popc_wide(const uint32_t* blk, int a, int b) { return range_popc_words<CG_WIDE_W>(blk, a, b); }
+// range_popc_words that leaves the packed running popcounts behind (cg_prefix_pack above), and the select on them: the word
+// from the sums, ONE read, the in-word rank by bisection.  pk is read only where the count was not zero.
+template <int W>
+__device__ __forceinline__ int range_popc_prefix(const uint32_t* blk, int a, int b, uint32_t* pk) {
+  if (a >= b) {
+#pragma unroll
+    for (int i = 0; i < cg_pk_regs(W); ++i) pk[i] = 0u;
+    return 0;
+  }
+  const int w0 = a >> 5, w1 = (b - 1) >> 5;
+  uint32_t x[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) { const int w = w0 + j; x[j] = blk[w <= w1 ? w : w1]; }
+  return cg_prefix_pack<W>(x, a, b, pk);
+}
+template <int W>
+__device__ __forceinline__ int range_select_prefix(const uint32_t* blk, const uint32_t* pk, int a, bool want, int r) {
+  int rank;
+  const int wsel = cg_prefix_word<W>(pk, want, r, a & 31, rank);
+  const int w = (a >> 5) + wsel;
+  uint32_t xs = blk[w] ^ (want ? 0u : 0xFFFFFFFFu);
+  if (wsel == 0) xs &= 0xFFFFFFFFu << (a & 31);
+  return (w << 5) + nth_bit32_bisect(xs, rank);
+}
 // slot of the r-th entry in [a, b) whose blocked bit == want (uniform); r must be in range
 __device__ __forceinline__ int range_select(const uint32_t* blk, int a, int b, bool want, int r) {
   const int w0 = a >> 5, w1 = (b - 1) >> 5;
@@ -134,29 +160,6 @@ __device__ __forceinline__ int range_select(const uint32_t* blk, int a, int b, b
   }
   return -1;
 }
-
-// range_select with W words read at once and the in-word rank by bisection; per-lane callers (block / unblock pools).
-// No masks at all: the candidates of the first word BELOW a are skipped by raising the rank by their number; what lies past b --
-// the last word's upper bits, the clamped re-reads of that word -- comes after every candidate in range and is never reached
-// (r is in range).  Five vector instructions per word.
-template <int W>
-__device__ __forceinline__ int range_select_words(const uint32_t* blk, int a, int b, bool want, int r) {
-  const int w0 = a >> 5, w1 = (b - 1) >> 5;
-  const uint32_t inv = want ? 0u : 0xFFFFFFFFu;
-  uint32_t x[W > 1 ? W - 1 : 1];
-#pragma unroll
-  for (int j = 0; j < W - 1; ++j) { const int w = w0 + j; x[j] = blk[w <= w1 ? w : w1] ^ inv; }
-  const int rr = r + __popc(x[0] & ~(0xFFFFFFFFu << (a & 31)));
-  int cum = 0, wsel = 0, rbase = 0;
-#pragma unroll
-  for (int j = 0; j < W - 1; ++j) {
-    cum += __popc(x[j]);
-    if (cum <= rr) { wsel = j + 1; rbase = cum; }   // the candidate lies beyond word j
-  }
-  const uint32_t xs = blk[w0 + wsel] ^ inv;   // one more read for the word itself
-  return ((w0 + wsel) << 5) + nth_bit32_bisect(xs, rr - rbase);
-}
-__device__ __forceinline__ int range_select_wide(const uint32_t* blk, int a, int b, bool want, int r) { return range_select_words<CG_WIDE_W>(blk, a, b, want, r); }
 
 // multiplicity of every device in a list -> bytes in scr (as uint8 [Mp]); ids >= M ignored.
 __device__ __forceinline__ void list_counts(Env& e, const int16_t* dev, int L) {
