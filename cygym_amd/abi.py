@@ -13,7 +13,7 @@ import numpy as np
 from . import rng as R
 from . import spec as S
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
@@ -128,6 +128,14 @@ class CommActor(C.Structure):
                 ("b_ctx", C.c_void_p), ("w_v2", C.c_void_p), ("value_out", C.c_void_p), ("logits_out", C.c_void_p),
                 ("exp_logits_out", C.c_void_p), ("app_logits_out", C.c_void_p), ("b_v2", C.c_float), ("H", C.c_int32),
                 ("tok_stride", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CommEval(C.Structure):
+    _fields_ = [("tok_base", C.c_void_p), ("tok_dev", C.c_void_p), ("w_type", C.c_void_p), ("w_type_rows", C.c_void_p), ("b_type", C.c_void_p),
+                ("types", C.c_void_p), ("vis", C.c_void_p), ("logp_dev", C.c_void_p), ("logp_lo", C.c_void_p), ("ent_dev", C.c_void_p), ("ctx", C.c_void_p),
+                ("logits_out", C.c_void_p), ("g_logp", C.c_void_p), ("g_ent", C.c_void_p), ("g_ctx", C.c_void_p), ("grad_tok_base", C.c_void_p),
+                ("grad_tok_dev", C.c_void_p), ("grad_w_type", C.c_void_p), ("grad_b_type", C.c_void_p), ("partials", C.c_void_p),
+                ("n", C.c_int32), ("M", C.c_int32), ("H", C.c_int32), ("K", C.c_int32), ("tok_stride", C.c_int32), ("n_partials", C.c_int32)]
 
 
 DECODE_TRUNCATED = 0x10000

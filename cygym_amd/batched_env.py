@@ -786,6 +786,83 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_comm_actor_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_actor_decode")
         return types, exp_o, app_o, logp, value
 
+    def _comm_eval(self, tok_base, tok_dev, w_type, b_type, types, vis, backward: bool):
+        """The CommEval struct of comm_actor_evaluate / comm_actor_evaluate_backward from the factorised inputs, and what has to
+        stay alive until the call has returned.  dev_type_head.weight is packed here, per call: the weights change every step."""
+        f32 = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not f32(tok_base) or tok_base.dim() != 2 or tok_base.stride(1) != 1:
+            raise ValueError("tok_base must be a [n, H] float32 tensor on the batch's device with unit inner stride")
+        n, H = int(tok_base.shape[0]), int(tok_base.shape[1])
+        if not f32(tok_dev) or tok_dev.dim() != 2 or int(tok_dev.shape[1]) != H or not tok_dev.is_contiguous():
+            raise ValueError(f"tok_dev must be a contiguous float32 [M, {H}] tensor on {self.device}")
+        M = int(tok_dev.shape[0])
+        if not f32(w_type) or w_type.dim() != 2 or int(w_type.shape[1]) != H or not w_type.is_contiguous():
+            raise ValueError(f"w_type must be a contiguous float32 [K, {H}] tensor on {self.device} (dev_type_head.weight)")
+        K = int(w_type.shape[0])
+        if not f32(b_type) or tuple(b_type.shape) != (K,) or not b_type.is_contiguous():
+            raise ValueError(f"b_type must be a contiguous float32 [{K}] tensor on {self.device}")
+        for name, t in (("types", types), ("vis", vis)):
+            if t.dtype != torch.uint8 or t.device != self.device or tuple(t.shape) != (n, M) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous uint8 [{n}, {M}] tensor on {self.device}")
+        e = abi.CommEval()
+        packed = self.pack_linear(w_type)
+        e.tok_base, e.tok_dev, e.w_type, e.b_type, e.types, e.vis = (t.data_ptr() for t in (tok_base, tok_dev, packed, b_type, types, vis))
+        if backward:
+            e.w_type_rows = w_type.data_ptr()
+        e.n, e.M, e.H, e.K, e.tok_stride = n, M, H, K, int(tok_base.stride(0)) if n > 1 else H
+        return e, (packed,), (n, M, H, K)
+
+    def _eval_out(self, out, shapes, what):
+        if out is None:
+            return tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
+        out = tuple(out)
+        if len(out) != len(shapes) or any(t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != tuple(s) or not t.is_contiguous()
+                                          for t, s in zip(out, shapes)):
+            raise ValueError(f"out must be contiguous float32 tensors {[list(s) for s in shapes]} on {self.device} ({what})")
+        return out
+
+    def comm_actor_evaluate(self, tok_base, tok_dev, w_type, b_type, types, vis, logits_out=None, out=None):
+        """The per-device part of the PPO update's evaluate (IPPO.py:711-739) for n stored decisions in ONE launch
+        (cygym_comm_actor_evaluate; include/cygym_abi.h states the arithmetic): with x[d] = relu(tok_base + tok_dev[d]),
+        the summed log-probability of the stored types and the summed entropy of the VISIBLE devices' Categoricals, and the pooled
+        context ctx = mean over all devices of x.  Tokens and logits never reach HBM.
+          tok_base [n, H], tok_dev [M, H], w_type [K, H] (dev_type_head.weight as it lies), b_type [K]: float32
+          types, vis [n, M] uint8: the stored decision (types clamped to K - 1) and the stored visibility mask -- the batch's
+                   flag plane is not read, and M is tok_dev's, not the batch's
+          logits_out optional [n, M, K] float32: receives every device's clean type logits (tests)
+          out      optional (logp_dev [n], ent_dev [n], ctx [n, H], logp_lo [n]) to write into
+        Returns (logp_dev, ent_dev, ctx, logp_lo): logp_dev is a compensated sum, logp_dev + logp_lo in float64 carries what the
+        fp32 rounding of a sum of tens of nats drops (the PPO ratio exp(logp - logp_old) sees that as relative error).  Limits: H a multiple of 16 in 16..128, K <= 32, M <= 2048 (CYGYM_EUNSUPPORTED)."""
+        e, keep, (n, M, H, K) = self._comm_eval(tok_base, tok_dev, w_type, b_type, types, vis, False)   # noqa: F841 (keep: alive until the call has returned)
+        logp, ent, ctx, lo = self._eval_out(out, ((n,), (n,), (n, H), (n,)), "logp_dev, ent_dev, ctx, logp_lo")
+        e.logp_dev, e.ent_dev, e.ctx, e.logp_lo = logp.data_ptr(), ent.data_ptr(), ctx.data_ptr(), lo.data_ptr()
+        if logits_out is not None:
+            if logits_out.dtype != torch.float32 or logits_out.device != self.device or tuple(logits_out.shape) != (n, M, K) or not logits_out.is_contiguous():
+                raise ValueError(f"logits_out must be a contiguous float32 {[n, M, K]} tensor on {self.device}")
+            e.logits_out = logits_out.data_ptr()
+        _lib.check(self.lib.cygym_comm_actor_evaluate(self._h, C.byref(e), self._stream()), self._h, "cygym_comm_actor_evaluate")
+        return logp, ent, ctx, lo
+
+    def comm_actor_evaluate_backward(self, tok_base, tok_dev, w_type, b_type, types, vis, g_logp, g_ent, g_ctx, out=None):
+        """The backward of comm_actor_evaluate (cygym_comm_actor_evaluate_backward: one launch plus the reduction of the
+        workgroups' partials): given the gradients of a loss with respect to logp_dev [n], ent_dev [n] and ctx [n, H], it
+        recomputes tokens, logits and softmax on chip and returns (grad_tok_base [n, H], grad_tok_dev [M, H], grad_w_type [K, H],
+        grad_b_type [K]).  No atomics: the same inputs give the same bits.  The workspace is ceil(n / 16) (M H + K H + K) floats."""
+        e, keep, (n, M, H, K) = self._comm_eval(tok_base, tok_dev, w_type, b_type, types, vis, True)   # noqa: F841
+        gs = []
+        for name, t, shape in (("g_logp", g_logp, (n,)), ("g_ent", g_ent, (n,)), ("g_ctx", g_ctx, (n, H))):
+            if t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be a float32 {list(shape)} tensor on {self.device}")
+            gs.append(t.contiguous())
+        e.g_logp, e.g_ent, e.g_ctx = (t.data_ptr() for t in gs)
+        ga, gp, gw, gb = self._eval_out(out, ((n, H), (M, H), (K, H), (K,)), "grad_tok_base, grad_tok_dev, grad_w_type, grad_b_type")
+        e.grad_tok_base, e.grad_tok_dev, e.grad_w_type, e.grad_b_type = ga.data_ptr(), gp.data_ptr(), gw.data_ptr(), gb.data_ptr()
+        nwg = (n + 15) // 16
+        part = torch.empty((nwg * (M * H + K * H + K),), dtype=torch.float32, device=self.device)
+        e.partials, e.n_partials = part.data_ptr(), nwg
+        _lib.check(self.lib.cygym_comm_actor_evaluate_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_comm_actor_evaluate_backward")
+        return ga, gp, gw, gb
+
     def take_status(self) -> int:
         """Read and clear the batch's status word: the OR of CG_E_TOPO_OVF | CG_E_BUSY_SAT | CG_E_DET_PENDING |
         CG_E_UNPINNED over the envs ticked since the last call (one 4-byte device-to-host copy; synchronises)."""

@@ -49,6 +49,7 @@ INST = os.path.join(HERE, "csrc", "cg_inst.hip")
 INST_ACTOR = os.path.join(HERE, "csrc", "cg_inst_actor.hip")
 INST_COORD = os.path.join(HERE, "csrc", "cg_inst_coord.hip")
 INST_COMM = os.path.join(HERE, "csrc", "cg_inst_comm.hip")
+INST_EVAL = os.path.join(HERE, "csrc", "cg_inst_eval.hip")
 N_GROUPS = 8   # CG_INST_GROUPS of csrc/cg_device.hpp
 GROUP_MT = {0: 256, 1: 256, 2: 64, 3: 64, 4: 0, 5: 0, 6: 0, 7: 0}   # device-count class each instantiation group holds
 
@@ -74,6 +75,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
             units.append(("inst_actor", base + ["-c", INST_ACTOR, "-o", os.path.join(tmp, "inst_actor.o")]))
         units.append(("inst_coord", base + ["-c", INST_COORD, "-o", os.path.join(tmp, "inst_coord.o")]))   # the coordinate-ascent decode
         units.append(("inst_comm", base + ["-c", INST_COMM, "-o", os.path.join(tmp, "inst_comm.o")]))   # the per-device actor-critic decode
+        units.append(("inst_eval", base + ["-c", INST_EVAL, "-o", os.path.join(tmp, "inst_eval.o")]))   # its evaluate / backward (the PPO update)
 
         def run(unit):
             name, cmd = unit

@@ -70,6 +70,16 @@ extern template __global__ void comm_actor_kernel<false>(cygym_comm_actor, cygym
 extern template __global__ void comm_actor_kernel<true>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 }  // namespace cygym_k
 
+// the evaluate / backward kernels of the PPO update live in their own unit (cg_inst_eval.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void comm_eval_fwd_kernel<1, false>(cygym_comm_eval);
+extern template __global__ void comm_eval_fwd_kernel<1, true>(cygym_comm_eval);
+extern template __global__ void comm_eval_fwd_kernel<2, false>(cygym_comm_eval);
+extern template __global__ void comm_eval_fwd_kernel<2, true>(cygym_comm_eval);
+extern template __global__ void comm_eval_bwd_kernel<1>(cygym_comm_eval);
+extern template __global__ void comm_eval_bwd_kernel<2>(cygym_comm_eval);
+}  // namespace cygym_k
+
 // =====================================================================
 // C ABI
 // =====================================================================
@@ -202,6 +212,7 @@ int cygym_sizeof(int32_t which) {
     case 10: return (int)sizeof(cygym_device_logits);
     case 11: return (int)sizeof(cygym_critic);
     case 12: return (int)sizeof(cygym_comm_actor);
+    case 14: return (int)sizeof(cygym_comm_eval);   // (13 stays unassigned: -1)
     default: return -1;
   }
 }
@@ -828,6 +839,56 @@ int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const 
   const uint8_t* live = h->b.live;
   int M = h->t.M;
   return launch_decode(h, k, dim3((src->n + CM_WAVES - 1) / CM_WAVES), dim3(CM_THREADS), lds, stream, {net, src, dst}, {&live, &M});   // 16 rows per workgroup
+}
+
+// What the two evaluate calls check alike, in the order of the decodes' shared check: handle, pointers, layout (CYGYM_EINVAL),
+// then the implemented range (CYGYM_EUNSUPPORTED).
+static int check_eval(cygym_handle* h, const cygym_comm_eval* e, const char* who, bool own_ptrs) {
+  if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
+  if (!e || !own_ptrs || !e->tok_base || !e->tok_dev || !e->w_type || !e->b_type || !e->types || !e->vis)
+    return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (e->n < 1 || e->K < 1 || e->M < 1 || e->H < 1 || e->tok_stride < e->H || (((uintptr_t)e->tok_dev | (uintptr_t)e->w_type) & 15))
+    return fail(h, CYGYM_EINVAL, "%s: bad layout (n, K, M >= 1, tok_stride >= H, 16-byte aligned tok_dev / w_type)", who);
+  if (e->H < 16 || e->H > CE_MAX_H || (e->H & 15) || e->K > CE_MAX_K || e->M > CE_MAX_M)
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: H must be a multiple of 16 in 16 .. 128, at most 32 action types, at most 2048 devices", who);
+  return CYGYM_OK;
+}
+
+int cygym_comm_actor_evaluate(cygym_handle* h, const cygym_comm_eval* e, void* stream) {
+  const char* const who = "cygym_comm_actor_evaluate";
+  if (const int rc = check_eval(h, e, who, e && e->logp_dev && e->ent_dev && e->ctx)) return rc;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const int KT = e->K > 16 ? 2 : 1;
+  const size_t lds = (size_t)ce_plan(e->H, KT, e->M, false).total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the workgroup's buffers do not fit in LDS", who);
+  const void* k = KT == 2 ? (e->logits_out ? (const void*)comm_eval_fwd_kernel<2, true> : (const void*)comm_eval_fwd_kernel<2, false>)
+                          : (e->logits_out ? (const void*)comm_eval_fwd_kernel<1, true> : (const void*)comm_eval_fwd_kernel<1, false>);
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  void* args[] = {(void*)e};
+  HIPCHK(h, hipLaunchKernel(k, dim3((e->n + CE_ROWS - 1) / CE_ROWS), dim3(CE_THREADS), args, lds, (hipStream_t)stream));   // 16 rows per workgroup
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+int cygym_comm_actor_evaluate_backward(cygym_handle* h, const cygym_comm_eval* e, void* stream) {
+  const char* const who = "cygym_comm_actor_evaluate_backward";
+  if (const int rc = check_eval(h, e, who, e && e->w_type_rows && e->g_logp && e->g_ent && e->g_ctx && e->grad_tok_base && e->grad_tok_dev &&
+                                               e->grad_w_type && e->grad_b_type && e->partials)) return rc;
+  const int nwg = (e->n + CE_ROWS - 1) / CE_ROWS;
+  if (e->n_partials < nwg) return fail(h, CYGYM_EINVAL, "%s: n_partials must be at least ceil(n / 16)", who);
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const int KT = e->K > 16 ? 2 : 1;
+  const size_t lds = (size_t)ce_plan(e->H, KT, e->M, true).total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the workgroup's buffers do not fit in LDS", who);
+  const void* k = KT == 2 ? (const void*)comm_eval_bwd_kernel<2> : (const void*)comm_eval_bwd_kernel<1>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  void* args[] = {(void*)e};
+  HIPCHK(h, hipLaunchKernel(k, dim3(nwg), dim3(CE_THREADS), args, lds, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  const size_t total = (size_t)e->M * e->H + (size_t)e->K * e->H + (size_t)e->K;
+  hipLaunchKernelGGL(comm_eval_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *e, nwg);
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
 }
 
 int cygym_fit_forests(const uint16_t* rows, const int64_t* row_ptr, const uint32_t* seeds, const int32_t* n_fits,

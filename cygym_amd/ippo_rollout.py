@@ -17,7 +17,10 @@ for all envs in one forward, the Categoricals are sampled as one batched draw, t
 lock step from a common step_num (episodes end at the step cap only, CyberDefenseEnv.py:547-552), so the turn is the same
 for every env; the cap's auto-reset reloads the snapshot the batch was created with, and the ownership reshuffle follows.
 
-`gae` is compute_gae (IPPO.py:301-310) for [T, N] tensors.
+`gae` is compute_gae (IPPO.py:301-310) for [T, N] tensors; `advantages` and `ppo_update` are the learning half (:626-781): the
+bootstrap value, the clips and the normalisation of the advantages, the minibatch loop with the clipped-surrogate loss, gradient
+clipping and the optimiser step -- the evaluation of the stored decisions through CommActorCritic.evaluate, which on a batch runs
+the per-device part and its backward in the library (cygym_comm_actor_evaluate).
 """
 from __future__ import annotations
 
@@ -31,6 +34,9 @@ from . import spec as S
 DEFENDER_NOOP, ATTACKER_NOOP = 8, 3          # IPPO.py:25-26
 SINGLE_DEVICE_TYPES = (11, 12)               # IPPO.py:27
 REWARD_SCALE = 1e-1                          # IPPO.py:31
+ADV_NORM_MIN_N, ADV_CLIP, RET_CLIP = 8, 1e4, 1e4                           # IPPO.py:32-34
+CLIP_LOGP_DIFF, VALUE_CLIP_EPS, VALUE_TARGET_CLIP = 20.0, 0.2, 1e4         # IPPO.py:35-37
+ENT_COEF, VF_COEF, MAX_GRAD_NORM, CLIP_EPS = 1e-3, 0.5, 0.5, 0.2           # IPPO.py:38-40, :341
 
 
 @dataclass
@@ -211,3 +217,77 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
     last_state = batch.observe(1 if role == HL.DEFENDER else 2)
     st = {k: torch.stack(v) for k, v in rec.items()}
     return Rollout(last_state=last_state, last_vis=batch.visibility_mask(role), **st)
+
+
+def advantages(rollout: Rollout, next_value: torch.Tensor, gamma: float = 0.99, lam: float = 0.95):
+    """IPPO.py:634-652 for [T, N]: nan_to_num of the rewards (+-inf -> +-1e6) and of the values (-> 0), `gae` per env column on
+    reward * REWARD_SCALE with next_value [N] as the bootstrap, the clips at ADV_CLIP / RET_CLIP, and -- when T N >= 8 -- the
+    normalisation of the advantages by their mean and unbiased standard deviation (clamp_min 1e-3) over all T N entries, clamped
+    to +-3.  Returns (advantages, returns) [T, N] float32."""
+    r = torch.nan_to_num(rollout.reward.to(torch.float32), nan=0.0, posinf=1e6, neginf=-1e6)
+    v = torch.nan_to_num(torch.cat([rollout.value.to(torch.float32), next_value.to(torch.float32).reshape(1, -1)]), nan=0.0, posinf=0.0, neginf=0.0)
+    adv, ret = gae(r * REWARD_SCALE, v, rollout.done)
+    adv = torch.nan_to_num(adv, nan=0.0, posinf=ADV_CLIP, neginf=-ADV_CLIP).clamp(-ADV_CLIP, ADV_CLIP)
+    ret = torch.nan_to_num(ret, nan=0.0, posinf=RET_CLIP, neginf=-RET_CLIP).clamp(-RET_CLIP, RET_CLIP)
+    if adv.numel() >= ADV_NORM_MIN_N:
+        mean = torch.nan_to_num(adv.mean(), nan=0.0)
+        std = torch.nan_to_num(adv.std(), nan=1.0).clamp_min(1e-3)
+        adv = ((adv - mean) / std).clamp(-3.0, 3.0)
+    return adv, ret
+
+
+def ppo_loss(logp, entropy, value, old_logp, old_value, adv, ret, *, clip_eps: float = CLIP_EPS, ent_coef: float = ENT_COEF,
+             vf_coef: float = VF_COEF):
+    """The loss of one minibatch (IPPO.py:751-767) from evaluate()'s outputs and the stored quantities (`ret` already clamped to
+    +-VALUE_TARGET_CLIP): returns (loss, policy loss, value loss, mean entropy)."""
+    clean = lambda t: torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0)  # noqa: E731
+    # (logp arrives in float64, see CommActorCritic.evaluate: the DIFFERENCE is what fp32 can hold)
+    ratio = torch.exp((clean(logp) - clean(old_logp)).clamp(-CLIP_LOGP_DIFF, CLIP_LOGP_DIFF).to(adv.dtype))
+    pol = -torch.min(ratio * adv, torch.clamp(ratio, 1.0 - clip_eps, 1.0 + clip_eps) * adv).mean()
+    v = clean(value)
+    v_clipped = old_value + (v - old_value).clamp(-VALUE_CLIP_EPS, VALUE_CLIP_EPS)
+    v_loss = torch.max(torch.nn.functional.mse_loss(v, ret), torch.nn.functional.mse_loss(v_clipped, ret))
+    ent = clean(entropy.mean())
+    return pol - ent_coef * ent + vf_coef * v_loss, pol, v_loss, ent
+
+
+def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minibatch_size: int = 256, generator=None, fused=None,
+               gamma: float = 0.99, lam: float = 0.95, clip_eps: float = CLIP_EPS, ent_coef: float = ENT_COEF, vf_coef: float = VF_COEF,
+               max_grad_norm: float = MAX_GRAD_NORM):
+    """The PPO update of IPPOCommBestResponse.train (IPPO.py:626-781) on a Rollout: the bootstrap value from rollout.last_state,
+    `advantages`, then `epochs` passes over the T N rows, flattened and shuffled (torch.randperm with `generator`) into minibatches
+    of `minibatch_size`; per minibatch net.evaluate (fused on `batch` by default, see CommActorCritic.evaluate), `ppo_loss`,
+    backward, clip_grad_norm_(max_grad_norm), opt.step().  A minibatch with non-finite advantages, returns or loss is skipped
+    (:707-709, :769): that decision is ONE scalar read (a device synchronisation) per minibatch, after the loss has been formed.
+    Returns the last stepped minibatch's {"loss", "policy_loss", "value_loss", "entropy", "grad_norm" (before clipping)} as
+    0-dim tensors, and "updates", the number of optimiser steps.
+
+    The reference's loop as shipped collects exactly ONE Step per update (`while len(local_batch) == 0`, :503): for T N = 1 this
+    function is that update.  For more rows it is the same formulas, which the reference writes for a minibatch.  Out of scope:
+    USE_GAT, AMP, the budget bookkeeping and the progress prints."""
+    with torch.no_grad():
+        next_value = net(rollout.last_state)["value"].reshape(-1)
+        adv, ret = advantages(rollout, next_value, gamma, lam)
+    T, N = rollout.logp.shape
+    B = T * N
+    flat = lambda t: t.reshape(B, *t.shape[2:])  # noqa: E731
+    state, types, vis, exp, app = (flat(t) for t in (rollout.state, rollout.per_dev_types, rollout.vis_mask, rollout.exp, rollout.app))
+    old_logp, old_value, adv, ret = (flat(t).to(torch.float32) for t in (rollout.logp, rollout.value, adv, ret))
+    last, updates = {}, 0
+    for _ in range(int(epochs)):
+        perm = torch.randperm(B, generator=generator).to(state.device)
+        for start in range(0, B, int(minibatch_size)):
+            mb = perm[start: start + int(minibatch_size)]
+            adv_mb, ret_mb = adv[mb], ret[mb].clamp(-VALUE_TARGET_CLIP, VALUE_TARGET_CLIP)
+            logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], batch=batch, fused=fused)
+            loss, pol, v_loss, ent_mean = ppo_loss(logp, ent, value, old_logp[mb], old_value[mb], adv_mb, ret_mb, clip_eps=clip_eps,
+                                                   ent_coef=ent_coef, vf_coef=vf_coef)
+            if not bool((torch.isfinite(adv_mb).all() & torch.isfinite(ret_mb).all() & torch.isfinite(loss)).item()):
+                continue
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            norm = torch.nn.utils.clip_grad_norm_(net.parameters(), max_grad_norm)
+            opt.step()
+            updates += 1
+            last = {"loss": loss.detach(), "policy_loss": pol.detach(), "value_loss": v_loss.detach(), "entropy": ent_mean.detach(), "grad_norm": norm.detach()}
+    return dict(last, updates=updates)

@@ -485,6 +485,27 @@ class CoordAscentPolicy:
         return {"atype": at, "exploit": ex.to(torch.int32), "dev_mask": on, "app": torch.zeros_like(at)}
 
 
+class _CommEvaluate(torch.autograd.Function):
+    """cygym_comm_actor_evaluate and its backward as one differentiable op: (tok_base, tok_dev, dev_type_head.weight, .bias) ->
+    (logp_dev, ent_dev, ctx, logp_lo) for stored types / visibility (logp_dev + logp_lo: the compensated sum, see evaluate()).  Nothing but the inputs is kept for backward: the kernel recomputes."""
+
+    @staticmethod
+    def forward(ctx, batch, types, vis, tok_base, tok_dev, w_type, b_type):
+        ins = tuple(t.detach().contiguous() for t in (tok_base, tok_dev, w_type, b_type))
+        ctx.batch = batch
+        ctx.save_for_backward(*ins, types, vis)
+        return batch.comm_actor_evaluate(*ins, types, vis)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logp, g_ent, g_ctx, g_lo):     # (g_lo is ignored: evaluate() adds logp_lo detached, as a correction of the value only)
+        a, P, w, b, types, vis = ctx.saved_tensors
+        z = lambda g, like: torch.zeros(like, dtype=torch.float32, device=a.device) if g is None else g.float()  # noqa: E731
+        n, H = a.shape
+        ga, gp, gw, gb = ctx.batch.comm_actor_evaluate_backward(a, P, w, b, types, vis, z(g_logp, (n,)), z(g_ent, (n,)), z(g_ctx, (n, H)))
+        return None, None, None, ga, gp, gw, gb
+
+
 class CommActorCritic(nn.Module):
     """The per-device actor-critic of the reference's IPPO / MAPPO agents as it runs with USE_GAT = False (IPPO.py:21, :135-196;
     MAPPO.py the same), with the reference's parameter names, so that a state dict saved there loads here:
@@ -537,6 +558,54 @@ class CommActorCritic(nn.Module):
         H, w = self.hidden, self.merge.weight.to(dt)
         hs = torch.relu(self._lin(self.state_proj, state.to(dt), dt))
         return hs @ w[:, :H].t() + self.merge.bias.to(dt), self.id_emb.weight.to(dt) @ w[:, H:].t()
+
+    def evaluate(self, state, types, vis, exp, app=None, *, batch=None, fused=None, dtype=None):
+        """The PPO update's evaluation of STORED decisions under the current weights (IPPO.py:719-749), vectorised over the batch:
+            logp    [B] = sum over visible devices of log_softmax(type logits)[stored type] + the exploit's (+ the app's, A > 0),
+                          accumulated and returned in float64 on both paths: the sum is some tens of nats, and one fp32 unit in its
+                          last place (2^-18 at 32..64 nats) is that much RELATIVE error on the PPO ratio exp(logp - logp_old), i.e.
+                          64 u on every policy gradient -- the terms are fp32 (or `dtype`), only their sum is wider
+            entropy [B] = sum over visible devices of the Categorical's entropy + the exploit's (+ the app's)
+            value   [B]
+        all differentiable with respect to every parameter.  state [B, state_dim]; types [B, D] integer (clamped to 0 .. K-1; 0
+        where invisible, :730-734); vis [B, D] (visible where > 0.5 -- the STORED mask: the rows come from past states); exp, app
+        [B] integer (app ignored when A = 0).
+        fused (the default when `batch`, a BatchedCyberDefenseEnv on the parameters' device, is given): factors() in torch with
+        autograd, then the per-device part -- tokens, type logits, softmax, the sums over devices, the pooled context, and their
+        backward -- as the library's two launches (cygym_comm_actor_evaluate / _backward behind one autograd.Function; neither
+        tokens nor logits reach HBM); the heads of ctx stay in torch ([B, H] products).
+        fused=False: the same quantities from forward() with one log_softmax over [B, D, K]; runs anywhere, in `dtype`
+        (torch.float64: the restatement the fused path is tested against)."""
+        fused = batch is not None if fused is None else bool(fused)
+        visb = vis > 0.5 if vis.dtype != torch.bool else vis
+        tgt = torch.where(visb, types.long().clamp(0, self.n_types - 1), torch.zeros_like(types, dtype=torch.long))
+        clean = lambda t: torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0)  # noqa: E731
+        if fused:
+            if batch is None:
+                raise ValueError("the fused evaluate runs through a BatchedCyberDefenseEnv: pass batch=")
+            if dtype not in (None, torch.float32):
+                raise ValueError("the fused evaluate is fp32")
+            a, P = self.factors(state.float())
+            hi, ent, ctx, lo = _CommEvaluate.apply(batch, tgt.to(torch.uint8).contiguous(), visb.to(torch.uint8).contiguous(), a, P,
+                                                   self.dev_type_head.weight, self.dev_type_head.bias)
+            logp = hi.double() + lo.detach().double()
+            dt = torch.float32
+            exp_logits = clean(self._lin(self.exp_head, ctx, dt))
+            app_logits = clean(self._lin(self.app_head, ctx, dt)) if self.app_head is not None else None
+            value = clean(self._lin(self.v_head[2], torch.relu(self._lin(self.v_head[0], ctx, dt)), dt).squeeze(-1))
+        else:
+            out = self.forward(state, dtype=dtype)
+            lp = torch.log_softmax(out["per_dev_type_logits"], dim=-1)                      # [B, D, K]
+            m = visb.to(lp.dtype)
+            logp = (lp.gather(-1, tgt[:, :, None])[:, :, 0] * m).sum(dim=1, dtype=torch.float64)
+            ent = (-(lp.exp() * lp).sum(dim=-1) * m).sum(dim=1)
+            exp_logits, app_logits, value = out["exp_logits"], out["app_logits"], out["value"]
+        for logits, pick in ((exp_logits, exp), (app_logits, app)):
+            if logits is not None and logits.shape[-1] > 0:
+                lp = torch.log_softmax(logits, dim=-1)
+                logp = logp + lp.gather(-1, pick.long()[:, None])[:, 0].double()
+                ent = ent - (lp.exp() * lp).sum(dim=-1)
+        return logp, ent, value
 
     def packed(self, batch=None):
         """What cygym_comm_actor_decode reads, as a dict (BatchedCyberDefenseEnv.comm_actor_decode): the table tok_dev, the packed

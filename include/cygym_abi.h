@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CYGYM_ABI_VERSION 6
+#define CYGYM_ABI_VERSION 7
 
 #define CYGYM_OK            0
 #define CYGYM_EINVAL       -1  /* bad argument / shape                       */
@@ -191,7 +191,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor; -1 for anything else): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval; -1 for anything else, 13 included: that index stays unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -524,10 +524,71 @@ typedef struct cygym_comm_actor {
  * Limits (CYGYM_EUNSUPPORTED beyond): H a multiple of 16 in 16 .. 128; K, E, A <= 32; any M of the handle whose per-row buffers fit in
  * LDS (every M <= 2048 does).  CYGYM_EINVAL (the argument check the decodes share): NULL mandatory pointers, K < 1, E < 1, A < 0,
  * tok_stride < H, a role other than 1 / 2, a packed matrix or tok_dev off 16-byte alignment.  CYGYM_ENOTBOUND without cygym_bind.
- * Out of scope: USE_GAT = True (the attention layers over masked_adjacency), populations of nets in one launch, the PPO update, and
- * building the observation on chip (tok_base comes from the caller). */
+ * Out of scope: USE_GAT = True (the attention layers over masked_adjacency), populations of nets in one launch, and building the
+ * observation on chip (tok_base comes from the caller).  The PPO update evaluates stored decisions with cygym_comm_actor_evaluate below. */
 int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst,
                             void* stream);
+
+/* The per-device part of the PPO update of those agents (IPPO.py:711-739: the log-probability and the entropy of a STORED decision
+ * under the current weights) and its backward, for n rows (a flattened rollout: no env, no flag plane -- the visibility mask is an
+ * input, the rows come from past states).  The factorised inputs are those of cygym_comm_actor: a = tok_base, P = tok_dev,
+ * dev_type_head packed the same way (per call: the weights change every step) and, for the backward, as plain rows too.  All fp32,
+ * DEVICE pointers.  The handle is used for its device, the stream and the error text only (no cygym_bind needed); M comes from the
+ * struct. */
+typedef struct cygym_comm_eval {
+  const float* tok_base;      /* [n][tok_stride] a of row b                                                                           */
+  const float* tok_dev;       /* [M][H] the table P, 16-byte aligned                                                                  */
+  const float* w_type;        /* dev_type_head.weight [K][H] packed as in cygym_comm_actor, 16-byte aligned                           */
+  const float* w_type_rows;   /* the same matrix as it lies, [K][H] (backward only)                                                   */
+  const float* b_type;        /* [K]                                                                                                  */
+  const uint8_t* types;       /* [n][M] the stored action type per device (clamped to 0 .. K-1; not read where vis is 0)              */
+  const uint8_t* vis;         /* [n][M] the stored visibility mask, non-zero = visible                                                */
+  float* logp_dev;            /* forward out [n]                                                                                      */
+  float* logp_lo;             /* forward out, optional [n]: what logp_dev's rounding dropped -- logp_dev + logp_lo in wider arithmetic is
+                                 the compensated sum (one unit in the last place of a sum of tens of nats is that much relative error
+                                 on the PPO ratio exp(logp - logp_old) and on every policy gradient)                                  */
+  float* ent_dev;             /* forward out [n]                                                                                      */
+  float* ctx;                 /* forward out [n][H]                                                                                   */
+  float* logits_out;          /* forward out, optional [n][M][K]: the clean type logits of EVERY device (tests)                       */
+  const float* g_logp;        /* backward in [n]: gradient of the loss with respect to logp_dev                                       */
+  const float* g_ent;         /* backward in [n]                                                                                      */
+  const float* g_ctx;         /* backward in [n][H]                                                                                   */
+  float* grad_tok_base;       /* backward out [n][H]                                                                                  */
+  float* grad_tok_dev;        /* backward out [M][H]                                                                                  */
+  float* grad_w_type;         /* backward out [K][H]                                                                                  */
+  float* grad_b_type;         /* backward out [K]                                                                                     */
+  float* partials;            /* backward workspace: n_partials * (M H + K H + K) floats, n_partials >= ceil(n / 16); it need not be
+                                 cleared, and holds [ceil(n / 16)][M][H] | [..][K][H] | [..][K] afterwards                            */
+  int32_t n, M, H, K;         /* rows, devices, hidden width, action types                                                            */
+  int32_t tok_stride;         /* floats per row of tok_base, >= H                                                                     */
+  int32_t n_partials;         /* capacity of `partials` in workgroups                                                                 */
+} cygym_comm_eval;
+
+/* Forward, ONE launch; a workgroup owns 16 rows.  Per row b, with x[d] = relu(a + P[d]) (x < 0 ? 0 : x) for ALL M devices:
+ *   ctx[h]   = (sum over d of x[d][h]) / M: wave w of 16 adds the devices w, w + 16, ... ascending, the 16 sums are added in ascending
+ *              wave order, then ONE division by M (unmasked, as in the decode; the order differs from the decode's single chain)
+ *   z[d][k]  = nan_to_num(b_type[k] + W[k] . x[d]): the decode's matrix-core chain (v_mfma_f32_16x16x4_f32, h in the order
+ *              g = 0 .. H/16-1, i = 0 .. 3, j = 0 .. 3 with h = 16 g + 4 j + i, bias last), NaN and +-inf to 0
+ *   lp[d]    = z[d] - (m + log(sum_k exp(z[d][k] - m))), m = max_k z[d][k];  p[d][k] = exp(z[d][k] - m) / sum;  sums and max over k as
+ *              a rotation all-reduce over 16 lanes (types 16 .. 31 are added lane-locally first); Hent[d] = -sum_k p lp (0 log 0 = 0)
+ *   t_d      = vis ? min(types, K - 1) : 0
+ *   logp_dev = sum over visible d of lp[d][t_d];  ent_dev = sum over visible d of Hent[d] -- per wave over its devices ascending,
+ *              then over the waves ascending; logp_dev as a compensated (two-sum) sum whose low part goes to logp_lo.
+ * Backward, TWO launches (the second adds the workgroups' partials).  It recomputes x, z, p, lp, Hent as above and forms
+ *   dz[d][k]      = vis fin(z) ( g_logp (1[k = t_d] - p[k]) - g_ent p[k] (lp[k] + Hent[d]) ),  fin = 0 where nan_to_num replaced the
+ *                   raw logit (torch's derivative of nan_to_num)
+ *   dx[d]         = W^T dz[d] (matrix cores, k ascending in steps of 4) + g_ctx / M;   dpre[d] = dx[d] where a + P[d] > 0, else 0
+ *   grad_tok_base[b] = sum_d dpre;  grad_tok_dev[d] = sum_b dpre;  grad_w_type[k] = sum_(b, d) dz[d][k] x[d];  grad_b_type[k] = sum_(b, d) dz[d][k]
+ * Invisible devices contribute through g_ctx only.  Summation order: over the 16 rows of a workgroup inside the matrix-core chain
+ * (grad_w_type) or a fixed lane order; over devices, group p of NG wave groups (NG = 8 for K <= 16, 4 above) adds the devices p,
+ * p + NG, ... ascending and the groups are added in ascending order; over workgroups (grad_tok_dev, grad_w_type, grad_b_type) the partials are added in ascending order.
+ * No floating-point atomics: the same inputs give the same bits.  Nothing of size n M H or n M K is written (logits_out aside).
+ * Limits (CYGYM_EUNSUPPORTED beyond): H a multiple of 16 in 16 .. 128, K <= 32, M <= 2048.  CYGYM_EINVAL: a NULL handle, struct
+ * or mandatory pointer (forward: the inputs but w_type_rows, and the three outputs; backward: every input, the four gradients and
+ * partials), n < 1, K < 1, M < 1, tok_stride < H, n_partials < ceil(n / 16) (backward), tok_dev or w_type off 16-byte alignment; nothing
+ * is written then.  Out of scope: the heads of ctx (exploit, app, value: [n][H] products of the caller) and the optimiser. */
+int cygym_comm_actor_evaluate(cygym_handle* h, const cygym_comm_eval* e, void* stream);
+int cygym_comm_actor_evaluate_backward(cygym_handle* h, const cygym_comm_eval* e, void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`
