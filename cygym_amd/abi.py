@@ -138,6 +138,13 @@ class CommEval(C.Structure):
                 ("n", C.c_int32), ("M", C.c_int32), ("H", C.c_int32), ("K", C.c_int32), ("tok_stride", C.c_int32), ("n_partials", C.c_int32)]
 
 
+class CriticTail(C.Structure):
+    _fields_ = [("h1_pre", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p), ("b3", C.c_void_p), ("q", C.c_void_p),
+                ("grad_q", C.c_void_p), ("grad_h1_pre", C.c_void_p), ("grad_w2", C.c_void_p), ("grad_b2", C.c_void_p), ("grad_w3", C.c_void_p),
+                ("grad_b3", C.c_void_p), ("partials", C.c_void_p),
+                ("n", C.c_int32), ("H1", C.c_int32), ("H2", C.c_int32), ("h_stride", C.c_int32), ("weight_grads", C.c_int32), ("n_partials", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

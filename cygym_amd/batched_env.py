@@ -863,6 +863,66 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_comm_actor_evaluate_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_comm_actor_evaluate_backward")
         return ga, gp, gw, gb
 
+    def _critic_tail(self, h1_pre, w2, b2, w3, b3):
+        """The CriticTail struct of critic_tail / critic_tail_backward from fc1's pre-activations and fc2 / fc3 as torch holds them
+        (fc3.weight [1, H2] or [H2], fc3.bias [1]: a device pointer, no host round trip)."""
+        f32 = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not f32(h1_pre) or h1_pre.dim() != 2 or h1_pre.stride(1) != 1 or int(h1_pre.shape[0]) < 1:
+            raise ValueError("h1_pre must be a [n >= 1, H1] float32 tensor on the batch's device with unit inner stride")
+        n, H1 = int(h1_pre.shape[0]), int(h1_pre.shape[1])
+        if not f32(w2) or w2.dim() != 2 or int(w2.shape[1]) != H1 or not w2.is_contiguous():
+            raise ValueError(f"w2 must be a contiguous float32 [H2, {H1}] tensor on {self.device} (fc2.weight)")
+        H2 = int(w2.shape[0])
+        for name, t, numel in (("b2", b2, H2), ("w3", w3, H2), ("b3", b3, 1)):
+            if not f32(t) or int(t.numel()) != numel or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {numel} values on {self.device}")
+        e = abi.CriticTail()
+        e.h1_pre, e.w2, e.b2, e.w3, e.b3 = (t.data_ptr() for t in (h1_pre, w2, b2, w3, b3))
+        e.n, e.H1, e.H2, e.h_stride = n, H1, H2, int(h1_pre.stride(0)) if n > 1 else H1
+        return e, (n, H1, H2)
+
+    def critic_tail(self, h1_pre, w2, b2, w3, b3, out=None, h_stride=None):
+        """The tail of the DDPG critic for n rows in ONE launch (cygym_critic_tail; include/cygym_abi.h states the arithmetic):
+        q [n] = fc3(relu(fc2(relu(h1_pre)))) from fc1's pre-activations h1_pre [n, H1] (float32, unit inner stride, any row stride)
+        and fc2.weight [H2, H1], fc2.bias [H2], fc3.weight [1, H2], fc3.bias [1] as torch holds them -- no pack step.  `out`: an
+        optional [n] tensor to write into; h_stride: the row stride to hand the library instead of the tensor's (tests of the
+        argument check).  Limits: H1, H2 multiples of 16 in 16..128 (CYGYM_EUNSUPPORTED)."""
+        e, (n, H1, H2) = self._critic_tail(h1_pre, w2, b2, w3, b3)
+        if h_stride is not None:
+            e.h_stride = int(h_stride)
+        q, = self._eval_out(None if out is None else (out,), ((n,),), "q")
+        e.q = q.data_ptr()
+        _lib.check(self.lib.cygym_critic_tail(self._h, C.byref(e), self._stream()), self._h, "cygym_critic_tail")
+        return q
+
+    def critic_tail_backward(self, h1_pre, w2, b2, w3, b3, grad_q, weight_grads: bool = True, out=None, h_stride=None):
+        """The backward of critic_tail (cygym_critic_tail_backward: one launch, plus the reduction of the workgroups' partials
+        with weight_grads): h1 and h2 are recomputed on chip from h1_pre.  Returns (grad_h1_pre [n, H1], grad_w2 [H2, H1], grad_b2
+        [H2], grad_w3 [H2], grad_b3 [1]); without weight_grads only grad_h1_pre is computed (the same bits) and the other four are
+        None -- or, when `out` gives all five, left untouched.  No atomics: the same inputs give the same bits.  The workspace is
+        min(ceil(n / 16), 256) (H2 H1 + 2 H2 + 1) floats."""
+        e, (n, H1, H2) = self._critic_tail(h1_pre, w2, b2, w3, b3)
+        if h_stride is not None:
+            e.h_stride = int(h_stride)
+        if grad_q.dtype != torch.float32 or grad_q.device != self.device or int(grad_q.numel()) != n:
+            raise ValueError(f"grad_q must be a float32 tensor of {n} values on {self.device}")
+        gq = grad_q.reshape(n).contiguous()
+        e.grad_q = gq.data_ptr()
+        shapes = ((n, H1), (H2, H1), (H2,), (H2,), (1,))
+        if weight_grads or out is not None:
+            gh, gw2, gb2, gw3, gb3 = self._eval_out(out, shapes, "grad_h1_pre, grad_w2, grad_b2, grad_w3, grad_b3")
+        else:
+            gh, = self._eval_out(None, shapes[:1], "grad_h1_pre")
+            gw2 = gb2 = gw3 = gb3 = None
+        e.grad_h1_pre = gh.data_ptr()
+        if weight_grads:
+            nwg = min((n + 15) // 16, 256)
+            part = torch.empty((nwg * (H2 * H1 + 2 * H2 + 1),), dtype=torch.float32, device=self.device)
+            e.grad_w2, e.grad_b2, e.grad_w3, e.grad_b3 = gw2.data_ptr(), gb2.data_ptr(), gw3.data_ptr(), gb3.data_ptr()
+            e.partials, e.n_partials, e.weight_grads = part.data_ptr(), nwg, 1
+        _lib.check(self.lib.cygym_critic_tail_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_critic_tail_backward")
+        return gh, gw2, gb2, gw3, gb3
+
     def take_status(self) -> int:
         """Read and clear the batch's status word: the OR of CG_E_TOPO_OVF | CG_E_BUSY_SAT | CG_E_DET_PENDING |
         CG_E_UNPINNED over the envs ticked since the last call (one 4-byte device-to-host copy; synchronises)."""

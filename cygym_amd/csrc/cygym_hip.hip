@@ -80,6 +80,16 @@ extern template __global__ void comm_eval_bwd_kernel<1>(cygym_comm_eval);
 extern template __global__ void comm_eval_bwd_kernel<2>(cygym_comm_eval);
 }  // namespace cygym_k
 
+// the critic-tail kernels of the DDPG update live in their own unit (cg_inst_ddpg.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void critic_tail_fwd_kernel<0>(cygym_critic_tail_desc);
+extern template __global__ void critic_tail_fwd_kernel<8>(cygym_critic_tail_desc);
+extern template __global__ void critic_tail_bwd_kernel<false, 0>(cygym_critic_tail_desc);
+extern template __global__ void critic_tail_bwd_kernel<false, 8>(cygym_critic_tail_desc);
+extern template __global__ void critic_tail_bwd_kernel<true, 0>(cygym_critic_tail_desc);
+extern template __global__ void critic_tail_bwd_kernel<true, 8>(cygym_critic_tail_desc);
+}  // namespace cygym_k
+
 // =====================================================================
 // C ABI
 // =====================================================================
@@ -213,6 +223,7 @@ int cygym_sizeof(int32_t which) {
     case 11: return (int)sizeof(cygym_critic);
     case 12: return (int)sizeof(cygym_comm_actor);
     case 14: return (int)sizeof(cygym_comm_eval);   // (13 stays unassigned: -1)
+    case 16: return (int)sizeof(cygym_critic_tail_desc);   // (15 stays unassigned too: earlier bindings probe it for -1)
     default: return -1;
   }
 }
@@ -888,6 +899,58 @@ int cygym_comm_actor_evaluate_backward(cygym_handle* h, const cygym_comm_eval* e
   const size_t total = (size_t)e->M * e->H + (size_t)e->K * e->H + (size_t)e->K;
   hipLaunchKernelGGL(comm_eval_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *e, nwg);
   HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+// What the two critic-tail calls check alike: handle, pointers, layout (CYGYM_EINVAL), then the implemented range (CYGYM_EUNSUPPORTED).
+static int check_tail(cygym_handle* h, const cygym_critic_tail_desc* e, const char* who, bool own_ptrs) {
+  if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
+  if (!e || !own_ptrs || !e->h1_pre || !e->w2 || !e->b2 || !e->w3 || !e->b3) return fail(h, CYGYM_EINVAL, "%s: null pointer", who);
+  if (e->n < 1 || e->H1 < 1 || e->H2 < 1 || e->h_stride < e->H1) return fail(h, CYGYM_EINVAL, "%s: bad layout (n, H1, H2 >= 1, h_stride >= H1)", who);
+  if (e->H1 < 16 || e->H1 > CT_MAX_H || (e->H1 & 15) || e->H2 < 16 || e->H2 > CT_MAX_H || (e->H2 & 15))
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: critic widths H1, H2 must be multiples of 16 in 16 .. 128", who);
+  return CYGYM_OK;
+}
+
+int cygym_critic_tail(cygym_handle* h, const cygym_critic_tail_desc* e, void* stream) {
+  const char* const who = "cygym_critic_tail";
+  if (const int rc = check_tail(h, e, who, e && e->q)) return rc;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const size_t lds = (size_t)ct_plan(e->H1, e->H2, false).total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the workgroup's buffers do not fit in LDS", who);
+  const void* k = e->H1 == 128 ? (const void*)critic_tail_fwd_kernel<8> : (const void*)critic_tail_fwd_kernel<0>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const int ntiles = (e->n + CT_ROWS - 1) / CT_ROWS;
+  void* args[] = {(void*)e};
+  HIPCHK(h, hipLaunchKernel(k, dim3(ntiles < CT_MAX_WG ? ntiles : CT_MAX_WG), dim3(CT_THREADS), args, lds, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+int cygym_critic_tail_backward(cygym_handle* h, const cygym_critic_tail_desc* e, void* stream) {
+  const char* const who = "cygym_critic_tail_backward";
+  const bool wg = e && e->weight_grads != 0;
+  if (const int rc = check_tail(h, e, who, e && e->grad_q && e->grad_h1_pre &&
+                                               (!wg || (e->grad_w2 && e->grad_b2 && e->grad_w3 && e->grad_b3 && e->partials)))) return rc;
+  if (wg && e->n_partials < 1) return fail(h, CYGYM_EINVAL, "%s: n_partials must be at least 1", who);
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const size_t lds = (size_t)ct_plan(e->H1, e->H2, true).total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the workgroup's buffers do not fit in LDS", who);
+  const bool wide = e->H1 == 128;
+  const void* k = wg ? (wide ? (const void*)critic_tail_bwd_kernel<true, 8> : (const void*)critic_tail_bwd_kernel<true, 0>)
+                     : (wide ? (const void*)critic_tail_bwd_kernel<false, 8> : (const void*)critic_tail_bwd_kernel<false, 0>);
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  int nwg = (e->n + CT_ROWS - 1) / CT_ROWS;
+  if (nwg > CT_MAX_WG) nwg = CT_MAX_WG;
+  if (wg && nwg > e->n_partials) nwg = e->n_partials;
+  void* args[] = {(void*)e};
+  HIPCHK(h, hipLaunchKernel(k, dim3(nwg), dim3(CT_THREADS), args, lds, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  if (wg) {
+    const size_t total = (size_t)e->H2 * e->H1 + 2 * (size_t)e->H2 + 1;
+    hipLaunchKernelGGL(critic_tail_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *e, nwg);
+    HIPCHK(h, hipGetLastError());
+  }
   return CYGYM_OK;
 }
 

@@ -12,7 +12,11 @@ at once, all tensors on the device:
 
 Here the actor runs once for all envs, the noise is one batched draw, decode_action + the scatter into the action tensors is
 ONE launch (cygym_decode_actions: the action vectors have to exist in HBM anyway -- the replay buffer stores them) and the
-tick writes the learner's next view itself.  `train_ddpg` (the update on the replay buffer) is the caller's.
+tick writes the learner's next view itself.
+
+The learning half is here too: `ReplayRing` is the reference's ReplayBuffer (:341-354) as preallocated device tensors, `train_ddpg`
+is the update on it (:391-450) with the critic's tail and its backward as the library's launches (cygym_critic_tail), and
+`best_response` is the loop itself: collect one decision for every env, push, update (:1334-1460).
 
 In the reference's DEFAULT mode (`--BR_type Cord_asc`) decode_action does not read `vec`: it is greedy_device_coord_ascent on the
 critic (:1375-1380 -> :952-968), in training mode with noise on Q (:2177-2178), and the replay buffer stores
@@ -25,6 +29,7 @@ from __future__ import annotations
 from dataclasses import dataclass
 
 import torch
+from torch import nn
 
 from . import host_logic as HL
 from . import spec as S
@@ -119,3 +124,167 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
         t += 1
     st = {k: torch.stack(v) for k, v in rec.items()}
     return Transitions(noise_std=sigma, **st)
+
+
+class ReplayRing:
+    """The reference's ReplayBuffer (do_agent.py:341-354: deque(maxlen=capacity) of (state, action, reward, next_state, done)) as
+    preallocated tensors on one device: a push overwrites the oldest rows, exactly as the deque drops them.  Rewards are stored
+    as float32 (the update's torch.tensor(rewards, dtype=float32), :413), `done` as float32 0 / 1 (:412).  Neither push nor sample
+    synchronises with the host: the write position and the fill are host integers (every push has a known size)."""
+
+    def __init__(self, capacity: int, state_dim: int, action_dim: int, device):
+        self.capacity, self.device = int(capacity), torch.device(device)
+        if self.capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)  # noqa: E731
+        self.state, self.action, self.next_state = z(self.capacity, int(state_dim)), z(self.capacity, int(action_dim)), z(self.capacity, int(state_dim))
+        self.reward, self.done = z(self.capacity), z(self.capacity)
+        self._head, self._size = 0, 0      # the row the next push writes; rows held
+
+    def __len__(self):
+        return self._size
+
+    def push(self, state, action_vec=None, reward=None, next_state=None, done=None):
+        """Append n rows ([n, ...] tensors), or a whole `Transitions` flattened over [T, N] in (t, n) order; with n > capacity only
+        the last `capacity` rows survive.  Index arithmetic plus index_copy_."""
+        if isinstance(state, Transitions):
+            tr = state
+            n = tr.done.numel()
+            state, action_vec, next_state = (t.reshape(n, t.shape[-1]) for t in (tr.state, tr.action_vec, tr.next_state))
+            reward, done = tr.reward.reshape(n), tr.done.reshape(n)
+        n = int(state.shape[0])
+        rows = [state, action_vec, reward.reshape(n), next_state, done.reshape(n)]
+        skip = max(0, n - self.capacity)     # the deque would have dropped these again
+        keep = n - skip
+        idx = (torch.arange(keep, device=self.device) + (self._head + skip)) % self.capacity
+        for dst, src in zip((self.state, self.action, self.reward, self.next_state, self.done), rows):
+            dst.index_copy_(0, idx, src[skip:].to(device=self.device, dtype=torch.float32))
+        self._head = (self._head + n) % self.capacity
+        self._size = min(self.capacity, self._size + n)
+
+    def sample_at(self, indices):
+        """(state, action, reward [B, 1], next_state, done [B, 1]) of the given logical rows: 0 is the oldest row held."""
+        i = (torch.as_tensor(indices, device=self.device).long() + (self._head - self._size)) % self.capacity
+        return self.state[i], self.action[i], self.reward[i][:, None], self.next_state[i], self.done[i][:, None]
+
+    def sample(self, batch_size: int, generator=None):
+        """`batch_size` distinct rows, uniformly (random.sample's distribution, :350) from torch's generator on the ring's device: the
+        head of a random permutation of the rows held.  ValueError when fewer are held."""
+        if self._size < int(batch_size):
+            raise ValueError(f"the ring holds {self._size} rows, fewer than the {int(batch_size)} asked for")
+        return self.sample_at(torch.randperm(self._size, generator=generator, device=self.device)[: int(batch_size)])
+
+
+@dataclass
+class DDPGAgent:
+    """What DoubleOracle.init_ddpg returns (do_agent.py:1032-1040)."""
+    actor: nn.Module
+    critic: nn.Module
+    target_actor: nn.Module
+    target_critic: nn.Module
+    actor_optimizer: torch.optim.Optimizer
+    critic_optimizer: torch.optim.Optimizer
+    replay: ReplayRing
+
+
+def init_ddpg(state_dim: int, n_types: int, M: int, n_exploits: int, n_apps: int, *, seed: int, device, capacity: int = 100_000) -> DDPGAgent:
+    """DoubleOracle.init_ddpg (do_agent.py:1016-1040): the reference's actor and critic over action vectors of n_types + M +
+    n_exploits + n_apps entries, targets loaded from the nets, Adam at 1e-3 (actor) and 1e-2 (critic), a replay buffer of 100000."""
+    from .policies import reference_actor, reference_critic
+    action_dim = int(n_types) + int(M) + int(n_exploits) + int(n_apps)
+    actor, target_actor = (reference_actor(state_dim, action_dim, seed=seed, device=device) for _ in range(2))
+    critic, target_critic = (reference_critic(state_dim, action_dim, seed=seed, device=device) for _ in range(2))
+    target_actor.load_state_dict(actor.state_dict())
+    target_critic.load_state_dict(critic.state_dict())
+    return DDPGAgent(actor, critic, target_actor, target_critic, torch.optim.Adam(actor.parameters(), lr=1e-3),
+                     torch.optim.Adam(critic.parameters(), lr=1e-2), ReplayRing(capacity, state_dim, action_dim, device))
+
+
+def train_ddpg(agent: DDPGAgent, *, batch=None, batch_size: int = 512, gamma: float = 0.99, tau: float = 1e-2, max_grad_norm: float = 0.5,
+               generator=None, fused=None, sample=None):
+    """One DDPG update on the replay ring: the reference's train_ddpg (do_agent.py:391-450), line for line.
+        fewer than batch_size rows held: return None                                                  (:404-405)
+        s, a, r, s', done = replay.sample(batch_size);  r = clamp(r, -10, +10)                        (:407-414)
+        no grad: a' = target_actor(s');  td = r + gamma (1 - done) target_critic(s', a')             (:423-428)
+        loss_critic = SmoothL1Loss()(critic(s, a), td); zero_grad; backward; clip_grad_norm_(0.5); critic_optimizer.step()   (:430-435)
+        loss_actor = -critic(s, actor(s)).mean() with the UPDATED critic; clip; actor_optimizer.step()                       (:437-444)
+        tgt <- tau src + (1 - tau) tgt for both targets, tau = 1e-2                                   (:446-450)
+    All three critic evaluations go through Critic.evaluate(batch=batch, fused=fused): with a batch (a BatchedCyberDefenseEnv on
+    the nets' device) the tail of the critic and its backward are the library's launches -- three forwards and two backwards per
+    update.  `sample`: the five tensors (state, action, reward, next_state, done) to use instead of a draw from the ring (tests,
+    fixtures).  Returns {"critic_loss", "actor_loss", "critic_grad_norm", "actor_grad_norm"} as 0-dim tensors, the norms as taken
+    before clipping.  No host synchronisation anywhere.
+    One difference: the actor's step takes the gradients of the actor's parameters only (the critic is frozen while loss_actor is
+    formed, so the tail's backward skips its weight gradients): after the call critic.*.grad holds the CRITIC loss's gradients,
+    where the reference leaves the actor loss's stale ones there -- nothing reads them before the next zero_grad (:432)."""
+    if sample is None:
+        if len(agent.replay) < int(batch_size):
+            return None
+        sample = agent.replay.sample(int(batch_size), generator)
+    s, a, r, s2, d = sample
+    B = int(s.shape[0])
+    r, d = r.reshape(B, 1).float().clamp(-10.0, +10.0), d.reshape(B, 1).float()
+    actor, critic = agent.actor, agent.critic
+    q_of = lambda net, st, ac: net.evaluate(st, ac, batch=batch, fused=fused)  # noqa: E731
+    with torch.no_grad():
+        td = r + gamma * (1 - d) * q_of(agent.target_critic, s2, agent.target_actor(s2))
+    loss_critic = nn.SmoothL1Loss()(q_of(critic, s, a), td)
+    agent.critic_optimizer.zero_grad()
+    loss_critic.backward()
+    critic_norm = nn.utils.clip_grad_norm_(critic.parameters(), max_grad_norm)
+    agent.critic_optimizer.step()
+
+    agent.actor_optimizer.zero_grad()
+    cp, ap = list(critic.parameters()), list(actor.parameters())
+    was = [p.requires_grad for p in cp]
+    for p in cp:
+        p.requires_grad_(False)
+    try:
+        loss_actor = -q_of(critic, s, actor(s)).mean()
+        grads = torch.autograd.grad(loss_actor, ap)
+    finally:
+        for p, w in zip(cp, was):
+            p.requires_grad_(w)
+    for p, g in zip(ap, grads):
+        p.grad = g
+    actor_norm = nn.utils.clip_grad_norm_(ap, max_grad_norm)
+    agent.actor_optimizer.step()
+
+    with torch.no_grad():      # tau * src + (1 - tau) * tgt: each product rounded, then the sum, as the reference's expression
+        for tgt, src in ((agent.target_actor, actor), (agent.target_critic, critic)):
+            tp, sp = list(tgt.parameters()), list(src.parameters())
+            torch._foreach_mul_(tp, 1 - tau)
+            torch._foreach_add_(tp, torch._foreach_mul(sp, tau))
+    return {"critic_loss": loss_critic.detach(), "actor_loss": loss_actor.detach(), "critic_grad_norm": critic_norm, "actor_grad_norm": actor_norm}
+
+
+def best_response(batch, role: str, agent: DDPGAgent, opponent, n_decisions: int, n_types: int, n_exploits: int | None = None, n_apps: int = 0, *,
+                  type_map=None, decoder=None, updates_per_decision: int = 1, noise_std: float = 1.0, sigma_min: float = 1e-5,
+                  batch_size: int = 512, gamma: float = 0.99, tau: float = 1e-2, generator=None, fused=None, t0: int = 0):
+    """The training loop of DoubleOracle.ddpg_best_response (do_agent.py:1334-1460) for every env of a batch: per decision
+    collect(n_decisions=1) from the loop's tick counter -- the opponent's tick first where the parity of t is theirs (:1335) --,
+    push the N transitions (:1422 / :1424-1425), then `updates_per_decision` calls of train_ddpg (:1427-1431).  The exploration
+    noise decays by decay_rate = (sigma_min / noise_std) ** (1 / n_decisions) per decision (:1322, :1372).  With a `decoder` (a
+    CoordAscentPolicy over agent.critic: the reference's Cord_asc mode) every decision decodes through the LIVE critic: the
+    policy's pack is keyed on the parameters' versions and is redone after each update.
+    Returns (the summed raw reward per env [N] float64, the last update's dict -- None while the ring held fewer than batch_size
+    rows).  Out of scope: the meta-controller observer, dynamic_neighbor_search, exploit_override, the time budget, and leaving
+    the loop at the first done (a batch goes on, as collect does)."""
+    if decoder is not None and decoder.critic is not agent.critic:
+        raise ValueError("decoder: a CoordAscentPolicy over agent.critic (the critic the updates train)")
+    n_decisions = int(n_decisions)
+    decay_rate = (sigma_min / noise_std) ** (1.0 / n_decisions) if noise_std > 0.0 and n_decisions > 0 else 1.0
+    total = torch.zeros((batch.N,), dtype=torch.float64, device=batch.device)
+    t, sigma, last = int(t0), float(noise_std), None
+    ours = 0 if role == HL.DEFENDER else 1
+    for _ in range(n_decisions):
+        tr = collect(batch, role, agent.actor, opponent, 1, n_types, n_exploits, n_apps, type_map=type_map, noise_std=sigma, sigma_min=sigma_min,
+                     decay_rate=decay_rate, generator=generator, t0=t, decoder=decoder)
+        t += 1 if t % 2 == ours else 2
+        sigma = tr.noise_std
+        agent.replay.push(tr)
+        total += tr.raw_reward.sum(dim=0)
+        for _ in range(int(updates_per_decision)):
+            out = train_ddpg(agent, batch=batch, batch_size=batch_size, gamma=gamma, tau=tau, generator=generator, fused=fused)
+            last = out if out is not None else last
+    return total, last

@@ -260,9 +260,28 @@ class ActorPolicyGroup:
                                 epsilon=self.epsilon, tanh=tanh, n_groups=S)
 
 
+class _AddmmRelu(torch.autograd.Function):
+    """relu(bias + x @ weight^T) as torch._addmm_activation (which has no derivative of its own) with the backward written out: the
+    same forward bits with and without autograd, so that a FusedMLP can be trained (ddpg_rollout.train_ddpg)."""
+
+    @staticmethod
+    def forward(ctx, bias, x, weight):
+        y = torch._addmm_activation(bias, x, weight.t())
+        ctx.save_for_backward(x, weight, y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, weight, y = ctx.saved_tensors
+        gp = g * (y > 0)
+        return gp.sum(dim=0), gp @ weight, gp.t() @ x
+
+
 class FusedMLP(nn.Sequential):
     """nn.Sequential of Linear / ReLU / Tanh whose Linear + ReLU pairs run as ONE GEMM with a ReLU epilogue
-    (torch._addmm_activation) on 2-D inputs -- one launch less per hidden layer of a closed-loop tick."""
+    (torch._addmm_activation) on 2-D inputs -- one launch less per hidden layer of a closed-loop tick.  Differentiable: under
+    autograd the pair goes through _AddmmRelu."""
 
     def forward(self, x):
         mods = list(self)
@@ -271,7 +290,10 @@ class FusedMLP(nn.Sequential):
             m = mods[i]
             if isinstance(m, nn.Linear) and x.dim() == 2:
                 if i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU) and hasattr(torch, "_addmm_activation"):
-                    x = torch._addmm_activation(m.bias, x, m.weight.t())
+                    if torch.is_grad_enabled() and (x.requires_grad or m.weight.requires_grad or m.bias.requires_grad):
+                        x = _AddmmRelu.apply(m.bias, x, m.weight)
+                    else:
+                        x = torch._addmm_activation(m.bias, x, m.weight.t())
                     i += 2
                     continue
                 x = torch.addmm(m.bias, x, m.weight.t())
@@ -317,6 +339,38 @@ class Critic(nn.Module):
     def forward(self, state, action):
         x = torch.relu(self.fc1(torch.cat([state, action], 1)))
         return self.fc3(torch.relu(self.fc2(x)))
+
+    def evaluate(self, state, action, *, batch=None, fused=None, dtype=None):
+        """Q(s, a) [n, 1] as train_ddpg evaluates it (do_agent.py:427, :430, :441), differentiable with respect to the parameters, the
+        state and the action: h1_pre = addmm(b1, state, W1[:, :W]^T) + action @ W1[:, W:]^T -- the split of fc1 CoordAscentPolicy
+        decodes through, no cat -- then the tail fc3(relu(fc2(relu(h1_pre)))).
+        fused (the default when `batch`, a BatchedCyberDefenseEnv on the parameters' device, is given, the widths are multiples of
+        16 in 16..128 and the tensors are float32 there): the tail and its backward as the library's launches (cygym_critic_tail /
+        _backward behind one autograd.Function; nothing of size [n, H2] is kept, the weight gradients are skipped when autograd
+        does not ask for them).  fused=False: the tail with torch ops in `dtype` (torch.float64: the restatement the fused path
+        is tested against), from the same fp32 parameters."""
+        W = int(state.shape[1])
+        if W + int(action.shape[1]) != self.fc1.in_features:
+            raise ValueError(f"state and action are {W} + {int(action.shape[1])} wide, fc1 takes {self.fc1.in_features}")
+        H1, H2 = self.fc1.out_features, self.fc2.out_features
+        fits = H1 % 16 == 0 and H2 % 16 == 0 and 16 <= H1 <= 128 and 16 <= H2 <= 128
+        here = batch is not None and all(t.dtype == torch.float32 and t.device == batch.device for t in (state, action, self.fc1.weight))
+        if fused is None:
+            fused = bool(here and fits and dtype in (None, torch.float32))
+        if fused:
+            if batch is None:
+                raise ValueError("the fused critic tail runs through a BatchedCyberDefenseEnv: pass batch=")
+            if dtype not in (None, torch.float32) or not here:
+                raise ValueError("the fused critic tail is fp32, on the batch's device")
+            if not fits:
+                raise ValueError("the fused critic tail takes widths H1, H2 that are multiples of 16 in 16..128")
+        dt = (state.dtype if dtype is None else dtype) if not fused else torch.float32
+        w1, b1 = self.fc1.weight.to(dt), self.fc1.bias.to(dt)
+        h1_pre = torch.addmm(b1, state.to(dt), w1[:, :W].t()) + action.to(dt) @ w1[:, W:].t()
+        if fused:
+            return _CriticTail.apply(batch, h1_pre, self.fc2.weight, self.fc2.bias, self.fc3.weight, self.fc3.bias)[:, None]
+        h2 = torch.relu(torch.addmm(self.fc2.bias.to(dt), torch.relu(h1_pre), self.fc2.weight.to(dt).t()))
+        return torch.addmm(self.fc3.bias.to(dt), h2, self.fc3.weight.to(dt).t())
 
 
 def reference_critic(state_dim: int, action_dim: int, seed: int = 0, device="cpu", hidden=(128, 128)) -> nn.Module:
@@ -483,6 +537,29 @@ class CoordAscentPolicy:
         tm = self._map(obs.device)
         at = at.to(torch.int32) if tm is None else tm[at]
         return {"atype": at, "exploit": ex.to(torch.int32), "dev_mask": on, "app": torch.zeros_like(at)}
+
+
+class _CriticTail(torch.autograd.Function):
+    """cygym_critic_tail and its backward as one differentiable op: (h1_pre [n, H1], fc2.weight, fc2.bias, fc3.weight, fc3.bias) -> q [n].
+    Nothing but the inputs is kept for backward: the kernel recomputes h1 and h2.  The weight gradients are computed only when
+    autograd asks for one of them (needs_input_grad): the actor's step of train_ddpg differentiates through the critic, not into it."""
+
+    @staticmethod
+    def forward(ctx, batch, h1_pre, w2, b2, w3, b3):
+        ins = tuple(t.detach().contiguous() for t in (h1_pre, w2, b2, w3, b3))
+        ctx.batch, ctx.w3_shape = batch, tuple(w3.shape)
+        ctx.save_for_backward(*ins)
+        return batch.critic_tail(*ins)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_q):
+        h, w2, b2, w3, b3 = ctx.saved_tensors
+        wg = any(ctx.needs_input_grad[2:])
+        gh, gw2, gb2, gw3, gb3 = ctx.batch.critic_tail_backward(h, w2, b2, w3, b3, g_q.float().contiguous(), weight_grads=wg)
+        if not wg:
+            return None, gh, None, None, None, None
+        return None, gh, gw2, gb2, gw3.reshape(ctx.w3_shape), gb3
 
 
 class _CommEvaluate(torch.autograd.Function):

@@ -191,7 +191,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval; -1 for anything else, 13 included: that index stays unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc; -1 for anything else, 13 and 15 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -589,6 +589,53 @@ typedef struct cygym_comm_eval {
  * is written then.  Out of scope: the heads of ctx (exploit, app, value: [n][H] products of the caller) and the optimiser. */
 int cygym_comm_actor_evaluate(cygym_handle* h, const cygym_comm_eval* e, void* stream);
 int cygym_comm_actor_evaluate_backward(cygym_handle* h, const cygym_comm_eval* e, void* stream);
+
+/* The tail of the reference's DDPG critic (do_agent.py:373-388: Q = fc3(relu(fc2(relu(fc1([s, a])))))) for n rows, and its backward:
+ * what train_ddpg (do_agent.py:391-450) evaluates three times (:427 the target, :430 the critic loss, :441 the actor loss) and
+ * differentiates twice (:433, :442) per update.  The input is h1_pre = fc1([s, a]) BEFORE its relu (a product of the caller: fc1 is as
+ * wide as the state), the weights are read AS TORCH HOLDS THEM -- no pack step, they change at every update.  All fp32, DEVICE
+ * pointers, fc3.bias included (one float: no host round trip).  The handle is used for its device, the stream and the error text only
+ * (no cygym_bind needed). */
+typedef struct cygym_critic_tail_desc {
+  const float* h1_pre;        /* [n][h_stride] fc1's output before the relu                                                           */
+  const float* w2;            /* fc2.weight [H2][H1], contiguous                                                                      */
+  const float* b2;            /* fc2.bias [H2]                                                                                        */
+  const float* w3;            /* fc3.weight [H2] (its one row)                                                                        */
+  const float* b3;            /* fc3.bias [1]                                                                                         */
+  float* q;                   /* forward out [n]                                                                                      */
+  const float* grad_q;        /* backward in [n]: gradient of the loss with respect to q                                              */
+  float* grad_h1_pre;         /* backward out [n][H1], contiguous                                                                     */
+  float* grad_w2;             /* backward out [H2][H1]   -- these four and `partials` only when weight_grads != 0                     */
+  float* grad_b2;             /* backward out [H2]                                                                                    */
+  float* grad_w3;             /* backward out [H2]                                                                                    */
+  float* grad_b3;             /* backward out [1]                                                                                     */
+  float* partials;            /* backward workspace: n_partials * (H2 H1 + 2 H2 + 1) floats; it need not be cleared                   */
+  int32_t n, H1, H2;          /* rows, width of fc1 / fc2                                                                             */
+  int32_t h_stride;           /* floats per row of h1_pre, >= H1                                                                      */
+  int32_t weight_grads;       /* backward: 0 = grad_h1_pre only (the actor's step, :441-443: the critic's gradients are not wanted)   */
+  int32_t n_partials;         /* capacity of `partials` in workgroups, >= 1: min(ceil(n / 16), n_partials, 256) workgroups run        */
+} cygym_critic_tail_desc;
+
+/* Forward, ONE launch; a workgroup of 8 waves stages W2 in LDS once and walks 16-row tiles (rows past n are zeros).  Per row b:
+ *   h1[k]     = h1_pre[k] < 0 ? 0 : h1_pre[k]
+ *   h2_pre[j] = matrix-core chain (v_mfma_f32_16x16x4_f32) over k in the order g = 0 .. H1/16-1, i = 0 .. 3, the four k = 16 g + 4 jj + i
+ *               (jj = 0 .. 3) of a step inside the instruction, starting at 0;  h2[j] = relu(h2_pre[j] + b2[j])
+ *   q         = ((sum over the eight column tiles t, ascending, of S_t) + b3),  S_t = the sum of w3[j] h2[j] over the 16 columns of tile t
+ *               as a rotation all-reduce (by 8, 4, 2, 1 lanes)
+ * Backward, ONE launch (TWO with weight_grads: the second adds the workgroups' partials).  It recomputes h1 and h2 as above -- nothing
+ * of size [n][H2] is kept between the calls -- and forms
+ *   g2[b][j]       = grad_q[b] w3[j] where h2_pre + b2 > 0, else 0
+ *   grad_h1_pre[b] = (g2[b] W2) where h1_pre > 0, else exactly 0 (matrix cores, j ascending in steps of 4)
+ *   grad_w2[j][k]  = sum_b g2[b][j] h1[b][k];  grad_b2[j] = sum_b g2[b][j];  grad_w3[j] = sum_b grad_q[b] h2[b][j];  grad_b3 = sum_b grad_q[b]
+ * Summation order: over the 16 rows of a tile inside the matrix-core chain (grad_w2) or a fixed lane order; over the tiles of a
+ * workgroup ascending; over workgroups the partials are added in ascending order.  No floating-point atomics: the same inputs (and
+ * the same n_partials) give the same bits; grad_h1_pre does not depend on weight_grads.
+ * Limits (CYGYM_EUNSUPPORTED beyond): H1 and H2 multiples of 16 in 16 .. 128 (those of cygym_coord_ascent_decode).  CYGYM_EINVAL: a NULL
+ * handle, struct or mandatory pointer (forward: the five inputs and q; backward: the five inputs, grad_q, grad_h1_pre and, with
+ * weight_grads, the four gradients and partials), n < 1, H1 < 1, H2 < 1, h_stride < H1, n_partials < 1 (with weight_grads); nothing is
+ * written then.  Out of scope: fc1 (the caller's addmm, split into its state and action parts without a cat) and the optimiser. */
+int cygym_critic_tail(cygym_handle* h, const cygym_critic_tail_desc* e, void* stream);
+int cygym_critic_tail_backward(cygym_handle* h, const cygym_critic_tail_desc* e, void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`
