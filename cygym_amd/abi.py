@@ -145,6 +145,14 @@ class CriticTail(C.Structure):
                 ("n", C.c_int32), ("H1", C.c_int32), ("H2", C.c_int32), ("h_stride", C.c_int32), ("weight_grads", C.c_int32), ("n_partials", C.c_int32)]
 
 
+class HierNet(C.Structure):
+    _fields_ = [("h0", C.c_void_p), ("w_mask_t", C.c_void_p), ("w_score", C.c_void_p), ("b_score", C.c_void_p), ("w_act2", C.c_void_p),
+                ("b_act2", C.c_void_p), ("w_dev2", C.c_void_p), ("b_dev2", C.c_void_p), ("w_act_head", C.c_void_p), ("b_act_head", C.c_void_p),
+                ("w_dev_head", C.c_void_p), ("b_dev_head", C.c_void_p), ("part_of", C.c_void_p), ("vis_fixed", C.c_void_p),
+                ("score_out", C.c_void_p), ("part_score_out", C.c_void_p), ("part_out", C.c_void_p), ("atype_logits_out", C.c_void_p),
+                ("dev_logits_out", C.c_void_p), ("n_parts", C.c_int32), ("role", C.c_int32), ("H", C.c_int32), ("h0_stride", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

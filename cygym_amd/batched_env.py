@@ -786,6 +786,58 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_comm_actor_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_actor_decode")
         return types, exp_o, app_o, logp, value
 
+    def hier_decode(self, rows, h0: torch.Tensor, pack, role: str = "defender", act=None, vis_fixed=None, type_map=None,
+                    score_out=None, part_score_out=None, part_out=None, atype_logits_out=None, dev_logits_out=None):
+        """HierarchicalBestResponse.execute (hierarchical_br.py:419-494, the HAGS best response) for a batch, fused with the scatter
+        into rows `rows` of `act` (group 0): ONE launch (cygym_hier_decode; include/cygym_abi.h states the decision and the arithmetic).
+          h0         [n, >= 3 H] float32 (unit inner stride): score.fc1(s) | act_body.0(s) | dev_body.0.weight[:, :S] s + bias of source
+                     row r, before the relu (policies.HierarchicalNet.h0: one addmm)
+          pack       policies.HierarchicalNet.packed(part_of): dict with w_mask_t [M, H], the packed w_score / w_act2 / w_dev2 /
+                     w_act_head / w_dev_head (pack_linear), their biases, part_of [M] uint8 (0xFF = in no part), n_parts, H, T
+          vis_fixed  None: every row reads the role's visibility mask off the flag plane of its env; a [M] uint8 / bool tensor: that ONE
+                     mask for every row (what the reference's execute does during payoff evaluation, :130 / :441)
+          outputs    optional, contiguous: score_out [n, M], part_score_out [n, n_parts], atype_logits_out [n, T], dev_logits_out [n, M]
+                     float32, part_out [n] int32 (the chosen part; -1 / -2: the fallbacks)
+        Limits: H a multiple of 16 in 16..256, T <= 32, M <= 2048, 1..255 parts (the library answers CYGYM_EUNSUPPORTED / CYGYM_EINVAL)."""
+        dst = self.actions_struct(act)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
+            raise ValueError("h0 must be a [n, >= 3 H] float32 tensor on the batch's device with unit inner stride")
+        n, H, T, P = int(h0.shape[0]), int(pack["H"]), int(pack["T"]), int(pack["n_parts"])
+        if int(h0.shape[1]) < 3 * H:
+            raise ValueError(f"h0 rows hold {int(h0.shape[1])} floats: fewer than the three {H}-wide blocks")
+        src, _, keep = _action_vectors(self, rows, n, T, 0, 0, type_map, 0.0)
+        Hp = (H + 15) // 16 * 16
+        sizes = {"w_mask_t": self.M * H, "w_score": (self.M + 15) // 16 * 16 * Hp, "b_score": self.M, "w_act2": Hp * Hp, "b_act2": H,
+                 "w_dev2": Hp * Hp, "b_dev2": H, "w_act_head": (T + 15) // 16 * 16 * Hp, "b_act_head": T,
+                 "w_dev_head": (self.M + 15) // 16 * 16 * Hp, "b_dev_head": self.M}
+        net = abi.HierNet()
+        for name, want in sizes.items():
+            t = pack[name]
+            if not ok(t) or not t.is_contiguous() or int(t.numel()) != want:
+                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device} (HierarchicalNet.packed)")
+            setattr(net, name, t.data_ptr())
+        po = pack["part_of"]
+        if po.dtype != torch.uint8 or po.device != self.device or not po.is_contiguous() or int(po.numel()) != self.M:
+            raise ValueError(f"pack['part_of'] must be a contiguous uint8 [{self.M}] tensor on {self.device}")
+        net.part_of, net.n_parts, net.role, net.H = po.data_ptr(), P, _role(role)["code"], H
+        net.h0, net.h0_stride = h0.data_ptr(), int(h0.stride(0)) if n > 1 else int(h0.shape[1])
+        if vis_fixed is not None:
+            if int(vis_fixed.numel()) != self.M:
+                raise ValueError(f"vis_fixed must hold {self.M} entries")
+            if vis_fixed.dtype != torch.uint8:
+                vis_fixed = vis_fixed != 0
+            keep.append(_on_device(vis_fixed.reshape(-1), vis_fixed.dtype, self.device, "vis_fixed"))
+            net.vis_fixed = keep[-1].data_ptr()
+        for name, t, shape, dt in (("score_out", score_out, (n, self.M), torch.float32), ("part_score_out", part_score_out, (n, P), torch.float32),
+                                   ("part_out", part_out, (n,), torch.int32), ("atype_logits_out", atype_logits_out, (n, T), torch.float32),
+                                   ("dev_logits_out", dev_logits_out, (n, self.M), torch.float32)):
+            if t is not None:
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
+                setattr(net, name, t.data_ptr())
+        _lib.check(self.lib.cygym_hier_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_hier_decode")
+
     def _comm_eval(self, tok_base, tok_dev, w_type, b_type, types, vis, backward: bool):
         """The CommEval struct of comm_actor_evaluate / comm_actor_evaluate_backward from the factorised inputs, and what has to
         stay alive until the call has returned.  dev_type_head.weight is packed here, per call: the weights change every step."""

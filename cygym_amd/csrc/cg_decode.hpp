@@ -1,5 +1,5 @@
 // cg_decode.hpp -- device code shared by the consumer-side kernels of the C-ABI unit (cg_aux_kernels.hpp), the tick + actor unit
-// (cg_inst_actor.hip) and the coordinate-ascent unit (cg_inst_coord.hip).  Templates and force-inlined device functions only
+// (cg_inst_actor.hip), the coordinate-ascent unit (cg_inst_coord.hip) and the hierarchical unit (cg_inst_hier.hip).  Templates and force-inlined device functions only
 // (included in more than one translation unit, inside namespace cygym_k).  What every writer of group 0 of an action row shares:
 //   dpp_pair_max, float_order_bits   wave-wide lexicographic max of (order bits, ~index) pairs
 //   wave_first_max                   ... read back as "index of the first maximum, 0 if none": decode_row_regs, the chunked decode of
@@ -7,7 +7,7 @@
 //   eps_greedy_type                  the epsilon-greedy type draw: decode_actions_kernel, decode_row_regs, the chunked decode
 //   RowList                          compaction of the ascending device list, cut at max_devs, zero fill, the row's scalars and
 //                                    CG_DECODE_TRUNCATED: write_actions_kernel, decode_actions_kernel, decode_row_regs, the chunked
-//                                    decode, the merge of coord_ascent_kernel (group_row writes several groups: its own code, cg_aux_kernels.hpp)
+//                                    decode, the merge of coord_ascent_kernel, hier_kernel (group_row writes several groups: its own code, cg_aux_kernels.hpp)
 //   decode_row_regs                  decode of a row held in registers: actor_head_kernel, and through head_decode_row (row from LDS)
 //                                    actor_head_mfma_kernel, actor_mlp_kernel, tick_actor_kernel
 #ifndef CG_DECODE_HPP
@@ -131,4 +131,5 @@ __device__ __forceinline__ void head_decode_row(const float* outs_row, const flo
 
 #include "cg_actor_mlp.hpp"
 #include "cg_coord_ascent.hpp"
+#include "cg_hier.hpp"
 #endif  // CG_DECODE_HPP

@@ -70,6 +70,12 @@ extern template __global__ void comm_actor_kernel<false>(cygym_comm_actor, cygym
 extern template __global__ void comm_actor_kernel<true>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 }  // namespace cygym_k
 
+// the hierarchical (HAGS) decode lives in its own unit (cg_inst_hier.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void hier_kernel<false>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+extern template __global__ void hier_kernel<true>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+}  // namespace cygym_k
+
 // the evaluate / backward kernels of the PPO update live in their own unit (cg_inst_eval.hip): declared, not instantiated, here
 namespace cygym_k {
 extern template __global__ void comm_eval_fwd_kernel<1, false>(cygym_comm_eval);
@@ -224,6 +230,7 @@ int cygym_sizeof(int32_t which) {
     case 12: return (int)sizeof(cygym_comm_actor);
     case 14: return (int)sizeof(cygym_comm_eval);   // (13 stays unassigned: -1)
     case 16: return (int)sizeof(cygym_critic_tail_desc);   // (15 stays unassigned too: earlier bindings probe it for -1)
+    case 17: return (int)sizeof(cygym_hier_net);
     default: return -1;
   }
 }
@@ -850,6 +857,33 @@ int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const 
   const uint8_t* live = h->b.live;
   int M = h->t.M;
   return launch_decode(h, k, dim3((src->n + CM_WAVES - 1) / CM_WAVES), dim3(CM_THREADS), lds, stream, {net, src, dst}, {&live, &M});   // 16 rows per workgroup
+}
+
+int cygym_hier_decode(cygym_handle* h, const cygym_hier_net* net, const cygym_action_vectors* src, const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_hier_decode";
+  const char* const bad_layout = "cygym_hier_decode: bad layout (types >= 1, the handle's device count, 1 .. 255 parts, role 1 or 2, h0_stride >= 3 H, 16-byte aligned packed matrices / w_mask_t)%s";
+  const bool own = net && net->h0 && net->w_mask_t && net->w_score && net->b_score && net->w_act2 && net->b_act2 && net->w_dev2 && net->b_dev2 &&
+                   net->w_act_head && net->b_act_head && net->w_dev_head && net->b_dev_head && net->part_of;
+  if (const int rc = check_vectors(h, src, dst, who, own, 0, bad_layout)) return rc;
+  if (src->n_types < 1 || net->n_parts < 1 || net->n_parts > HR_MAX_PARTS || (net->role != 1 && net->role != 2) || net->H < 1 ||
+      (long long)net->h0_stride < 3ll * net->H ||
+      (((uintptr_t)net->w_mask_t | (uintptr_t)net->w_score | (uintptr_t)net->w_act2 | (uintptr_t)net->w_dev2 | (uintptr_t)net->w_act_head | (uintptr_t)net->w_dev_head) & 15))
+    return fail(h, CYGYM_EINVAL, bad_layout, "");
+  if (net->H < 16 || net->H > HR_MAX_H || (net->H & 15) || src->n_types > HR_MAX_T || h->t.M > HR_MAX_M)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_hier_decode: H must be a multiple of 16 in 16 .. 256, at most 32 action types, at most 2048 devices%s", "");
+  if (!net->vis_fixed && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_hier_decode: handle not bound (without vis_fixed the visibility mask is read off the flag plane)%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const HrPlan pl = hr_plan(net->H, h->t.M);
+  const size_t lds = (size_t)pl.total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_hier_decode: the tiles do not fit in LDS%s", "");
+  const bool outs = net->score_out || net->part_score_out || net->part_out || net->atype_logits_out || net->dev_logits_out;
+  const void* k = outs ? (const void*)hier_kernel<true> : (const void*)hier_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const uint8_t* live = h->bound ? (const uint8_t*)h->b.live : nullptr;
+  int M = h->t.M;
+  return launch_decode(h, k, dim3((src->n + HR_WAVES - 1) / HR_WAVES), dim3(HR_THREADS), lds, stream, {net, src, dst}, {&live, &M});   // 16 rows per workgroup
 }
 
 // What the two evaluate calls check alike, in the order of the decodes' shared check: handle, pointers, layout (CYGYM_EINVAL),

@@ -16,6 +16,10 @@ decode_action does not read the actor at all but scores one-device candidate act
 (IPPO.py:135-196 with USE_GAT off, as shipped) and its greedy executor (IPPOCommPolicy.select_action, IPPO.py:237-284), which
 answers with GROUPS of devices per action type; the batch evaluates the network, samples and groups in one launch
 (cygym_comm_actor_decode).
+
+`HierarchicalNet` / `HierarchicalPolicy` are the fourth: the HAGS best response of hierarchical_br.py (`--BR_type hierarchical`) --
+a score net picks one part of the partitioned graph, a two-stage net picks the action type and the devices inside that part's
+visible subset (HierarchicalBestResponse.execute, :419-494); the batch does it in one addmm plus one launch (cygym_hier_decode).
 """
 from __future__ import annotations
 
@@ -744,6 +748,221 @@ class CommActorPolicy:
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("a CommActorPolicy answers with groups of devices per action type: a dict of single actions cannot "
                                   "carry them (it runs through write(), on a batch with cygym_comm_actor_decode)")
+
+
+class _ScoreNet(nn.Module):
+    def __init__(self, state_dim, M, hidden):
+        super().__init__()
+        self.fc1, self.fc2 = nn.Linear(state_dim, hidden), nn.Linear(hidden, M)
+
+
+class _TwoStage(nn.Module):
+    def __init__(self, state_dim, M, n_types, hidden):
+        super().__init__()
+        self.act_body = nn.Sequential(nn.Linear(state_dim, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU())
+        self.act_head = nn.Linear(hidden, n_types)
+        self.dev_body = nn.Sequential(nn.Linear(state_dim + M, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU())
+        self.dev_head = nn.Linear(hidden, M)
+
+
+NO_PART = 0xFF      # part_of entry of a device that belongs to no part
+
+
+class HierarchicalNet(nn.Module):
+    """The two networks of the reference's HAGS best response (hierarchical_br.py) with the reference's parameter names, so that
+    the two state dicts of `strategy.type_mapping["hierarchical"]` load unchanged (load_strategy):
+        score_net  ScoreNet (:56-66): fc1 - ReLU - fc2, one raw score per device
+        two_stage  TwoStageEndToEnd (:71-115): act_body.0 - ReLU - act_body.2 - ReLU - act_head on the state;
+                   dev_body.0 - ReLU - dev_body.2 - ReLU - dev_head on [state, subset mask]; both outputs through nan_to_num(0, 0, 0)
+    decide() is HierarchicalBestResponse.execute (:419-494) vectorised over a batch with torch ops -- it runs anywhere, and in
+    torch.float64 it is the restatement cygym_hier_decode is tested against.  packed() / h0() give the form that kernel reads."""
+
+    def __init__(self, state_dim: int, M: int, n_types: int, hidden: int = 256):
+        super().__init__()
+        self.state_dim, self.M, self.n_types, self.hidden = int(state_dim), int(M), int(n_types), int(hidden)
+        self.score_net = _ScoreNet(self.state_dim, self.M, self.hidden)
+        self.two_stage = _TwoStage(self.state_dim, self.M, self.n_types, self.hidden)
+
+    def load_strategy(self, mapping):
+        """Load `score_net` and `two_stage` of a reference strategy's type_mapping["hierarchical"] (or that dict itself)."""
+        mapping = mapping.get("hierarchical", mapping)
+        as_t = lambda sd: {k: torch.as_tensor(v) for k, v in sd.items()}  # noqa: E731
+        self.score_net.load_state_dict(as_t(mapping["score_net"]))
+        self.two_stage.load_state_dict(as_t(mapping["two_stage"]))
+        return self
+
+    _lin = staticmethod(CommActorCritic._lin)
+
+    @torch.no_grad()
+    def decide(self, state, vis, part_of, dtype=None, n_parts=None, subset=None):
+        """execute (:419-494) for a batch.  state [B, state_dim]; vis [B, M] or [M] (visible where > 0.5, or bool); part_of [M]
+        integer, NO_PART = in no part (an entry >= n_parts counts as NO_PART; n_parts defaults to the largest entry + 1).
+        Returns a dict: atype [B] int64 (the index, before any type map), dev_mask [B, M] bool, part [B] int64 (the chosen part; -1:
+        the [0] fallback, -2: the single-device fallback), subset [B, M] bool, score [B, M], part_scores [B, n_parts],
+        atype_logits [B, T], dev_logits [B, M] -- in `dtype` (default: the state's) from the same fp32 parameters.
+        `subset` [B, M] bool: skip steps 1-3 and run the low-level net and the decision on that subset (tests: the kernel's own)."""
+        dt = state.dtype if dtype is None else dtype
+        s = state.to(dt)
+        B, M, dev = s.shape[0], self.M, s.device
+        sn, ts = self.score_net, self.two_stage
+        clean = lambda t: torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0)  # noqa: E731
+        score = self._lin(sn.fc2, torch.relu(self._lin(sn.fc1, s, dt)), dt)
+        v = (vis if vis.dtype == torch.bool else vis > 0.5).to(dev)
+        v = v[None].expand(B, M) if v.dim() == 1 else v
+        po = torch.as_tensor(part_of).to(dev).long()
+        P = int(po[po != NO_PART].max()) + 1 if n_parts is None else int(n_parts)
+        onehot = (po[:, None] == torch.arange(P, device=dev)[None])                       # [M, P]; an entry >= P is in no part
+        vin = v & onehot.any(dim=1)[None]
+        psum = torch.where(vin, score, torch.zeros_like(score)) @ onehot.to(dt)
+        pscore = torch.where((vin.to(dt) @ onehot.to(dt)) > 0, psum, torch.full_like(psum, -1e9))
+        chosen = torch.argmax(pscore, dim=1)                                               # first maximum
+        sub = vin & (po[None] == chosen[:, None])
+        empty, anyvis = ~sub.any(dim=1), v.any(dim=1)
+        dstar = torch.argmax(score * v.to(dt), dim=1)                                      # the product over ALL d (:470)
+        lone = torch.where(anyvis, dstar, torch.zeros_like(dstar))
+        sub = torch.where(empty[:, None], torch.arange(M, device=dev)[None] == lone[:, None], sub)
+        part = torch.where(empty, torch.where(anyvis, torch.full_like(chosen, -2), torch.full_like(chosen, -1)), chosen)
+        if subset is not None:
+            sub = subset.to(dev).bool()
+        at_logits = clean(self._lin(ts.act_head, torch.relu(self._lin(ts.act_body[2], torch.relu(self._lin(ts.act_body[0], s, dt)), dt)), dt))
+        x = torch.relu(self._lin(ts.dev_body[0], torch.cat([s, sub.to(dt)], dim=-1), dt))
+        dev_logits = clean(self._lin(ts.dev_head, torch.relu(self._lin(ts.dev_body[2], x, dt)), dt))
+        sel = sub & (dev_logits > 0)                                                       # sigmoid(l) > 0.5, decided on the logit
+        fb = torch.argmax(torch.where(sub, dev_logits, torch.full_like(dev_logits, float("-inf"))), dim=1)
+        sel = torch.where(sel.any(dim=1)[:, None], sel, torch.arange(M, device=dev)[None] == fb[:, None])
+        return {"atype": torch.argmax(at_logits, dim=1), "dev_mask": sel, "part": part, "subset": sub, "score": score,
+                "part_scores": pscore, "atype_logits": at_logits, "dev_logits": dev_logits}
+
+    def packed(self):
+        """What cygym_hier_decode reads of the parameters, as a dict (BatchedCyberDefenseEnv.hier_decode adds part_of / n_parts of
+        the policy): the three first layers as ONE transposed matrix for h0(), the mask part of dev_body.0 as rows, the packed
+        second layers and heads.  Built once per parameter version."""
+        sn, ts = self.score_net, self.two_stage
+        mods = [sn.fc1, sn.fc2, ts.act_body[0], ts.act_body[2], ts.act_head, ts.dev_body[0], ts.dev_body[2], ts.dev_head]
+        ver = tuple((m.weight._version, m.weight.data_ptr(), m.bias._version) for m in mods)
+        if getattr(self, "_pk_ver", None) != ver:
+            from .batched_env import BatchedCyberDefenseEnv as B
+            S_ = self.state_dim
+            with torch.no_grad():
+                wd0 = ts.dev_body[0].weight.detach()
+                c = lambda t: t.detach().contiguous()  # noqa: E731
+                self._pk = {
+                    "H": self.hidden, "T": self.n_types,
+                    "w0_t": torch.cat([sn.fc1.weight.detach(), ts.act_body[0].weight.detach(), wd0[:, :S_]]).t().contiguous(),
+                    "b0": torch.cat([sn.fc1.bias.detach(), ts.act_body[0].bias.detach(), ts.dev_body[0].bias.detach()]).contiguous(),
+                    "w_mask_t": wd0[:, S_:].t().contiguous(),
+                    "w_score": B.pack_linear(sn.fc2.weight), "b_score": c(sn.fc2.bias),
+                    "w_act2": B.pack_linear(ts.act_body[2].weight), "b_act2": c(ts.act_body[2].bias),
+                    "w_dev2": B.pack_linear(ts.dev_body[2].weight), "b_dev2": c(ts.dev_body[2].bias),
+                    "w_act_head": B.pack_linear(ts.act_head.weight), "b_act_head": c(ts.act_head.bias),
+                    "w_dev_head": B.pack_linear(ts.dev_head.weight), "b_dev_head": c(ts.dev_head.bias),
+                }
+            self._pk_ver = ver
+        return self._pk
+
+    @torch.no_grad()
+    def h0(self, state, pack=None):
+        """score.fc1(s) | act_body.0(s) | dev_body.0.weight[:, :S] s + dev_body.0.bias for a batch, before the relu: ONE addmm."""
+        pk = self.packed() if pack is None else pack
+        return torch.addmm(pk["b0"], state, pk["w0_t"])
+
+
+def part_table(partitions, M: int) -> torch.Tensor:
+    """Lists of device ids (Subnet.partitions) -> part_of [M] uint8, NO_PART where a device is in no list.  The parts must be
+    disjoint, their ids inside 0 .. M-1, and there may be at most 255 of them."""
+    if not 1 <= len(partitions) <= 255:
+        raise ValueError("1 to 255 parts")
+    po = [NO_PART] * int(M)
+    for p, ids in enumerate(partitions):
+        for d in ids:
+            d = int(d)
+            if not 0 <= d < M or po[d] != NO_PART:
+                raise ValueError(f"part {p}: device {d} is out of range or already in part {po[d] if 0 <= d < M else '?'}")
+            po[d] = p
+    return torch.tensor(po, dtype=torch.uint8)
+
+
+class HierarchicalPolicy:
+    """A trained `hierarchical` (HAGS) strategy in the closed loop: HierarchicalBestResponse.execute (hierarchical_br.py:419-494) for
+    a batch as one addmm plus ONE launch (cygym_hier_decode; include/cygym_abi.h states the decision).
+      partitions  lists of device ids (Subnet.create_partitions); a device in no list is in no part
+      vis         "env": every row reads its own env's visibility off the flag plane (what the reference's training loop does, :285);
+                  a [M] tensor: that ONE mask for every decision (what the reference's execute does in payoff evaluation: it reads
+                  the env copy made at construction, :130 / :441)
+      type_map    optional [n_types]: the reference hands the arg-max index straight to env.step
+    write() does not synchronise with the host (simulate_grid may capture it in a HIP graph).  __call__ raises: with vis = "env" the
+    decision needs the batch's flag plane, which a dict-returning policy call does not see; HierarchicalNet.decide is the torch form."""
+
+    tick_free = True
+
+    def __init__(self, net: HierarchicalNet, role: str, partitions, type_map=None, vis="env"):
+        if role not in ("defender", "attacker"):
+            raise ValueError("role must be 'attacker' or 'defender'")
+        self.net, self.role = net, role
+        self.part_of, self.n_parts = part_table(partitions, net.M), len(partitions)
+        if isinstance(vis, str):
+            if vis != "env":
+                raise ValueError("vis is 'env' or a [M] mask")
+            self.vis = None
+        else:
+            vis = torch.as_tensor(vis)
+            if vis.numel() != net.M:
+                raise ValueError(f"vis must hold {net.M} entries")
+            self.vis = (vis.reshape(-1) != 0).to(torch.uint8).contiguous()
+        self.n_types = net.n_types
+        self.type_map = None if type_map is None else torch.as_tensor(type_map, dtype=torch.int32)
+        self.action_types = list(range(self.n_types)) if type_map is None else sorted({int(x) for x in self.type_map.tolist()})
+
+    _map = ActorPolicy._map
+
+    @classmethod
+    def from_strategy(cls, mapping, batch, role: str, partitions=None, type_map=None, vis="env"):
+        """From a reference strategy's type_mapping["hierarchical"] (or that dict itself): `M` and `partition_size` are read from
+        it, the widths from the state dicts; `partitions` default to the facade's SubnetView.create_partitions(partition_size) on
+        the batch's topology."""
+        import math
+        mapping = mapping.get("hierarchical", mapping)
+        M = int(mapping.get("M", batch.M))
+        if M != batch.M:
+            raise ValueError(f"the strategy was trained on {M} devices, the batch has {batch.M}")
+        hidden, state_dim = (int(x) for x in mapping["score_net"]["fc1.weight"].shape)
+        n_types = int(mapping["two_stage"]["act_head.weight"].shape[0])
+        if state_dim != batch.role_width(role):
+            raise ValueError(f"the strategy reads {state_dim} state columns, the {role} view has {batch.role_width(role)}")
+        net = HierarchicalNet(state_dim, M, n_types, hidden=hidden).load_strategy(mapping).eval().to(batch.device)
+        if partitions is None:
+            import numpy as np
+            from .facade import GraphView, SubnetView
+            sub = SubnetView({}, GraphView(batch.topo, np.zeros(batch.topo.E, np.uint8)))
+            sub.create_partitions(int(mapping.get("partition_size", math.ceil(math.sqrt(M)))))
+            partitions = sub.partitions
+        pol = cls(net, role, partitions, type_map=type_map, vis=vis)
+        pol._packed(torch.device(batch.device))      # the tables move to the batch's device here: write() then copies nothing from the host
+        pol._map(torch.device(batch.device))
+        return pol
+
+    def _packed(self, device):
+        pk = self.net.packed()
+        if getattr(self, "_pk_src", None) is not pk or self.part_of.device != device:
+            self.part_of = self.part_of.to(device)
+            if self.vis is not None:
+                self.vis = self.vis.to(device)
+            self._pk, self._pk_src = dict(pk, part_of=self.part_of, n_parts=self.n_parts), pk
+        return self._pk
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, **outs):
+        """h0 = one addmm, then the whole decision + scatter into rows `rows` of the action tensors in ONE launch."""
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != self.net.state_dim:
+            raise ValueError(f"obs must be a float32 [n, {self.net.state_dim}] role view")
+        if batch.M != self.net.M:
+            raise ValueError(f"the net was built for {self.net.M} devices, the batch has {batch.M}")
+        pk = self._packed(obs.device)
+        batch.hier_decode(rows, self.net.h0(obs, pk), pk, self.role, act=act, vis_fixed=self.vis, type_map=self._map(obs.device), **outs)
+
+    def __call__(self, obs, t, M, L):
+        raise NotImplementedError("a HierarchicalPolicy reads the visibility of the env it decides for off the batch's flag plane: it "
+                                  "runs through write(), on a batch with cygym_hier_decode (HierarchicalNet.decide is the torch form)")
 
 
 @torch.no_grad()

@@ -191,7 +191,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc; -1 for anything else, 13 and 15 included: those indices stay unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net; -1 for anything else, 13 and 15 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -636,6 +636,87 @@ typedef struct cygym_critic_tail_desc {
  * written then.  Out of scope: fc1 (the caller's addmm, split into its state and action parts without a cat) and the optimiser. */
 int cygym_critic_tail(cygym_handle* h, const cygym_critic_tail_desc* e, void* stream);
 int cygym_critic_tail_backward(cygym_handle* h, const cygym_critic_tail_desc* e, void* stream);
+
+/* The HAGS (hierarchical) best response of the reference, hierarchical_br.py: ScoreNet (:56-66: fc1 - ReLU - fc2, one raw score per
+ * device) and TwoStageEndToEnd (:71-115: act_body.0 - ReLU - act_body.2 - ReLU - act_head on the state s; dev_body.0 - ReLU - dev_body.2 -
+ * ReLU - dev_head on [s, mask]) in the pieces the decode below reads.  H = the hidden width (the reference: 256), S = the width of the
+ * role view, T = the role's action types, P = n_parts.  All DEVICE pointers, fp32 unless noted; packed matrices in the fragment order
+ * of cygym_amd.batched_env.pack_linear: packed[t][g][lane][i] = W[16 t + lane % 16][16 g + 4 (lane / 16) + i], zero rows past the last. */
+typedef struct cygym_hier_net {
+  const float* h0;            /* [n][h0_stride], h0_stride >= 3 H: the pre-activations  score.fc1(s) | act_body.0(s) | dev_body.0.weight[:, :S] s +
+                                 dev_body.0.bias  of SOURCE row r, three H-wide blocks of ONE addmm of the caller over the concatenated weights */
+  const float* w_mask_t;      /* [M][H] dev_body.0.weight[:, S:] transposed: one contiguous row per device, 16-byte aligned                   */
+  const float* w_score;       /* score_net.fc2.weight [M][H] packed: [ceil(M / 16)][H / 16][64][4], 16-byte aligned                           */
+  const float* b_score;       /* [M]                                                                                                          */
+  const float* w_act2;        /* act_body.2.weight [H][H] packed, 16-byte aligned                                                             */
+  const float* b_act2;        /* [H]                                                                                                          */
+  const float* w_dev2;        /* dev_body.2.weight [H][H] packed, 16-byte aligned                                                             */
+  const float* b_dev2;        /* [H]                                                                                                          */
+  const float* w_act_head;    /* act_head.weight [T][H] packed: [ceil(T / 16)][H / 16][64][4], 16-byte aligned                                */
+  const float* b_act_head;    /* [T]                                                                                                          */
+  const float* w_dev_head;    /* dev_head.weight [M][H] packed like w_score, 16-byte aligned                                                  */
+  const float* b_dev_head;    /* [M]                                                                                                          */
+  const uint8_t* part_of;     /* [M] the part (Subnet.create_partitions) device d belongs to, 0 .. n_parts - 1; 0xFF = in no part            */
+  const uint8_t* vis_fixed;   /* optional [M], non-zero = visible: ONE visibility mask used for every row in place of the flag plane          */
+  float* score_out;           /* optional [n][M] the score net's logits                                                                       */
+  float* part_score_out;      /* optional [n][n_parts] the parts' scores                                                                      */
+  int32_t* part_out;          /* optional [n] the chosen part; -1: the [0] fallback, -2: the single-device fallback (see below)               */
+  float* atype_logits_out;    /* optional [n][T]                                                                                              */
+  float* dev_logits_out;      /* optional [n][M] the logits of EVERY device (only the chosen subset's are read by the decision)               */
+  int32_t n_parts;            /* 1 .. 255                                                                                                     */
+  int32_t role;               /* 1 defender, 2 attacker: which mask is read off the flag plane (not read when vis_fixed is given)             */
+  int32_t H;                  /* a multiple of 16, 16 .. 256                                                                                  */
+  int32_t h0_stride;          /* floats per row of h0, >= 3 H                                                                                 */
+} cygym_hier_net;
+
+/* Replaces: HierarchicalBestResponse.execute (hierarchical_br.py:419-494), what DoubleOracle._strategy_decide_action dispatches a
+ * `hierarchical` strategy to per decision (do_agent.py:729-730), for a batch, in ONE launch, fused with the scatter into the action
+ * tensors.  Per source row r (env rows[r]):
+ *   1. visibility v (:19-41): attacker known and attacker-owned and not not-yet-added; defender attacker-owned and not not-yet-added --
+ *      off the bound flag plane of env rows[r], or vis_fixed for every row.  (The reference's execute reads the mask of the env copy made
+ *      when the best response was constructed, :130 / :441, i.e. ONE mask for all decisions of a payoff evaluation: that is vis_fixed;
+ *      its training loop, :285, reads the env being stepped: that is the default.)
+ *   2. score[d] = fc2(relu(fc1(s)))[d], no nan_to_num.  Score of part p = the sum of score[d] over the visible devices of p; a part
+ *      without a visible device scores -1e9 (:447-453).  Chosen part = the first maximum (:465).  -1e9 is not -inf, so the branch at
+ *      :455-463 never runs and is not restated.
+ *   3. subset = the visible devices of the chosen part, ascending.  Empty (:467-472): with a visible device anywhere, the ONE device
+ *      argmax_d (score[d] * v[d]) -- the fp32 product over ALL d, first maximum: an invisible device contributes 0 and wins against
+ *      negative visible scores (part_out = -2); with none, the subset [0] (part_out = -1).
+ *   4. atype_logits = act_head(relu(act_body.2(relu(act_body.0(s))))), dev_logits = dev_head(relu(dev_body.2(relu(dev_body.0([s, mask]))))),
+ *      mask = the 0/1 vector of the subset; both through nan_to_num(nan = 0, posinf = 0, neginf = 0) (:16-17, :112-115).
+ *   5. type = the first maximum of atype_logits, through `type_map`; devices = the subset's d with dev_logit[d] > 0, and when there is
+ *      none the subset's first maximum of dev_logit; exploit list [0], app 0 (:478-493).
+ * Deviations, deliberate: the reference selects sigmoid(dev_logit) > 0.5 and falls back to the first maximum of the PROBABILITIES
+ * (:481-484).  The kernel decides on the logits.  The two differ only where 0 < logit <~ 1.2e-7 (fp32 sigmoid rounds to exactly 0.5: not
+ * selected there, selected here) or where two probabilities round to the same float (the fallback's first maximum may then be an earlier
+ * device there) -- both below the fp32 network's own error.  The reference's subset keeps the order of the partition's list, which
+ * create_partitions emits ascending; here it IS ascending.
+ * Arithmetic, fp32 throughout:
+ *   a linear layer y = bias + sum_k W[.][k] x[k] on the matrix cores (v_mfma_f32_16x16x4_f32), TWO fused-multiply-add chains per output,
+ *     both starting at 0: with k = 16 g + 4 j + i (the instruction's four j inside one step), chain 0 takes i = 0, 2 and chain 1 takes
+ *     i = 1, 3 of g = 0 .. H/16 - 1 in ascending order; the chains are added, then the bias (the order of cygym_actor_mlp_decode).
+ *   relu(x) = x < 0 ? 0 : x (NaN stays NaN, as in torch).
+ *   part sums: ONE running fp32 sum per part that starts at 0 and takes the part's visible devices in ascending id.
+ *   dev_body.0: x = h0's third block, then + w_mask_t[d] for the subset's d in ascending id, one add each, then relu.
+ *   first maximum: +0 and -0 tie (the lower index wins), as in torch.argmax.
+ * No floating-point atomics: the same inputs give the same bits.  The decode reads no Philox draw and neither reads nor advances the
+ * rng tick.  The row is written as group 0 exactly like cygym_decode_actions: ascending ids, cut at max_devs with CG_DECODE_TRUNCATED
+ * raised in `status`, n_exploit = 1, exploit 0, app 0 (n_groups and mode are not touched).
+ * From `layout`: rows, type_map (the reference hands the index straight to env.step: NULL = identity), n_types = T, n_devices (= the
+ * handle's), n, status; n_exploits, n_apps, vec and epsilon_thr are not read.
+ * Limits (CYGYM_EUNSUPPORTED beyond): H a multiple of 16 in 16 .. 256; T <= 32; any M of the handle up to 2048 (wider than 512, the score
+ * pass and the dev_head pass run in chunks of 512 columns; the part sums, the subset and the running maxima persist across chunks).
+ * CYGYM_EINVAL (the argument check the decodes share): a NULL handle or mandatory pointer, T < 1, n_parts outside 1 .. 255, a role
+ * other than 1 / 2, h0_stride < 3 H, a packed matrix or w_mask_t off 16-byte alignment; nothing is written then.  part_of lives in
+ * device memory, so the call cannot inspect it without a synchronisation: an entry >= n_parts is treated like 0xFF (in no part) by the
+ * kernel, and the Python layer (policies.HierarchicalPolicy) refuses such a table when it builds it.  CYGYM_ENOTBOUND only when the flag
+ * plane is needed (vis_fixed == NULL) and the handle is not bound.
+ * Out of scope: the sampled mode of train() (:285-398: a Categorical over parts, a Bernoulli per subset device, log-probabilities and
+ * entropies) and its REINFORCE update; `meta` (meta_hierarchical_br.py) and the HMARL families; populations of nets in one launch;
+ * building h0 from the flag planes on chip; non-finite score logits (torch.argmax treats NaN as the maximum: here a valid row is
+ * still written, which part wins is unspecified). */
+int cygym_hier_decode(cygym_handle* h, const cygym_hier_net* net, const cygym_action_vectors* layout, const cygym_actions* dst,
+                      void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`
