@@ -156,7 +156,9 @@ typedef struct cygym_actions {
   const int32_t* n_exploit; /* [N][G]                                           */
   const int32_t* exploit;   /* [N][G][CG_MAX_EXPLOITS]                          */
   const int32_t* app;       /* [N][G] app_index, -1 when not a Python int       */
-  const int32_t* dev_cnt;   /* [N][G] len(device_indices)                       */
+  const int32_t* dev_cnt;   /* [N][G] len(device_indices).  A negative count is an empty list; a list that does not
+                               fit what is left of the row's L entries is cut there (the groups behind it are empty),
+                               and everything that depends on the length (costs of actions 2 / 3) sees the cut one   */
   const int16_t* dev_idx;   /* [N][L] the groups' device lists, concatenated    */
   int32_t max_groups;       /* G                                                */
   int32_t max_devs;         /* L                                                */

@@ -777,6 +777,7 @@ static void step_one(env_t* e, const cygym_actions* a, const cygym_outputs* o, i
     int at = a->atype[(size_t)idx * G];
     int Ld = a->dev_cnt[(size_t)idx * G];
     if (Ld > L) Ld = L;
+    if (Ld < 0) Ld = 0; /* a negative count is an empty list (cygym_abi.h) */
     if (mode == CG_MODE_DEFENDER) { if (!(at >= 0 && at < e->c->n_def_actions)) at = 8; }
     else                          { if (!(at >= 0 && at < e->c->n_att_actions)) at = 3; }
     for (int d = 0; d < M; ++d) { /* :904-908 */
@@ -810,6 +811,7 @@ static void step_one(env_t* e, const cygym_actions* a, const cygym_outputs* o, i
     for (int g = 0; g < ng && g < G; ++g) { /* _step_apply_only :612-692 */
       int at = a->atype[(size_t)idx * G + g];
       int Ld = a->dev_cnt[(size_t)idx * G + g];
+      if (Ld < 0) Ld = 0; /* a negative count is an empty list: dp never walks backwards */
       if (used + Ld > L) Ld = L - used;
       if (mode == CG_MODE_DEFENDER && at == 0) at = 8;
       else if (mode == CG_MODE_ATTACKER && at == 0) at = 3;

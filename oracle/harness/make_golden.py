@@ -123,6 +123,46 @@ def s32_grouped():
     return H.run_scenario(env0, 2, 240, fn, seed=15, env_id_base=50), 4
 
 
+@scenario("s96_grouped")
+def s96_grouped():
+    """step_grouped at the size of an IPPO/MAPPO grouping: up to 13 groups per tick whose lists run to the whole network
+    (longer than one 64-lane wave), with and without repeats, the same device cleaned by several groups of one tick, empty
+    lists, checkpoint / revert / detector training / per-device checkpoint groups between the cleans, attacker-mode grouped
+    ticks, interleaved with single-action steps.  Action 11 always names a device (the reference raises without one)."""
+    M = 96
+    env0 = H.build_env(M, 80, init_seed=191, strip_vuln_frac=0.4, extra_reachable=3)
+    single = mixed_actions(M, ALL_DEF, ALL_ATT, 8)
+
+    def one_list(rs):
+        kind = rs.rand()
+        if kind < 0.30:
+            return [int(x) for x in rs.choice(M, size=int(rs.randint(0, 9)), replace=False)]
+        if kind < 0.55:
+            return [int(x) for x in rs.randint(0, M, size=int(rs.randint(1, 65)))]
+        if kind < 0.85:
+            return [int(x) for x in rs.permutation(M)[:int(rs.randint(65, M + 1))]]
+        return [int(x) for x in rs.randint(0, M, size=int(rs.randint(65, M + 1)))]
+
+    def fn(e, t, env, rs):
+        if (t // 3) % 2 == 0 or rs.rand() < 0.3:
+            mode = DEF if (t % 2 == 0) else ATT
+            ng = int(rs.choice([1, 2, 3, 5, 8, 13, 13]))
+            groups = []
+            for _ in range(ng):
+                if mode == DEF:
+                    at = int(rs.choice([0, 1, 1, 1, 1, 1, 2, 3, 10, 11, 13]))
+                    dv = one_list(rs)
+                    if at == 11 and not dv:
+                        dv = [int(rs.randint(0, M))]
+                else:
+                    at = int(rs.choice([0, 1, 2, 3]))
+                    dv = dev_list(rs, M, 3)
+                groups.append((at, np.array([0]), dv, 0))
+            return mode, groups
+        return single(e, t, env, rs)
+    return H.run_scenario(env0, 2, 120, fn, seed=61, env_id_base=700), 13
+
+
 @scenario("s24_norng")
 def s24_norng():
     """RNG-free: lambda_events = 0, workload_cap = 0, no stalling / picking actions."""
