@@ -91,6 +91,14 @@ def s256_mixed():
     return H.run_scenario(env0, 2, 90, mixed_actions(256, ALL_DEF, ALL_ATT, 32), seed=13, env_id_base=7), 1
 
 
+@scenario("s129_mixed")
+def s129_mixed():
+    """An odd device count over three 64-lane chunks with one device in the last (M % 4 == 1): the scalar observation
+    writers, the padded byte planes and every chunk loop against the reference itself."""
+    env0 = H.build_env(129, 100, init_seed=201, strip_vuln_frac=0.5, extra_reachable=4)
+    return H.run_scenario(env0, 2, 90, mixed_actions(129, ALL_DEF, ALL_ATT, 16), seed=71, env_id_base=129), 1
+
+
 @scenario("s16_train")
 def s16_train():
     """Action 10 (detector training) present; later scans run the trained detector."""
@@ -395,6 +403,15 @@ def s16_slowscan():
     M = 16
     env0 = H.build_env(M, 14, init_seed=161, strip_vuln_frac=0.2, extra_reachable=1, overrides=dict(fast_scan=False))
     return H.run_scenario(env0, 3, 220, slow_scan_actions(M, 4), seed=51), 1
+
+
+@scenario("s65_slowscan")
+def s65_slowscan():
+    """The per-log scan path at an odd device count one past a chunk (65): the per-env anomaly plane is read by the scalar
+    observation writers, with trainings as in s16_slowscan."""
+    M = 65
+    env0 = H.build_env(M, 56, init_seed=211, strip_vuln_frac=0.3, extra_reachable=2, overrides=dict(fast_scan=False))
+    return H.run_scenario(env0, 2, 120, slow_scan_actions(M, 9), seed=72), 1
 
 
 @scenario("s16_slowcoin")

@@ -5,6 +5,7 @@
 //   wpb wpb_fused wave_lds shared_lds lds_bytes in_lds x_bytes cby_global lists_global wide max_devs waves
 // A line that starts with '+' re-plans the previous line's handle, as cygym_bind / cygym_step do for new buffers or a longer
 // device list: a plan that does not fit leaves the old one in place, and that one is printed.
+// A line that starts with '!' also prints " ct=<0 / 1>": whether the network runs on the compile-time-size kernels.
 #include <stdio.h>
 #include "cg_plan.hpp"
 
@@ -13,8 +14,8 @@ int main() {
   LaunchPlan cur = {};
   while (fgets(line, sizeof line, stdin)) {
     const char* s = line;
-    const bool again = *s == '+';
-    if (again) ++s;
+    const bool again = *s == '+', show_ct = *s == '!';
+    if (again || show_ct) ++s;
     int M, E, K, max_row, few, full, max_devs, forced, f_cby, f_lists;
     if (sscanf(s, "%d %d %d %d %d %d %d %d %d %d", &M, &E, &K, &max_row, &few, &full, &max_devs, &forced, &f_cby, &f_lists) != 10) return 1;
     PlanInput in = plan_shape(M, E, K, max_row);
@@ -26,6 +27,7 @@ int main() {
     if (cur.fits())
       printf(" %d %d %d %d %d %d %d %d %d %d %d %d", cur.wpb, cur.wpb_fused, cur.wave_lds, cur.shared_lds, cur.lds_bytes, cur.in_lds,
              cur.x_bytes, cur.cby_global, cur.lists_global, cur.wide ? 1 : 0, cur.max_devs, cur.waves);
+    if (show_ct) printf(" ct=%d", in.ct);
     printf("\n");
   }
   return 0;

@@ -460,21 +460,121 @@ PLAN_TABLE = [
 ]
 
 
+def _plan_probe(tmp_path, lines):
+    """Build tests/plan_probe.cpp with the host compiler and return its answers to `lines`, one per line."""
+    import subprocess
+    exe = str(tmp_path / "plan_probe")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "cygym_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "plan_probe.cpp")])
+    out = subprocess.run([exe], input="".join(line + "\n" for line in lines), capture_output=True, text=True, check=True).stdout
+    return out.splitlines()
+
+
 def test_launch_planner_without_a_gpu(tmp_path):
     """The complete launch plan for a fixed table of inputs: the bench workloads (lean / full-feature, few_waves on / off),
     2048 devices with and without an extra-edge list, every forced workgroup shape and both placement hooks, the fall
     to the run-time kernels, M % 4 != 0, one device, inputs that fit no layout, and re-plans -- among them the failed
     re-plan of test_failed_replan_keeps_the_launch_plan, after which the old plan must still be in place."""
-    import subprocess
-    exe = str(tmp_path / "plan_probe")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "cygym_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "plan_probe.cpp")])
-    out = subprocess.run([exe], input="".join(line + "\n" for line, _ in PLAN_TABLE), capture_output=True, text=True, check=True).stdout
-    got = out.splitlines()
+    got = _plan_probe(tmp_path, [line for line, _ in PLAN_TABLE])
     assert len(got) == len(PLAN_TABLE)
     for (line, want), have in zip(PLAN_TABLE, got):
         print(line, "->", have)
         assert have == want, (line, have, want)
+
+
+# The networks of tests/test_size_edges_gpu.py (E, K and max_row as topology.make_topology gives them for its scenarios, the odd
+# list lengths it uses): odd and chunk-edge device counts on a free plan and with a forced workgroup shape, and 68 / 140 / 272
+# devices with comp_by (and the lists) forced into global memory.  '!': the probe also says whether the network runs on the
+# compile-time-size kernels.  The answers are plan_launch's own, recorded as it stands.
+SIZE_EDGE_PLANS = [
+    # 63-b1-lean
+    ('!63 303 0 62 1 0 7 0 0 0', '1 5 5 1040 1824 1824 1 0 0 0 0 7 20 ct=0'),
+    # 63-b1-full
+    ('!63 303 20 62 1 1 7 0 0 0', '1 5 5 1152 1824 1824 1 112 0 0 0 7 20 ct=0'),
+    # 63-b2-lean
+    ('!63 306 0 62 1 0 7 0 0 0', '1 5 5 1040 1840 1840 1 0 0 0 0 7 20 ct=0'),
+    # 63-b2-full
+    ('!63 306 20 62 1 1 7 0 0 0', '1 5 5 1152 1840 1840 1 112 0 0 0 7 20 ct=0'),
+    # 65-b1-lean
+    ('!65 313 0 64 1 0 9 0 0 0', '1 5 5 1472 1984 1984 1 0 0 0 0 9 20 ct=0'),
+    # 65-b1-full, 65-b1-full-det
+    ('!65 313 20 64 1 1 9 0 0 0', '1 5 5 1600 1984 1984 1 128 0 0 0 9 20 ct=0'),
+    # 65-b2-lean
+    ('!65 318 0 64 1 0 9 0 0 0', '1 5 5 1472 1984 1984 1 0 0 0 0 9 20 ct=0'),
+    # 65-b2-full
+    ('!65 318 20 64 1 1 9 0 0 0', '1 5 5 1600 1984 1984 1 128 0 0 0 9 20 ct=0'),
+    # 127-b1-full-K1
+    ('!127 995 1 126 1 1 15 0 0 0', '1 5 5 1920 4432 4432 1 48 0 0 0 15 20 ct=0'),
+    # 129-b3-lean
+    ('!129 1019 0 128 1 0 17 0 0 0', '1 5 5 2304 4608 4608 1 0 0 0 0 17 20 ct=0'),
+    # 129-b3-full, 129-b3-full-X5, 129-b3-full-det
+    ('!129 1019 32 128 1 1 17 0 0 0', '1 5 5 2496 4608 4608 1 192 0 0 0 17 20 ct=0'),
+    # 191-b2-full-K31
+    ('!191 2278 31 190 1 1 23 0 0 0', '1 5 5 3056 8208 8208 1 192 0 0 0 23 20 ct=0'),
+    # 255-b1-full-K65-X5
+    ('!255 3783 65 254 1 1 31 0 0 0', '1 5 5 4272 12432 12432 1 352 0 0 0 31 20 ct=0'),
+    # 257-b1-lean
+    ('!257 3813 0 256 1 0 33 0 0 0', '1 5 5 4352 12624 12624 1 0 0 0 0 33 20 ct=0'),
+    # 257-b1-full
+    ('!257 3813 60 256 1 1 33 0 0 0', '1 5 5 4688 12624 12624 1 336 0 0 0 33 20 ct=0'),
+    # 1025-b8-full-K100
+    ('!1025 3531 100 105 1 1 129 0 0 0', '1 5 5 13040 14320 14320 0 688 0 0 0 129 10 ct=0'),
+    # 2047-b16-lean
+    ('!2047 9122 0 156 1 0 255 0 0 0', '1 5 5 24080 32592 32592 0 0 0 0 0 255 5 ct=0'),
+    # 2047-b16-full
+    ('!2047 9122 416 156 1 1 255 0 0 0', '1 4 4 26320 57168 57168 1 2240 0 0 0 255 4 ct=0'),
+    # 129-b3-lean-wpb1
+    ('!129 1019 0 128 1 0 17 1 0 0', '1 1 1 2304 4608 4608 1 0 0 0 0 17 20 ct=0'),
+    # 129-b3-full-wpb1
+    ('!129 1019 32 128 1 1 17 1 0 0', '1 1 1 2496 4608 4608 1 192 0 0 0 17 20 ct=0'),
+    # 129-b3-lean-wpb5
+    ('!129 1019 0 128 1 0 17 5 0 0', '1 5 5 2304 4608 4608 1 0 0 0 0 17 20 ct=0'),
+    # 129-b3-full-wpb5
+    ('!129 1019 32 128 1 1 17 5 0 0', '1 5 5 2496 4608 4608 1 192 0 0 0 17 20 ct=0'),
+    # 129-b3-lean-wpb16
+    ('!129 1019 0 128 1 0 17 16 0 0', '1 16 16 2304 4608 4608 1 0 0 0 0 17 16 ct=0'),
+    # 129-b3-full-wpb16
+    ('!129 1019 32 128 1 1 17 16 0 0', '1 16 16 2496 4608 4608 1 192 0 0 0 17 16 ct=0'),
+    # 68-b1-full-K33-cbyg-listsg
+    ('!68 328 33 67 1 1 9 0 1 1', '1 5 5 1408 1040 1040 0 32 1 1 0 9 20 ct=0'),
+    # 68-b1-full-K33-cbyg
+    ('!68 328 33 67 1 1 9 0 1 0', '1 5 5 1584 2000 2000 1 176 1 0 0 9 20 ct=0'),
+    # 140-b2-full-K33-cbyg-listsg
+    ('!140 1247 33 139 1 1 17 0 1 1', '1 5 5 2272 3216 3216 0 48 1 1 0 17 20 ct=0'),
+    # 140-b2-full-K33-cbyg
+    ('!140 1247 33 139 1 1 17 0 1 0', '1 5 5 2464 5184 5184 1 192 1 0 0 17 20 ct=0'),
+    # 272-b4-full-K33-cbyg-listsg
+    ('!272 4330 33 271 1 1 35 0 1 1', '1 5 5 4256 10048 10048 0 80 1 1 0 35 20 ct=0'),
+    # 272-b4-full-K33-cbyg
+    ('!272 4330 33 271 1 1 35 0 1 0', '1 5 5 4480 13872 13872 1 224 1 0 0 35 20 ct=0'),
+]
+
+
+def test_launch_planner_at_the_size_edges(tmp_path):
+    """The plans of the size-edge networks are pinned; none of them is a compile-time size; comp_by stays in LDS wherever
+    M % 4 != 0, whatever the hooks say; and every forced placement fits and is taken."""
+    got = _plan_probe(tmp_path, [line for line, _ in SIZE_EDGE_PLANS])
+    assert len(got) == len(SIZE_EDGE_PLANS)
+    sizes = set()
+    for (line, want), have in zip(SIZE_EDGE_PLANS, got):
+        print(line, "->", have)
+        assert have == want, (line, have, want)
+        M, _, _, _, _, _, _, _, f_cby, f_lists = (int(x) for x in line.lstrip("!").split())
+        plan, ct = have.split(" ct=")
+        fits, _, _, _, _, _, _, _, cby_global, lists_global, wide, _, _ = (int(x) for x in plan.split())
+        sizes.add(M)
+        assert ct == "0" and not wide, (line, "a compile-time size")
+        assert fits == 1, (line, "does not fit")
+        if M % 4:
+            assert cby_global == 0 and lists_global == 0, (line, "comp_by left in global memory at M % 4 != 0")
+        if f_cby:
+            assert cby_global == 1, (line, "the forced placement of comp_by was not taken")
+        if f_lists:
+            assert lists_global == 1, (line, "the forced placement of the lists was not taken")
+    assert sizes == {63, 65, 127, 129, 191, 255, 257, 1025, 2047, 68, 140, 272}
+    # the hook on an odd size, asked for outright: not applicable
+    odd = _plan_probe(tmp_path, [f"!{line.lstrip('!').rsplit(' ', 2)[0]} 1 1" for line, _ in SIZE_EDGE_PLANS if int(line.lstrip("!").split()[0]) % 2])
+    assert odd and all(int(a.split()[8]) == 0 and int(a.split()[9]) == 0 for a in odd), odd
 
 
 def _create(topo, cfg, n=4):
