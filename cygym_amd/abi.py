@@ -153,6 +153,17 @@ class HierNet(C.Structure):
                 ("dev_logits_out", C.c_void_p), ("n_parts", C.c_int32), ("role", C.c_int32), ("H", C.c_int32), ("h0_stride", C.c_int32)]
 
 
+class HierSample(C.Structure):
+    _fields_ = [("part_out", C.c_void_p), ("atype_out", C.c_void_p), ("dec_out", C.c_void_p)]
+
+
+class HierLoss(C.Structure):
+    _fields_ = [("score", C.c_void_p), ("atype_logits", C.c_void_p), ("dev_logits", C.c_void_p), ("vis", C.c_void_p), ("part_of", C.c_void_p),
+                ("part", C.c_void_p), ("atype", C.c_void_p), ("dec", C.c_void_p), ("stats", C.c_void_p), ("g_stats", C.c_void_p),
+                ("grad_score", C.c_void_p), ("grad_atype_logits", C.c_void_p), ("grad_dev_logits", C.c_void_p),
+                ("n", C.c_int32), ("M", C.c_int32), ("T", C.c_int32), ("n_parts", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

@@ -799,6 +799,13 @@ class BatchedCyberDefenseEnv:
           outputs    optional, contiguous: score_out [n, M], part_score_out [n, n_parts], atype_logits_out [n, T], dev_logits_out [n, M]
                      float32, part_out [n] int32 (the chosen part; -1 / -2: the fallbacks)
         Limits: H a multiple of 16 in 16..256, T <= 32, M <= 2048, 1..255 parts (the library answers CYGYM_EUNSUPPORTED / CYGYM_EINVAL)."""
+        self._hier(None, rows, h0, pack, role, act, vis_fixed, type_map, score_out=score_out, part_score_out=part_score_out, part_out=part_out,
+                   atype_logits_out=atype_logits_out, dev_logits_out=dev_logits_out)
+
+    def _hier(self, sample, rows, h0, pack, role, act, vis_fixed, type_map, score_out=None, part_score_out=None, part_out=None,
+              atype_logits_out=None, dev_logits_out=None):
+        """The marshalling hier_decode and hier_sample_decode share: the cygym_hier_net of the arguments, then cygym_hier_decode
+        (sample is None) or cygym_hier_sample_decode with the abi.HierSample `sample`."""
         dst = self.actions_struct(act)
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
         if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
@@ -836,7 +843,74 @@ class BatchedCyberDefenseEnv:
                 if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
                     raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
                 setattr(net, name, t.data_ptr())
+        if sample is not None:
+            _lib.check(self.lib.cygym_hier_sample_decode(self._h, C.byref(net), C.byref(sample), C.byref(src), C.byref(dst), self._stream()), self._h,
+                       "cygym_hier_sample_decode")
+            return
         _lib.check(self.lib.cygym_hier_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_hier_decode")
+
+    def hier_sample_decode(self, rows, h0: torch.Tensor, pack, role: str = "defender", act=None, vis_fixed=None, type_map=None, out=None, **logit_outs):
+        """The learner's SAMPLED decision of HierarchicalBestResponse.train (hierarchical_br.py:285-323, :172-231) for a batch, fused with
+        the scatter into rows `rows` of `act` (group 0): ONE launch (cygym_hier_sample_decode; include/cygym_abi.h states the decision).
+        Arguments as hier_decode (the optional logit outputs too, by keyword).  The part, the type and one Bernoulli per subset device
+        are drawn from addressed Philox draws (env, rng tick, SITE_HIER_PART / _TYPE / _DEV); the tick is read and not advanced.
+          out   optional (part [n] int32, atype [n] int32, dec [n, M] uint8) to write into
+        Returns (part, atype, dec): the drawn part (-1: the [0] subset), the type INDEX before type_map, and per device bit 0 = in the
+        subset, bit 1 = selected -- what HierarchicalNet.evaluate takes."""
+        n = int(h0.shape[0]) if h0.dim() == 2 else 0
+        shapes = (((n,), torch.int32), ((n,), torch.int32), ((n, self.M), torch.uint8))
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=dt, device=self.device) for sh, dt in shapes)
+        out = tuple(out)
+        if len(out) != 3 or any(t.dtype != dt or t.device != self.device or tuple(t.shape) != sh or not t.is_contiguous() for t, (sh, dt) in zip(out, shapes)):
+            raise ValueError(f"out must be contiguous (int32 [{n}], int32 [{n}], uint8 [{n}, {self.M}]) tensors on {self.device}")
+        smp = abi.HierSample()
+        smp.part_out, smp.atype_out, smp.dec_out = (t.data_ptr() for t in out)
+        self._hier(smp, rows, h0, pack, role, act, vis_fixed, type_map, **logit_outs)
+        return out
+
+    def _hier_loss(self, score, atype_logits, dev_logits, vis, part_of, n_parts, part, atype, dec):
+        f32 = lambda t: t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()  # noqa: E731
+        if not f32(score) or score.dim() != 2:
+            raise ValueError("score must be a contiguous float32 [n, M] tensor on the batch's device")
+        n, M = (int(x) for x in score.shape)
+        if not f32(atype_logits) or atype_logits.dim() != 2 or int(atype_logits.shape[0]) != n:
+            raise ValueError(f"atype_logits must be a contiguous float32 [{n}, T] tensor on {self.device}")
+        T = int(atype_logits.shape[1])
+        if not f32(dev_logits) or tuple(dev_logits.shape) != (n, M):
+            raise ValueError(f"dev_logits must be a contiguous float32 [{n}, {M}] tensor on {self.device}")
+        for name, t, shape, dt in (("vis", vis, (n, M), torch.uint8), ("dec", dec, (n, M), torch.uint8), ("part_of", part_of, (M,), torch.uint8),
+                                   ("part", part, (n,), torch.int32), ("atype", atype, (n,), torch.int32)):
+            if t.dtype != dt or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
+        e = abi.HierLoss()
+        e.score, e.atype_logits, e.dev_logits, e.vis, e.part_of, e.part, e.atype, e.dec = (
+            t.data_ptr() for t in (score, atype_logits, dev_logits, vis, part_of, part, atype, dec))
+        e.n, e.M, e.T, e.n_parts = n, M, T, int(n_parts)
+        return e, (n, M, T)
+
+    def hier_loss(self, score, atype_logits, dev_logits, vis, part_of, n_parts, part, atype, dec):
+        """The head of the HAGS REINFORCE update for n STORED decisions in ONE launch (cygym_hier_loss; include/cygym_abi.h states the
+        formulas): stats [n, 6] = logp_hi, ent_hi, logp_at, ent_at, logp_dev, ent_dev from the three logit tensors (score [n, M],
+        atype_logits [n, T], dev_logits [n, M], float32, the latter two through nan_to_num), the stored visibility vis [n, M] uint8,
+        part_of [M] uint8 / n_parts, and the stored decision (part, atype int32 [n], dec uint8 [n, M]: hier_sample_decode)."""
+        e, (n, M, T) = self._hier_loss(score, atype_logits, dev_logits, vis, part_of, n_parts, part, atype, dec)
+        stats = torch.empty((n, 6), dtype=torch.float32, device=self.device)
+        e.stats = stats.data_ptr()
+        _lib.check(self.lib.cygym_hier_loss(self._h, C.byref(e), self._stream()), self._h, "cygym_hier_loss")
+        return stats
+
+    def hier_loss_backward(self, score, atype_logits, dev_logits, vis, part_of, n_parts, part, atype, dec, g_stats):
+        """The backward of hier_loss (cygym_hier_loss_backward, one launch, row-local): g_stats [n, 6] float32 ->
+        (grad_score [n, M], grad_atype_logits [n, T], grad_dev_logits [n, M]), exactly 0 outside the visible / subset devices."""
+        e, (n, M, T) = self._hier_loss(score, atype_logits, dev_logits, vis, part_of, n_parts, part, atype, dec)
+        if g_stats.dtype != torch.float32 or g_stats.device != self.device or tuple(g_stats.shape) != (n, 6):
+            raise ValueError(f"g_stats must be a float32 [{n}, 6] tensor on {self.device}")
+        g = g_stats.contiguous()
+        gs, ga, gd = (torch.empty(sh, dtype=torch.float32, device=self.device) for sh in ((n, M), (n, T), (n, M)))
+        e.g_stats, e.grad_score, e.grad_atype_logits, e.grad_dev_logits = g.data_ptr(), gs.data_ptr(), ga.data_ptr(), gd.data_ptr()
+        _lib.check(self.lib.cygym_hier_loss_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_hier_loss_backward")
+        return gs, ga, gd
 
     def _comm_eval(self, tok_base, tok_dev, w_type, b_type, types, vis, backward: bool):
         """The CommEval struct of comm_actor_evaluate / comm_actor_evaluate_backward from the factorised inputs, and what has to

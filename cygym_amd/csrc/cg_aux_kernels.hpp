@@ -1,8 +1,9 @@
 // cg_aux_kernels.hpp -- reset / randomize / derive / observe kernels and the synthetic action script of bench.py.
 // Part of the device code gathered by cg_device.hpp (included inside namespace cygym_k, in order); not a standalone header.
-// The plain (non-template) kernels are defined in the C-ABI unit only (CG_MAIN_UNIT).  group_row and sample_head are force-inlined
-// device functions that comm_actor_kernel (cg_comm_actor.hpp, included at the end) shares with the kernels here: its instantiation
-// unit (cg_inst_comm.hip) includes this file without CG_MAIN_UNIT and sees those two and the template only.
+// The plain (non-template) kernels are defined in the C-ABI unit only (CG_MAIN_UNIT).  group_row is a force-inlined
+// device function that comm_actor_kernel (cg_comm_actor.hpp, included at the end) shares with the kernels here (sample_head, the other
+// one, lives in cg_decode.hpp): its instantiation unit (cg_inst_comm.hip) includes this file without CG_MAIN_UNIT and sees it and the
+// template only.
 #ifndef CG_AUX_KERNELS_HPP
 #define CG_AUX_KERNELS_HPP
 
@@ -257,24 +258,6 @@ __global__ void group_actions_kernel(cygym_device_types src, cygym_actions dst, 
 // cygym_sample_group_actions (IPPO.py:524-572 for a batch): one wave per row, a lane per device.  Sampling = the inverse CDF
 // of softmax(logits) walked with u = addressed Philox draw / 2^32; the sampled types stay in LDS for the grouping.
 constexpr int SAMPLE_WPB = 4;
-#endif  // CG_MAIN_UNIT
-__device__ __forceinline__ int sample_head(const float* l, const int K, const uint32_t u32, const bool greedy, float& logp) {
-  float mx = -__builtin_inff();
-  int am = 0;
-  for (int k = 0; k < K; ++k) { const float x = l[k]; if (x > mx) { mx = x; am = k; } }   // (first maximum)
-  float S = 0.f;
-  for (int k = 0; k < K; ++k) S += __expf(l[k] - mx);
-  int pick = am;
-  if (!greedy) {
-    const float target = (float)u32 * (1.0f / 4294967296.0f) * S;
-    float acc = 0.f;
-    pick = K - 1;
-    for (int k = 0; k < K; ++k) { acc += __expf(l[k] - mx); if (acc > target) { pick = k; break; } }
-  }
-  logp = l[pick] - mx - __logf(S);
-  return pick;
-}
-#ifdef CG_MAIN_UNIT
 __global__ __launch_bounds__(SAMPLE_WPB * WAVE) void sample_group_actions_kernel(cygym_device_logits src, cygym_actions dst, int M, int n_envs,
                                                                                  const uint8_t* live, const int32_t* ienv, uint64_t seed,
                                                                                  int64_t env_id_base) {

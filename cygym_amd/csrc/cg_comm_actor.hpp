@@ -1,6 +1,6 @@
 // cg_comm_actor.hpp -- cygym_comm_actor_decode: the per-device actor-critic of the reference's IPPO / MAPPO agents
 // (CommActorCritic.forward with USE_GAT off, IPPO.py:135-196), the sampling (:524-557) and the grouping (:560-572) for a batch,
-// in ONE launch.  Included at the end of cg_aux_kernels.hpp (after group_row and sample_head); instantiated in cg_inst_comm.hip.
+// in ONE launch.  Included at the end of cg_aux_kernels.hpp (after group_row; sample_head: cg_decode.hpp); instantiated in cg_inst_comm.hip.
 //
 // A workgroup of 16 waves owns 16 source rows, wave w the row 16 b + w.  With a = tok_base[row] and P = tok_dev:
 //   * ctx: the table P is walked in chunks of 64 devices, staged through LDS once per workgroup (two buffers, the next chunk's

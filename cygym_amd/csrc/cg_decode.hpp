@@ -128,6 +128,24 @@ __device__ __forceinline__ void head_decode_row(const float* outs_row, const flo
   decode_row_regs<HEAD_OPL>(v, row, tick, [&](int at) { return src.n_types <= WAVE ? __shfl(tmap, at) : (src.type_map ? src.type_map[at] : at); },
                             src, dst, lane, seed, env_id_base);
 }
+// One Categorical draw by the inverse CDF of softmax(l[0 .. K-1]), walked with u = u32 / 2^32 (greedy: the first maximum), and its
+// log-probability: cygym_sample_group_actions, cygym_comm_actor_decode, the type draw of cygym_hier_sample_decode.
+__device__ __forceinline__ int sample_head(const float* l, const int K, const uint32_t u32, const bool greedy, float& logp) {
+  float mx = -__builtin_inff();
+  int am = 0;
+  for (int k = 0; k < K; ++k) { const float x = l[k]; if (x > mx) { mx = x; am = k; } }   // (first maximum)
+  float S = 0.f;
+  for (int k = 0; k < K; ++k) S += __expf(l[k] - mx);
+  int pick = am;
+  if (!greedy) {
+    const float target = (float)u32 * (1.0f / 4294967296.0f) * S;
+    float acc = 0.f;
+    pick = K - 1;
+    for (int k = 0; k < K; ++k) { acc += __expf(l[k] - mx); if (acc > target) { pick = k; break; } }
+  }
+  logp = l[pick] - mx - __logf(S);
+  return pick;
+}
 
 #include "cg_actor_mlp.hpp"
 #include "cg_coord_ascent.hpp"

@@ -3,7 +3,7 @@
 // logits of the visible devices only.
 #include "cg_device.hpp"
 namespace cygym_k {
-#include "cg_aux_kernels.hpp"   // (without CG_MAIN_UNIT: group_row, sample_head and the template, none of the plain kernels)
+#include "cg_aux_kernels.hpp"   // (without CG_MAIN_UNIT: group_row and the template, none of the plain kernels)
 template __global__ void comm_actor_kernel<false>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 template __global__ void comm_actor_kernel<true>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 }  // namespace cygym_k

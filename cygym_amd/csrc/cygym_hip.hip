@@ -74,6 +74,10 @@ extern template __global__ void comm_actor_kernel<true>(cygym_comm_actor, cygym_
 namespace cygym_k {
 extern template __global__ void hier_kernel<false>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 extern template __global__ void hier_kernel<true>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+extern template __global__ void hier_kernel<false, true>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int, cygym_hier_sample);
+extern template __global__ void hier_kernel<true, true>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int, cygym_hier_sample);
+extern template __global__ void hier_loss_kernel<false>(cygym_hier_loss_desc);
+extern template __global__ void hier_loss_kernel<true>(cygym_hier_loss_desc);
 }  // namespace cygym_k
 
 // the evaluate / backward kernels of the PPO update live in their own unit (cg_inst_eval.hip): declared, not instantiated, here
@@ -231,6 +235,8 @@ int cygym_sizeof(int32_t which) {
     case 14: return (int)sizeof(cygym_comm_eval);   // (13 stays unassigned: -1)
     case 16: return (int)sizeof(cygym_critic_tail_desc);   // (15 stays unassigned too: earlier bindings probe it for -1)
     case 17: return (int)sizeof(cygym_hier_net);
+    case 19: return (int)sizeof(cygym_hier_sample);   // (index 18 stays unassigned)
+    case 20: return (int)sizeof(cygym_hier_loss_desc);
     default: return -1;
   }
 }
@@ -859,32 +865,67 @@ int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const 
   return launch_decode(h, k, dim3((src->n + CM_WAVES - 1) / CM_WAVES), dim3(CM_THREADS), lds, stream, {net, src, dst}, {&live, &M});   // 16 rows per workgroup
 }
 
-int cygym_hier_decode(cygym_handle* h, const cygym_hier_net* net, const cygym_action_vectors* src, const cygym_actions* dst, void* stream) {
-  const char* const who = "cygym_hier_decode";
-  const char* const bad_layout = "cygym_hier_decode: bad layout (types >= 1, the handle's device count, 1 .. 255 parts, role 1 or 2, h0_stride >= 3 H, 16-byte aligned packed matrices / w_mask_t)%s";
+// cygym_hier_decode (smp == NULL) and cygym_hier_sample_decode: one argument check, one launch shape.
+static int hier_launch(cygym_handle* h, const cygym_hier_net* net, const cygym_hier_sample* smp, bool sample, const cygym_action_vectors* src,
+                       const cygym_actions* dst, void* stream, const char* who, const char* bad_layout) {
   const bool own = net && net->h0 && net->w_mask_t && net->w_score && net->b_score && net->w_act2 && net->b_act2 && net->w_dev2 && net->b_dev2 &&
-                   net->w_act_head && net->b_act_head && net->w_dev_head && net->b_dev_head && net->part_of;
+                   net->w_act_head && net->b_act_head && net->w_dev_head && net->b_dev_head && net->part_of &&
+                   (!sample || (smp && smp->part_out && smp->atype_out && smp->dec_out));
   if (const int rc = check_vectors(h, src, dst, who, own, 0, bad_layout)) return rc;
   if (src->n_types < 1 || net->n_parts < 1 || net->n_parts > HR_MAX_PARTS || (net->role != 1 && net->role != 2) || net->H < 1 ||
       (long long)net->h0_stride < 3ll * net->H ||
       (((uintptr_t)net->w_mask_t | (uintptr_t)net->w_score | (uintptr_t)net->w_act2 | (uintptr_t)net->w_dev2 | (uintptr_t)net->w_act_head | (uintptr_t)net->w_dev_head) & 15))
     return fail(h, CYGYM_EINVAL, bad_layout, "");
   if (net->H < 16 || net->H > HR_MAX_H || (net->H & 15) || src->n_types > HR_MAX_T || h->t.M > HR_MAX_M)
-    return fail(h, CYGYM_EUNSUPPORTED, "cygym_hier_decode: H must be a multiple of 16 in 16 .. 256, at most 32 action types, at most 2048 devices%s", "");
-  if (!net->vis_fixed && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_hier_decode: handle not bound (without vis_fixed the visibility mask is read off the flag plane)%s", "");
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: H must be a multiple of 16 in 16 .. 256, at most 32 action types, at most 2048 devices", who);
+  if (sample && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (the draws are addressed by the envs' rng ticks)", who);
+  if (!net->vis_fixed && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (without vis_fixed the visibility mask is read off the flag plane)", who);
   if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   const HrPlan pl = hr_plan(net->H, h->t.M);
   const size_t lds = (size_t)pl.total * sizeof(float);
-  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_hier_decode: the tiles do not fit in LDS%s", "");
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the tiles do not fit in LDS", who);
   const bool outs = net->score_out || net->part_score_out || net->part_out || net->atype_logits_out || net->dev_logits_out;
-  const void* k = outs ? (const void*)hier_kernel<true> : (const void*)hier_kernel<false>;
+  const void* k = sample ? (outs ? (const void*)hier_kernel<true, true, cygym_hier_sample> : (const void*)hier_kernel<false, true, cygym_hier_sample>)
+                         : (outs ? (const void*)hier_kernel<true> : (const void*)hier_kernel<false>);
   if (const int rc = raise_lds_once(h, k)) return rc;
   const uint8_t* live = h->bound ? (const uint8_t*)h->b.live : nullptr;
   int M = h->t.M;
-  return launch_decode(h, k, dim3((src->n + HR_WAVES - 1) / HR_WAVES), dim3(HR_THREADS), lds, stream, {net, src, dst}, {&live, &M});   // 16 rows per workgroup
+  const dim3 grid((src->n + HR_WAVES - 1) / HR_WAVES);   // 16 rows per workgroup
+  if (sample) return launch_decode(h, k, grid, dim3(HR_THREADS), lds, stream, {net, src, dst}, {&live, &M, smp});
+  return launch_decode(h, k, grid, dim3(HR_THREADS), lds, stream, {net, src, dst}, {&live, &M});
 }
+
+int cygym_hier_decode(cygym_handle* h, const cygym_hier_net* net, const cygym_action_vectors* src, const cygym_actions* dst, void* stream) {
+  return hier_launch(h, net, nullptr, false, src, dst, stream, "cygym_hier_decode",
+                     "cygym_hier_decode: bad layout (types >= 1, the handle's device count, 1 .. 255 parts, role 1 or 2, h0_stride >= 3 H, 16-byte aligned packed matrices / w_mask_t)%s");
+}
+
+int cygym_hier_sample_decode(cygym_handle* h, const cygym_hier_net* net, const cygym_hier_sample* smp, const cygym_action_vectors* src,
+                             const cygym_actions* dst, void* stream) {
+  return hier_launch(h, net, smp, true, src, dst, stream, "cygym_hier_sample_decode",
+                     "cygym_hier_sample_decode: bad layout (types >= 1, the handle's device count, 1 .. 255 parts, role 1 or 2, h0_stride >= 3 H, 16-byte aligned packed matrices / w_mask_t)%s");
+}
+
+static int hier_loss_launch(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream, bool bwd, const char* who) {
+  if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
+  if (!e || !e->score || !e->atype_logits || !e->dev_logits || !e->vis || !e->part_of || !e->part || !e->atype || !e->dec ||
+      (bwd ? !(e->g_stats && e->grad_score && e->grad_atype_logits && e->grad_dev_logits) : !e->stats))
+    return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (e->n < 1 || e->M < 1 || e->T < 1 || e->n_parts < 1 || e->n_parts > HR_MAX_PARTS)
+    return fail(h, CYGYM_EINVAL, "%s: bad layout (n, M, T >= 1, 1 .. 255 parts)", who);
+  if (e->T > HR_MAX_T || e->M > HR_MAX_M) return fail(h, CYGYM_EUNSUPPORTED, "%s: at most 32 action types, at most 2048 devices", who);
+  HIPCHK(h, hipSetDevice(h->device_id));
+  cygym_hier_loss_desc arg = *e;
+  void* args[1] = {&arg};
+  const void* k = bwd ? (const void*)hier_loss_kernel<true> : (const void*)hier_loss_kernel<false>;
+  HIPCHK(h, hipLaunchKernel(k, dim3((e->n + HL_WPB - 1) / HL_WPB), dim3(HL_WPB * WAVE), args, 0, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+int cygym_hier_loss(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream) { return hier_loss_launch(h, e, stream, false, "cygym_hier_loss"); }
+int cygym_hier_loss_backward(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream) { return hier_loss_launch(h, e, stream, true, "cygym_hier_loss_backward"); }
 
 // What the two evaluate calls check alike, in the order of the decodes' shared check: handle, pointers, layout (CYGYM_EINVAL),
 // then the implemented range (CYGYM_EUNSUPPORTED).

@@ -95,6 +95,81 @@ def _sample(logits: torch.Tensor, greedy: bool, generator):
     return idx, torch.gather(logp_all, -1, idx.unsqueeze(-1)).squeeze(-1)
 
 
+class Turns:
+    """The scaffolding of a learner's rollout loop on a batch whose envs tick in lock step, shared by collect() and
+    hier_rollout.train: whose turn it is (the defender moves on even step_num), the mode word with a baseline opponent's persisting
+    env.base_line, the opponent's action, the tick with the view of whoever moves next, and the episode cap with batch.randomize().
+        t = Turns(batch, role, opponent)
+        while ...:
+            turn, obs = t.begin()
+            if turn == role: <write the learner's action into t.act>
+            else: t.opponent(obs)
+            _, raw, shaped, done = t.step()
+            ...
+            t.advance(randomize_on_reset)"""
+
+    def __init__(self, batch, role: str, opponent):
+        from .rollout_grid import SequencePolicy, _baseline_code
+        if role not in (HL.DEFENDER, HL.ATTACKER):
+            raise ValueError("role must be 'attacker' or 'defender'")
+        other = HL.ATTACKER if role == HL.DEFENDER else HL.DEFENDER
+        N, dev = batch.N, batch.device
+        self.batch, self.role = batch, role
+        self.opp = opponent if (callable(opponent) or hasattr(opponent, "write")) else SequencePolicy(opponent, other)
+        # a baseline opponent sets env.base_line on its turn and nobody resets it (IPPO.py:395-397): from then on EVERY tick runs
+        # under that baseline (volt_typhoon_env.py:847-874, :913-914) -- carried in the mode word like the reference's loops do
+        self.bl_code = _baseline_code(opponent, other)
+        self.cur_bl = None
+        step_num = batch.state["ienv"][:, S.I_STEP_NUM]
+        s0 = int(step_num[0].item())
+        if not bool((step_num == s0).all().item()):
+            raise ValueError("the envs of the batch must share their step_num (they tick in lock step)")
+        self.cap = int(batch.cfg.episode_limit)                           # done iff step_num > cap (CyberDefenseEnv.py:547-552)
+        if not batch.cfg.auto_reset:
+            raise ValueError("create the batch with auto_reset=1: a done env starts over (IPPO.py:613-624)")
+        self.rows_all = torch.arange(N, dtype=torch.int32, device=dev)
+        self.act = batch.act
+        self.mode_word = {HL.DEFENDER: torch.full((N,), S.MODE_DEFENDER, dtype=torch.int32, device=dev),
+                          HL.ATTACKER: torch.full((N,), S.MODE_ATTACKER, dtype=torch.int32, device=dev)}
+        self.s, self.ticks = s0, 0
+        batch.prime_view(HL.DEFENDER if s0 % 2 == 0 else HL.ATTACKER)
+
+    def begin(self):
+        """(whose turn, its role view); the mode word of the tick is written."""
+        turn = HL.DEFENDER if self.s % 2 == 0 else HL.ATTACKER
+        obs = self.batch.role_obs[turn]
+        if turn != self.role and self.bl_code >= 0:
+            self.cur_bl = self.bl_code
+        self.act["mode"].copy_(self.mode_word[turn])
+        if self.cur_bl is not None:
+            self.act["mode"] |= (self.cur_bl + 1) << S.MODE_BASELINE_SHIFT
+        return turn, obs
+
+    def opponent(self, obs):
+        batch, act, opp, s = self.batch, self.act, self.opp, self.s
+        act["n_groups"].zero_()
+        if hasattr(opp, "write"):
+            opp.write(batch, act, self.rows_all, obs)
+        else:
+            a = opp(obs, s if getattr(opp, "uses_global_tick", False) else s // 2, batch.M, batch.L)
+            batch.write_actions(self.rows_all, a, act)
+
+    def step(self):
+        nxt = HL.DEFENDER if (self.s + 1) % 2 == 0 else HL.ATTACKER
+        if self.s + 1 > self.cap:  # this tick reports done: every env reloads its snapshot (step_num 0: a defender turn)
+            nxt = HL.DEFENDER
+        return self.batch.step(self.act, view=nxt, full_obs=False)
+
+    def advance(self, randomize_on_reset: bool = True):
+        self.s += 1
+        self.ticks += 1
+        if self.s > self.cap:
+            self.s = 0
+            if randomize_on_reset:
+                self.batch.randomize()                                      # :615-616
+                self.batch.prime_view(HL.DEFENDER)                          # (the reshuffle changed the state the view was written from)
+
+
 @torch.no_grad()
 def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool = False, generator=None, n_types: int | None = None,
             randomize_on_reset: bool = True, max_ticks: int | None = None, fused_sampling: bool = True, fused_net: bool | None = None) -> Rollout:
@@ -118,41 +193,14 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
         raise ValueError("fused_net needs a policies.CommActorCritic")
     if fused and n_types is not None and int(n_types) != net.n_types:
         raise ValueError(f"the net has {net.n_types} action types, n_types = {n_types}")
-    from .rollout_grid import SequencePolicy, _baseline_code
-    if role not in (HL.DEFENDER, HL.ATTACKER):
-        raise ValueError("role must be 'attacker' or 'defender'")
-    other = HL.ATTACKER if role == HL.DEFENDER else HL.DEFENDER
-    N, M, L, dev = batch.N, batch.M, batch.L, batch.device
+    turns = Turns(batch, role, opponent)
+    N, dev = batch.N, batch.device
     noop = DEFENDER_NOOP if role == HL.DEFENDER else ATTACKER_NOOP
-    opp = opponent if (callable(opponent) or hasattr(opponent, "write")) else SequencePolicy(opponent, other)
-    # a baseline opponent sets env.base_line on its turn and nobody resets it (IPPO.py:395-397): from then on EVERY tick runs
-    # under that baseline (volt_typhoon_env.py:847-874, :913-914) -- carried in the mode word like the reference's loops do
-    bl_code = _baseline_code(opponent, other)
-    cur_bl = None
-    step_num = batch.state["ienv"][:, S.I_STEP_NUM]
-    s0 = int(step_num[0].item())
-    if not bool((step_num == s0).all().item()):
-        raise ValueError("the envs of the batch must share their step_num (they tick in lock step)")
-    cap = int(batch.cfg.episode_limit)                                # done iff step_num > cap (CyberDefenseEnv.py:547-552)
-    if not batch.cfg.auto_reset:
-        raise ValueError("create the batch with auto_reset=1: a done env starts over (IPPO.py:613-624)")
-    rows_all = torch.arange(N, dtype=torch.int32, device=dev)
-    act = batch.act
+    act = turns.act
     rec = {k: [] for k in ("state", "logp", "value", "reward", "raw_reward", "done", "per_dev_types", "exp", "app", "vis_mask")}
-    mode_word = {HL.DEFENDER: torch.full((N,), S.MODE_DEFENDER, dtype=torch.int32, device=dev),
-                 HL.ATTACKER: torch.full((N,), S.MODE_ATTACKER, dtype=torch.int32, device=dev)}
-    s, ticks = s0, 0
-    turn = HL.DEFENDER if s % 2 == 0 else HL.ATTACKER
-    batch.prime_view(turn)
     limit = max_ticks if max_ticks is not None else 4 * n_decisions + 8
-    while len(rec["logp"]) < n_decisions and ticks < limit:
-        turn = HL.DEFENDER if s % 2 == 0 else HL.ATTACKER
-        obs = batch.role_obs[turn]
-        if turn != role and bl_code >= 0:
-            cur_bl = bl_code
-        act["mode"].copy_(mode_word[turn])
-        if cur_bl is not None:
-            act["mode"] |= (cur_bl + 1) << S.MODE_BASELINE_SHIFT
+    while len(rec["logp"]) < n_decisions and turns.ticks < limit:
+        turn, obs = turns.begin()
         if turn == role:
             vis = batch.visibility_mask(role)
             if fused:
@@ -190,28 +238,14 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
                 batch.group_actions(None, types, exp_i, app_i, role, n_types=K, noop=noop, single_types=SINGLE_DEVICE_TYPES, act=act)
             state_rec = obs.clone()
         else:
-            act["n_groups"].zero_()
-            if hasattr(opp, "write"):
-                opp.write(batch, act, rows_all, obs)
-            else:
-                a = opp(obs, s if getattr(opp, "uses_global_tick", False) else s // 2, M, L)
-                batch.write_actions(rows_all, a, act)
-        nxt = HL.DEFENDER if (s + 1) % 2 == 0 else HL.ATTACKER
-        if s + 1 > cap:            # this tick reports done: every env reloads its snapshot (step_num 0: a defender turn)
-            nxt = HL.DEFENDER
-        _, raw, shaped, done = batch.step(act, view=nxt, full_obs=False)
+            turns.opponent(obs)
+        _, raw, shaped, done = turns.step()
         if turn == role:
             rec["state"].append(state_rec); rec["logp"].append(logp); rec["value"].append(out["value"].reshape(N).float())
             rec["reward"].append(torch.where(torch.isfinite(shaped), shaped, raw.nan_to_num(0.0, 0.0, 0.0)).to(torch.float32).clamp(-1e6, 1e6)); rec["raw_reward"].append(raw.clone())   # (IPPO.py:575-581: a non-finite shaped reward falls back to nan_to_num(raw))
             rec["done"].append(done != 0); rec["per_dev_types"].append(types); rec["exp"].append(exp_i); rec["app"].append(app_i)
             rec["vis_mask"].append(vis)
-        s += 1
-        ticks += 1
-        if s > cap:
-            s = 0
-            if randomize_on_reset:
-                batch.randomize()                                           # :615-616
-                batch.prime_view(HL.DEFENDER)                               # (the reshuffle changed the state the view was written from)
+        turns.advance(randomize_on_reset)
     if not rec["logp"]:
         raise RuntimeError("no decision of the role within the tick limit")
     last_state = batch.observe(1 if role == HL.DEFENDER else 2)

@@ -20,6 +20,8 @@ answers with GROUPS of devices per action type; the batch evaluates the network,
 `HierarchicalNet` / `HierarchicalPolicy` are the fourth: the HAGS best response of hierarchical_br.py (`--BR_type hierarchical`) --
 a score net picks one part of the partitioned graph, a two-stage net picks the action type and the devices inside that part's
 visible subset (HierarchicalBestResponse.execute, :419-494); the batch does it in one addmm plus one launch (cygym_hier_decode).
+HierarchicalNet.logits / .evaluate are the differentiable side: the REINFORCE update of hier_rollout.train (:246-416) evaluates a
+stored sampled decision through them (the loss head as cygym_hier_loss / _backward).
 """
 from __future__ import annotations
 
@@ -768,6 +770,25 @@ class _TwoStage(nn.Module):
 NO_PART = 0xFF      # part_of entry of a device that belongs to no part
 
 
+class _HierLoss(torch.autograd.Function):
+    """cygym_hier_loss and its backward as one differentiable op: (score, atype_logits, dev_logits) -> stats [n, 6] for a stored
+    decision.  Nothing but the inputs is kept for backward: the kernel recomputes."""
+
+    @staticmethod
+    def forward(ctx, batch, vis, part_of, n_parts, part, atype, dec, score, atype_logits, dev_logits):
+        ins = tuple(t.detach().contiguous() for t in (score, atype_logits, dev_logits))
+        ctx.batch, ctx.n_parts = batch, n_parts
+        ctx.save_for_backward(*ins, vis, part_of, part, atype, dec)
+        return batch.hier_loss(*ins, vis, part_of, n_parts, part, atype, dec)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_stats):
+        sc, al, dl, vis, part_of, part, atype, dec = ctx.saved_tensors
+        gs, ga, gd = ctx.batch.hier_loss_backward(sc, al, dl, vis, part_of, ctx.n_parts, part, atype, dec, g_stats.float())
+        return None, None, None, None, None, None, None, gs, ga, gd
+
+
 class HierarchicalNet(nn.Module):
     """The two networks of the reference's HAGS best response (hierarchical_br.py) with the reference's parameter names, so that
     the two state dicts of `strategy.type_mapping["hierarchical"]` load unchanged (load_strategy):
@@ -832,6 +853,76 @@ class HierarchicalNet(nn.Module):
         sel = torch.where(sel.any(dim=1)[:, None], sel, torch.arange(M, device=dev)[None] == fb[:, None])
         return {"atype": torch.argmax(at_logits, dim=1), "dev_mask": sel, "part": part, "subset": sub, "score": score,
                 "part_scores": pscore, "atype_logits": at_logits, "dev_logits": dev_logits}
+
+    def logits(self, state, subset, dtype=None):
+        """The differentiable torch forward of the three logit tensors -- the body of decide() without the decision: state [B, state_dim],
+        subset [B, M] (bool or 0/1: the mask dev_body.0 reads) -> (score [B, M], atype_logits [B, T], dev_logits [B, M]) in `dtype`
+        (default: the state's) from the same fp32 parameters, the latter two through nan_to_num (:112-115)."""
+        dt = state.dtype if dtype is None else dtype
+        s = state.to(dt)
+        sn, ts = self.score_net, self.two_stage
+        clean = lambda t: torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0)  # noqa: E731
+        score = self._lin(sn.fc2, torch.relu(self._lin(sn.fc1, s, dt)), dt)
+        at_logits = clean(self._lin(ts.act_head, torch.relu(self._lin(ts.act_body[2], torch.relu(self._lin(ts.act_body[0], s, dt)), dt)), dt))
+        x = torch.relu(self._lin(ts.dev_body[0], torch.cat([s, subset.to(s.device).to(dt)], dim=-1), dt))
+        dev_logits = clean(self._lin(ts.dev_head, torch.relu(self._lin(ts.dev_body[2], x, dt)), dt))
+        return score, at_logits, dev_logits
+
+    def evaluate(self, state, vis, part_of, n_parts, part, atype, dec, *, batch=None, fused=None, dtype=None):
+        """The REINFORCE update's evaluation of a STORED decision under the current weights (hierarchical_br.py:292-319, :190-210),
+        vectorised: stats [B, 6] = logp_hi, ent_hi, logp_at, ent_at, logp_dev, ent_dev, differentiable in every parameter.
+          state [B, state_dim]; vis [B, M] (visible where non-zero: the STORED mask); part_of [M] integer (NO_PART / >= n_parts: in no part)
+          part [B] the drawn part (-1: the [0] subset -- logp_hi = ent_hi = 0); atype [B] the type index; dec [B, M] bit 0 = in the
+          subset, bit 1 = selected (BatchedCyberDefenseEnv.hier_sample_decode returns the three)
+        fused (the default when `batch`, a BatchedCyberDefenseEnv on the parameters' device, is given): logits() in torch with autograd,
+        then the head -- part sums, softmax, the type Categorical, the subset's Bernoullis, and their backward -- as the library's two
+        launches (cygym_hier_loss / _backward behind one autograd.Function that saves only its inputs); fp32.
+        fused=False: the same formulas with torch ops; runs anywhere, in `dtype` (torch.float64: the restatement everything is judged
+        against)."""
+        fused = batch is not None if fused is None else bool(fused)
+        M, P = self.M, int(n_parts)
+        dev = state.device
+        dec = torch.as_tensor(dec).to(dev)
+        if tuple(dec.shape) != (state.shape[0], M):
+            raise ValueError(f"dec must have shape {(int(state.shape[0]), M)}")
+        po = torch.as_tensor(part_of).to(dev)
+        if po.numel() != M:
+            raise ValueError(f"part_of must hold {M} entries")
+        if not 1 <= P <= 255:
+            raise ValueError("1 to 255 parts")
+        sub, sel = (dec.to(torch.uint8) & 1) != 0, (dec.to(torch.uint8) & 2) != 0
+        visb = (torch.as_tensor(vis).to(dev) != 0)
+        if fused:
+            if batch is None:
+                raise ValueError("the fused evaluate runs through a BatchedCyberDefenseEnv: pass batch=")
+            if dtype not in (None, torch.float32):
+                raise ValueError("the fused evaluate is fp32")
+            score, al, dl = self.logits(state.float(), sub)
+            return _HierLoss.apply(batch, visb.to(torch.uint8).contiguous(), po.to(torch.uint8).contiguous(), P, part.to(torch.int32).contiguous(),
+                                   atype.to(torch.int32).contiguous(), dec.to(torch.uint8).contiguous(), score, al, dl)
+        score, al, dl = self.logits(state, sub, dtype=dtype)
+        dt = score.dtype
+        po = po.long()
+        onehot = (po[:, None] == torch.arange(P, device=dev)[None])                       # [M, P]
+        vin = visb & onehot.any(dim=1)[None]
+        psum = torch.where(vin, score, torch.zeros_like(score)) @ onehot.to(dt)
+        pscore = torch.where((vin.to(dt) @ onehot.to(dt)) > 0, psum, torch.full_like(psum, -1e9))
+        probs = torch.softmax(pscore, dim=1)
+        probs = probs / probs.sum(dim=-1, keepdim=True)                                   # (Categorical(probs=) normalises once more)
+        eps = 2.0 ** -23                                                                  # finfo(float32).eps: the reference runs in fp32
+        lq = torch.log(probs.clamp(min=eps, max=1 - eps))
+        has = part.to(dev).long() >= 0
+        logp_hi = torch.where(has, lq.gather(1, part.to(dev).long().clamp(min=0)[:, None])[:, 0], torch.zeros_like(lq[:, 0]))
+        ent_hi = torch.where(has, -(probs * lq).sum(dim=1), torch.zeros_like(lq[:, 0]))
+        lp = torch.log_softmax(al, dim=1)
+        logp_at = lp.gather(1, atype.to(dev).long()[:, None])[:, 0]
+        ent_at = -(lp.exp() * lp).sum(dim=1)
+        p = torch.sigmoid(dl)
+        lpos, lneg = torch.log(p + 1e-8), torch.log(1.0 - p + 1e-8)
+        m, sl = sub.to(dt), sel.to(dt)
+        logp_dev = ((sl * lpos + (1.0 - sl) * lneg) * m).sum(dim=1)
+        ent_dev = (-(p * lpos + (1.0 - p) * lneg) * m).sum(dim=1)
+        return torch.stack([logp_hi, ent_hi, logp_at, ent_at, logp_dev, ent_dev], dim=1)
 
     def packed(self):
         """What cygym_hier_decode reads of the parameters, as a dict (BatchedCyberDefenseEnv.hier_decode adds part_of / n_parts of

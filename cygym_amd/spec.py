@@ -52,6 +52,9 @@ SITE_GROUP_PICK = 66
 SITE_SAMPLE = 67
 SITE_COORD_PICK = 68
 SITE_COORD_NOISE = 69
+SITE_HIER_PART = 70
+SITE_HIER_TYPE = 71
+SITE_HIER_DEV = 72
 
 POISSON_TABLE = 16
 TRI_TABLE = 8

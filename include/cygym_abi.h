@@ -193,7 +193,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net; -1 for anything else, 13 and 15 included: those indices stay unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc; -1 for anything else, 13, 15 and 18 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -713,12 +713,93 @@ typedef struct cygym_hier_net {
  * device memory, so the call cannot inspect it without a synchronisation: an entry >= n_parts is treated like 0xFF (in no part) by the
  * kernel, and the Python layer (policies.HierarchicalPolicy) refuses such a table when it builds it.  CYGYM_ENOTBOUND only when the flag
  * plane is needed (vis_fixed == NULL) and the handle is not bound.
- * Out of scope: the sampled mode of train() (:285-398: a Categorical over parts, a Bernoulli per subset device, log-probabilities and
- * entropies) and its REINFORCE update; `meta` (meta_hierarchical_br.py) and the HMARL families; populations of nets in one launch;
+ * Out of scope (the sampled mode of train() and the head of its REINFORCE update are the calls below): `meta`
+ * (meta_hierarchical_br.py) and the HMARL families; populations of nets in one launch;
  * building h0 from the flag planes on chip; non-finite score logits (torch.argmax treats NaN as the maximum: here a valid row is
  * still written, which part wins is unspecified). */
 int cygym_hier_decode(cygym_handle* h, const cygym_hier_net* net, const cygym_action_vectors* layout, const cygym_actions* dst,
                       void* stream);
+
+/* What the SAMPLED decision of the HAGS training loop hands back per source row (all three mandatory, DEVICE pointers): what the
+ * REINFORCE update needs to evaluate the decision again under later weights (cygym_hier_loss). */
+typedef struct cygym_hier_sample {
+  int32_t* part_out;          /* [n] the drawn part; -1: no visible device in it, the subset is [0]                                          */
+  int32_t* atype_out;         /* [n] the drawn type INDEX, before type_map                                                                    */
+  uint8_t* dec_out;           /* [n][M] bit 0: device d is in the subset; bit 1: device d was selected                                        */
+} cygym_hier_sample;
+
+/* Replaces: the learner's decision in HierarchicalBestResponse.train (hierarchical_br.py:285-323) with _sample_low_within_subset
+ * (:172-231), for a batch, in ONE launch, fused with the scatter into the action tensors: cygym_hier_decode with the three arg-maxes
+ * replaced by draws.  The part draw decides which rows of w_mask_t enter dev_body.0, so it sits inside the launch, between the score
+ * pass and the low-level net.  Per source row r (env rows[r]):
+ *   1. visibility and part scores exactly as in cygym_hier_decode: the same code, the same summation order, the same bits (:285-298).
+ *   2. part ~ Categorical(softmax(part scores)) (:315-317), fp32, max-subtracted: e[p] = __expf(score[p] - max), S = the sum of e over
+ *      the parts in ascending id, target = (float)u32 * 2^-32 * S, the part is the first p whose running sum e[0] + .. + e[p] exceeds
+ *      target; if none does ((float)u32 rounds to 2^32 for u32 >= 2^32 - 128: target = S), the LAST part with e > 0 -- the inverse-CDF
+ *      walk of cygym_sample_group_actions, whose fall-through is its last entry; u32 = the draw (env, rng tick,
+ *      CG_SITE_HIER_PART).  A part without a visible device scores -1e9: e = 0 exactly, it cannot be drawn -- unless every part is
+ *      empty: then e = 1 everywhere and the draw is uniform, as softmax of equal scores is in the reference (-1e9 is not -inf, so the
+ *      branch at :301-313 never runs there and is not restated).
+ *   3. subset = the visible devices of the drawn part, ascending; empty: the subset [0], part_out = -1 (:179).  train() has no
+ *      single-device fallback: -2 never occurs.
+ *   4. the low-level net exactly as in the decode, nan_to_num included.
+ *   5. type ~ Categorical(logits = atype_logits) (:190-191) by the same walk over the types, u32 = the draw (.., CG_SITE_HIER_TYPE).
+ *   6. device d of the subset is selected iff (float)u32_d * 2^-32 < 1 / (1 + __expf(-dev_logit[d])) (:197-198), u32_d = the draw
+ *      (.., CG_SITE_HIER_DEV, a = d).  When none is selected, the subset's first maximum of the LOGITS is (:201-203 take the first
+ *      maximum of the probabilities: the decode's documented deviation).
+ *   7. the row is written through the row writer every decode shares, as in cygym_hier_decode: the type through type_map, the selected
+ *      devices ascending, exploit [0], app 0, cut at max_devs with CG_DECODE_TRUNCATED.
+ * The rng tick is read and not advanced.  No floating-point atomics: the same inputs and draws give the same bits.  The optional logit
+ * outputs of cygym_hier_net keep their meaning (part_out there receives what cygym_hier_sample.part_out does).  Limits and argument
+ * check: those of cygym_hier_decode; in addition CYGYM_EINVAL when `smp` or one of its three pointers is NULL, and CYGYM_ENOTBOUND on an
+ * unbound handle even with vis_fixed (the draws need the envs' rng ticks). */
+int cygym_hier_sample_decode(cygym_handle* h, const cygym_hier_net* net, const cygym_hier_sample* smp,
+                             const cygym_action_vectors* layout, const cygym_actions* dst, void* stream);
+
+/* The head of the REINFORCE update of HierarchicalBestResponse.train (hierarchical_br.py:338-348) behind the three logit tensors: the
+ * log-probabilities and entropies of a STORED decision under the current weights, and their backward.  The Linear layers stay with the
+ * caller (plain GEMMs under autograd).  All DEVICE pointers, contiguous; the handle is used for its device and the error text only. */
+typedef struct cygym_hier_loss_desc {
+  const float* score;         /* [n][M] the score net's logits                                                                                */
+  const float* atype_logits;  /* [n][T] through nan_to_num                                                                                    */
+  const float* dev_logits;    /* [n][M] through nan_to_num, of the net run on the stored subset                                               */
+  const uint8_t* vis;         /* [n][M] non-zero = device d was visible when the decision was made                                            */
+  const uint8_t* part_of;     /* [M] as in cygym_hier_net                                                                                     */
+  const int32_t* part;        /* [n] cygym_hier_sample.part_out                                                                               */
+  const int32_t* atype;       /* [n] cygym_hier_sample.atype_out                                                                              */
+  const uint8_t* dec;         /* [n][M] cygym_hier_sample.dec_out                                                                             */
+  float* stats;               /* forward out [n][6]: logp_hi, ent_hi, logp_at, ent_at, logp_dev, ent_dev                                      */
+  const float* g_stats;       /* backward in [n][6]: gradient of the loss with respect to stats                                               */
+  float* grad_score;          /* backward out [n][M]                                                                                          */
+  float* grad_atype_logits;   /* backward out [n][T]                                                                                          */
+  float* grad_dev_logits;     /* backward out [n][M]                                                                                          */
+  int32_t n, M, T, n_parts;   /* rows, devices, action types, parts (1 .. 255)                                                                */
+} cygym_hier_loss_desc;
+
+/* Forward, ONE launch, one wave per row, fp32 (expf / logf, not the fast forms):
+ *   high level (:292-319): part scores as in the decode (one running sum per part over its visible devices ascending, -1e9 for a part
+ *     without one); p = softmax (max-subtracted); q = clamp(p, eps, 1 - eps), eps = 2^-23 (torch's probs_to_logits);
+ *     logp_hi = log q[part], ent_hi = -sum_p p log q.  part = -1: both 0 (the row's subset did not come from a part's devices; in the
+ *     reference the softmax is then uniform over constants: log(1 / P) and log P, whose gradients are 0 as well -- :311-312 state the 0).
+ *   type (:190-193): lp = l - max - log(sum exp(l - max)); logp_at = lp[atype], ent_at = -sum p lp, p = exp(l - max) / sum.
+ *   devices (:196-210), over the subset (dec bit 0): p = 1 / (1 + exp(-x)), logp_dev = sum of (bit 1 ? log(p + 1e-8) : log(1 - p + 1e-8)),
+ *     ent_dev = -sum of (p log(p + 1e-8) + (1 - p) log(1 - p + 1e-8)).
+ *   Sums over parts, types and devices: lane i % 64 adds its entries in ascending order, then the xor butterfly (offsets 32, 16, .., 1),
+ *     the order the sampler's logp uses.
+ * Backward, ONE launch, recomputes the above:
+ *   grad_dev_logits[d]   = p (1 - p) (g_logp_dev (bit 1 ? 1 / (p + 1e-8) : -1 / (1 - p + 1e-8))
+ *                          - g_ent_dev (log(p + 1e-8) + p / (p + 1e-8) - log(1 - p + 1e-8) - (1 - p) / (1 - p + 1e-8))) on the subset, exactly 0 elsewhere
+ *   grad_atype_logits[t] = g_logp_at (1[t = atype] - p[t]) - g_ent_at p[t] (lp[t] + ent_at)
+ *   grad_score[d]        = G[part_of[d]] for a visible device of a part, exactly 0 elsewhere (and everywhere when part = -1), with
+ *                          a[j] = g_logp_hi 1[j = part] in[j] / p[j] - g_ent_hi (log q[j] + in[j]), in[j] = eps <= p[j] <= 1 - eps (clamp
+ *                          passes the gradient only inside its range, as in torch), G[j] = p[j] (a[j] - sum_k p[k] a[k]); G = 0 for a part without
+ *                          a visible device (its score is a constant).
+ * Both directions are row-local: no partials, no atomics; the same inputs give the same bits.
+ * Limits (CYGYM_EUNSUPPORTED beyond): T <= 32, M <= 2048.  CYGYM_EINVAL: a NULL handle, struct or mandatory pointer (forward: the eight
+ * inputs and stats; backward: the eight inputs, g_stats and the three gradients), n, M or T < 1, n_parts outside 1 .. 255; nothing is
+ * written then.  Out of scope: the Linear layers and their backward, the baseline, the clipping and the optimisers (torch). */
+int cygym_hier_loss(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream);
+int cygym_hier_loss_backward(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`

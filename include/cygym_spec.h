@@ -196,12 +196,19 @@ enum {
   CG_SITE_COORD_PICK = 68,   /* do_agent.py:2185 np.random.choice(len(topk), p=probs) of greedy_device_coord_ascent
                                 (cygym_coord_ascent_decode): a = device id; u = word 0 / 2^32 walks the inverse CDF of the
                                 top-K softmax; same addressing                                                     */
-  CG_SITE_COORD_NOISE = 69   /* do_agent.py:2178 coord_noise_std * np.random.randn(T E) on the Q of a device's candidates while
+  CG_SITE_COORD_NOISE = 69,  /* do_agent.py:2178 coord_noise_std * np.random.randn(T E) on the Q of a device's candidates while
                                 the critic trains (cygym_critic.noise_std > 0): a = device id, b = candidate c = 1 .. T E (the
                                 no-op, c = 0, gets none); the rng tick CG_SITE_COORD_PICK reads, not advanced.  The contract's
                                 mapping of randn -- addressed, not sequenced, like every other site: a standard normal from ONE
                                 call, in f64: u1 = (word 0 + 1) / 2^32 in (0, 1], u2 = word 1 / 2^32,
                                 z = sqrt(-2 ln u1) cos(2 pi u2)                                                    */
+  CG_SITE_HIER_PART = 70,    /* hierarchical_br.py:315-317 Categorical(softmax(subset_scores)).sample() of the HAGS training
+                                decision (cygym_hier_sample_decode): a = b = 0; u = word 0 / 2^32 walks the inverse CDF of the
+                                parts' softmax in ascending part id; the env's rng tick, read and not advanced    */
+  CG_SITE_HIER_TYPE = 71,    /* hierarchical_br.py:190-191 Categorical(logits=atype_logits).sample(): a = b = 0; the same walk
+                                over the action types; same addressing                                            */
+  CG_SITE_HIER_DEV = 72      /* hierarchical_br.py:197-198 torch.bernoulli(sigmoid(dev_logits[subset])): a = device id; device d
+                                of the subset is selected iff word 0 / 2^32 < sigmoid(dev_logit[d]); same addressing */
 };
 
 /* ---- Philox4x32-10 (Salmon et al., SC'11), counter-based ----
