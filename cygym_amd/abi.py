@@ -164,6 +164,20 @@ class HierLoss(C.Structure):
                 ("n", C.c_int32), ("M", C.c_int32), ("T", C.c_int32), ("n_parts", C.c_int32)]
 
 
+HMARL_MAX_SKILLS, HMARL_MAX_TYPES = 8, 32
+HMARL_EMPTY, HMARL_FALLBACK, HMARL_HIGH, HMARL_SHUFFLE = 0, 1, 2, 3      # cygym_hmarl.kind
+
+
+class Hmarl(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("master_logits", C.c_void_p), ("sub_logits", C.c_void_p), ("skill_out", C.c_void_p), ("type_out", C.c_void_p),
+                ("status", C.c_void_p), ("coin_thr", C.c_uint64), ("budget", C.c_double), ("cost_comp", C.c_double * HMARL_MAX_TYPES),
+                ("cost_not", C.c_double * HMARL_MAX_TYPES), ("batch_len", C.c_int32 * HMARL_MAX_TYPES), ("kind", C.c_uint8 * HMARL_MAX_TYPES),
+                ("allowed", C.c_uint8 * (HMARL_MAX_SKILLS * HMARL_MAX_TYPES)), ("n_allowed", C.c_uint8 * HMARL_MAX_SKILLS),
+                ("n", C.c_int32), ("role", C.c_int32), ("master", C.c_int32), ("cheap_idx", C.c_int32), ("costly_idx", C.c_int32),
+                ("global_idx", C.c_int32), ("n_skills", C.c_int32), ("n_logits", C.c_int32), ("net_mask", C.c_uint32), ("n_types", C.c_int32),
+                ("fanout", C.c_int32), ("fallback", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

@@ -869,6 +869,45 @@ class BatchedCyberDefenseEnv:
         self._hier(smp, rows, h0, pack, role, act, vis_fixed, type_map, **logit_outs)
         return out
 
+    def hmarl_decode(self, rows, cfg, master_logits=None, sub_logits=None, act=None, skill_out=None, type_out=None, n: int | None = None):
+        """BaseHMARLBR.execute (HMARL.py:595-607: the master's skill, the sub-policy's action type, its ordered targets and their cost
+        batches) for a batch, written as GROUPS into rows `rows` of `act`: ONE launch (cygym_hmarl_decode; include/cygym_abi.h states
+        the decision).
+          cfg            policies.HMARLConfig: role, master kind, skills' allowed types, which skills have a net, budget, fanout
+          master_logits  [n, n_skills] float32, contiguous (learned master): pi_fc2(relu(pi_fc1(s)))
+          sub_logits     [n, n_skills * n_logits] float32, contiguous (when a skill has a net): every skill's policy_net(s)
+          skill_out      optional [n] int32: the chosen skill; type_out optional [n] int32: the sub-policy's action type
+          n              source rows, when neither rows nor logits tell (an expert master over netless skills)
+        Needs max_groups / max_devs as policies.HMARLPolicy.groups_needed says, else the row is cut and abi.DECODE_TRUNCATED raised.
+        The rng tick is read, not advanced."""
+        dst = self.actions_struct(act)
+        q = cfg.to_c()
+        if cfg.role_code != _role(cfg.role)["code"]:
+            raise ValueError("cfg.role must be 'attacker' or 'defender'")
+        S_, K = cfg.n_skills, cfg.n_logits
+        f32 = lambda t: t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()  # noqa: E731
+        for t in (master_logits, sub_logits):
+            if t is not None and n is None:
+                n = int(t.shape[0])
+        if n is None:
+            n = self.N if rows is None else int(rows.numel())
+        if q.master == 1:
+            if master_logits is None or not f32(master_logits) or tuple(master_logits.shape) != (n, S_):
+                raise ValueError(f"master_logits must be a contiguous float32 [{n}, {S_}] tensor on {self.device}")
+            q.master_logits = master_logits.data_ptr()
+        if q.net_mask:
+            if sub_logits is None or not f32(sub_logits) or sub_logits.dim() != 2 or tuple(sub_logits.shape) != (n, S_ * K):
+                raise ValueError(f"sub_logits must be a contiguous float32 [{n}, {S_ * K}] tensor on {self.device}")
+            q.sub_logits = sub_logits.data_ptr()
+        for name, t in (("skill_out", skill_out), ("type_out", type_out)):
+            if t is not None:
+                if t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n,):
+                    raise ValueError(f"{name} must be a contiguous int32 [{n}] tensor on {self.device}")
+                setattr(q, name, t.data_ptr())
+        q.status = self.status.data_ptr()
+        r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
+        _lib.check(self.lib.cygym_hmarl_decode(self._h, C.byref(q), C.byref(dst), self._stream()), self._h, "cygym_hmarl_decode")
+
     def _hier_loss(self, score, atype_logits, dev_logits, vis, part_of, n_parts, part, atype, dec):
         f32 = lambda t: t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()  # noqa: E731
         if not f32(score) or score.dim() != 2:

@@ -1,10 +1,11 @@
 // cg_decode.hpp -- device code shared by the consumer-side kernels of the C-ABI unit (cg_aux_kernels.hpp), the tick + actor unit
-// (cg_inst_actor.hip), the coordinate-ascent unit (cg_inst_coord.hip) and the hierarchical unit (cg_inst_hier.hip).  Templates and force-inlined device functions only
+// (cg_inst_actor.hip), the coordinate-ascent unit (cg_inst_coord.hip), the hierarchical unit (cg_inst_hier.hip) and the H-MARL unit (cg_inst_hmarl.hip).  Templates and force-inlined device functions only
 // (included in more than one translation unit, inside namespace cygym_k).  What every writer of group 0 of an action row shares:
 //   dpp_pair_max, float_order_bits   wave-wide lexicographic max of (order bits, ~index) pairs
 //   wave_first_max                   ... read back as "index of the first maximum, 0 if none": decode_row_regs, the chunked decode of
 //                                    actor_mlp_body, the top-K' rounds and the merge of coord_ascent_kernel
 //   eps_greedy_type                  the epsilon-greedy type draw: decode_actions_kernel, decode_row_regs, the chunked decode
+//   RowGroups                        the group arrays of a row and the raise of CG_DECODE_TRUNCATED: RowList, hmarl_kernel
 //   RowList                          compaction of the ascending device list, cut at max_devs, zero fill, the row's scalars and
 //                                    CG_DECODE_TRUNCATED: write_actions_kernel, decode_actions_kernel, decode_row_regs, the chunked
 //                                    decode, the merge of coord_ascent_kernel, hier_kernel (group_row writes several groups: its own code, cg_aux_kernels.hpp)
@@ -48,6 +49,21 @@ __device__ __forceinline__ int eps_greedy_type(int at, const cygym_action_vector
   }
   return at;
 }
+// The group arrays of ONE action row and the one place that raises CG_DECODE_TRUNCATED: what RowList::finish (group 0) and a writer of
+// several groups per row (hmarl_kernel: one group per cost batch) store through.
+struct RowGroups {
+  int32_t *atype, *n_exploit, *exploit, *app, *dev_cnt;
+  __device__ __forceinline__ RowGroups(const cygym_actions& dst, const int row) {
+    const size_t o = (size_t)row * dst.max_groups;
+    atype = const_cast<int32_t*>(dst.atype) + o; n_exploit = const_cast<int32_t*>(dst.n_exploit) + o;
+    exploit = const_cast<int32_t*>(dst.exploit) + o * CG_MAX_EXPLOITS; app = const_cast<int32_t*>(dst.app) + o;
+    dev_cnt = const_cast<int32_t*>(dst.dev_cnt) + o;
+  }
+  __device__ __forceinline__ void set(const int g, const int at, const int ex, const int n_ex, const int ap) const {   // all but the count
+    atype[g] = at; exploit[(size_t)g * CG_MAX_EXPLOITS] = ex; n_exploit[g] = n_ex; app[g] = ap;
+  }
+  __device__ static __forceinline__ void truncated(uint32_t* status) { if (status) atomicOr(status, CG_DECODE_TRUNCATED); }
+};
 // The writer of group 0 of ONE action row, one object per (wave, row); every lane of the wave calls every member.  The devices
 // come in ascending id order, 64 candidates per push: a chosen device's place is the count of chosen devices below it (ballot +
 // mbcnt), the list is cut at max_devs.  finish() zeroes the entries behind the list, writes the row's five scalars and ORs
@@ -66,14 +82,12 @@ struct RowList {
   }
   __device__ __forceinline__ void finish(const cygym_actions& dst, const int row, const int lane, const int at, const int ex, const int n_ex,
                                          const int app, uint32_t* status) {
-    const int G = dst.max_groups, cnt = n < L ? n : L;
+    const int cnt = n < L ? n : L;
     if (lane == 0) {   // (the scalars first: behind the fill loop they stay live across it, two VGPRs more in write_actions_kernel)
-      const_cast<int32_t*>(dst.atype)[(size_t)row * G] = at;
-      const_cast<int32_t*>(dst.exploit)[(size_t)row * G * CG_MAX_EXPLOITS] = ex;
-      const_cast<int32_t*>(dst.n_exploit)[(size_t)row * G] = n_ex;
-      const_cast<int32_t*>(dst.app)[(size_t)row * G] = app;
-      const_cast<int32_t*>(dst.dev_cnt)[(size_t)row * G] = cnt;
-      if (n > L && status) atomicOr(status, CG_DECODE_TRUNCATED);
+      const RowGroups o(dst, row);
+      o.set(0, at, ex, n_ex, app);
+      o.dev_cnt[0] = cnt;
+      if (n > L) RowGroups::truncated(status);
     }
     for (int q = cnt + lane; q < L; q += WAVE) out[q] = 0;
   }
@@ -150,4 +164,5 @@ __device__ __forceinline__ int sample_head(const float* l, const int K, const ui
 #include "cg_actor_mlp.hpp"
 #include "cg_coord_ascent.hpp"
 #include "cg_hier.hpp"
+#include "cg_hmarl.hpp"
 #endif  // CG_DECODE_HPP

@@ -80,6 +80,12 @@ extern template __global__ void hier_loss_kernel<false>(cygym_hier_loss_desc);
 extern template __global__ void hier_loss_kernel<true>(cygym_hier_loss_desc);
 }  // namespace cygym_k
 
+// the H-MARL decode lives in its own unit (cg_inst_hmarl.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void hmarl_kernel<false>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
+extern template __global__ void hmarl_kernel<true>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
+}  // namespace cygym_k
+
 // the evaluate / backward kernels of the PPO update live in their own unit (cg_inst_eval.hip): declared, not instantiated, here
 namespace cygym_k {
 extern template __global__ void comm_eval_fwd_kernel<1, false>(cygym_comm_eval);
@@ -237,6 +243,7 @@ int cygym_sizeof(int32_t which) {
     case 17: return (int)sizeof(cygym_hier_net);
     case 19: return (int)sizeof(cygym_hier_sample);   // (index 18 stays unassigned)
     case 20: return (int)sizeof(cygym_hier_loss_desc);
+    case 21: return (int)sizeof(cygym_hmarl);
     default: return -1;
   }
 }
@@ -926,6 +933,42 @@ static int hier_loss_launch(cygym_handle* h, const cygym_hier_loss_desc* e, void
 }
 int cygym_hier_loss(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream) { return hier_loss_launch(h, e, stream, false, "cygym_hier_loss"); }
 int cygym_hier_loss_backward(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream) { return hier_loss_launch(h, e, stream, true, "cygym_hier_loss_backward"); }
+
+int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_hmarl_decode";
+  if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
+  if (!q || !dst || (q->master == 1 && !q->master_logits) || (q->net_mask && !q->sub_logits)) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (const int rc = check_dst(h, dst, who, true)) return rc;
+  const char* const bad = "cygym_hmarl_decode: bad layout (%s)";
+  if ((q->master != 0 && q->master != 1) || (q->role != 1 && q->role != 2)) return fail(h, CYGYM_EINVAL, bad, "master 0 or 1, role 1 or 2");
+  if (q->n_skills < 1 || q->n_skills > CG_HMARL_MAX_SKILLS || q->n_types < 1 || q->n_types > CG_HMARL_MAX_TYPES)
+    return fail(h, CYGYM_EINVAL, bad, "1 to 8 skills, 1 to 32 action types");
+  if (q->net_mask && (q->n_logits < 1 || q->n_logits > HM_MAX_LOGITS || (q->net_mask >> q->n_skills))) return fail(h, CYGYM_EINVAL, bad, "1 to 32 logits per skill, net_mask within the skills");
+  if (q->master == 0 && (q->cheap_idx < 0 || q->cheap_idx >= q->n_skills || q->costly_idx < 0 || q->costly_idx >= q->n_skills || q->global_idx < 0 || q->global_idx >= q->n_skills))
+    return fail(h, CYGYM_EINVAL, bad, "the expert master's indices must name skills");
+  for (int s = 0; s < q->n_skills; ++s) {
+    if (q->n_allowed[s] < 1 || q->n_allowed[s] > CG_HMARL_MAX_TYPES) return fail(h, CYGYM_EINVAL, bad, "a skill allows 1 to 32 action types");
+    for (int i = 0; i < q->n_allowed[s]; ++i)
+      if (q->allowed[s * CG_HMARL_MAX_TYPES + i] >= q->n_types) return fail(h, CYGYM_EINVAL, bad, "an allowed action type is not below n_types");
+  }
+  if (q->fanout < 1 || q->fallback < 0 || q->fallback >= CG_HMARL_MAX_TYPES || !(q->budget >= 0.0) || !(q->budget < 1e300))
+    return fail(h, CYGYM_EINVAL, bad, "fanout >= 1, fallback 0 .. 31, a finite budget >= 0");
+  for (int t = 0; t < q->n_types; ++t)
+    if (q->kind[t] > CG_HMARL_SHUFFLE || q->batch_len[t] < 0 || !(q->cost_comp[t] >= 0.0) || !(q->cost_comp[t] < 1e300) || !(q->cost_not[t] >= 0.0) || !(q->cost_not[t] < 1e300))
+      return fail(h, CYGYM_EINVAL, bad, "a kind above CG_HMARL_SHUFFLE, a negative batch length, or a cost that is negative or not finite");
+  if (!h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (the decision reads the flag plane and the envs' rng ticks)", who);
+  if (h->t.M > HM_MAX_M) return fail(h, CYGYM_EUNSUPPORTED, "%s: at most 2048 devices", who);
+  if (const int rc = check_rows(h, q->n, q->rows, 0, who)) return rc;
+  if (q->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const int wpb = hm_waves(h->t.M);
+  const size_t lds = (size_t)wpb * hm_wave_bytes(h->t.M);
+  const void* k = (q->skill_out || q->type_out) ? (const void*)hmarl_kernel<true> : (const void*)hmarl_kernel<false>;
+  const uint8_t* live = (const uint8_t*)h->b.live;
+  const uint8_t* dstatic = h->t.dstatic;
+  int M = h->t.M;
+  return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &dstatic, &M});
+}
 
 // What the two evaluate calls check alike, in the order of the decodes' shared check: handle, pointers, layout (CYGYM_EINVAL),
 // then the implemented range (CYGYM_EUNSUPPORTED).

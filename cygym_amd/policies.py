@@ -22,6 +22,11 @@ a score net picks one part of the partitioned graph, a two-stage net picks the a
 visible subset (HierarchicalBestResponse.execute, :419-494); the batch does it in one addmm plus one launch (cygym_hier_decode).
 HierarchicalNet.logits / .evaluate are the differentiable side: the REINFORCE update of hier_rollout.train (:246-416) evaluates a
 stored sampled decision through them (the loss head as cygym_hier_loss / _backward).
+
+`HMARLConfig` / `hmarl_decide` / `HMARLPolicy` are the fifth: the H-MARL expert baselines of HMARL.py (`hmarl_expert`, `hmarl_meta`) -- a
+rule-based or learned master picks a skill, the skill's frozen sub-policy picks an action type, orders its target devices and cuts them
+into float64 cost batches (BaseHMARLBR.execute, :595-607); the batch does it in at most three addmm plus one launch
+(cygym_hmarl_decode), answering with one group per batch.  hmarl_decide is the numpy restatement the kernel is tested against.
 """
 from __future__ import annotations
 
@@ -1067,3 +1072,370 @@ def calibrate_device_head(policy: ActorPolicy, obs: torch.Tensor, M: int, fracti
     v = policy.net(obs)[:, k: k + M]
     q = torch.quantile(v.flatten().float()[: 1 << 22], 1.0 - float(fraction))
     last.bias[k: k + M] -= q
+
+
+# ---- H-MARL (HMARL.py): a master picks a skill, the skill's frozen sub-policy picks the type, its targets and their cost batches ----------
+
+HMARL_DEVICE_COST = {1: (0.3, 0.01), 4: (1.0, 1.0), 5: (0.5, 0.5), 6: (0.5, 0.5), 7: (0.5, 0.5), 9: (0.5, 0.5), 11: (0.1, 0.1),
+                     12: (1.0, 1.0), 13: (3.0, 3.0)}      # DEFENDER_PER_DEVICE_COST_EST (HMARL.py:99-109): (compromised, not)
+HMARL_GLOBAL_TYPES = (2, 3, 8, 10)                         # DEFENDER_GLOBAL_ATYPES (:117)
+HMARL_SKILLS = {"defender": [[1, 5, 6, 7, 9, 11], [4, 12, 13], [2, 3, 8, 10]],      # benchmark_algos.py:476-485
+                "attacker": [[1], [2], [3]]}
+
+
+def hmarl_batch_len(cost: float, budget: float) -> int:
+    """Devices per batch of _batch_devices_by_cost (HMARL.py:170-187) when every device costs `cost`: the reference's own float64 loop
+    (29 for 0.1 under a budget of 3.0, not 30).  0: the batch never closes (cost 0) or is too long to matter."""
+    cost, budget = float(cost), float(budget)
+    if not cost > 0.0 or budget / cost > 1e6:
+        return 0
+    cur, n = 0.0, 0
+    while not (n and cur + cost > budget):
+        cur += cost
+        n += 1
+    return n
+
+
+class HMARLConfig:
+    """What one H-MARL strategy's decision depends on besides its nets' logits (BaseHMARLBR and its parts, HMARL.py):
+      role         'defender' / 'attacker'
+      master       'expert' (ExpertRuleMaster: cheap_idx, costly_idx, global_idx, global_prob) or 'learned' (LearnedMasterPolicy)
+      allowed      per skill, the allowed_action_types list of its FrozenSubPolicy (the order is what the arg-max indexes)
+      has_net      per skill, whether it has a policy_net (None: it has one)
+      n_logits     outputs of a skill's net (the reference's TinyNet: 8)
+      budget, fanout   per_group_cost_budget (3.0) and MAX_FANOUT (5)
+    table() is the per-type table the reference's constants give (kind, the two costs, the constant-cost batch length, the fallback
+    type); to_c() the cygym_hmarl without its pointers."""
+
+    def __init__(self, role: str, master: str, allowed=None, has_net=None, n_logits: int = 8, cheap_idx: int = 0, costly_idx: int = 1,
+                 global_idx: int = 2, global_prob: float = 0.1, budget: float = 3.0, fanout: int = 5):
+        from . import abi
+        if role not in ("defender", "attacker"):
+            raise ValueError("role must be 'attacker' or 'defender'")
+        if master not in ("expert", "learned"):
+            raise ValueError("master must be 'expert' or 'learned'")
+        self.role, self.master, self.role_code = role, master, 1 if role == "defender" else 2
+        self.allowed = [[int(t) for t in a] for a in (HMARL_SKILLS[role] if allowed is None else allowed)]
+        self.n_skills = len(self.allowed)
+        self.has_net = [True] * self.n_skills if has_net is None else [bool(x) for x in has_net]
+        if not 1 <= self.n_skills <= abi.HMARL_MAX_SKILLS or len(self.has_net) != self.n_skills:
+            raise ValueError(f"1 to {abi.HMARL_MAX_SKILLS} skills, one has_net entry each")
+        for a in self.allowed:
+            if not 1 <= len(a) <= abi.HMARL_MAX_TYPES or any(not 0 <= t < abi.HMARL_MAX_TYPES for t in a):
+                raise ValueError(f"a skill allows 1 to {abi.HMARL_MAX_TYPES} action types in 0 .. {abi.HMARL_MAX_TYPES - 1}")
+        self.n_logits = int(n_logits)
+        if any(self.has_net) and not 1 <= self.n_logits <= 32:
+            raise ValueError("n_logits must be in 1 .. 32")
+        self.cheap_idx, self.costly_idx, self.global_idx, self.global_prob = int(cheap_idx), int(costly_idx), int(global_idx), float(global_prob)
+        if master == "expert" and any(not 0 <= i < self.n_skills for i in (self.cheap_idx, self.costly_idx, self.global_idx)):
+            raise ValueError("the expert master's indices must name skills")
+        self.budget, self.fanout = float(budget), int(fanout)
+        if not (0.0 <= self.budget < 1e300) or self.fanout < 1:
+            raise ValueError("budget must be finite and >= 0, fanout >= 1")
+        self.fallback = 8 if role == "defender" else 3      # HMARL.py:311
+        self._c = None
+
+    def table(self):
+        """(kind [32], cost_comp [32], cost_not [32], batch_len [32]) by action type: HMARL.py:99-124, :246-313 as cygym_abi.h restates them."""
+        import numpy as np
+        from . import abi
+        T = abi.HMARL_MAX_TYPES
+        kind, cc, cn, bl = np.full(T, abi.HMARL_FALLBACK, np.uint8), np.zeros(T), np.zeros(T), np.zeros(T, np.int32)
+        for t in HMARL_GLOBAL_TYPES:
+            kind[t] = abi.HMARL_EMPTY
+        if self.role == "attacker":
+            kind[1] = abi.HMARL_SHUFFLE      # (types 2, 3 are in HMARL_GLOBAL_TYPES; type 1 is batched under the DEFENDER's costs, :173 / :100)
+            per_device = (1,)
+        else:
+            per_device = tuple(HMARL_DEVICE_COST)
+            kind[list(per_device)] = abi.HMARL_HIGH
+        for t in per_device:
+            cc[t], cn[t] = HMARL_DEVICE_COST[t]
+            bl[t] = hmarl_batch_len(cc[t], self.budget) if cc[t] == cn[t] else 0
+        return kind, cc, cn, bl
+
+    @property
+    def action_types(self):
+        """What the strategy can emit: the union of the allowed types plus the fallback no-op."""
+        return sorted({t for a in self.allowed for t in a} | {self.fallback})
+
+    def shortest_batch(self, t: int) -> int:
+        """The fewest devices a batch of type t can hold (what the dearer of its two costs allows); 0: the type makes one empty group."""
+        kind, cc, cn, _ = self.table()
+        from . import abi
+        if kind[t] < abi.HMARL_HIGH:
+            return 0
+        b = hmarl_batch_len(max(cc[t], cn[t]), self.budget)
+        return b if b > 0 else 1 << 30
+
+    def groups_needed(self, M: int) -> int:
+        need = 1
+        for t in self.action_types:
+            b = self.shortest_batch(t)
+            if b:
+                need = max(need, -(-int(M) // b))
+        return need
+
+    def to_c(self):
+        from . import abi, rng as R
+        if self._c is None:
+            q = abi.Hmarl()
+            kind, cc, cn, bl = self.table()
+            for t in range(abi.HMARL_MAX_TYPES):
+                q.kind[t], q.cost_comp[t], q.cost_not[t], q.batch_len[t] = int(kind[t]), float(cc[t]), float(cn[t]), int(bl[t])
+            for s, a in enumerate(self.allowed):
+                q.n_allowed[s] = len(a)
+                for i, t in enumerate(a):
+                    q.allowed[s * abi.HMARL_MAX_TYPES + i] = t
+            q.coin_thr, q.budget, q.role, q.master = R.bernoulli_threshold(self.global_prob), self.budget, self.role_code, int(self.master == "learned")
+            q.cheap_idx, q.costly_idx, q.global_idx = self.cheap_idx, self.costly_idx, self.global_idx
+            q.n_skills, q.n_logits, q.n_types = self.n_skills, self.n_logits, abi.HMARL_MAX_TYPES
+            q.net_mask = sum(1 << s for s, h in enumerate(self.has_net) if h)
+            q.fanout, q.fallback = self.fanout, self.fallback
+            self._c = q
+        import ctypes as C
+        q = type(self._c)()
+        C.memmove(C.byref(q), C.byref(self._c), C.sizeof(q))
+        return q
+
+
+def _hmarl_walk(x, u32):
+    """sample_head's walk (csrc/cg_decode.hpp: fp32, max-subtracted __expf, the first k whose running sum exceeds (float)u32 2^-32 S, else
+    the last entry) in float64, and whether the draw is CLEAR of every CDF boundary by more than twice the fp32 walk's error bound
+    (u = 2^-24 per operation; __expf(d) within (4 + |d|) u relative; running sums and S within (K + 4) u more; the target within 3 u)."""
+    import numpy as np
+    U = 2.0 ** -24
+    x = np.asarray(x, np.float64)
+    d = x - x.max()
+    e = np.exp(d)
+    cum, S = np.cumsum(e), e.sum()
+    err = np.cumsum(e * (4.0 + np.abs(d)) * U) + (len(x) + 4) * U * cum
+    frac = float(u32) / 4294967296.0
+    target = frac * S
+    terr = target * 3 * U + frac * err[-1]
+    hit = np.flatnonzero(cum > target)
+    pick = int(hit[0]) if len(hit) else len(x) - 1
+    clear = bool((np.abs(cum[:-1] - target) > 2.0 * (err[:-1] + terr)).all()) if len(x) > 1 else True
+    return pick, clear
+
+
+def hmarl_decide(flags, dstatic, role, cfg: HMARLConfig, master_logits, sub_logits, seed, env_ids, ticks):
+    """BaseHMARLBR.execute (HMARL.py:595-607) for n rows in numpy, as include/cygym_abi.h restates it under cygym_hmarl_decode: the
+    restatement the kernel is tested against.
+      flags [n, M] uint8 flag bytes, dstatic [M] uint8; master_logits [n, S] / sub_logits [n, S * n_logits] fp32 (or None where unused)
+      seed, env_ids [n] (global env ids), ticks [n] (the envs' rng ticks): the address of the draws (rng.draw_np)
+    Returns (skill [n], atype [n] -- the sub-policy's type --, groups: per row the list of (type, [device ids]) in group order, clear [n]:
+    False where the learned master's draw lies within the fp32 walk's error bound of a CDF boundary, such a row may differ)."""
+    import numpy as np
+    from . import abi, rng as R, spec as S
+    if role != cfg.role:
+        raise ValueError(f"the config belongs to the {cfg.role}")
+    flags, dstatic = np.asarray(flags, np.uint8), np.asarray(dstatic, np.uint8)
+    n, M = flags.shape
+    kind, cc, cn, _ = cfg.table()
+    thr = R.bernoulli_threshold(cfg.global_prob)
+    ids = np.arange(M)
+    skill, atype, groups, clear = np.zeros(n, np.int64), np.zeros(n, np.int64), [], np.ones(n, bool)
+    for i in range(n):
+        f, e, tk = flags[i], int(env_ids[i]), int(ticks[i])
+        comp, owned, reach, nya = (f & S.F_COMP) != 0, (f & S.F_OWNED) != 0, (f & S.F_REACH) != 0, (f & S.F_NYA) != 0
+        dc = (dstatic & S.D_DC) != 0
+        hot = comp & ~owned
+        if cfg.master == "expert":                                   # HMARL.py:336-354
+            if (hot & dc).any():
+                sk = cfg.costly_idx
+            elif int(hot.sum()) >= 3:
+                sk = cfg.cheap_idx
+            else:
+                sk = cfg.global_idx if int(R.draw_np(seed, e, tk, S.SITE_HMARL_COIN)) < thr else cfg.cheap_idx
+        else:                                                        # :381-389
+            sk, clear[i] = _hmarl_walk(np.asarray(master_logits[i], np.float32), int(R.draw_np(seed, e, tk, S.SITE_HMARL_SKILL)))
+        allowed = cfg.allowed[sk]
+        if cfg.has_net[sk]:                                          # :229-244
+            lg = np.asarray(sub_logits[i], np.float32).reshape(cfg.n_skills, cfg.n_logits)[sk]
+            t = allowed[min(int(np.argmax(lg)), len(allowed) - 1)]
+        else:
+            t = allowed[int(R.draw_np(seed, e, tk, S.SITE_HMARL_TYPE)) % len(allowed)]
+        skill[i], atype[i] = sk, t
+        order = []
+        if kind[t] == abi.HMARL_HIGH:                                # :139-154
+            score = np.where(hot & dc, 100, np.where(hot, 50, np.where(comp, 40, np.where(reach, 20, 0))))
+            vis = ids[~nya]
+            order = vis[np.argsort(-score[vis], kind="stable")].tolist()
+        elif kind[t] == abi.HMARL_SHUFFLE:                           # :263-267
+            seeds = ids[~nya & (owned | comp)]
+            if not len(seeds):
+                seeds = ids[~nya]
+            key = R.draw_np(seed, np.full(len(seeds), e, np.uint64), np.full(len(seeds), tk, np.uint64), S.SITE_HMARL_SHUFFLE, a=seeds)
+            order = seeds[np.lexsort((seeds, key))].tolist()
+        if kind[t] == abi.HMARL_EMPTY:
+            groups.append([(int(t), [])])
+            continue
+        if not order:                                                # :309-312
+            groups.append([(cfg.fallback, [])])
+            continue
+        batches, cur, cost = [], [], 0.0                             # :170-187, the float64 loop as it stands
+        for d in order:
+            dcost = float(cc[t]) if comp[d] else float(cn[t])
+            if cur and (cost + dcost) > cfg.budget:
+                batches.append(cur)
+                cur, cost = [], 0.0
+            cur.append(int(d))
+            cost += dcost
+        batches.append(cur)
+        groups.append([(int(t), b[:cfg.fanout]) for b in batches])   # :304-306
+    return skill, atype, groups, clear
+
+
+class _HMARLMaster(nn.Module):
+    """LearnedMasterPolicy (HMARL.py:364-379) with the reference's parameter names: `master_state_dict` loads unchanged."""
+
+    def __init__(self, state_dim, n_skills, hidden=128):
+        super().__init__()
+        self.pi_fc1, self.pi_fc2 = nn.Linear(state_dim, hidden), nn.Linear(hidden, n_skills)
+        self.v_fc1, self.v_fc2 = nn.Linear(state_dim, hidden), nn.Linear(hidden, 1)
+
+
+class _HMARLSkillNet(nn.Module):
+    """The policy_net of a skill as the reference's driver builds it (benchmark_algos.py:466-471): one Linear layer named `fc`."""
+
+    def __init__(self, state_dim, n_logits=8):
+        super().__init__()
+        self.fc = nn.Linear(state_dim, n_logits)
+
+    def forward(self, x):
+        return self.fc(x)
+
+
+class HMARLPolicy:
+    """A `hmarl_expert` / `hmarl_meta` strategy in the closed loop: BaseHMARLBR.execute (HMARL.py:595-607) for a batch as at most three
+    addmm (the learned master's two layers, ONE for every skill's net over the concatenated fc weights) plus ONE launch
+    (cygym_hmarl_decode; include/cygym_abi.h states the decision).
+      master    a dict (the expert master's config: cheaplocal_idx, costlylocal_idx, global_idx, global_prob) or an _HMARLMaster
+      subnets   per skill an _HMARLSkillNet (any module with a Linear `fc`) or None (a netless skill draws its type)
+      allowed   per skill its allowed action types (default: the reference driver's lists, benchmark_algos.py:476-485)
+    It writes GROUPS (`writes_groups`), up to groups_needed(M) of them and up to M list entries.  write() does not synchronise with the
+    host.  __call__ raises, like CommActorPolicy's."""
+
+    tick_free = True
+    writes_groups = True
+
+    def __init__(self, role: str, master, subnets, allowed=None, budget: float = 3.0, fanout: int = 5):
+        learned = isinstance(master, nn.Module)
+        mc = {} if learned else dict(master or {})
+        nets = list(subnets)
+        widths = {int(m.fc.out_features) for m in nets if m is not None}
+        if len(widths) > 1:
+            raise ValueError("the skills' nets must have the same number of outputs")
+        self.cfg = HMARLConfig(role, "learned" if learned else "expert", allowed, [m is not None for m in nets], widths.pop() if widths else 8,
+                               int(mc.get("cheaplocal_idx", 0)), int(mc.get("costlylocal_idx", 1)), int(mc.get("global_idx", 2)),
+                               float(mc.get("global_prob", 0.1)), budget, fanout)
+        if len(nets) != self.cfg.n_skills:
+            raise ValueError(f"{self.cfg.n_skills} skills, {len(nets)} sub-policies")
+        self.role, self.master, self.subnets = role, (master if learned else None), nets
+        dims = {int(m.fc.in_features) for m in nets if m is not None} | ({int(master.pi_fc1.in_features)} if learned else set())
+        if len(dims) > 1:
+            raise ValueError("the master and the skills' nets must read the same state")
+        self.state_dim = dims.pop() if dims else None
+        if learned and int(master.pi_fc2.out_features) != self.cfg.n_skills:
+            raise ValueError("the master's head must have one output per skill")
+        self.action_types = self.cfg.action_types
+        self.n_types = max(self.action_types) + 1
+        self._pk = None
+
+    def groups_needed(self, M: int) -> int:
+        """The most groups a row can have: the largest ceil(M / shortest batch of the type) over the strategy's types, at least 1."""
+        return self.cfg.groups_needed(M)
+
+    @classmethod
+    def from_strategy(cls, mapping, batch, role: str, allowed=None, **kw):
+        """From a reference strategy's type_mapping: `hmarl_expert` ({master_cfg, subpolicies}, HMARL.py:684-694) or `hmarl_meta`
+        ({master_state_dict, subpolicies, state_dim, num_skills}, :922-934); `subpolicies` is a list of state dicts, {} for a skill
+        without a net.  The skills' lists default to the reference driver's (benchmark_algos.py:476-485)."""
+        mapping = getattr(mapping, "type_mapping", mapping)
+        if "hmarl_expert" in mapping:
+            payload, learned = mapping["hmarl_expert"], False
+        elif "hmarl_meta" in mapping:
+            payload, learned = mapping["hmarl_meta"], True
+        else:
+            payload, learned = mapping, "master_state_dict" in mapping
+        width = batch.role_width(role)
+        nets = []
+        for sd in payload.get("subpolicies", []):
+            if not sd:
+                nets.append(None)
+                continue
+            n_logits, state_dim = (int(x) for x in sd["fc.weight"].shape)
+            if state_dim != width:
+                raise ValueError(f"a skill's net reads {state_dim} state columns, the {role} view has {width}")
+            net = _HMARLSkillNet(state_dim, n_logits)
+            net.load_state_dict(sd)
+            nets.append(net.eval().to(batch.device))
+        if not nets:
+            nets = [None] * len(HMARL_SKILLS[role] if allowed is None else allowed)
+        if learned:
+            sd = payload["master_state_dict"]
+            hidden, state_dim = (int(x) for x in sd["pi_fc1.weight"].shape)
+            if state_dim != width:
+                raise ValueError(f"the master reads {state_dim} state columns, the {role} view has {width}")
+            master = _HMARLMaster(state_dim, int(sd["pi_fc2.weight"].shape[0]), hidden)
+            master.load_state_dict(sd)
+            master = master.eval().to(batch.device)
+        else:
+            master = dict(payload.get("master_cfg", {}))
+        pol = cls(role, master, nets, allowed, **kw)
+        if pol.state_dim is not None:
+            pol._packed(torch.device(batch.device))
+        return pol
+
+    def to_strategy(self):
+        """The payload the reference's save() builds (HMARL.py:684-694 / :922-934) under its type_mapping key."""
+        subs = [({} if m is None else {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}) for m in self.subnets]
+        if self.master is None:
+            c = self.cfg
+            return {"hmarl_expert": {"master_type": "expert_rule", "subpolicies": subs,
+                                     "master_cfg": {"cheaplocal_idx": c.cheap_idx, "costlylocal_idx": c.costly_idx, "global_idx": c.global_idx,
+                                                    "global_prob": c.global_prob}}}
+        return {"hmarl_meta": {"master_type": "learned_meta_ppo", "subpolicies": subs, "state_dim": self.state_dim, "num_skills": self.cfg.n_skills,
+                               "master_state_dict": {k: v.detach().cpu().clone() for k, v in self.master.state_dict().items()}}}
+
+    @torch.no_grad()
+    def _packed(self, device):
+        """The transposed weights on `device`: the master's two layers, and the skills' fc layers concatenated into ONE [state, S * n_logits]
+        matrix (zero columns for a netless skill)."""
+        if self._pk is None or self._pk["device"] != device:
+            pk = {"device": device}
+            if self.master is not None:
+                m = self.master.to(device)
+                pk.update(w1=m.pi_fc1.weight.t().contiguous(), b1=m.pi_fc1.bias.clone(), w2=m.pi_fc2.weight.t().contiguous(), b2=m.pi_fc2.bias.clone())
+            if any(self.cfg.has_net):
+                K = self.cfg.n_logits
+                w = torch.zeros((self.state_dim, self.cfg.n_skills * K), dtype=torch.float32, device=device)
+                b = torch.zeros((self.cfg.n_skills * K,), dtype=torch.float32, device=device)
+                for s, net in enumerate(self.subnets):
+                    if net is not None:
+                        w[:, s * K:(s + 1) * K] = net.fc.weight.t().to(device)
+                        b[s * K:(s + 1) * K] = net.fc.bias.to(device)
+                pk.update(ws=w, bs=b)
+            self._pk = pk
+        return self._pk
+
+    @torch.no_grad()
+    def logits(self, obs):
+        """(master_logits [n, S] or None, sub_logits [n, S * n_logits] or None) of the role views `obs`: the addmm of write()."""
+        pk = self._packed(obs.device)
+        ml = torch.addmm(pk["b2"], torch.relu_(torch.addmm(pk["b1"], obs, pk["w1"])), pk["w2"]) if "w1" in pk else None
+        sl = torch.addmm(pk["bs"], obs, pk["ws"]) if "ws" in pk else None
+        return ml, sl
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, skill_out=None, type_out=None):
+        """The addmm, then the whole decision + its groups into rows `rows` of the action tensors in ONE launch."""
+        if self.state_dim is not None and (obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != self.state_dim):
+            raise ValueError(f"obs must be a float32 [n, {self.state_dim}] role view")
+        ml, sl = self.logits(obs) if self.state_dim is not None else (None, None)
+        batch.hmarl_decode(rows, self.cfg, ml, sl, act=act, skill_out=skill_out, type_out=type_out, n=int(obs.shape[0]))
+
+    def __call__(self, obs, t, M, L):
+        raise NotImplementedError("an HMARLPolicy answers with groups of devices in cost batches: a dict of single actions cannot "
+                                  "carry them (it runs through write(), on a batch with cygym_hmarl_decode)")

@@ -227,7 +227,7 @@ def _group_actors(batch, items, M, env_order_rpg=None):
 
 def _role_actions(batch, pol, M, L):
     """One action dict per role: the roles share every tensor but the mode words (no per-tick copy in steady state).  A role
-    with a strategy that writes groups (`writes_groups`: policies.CommActorPolicy) also gets an n_groups tensor of its own: the
+    with a strategy that writes groups (`writes_groups`: policies.CommActorPolicy, policies.HMARLPolicy) also gets an n_groups tensor of its own: the
     rows its ordinary strategies play stay at 0, and the other role's ticks never see its group counts."""
     acts = {r: dict(batch.act) for r in pol}
     for r in acts:
@@ -237,10 +237,19 @@ def _role_actions(batch, pol, M, L):
     for r in pol:
         grouping = [p for p in pol[r] if getattr(p, "writes_groups", False)]
         if grouping:
-            K, G = max(int(p.n_types) for p in grouping), int(batch.act["atype"].shape[1])
-            if G < K - 1 or L < M:
-                raise ValueError(f"a {r} strategy writes groups: the batch needs max_groups >= {K - 1} and max_devs >= {M} "
-                                 f"(it has max_groups = {G}, max_devs = {L})")
+            G = int(batch.act["atype"].shape[1])
+            by_types = [p for p in grouping if not hasattr(p, "groups_needed")]      # one group per action type but the no-op
+            if by_types:
+                K = max(int(p.n_types) for p in by_types)
+                if G < K - 1 or L < M:
+                    raise ValueError(f"a {r} strategy writes groups: the batch needs max_groups >= {K - 1} and max_devs >= {M} "
+                                     f"(it has max_groups = {G}, max_devs = {L})")
+            for p in grouping:
+                if hasattr(p, "groups_needed"):      # a strategy that says itself how many groups a row can have (policies.HMARLPolicy)
+                    need = int(p.groups_needed(M))
+                    if G < need or L < M:
+                        raise ValueError(f"a {r} strategy writes up to {need} groups per row: the batch needs max_groups >= {need} and "
+                                         f"max_devs >= {M} (it has max_groups = {G}, max_devs = {L})")
             acts[r]["n_groups"] = torch.zeros_like(batch.act["n_groups"])
     return acts
 

@@ -193,7 +193,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc; -1 for anything else, 13, 15 and 18 included: those indices stay unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl; -1 for anything else, 13, 15 and 18 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -800,6 +800,96 @@ typedef struct cygym_hier_loss_desc {
  * written then.  Out of scope: the Linear layers and their backward, the baseline, the clipping and the optimisers (torch). */
 int cygym_hier_loss(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream);
 int cygym_hier_loss_backward(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream);
+
+/* An H-MARL strategy (HMARL.py: HMARLExpertBestResponse / HMARLMetaBestResponse, type_mapping["hmarl_expert"] / ["hmarl_meta"]) in the
+ * pieces the decode below reads.  Pointers are DEVICE pointers; the tables are part of the struct (it travels as the kernel argument). */
+#define CG_HMARL_MAX_SKILLS 8
+#define CG_HMARL_MAX_TYPES 32
+#define CG_HMARL_EMPTY    0   /* kind: one empty group of the type                                      */
+#define CG_HMARL_FALLBACK 1   /* kind: one empty group of the role's fallback type                      */
+#define CG_HMARL_HIGH     2   /* kind: the high-value order, cut into cost batches                      */
+#define CG_HMARL_SHUFFLE  3   /* kind: the shuffled seeds, cut into cost batches                        */
+typedef struct cygym_hmarl {
+  const int32_t* rows;        /* [n] env ids (rows of the action tensors) to write; NULL = rows 0..n-1                                       */
+  const float* master_logits; /* [n][n_skills] pi_fc2(relu(pi_fc1(s))) of source row r (master == 1; two addmm of the caller)                */
+  const float* sub_logits;    /* [n][n_skills][n_logits] the skills' policy_net(s), ONE addmm over the concatenated fc weights; the block of
+                                 a skill without a net is not read; may be NULL when net_mask == 0                                          */
+  int32_t* skill_out;         /* optional [n]: the skill index of source row r (what a later master update needs from this launch)          */
+  int32_t* type_out;          /* optional [n]: the sub-policy's action type, before the fallback replaces it                                */
+  uint32_t* status;           /* optional, ONE word: CG_DECODE_TRUNCATED is OR-ed in when a row needs more groups than max_groups or more
+                                 list entries than max_devs                                                                                 */
+  uint64_t coin_thr;          /* ceil(global_prob * 2^32) of the expert master: >= 2^32 always, 0 never                                     */
+  double   budget;            /* per_group_cost_budget (HMARL.py:207: 3.0)                                                                   */
+  double   cost_comp[CG_HMARL_MAX_TYPES];   /* cost of a COMPROMISED device under type t (HMARL.py:99-109), float64                          */
+  double   cost_not[CG_HMARL_MAX_TYPES];    /* ... of any other device                                                                       */
+  int32_t  batch_len[CG_HMARL_MAX_TYPES];   /* > 0: both costs are equal and a batch holds this many devices -- the length the reference's
+                                               float64 loop gives (computed by that loop on the host: 29 for cost 0.1, not 30);
+                                               0: the kernel walks the float64 running sum itself                                           */
+  uint8_t  kind[CG_HMARL_MAX_TYPES];        /* CG_HMARL_* of action type t under this role                                                   */
+  uint8_t  allowed[CG_HMARL_MAX_SKILLS * CG_HMARL_MAX_TYPES];   /* allowed[32 s + i]: allowed_action_types[i] of skill s                     */
+  uint8_t  n_allowed[CG_HMARL_MAX_SKILLS];  /* 1 .. 32                                                                                       */
+  int32_t  n;                 /* source rows                                                                                                */
+  int32_t  role;              /* 1 defender, 2 attacker (documentation of the tables; the kernel reads kind / fallback)                     */
+  int32_t  master;            /* 0 ExpertRuleMaster, 1 LearnedMasterPolicy                                                                  */
+  int32_t  cheap_idx, costly_idx, global_idx;   /* the expert master's skill indices, 0 .. n_skills - 1                                      */
+  int32_t  n_skills;          /* 1 .. 8                                                                                                     */
+  int32_t  n_logits;          /* outputs of a skill's net (the reference: 8), 1 .. 32; read when net_mask != 0                               */
+  uint32_t net_mask;          /* bit s: skill s has a policy_net                                                                            */
+  int32_t  n_types;           /* entries of the per-type tables in use, 1 .. 32; every allowed type is below it                             */
+  int32_t  fanout;            /* MAX_FANOUT (HMARL.py:304: 5), >= 1                                                                          */
+  int32_t  fallback;          /* the type of the fallback group: 8 defender, 3 attacker (HMARL.py:311)                                       */
+} cygym_hmarl;
+
+/* Replaces: BaseHMARLBR.execute (HMARL.py:595-607) -- the master's skill (:336-354 ExpertRuleMaster, :381-389 / :754-756
+ * LearnedMasterPolicy), FrozenSubPolicy.select_action (:315-322): _pick_action_type (:229-244), _choose_devices_for_action (:246-274) with
+ * _high_value_targets (:139-154), _batch_devices_by_cost (:170-187) and _batchify (:276-313) -- for a batch, in ONE launch, fused with the
+ * scatter into the action tensors as GROUPS (cygym_group_actions' layout: n_groups, the groups' atype / n_exploit = 1 / exploit[.][0] = 0 /
+ * app = 0 / dev_cnt and the concatenated device lists; `mode` is not touched).  Per source row r (env e = rows[r]) the kernel reads the
+ * flag byte f[d] of the bound live plane and the topology's CG_D_DC bit; device ids are 0 .. M-1 in dict order (ascending id).
+ * Skill.
+ *   expert master (:336-354): cnt = the devices with COMP && !OWNED, over ALL devices, Not_yet_added ones included (:339 does not
+ *     filter); dc = one of them has CG_D_DC.  dc -> costly_idx; else cnt >= 3 -> cheap_idx; else the coin -> global_idx; else cheap_idx.
+ *     The coin is  word 0 < coin_thr  of the draw (e, rng tick, CG_SITE_HMARL_COIN).
+ *   learned master (:381-389): Categorical(logits = master_logits[r]) by the inverse-CDF walk of cygym_sample_group_actions (fp32,
+ *     max-subtracted __expf, the first k whose running sum exceeds (float)u32 2^-32 S, else the last skill), u32 = the draw
+ *     (.., CG_SITE_HMARL_SKILL).
+ * Type (:229-244).  idx = the first maximum of sub_logits[r][skill][0 .. n_logits), clamped to n_allowed[skill] - 1 (:241); the type is
+ *   allowed[skill][idx].  Deviation, deliberate: the arg-max is taken on the logits, not on fp32 softmax probabilities (:239-240) -- the
+ *   two differ only where two probabilities round to one float.  +0 and -0 tie (the lower index wins).  Non-finite logits: +inf and a NaN
+ *   with a clear sign bit count as larger than every finite value, -inf and a NaN with the sign bit set as smaller (the order of the bit
+ *   patterns); a valid row is written in any case; this is not pinned to the reference (whose softmax turns them into NaN and whose
+ *   np.argmax then answers the first NaN).  A skill without a net (policy_net is None, :232-233): allowed[skill][word 0 % n_allowed] of
+ *   the draw (.., CG_SITE_HMARL_TYPE).
+ * Targets, by kind[type] (the host builds the table from the reference's constants, :99-124 and :246-313):
+ *   CG_HMARL_EMPTY     defender 2, 3, 8, 10 and attacker 2, 3, 8, 10: _batch_devices_by_cost answers [[]] (:172-174), the row is
+ *                      [(t, [0], [], 0)].  Attacker type 2's shuffled seeds (:268-272) never reach the action: no draw is made for them.
+ *   CG_HMARL_HIGH      defender 1, 4, 5, 6, 7, 9, 11, 12, 13: the devices with !NYA by descending score, ties in ascending id (sorted(...,
+ *                      reverse=True) is stable): 100 = COMP && DC && !OWNED; 50 = COMP && !OWNED; 40 = COMP && OWNED; 20 = REACH; 0
+ *                      otherwise.  (_random_targets at :253-254 is reached only when that list is empty: never observable.)
+ *   CG_HMARL_SHUFFLE   attacker 1: the !NYA devices with OWNED || COMP, or all !NYA devices when there is none, in ascending (word 0 of
+ *                      the draw (.., CG_SITE_HMARL_SHUFFLE, a = d), d) -- the contract's reading of random.shuffle.  Attacker type 1
+ *                      falls into the DEFENDER's cost table (:173, :100): 0.3 compromised, 0.01 otherwise.  Kept.
+ *   CG_HMARL_FALLBACK  any other type, and a HIGH / SHUFFLE type whose list is empty: [(fallback, [0], [], 0)] (:309-312).
+ * Batches (:170-187).  The ordered list is walked with a float64 running cost that starts at 0.0: a device opens a new batch when the
+ *   current one is not empty and  cur + cost > budget  in float64, exactly the reference's sequential loop (real arithmetic is wrong:
+ *   the loop gives 29 devices for cost 0.1, 300 for 0.01, 10 for 0.3, 6 for 0.5, 3 for 1.0, 1 for 3.0).  batch_len[t] > 0 replaces the
+ *   walk by  position % batch_len[t] == 0  for a type whose two costs are equal.
+ * Groups (:297-308).  Each batch keeps its first `fanout` ids and DROPS the rest (a full 0.5-cost batch of six loses its sixth device).
+ *   Group g = (t, n_exploit 1, exploit[0] = 0, app 0, the kept ids of batch g); groups in batch order, device lists concatenated in
+ *   dev_idx: a row needs at most M list entries and up to M groups (type 13: one device per batch).
+ * Cut: groups >= max_groups are not written, list entries >= max_devs neither (a group's count is cut to what is left of the row's
+ *   entries, 0 behind it); either raises CG_DECODE_TRUNCATED in `status`; n_groups = min(groups, max_groups).  Nothing is written
+ *   behind a row's groups or behind its list entries, and no other row is touched.
+ * The four draws are addressed by the env's rng tick, which is read and not advanced.  Everything written is an integer: the same
+ * inputs give the same rows.
+ * CYGYM_EINVAL (nothing is written): a NULL handle, struct, destination array (n_groups included), master_logits with master == 1 or
+ *   sub_logits with net_mask != 0; master outside 0 / 1; role outside 1 / 2; n_skills outside 1 .. 8; n_types outside 1 .. 32;
+ *   n_logits outside 1 .. 32 with net_mask != 0; an n_allowed outside 1 .. 32 or an allowed type >= n_types; an expert index outside
+ *   0 .. n_skills - 1; a kind above CG_HMARL_SHUFFLE; fanout < 1; a negative batch_len; a budget or cost that is negative or not finite;
+ *   a fallback outside 0 .. 31; a bad row count.  CYGYM_ENOTBOUND without cygym_bind.  M up to 2048.
+ * Out of scope: training (_phase1 / _phase2, SubPolicyPPO, _master_update; skill_out is what that needs from this launch), the
+ * sanitising of _step_env_grouped (:520-564), `meta` (meta_hierarchical_br.py), and building the logits on chip. */
+int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_actions* dst, void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`

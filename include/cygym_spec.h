@@ -207,8 +207,17 @@ enum {
                                 parts' softmax in ascending part id; the env's rng tick, read and not advanced    */
   CG_SITE_HIER_TYPE = 71,    /* hierarchical_br.py:190-191 Categorical(logits=atype_logits).sample(): a = b = 0; the same walk
                                 over the action types; same addressing                                            */
-  CG_SITE_HIER_DEV = 72      /* hierarchical_br.py:197-198 torch.bernoulli(sigmoid(dev_logits[subset])): a = device id; device d
+  CG_SITE_HIER_DEV = 72,     /* hierarchical_br.py:197-198 torch.bernoulli(sigmoid(dev_logits[subset])): a = device id; device d
                                 of the subset is selected iff word 0 / 2^32 < sigmoid(dev_logit[d]); same addressing */
+  CG_SITE_HMARL_COIN = 73,   /* HMARL.py:352 random.random() < global_prob of ExpertRuleMaster (cygym_hmarl_decode): a = b = 0; the coin
+                                is word 0 < ceil(global_prob * 2^32), as CG_SITE_EPS_TYPE compares its coin; the env's rng tick, read
+                                and not advanced                                                                  */
+  CG_SITE_HMARL_SKILL = 74,  /* HMARL.py:385-386 Categorical(logits = master logits).sample() of LearnedMasterPolicy: a = b = 0;
+                                u = word 0 / 2^32 walks the inverse CDF of the skills' softmax; same addressing    */
+  CG_SITE_HMARL_TYPE = 75,   /* HMARL.py:233 random.choice(allowed_action_types) of a skill without a net: a = b = 0; the type is
+                                allowed[word 0 % len(allowed)]; same addressing                                   */
+  CG_SITE_HMARL_SHUFFLE = 76 /* HMARL.py:266 random.shuffle(seeds) of attacker type 1: a = device id (sort key): the seeds in
+                                ascending (word 0, id), the contract's reading of a shuffle as at CG_SITE_SHUFFLE; same addressing */
 };
 
 /* ---- Philox4x32-10 (Salmon et al., SC'11), counter-based ----
