@@ -1060,12 +1060,13 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_critic_tail(self._h, C.byref(e), self._stream()), self._h, "cygym_critic_tail")
         return q
 
-    def critic_tail_backward(self, h1_pre, w2, b2, w3, b3, grad_q, weight_grads: bool = True, out=None, h_stride=None):
+    def critic_tail_backward(self, h1_pre, w2, b2, w3, b3, grad_q, weight_grads: bool = True, out=None, h_stride=None, n_partials=None):
         """The backward of critic_tail (cygym_critic_tail_backward: one launch, plus the reduction of the workgroups' partials
         with weight_grads): h1 and h2 are recomputed on chip from h1_pre.  Returns (grad_h1_pre [n, H1], grad_w2 [H2, H1], grad_b2
         [H2], grad_w3 [H2], grad_b3 [1]); without weight_grads only grad_h1_pre is computed (the same bits) and the other four are
         None -- or, when `out` gives all five, left untouched.  No atomics: the same inputs give the same bits.  The workspace is
-        min(ceil(n / 16), 256) (H2 H1 + 2 H2 + 1) floats."""
+        min(ceil(n / 16), 256) (H2 H1 + 2 H2 + 1) floats.  n_partials: the number of partial blocks to size the workspace for and to
+        hand the library instead (tests of the clamp: the library launches no more workgroups than that, each walks more row tiles)."""
         e, (n, H1, H2) = self._critic_tail(h1_pre, w2, b2, w3, b3)
         if h_stride is not None:
             e.h_stride = int(h_stride)
@@ -1081,8 +1082,8 @@ class BatchedCyberDefenseEnv:
             gw2 = gb2 = gw3 = gb3 = None
         e.grad_h1_pre = gh.data_ptr()
         if weight_grads:
-            nwg = min((n + 15) // 16, 256)
-            part = torch.empty((nwg * (H2 * H1 + 2 * H2 + 1),), dtype=torch.float32, device=self.device)
+            nwg = min((n + 15) // 16, 256) if n_partials is None else int(n_partials)
+            part = torch.empty((max(nwg, 1) * (H2 * H1 + 2 * H2 + 1),), dtype=torch.float32, device=self.device)
             e.grad_w2, e.grad_b2, e.grad_w3, e.grad_b3 = gw2.data_ptr(), gb2.data_ptr(), gw3.data_ptr(), gb3.data_ptr()
             e.partials, e.n_partials, e.weight_grads = part.data_ptr(), nwg, 1
         _lib.check(self.lib.cygym_critic_tail_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_critic_tail_backward")
