@@ -178,6 +178,16 @@ class Hmarl(C.Structure):
                 ("fanout", C.c_int32), ("fallback", C.c_int32)]
 
 
+class Meta(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("h0", C.c_void_p), ("sp_w2_t", C.c_void_p), ("sp_b2", C.c_void_p), ("base", C.c_void_p), ("w_feat", C.c_void_p),
+                ("np_w2", C.c_void_p), ("np_b2", C.c_void_p), ("nbr_ptr", C.c_void_p), ("nbr_col", C.c_void_p), ("flags_fixed", C.c_void_p),
+                ("type_map", C.c_void_p), ("w1a_t", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
+                ("score_out", C.c_void_p), ("selected_out", C.c_void_p), ("q_out", C.c_void_p), ("deg_out", C.c_void_p), ("status", C.c_void_p),
+                ("b3", C.c_float), ("n", C.c_int32), ("role", C.c_int32), ("k", C.c_int32), ("n_types", C.c_int32), ("n_exploits", C.c_int32),
+                ("n_apps", C.c_int32), ("id_dim", C.c_int32), ("embed_dim", C.c_int32), ("proj_dim", C.c_int32), ("Hp", C.c_int32),
+                ("H1", C.c_int32), ("H2", C.c_int32), ("h0_stride", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

@@ -908,6 +908,71 @@ class BatchedCyberDefenseEnv:
         r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
         _lib.check(self.lib.cygym_hmarl_decode(self._h, C.byref(q), C.byref(dst), self._stream()), self._h, "cygym_hmarl_decode")
 
+    def meta_decode(self, rows, h0: torch.Tensor, pack, role: str = "defender", act=None, flags_fixed=None, type_map=None,
+                    score_out=None, selected_out=None, q_out=None, deg_out=None):
+        """MetaHierarchicalBestResponse.execute (meta_hierarchical_br.py:660-790, the MetaDOAR best response on a fresh object: the
+        controller's scores, the k best visible devices, the critic's action type per kept device) for a batch, written as GROUPS into
+        rows `rows` of `act`: ONE launch (cygym_meta_decode; include/cygym_abi.h states the decision and the arithmetic).
+          h0           [n, >= Hp + H1] float32 (unit inner stride): state_proj.fc1(s) | critic fc1's state part + bias (+ the app column),
+                       before the relu (policies.MetaNet.h0: one addmm)
+          pack         policies.MetaPolicy's merged tables: MetaNet.packed() (base, w_feat, sp_w2_t, sp_b2, np_w2, np_b2, dims), the
+                       critic's (w1a_t, w2, b2, w3, b3), nbr_ptr / nbr_col (policies.meta_neighbours of the batch's topology), k and
+                       the critic's layout n_types / n_exploits / n_apps
+          flags_fixed  None: every row reads the flag bytes and the added edges of its env; a [M] uint8 tensor: that ONE snapshot for
+                       every row, base graph only (what the reference's execute does in payoff evaluation)
+          outputs      optional, contiguous: score_out [n, M] float32, selected_out [n, k] int32 (ascending ids, -1 behind them),
+                       q_out [n, k, n_types] float32 (slots behind the kept count stay untouched), deg_out [n, M] int32
+        Needs max_groups >= k and max_devs >= k, else the row is cut and abi.DECODE_TRUNCATED raised.  No draw: the rng tick is
+        neither read nor advanced.  Limits: M <= 1000, k, n_types <= 32, id_dim <= 32, embed_dim, proj_dim <= 64, Hp <= 256, the
+        critic's widths multiples of 16 in 16..128 (the library answers CYGYM_EUNSUPPORTED / CYGYM_EINVAL)."""
+        dst = self.actions_struct(act)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
+            raise ValueError("h0 must be a [n, >= Hp + H1] float32 tensor on the batch's device with unit inner stride")
+        n, M = int(h0.shape[0]), self.M
+        T, E, A, k = int(pack["n_types"]), int(pack["n_exploits"]), int(pack["n_apps"]), int(pack["k"])
+        ID, ED, P, Hp, H1, H2 = (int(pack[x]) for x in ("id_dim", "embed_dim", "proj_dim", "Hp", "H1", "H2"))
+        if int(h0.shape[1]) < Hp + H1:
+            raise ValueError(f"h0 rows hold {int(h0.shape[1])} floats: fewer than Hp + H1 = {Hp + H1}")
+        ed4 = (ED + 3) // 4 * 4
+        sizes = {"sp_w2_t": Hp * P, "sp_b2": P, "base": M * ed4, "w_feat": 3 * ed4, "np_w2": P * ED, "np_b2": P,
+                 "w1a_t": (T + M + E + A) * H1, "w2": (H2 + 15) // 16 * ((H1 + 15) // 16) * 256, "w3": H2}
+        q = abi.Meta()
+        for name, want in sizes.items():
+            t = pack[name]
+            if not ok(t) or not t.is_contiguous() or int(t.numel()) != want:
+                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device}")
+            setattr(q, name, t.data_ptr())
+        if pack.get("b2") is not None:
+            if not ok(pack["b2"]) or not pack["b2"].is_contiguous() or int(pack["b2"].numel()) != H2:
+                raise ValueError(f"pack['b2'] must hold {H2} float32 values on {self.device}")
+            q.b2 = pack["b2"].data_ptr()
+        ptr, col = pack["nbr_ptr"], pack["nbr_col"]
+        if ptr.dtype != torch.int32 or ptr.device != self.device or not ptr.is_contiguous() or int(ptr.numel()) != M + 1:
+            raise ValueError(f"pack['nbr_ptr'] must be a contiguous int32 [{M + 1}] tensor on {self.device}")
+        if col.dtype != torch.int16 or col.device != self.device or not col.is_contiguous() or int(col.numel()) != int(pack["nbr_len"]):
+            raise ValueError(f"pack['nbr_col'] must be a contiguous int16 [{int(pack['nbr_len'])}] tensor on {self.device} (policies.meta_neighbours)")
+        q.nbr_ptr, q.nbr_col = ptr.data_ptr(), col.data_ptr()
+        q.b3, q.role, q.k, q.n_types, q.n_exploits, q.n_apps = float(pack["b3"]), _role(role)["code"], k, T, E, A
+        q.id_dim, q.embed_dim, q.proj_dim, q.Hp, q.H1, q.H2 = ID, ED, P, Hp, H1, H2
+        q.h0, q.h0_stride = h0.data_ptr(), int(h0.stride(0)) if n > 1 else int(h0.shape[1])
+        keep = []
+        if flags_fixed is not None:
+            keep.append(_exactly(M, flags_fixed.reshape(-1), torch.uint8, self.device, "flags_fixed"))
+            q.flags_fixed = keep[-1].data_ptr()
+        if type_map is not None:
+            keep.append(_exactly(T, type_map, torch.int32, self.device, "type_map"))
+            q.type_map = keep[-1].data_ptr()
+        for name, t, shape, dt in (("score_out", score_out, (n, M), torch.float32), ("selected_out", selected_out, (n, k), torch.int32),
+                                   ("q_out", q_out, (n, k, T), torch.float32), ("deg_out", deg_out, (n, M), torch.int32)):
+            if t is not None:
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
+                setattr(q, name, t.data_ptr())
+        q.status = self.status.data_ptr()
+        r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
+        _lib.check(self.lib.cygym_meta_decode(self._h, C.byref(q), C.byref(dst), self._stream()), self._h, "cygym_meta_decode")
+
     def _hier_loss(self, score, atype_logits, dev_logits, vis, part_of, n_parts, part, atype, dec):
         f32 = lambda t: t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()  # noqa: E731
         if not f32(score) or score.dim() != 2:

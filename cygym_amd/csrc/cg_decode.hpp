@@ -1,11 +1,11 @@
 // cg_decode.hpp -- device code shared by the consumer-side kernels of the C-ABI unit (cg_aux_kernels.hpp), the tick + actor unit
-// (cg_inst_actor.hip), the coordinate-ascent unit (cg_inst_coord.hip), the hierarchical unit (cg_inst_hier.hip) and the H-MARL unit (cg_inst_hmarl.hip).  Templates and force-inlined device functions only
+// (cg_inst_actor.hip), the coordinate-ascent unit (cg_inst_coord.hip), the hierarchical unit (cg_inst_hier.hip), the H-MARL unit (cg_inst_hmarl.hip) and the MetaDOAR unit (cg_inst_meta.hip).  Templates and force-inlined device functions only
 // (included in more than one translation unit, inside namespace cygym_k).  What every writer of group 0 of an action row shares:
 //   dpp_pair_max, float_order_bits   wave-wide lexicographic max of (order bits, ~index) pairs
 //   wave_first_max                   ... read back as "index of the first maximum, 0 if none": decode_row_regs, the chunked decode of
 //                                    actor_mlp_body, the top-K' rounds and the merge of coord_ascent_kernel
 //   eps_greedy_type                  the epsilon-greedy type draw: decode_actions_kernel, decode_row_regs, the chunked decode
-//   RowGroups                        the group arrays of a row and the raise of CG_DECODE_TRUNCATED: RowList, hmarl_kernel
+//   RowGroups                        the group arrays of a row and the raise of CG_DECODE_TRUNCATED: RowList, hmarl_kernel, meta_kernel
 //   RowList                          compaction of the ascending device list, cut at max_devs, zero fill, the row's scalars and
 //                                    CG_DECODE_TRUNCATED: write_actions_kernel, decode_actions_kernel, decode_row_regs, the chunked
 //                                    decode, the merge of coord_ascent_kernel, hier_kernel (group_row writes several groups: its own code, cg_aux_kernels.hpp)
@@ -165,4 +165,5 @@ __device__ __forceinline__ int sample_head(const float* l, const int K, const ui
 #include "cg_coord_ascent.hpp"
 #include "cg_hier.hpp"
 #include "cg_hmarl.hpp"
+#include "cg_meta.hpp"
 #endif  // CG_DECODE_HPP

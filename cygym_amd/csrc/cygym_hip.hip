@@ -86,6 +86,12 @@ extern template __global__ void hmarl_kernel<false>(cygym_hmarl, cygym_actions, 
 extern template __global__ void hmarl_kernel<true>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
 }  // namespace cygym_k
 
+// the MetaDOAR decode lives in its own unit (cg_inst_meta.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void meta_kernel<false>(cygym_meta, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
+extern template __global__ void meta_kernel<true>(cygym_meta, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
+}  // namespace cygym_k
+
 // the evaluate / backward kernels of the PPO update live in their own unit (cg_inst_eval.hip): declared, not instantiated, here
 namespace cygym_k {
 extern template __global__ void comm_eval_fwd_kernel<1, false>(cygym_comm_eval);
@@ -244,6 +250,7 @@ int cygym_sizeof(int32_t which) {
     case 19: return (int)sizeof(cygym_hier_sample);   // (index 18 stays unassigned)
     case 20: return (int)sizeof(cygym_hier_loss_desc);
     case 21: return (int)sizeof(cygym_hmarl);
+    case 23: return (int)sizeof(cygym_meta);   // (index 22 stays unassigned)
     default: return -1;
   }
 }
@@ -968,6 +975,43 @@ int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_action
   const uint8_t* dstatic = h->t.dstatic;
   int M = h->t.M;
   return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &dstatic, &M});
+}
+
+int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_meta_decode";
+  const char* const bad_layout = "cygym_meta_decode: bad layout (types, exploits >= 1, role 1 or 2, h0_stride >= Hp + H1, 16-byte aligned base / w_feat / packed w2)%s";
+  // the checks the decodes share, on this call's layout: T types, the handle's devices, E exploits, A apps
+  cygym_action_vectors lay;
+  memset(&lay, 0, sizeof(lay));
+  if (h && q) { lay.n_types = q->n_types; lay.n_devices = h->t.M; lay.n_exploits = q->n_exploits; lay.n_apps = q->n_apps; }
+  const bool own = q && q->h0 && q->sp_w2_t && q->sp_b2 && q->base && q->w_feat && q->np_w2 && q->np_b2 && q->nbr_ptr && q->nbr_col && q->w1a_t &&
+                   q->w2 && q->w3;
+  if (const int rc = check_vectors(h, q ? &lay : nullptr, dst, who, own, 1, bad_layout)) return rc;
+  if (const int rc = check_dst(h, dst, who, true)) return rc;
+  if ((q->role != 1 && q->role != 2) || q->Hp < 1 || q->H1 < 1 || (long long)q->h0_stride < (long long)q->Hp + q->H1 ||
+      (((uintptr_t)q->base | (uintptr_t)q->w_feat | (uintptr_t)q->w2) & 15))
+    return fail(h, CYGYM_EINVAL, bad_layout, "");
+  if (h->t.M > MT_MAX_M) return fail(h, CYGYM_EUNSUPPORTED, "%s: at most 1000 devices (the reference's dense adjacency path)", who);
+  if (q->k < 1 || q->k > MT_MAX_K || q->n_types > MT_MAX_T || q->n_exploits > CG_MAX_EXPLOITS || q->id_dim < 1 || q->id_dim > MT_MAX_ID ||
+      q->embed_dim < 1 || q->embed_dim > MT_MAX_ED || q->proj_dim < 1 || q->proj_dim > MT_MAX_P || q->Hp > MT_MAX_HP)
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: k, action types 1 .. 32, at most CG_MAX_EXPLOITS exploits, id_dim 1 .. 32, embed_dim, proj_dim 1 .. 64, Hp 1 .. 256", who);
+  if (q->H1 < 16 || q->H1 > MT_MAX_H || (q->H1 & 15) || q->H2 < 16 || q->H2 > MT_MAX_H || (q->H2 & 15))
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: critic widths H1, H2 must be multiples of 16 in 16 .. 128", who);
+  if (!q->flags_fixed && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (without flags_fixed the flags and the added edges are read off the bound state)", who);
+  if (const int rc = check_rows(h, q->n, q->rows, 0, who)) return rc;
+  if (q->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const MtPlan pl = mt_plan(q->H1, q->H2, q->n_types, q->embed_dim, q->Hp, h->t.M);
+  const int wpb = mt_waves(pl, CG_LDS_BYTES);
+  const size_t lds = (size_t)(pl.wave0 + wpb * pl.wave_pitch) * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the critic and a row's buffers do not fit in LDS", who);
+  const void* k = (q->score_out || q->selected_out || q->q_out || q->deg_out) ? (const void*)meta_kernel<true> : (const void*)meta_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const bool env_mode = !q->flags_fixed;
+  const uint8_t* live = env_mode ? (const uint8_t*)h->b.live : nullptr;
+  const uint32_t* extra = env_mode && h->t.K > 0 ? (const uint32_t*)h->b.extra : nullptr;
+  int K = h->t.K, M = h->t.M;
+  return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &extra, &K, &M});
 }
 
 // What the two evaluate calls check alike, in the order of the decodes' shared check: handle, pointers, layout (CYGYM_EINVAL),

@@ -27,6 +27,12 @@ stored sampled decision through them (the loss head as cygym_hier_loss / _backwa
 rule-based or learned master picks a skill, the skill's frozen sub-policy picks an action type, orders its target devices and cuts them
 into float64 cost batches (BaseHMARLBR.execute, :595-607); the batch does it in at most three addmm plus one launch
 (cygym_hmarl_decode), answering with one group per batch.  hmarl_decide is the numpy restatement the kernel is tested against.
+
+`MetaNet` / `MetaPolicy` are the sixth: the MetaDOAR best response of meta_hierarchical_br.py (`--BR_type meta`) -- a controller scores
+every device from a structural embedding against a projection of the state, keeps the select_k best visible ones, and the role's DDPG
+critic picks one action type per kept device (MetaHierarchicalBestResponse.execute, :660-790, on a fresh object: its caches never act);
+the batch does it in one addmm plus one launch (cygym_meta_decode), answering with one group per kept device.  MetaNet.decide is the
+torch restatement the kernel is tested against.
 """
 from __future__ import annotations
 
@@ -1439,3 +1445,338 @@ class HMARLPolicy:
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("an HMARLPolicy answers with groups of devices in cost batches: a dict of single actions cannot "
                                   "carry them (it runs through write(), on a batch with cygym_hmarl_decode)")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# MetaDOAR (`--BR_type meta`, meta_hierarchical_br.py)
+
+def meta_select_k(M: int, alpha: float = 1.0) -> int:
+    """select_k of MetaHierarchicalBestResponse (meta_hierarchical_br.py:337): max(1, ceil(alpha log10(max(10, M))))."""
+    import math
+    return max(1, int(math.ceil(float(alpha) * math.log10(max(10, int(M))))))
+
+
+def meta_adjacency(M: int, edges):
+    """adjacency_matrix_from_env's dense A (meta_hierarchical_br.py:74-109) as a bool [M, M] numpy array: the edge list symmetrised plus
+    the identity, entries SET (a duplicate or reciprocal edge counts once)."""
+    import numpy as np
+    A = np.eye(int(M), dtype=bool)
+    for u, v in edges:
+        A[int(u), int(v)] = True
+        A[int(v), int(u)] = True
+    return A
+
+
+def meta_neighbours(topo):
+    """The rows of that A for a batch's base topology, as cygym_meta_decode reads them: (nbr_ptr int32 [M + 1], nbr_col int16: row i =
+    {i} u out(i) u in(i), every id once, ascending)."""
+    import numpy as np
+    M = int(topo.M)
+    src = np.repeat(np.arange(M), np.diff(np.asarray(topo.out_ptr)))
+    A = meta_adjacency(M, zip(src.tolist(), np.asarray(topo.out_col).tolist()))
+    ptr = np.zeros(M + 1, np.int32)
+    ptr[1:] = np.cumsum(A.sum(axis=1))
+    return torch.from_numpy(ptr), torch.from_numpy(np.nonzero(A)[1].astype(np.int16))
+
+
+def _meta_topo_key(topo):
+    """A digest of a topology's edges, computed once per topology object: batches built over equal topologies share a policy's tables."""
+    key = topo.__dict__.get("_meta_key")
+    if key is None:
+        import hashlib
+        import numpy as np
+        key = topo.__dict__["_meta_key"] = (int(topo.M), hashlib.sha1(np.asarray(topo.out_ptr).tobytes() + np.asarray(topo.out_col).tobytes()).hexdigest())
+    return key
+
+
+class _MetaStructFeats(nn.Module):
+    def __init__(self, M, id_dim):
+        super().__init__()
+        self.id_emb = nn.Embedding(int(M), int(id_dim))
+
+
+class _MetaStateProj(nn.Module):
+    def __init__(self, state_dim, proj_dim, hidden):
+        super().__init__()
+        self.fc1, self.fc2 = nn.Linear(int(state_dim), int(hidden)), nn.Linear(int(hidden), int(proj_dim))
+
+
+class MetaNet(nn.Module):
+    """The controller of the reference's MetaDOAR best response (meta_hierarchical_br.py) under the reference's parameter names, so that
+    the three state dicts of `strategy.type_mapping["meta"]` load unchanged (load_strategy):
+        struct_feats.id_emb  StructuralNodeFeaturizer's id embedding (:142-148)
+        node_proj            Linear(id_dim + 3, embed_dim) - ReLU - Linear(embed_dim, proj_dim) on [id_emb, degn, known, owned] (:314-318)
+        state_proj           StateProjector (:190-199): fc1 - ReLU - fc2
+        node_bias            added to every score (:427); it changes no order
+    decide() is MetaHierarchicalBestResponse.execute (:660-790) on a fresh object, vectorised over a batch with torch ops -- it runs
+    anywhere, and in torch.float64 it is the restatement cygym_meta_decode is tested against.  packed() / h0() give the kernel's form."""
+
+    def __init__(self, state_dim: int, M: int, id_dim: int = 16, embed_dim: int = 32, proj_dim: int = 32, hidden: int = 64):
+        super().__init__()
+        self.state_dim, self.M, self.id_dim, self.embed_dim, self.proj_dim, self.hidden = (int(x) for x in (state_dim, M, id_dim, embed_dim, proj_dim, hidden))
+        self.struct_feats = _MetaStructFeats(self.M, self.id_dim)
+        self.node_proj = nn.Sequential(nn.Linear(self.id_dim + 3, self.embed_dim), nn.ReLU(), nn.Linear(self.embed_dim, self.proj_dim))
+        self.state_proj = _MetaStateProj(self.state_dim, self.proj_dim, self.hidden)
+        self.node_bias = nn.Parameter(torch.zeros(1))
+        with torch.no_grad():
+            nn.init.normal_(self.struct_feats.id_emb.weight, std=0.02)
+
+    @classmethod
+    def from_mapping(cls, mapping):
+        """A MetaNet with the widths of the state dicts of type_mapping["meta"] (or that dict itself), loaded."""
+        mapping = mapping.get("meta", mapping)
+        for key in ("state_proj", "node_proj", "struct_feats"):
+            if not isinstance(mapping.get(key), dict):
+                raise ValueError(f"a meta strategy carries the state dicts state_proj, node_proj and struct_feats: {key!r} is missing")
+        hidden, state_dim = (int(x) for x in mapping["state_proj"]["fc1.weight"].shape)
+        M, id_dim = (int(x) for x in mapping["struct_feats"]["id_emb.weight"].shape)
+        embed_dim, proj_dim = int(mapping["node_proj"]["0.weight"].shape[0]), int(mapping["node_proj"]["2.weight"].shape[0])
+        if int(mapping["node_proj"]["0.weight"].shape[1]) != id_dim + 3 or int(mapping["state_proj"]["fc2.weight"].shape[0]) != proj_dim:
+            raise ValueError("node_proj.0 must read id_dim + 3 features, and state_proj.fc2 and node_proj.2 must share proj_dim")
+        return cls(state_dim, M, id_dim, embed_dim, proj_dim, hidden).load_strategy(mapping)
+
+    def load_strategy(self, mapping):
+        """Load state_proj, node_proj and struct_feats (all three required) and, when present, node_bias of type_mapping["meta"]."""
+        mapping = mapping.get("meta", mapping)
+        as_t = lambda sd: {k: torch.as_tensor(v) for k, v in sd.items()}  # noqa: E731
+        for key in ("state_proj", "node_proj", "struct_feats"):
+            if not isinstance(mapping.get(key), dict):
+                raise ValueError(f"a meta strategy carries the state dicts state_proj, node_proj and struct_feats: {key!r} is missing")
+            getattr(self, key).load_state_dict(as_t(mapping[key]))
+        if mapping.get("node_bias") is not None:
+            with torch.no_grad():
+                self.node_bias.copy_(torch.as_tensor(mapping["node_bias"]).reshape(1))
+        return self
+
+    def save(self, path, select_k=None):
+        """The file the reference's save() writes (:365-374): the three state dicts, node_bias, select_k, M."""
+        cpu = lambda m: {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}  # noqa: E731
+        torch.save({"state_proj": cpu(self.state_proj), "node_proj": cpu(self.node_proj), "struct_feats": cpu(self.struct_feats),
+                    "node_bias": self.node_bias.detach().cpu().clone(), "select_k": None if select_k is None else int(select_k), "M": self.M}, path)
+
+    @torch.no_grad()
+    def decide(self, state, flags, adj, role: str, critic, k: int, dtype=None, n_types=None, n_exploits=None, n_apps: int = 0, selected=None):
+        """execute (:660-790) on a fresh object, for a batch.  state [B, state_dim]; flags [B, M] or [M] uint8 in the flag plane's bit
+        layout; adj bool [M, M] or [B, M, M] (meta_adjacency: symmetric, with the identity); critic: a module with fc1 / fc2 / fc3 whose
+        action vector is [n_types | M | n_exploits | n_apps] (n_types defaults to what is left of fc1's inputs with n_exploits = 1).
+        Returns a dict, floats in `dtype` (default: the state's) from the same fp32 parameters:
+          vis [B, M] bool, deg [B, M] int64, degn [B, M], score [B, M] (before node_bias), n_sel [B] = min(k, |V|),
+          sel [B, k] int64 the kept devices in ascending id (-1 behind them), q [B, k, T] after nan_to_num (NaN behind them),
+          atype [B, k] int64 the first maximum over the types whose candidate number is below META_MAX_CANDIDATES (-1 behind them).
+        Ties at the k-th place go to the lower id (where the reference's np.argpartition is unspecified).
+        `selected` [B, k] int64 (-1 padded, ascending): skip the selection and score those devices (tests: the kernel's own)."""
+        from . import spec as S
+        dt = state.dtype if dtype is None else dtype
+        s = state.to(dt)
+        B, M, dev = int(s.shape[0]), self.M, s.device
+        f = torch.as_tensor(flags).to(dev).to(torch.uint8)
+        f = f[None].expand(B, M) if f.dim() == 1 else f
+        known, owned, nya = (f & S.F_KNOWN) != 0, (f & S.F_OWNED) != 0, (f & S.F_NYA) != 0
+        vis = (known & owned & ~nya) if role == "attacker" else (~nya & ~owned)
+        A = torch.as_tensor(adj).to(dev).bool()
+        A = A[None].expand(B, M, M) if A.dim() == 2 else A
+        if role == "attacker":
+            A = A & vis[:, :, None] & vis[:, None, :]
+        deg = A.sum(dim=2)
+        mx = deg.max(dim=1, keepdim=True).values
+        degn = torch.where(mx > 0, deg.float() / mx.clamp(min=1).float(), deg.float()).to(dt)       # the fp32 quotient (:163-164)
+        lin0, lin2, ID = self.node_proj[0], self.node_proj[2], self.id_dim
+        w0 = lin0.weight.detach().to(dt)
+        base = self.struct_feats.id_emb.weight.detach().to(dt) @ w0[:, :ID].t() + lin0.bias.detach().to(dt)      # [M, ED]
+        x = base[None] + degn[:, :, None] * w0[:, ID] + known.to(dt)[:, :, None] * w0[:, ID + 1] + owned.to(dt)[:, :, None] * w0[:, ID + 2]
+        emb = torch.relu(x) @ lin2.weight.detach().to(dt).t() + lin2.bias.detach().to(dt)                       # [B, M, P]
+        sp = self.state_proj
+        proj = torch.relu(s @ sp.fc1.weight.detach().to(dt).t() + sp.fc1.bias.detach().to(dt)) @ sp.fc2.weight.detach().to(dt).t() + sp.fc2.bias.detach().to(dt)
+        score = (emb * proj[:, None, :]).sum(dim=2)
+        k = int(k)
+        n_sel = vis.sum(dim=1).clamp(max=k)
+        if selected is None:
+            masked = torch.where(vis, score, torch.full_like(score, float("-inf")))
+            order = torch.sort(-masked, dim=1, stable=True).indices[:, :k]                                       # descending score, ascending id among equals
+            if order.shape[1] < k:
+                order = torch.cat([order, torch.zeros((B, k - order.shape[1]), dtype=order.dtype, device=dev)], 1)
+            order = torch.where(torch.arange(k, device=dev)[None] < n_sel[:, None], order, torch.full_like(order, M))
+            sel = torch.sort(order, dim=1).values
+            sel = torch.where(sel >= M, torch.full_like(sel, -1), sel)
+        else:
+            sel = torch.as_tensor(selected).to(dev).long()
+            n_sel = (sel >= 0).sum(dim=1)
+        lins = [critic.fc1, critic.fc2, critic.fc3] if hasattr(critic, "fc1") else list(critic)
+        E = 1 if n_exploits is None else int(n_exploits)
+        T = lins[0].in_features - self.state_dim - M - E - int(n_apps) if n_types is None else int(n_types)
+        W = lins[0].in_features - (T + M + E + int(n_apps))
+        if W != self.state_dim or T < 1:
+            raise ValueError(f"the critic's fc1 takes {lins[0].in_features} inputs: not the state ({self.state_dim}) plus an action vector of {T} + {M} + {E} + {int(n_apps)}")
+        w1 = lins[0].weight.detach().to(dt)
+        hs = s @ w1[:, :W].t() + lins[0].bias.detach().to(dt)
+        wa = w1[:, W:].t()                                                                                       # [n_out, H1]
+        if n_apps > 0:
+            hs = hs + wa[T + M + E]
+        dsel = sel.clamp(min=0)
+        h1 = torch.relu(hs[:, None, None, :] + wa[T + dsel][:, :, None, :] + wa[:T][None, None] + wa[T + M])      # [B, k, T, H1]
+        h2 = torch.relu(h1 @ lins[1].weight.detach().to(dt).t() + lins[1].bias.detach().to(dt))
+        q = h2 @ lins[2].weight.detach().to(dt).reshape(-1) + lins[2].bias.detach().to(dt).reshape(())
+        q = torch.nan_to_num(q, nan=-1e9, posinf=1e9, neginf=-1e9)
+        cand = torch.arange(k, device=dev)[:, None] * T + torch.arange(T, device=dev)[None]                      # the candidate's number
+        qa = torch.where((cand < S.META_MAX_CANDIDATES)[None], q, torch.full_like(q, float("-inf")))
+        atype = torch.argmax(qa, dim=2)                                                                          # first maximum
+        pad = sel < 0
+        return {"vis": vis, "deg": deg, "degn": degn, "score": score, "n_sel": n_sel, "sel": sel,
+                "q": torch.where(pad[:, :, None], torch.full_like(q, float("nan")), q), "atype": torch.where(pad, torch.full_like(atype, -1), atype)}
+
+    def packed(self):
+        """What cygym_meta_decode reads of the parameters, as a dict: base [M, ED4] (node_proj.0 applied to the id embeddings, with its
+        bias; ED4 = embed_dim rounded up to 4, zero padded), w_feat [3, ED4] (the degn / known / owned columns), state_proj transposed,
+        node_proj.2 as it is.  Built once per parameter version."""
+        mods = [self.node_proj[0], self.node_proj[2], self.state_proj.fc1, self.state_proj.fc2]
+        emb = self.struct_feats.id_emb.weight
+        ver = tuple((m.weight._version, m.weight.data_ptr(), m.bias._version) for m in mods) + (emb._version, emb.data_ptr())
+        if getattr(self, "_pk_ver", None) != ver:
+            with torch.no_grad():
+                ID, ED = self.id_dim, self.embed_dim
+                ed4 = (ED + 3) // 4 * 4
+                w0 = self.node_proj[0].weight.detach()
+                base = torch.zeros((self.M, ed4), dtype=torch.float32, device=w0.device)
+                base[:, :ED] = torch.addmm(self.node_proj[0].bias.detach(), emb.detach(), w0[:, :ID].t())
+                wf = torch.zeros((3, ed4), dtype=torch.float32, device=w0.device)
+                wf[:, :ED] = w0[:, ID:ID + 3].t()
+                c = lambda t: t.detach().contiguous()  # noqa: E731
+                sp = self.state_proj
+                self._pk = {"id_dim": ID, "embed_dim": ED, "proj_dim": self.proj_dim, "Hp": self.hidden, "base": base, "w_feat": wf,
+                            "sp_w1": c(sp.fc1.weight), "sp_b1": c(sp.fc1.bias), "sp_w2_t": sp.fc2.weight.detach().t().contiguous(), "sp_b2": c(sp.fc2.bias),
+                            "np_w2": c(self.node_proj[2].weight), "np_b2": c(self.node_proj[2].bias)}
+            self._pk_ver = ver
+        return self._pk
+
+    @torch.no_grad()
+    def h0(self, state, pack):
+        """state_proj.fc1(s) | the critic's fc1 state part + bias (+ app column) for a batch, before the relu: ONE addmm over the merged
+        pack of a MetaPolicy (`w0_t` [state_dim, Hp + H1], `b0`)."""
+        return torch.addmm(pack["b0"], state, pack["w0_t"])
+
+
+class MetaPolicy:
+    """A trained `meta` (MetaDOAR) strategy in the closed loop: MetaHierarchicalBestResponse.execute (meta_hierarchical_br.py:660-790) as
+    payoff evaluation calls it -- on a fresh object per decision, so its caches have no effect -- for a batch, as one addmm plus ONE
+    launch (cygym_meta_decode; include/cygym_abi.h states the decision).
+      critic      the role's DDPG critic of the oracle (a module with fc1 / fc2 / fc3, or three nn.Linear): the strategy carries none
+      select_k    the kept devices per decision; None: the reference's max(1, ceil(alpha log10(max(10, M))))
+      flags       "env": every row reads the flags and the added edges of its own env; a [M] uint8 flag-byte snapshot: that ONE
+                  snapshot and the base graph for every decision (what the reference's execute does in payoff evaluation: it reads
+                  the env copy made at construction, :300)
+      type_map    optional [n_types]: the reference hands the type index straight to env.step
+    It writes GROUPS (`writes_groups`), up to groups_needed(M) = select_k of them, one device each.  write() does not synchronise with
+    the host (simulate_grid may capture it in a HIP graph).  __call__ raises, like HierarchicalPolicy's."""
+
+    tick_free = True
+    writes_groups = True
+
+    def __init__(self, net: MetaNet, critic, role: str, n_types: int, n_exploits: int, n_apps: int = 0, select_k=None, alpha: float = 1.0,
+                 type_map=None, flags="env"):
+        if role not in ("defender", "attacker"):
+            raise ValueError("role must be 'attacker' or 'defender'")
+        lins = [critic.fc1, critic.fc2, critic.fc3] if hasattr(critic, "fc1") else list(critic)
+        if len(lins) != 3 or not all(isinstance(m, nn.Linear) and m.bias is not None and m.weight.dtype == torch.float32 for m in lins):
+            raise ValueError("critic: a module with fc1 / fc2 / fc3 or three nn.Linear layers (float32, with biases)")
+        self.net, self.role, self.critic, (self.fc1, self.fc2, self.fc3) = net, role, critic, lins
+        self.n_types, self.n_exploits, self.n_apps = int(n_types), int(n_exploits), int(n_apps)
+        H1, H2 = self.fc1.out_features, self.fc2.out_features
+        if H1 % 16 or H2 % 16 or not (16 <= H1 <= 128 and 16 <= H2 <= 128) or self.fc2.in_features != H1 \
+                or self.fc3.in_features != H2 or self.fc3.out_features != 1:
+            raise ValueError("critic widths: fc1 -> H1 -> H2 -> 1 with H1, H2 multiples of 16 in 16..128")
+        if not (1 <= self.n_types <= 32 and 1 <= self.n_exploits <= 6 and self.n_apps >= 0):
+            raise ValueError("1..32 action types, 1..6 exploits, n_apps >= 0")
+        if self.fc1.in_features != net.state_dim + self.n_types + net.M + self.n_exploits + self.n_apps:
+            raise ValueError(f"the critic's fc1 takes {self.fc1.in_features} inputs: not the state ({net.state_dim}) plus an action vector of "
+                             f"{self.n_types} + {net.M} + {self.n_exploits} + {self.n_apps}")
+        self.k = meta_select_k(net.M, alpha) if select_k is None else int(select_k)
+        if not 1 <= self.k <= 32:
+            raise ValueError("select_k must be in 1..32")
+        if net.M > 1000:
+            raise ValueError("at most 1000 devices (the reference's dense adjacency path)")
+        if isinstance(flags, str):
+            if flags != "env":
+                raise ValueError("flags is 'env' or a [M] flag-byte snapshot")
+            self.flags = None
+        else:
+            flags = torch.as_tensor(flags)
+            if flags.numel() != net.M:
+                raise ValueError(f"flags must hold {net.M} entries")
+            self.flags = flags.reshape(-1).to(torch.uint8).contiguous()
+        self.type_map = None if type_map is None else torch.as_tensor(type_map, dtype=torch.int32)
+        self.action_types = sorted({0} | (set(range(self.n_types)) if type_map is None else {int(x) for x in self.type_map.tolist()}))
+
+    _map = ActorPolicy._map
+
+    def groups_needed(self, M: int) -> int:
+        """The most groups (and list entries) a row can have: select_k."""
+        return self.k
+
+    @classmethod
+    def from_strategy(cls, mapping, batch, role: str, critic, n_types: int, n_exploits=None, n_apps: int = 0, select_k=None, alpha: float = 1.0,
+                      type_map=None, flags="env"):
+        """From a reference strategy's type_mapping["meta"] (or that dict itself): the three state dicts state_proj, node_proj and
+        struct_feats -- all required; the reference's silent random initialisation of a missing one is not restated -- or {"path": file}
+        for a file written by MetaNet.save (the reference's save() layout, :365-374), which also restores node_bias, select_k and M as
+        load() does (:376-388).  M and the width of the role view are checked against the batch; every table moves to the batch's device
+        here, so write() copies nothing from the host."""
+        mapping = getattr(mapping, "type_mapping", mapping)
+        mapping = mapping.get("meta", mapping)
+        if "path" in mapping:
+            data = torch.load(mapping["path"], map_location="cpu", weights_only=True)
+            if select_k is None and data.get("select_k") is not None:
+                select_k = int(data["select_k"])
+            if int(data.get("M", batch.M)) != batch.M:
+                raise ValueError(f"the strategy was trained on {int(data['M'])} devices, the batch has {batch.M}")
+            mapping = data
+        net = MetaNet.from_mapping(mapping)
+        if net.M != batch.M:
+            raise ValueError(f"the strategy was trained on {net.M} devices, the batch has {batch.M}")
+        if net.state_dim != batch.role_width(role):
+            raise ValueError(f"the strategy reads {net.state_dim} state columns, the {role} view has {batch.role_width(role)}")
+        net = net.eval().to(batch.device)
+        pol = cls(net, critic, role, n_types, batch.cfg.max_exploits if n_exploits is None else n_exploits, n_apps, select_k=select_k, alpha=alpha,
+                  type_map=type_map, flags=flags)
+        pol._packed(batch)
+        pol._map(torch.device(batch.device))
+        return pol
+
+    @torch.no_grad()
+    def _packed(self, batch):
+        """The merged tables on the batch's device: MetaNet.packed(), the critic's pack, the ONE matrix of h0(), the neighbour lists of the
+        batch's topology.  Redone when a parameter changes."""
+        device = torch.device(batch.device)
+        npk = self.net.packed()
+        ver = (_meta_topo_key(batch.topo), device) + tuple((m.weight._version, m.weight.data_ptr(), m.bias._version) for m in (self.fc1, self.fc2, self.fc3))
+        if getattr(self, "_pk_src", None) is not npk or getattr(self, "_pk_ver", None) != ver:
+            M, T, E, A = self.net.M, self.n_types, self.n_exploits, self.n_apps
+            if batch.M != M:
+                raise ValueError(f"the net was built for {M} devices, the batch has {batch.M}")
+            W = self.net.state_dim
+            w1 = self.fc1.weight.detach().to(device)
+            b1 = self.fc1.bias.detach().to(device)
+            if A > 0:
+                b1 = b1 + w1[:, W + T + M + E]                   # the app column of app index 0, once for every candidate
+            ptr, col = meta_neighbours(batch.topo)
+            pk = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in npk.items()}
+            pk.update(w0_t=torch.cat([pk["sp_w1"], w1[:, :W]]).t().contiguous(), b0=torch.cat([pk["sp_b1"], b1]).contiguous(),
+                      w1a_t=w1[:, W:].t().contiguous(), w2=batch.pack_linear(self.fc2.weight.detach().to(device)),
+                      b2=self.fc2.bias.detach().to(device).contiguous(), w3=self.fc3.weight.detach().to(device).reshape(-1).contiguous(),
+                      b3=float(self.fc3.bias.detach().reshape(-1)[0]), H1=self.fc1.out_features, H2=self.fc2.out_features,
+                      n_types=T, n_exploits=E, n_apps=A, k=self.k, nbr_ptr=ptr.to(device), nbr_col=col.to(device), nbr_len=int(col.numel()))
+            if self.flags is not None:
+                self.flags = self.flags.to(device)
+            self._pk, self._pk_src, self._pk_ver = pk, npk, ver
+        return self._pk
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, **outs):
+        """h0 = one addmm, then the whole decision + its groups into rows `rows` of the action tensors in ONE launch."""
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != self.net.state_dim:
+            raise ValueError(f"obs must be a float32 [n, {self.net.state_dim}] role view")
+        pk = self._packed(batch)
+        batch.meta_decode(rows, self.net.h0(obs, pk), pk, self.role, act=act, flags_fixed=self.flags, type_map=self._map(obs.device), **outs)
+
+    def __call__(self, obs, t, M, L):
+        raise NotImplementedError("a MetaPolicy reads the flags and the graph of the env it decides for and answers with groups: it runs "
+                                  "through write(), on a batch with cygym_meta_decode (MetaNet.decide is the torch form)")

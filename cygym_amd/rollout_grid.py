@@ -227,7 +227,7 @@ def _group_actors(batch, items, M, env_order_rpg=None):
 
 def _role_actions(batch, pol, M, L):
     """One action dict per role: the roles share every tensor but the mode words (no per-tick copy in steady state).  A role
-    with a strategy that writes groups (`writes_groups`: policies.CommActorPolicy, policies.HMARLPolicy) also gets an n_groups tensor of its own: the
+    with a strategy that writes groups (`writes_groups`: policies.CommActorPolicy, policies.HMARLPolicy, policies.MetaPolicy) also gets an n_groups tensor of its own: the
     rows its ordinary strategies play stay at 0, and the other role's ticks never see its group counts."""
     acts = {r: dict(batch.act) for r in pol}
     for r in acts:
@@ -245,7 +245,7 @@ def _role_actions(batch, pol, M, L):
                     raise ValueError(f"a {r} strategy writes groups: the batch needs max_groups >= {K - 1} and max_devs >= {M} "
                                      f"(it has max_groups = {G}, max_devs = {L})")
             for p in grouping:
-                if hasattr(p, "groups_needed"):      # a strategy that says itself how many groups a row can have (policies.HMARLPolicy)
+                if hasattr(p, "groups_needed"):      # a strategy that says itself how many groups a row can have (policies.HMARLPolicy, policies.MetaPolicy)
                     need = int(p.groups_needed(M))
                     if G < need or L < M:
                         raise ValueError(f"a {r} strategy writes up to {need} groups per row: the batch needs max_groups >= {need} and "

@@ -64,3 +64,6 @@ POISSON_TABLE = 16
 TRI_TABLE = 8
 MAX_EXPLOITS = 6
 MAX_EVENTS = 16
+
+# cygym_meta_decode: the candidate cap of execute's call, the dense adjacency path's device limit, the implemented select_k
+META_MAX_CANDIDATES, META_MAX_M, META_MAX_K = 1000, 1000, 32

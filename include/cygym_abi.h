@@ -888,8 +888,114 @@ typedef struct cygym_hmarl {
  *   0 .. n_skills - 1; a kind above CG_HMARL_SHUFFLE; fanout < 1; a negative batch_len; a budget or cost that is negative or not finite;
  *   a fallback outside 0 .. 31; a bad row count.  CYGYM_ENOTBOUND without cygym_bind.  M up to 2048.
  * Out of scope: training (_phase1 / _phase2, SubPolicyPPO, _master_update; skill_out is what that needs from this launch), the
- * sanitising of _step_env_grouped (:520-564), `meta` (meta_hierarchical_br.py), and building the logits on chip. */
+ * sanitising of _step_env_grouped (:520-564), and building the logits on chip. */
 int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_actions* dst, void* stream);
+
+/* A MetaDOAR strategy (meta_hierarchical_br.py: MetaHierarchicalBestResponse, type_mapping["meta"]) and the role's DDPG critic in the
+ * pieces the decode below reads, all fp32.  DEVICE pointers.  With id_dim, embed_dim = ED, proj_dim = P the controller is
+ *   X_i   = [struct_feats.id_emb[i] (id_dim), degn_i, known_i, owned_i]                      (:150-185; Not_yet_added is no feature)
+ *   E_i   = node_proj.2(relu(node_proj.0(X_i)))        node_proj.0: id_dim + 3 -> ED,  node_proj.2: ED -> P              (:314-318)
+ *   proj  = state_proj.fc2(relu(state_proj.fc1(s)))    fc1: state -> Hp,  fc2: Hp -> P                                  (:190-199)
+ *   score_i = E_i . proj                                (:427; the added node_bias changes no order and is not part of score_out) */
+typedef struct cygym_meta {
+  const int32_t* rows;        /* [n] env ids (rows of the action tensors) to write; NULL = rows 0..n-1                                       */
+  const float* h0;            /* [n][h0_stride] per SOURCE row, BEFORE the relu: state_proj.fc1(s) (Hp floats) | the critic's b1 + W1[:, :W] s
+                                 (H1 floats; PLUS the action column of app index 0 when n_apps > 0).  One addmm of the caller               */
+  const float* sp_w2_t;       /* [Hp][P] state_proj.fc2.weight transposed                                                                    */
+  const float* sp_b2;         /* [P] state_proj.fc2.bias                                                                                     */
+  const float* base;          /* [M][ED4], ED4 = ED rounded up to 4, 16-byte aligned: base[i][e] = node_proj.0.bias[e] + node_proj.0.weight[e][:id_dim]
+                                 . id_emb[i] (a per-policy table, any summation: it is an INPUT of the contract); 0 in the padding          */
+  const float* w_feat;        /* [3][ED4] the columns id_dim, id_dim + 1, id_dim + 2 of node_proj.0.weight (degn, known, owned); 0 padded     */
+  const float* np_w2;         /* [P][ED] node_proj.2.weight as torch holds it                                                                */
+  const float* np_b2;         /* [P] node_proj.2.bias                                                                                        */
+  const int32_t* nbr_ptr;     /* [M + 1] row pointers of ...                                                                                 */
+  const uint16_t* nbr_col;    /* ... the symmetric neighbour lists of the handle's topology: row i = {i} u out(i) u in(i), every id ONCE,
+                                 ascending -- the rows of the reference's adjacency A (:74-109: the edge list symmetrised plus the identity,
+                                 entries SET to 1, so duplicate and reciprocal edges count once)                                            */
+  const uint8_t* flags_fixed; /* NULL: source row r reads the flag bytes and the extra-edge list of env rows[r]; else ONE [M] flag-byte
+                                 snapshot (CG_F_KNOWN / CG_F_OWNED / CG_F_NYA are read) for every row, base lists only                       */
+  const int32_t* type_map;    /* optional [n_types]: action type of type index t (the reference hands the index to env.step)                 */
+  const float* w1a_t;         /* the critic as in cygym_critic: [n_out][H1] action part of fc1, transposed; n_out = n_types + M + n_exploits + n_apps */
+  const float* w2;            /* fc2.weight PACKED (pack_linear): [H2 / 16][H1 / 16][64][4], 16-byte aligned                                 */
+  const float* b2;            /* [H2] or NULL                                                                                                */
+  const float* w3;            /* [H2] fc3.weight                                                                                             */
+  float*   score_out;         /* optional [n][M]: score_i of source row r (every device, visible or not)                                     */
+  int32_t* selected_out;      /* optional [n][k]: the kept devices in ascending id, -1 behind them                                           */
+  float*   q_out;             /* optional [n][k][n_types]: Q of (kept device j, type t), after nan_to_num; slots j >= the kept count are NOT
+                                 written.  A candidate behind the CG_META_MAX_CANDIDATES-th is written too, but cannot be chosen             */
+  int32_t* deg_out;           /* optional [n][M]: the row sums deg_i                                                                          */
+  uint32_t* status;           /* optional, ONE word: CG_DECODE_TRUNCATED as in cygym_hmarl                                                    */
+  float    b3;                /* fc3.bias                                                                                                    */
+  int32_t  n;                 /* source rows                                                                                                 */
+  int32_t  role;              /* 1 defender, 2 attacker                                                                                      */
+  int32_t  k;                 /* select_k, 1 .. 32                                                                                           */
+  int32_t  n_types, n_exploits, n_apps;   /* the layout of the critic's action vector: 1 .. 32 types, 1 .. CG_MAX_EXPLOITS, >= 0              */
+  int32_t  id_dim, embed_dim, proj_dim;   /* 1 .. 32, 1 .. 64, 1 .. 64 (id_dim documents `base`; the kernel does not read it)                 */
+  int32_t  Hp;                /* width of state_proj.fc1, 1 .. 256                                                                           */
+  int32_t  H1, H2;            /* the critic's widths, multiples of 16 in 16 .. 128                                                            */
+  int32_t  h0_stride;         /* floats per row of h0, >= Hp + H1                                                                            */
+} cygym_meta;
+
+/* Replaces: MetaHierarchicalBestResponse.execute (meta_hierarchical_br.py:660-790) as payoff evaluation calls it -- on a FRESH object
+ * per decision (do_agent.py:224-226, :727-728) -- with build_visibility_mask (:122-137), adjacency_matrix_from_env / _feature_adjacency
+ * (:25-119, the dense path), StructuralNodeFeaturizer.forward_indices (:150-185), select_devices (:415-446),
+ * _batch_score_candidates_with_cache (:480-633) and _top_candidate_per_node (:638-655), for a batch, in ONE launch, fused with the scatter
+ * into the action tensors as GROUPS (cygym_group_actions' layout: n_groups, the groups' atype / n_exploit = 1 / exploit[.][0] = 0 /
+ * app = 0 / dev_cnt = 1 and the device ids concatenated in dev_idx; `mode` is not touched).
+ * On a fresh object node_dirty is all ones (every embedding is recomputed, :683-685), the Q cache is empty (no hit, no TTL test, no
+ * random.random() resample draw) and _cache_step is 1 (no flush): the LRU cache, the k-hop invalidation and _last_selection have no
+ * effect on the returned action, execute is a pure function of (weights, state, flags, adjacency, critic), and that function is what
+ * is restated here.  Per source row r (env e = rows[r]; f[d] its flag byte, or flags_fixed[d]):
+ * 1. Visibility (:122-137, this file's own mask, NOT the role view's): attacker KNOWN && OWNED && !NYA; defender !NYA && !OWNED.
+ *    (The reference defines _feature_adjacency at module level, :25, and calls it as a method, :397 -- as shipped that call raises
+ *    AttributeError; the function is restated as the method it was written to be.)
+ * 2. Degree.  deg_i = the number of ids in row i of nbr, for the defender; for the attacker the number of VISIBLE ids in it when i is
+ *    visible, else 0 (A masked on rows and columns, :63-68).  In env mode every entry (a, b) of e's extra-edge list
+ *    (cygym_buffers.extra, the count in CG_I_FLAGS) adds 1 to deg_a and deg_b when a != b, the unordered pair {a, b} is neither in the
+ *    base lists nor earlier in the list (a repeated or reciprocal entry counts once), and -- attacker -- both ends are visible.
+ *    degn_i = (float) deg_i / (float) max_j deg_j when that maximum is positive (:163-164), else (float) deg_i: the correctly rounded
+ *    fp32 quotient (IEEE division), bit-equal to torch's.
+ * 3. Score, in fp32 with fused multiply-adds, every sum in ASCENDING index from the stated start:
+ *      hr_j   = relu(h0[r][j])                                            j < Hp   (x < 0 ? 0 : x)
+ *      proj_p = fma(sp_w2_t[j][p], hr_j, .)  over j,  start sp_b2[p]
+ *      u_e    = fma(np_w2[p][e], proj_p, .)  over p,  start 0;        c = fma(np_b2[p], proj_p, .) over p, start 0
+ *      x_ie   = fma(w_feat[0][e], degn_i, base[i][e]), then + w_feat[1][e] when KNOWN, then + w_feat[2][e] when OWNED
+ *      score_i = fma(relu(x_ie), u_e, .)     over e,  start c
+ *    i.e. node_proj.2 is folded into the row (E_i . proj = c + sum_e relu(x_ie) u_e): M ED multiply-adds per row, not M ED P.  The
+ *    reference sums E_i first; the two agree within the fp32 bound the tests derive, and exactly on integer-valued weights.
+ * 4. Selection (:435-446): the min(k, |V|) visible devices with the largest scores; only the SET reaches the action.  Deviation where
+ *    np.argpartition is unspecified: min(k, |V|) rounds of arg-max on (order bits of the fp32 score, ascending id among equals) -- it
+ *    matters only for exact ties at the k-th place.  +0 and -0 tie.  Non-finite scores are ordered by their bit pattern as in
+ *    cygym_hmarl_decode (+inf and NaN with a clear sign bit above, -inf and NaN with the sign bit below every finite value); this is not
+ *    pinned to the reference, and a valid row is written in any case.
+ * 5. Nothing visible (:699-717): the low-level policy's groups are filtered by the EMPTY allowed set, so the action is exactly
+ *    [(0, [0], [], 0)] -- n_groups = 1, atype the literal 0 (NOT type_map[0]), dev_cnt 0; the actor is never needed.
+ * 6. Candidates (:516-523 with max_exploit_candidates = 1): per kept device d in ascending id, per type index t = 0 .. n_types - 1 the
+ *    tuple (t, [0], [d], 0), encoded by encode_action (do_agent.py:910-933; the exploit [0] is in range, so the exploit / device swap of
+ *    :919-920 never fires): ones at t, n_types + d, n_types + M + 0 and, when n_apps > 0, n_types + M + n_exploits + 0.  Scored by the
+ *    role's critic of the ORACLE (do_agent.py:373-388), not one carried in the strategy, in the scheme of cygym_coord_ascent_decode:
+ *    the fc1 pre-activation is ((h_state + device column) + type column) + exploit-0 column, h_state = the second block of h0 (the
+ *    caller has added the app column); relu; fc2 on the matrix cores (fp32 in and out, k ascending in groups of four); relu(. + b2);
+ *    the fc3 dot; + b3; then nan_to_num(NaN -> -1e9, +-inf -> +-1e9).  The reference has no nan_to_num here: for a finite Q it is the
+ *    identity, non-finite Q values are not pinned.  Candidate number c = j n_types + t (j = the device's place among the kept ones) is
+ *    scored only while c < CG_META_MAX_CANDIDATES (:575-583): at k = 32, n_types = 32 the last device keeps its types 0 .. 7.
+ * 7. Per kept device the FIRST maximum over its scored types (:638-655, strict >, ascending t), through type_map when given.
+ * 8. Action (:759-763): group j = (t*, [0], [d_j], 0), devices ascending.  It reaches env.step as a list, i.e. step_grouped, where only
+ *    types 1, 2, 3, 10, 11 act and attacker groups are no-ops.  Kept: it is the reference.
+ * Cut, as cygym_hmarl_decode: groups >= max_groups and list entries >= max_devs are not written (such a group's dev_cnt is 0),
+ * either raises CG_DECODE_TRUNCATED; n_groups = min(groups, max_groups); nothing is written behind a row's groups or entries, and no
+ * other row is touched.  A row needs min(k, M) groups and as many list entries.
+ * The decode makes NO draw: the rng tick is neither read nor advanced.  flags_fixed != NULL needs no bound handle and reads nothing of
+ * the bound state: this is the reference's execute, which reads the deep copy of oracle.env made at construction (:300), not the
+ * stepped env.  flags_fixed == NULL (the stepped env's own flags and added edges) needs cygym_bind.
+ * CYGYM_EINVAL (nothing is written): a NULL handle, struct, destination array (n_groups included) or required pointer; role outside
+ *   1 / 2; h0_stride < Hp + H1; base / w_feat / w2 not 16-byte aligned; n_types, n_exploits < 1 or n_apps < 0; a bad row count.
+ * CYGYM_EUNSUPPORTED (nothing is written): M > 1000 (the reference switches to a sparse path whose coalesce counts reciprocal edges
+ *   twice: a different function); k outside 1 .. 32; n_types > 32; n_exploits > CG_MAX_EXPLOITS; id_dim outside 1 .. 32; embed_dim or
+ *   proj_dim outside 1 .. 64; Hp outside 1 .. 256; H1 or H2 not a multiple of 16 in 16 .. 128.
+ * Out of scope: train / train_controller / the observer mode of ddpg_best_response (score_out, selected_out, q_out and deg_out are what
+ *   a controller update needs from this launch), M > 1000, exploit_override, the `committee` mapping, and the cache itself. */
+int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions* dst, void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`

@@ -275,6 +275,10 @@ CYGYM_HD int cg_cdf_lookup(uint32_t u, const uint64_t* thr, int n) {
 #define CG_POISSON_TABLE 16   /* thresholds kept for np.random.poisson       */
 #define CG_TRI_TABLE 8        /* thresholds kept for ceil(triangular(0,m,h)) */
 #define CG_MAX_EXPLOITS 6     /* CyberDefenseEnv.py:48 (MaxExploits)         */
+/* cygym_meta_decode (meta_hierarchical_br.py) */
+#define CG_META_MAX_CANDIDATES 1000   /* max_total_candidates of execute's call (:755): candidates behind the 1000th are not scored */
+#define CG_META_MAX_M 1000            /* adjacency_matrix_from_env's dense path (:100); above it the reference is a different function */
+#define CG_META_MAX_K 32              /* select_k the decode implements                                                               */
 #define CG_MAX_EVENTS 16      /* evolve events per call (Poisson table cap)  */
 
 #endif /* CYGYM_SPEC_H */
