@@ -65,10 +65,12 @@ __device__ __forceinline__ int spread_scan_lane(const Env& e, const TW* T, int s
   }
   return o1;
 }
-// The same with v / low = the device and the constant low bits of T[v], STAGED (run-time sizes, where one resident wave
-// per SIMD leaves every LDS round trip exposed; at 256 devices with 4 waves per SIMD it measured -1 %): the row's blocked words and its first four neighbours are read together, then the four T words -- two LDS
-// round trips for the usual two- or three-slot row instead of two per slot.
-template <class TW>
+// The same with v / low = the device and the constant low bits of T[v], STAGED: the row's blocked words and its first NSS
+// neighbours are read together, then their T words -- two LDS round trips for the usual two- or three-slot row instead of
+// two per slot; slots behind the staged ones are walked one by one.  NSS = 4: sweep 0 at the run-time sizes, where one
+// resident wave per SIMD leaves every LDS round trip exposed (at 256 devices with 4 waves per SIMD it measured -1 %).
+// NSS = 1: the rescans of attacker_spread_ct's verification sweeps (see there).
+template <int NSS = 4, class TW>
 __device__ __forceinline__ int spread_scan_lane_st(const Env& e, const TW* T, int s, bool dc,
                                                 int from, int o1, int& v, uint32_t& low) {
   if (from >= o1) return o1;
@@ -76,23 +78,23 @@ __device__ __forceinline__ int spread_scan_lane_st(const Env& e, const TW* T, in
   const int w0 = from >> 5;
   const bool two = ((o1 - 1) >> 5) != w0;
   const uint32_t b_lo = e.blk[w0], b_hi = e.blk[two ? w0 + 1 : w0];
-  int vv[4];
+  int vv[NSS];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) vv[j] = e.ocol[from + j < o1 ? from + j : o1 - 1];
-  uint32_t tt[4];
+  for (int j = 0; j < NSS; ++j) vv[j] = e.ocol[from + j < o1 ? from + j : o1 - 1];
+  uint32_t tt[NSS];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) tt[j] = T[vv[j]];
+  for (int j = 0; j < NSS; ++j) tt[j] = T[vv[j]];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) PIN(tt[j]);
+  for (int j = 0; j < NSS; ++j) PIN(tt[j]);
   uint64_t bits = (uint64_t)b_lo | (two ? (uint64_t)b_hi << 32 : 0ull);
   bits >>= (from & 31);   // bit i <-> slot from + i
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < NSS; ++j) {
     const bool okv = (tt[j] & 1u) || ((tt[j] & 2u) && ((tt[j] >> 2) >= (uint32_t)(s + 1)));
     if (from + j < o1 && !((bits >> j) & 1ull) && (dc || okv)) { v = vv[j]; low = tt[j] & 3u; return from + j; }
   }
-  bits >>= 4;
-  for (int k = from + 4; k < o1; ++k, bits >>= 1) {
+  bits >>= NSS;
+  for (int k = from + NSS; k < o1; ++k, bits >>= 1) {
     if (bits & 1ull) continue;
     const int vk = e.ocol[k];
     const uint32_t tk = T[vk];
@@ -604,7 +606,7 @@ __device__ __forceinline__ void attacker_spread(Env& e, const KP& P, const int32
 //     ascending) rides in the same stages -- its first candidate comes from the candidate masks (uniform), so its
 //     stage-3 / 4 reads are the blocked word and T word of that one slot;
 //   * a verification sweep (only after a conflict) is ONE round trip for all blocks -- the T words of the picks -- and
-//     only the sources that lost theirs rescan.
+//     only the sources that lost theirs rescan, a short row with one staged slot (spread_scan_lane_st<1>).
 template <int MCT, bool WIDE, class KP>
 __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const int32_t* expl, int ex0, int n_expl) {
   const int M = e.M, E1 = P.t.E > 0 ? P.t.E - 1 : 0;
@@ -782,9 +784,18 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
         const bool full = !shortrow && (st & CG_D_FULLROW);
         int k = k0, v = (int)(pkv[b] >> 16);
         if (lost && (shortrow || full)) {
-          if (shortrow) { k = spread_scan_lane(e, T, s, false, k0 + 1, o1); v = k < o1 ? (int)e.ocol[k] : 0; }
-          else { k = spread_scan_full(e, T, cand, s, k0 + 1, o0, o1); v = k < o1 ? (k - o0) + ((k - o0) >= s ? 1 : 0) : 0; }
-          if (k < o1 && spread_take_c(T, v, s, T[v] & 3u)) lost_any = true;
+          // A short row rescans in stages: [blocked pair + the next neighbour] -> [its T word] -> take, and the scan hands back
+          // the device and its low bits (no second read of ocol[k] and T[v]): three dependent round trips for the usual
+          // two-slot row where the slot-by-slot scan took six.  ONE staged slot: this late in the launch the env is nearly
+          // alone on its CU and an LDS trip is cheap next to the instructions around it -- staged at four slots a sweep
+          // measured 180 cycles SLOWER than the slot-by-slot scan, at three +20, at two -120, at one -480 (PERFLOG.md).
+          uint32_t low = 0;
+          if (shortrow) { v = 0; k = spread_scan_lane_st<1>(e, T, s, false, k0 + 1, o1, v, low); }
+          else {
+            k = spread_scan_full(e, T, cand, s, k0 + 1, o0, o1); v = k < o1 ? (k - o0) + ((k - o0) >= s ? 1 : 0) : 0;
+            if (k < o1) low = T[v] & 3u;
+          }
+          if (k < o1 && spread_take_c(T, v, s, low)) lost_any = true;
         }
         uint64_t nm = ballot(lost && !shortrow && !full);
         while (nm) {

@@ -259,19 +259,38 @@ constexpr bool karg_line_needed(int i) {
       || hit(offsetof(KParams, b), offsetof(KParams, snap) + 8)
       || hit(offsetof(KParams, a), sizeof(KParams));
 }
-// One dword of every needed line from I on, requested (results unused) / their registers named as still in use.
+// One dword of every needed line from I on, requested BEHIND the hot block's wait (the lines are for later phases: in front of
+// that wait they only lengthened it).  The results are unused, so every request targets the same scratch SGPR `ks`: the first one
+// defines it, the others are tied to it ("+s"), and it stays allocated until karg_prefetch_done -- the statement that waits for the
+// requests -- so no load is in flight into a register the compiler holds to be free.  (A spill of `ks` in between would break
+// that; tests/test_prologue_wait_isa_cpu.py reads the assembly for it.)
+template <int I, int N, bool FIRST = true>
+__device__ __forceinline__ void karg_prefetch(uint64_t kb, uint32_t& ks) {
+  if constexpr (I < N) {
+    if constexpr (karg_line_needed(I)) {
+      if constexpr (FIRST) asm volatile("s_load_dword %0, %1, %2" : "=&s"(ks) : "s"(kb), "n"(64 * I));
+      else asm volatile("s_load_dword %0, %1, %2" : "+s"(ks) : "s"(kb), "n"(64 * I));
+      karg_prefetch<I + 1, N, false>(kb, ks);
+    } else karg_prefetch<I + 1, N, FIRST>(kb, ks);
+  }
+}
+// Ends the scratch register's live range and carries the wait for the requests itself.  It stands right behind the staging
+// barrier: the compiler's own full wait in front of s_barrier has drained the scalar queue by then, so this one costs nothing.
+__device__ __forceinline__ void karg_prefetch_done(uint32_t& ks) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(ks) :: "memory"); }
+// The full-feature kernels keep the earlier form: the requests in FRONT of the hot block, one register each, under its wait
+// (their registers named as still in use behind it).
 template <int I, int N>
-__device__ __forceinline__ void karg_prefetch(uint64_t kb, uint32_t* kpf) {
+__device__ __forceinline__ void karg_prefetch_front(uint64_t kb, uint32_t* kpf) {
   if constexpr (I < N) {
     if constexpr (karg_line_needed(I)) asm volatile("s_load_dword %0, %1, %2" : "=&s"(kpf[I]) : "s"(kb), "n"(64 * I));
-    karg_prefetch<I + 1, N>(kb, kpf);
+    karg_prefetch_front<I + 1, N>(kb, kpf);
   }
 }
 template <int I, int N>
-__device__ __forceinline__ void karg_prefetch_done(const uint32_t* kpf) {
+__device__ __forceinline__ void karg_prefetch_front_done(const uint32_t* kpf) {
   if constexpr (I < N) {
     if constexpr (karg_line_needed(I)) asm volatile("" :: "s"(kpf[I]));
-    karg_prefetch_done<I + 1, N>(kpf);
+    karg_prefetch_front_done<I + 1, N>(kpf);
   }
 }
 typedef uint32_t cg_s16v __attribute__((ext_vector_type(16)));

@@ -24,24 +24,32 @@
     pk = (KPT*)(((uint64_t)phi << 32) | plo);
   }
 #define P (*pk)
-  // the prologue's own fields (KHot, cg_params.hpp).  Compile-time sizes: every OTHER 64-byte line of the argument that a
-  // common tick reads is requested first (one dword each, results unused): the tick body reads its ~150 scalars through the
-  // laundered pointer next to their uses, and the first touch of each of the block's ~20 lines was a cold miss of the
-  // scalar cache in the middle of some phase (observation pointers, config doubles, ...: ~700 cycles each, for every wave of
-  // the batch at once).  Then the hot block itself, and one wait for all of it (hot_batch, cg_tick.hpp): scalar loads
-  // return out of order, so every wait on them is a wait for all of them.
-  // (run-time sizes read the block by name through the plain kernarg pointer: the registers of the line requests, held
+  // the prologue's own fields (KHot, cg_params.hpp).  Compile-time sizes: the hot block itself, and one wait for all of it
+  // (hot_batch, cg_tick.hpp): scalar loads return out of order, so every wait on them is a wait for all of them.  Right
+  // behind that wait every OTHER 64-byte line of the argument that a common tick reads is requested (one dword each, results
+  // unused, karg_prefetch): the tick body reads its ~150 scalars through the laundered pointer next to their uses, and the
+  // first touch of each of the block's ~20 lines was a cold miss of the scalar cache in the middle of some phase (observation
+  // pointers, config doubles, ...: ~700 cycles each, for every wave of the batch at once).  The requests are outstanding
+  // while the gather and DMA addresses issue; nothing in front of the staging barrier reads LDS or a scalar, so the next
+  // wait they meet is the one the barrier has anyway (entry -> behind the barrier: -110 cycles at the median, PERFLOG.md).
+  // (the full-feature kernels keep the requests in front of the hot block: not measured there; run-time sizes read the block by name through the plain kernarg pointer: the registers of the line requests, held
   // through the prologue, cost more there than the misses -- 4096 x 2048: +5 % without)
   using KHT = const __attribute__((address_space(4))) KHot;
   KHT* const hk = (KHT*)__builtin_amdgcn_kernarg_segment_ptr();
   KHot hp;
+  [[maybe_unused]] uint32_t kscr = 0;   // scratch target of the line requests: allocated from the requests to behind the barrier
   if constexpr (MT != 0) {
     constexpr int KARG_LINES = (int)((sizeof(KParams) + 63) / 64);
     const uint64_t kb = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t kpf[KARG_LINES];
-    karg_prefetch<4, KARG_LINES>(kb, kpf);   // (lines 0..3 are the hot block)
-    hot_batch<XE>(kb, hp);
-    karg_prefetch_done<4, KARG_LINES>(kpf);   // (their registers were reserved up to here)
+    if constexpr (XE) {   // (full-feature kernels: the line requests in front of the hot block, under its wait)
+      uint32_t kpf[KARG_LINES];
+      karg_prefetch_front<4, KARG_LINES>(kb, kpf);   // (lines 0..3 are the hot block)
+      hot_batch<XE>(kb, hp);
+      karg_prefetch_front_done<4, KARG_LINES>(kpf);   // (their registers were reserved up to here)
+    } else {
+      hot_batch<XE>(kb, hp);
+      karg_prefetch<4, KARG_LINES>(kb, kscr);
+    }
   }
 #define H (hot_sel<MT != 0>(hp, *hk))
   const int M = MT ? MT : H.t.M, MC = MT ? (MT + WAVE - 1) / WAVE : H.t.MC, Mp = MC * WAVE, MS = (M + 3) & ~3;
@@ -257,6 +265,7 @@
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_back) :: "memory");
 #endif
   __syncthreads();   // the only workgroup barrier: waves diverge per env from here on
+  if constexpr (MT != 0 && !XE) karg_prefetch_done(kscr);   // (the line requests' register is free from here on)
   if (!live) return;
   STAMP(1);
 #ifdef CG_STAMPS
