@@ -188,6 +188,14 @@ class Meta(C.Structure):
                 ("H1", C.c_int32), ("H2", C.c_int32), ("h0_stride", C.c_int32)]
 
 
+class MetaSelect(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("h0", C.c_void_p), ("sp_w2_t", C.c_void_p), ("sp_b2", C.c_void_p), ("base", C.c_void_p), ("w_feat", C.c_void_p),
+                ("np_w2", C.c_void_p), ("np_b2", C.c_void_p), ("nbr_ptr", C.c_void_p), ("nbr_col", C.c_void_p), ("snap_degn", C.c_void_p),
+                ("snap_flags", C.c_void_p), ("snap_valid", C.c_void_p), ("selected_out", C.c_void_p), ("ebar_out", C.c_void_p),
+                ("score_out", C.c_void_p), ("deg_out", C.c_void_p), ("n", C.c_int32), ("role", C.c_int32), ("k", C.c_int32), ("id_dim", C.c_int32),
+                ("embed_dim", C.c_int32), ("proj_dim", C.c_int32), ("Hp", C.c_int32), ("h0_stride", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

@@ -973,6 +973,60 @@ class BatchedCyberDefenseEnv:
         r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
         _lib.check(self.lib.cygym_meta_decode(self._h, C.byref(q), C.byref(dst), self._stream()), self._h, "cygym_meta_decode")
 
+    def meta_select(self, rows, h0: torch.Tensor, pack, role: str = "defender", snapshot=None, selected_out=None, ebar_out=None,
+                    score_out=None, deg_out=None):
+        """The MetaDOAR observer's selection while a DDPG best response trains (do_agent.py:1342-1361 -> select_devices,
+        meta_hierarchical_br.py:415-446, with its embedding cache) for the envs `rows`: ONE launch (cygym_meta_select;
+        include/cygym_abi.h states the decision and the arithmetic).  It writes no action tensor and makes no draw.
+          h0        [n, >= Hp] float32 (unit inner stride): state_proj.fc1(s) before the relu (the first Hp floats of a row are read)
+          pack      MetaNet.packed() on the batch's device plus nbr_ptr / nbr_col / nbr_len (policies.meta_neighbours) and k
+          snapshot  None: live features every time (what cygym_meta_decode computes); else (degn float32 [N, M], flags uint8 [N, M],
+                    valid uint8 [N]), contiguous: an env with valid == 0 has its features taken and stored, any other reads them from
+                    there.  With a snapshot an env may appear at most once in `rows` (not checked: it would need a host read)
+          outputs   contiguous: selected_out int32 [n, k] (made when None), ebar_out float32 [n, P], score_out float32 [n, M], deg_out
+                    int32 [n, M] (written only for rows whose features are computed in this launch)
+        Returns selected_out.  Limits: M <= 1000, k <= 32, id_dim <= 32, embed_dim, proj_dim <= 64, Hp <= 256."""
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
+            raise ValueError("h0 must be a [n, >= Hp] float32 tensor on the batch's device with unit inner stride")
+        n, M, k = int(h0.shape[0]), self.M, int(pack["k"])
+        ID, ED, P, Hp = (int(pack[x]) for x in ("id_dim", "embed_dim", "proj_dim", "Hp"))
+        if int(h0.shape[1]) < Hp:
+            raise ValueError(f"h0 rows hold {int(h0.shape[1])} floats: fewer than Hp = {Hp}")
+        ed4 = (ED + 3) // 4 * 4
+        q = abi.MetaSelect()
+        for name, want in {"sp_w2_t": Hp * P, "sp_b2": P, "base": M * ed4, "w_feat": 3 * ed4, "np_w2": P * ED, "np_b2": P}.items():
+            t = pack[name]
+            if not ok(t) or not t.is_contiguous() or int(t.numel()) != want:
+                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device}")
+            setattr(q, name, t.data_ptr())
+        ptr, col = pack["nbr_ptr"], pack["nbr_col"]
+        if ptr.dtype != torch.int32 or ptr.device != self.device or not ptr.is_contiguous() or int(ptr.numel()) != M + 1:
+            raise ValueError(f"pack['nbr_ptr'] must be a contiguous int32 [{M + 1}] tensor on {self.device}")
+        if col.dtype != torch.int16 or col.device != self.device or not col.is_contiguous() or int(col.numel()) != int(pack["nbr_len"]):
+            raise ValueError(f"pack['nbr_col'] must be a contiguous int16 [{int(pack['nbr_len'])}] tensor on {self.device} (policies.meta_neighbours)")
+        q.nbr_ptr, q.nbr_col = ptr.data_ptr(), col.data_ptr()
+        q.role, q.k, q.id_dim, q.embed_dim, q.proj_dim, q.Hp = _role(role)["code"], k, ID, ED, P, Hp
+        q.h0, q.h0_stride = h0.data_ptr(), int(h0.stride(0)) if n > 1 else int(h0.shape[1])
+        if snapshot is not None:
+            snapshot = tuple(snapshot)
+            shapes = (((self.N, M), torch.float32), ((self.N, M), torch.uint8), ((self.N,), torch.uint8))
+            if len(snapshot) != 3 or any(t.dtype != dt or t.device != self.device or tuple(t.shape) != sh or not t.is_contiguous()
+                                         for t, (sh, dt) in zip(snapshot, shapes)):
+                raise ValueError(f"snapshot must be contiguous (float32 [{self.N}, {M}], uint8 [{self.N}, {M}], uint8 [{self.N}]) tensors on {self.device}")
+            q.snap_degn, q.snap_flags, q.snap_valid = (t.data_ptr() for t in snapshot)
+        if selected_out is None:
+            selected_out = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        for name, t, shape, dt in (("selected_out", selected_out, (n, k), torch.int32), ("ebar_out", ebar_out, (n, P), torch.float32),
+                                   ("score_out", score_out, (n, M), torch.float32), ("deg_out", deg_out, (n, M), torch.int32)):
+            if t is not None:
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
+                setattr(q, name, t.data_ptr())
+        r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
+        _lib.check(self.lib.cygym_meta_select(self._h, C.byref(q), self._stream()), self._h, "cygym_meta_select")
+        return selected_out
+
     def _hier_loss(self, score, atype_logits, dev_logits, vis, part_of, n_parts, part, atype, dec):
         f32 = lambda t: t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()  # noqa: E731
         if not f32(score) or score.dim() != 2:

@@ -52,6 +52,7 @@ INST_COMM = os.path.join(HERE, "csrc", "cg_inst_comm.hip")
 INST_HIER = os.path.join(HERE, "csrc", "cg_inst_hier.hip")
 INST_HMARL = os.path.join(HERE, "csrc", "cg_inst_hmarl.hip")
 INST_META = os.path.join(HERE, "csrc", "cg_inst_meta.hip")
+INST_META_SELECT = os.path.join(HERE, "csrc", "cg_inst_meta_select.hip")
 INST_EVAL = os.path.join(HERE, "csrc", "cg_inst_eval.hip")
 INST_DDPG = os.path.join(HERE, "csrc", "cg_inst_ddpg.hip")
 N_GROUPS = 8   # CG_INST_GROUPS of csrc/cg_device.hpp
@@ -82,6 +83,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         units.append(("inst_hier", base + ["-c", INST_HIER, "-o", os.path.join(tmp, "inst_hier.o")]))   # the hierarchical (HAGS) decode
         units.append(("inst_hmarl", base + ["-c", INST_HMARL, "-o", os.path.join(tmp, "inst_hmarl.o")]))   # the H-MARL decode
         units.append(("inst_meta", base + ["-c", INST_META, "-o", os.path.join(tmp, "inst_meta.o")]))   # the MetaDOAR decode
+        units.append(("inst_meta_select", base + ["-c", INST_META_SELECT, "-o", os.path.join(tmp, "inst_meta_select.o")]))   # its observer's selection
         units.append(("inst_eval", base + ["-c", INST_EVAL, "-o", os.path.join(tmp, "inst_eval.o")]))   # its evaluate / backward (the PPO update)
         units.append(("inst_ddpg", base + ["-c", INST_DDPG, "-o", os.path.join(tmp, "inst_ddpg.o")]))   # the critic's tail and its backward (the DDPG update)
 

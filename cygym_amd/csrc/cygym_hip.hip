@@ -92,6 +92,12 @@ extern template __global__ void meta_kernel<false>(cygym_meta, cygym_actions, in
 extern template __global__ void meta_kernel<true>(cygym_meta, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
 }  // namespace cygym_k
 
+// the MetaDOAR observer's selection lives in its own unit (cg_inst_meta_select.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void meta_select_kernel<false>(cygym_meta_select_desc, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
+extern template __global__ void meta_select_kernel<true>(cygym_meta_select_desc, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
+}  // namespace cygym_k
+
 // the evaluate / backward kernels of the PPO update live in their own unit (cg_inst_eval.hip): declared, not instantiated, here
 namespace cygym_k {
 extern template __global__ void comm_eval_fwd_kernel<1, false>(cygym_comm_eval);
@@ -251,6 +257,7 @@ int cygym_sizeof(int32_t which) {
     case 20: return (int)sizeof(cygym_hier_loss_desc);
     case 21: return (int)sizeof(cygym_hmarl);
     case 23: return (int)sizeof(cygym_meta);   // (index 22 stays unassigned)
+    case 25: return (int)sizeof(cygym_meta_select_desc);   // (index 24 stays unassigned)
     default: return -1;
   }
 }
@@ -1012,6 +1019,35 @@ int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions*
   const uint32_t* extra = env_mode && h->t.K > 0 ? (const uint32_t*)h->b.extra : nullptr;
   int K = h->t.K, M = h->t.M;
   return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &extra, &K, &M});
+}
+
+int cygym_meta_select(cygym_handle* h, const cygym_meta_select_desc* q, void* stream) {
+  const char* const who = "cygym_meta_select";
+  if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
+  if (!q || !q->h0 || !q->sp_w2_t || !q->sp_b2 || !q->base || !q->w_feat || !q->np_w2 || !q->np_b2 || !q->nbr_ptr || !q->nbr_col || !q->selected_out)
+    return fail(h, CYGYM_EINVAL, "%s: null pointer", who);
+  const int n_snap = (q->snap_degn != nullptr) + (q->snap_flags != nullptr) + (q->snap_valid != nullptr);
+  if (n_snap != 0 && n_snap != 3) return fail(h, CYGYM_EINVAL, "%s: the snapshot is snap_degn, snap_flags and snap_valid together, or none of them", who);
+  if ((q->role != 1 && q->role != 2) || q->Hp < 1 || q->h0_stride < q->Hp || (((uintptr_t)q->base | (uintptr_t)q->w_feat) & 15))
+    return fail(h, CYGYM_EINVAL, "%s: bad layout (role 1 or 2, Hp >= 1, h0_stride >= Hp, 16-byte aligned base / w_feat)", who);
+  if (h->t.M > MT_MAX_M) return fail(h, CYGYM_EUNSUPPORTED, "%s: at most 1000 devices (the reference's dense adjacency path)", who);
+  if (q->k < 1 || q->k > MT_MAX_K || q->id_dim < 1 || q->id_dim > MT_MAX_ID || q->embed_dim < 1 || q->embed_dim > MT_MAX_ED || q->proj_dim < 1 ||
+      q->proj_dim > MT_MAX_P || q->Hp > MT_MAX_HP)
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: k 1 .. 32, id_dim 1 .. 32, embed_dim, proj_dim 1 .. 64, Hp 1 .. 256", who);
+  if (!h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (the flags and the added edges are read off the bound state)", who);
+  if (const int rc = check_rows(h, q->n, q->rows, 0, who)) return rc;
+  if (q->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const MsPlan pl = ms_plan(q->embed_dim, q->Hp, h->t.M);
+  const int wpb = ms_waves(pl, CG_LDS_BYTES);
+  const size_t lds = (size_t)(pl.wave0 + wpb * pl.wave_pitch) * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: a row's buffers do not fit in LDS", who);
+  const void* k = q->ebar_out ? (const void*)meta_select_kernel<true> : (const void*)meta_select_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const uint8_t* live = (const uint8_t*)h->b.live;
+  const uint32_t* extra = h->t.K > 0 ? (const uint32_t*)h->b.extra : nullptr;
+  int K = h->t.K, M = h->t.M;
+  return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q}, {&live, &extra, &K, &M});
 }
 
 // What the two evaluate calls check alike, in the order of the decodes' shared check: handle, pointers, layout (CYGYM_EINVAL),

@@ -53,7 +53,7 @@ class Transitions:
 @torch.no_grad()
 def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n_exploits: int | None = None, n_apps: int = 0, *,
             type_map=None, noise_std: float = 0.0, sigma_min: float = 0.0, decay_rate: float = 1.0, clip=(-1.0, 1.0), generator=None,
-            t0: int = 0, decoder=None) -> Transitions:
+            t0: int = 0, decoder=None, observer=None) -> Transitions:
     """Collect `n_decisions` transitions of `role` in every env of `batch` (the for-loop of do_agent.py:1334-1460 without the
     update).  actor(state [N, W]) -> [N, n_types + M + n_exploits + n_apps] action vectors; opponent: a baseline name / fixed
     sequence, a policy(obs, t, M, L) -> action tensors, or an object with write(batch, act, rows, obs).  The loop's tick
@@ -62,7 +62,10 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
     decoder: a policies.CoordAscentPolicy -- the reference's `Cord_asc` mode: on the learner's turn decoder.write(batch, act, rows,
     state, vec_out=...) decodes through the critic (with the policy's training-mode noise) and `action_vec` records the encoded
     action; `actor` may be None and is not evaluated; n_types / n_exploits / n_apps (and type_map, when given) must be the decoder's own
-    (ValueError otherwise)."""
+    (ValueError otherwise).
+    observer: an object with observe(batch, state) (meta_rollout.MetaController: the reference's meta_controller in observer mode,
+    :1342-1361), called on the learner's turn BEFORE the decode and the step, so that it sees the flags of the state the decision is
+    made on.  It writes no action and draws nothing: the transitions are the same with and without it."""
     from .rollout_grid import SequencePolicy, _baseline_code
     if role not in (HL.DEFENDER, HL.ATTACKER):
         raise ValueError("role must be 'attacker' or 'defender'")
@@ -96,6 +99,8 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
             act["mode"] |= (cur_bl + 1) << S.MODE_BASELINE_SHIFT
         act["n_groups"].zero_()
         if turn == role:
+            if observer is not None:
+                observer.observe(batch, state)
             if decoder is not None:      # Cord_asc: the decode through the critic writes the action and its encoding; `raw + noise` is never read
                 vec = torch.empty((N, n_out), dtype=torch.float32, device=dev)
                 decoder.write(batch, act, rows_all, state, vec_out=vec)
@@ -126,23 +131,49 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
     return Transitions(noise_std=sigma, **st)
 
 
-class ReplayRing:
+class RingIndex:
+    """The index arithmetic of a ring of preallocated rows that behaves like deque(maxlen=capacity): where a push of n rows lands,
+    which of them survive, and where logical row i (0 = the oldest row held) lives.  Host integers only: every push has a known size.
+    Shared by ReplayRing and meta_rollout.MetaReplay."""
+
+    def _init_ring(self, capacity: int, device):
+        self.capacity, self.device = int(capacity), torch.device(device)
+        if self.capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        self._head, self._size = 0, 0      # the row the next push writes; rows held
+
+    def __len__(self):
+        return self._size
+
+    def _advance(self, n: int):
+        """(physical rows of the surviving source rows, how many leading source rows to skip) of a push of n rows; moves the head."""
+        skip = max(0, n - self.capacity)     # the deque would have dropped these again
+        idx = (torch.arange(n - skip, device=self.device) + (self._head + skip)) % self.capacity
+        self._head = (self._head + n) % self.capacity
+        self._size = min(self.capacity, self._size + n)
+        return idx, skip
+
+    def _physical(self, indices):
+        return (torch.as_tensor(indices, device=self.device).long() + (self._head - self._size)) % self.capacity
+
+    def _draw(self, batch_size: int, generator=None):
+        """Logical indices of `batch_size` distinct rows, uniformly: the head of a random permutation of the rows held."""
+        if self._size < int(batch_size):
+            raise ValueError(f"the ring holds {self._size} rows, fewer than the {int(batch_size)} asked for")
+        return torch.randperm(self._size, generator=generator, device=self.device)[: int(batch_size)]
+
+
+class ReplayRing(RingIndex):
     """The reference's ReplayBuffer (do_agent.py:341-354: deque(maxlen=capacity) of (state, action, reward, next_state, done)) as
     preallocated tensors on one device: a push overwrites the oldest rows, exactly as the deque drops them.  Rewards are stored
     as float32 (the update's torch.tensor(rewards, dtype=float32), :413), `done` as float32 0 / 1 (:412).  Neither push nor sample
     synchronises with the host: the write position and the fill are host integers (every push has a known size)."""
 
     def __init__(self, capacity: int, state_dim: int, action_dim: int, device):
-        self.capacity, self.device = int(capacity), torch.device(device)
-        if self.capacity < 1:
-            raise ValueError("capacity must be >= 1")
+        self._init_ring(capacity, device)
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)  # noqa: E731
         self.state, self.action, self.next_state = z(self.capacity, int(state_dim)), z(self.capacity, int(action_dim)), z(self.capacity, int(state_dim))
         self.reward, self.done = z(self.capacity), z(self.capacity)
-        self._head, self._size = 0, 0      # the row the next push writes; rows held
-
-    def __len__(self):
-        return self._size
 
     def push(self, state, action_vec=None, reward=None, next_state=None, done=None):
         """Append n rows ([n, ...] tensors), or a whole `Transitions` flattened over [T, N] in (t, n) order; with n > capacity only
@@ -154,25 +185,19 @@ class ReplayRing:
             reward, done = tr.reward.reshape(n), tr.done.reshape(n)
         n = int(state.shape[0])
         rows = [state, action_vec, reward.reshape(n), next_state, done.reshape(n)]
-        skip = max(0, n - self.capacity)     # the deque would have dropped these again
-        keep = n - skip
-        idx = (torch.arange(keep, device=self.device) + (self._head + skip)) % self.capacity
+        idx, skip = self._advance(n)
         for dst, src in zip((self.state, self.action, self.reward, self.next_state, self.done), rows):
             dst.index_copy_(0, idx, src[skip:].to(device=self.device, dtype=torch.float32))
-        self._head = (self._head + n) % self.capacity
-        self._size = min(self.capacity, self._size + n)
 
     def sample_at(self, indices):
         """(state, action, reward [B, 1], next_state, done [B, 1]) of the given logical rows: 0 is the oldest row held."""
-        i = (torch.as_tensor(indices, device=self.device).long() + (self._head - self._size)) % self.capacity
+        i = self._physical(indices)
         return self.state[i], self.action[i], self.reward[i][:, None], self.next_state[i], self.done[i][:, None]
 
     def sample(self, batch_size: int, generator=None):
         """`batch_size` distinct rows, uniformly (random.sample's distribution, :350) from torch's generator on the ring's device: the
         head of a random permutation of the rows held.  ValueError when fewer are held."""
-        if self._size < int(batch_size):
-            raise ValueError(f"the ring holds {self._size} rows, fewer than the {int(batch_size)} asked for")
-        return self.sample_at(torch.randperm(self._size, generator=generator, device=self.device)[: int(batch_size)])
+        return self.sample_at(self._draw(batch_size, generator))
 
 
 @dataclass
@@ -260,7 +285,8 @@ def train_ddpg(agent: DDPGAgent, *, batch=None, batch_size: int = 512, gamma: fl
 
 def best_response(batch, role: str, agent: DDPGAgent, opponent, n_decisions: int, n_types: int, n_exploits: int | None = None, n_apps: int = 0, *,
                   type_map=None, decoder=None, updates_per_decision: int = 1, noise_std: float = 1.0, sigma_min: float = 1e-5,
-                  batch_size: int = 512, gamma: float = 0.99, tau: float = 1e-2, generator=None, fused=None, t0: int = 0):
+                  batch_size: int = 512, gamma: float = 0.99, tau: float = 1e-2, generator=None, fused=None, t0: int = 0, meta=None,
+                  meta_period: int = 10):
     """The training loop of DoubleOracle.ddpg_best_response (do_agent.py:1334-1460) for every env of a batch: per decision
     collect(n_decisions=1) from the loop's tick counter -- the opponent's tick first where the parity of t is theirs (:1335) --,
     push the N transitions (:1422 / :1424-1425), then `updates_per_decision` calls of train_ddpg (:1427-1431).  The exploration
@@ -268,8 +294,13 @@ def best_response(batch, role: str, agent: DDPGAgent, opponent, n_decisions: int
     CoordAscentPolicy over agent.critic: the reference's Cord_asc mode) every decision decodes through the LIVE critic: the
     policy's pack is keyed on the parameters' versions and is redone after each update.
     Returns (the summed raw reward per env [N] float64, the last update's dict -- None while the ring held fewer than batch_size
-    rows).  Out of scope: the meta-controller observer, dynamic_neighbor_search, exploit_override, the time budget, and leaving
-    the loop at the first done (a batch goes on, as collect does)."""
+    rows).
+    meta: a meta_rollout.MetaController -- the reference's meta_controller in observer mode (:1342-1361, :1410-1416): on every learner
+    turn it selects devices for the state the decision is made on (collect's `observer`), after the step it stores (state, selection,
+    raw reward) (meta.store), and it runs one train_controller when meta_rollout.trains_at(t, meta_period) holds for the learner's
+    tick t ((t + 1) % 10 == 0 as shipped: never for a defender, whose ticks are even).  It changes neither the actions nor the agent.
+    Out of scope: dynamic_neighbor_search, exploit_override, the time budget, and leaving the loop at the first done (a batch goes
+    on, as collect does)."""
     if decoder is not None and decoder.critic is not agent.critic:
         raise ValueError("decoder: a CoordAscentPolicy over agent.critic (the critic the updates train)")
     n_decisions = int(n_decisions)
@@ -277,11 +308,19 @@ def best_response(batch, role: str, agent: DDPGAgent, opponent, n_decisions: int
     total = torch.zeros((batch.N,), dtype=torch.float64, device=batch.device)
     t, sigma, last = int(t0), float(noise_std), None
     ours = 0 if role == HL.DEFENDER else 1
+    if meta is not None:
+        meta.prepare(batch)      # (the one host copy of the observer: the topology's neighbour lists)
     for _ in range(n_decisions):
         tr = collect(batch, role, agent.actor, opponent, 1, n_types, n_exploits, n_apps, type_map=type_map, noise_std=sigma, sigma_min=sigma_min,
-                     decay_rate=decay_rate, generator=generator, t0=t, decoder=decoder)
-        t += 1 if t % 2 == ours else 2
+                     decay_rate=decay_rate, generator=generator, t0=t, decoder=decoder, observer=meta)
+        t_learner = t if t % 2 == ours else t + 1
+        t = t_learner + 1
         sigma = tr.noise_std
+        if meta is not None:
+            from .meta_rollout import trains_at
+            meta.store(tr.raw_reward[0])
+            if trains_at(t_learner, meta_period):
+                meta.train_controller()
         agent.replay.push(tr)
         total += tr.raw_reward.sum(dim=0)
         for _ in range(int(updates_per_decision)):

@@ -32,7 +32,8 @@ into float64 cost batches (BaseHMARLBR.execute, :595-607); the batch does it in 
 every device from a structural embedding against a projection of the state, keeps the select_k best visible ones, and the role's DDPG
 critic picks one action type per kept device (MetaHierarchicalBestResponse.execute, :660-790, on a fresh object: its caches never act);
 the batch does it in one addmm plus one launch (cygym_meta_decode), answering with one group per kept device.  MetaNet.decide is the
-torch restatement the kernel is tested against.
+torch restatement the kernel is tested against.  MetaNet.observe is the same for the controller's TRAINING (meta_rollout.py): the
+observer's selection with the reference's frozen embedding cache and the kept devices' mean embedding (cygym_meta_select).
 """
 from __future__ import annotations
 
@@ -1554,6 +1555,77 @@ class MetaNet(nn.Module):
         torch.save({"state_proj": cpu(self.state_proj), "node_proj": cpu(self.node_proj), "struct_feats": cpu(self.struct_feats),
                     "node_bias": self.node_bias.detach().cpu().clone(), "select_k": None if select_k is None else int(select_k), "M": self.M}, path)
 
+    def _controller(self, state, flags, adj, role, dtype=None, feat=None):
+        """What decide() and observe() share: visibility, degrees, the embeddings E [B, M, P], proj [B, P] and the scores, floats in
+        `dtype` (default: the state's).  feat = (degn, known, owned): the structural features to use instead of the live ones (the
+        reference's frozen E_cache); visibility always comes from `flags`, and `adj` may then be None (deg is None)."""
+        from . import spec as S
+        dt = state.dtype if dtype is None else dtype
+        s = state.to(dt)
+        B, M, dev = int(s.shape[0]), self.M, s.device
+        f = torch.as_tensor(flags).to(dev).to(torch.uint8)
+        f = f[None].expand(B, M) if f.dim() == 1 else f
+        known, owned, nya = (f & S.F_KNOWN) != 0, (f & S.F_OWNED) != 0, (f & S.F_NYA) != 0
+        vis = (known & owned & ~nya) if role == "attacker" else (~nya & ~owned)
+        deg = None
+        if feat is None or adj is not None:
+            A = torch.as_tensor(adj).to(dev).bool()
+            A = A[None].expand(B, M, M) if A.dim() == 2 else A
+            if role == "attacker":
+                A = A & vis[:, :, None] & vis[:, None, :]
+            deg = A.sum(dim=2)
+        if feat is None:
+            mx = deg.max(dim=1, keepdim=True).values
+            degn = torch.where(mx > 0, deg.float() / mx.clamp(min=1).float(), deg.float()).to(dt)       # the fp32 quotient (:163-164)
+        else:
+            degn, known, owned = torch.as_tensor(feat[0]).to(dev).to(dt), torch.as_tensor(feat[1]).to(dev).bool(), torch.as_tensor(feat[2]).to(dev).bool()
+        lin0, lin2, ID = self.node_proj[0], self.node_proj[2], self.id_dim
+        w0 = lin0.weight.detach().to(dt)
+        base = self.struct_feats.id_emb.weight.detach().to(dt) @ w0[:, :ID].t() + lin0.bias.detach().to(dt)      # [M, ED]
+        x = base[None] + degn[:, :, None] * w0[:, ID] + known.to(dt)[:, :, None] * w0[:, ID + 1] + owned.to(dt)[:, :, None] * w0[:, ID + 2]
+        emb = torch.relu(x) @ lin2.weight.detach().to(dt).t() + lin2.bias.detach().to(dt)                       # [B, M, P]
+        sp = self.state_proj
+        proj = torch.relu(s @ sp.fc1.weight.detach().to(dt).t() + sp.fc1.bias.detach().to(dt)) @ sp.fc2.weight.detach().to(dt).t() + sp.fc2.bias.detach().to(dt)
+        score = (emb * proj[:, None, :]).sum(dim=2)
+        return {"dt": dt, "s": s, "vis": vis, "deg": deg, "degn": degn, "known": known, "owned": owned, "emb": emb, "proj": proj, "score": score}
+
+    def _select(self, score, vis, k: int):
+        """(sel [B, k] int64 ascending ids, -1 behind them; n_sel [B]): the min(k, |V|) visible devices with the largest score, the lower
+        id among equals."""
+        B, M, dev = int(score.shape[0]), self.M, score.device
+        n_sel = vis.sum(dim=1).clamp(max=k)
+        masked = torch.where(vis, score, torch.full_like(score, float("-inf")))
+        order = torch.sort(-masked, dim=1, stable=True).indices[:, :k]                                       # descending score, ascending id among equals
+        if order.shape[1] < k:
+            order = torch.cat([order, torch.zeros((B, k - order.shape[1]), dtype=order.dtype, device=dev)], 1)
+        order = torch.where(torch.arange(k, device=dev)[None] < n_sel[:, None], order, torch.full_like(order, M))
+        sel = torch.sort(order, dim=1).values
+        return torch.where(sel >= M, torch.full_like(sel, -1), sel), n_sel
+
+    @torch.no_grad()
+    def observe(self, state, flags, adj, role: str, k: int, feat=None, dtype=None, selected=None):
+        """The observer's selection (do_agent.py:1342-1361 -> select_devices, :415-446) for a batch with torch ops: the torch form of
+        cygym_meta_select, and in torch.float64 the restatement it is tested against.  Arguments as decide().  feat = (degn [B, M],
+        known [B, M], owned [B, M]): structural features fed back in -- the reference's frozen E_cache: pass what the FIRST decision
+        of a run returned; None: the live ones.  Returns a dict: sel [B, k] int64 (ascending ids, -1 behind them), n_sel [B], ebar
+        [B, P] = the sum of the kept devices' embeddings in ascending id times the fp32 value 1 / n_sel (zeros when nothing is kept),
+        score [B, M] (before node_bias), deg [B, M] int64 (None without adj), vis, and feat = the (degn, known, owned) it used.
+        `selected` [B, k] int64 (-1 padded, ascending): skip the selection and pool those devices (tests: the kernel's own)."""
+        c = self._controller(state, flags, adj, role, dtype, feat)
+        if selected is None:
+            sel, n_sel = self._select(c["score"], c["vis"], int(k))
+        else:
+            sel = torch.as_tensor(selected).to(c["s"].device).long()
+            n_sel = (sel >= 0).sum(dim=1)
+        keep = (sel >= 0).to(c["dt"])
+        rows = torch.arange(sel.shape[0], device=sel.device)[:, None]
+        ebar = torch.zeros_like(c["proj"])
+        for j in range(sel.shape[1]):                                                                           # ascending id
+            ebar = ebar + c["emb"][rows[:, 0], sel[:, j].clamp(min=0)] * keep[:, j:j + 1]
+        inv = torch.where(n_sel > 0, 1.0 / n_sel.clamp(min=1).float(), torch.zeros_like(n_sel, dtype=torch.float32)).to(c["dt"])
+        return {"sel": sel, "n_sel": n_sel, "ebar": ebar * inv[:, None], "score": c["score"], "deg": c["deg"], "vis": c["vis"],
+                "feat": (c["degn"], c["known"], c["owned"])}
+
     @torch.no_grad()
     def decide(self, state, flags, adj, role: str, critic, k: int, dtype=None, n_types=None, n_exploits=None, n_apps: int = 0, selected=None):
         """execute (:660-790) on a fresh object, for a batch.  state [B, state_dim]; flags [B, M] or [M] uint8 in the flag plane's bit
@@ -1566,38 +1638,11 @@ class MetaNet(nn.Module):
         Ties at the k-th place go to the lower id (where the reference's np.argpartition is unspecified).
         `selected` [B, k] int64 (-1 padded, ascending): skip the selection and score those devices (tests: the kernel's own)."""
         from . import spec as S
-        dt = state.dtype if dtype is None else dtype
-        s = state.to(dt)
-        B, M, dev = int(s.shape[0]), self.M, s.device
-        f = torch.as_tensor(flags).to(dev).to(torch.uint8)
-        f = f[None].expand(B, M) if f.dim() == 1 else f
-        known, owned, nya = (f & S.F_KNOWN) != 0, (f & S.F_OWNED) != 0, (f & S.F_NYA) != 0
-        vis = (known & owned & ~nya) if role == "attacker" else (~nya & ~owned)
-        A = torch.as_tensor(adj).to(dev).bool()
-        A = A[None].expand(B, M, M) if A.dim() == 2 else A
-        if role == "attacker":
-            A = A & vis[:, :, None] & vis[:, None, :]
-        deg = A.sum(dim=2)
-        mx = deg.max(dim=1, keepdim=True).values
-        degn = torch.where(mx > 0, deg.float() / mx.clamp(min=1).float(), deg.float()).to(dt)       # the fp32 quotient (:163-164)
-        lin0, lin2, ID = self.node_proj[0], self.node_proj[2], self.id_dim
-        w0 = lin0.weight.detach().to(dt)
-        base = self.struct_feats.id_emb.weight.detach().to(dt) @ w0[:, :ID].t() + lin0.bias.detach().to(dt)      # [M, ED]
-        x = base[None] + degn[:, :, None] * w0[:, ID] + known.to(dt)[:, :, None] * w0[:, ID + 1] + owned.to(dt)[:, :, None] * w0[:, ID + 2]
-        emb = torch.relu(x) @ lin2.weight.detach().to(dt).t() + lin2.bias.detach().to(dt)                       # [B, M, P]
-        sp = self.state_proj
-        proj = torch.relu(s @ sp.fc1.weight.detach().to(dt).t() + sp.fc1.bias.detach().to(dt)) @ sp.fc2.weight.detach().to(dt).t() + sp.fc2.bias.detach().to(dt)
-        score = (emb * proj[:, None, :]).sum(dim=2)
-        k = int(k)
-        n_sel = vis.sum(dim=1).clamp(max=k)
+        c = self._controller(state, flags, adj, role, dtype)
+        dt, s, dev, vis, deg, degn, score = c["dt"], c["s"], c["s"].device, c["vis"], c["deg"], c["degn"], c["score"]
+        B, M, k = int(s.shape[0]), self.M, int(k)
         if selected is None:
-            masked = torch.where(vis, score, torch.full_like(score, float("-inf")))
-            order = torch.sort(-masked, dim=1, stable=True).indices[:, :k]                                       # descending score, ascending id among equals
-            if order.shape[1] < k:
-                order = torch.cat([order, torch.zeros((B, k - order.shape[1]), dtype=order.dtype, device=dev)], 1)
-            order = torch.where(torch.arange(k, device=dev)[None] < n_sel[:, None], order, torch.full_like(order, M))
-            sel = torch.sort(order, dim=1).values
-            sel = torch.where(sel >= M, torch.full_like(sel, -1), sel)
+            sel, n_sel = self._select(score, vis, k)
         else:
             sel = torch.as_tensor(selected).to(dev).long()
             n_sel = (sel >= 0).sum(dim=1)

@@ -993,9 +993,70 @@ typedef struct cygym_meta {
  * CYGYM_EUNSUPPORTED (nothing is written): M > 1000 (the reference switches to a sparse path whose coalesce counts reciprocal edges
  *   twice: a different function); k outside 1 .. 32; n_types > 32; n_exploits > CG_MAX_EXPLOITS; id_dim outside 1 .. 32; embed_dim or
  *   proj_dim outside 1 .. 64; Hp outside 1 .. 256; H1 or H2 not a multiple of 16 in 16 .. 128.
- * Out of scope: train / train_controller / the observer mode of ddpg_best_response (score_out, selected_out, q_out and deg_out are what
- *   a controller update needs from this launch), M > 1000, exploit_override, the `committee` mapping, and the cache itself. */
+ * Out of scope: M > 1000, exploit_override, the `committee` mapping, and the Q cache itself.  (The observer mode of
+ *   ddpg_best_response -- select_devices with the frozen embedding cache -- is cygym_meta_select below; train_controller is a 64-row
+ *   update of state_proj and stays with the caller, cygym_amd/meta_rollout.py.) */
 int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions* dst, void* stream);
+
+/* The controller of a MetaDOAR strategy as cygym_meta carries it, WITHOUT the critic, plus the observer's own arrays.  DEVICE pointers;
+ * the fields shared with cygym_meta mean what they mean there. */
+typedef struct cygym_meta_select_desc {
+  const int32_t* rows;        /* [n] env ids whose state is read; NULL = envs 0..n-1.  With a snapshot an env may appear AT MOST ONCE     */
+  const float* h0;            /* [n][h0_stride] per SOURCE row, before the relu: state_proj.fc1(s) (Hp floats); nothing else is read       */
+  const float* sp_w2_t;       /* [Hp][P]                                                                                                     */
+  const float* sp_b2;         /* [P]                                                                                                         */
+  const float* base;          /* [M][ED4], 16-byte aligned                                                                                   */
+  const float* w_feat;        /* [3][ED4], 16-byte aligned                                                                                   */
+  const float* np_w2;         /* [P][ED]                                                                                                     */
+  const float* np_b2;         /* [P]                                                                                                         */
+  const int32_t* nbr_ptr;     /* [M + 1]                                                                                                     */
+  const uint16_t* nbr_col;    /* the symmetric neighbour lists, as in cygym_meta                                                             */
+  float*   snap_degn;         /* the snapshot, all three or none: [n_envs][M] degn_i of the env's first decision ...                         */
+  uint8_t* snap_flags;        /* ... [n_envs][M] its CG_F_KNOWN | CG_F_OWNED bits (no other bit is set) ...                                  */
+  uint8_t* snap_valid;        /* ... [n_envs] 0: env e has no snapshot yet (the launch takes one), else: its features are read from it       */
+  int32_t* selected_out;      /* REQUIRED [n][k]: the kept devices in ascending id, -1 behind them                                           */
+  float*   ebar_out;          /* optional [n][P]: the mean embedding of the kept devices (zeros when none is kept)                           */
+  float*   score_out;         /* optional [n][M]: score_i (every device, visible or not; before node_bias)                                   */
+  int32_t* deg_out;           /* optional [n][M]: the row sums deg_i -- written ONLY for a row whose features are computed from the live
+                                 state in this launch (no snapshot, or the launch that takes it)                                            */
+  int32_t  n;                 /* source rows                                                                                                 */
+  int32_t  role;              /* 1 defender, 2 attacker                                                                                      */
+  int32_t  k;                 /* select_k, 1 .. 32                                                                                           */
+  int32_t  id_dim, embed_dim, proj_dim;   /* 1 .. 32, 1 .. 64, 1 .. 64                                                                       */
+  int32_t  Hp;                /* width of state_proj.fc1, 1 .. 256                                                                           */
+  int32_t  h0_stride;         /* floats per row of h0, >= Hp                                                                                 */
+} cygym_meta_select_desc;
+
+/* Replaces: the observer's selection while a DDPG best response trains -- do_agent.py:1342-1361 (build_visibility_mask of the stepped
+ * env, meta_controller.select_devices, _last_selection) with select_devices itself (meta_hierarchical_br.py:415-446) and its embedding
+ * cache (:393-410) -- for a batch, in ONE launch, together with what train_controller (:843-887) later needs of the decision.  It
+ * writes NO action tensor, makes NO draw and reads NO rng tick.  Per source row r (env e = rows[r], f[d] its LIVE flag byte):
+ * 1. Visibility and the candidate set: step 1 of cygym_meta_decode on the live flags, always (do_agent.py:1344-1345).
+ * 2. Features.  Without a snapshot (all three snap_* NULL), or with snap_valid[e] == 0: deg_i, degn_i as step 2 of cygym_meta_decode in
+ *    env mode (the env's added edges included, the attacker's adjacency masked by the visibility of THIS state), known_i / owned_i off
+ *    f.  With snap_valid[e] == 0 these are then stored -- snap_degn[e][i] = degn_i, snap_flags[e][i] = f[i] & (KNOWN | OWNED) -- and
+ *    snap_valid[e] = 1.  With snap_valid[e] != 0 degn_i, known_i and owned_i are READ from the snapshot and nothing of it is written.
+ *    This is the reference's E_cache: node_dirty is all ones at construction, the first select_devices recomputes every embedding from
+ *    the env as it is then and clears the flags (:419-422), and only execute ever sets them again -- in observer mode nothing does, so
+ *    for the whole run the embeddings are those of the FIRST decision, while visibility is read fresh.  The embeddings are a function
+ *    of (weights, degn, known, owned); storing those three instead of E keeps the cache valid across updates of the weights (the
+ *    reference's updates move state_proj only, so its E_cache never goes stale either).  A caller clears snap_valid to start a new run.
+ *    (_feature_adjacency is restated as the method it was written to be, as at cygym_meta_decode.)
+ * 3. Scores and selection: steps 3 and 4 of cygym_meta_decode, the same fp32 expressions in the same order.  For equal inputs and no
+ *    snapshot, score_out, deg_out and the kept set are BIT-EQUAL to cygym_meta_decode's in env mode.
+ * 4. The pooled embedding, fp32 with fused multiply-adds:
+ *      E_ip   = fma(np_w2[p][e], relu(x_ie), .)  over ASCENDING e, start np_b2[p]          (x_ie as in step 3 of cygym_meta_decode)
+ *      ebar_p = (sum of E_ip over the kept devices i in ASCENDING id, start 0) * (1.0f / n_sel)     n_sel = min(k, |V|)
+ *    with 1.0f / n_sel the correctly rounded fp32 quotient; n_sel == 0: ebar = 0 and selected_out all -1.  train_controller's
+ *    prediction sum_i mask_i (E_i . proj + bias), mask = 1 / n_sel on the kept devices (:861-873), is ebar . proj + bias.
+ * Precondition: with a snapshot no env id occurs twice in rows (two waves would take and read one env's snapshot at once).
+ * CYGYM_EINVAL (nothing is written, the snapshot included): a NULL handle, struct, required pointer (selected_out among them); one or
+ *   two of the three snapshot pointers; role outside 1 / 2; Hp < 1 or h0_stride < Hp; base / w_feat not 16-byte aligned; a bad row count.
+ * CYGYM_EUNSUPPORTED (nothing is written): M > 1000; k outside 1 .. 32; id_dim outside 1 .. 32; embed_dim or proj_dim outside 1 .. 64;
+ *   Hp > 256.  CYGYM_ENOTBOUND (nothing is written) without cygym_bind: the flags and the added edges are the bound state's.
+ * Out of scope: train_controller itself (64 rows through state_proj: torch, cygym_amd/meta_rollout.py), next_state / done and
+ *   target_state_proj (stored or updated by the reference, never read), M > 1000. */
+int cygym_meta_select(cygym_handle* h, const cygym_meta_select_desc* q, void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`
