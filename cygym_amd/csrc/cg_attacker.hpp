@@ -592,6 +592,16 @@ __device__ __forceinline__ void attacker_spread(Env& e, const KP& P, const int32
   }
 }
 
+// A wave-uniform value made opaque to the optimiser: nothing computed from it before this point is reused behind it, nothing
+// computed from it behind this point is hoisted in front of it.  (readfirstlane first: free where the compiler knows the value
+// to be uniform, and where it does not, the "s" constraint alone is an illegal VGPR-to-SGPR copy.)
+template <class T>
+__device__ __forceinline__ void opaque_uniform(T& v) {
+  static_assert(sizeof(T) == 4, "one SGPR");
+  v = (T)__builtin_amdgcn_readfirstlane((int)v);
+  asm volatile("" : "+s"(v));
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The spread at a compile-time size without added edges (lean kernels, 64 / 256 devices), written against what the launch
 // time of a one-residency-round batch is made of: the slowest env's chain of DEPENDENT LDS round trips (~300 cycles each
@@ -607,6 +617,16 @@ __device__ __forceinline__ void attacker_spread(Env& e, const KP& P, const int32
 //     stage-3 / 4 reads are the blocked word and T word of that one slot;
 //   * a verification sweep (only after a conflict) is ONE round trip for all blocks -- the T words of the picks -- and
 //     only the sources that lost theirs rescan, a short row with one staged slot (spread_scan_lane_st<1>).
+// Nothing derived from `n_src` is carried across the exploit loop or a block loop: the count is made opaque (an empty asm on its
+// SGPR) at the top of every exploit iteration and in front of the `b * 64 >= n_src` test of sweep 0, of the verification sweep
+// and of the log counts, so the per-block lane masks `lane + 64 b < n_src` with their complements, the clamped slist addresses
+// and the `n_src > 64 / 128 / 192` conditions are formed at their uses -- one compare each.  Hoisted, as the compiler had them,
+// they were some thirty scalars live across the whole action, parked in the lanes of a spill VGPR at the top of the spread (one
+// v_writelane each, with hazard no-ops, while all sixteen waves of the CU are alive and an instruction costs 12-16 cycles) and
+// read back all through the sweeps, the counts and the ring.  The same for the zero-day mask: its popcount and the conditions
+// on it belong to the rare iteration that draws.  (Spill slots of the WIDE kernel 68 -> 25, v_writelane in the spread 57 -> 17;
+// tests/test_spread_parking_isa_cpu.py.  Not re-formed, each tried and dropped, PERFLOG.md (r12_spread_parking): the lane id per iteration,
+// the last blocked word's index, the tick's header scalars.)
 template <int MCT, bool WIDE, class KP>
 __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const int32_t* expl, int ex0, int n_expl) {
   const int M = e.M, E1 = P.t.E > 0 ? P.t.E - 1 : 0;
@@ -630,9 +650,11 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
   }
   int zocc = 0;
   for (int jx = 0; jx < n_expl; ++jx) {
+    opaque_uniform(n_src);   // (opaque per iteration: see above)
     int raw = jx == 0 ? ex0 : expl[jx];   // expl[0] was fetched with the tick's header
     if (P.c.zero_day) {  // :1131-1146
       uint32_t mask = (uint32_t)P.c.zero_day_owned_mask;
+      opaque_uniform(mask);   // its popcount and the tests on it are formed in this arm, by the iteration that draws
       bool in = raw >= 0 && raw < 32 && ((mask >> raw) & 1u);
       if (!in) {
         int cnt = __popc(mask);
@@ -653,9 +675,13 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
       for (int c = 0; c < MCT; ++c) {
         const int d = c * WAVE + lane;
         const uint32_t f = d < M ? fj[c] : 0u;
-        const uint32_t x = ((f & CG_F_REACH) ? 1u : 0u) | (((f & CG_F_KNOWN) && (vj[c] & ebit)) ? 2u : 0u);
-        uint64_t cm = ballot((x & 1u) || ((x & 2u) && !(f & CG_F_COMP)));
-        T[d] = (((f & CG_F_COMP) ? 0u : T_TIME_INF) << 2) | x;
+        // as shifts and ands -- x = reach | (known & vulnerable) << 1, the time field all ones unless compromised: one compare per
+        // chunk (the candidate ballot) where the conditional form took four, with three mask operations and three selects
+        static_assert(CG_F_COMP == 1u && CG_F_KNOWN == 4u && CG_F_REACH == 8u, "T-word bit arithmetic");
+        const uint32_t nc = (f & 1u) ^ 1u;   // not compromised
+        const uint32_t x = ((f >> 3) & 1u) | ((((f >> 2) & (vj[c] >> raw)) & 1u) << 1);
+        uint64_t cm = ballot((x & (1u | (nc << 1))) != 0u);
+        T[d] = ((0u - nc) & (T_TIME_INF << 2)) | x;
         if (lane == 0) cand[c] = cm;
         if (u1 < 0 && cm) { u1 = c * WAVE + __builtin_ctzll(cm); cm &= cm - 1; }
         if (u1 >= 0 && u2 < 0 && cm) u2 = c * WAVE + __builtin_ctzll(cm);
@@ -674,6 +700,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
     constexpr int BP = (WIDE && MCT >= 2) ? 2 : 1;   // blocks per staged group (two where the registers allow it: the kernels capped at 80 VGPRs spill with two)
 #pragma unroll
     for (int b0 = 0; b0 < MCT; b0 += BP) {
+      opaque_uniform(n_src);
       if (b0 * WAVE >= n_src) break;
       int sv[BP], o0[BP], o1[BP];
       uint32_t stv[BP];
@@ -773,6 +800,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
       for (int b = 0; b < MCT; ++b) tv[b] = T[pkv[b] >> 16];
 #pragma unroll
       for (int b = 0; b < MCT; ++b) {
+        opaque_uniform(n_src);
         if (b * WAVE >= n_src) break;
         const int s = (int)(sst[b] & 0xFFFFu), o0 = (int)(row[b] & 0xFFFFu), o1 = (int)(row[b] >> 16), k0 = (int)(pkv[b] & 0xFFFFu);
         const uint32_t st = sst[b] >> 16;
@@ -838,6 +866,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
 #pragma unroll
     for (int b = 0; b < MCT; ++b) {
       cnt[b] = 0;
+      opaque_uniform(n_src);
       if (b * WAVE >= n_src) continue;   // (uniform)
       const int o0 = (int)(row[b] & 0xFFFFu), o1 = (int)(row[b] >> 16), k = (int)(pkv[b] & 0xFFFFu);
       int n = 0;
