@@ -178,6 +178,15 @@ class Hmarl(C.Structure):
                 ("fanout", C.c_int32), ("fallback", C.c_int32)]
 
 
+class HmarlTrain(C.Structure):
+    _fields_ = [("h0", C.c_void_p), ("pi_w2", C.c_void_p), ("pi_b2", C.c_void_p), ("v_w2", C.c_void_p), ("v_b2", C.c_void_p),
+                ("skill_out", C.c_void_p), ("idx_out", C.c_void_p), ("type_out", C.c_void_p), ("logp_out", C.c_void_p), ("value_out", C.c_void_p),
+                ("logits_out", C.c_void_p), ("ld", C.c_int32), ("Hp", C.c_int32), ("Hv", C.c_int32), ("force_skill", C.c_int32)]
+
+
+HMARL_MAX_HIDDEN = 256
+
+
 class Meta(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("h0", C.c_void_p), ("sp_w2_t", C.c_void_p), ("sp_b2", C.c_void_p), ("base", C.c_void_p), ("w_feat", C.c_void_p),
                 ("np_w2", C.c_void_p), ("np_b2", C.c_void_p), ("nbr_ptr", C.c_void_p), ("nbr_col", C.c_void_p), ("flags_fixed", C.c_void_p),
@@ -194,6 +203,20 @@ class MetaSelect(C.Structure):
                 ("snap_flags", C.c_void_p), ("snap_valid", C.c_void_p), ("selected_out", C.c_void_p), ("ebar_out", C.c_void_p),
                 ("score_out", C.c_void_p), ("deg_out", C.c_void_p), ("n", C.c_int32), ("role", C.c_int32), ("k", C.c_int32), ("id_dim", C.c_int32),
                 ("embed_dim", C.c_int32), ("proj_dim", C.c_int32), ("Hp", C.c_int32), ("h0_stride", C.c_int32)]
+
+
+class PpoFinish(C.Structure):
+    _fields_ = [("rew", C.c_void_p), ("val", C.c_void_p), ("last_value", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p),
+                ("gamma", C.c_double), ("lam", C.c_double), ("T", C.c_int32), ("N", C.c_int32)]
+
+
+PPO_MAX_K = 32
+
+
+class CatPpo(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("act", C.c_void_p), ("old_logp", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p),
+                ("v_pred", C.c_void_p), ("stats", C.c_void_p), ("g_stats", C.c_void_p), ("d_logits", C.c_void_p), ("d_v", C.c_void_p),
+                ("clip", C.c_double), ("B", C.c_int32), ("K", C.c_int32)]
 
 
 DECODE_TRUNCATED = 0x10000

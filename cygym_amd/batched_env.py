@@ -908,6 +908,51 @@ class BatchedCyberDefenseEnv:
         r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
         _lib.check(self.lib.cygym_hmarl_decode(self._h, C.byref(q), C.byref(dst), self._stream()), self._h, "cygym_hmarl_decode")
 
+    def hmarl_sample_decode(self, rows, cfg, h0: torch.Tensor, pack, force_skill: int = -1, act=None, logits_out=None, out=None):
+        """The TRAINING decision of HMARLMetaBestResponse.train (HMARL.py:792-872) for a batch, written as GROUPS into rows `rows` of `act`:
+        ONE launch (cygym_hmarl_sample_decode; include/cygym_abi.h states the decision).
+          cfg          policies.HMARLConfig (a learned master)
+          h0           [n, >= Hp + Hv + S * n_logits] float32, unit inner stride: policies.HMARLPolicy.h0(obs, pack), ONE addmm
+          pack         policies.HMARLPolicy.train_pack(...): pi_w2 [S, Hp], pi_b2 [S] (phase 2), v_w2 [Hv], v_b2 [1], Hp, Hv
+          force_skill  -1: phase 2, the master draws the skill and the skill's type is the greedy one;
+                       >= 0: phase 1, that skill's net draws the type index (clamped; logp of the clamped index)
+          logits_out   optional [n, S] (phase 2) / [n, n_logits] (phase 1) float32
+          out          optional (skill, idx, type int32 [n], logp, value float32 [n]) to write into
+        Returns (skill, idx, type, logp, value): idx is what the PPO buffer stores.  The rng tick is read, not advanced; no host
+        synchronisation."""
+        dst = self.actions_struct(act)
+        q = cfg.to_c()
+        if h0.dtype != torch.float32 or h0.device != self.device or h0.dim() != 2 or h0.stride(1) != 1:
+            raise ValueError("h0 must be a [n, ld] float32 tensor on the batch's device with unit inner stride")
+        n, S_, K = int(h0.shape[0]), cfg.n_skills, cfg.n_logits
+        force_skill = int(force_skill)
+        p2 = force_skill < 0
+        Hp, Hv = (int(pack["Hp"]) if p2 else 0), int(pack["Hv"])
+        if int(h0.shape[1]) < Hp + Hv + S_ * K:
+            raise ValueError(f"h0 needs at least {Hp + Hv + S_ * K} columns")
+        f32 = lambda t, shape: t.dtype == torch.float32 and t.device == self.device and t.is_contiguous() and tuple(t.shape) == shape  # noqa: E731
+        tr = abi.HmarlTrain()
+        need = [("v_w2", (Hv,)), ("v_b2", (1,))] + ([("pi_w2", (S_, Hp)), ("pi_b2", (S_,))] if p2 else [])
+        for name, shape in need:
+            if name not in pack or not f32(pack[name], shape):
+                raise ValueError(f"pack[{name!r}] must be a contiguous float32 {list(shape)} tensor on {self.device}")
+            setattr(tr, name, pack[name].data_ptr())
+        if out is None:
+            out = tuple(torch.empty((n,), dtype=dt, device=self.device) for dt in (torch.int32, torch.int32, torch.int32, torch.float32, torch.float32))
+        for name, t, dt in zip(("skill_out", "idx_out", "type_out", "logp_out", "value_out"), out, (torch.int32,) * 3 + (torch.float32,) * 2):
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n,):
+                raise ValueError(f"{name} must be a contiguous {dt} [{n}] tensor on {self.device}")
+            setattr(tr, name, t.data_ptr())
+        if logits_out is not None:
+            if not f32(logits_out, (n, S_ if p2 else K)):
+                raise ValueError(f"logits_out must be a contiguous float32 [{n}, {S_ if p2 else K}] tensor on {self.device}")
+            tr.logits_out = logits_out.data_ptr()
+        tr.h0, tr.ld, tr.Hp, tr.Hv, tr.force_skill = h0.data_ptr(), int(h0.stride(0)), Hp, Hv, force_skill
+        q.status = self.status.data_ptr()
+        r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
+        _lib.check(self.lib.cygym_hmarl_sample_decode(self._h, C.byref(q), C.byref(tr), C.byref(dst), self._stream()), self._h, "cygym_hmarl_sample_decode")
+        return out
+
     def meta_decode(self, rows, h0: torch.Tensor, pack, role: str = "defender", act=None, flags_fixed=None, type_map=None,
                     score_out=None, selected_out=None, q_out=None, deg_out=None):
         """MetaHierarchicalBestResponse.execute (meta_hierarchical_br.py:660-790, the MetaDOAR best response on a fresh object: the

@@ -51,10 +51,12 @@ INST_COORD = os.path.join(HERE, "csrc", "cg_inst_coord.hip")
 INST_COMM = os.path.join(HERE, "csrc", "cg_inst_comm.hip")
 INST_HIER = os.path.join(HERE, "csrc", "cg_inst_hier.hip")
 INST_HMARL = os.path.join(HERE, "csrc", "cg_inst_hmarl.hip")
+INST_HMARL_TRAIN = os.path.join(HERE, "csrc", "cg_inst_hmarl_train.hip")
 INST_META = os.path.join(HERE, "csrc", "cg_inst_meta.hip")
 INST_META_SELECT = os.path.join(HERE, "csrc", "cg_inst_meta_select.hip")
 INST_EVAL = os.path.join(HERE, "csrc", "cg_inst_eval.hip")
 INST_DDPG = os.path.join(HERE, "csrc", "cg_inst_ddpg.hip")
+INST_PPO = os.path.join(HERE, "csrc", "cg_inst_ppo.hip")
 N_GROUPS = 8   # CG_INST_GROUPS of csrc/cg_device.hpp
 GROUP_MT = {0: 256, 1: 256, 2: 64, 3: 64, 4: 0, 5: 0, 6: 0, 7: 0}   # device-count class each instantiation group holds
 
@@ -82,10 +84,12 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         units.append(("inst_comm", base + ["-c", INST_COMM, "-o", os.path.join(tmp, "inst_comm.o")]))   # the per-device actor-critic decode
         units.append(("inst_hier", base + ["-c", INST_HIER, "-o", os.path.join(tmp, "inst_hier.o")]))   # the hierarchical (HAGS) decode
         units.append(("inst_hmarl", base + ["-c", INST_HMARL, "-o", os.path.join(tmp, "inst_hmarl.o")]))   # the H-MARL decode
+        units.append(("inst_hmarl_train", base + ["-c", INST_HMARL_TRAIN, "-o", os.path.join(tmp, "inst_hmarl_train.o")]))   # its training decision
         units.append(("inst_meta", base + ["-c", INST_META, "-o", os.path.join(tmp, "inst_meta.o")]))   # the MetaDOAR decode
         units.append(("inst_meta_select", base + ["-c", INST_META_SELECT, "-o", os.path.join(tmp, "inst_meta_select.o")]))   # its observer's selection
         units.append(("inst_eval", base + ["-c", INST_EVAL, "-o", os.path.join(tmp, "inst_eval.o")]))   # its evaluate / backward (the PPO update)
         units.append(("inst_ddpg", base + ["-c", INST_DDPG, "-o", os.path.join(tmp, "inst_ddpg.o")]))   # the critic's tail and its backward (the DDPG update)
+        units.append(("inst_ppo", base + ["-c", INST_PPO, "-o", os.path.join(tmp, "inst_ppo.o")]))   # the GAE walk and the Categorical PPO loss head (the H-MARL updates)
 
         def run(unit):
             name, cmd = unit

@@ -35,10 +35,32 @@ __device__ __forceinline__ int hm_byte(const uint8_t* tab, const int i) {
 }
 __device__ __forceinline__ int hm_top(uint64_t m) { return 63 - __clzll((long long)m); }   // highest set bit (m != 0)
 
-// OUTS: skill_out / type_out are given.
-template <bool OUTS>
+// The log-probability of entry k of softmax(l[0 .. K-1]) in sample_head's arithmetic (max-subtracted __expf, __logf of the sum).
+__device__ __forceinline__ float hm_logp(const float* l, const int K, const int k) {
+  float mx = -__builtin_inff();
+  for (int j = 0; j < K; ++j) mx = l[j] > mx ? l[j] : mx;
+  float S = 0.f;
+  for (int j = 0; j < K; ++j) S += __expf(l[j] - mx);
+  return l[k] - mx - __logf(S);
+}
+// One output of a second layer on chip: sum over c of relu(x[c]) * w[c], c = 0 .. H-1.  Lane j adds its columns j, j + 64, ... in
+// ascending order (fmaf), then the xor butterfly with offsets 32, 16, .., 1: every lane holds the sum.
+__device__ __forceinline__ float hm_dot_relu(const float* x, const float* w, const int H, const int lane) {
+  float acc = 0.f;
+  for (int c = lane; c < H; c += WAVE) { const float a = x[c]; acc = fmaf(a > 0.f ? a : 0.f, w[c], acc); }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  return acc;
+}
+
+// OUTS: skill_out / type_out are given.  TRAIN (cygym_hmarl_sample_decode): the kernel takes ONE more argument, the cygym_hmarl_train,
+// and steps 1 and 2 are the training decision -- the second layers of the master (or of a skill's value head) on chip, the skill or the
+// type index DRAWN, its log-probability and the value estimate stored.  <.., false> holds none of that code and has the argument list
+// of the eval-mode decode.  Steps 3 to 5 are the same code either way.
+template <bool OUTS, bool TRAIN = false, class... TR>
 __global__ __launch_bounds__(HM_THREADS_MAX) void hmarl_kernel(cygym_hmarl q, cygym_actions dst, int n_envs, const int32_t* ienv, uint64_t seed,
-                                                               int64_t env_id_base, const uint8_t* live, const uint8_t* dstatic, int M) {
+                                                               int64_t env_id_base, const uint8_t* live, const uint8_t* dstatic, int M, TR... trs) {
+  static_assert(sizeof...(TR) == (TRAIN ? 1 : 0), "the training kernel takes the cygym_hmarl_train, the eval-mode kernel nothing");
   extern __shared__ __align__(16) uint8_t smem[];
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int srow = blockIdx.x * (int)(blockDim.x >> 6) + wv;
@@ -51,8 +73,60 @@ __global__ __launch_bounds__(HM_THREADS_MAX) void hmarl_kernel(cygym_hmarl q, cy
   const uint8_t* fl = live + (size_t)row * 4 * M;   // plane 0 of the env's live planes = the flags
   const uint32_t tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];   // read, not advanced
   const uint32_t env_g = (uint32_t)(env_id_base + row), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  int skill, idx;
+  if constexpr (TRAIN) {
+    const cygym_hmarl_train& tr = hr_first(trs...);
+    const int S = q.n_skills, K = q.n_logits;
+    const int Hp = tr.force_skill < 0 ? tr.Hp : 0, Hv = tr.Hv;
+    const float* hrow = tr.h0 + (size_t)srow * tr.ld;
+    const float* subs = hrow + Hp + Hv;                    // the skills' fc logits, already final
+    const float value = hm_dot_relu(hrow + Hp, tr.v_w2, Hv, lane) + tr.v_b2[0];
+    float logp;
+    if (tr.force_skill < 0) {   // phase 2 (HMARL.py:848-852): _master_act's Categorical over the skills, then select_action's greedy type
+      float* ml = reinterpret_cast<float*>(keys);          // the master's logits in the wave's LDS block (>= 640 bytes; step 3 reuses it)
+      for (int s = 0; s < S; ++s) {
+        const float z = hm_dot_relu(hrow, tr.pi_w2 + (size_t)s * Hp, Hp, lane) + tr.pi_b2[s];
+        if (lane == 0) ml[s] = z;
+      }
+      wsync();
+      skill = sample_head(ml, S, cg_philox4x32_10(env_g, tick, CG_SITE_HMARL_SKILL, 0u, k0, k1).v[0], false, logp);
+      skill = __builtin_amdgcn_readfirstlane(skill);
+      if (tr.logits_out && lane < S) tr.logits_out[(size_t)srow * S + lane] = ml[lane];
+      wsync();                                             // (the block is free again before step 3 writes it)
+      const int na = hm_byte(q.n_allowed, skill);
+      if ((q.net_mask >> skill) & 1u) {
+        uint32_t bh = 0u, bl = 0u;
+        if (lane < K) {
+          bh = float_order_bits(subs[skill * K + lane]);
+          bl = ~(uint32_t)lane;
+        }
+        idx = wave_first_max(bh, bl);
+        idx = idx < na - 1 ? idx : na - 1;   // :241
+      } else {
+        idx = (int)(cg_philox4x32_10(env_g, tick, CG_SITE_HMARL_TYPE, 0u, k0, k1).v[0] % (uint32_t)na);   // random.choice (:233)
+      }
+      idx = __builtin_amdgcn_readfirstlane(idx);
+      if (lane == 0) tr.idx_out[srow] = skill;             // what the master's buffer stores
+    } else {   // phase 1 (:808-814): the type index drawn over ALL K outputs of the forced skill's net, clamped, logp of the CLAMPED index
+      skill = tr.force_skill;
+      const int na = hm_byte(q.n_allowed, skill);
+      const float* l = subs + skill * K;
+      float lp_raw;
+      idx = sample_head(l, K, cg_philox4x32_10(env_g, tick, CG_SITE_HMARL_TYPE_SAMPLE, 0u, k0, k1).v[0], false, lp_raw);
+      idx = idx < na - 1 ? idx : na - 1;   // :812
+      idx = __builtin_amdgcn_readfirstlane(idx);
+      logp = hm_logp(l, K, idx);           // :814
+      if (tr.logits_out && lane < K) tr.logits_out[(size_t)srow * K + lane] = l[lane];
+      if (lane == 0) tr.idx_out[srow] = idx;               // :823
+    }
+    if (lane == 0) {
+      tr.skill_out[srow] = skill;
+      tr.type_out[srow] = hm_byte(q.allowed, skill * HM_MAX_TYPES + idx);
+      tr.logp_out[srow] = logp;
+      tr.value_out[srow] = value;
+    }
+  } else {
   // ---------------- 1. the skill ----------------
-  int skill;
   if (q.master == 0) {   // ExpertRuleMaster.select_skill_index (HMARL.py:336-354)
     int cnt = 0;
     bool dc = false;
@@ -72,7 +146,6 @@ __global__ __launch_bounds__(HM_THREADS_MAX) void hmarl_kernel(cygym_hmarl q, cy
   skill = __builtin_amdgcn_readfirstlane(skill);
   // ---------------- 2. the type (FrozenSubPolicy._pick_action_type, :229-244) ----------------
   const int na = hm_byte(q.n_allowed, skill);
-  int idx;
   if ((q.net_mask >> skill) & 1u) {
     uint32_t bh = 0u, bl = 0u;
     if (lane < q.n_logits) {
@@ -85,6 +158,7 @@ __global__ __launch_bounds__(HM_THREADS_MAX) void hmarl_kernel(cygym_hmarl q, cy
     idx = (int)(cg_philox4x32_10(env_g, tick, CG_SITE_HMARL_TYPE, 0u, k0, k1).v[0] % (uint32_t)na);   // random.choice (:233)
   }
   idx = __builtin_amdgcn_readfirstlane(idx);
+  }
   int t = __builtin_amdgcn_readfirstlane(hm_byte(q.allowed, skill * HM_MAX_TYPES + idx));
   if (OUTS && lane == 0) {
     if (q.skill_out) q.skill_out[srow] = skill;

@@ -84,6 +84,7 @@ extern template __global__ void hier_loss_kernel<true>(cygym_hier_loss_desc);
 namespace cygym_k {
 extern template __global__ void hmarl_kernel<false>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
 extern template __global__ void hmarl_kernel<true>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
+extern template __global__ void hmarl_kernel<true, true>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int, cygym_hmarl_train);
 }  // namespace cygym_k
 
 // the MetaDOAR decode lives in its own unit (cg_inst_meta.hip): declared, not instantiated, here
@@ -116,6 +117,14 @@ extern template __global__ void critic_tail_bwd_kernel<false, 0>(cygym_critic_ta
 extern template __global__ void critic_tail_bwd_kernel<false, 8>(cygym_critic_tail_desc);
 extern template __global__ void critic_tail_bwd_kernel<true, 0>(cygym_critic_tail_desc);
 extern template __global__ void critic_tail_bwd_kernel<true, 8>(cygym_critic_tail_desc);
+}  // namespace cygym_k
+
+// the H-MARL PPO kernels live in their own unit (cg_inst_ppo.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void ppo_finish_kernel<false>(cygym_ppo_finish_desc, float, float);
+extern template __global__ void ppo_finish_kernel<true>(cygym_ppo_finish_desc, float, float);
+extern template __global__ void cat_ppo_kernel<false>(cygym_cat_ppo_desc, float, float);
+extern template __global__ void cat_ppo_kernel<true>(cygym_cat_ppo_desc, float, float);
 }  // namespace cygym_k
 
 // =====================================================================
@@ -258,6 +267,9 @@ int cygym_sizeof(int32_t which) {
     case 21: return (int)sizeof(cygym_hmarl);
     case 23: return (int)sizeof(cygym_meta);   // (index 22 stays unassigned)
     case 25: return (int)sizeof(cygym_meta_select_desc);   // (index 24 stays unassigned)
+    case 27: return (int)sizeof(cygym_ppo_finish_desc);   // (index 26 stays unassigned: earlier bindings probe it for -1)
+    case 28: return (int)sizeof(cygym_cat_ppo_desc);
+    case 29: return (int)sizeof(cygym_hmarl_train);
     default: return -1;
   }
 }
@@ -948,16 +960,48 @@ static int hier_loss_launch(cygym_handle* h, const cygym_hier_loss_desc* e, void
 int cygym_hier_loss(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream) { return hier_loss_launch(h, e, stream, false, "cygym_hier_loss"); }
 int cygym_hier_loss_backward(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream) { return hier_loss_launch(h, e, stream, true, "cygym_hier_loss_backward"); }
 
-int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_actions* dst, void* stream) {
-  const char* const who = "cygym_hmarl_decode";
+int cygym_ppo_finish(cygym_handle* h, const cygym_ppo_finish_desc* e, void* stream) {
+  const char* const who = "cygym_ppo_finish";
+  if (!e || !e->rew || !e->val || !e->adv || !e->ret) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (e->T < 1 || e->N < 1 || !(e->gamma == e->gamma) || !(e->lam == e->lam)) return fail(h, CYGYM_EINVAL, "%s: bad layout (T, N >= 1, gamma and lam numbers)", who);
+  if (h) HIPCHK(h, hipSetDevice(h->device_id));
+  cygym_ppo_finish_desc arg = *e;
+  float g = (float)e->gamma, gl = (float)(e->gamma * e->lam);   // the reference's Python floats, as its fp32 tensor ops receive them
+  void* args[3] = {&arg, &g, &gl};
+  const void* k = e->T > 1 ? (const void*)ppo_finish_kernel<true> : (const void*)ppo_finish_kernel<false>;
+  HIPCHK(h, hipLaunchKernel(k, dim3((e->N + PF_TPB - 1) / PF_TPB), dim3(PF_TPB), args, 0, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+static int cat_ppo_launch(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream, bool bwd, const char* who) {
+  if (!e || !e->logits || !e->act || !e->old_logp || !e->adv || !e->ret || !e->v_pred || (bwd ? !(e->g_stats && e->d_logits && e->d_v) : !e->stats))
+    return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (e->B < 1 || e->K < 1 || !(e->clip >= 0.0)) return fail(h, CYGYM_EINVAL, "%s: bad layout (B, K >= 1, clip >= 0)", who);
+  if (e->K > PPO_MAX_K) return fail(h, CYGYM_EUNSUPPORTED, "%s: at most 32 classes", who);
+  if (h) HIPCHK(h, hipSetDevice(h->device_id));
+  cygym_cat_ppo_desc arg = *e;
+  float lo = (float)(1.0 - e->clip), hi = (float)(1.0 + e->clip);   // torch.clamp's Python-float bounds as fp32
+  void* args[3] = {&arg, &lo, &hi};
+  const void* k = bwd ? (const void*)cat_ppo_kernel<true> : (const void*)cat_ppo_kernel<false>;
+  HIPCHK(h, hipLaunchKernel(k, dim3((e->B + CP_TPB - 1) / CP_TPB), dim3(CP_TPB), args, 0, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+int cygym_cat_ppo_loss(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream) { return cat_ppo_launch(h, e, stream, false, "cygym_cat_ppo_loss"); }
+int cygym_cat_ppo_loss_backward(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream) { return cat_ppo_launch(h, e, stream, true, "cygym_cat_ppo_loss_backward"); }
+
+// What cygym_hmarl_decode and cygym_hmarl_sample_decode check alike (tr: the training launch, whose logits come from h0).
+static int hmarl_check(cygym_handle* h, const cygym_hmarl* q, const cygym_hmarl_train* tr, const cygym_actions* dst, const char* who) {
   if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
-  if (!q || !dst || (q->master == 1 && !q->master_logits) || (q->net_mask && !q->sub_logits)) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (!q || !dst || (!tr && ((q->master == 1 && !q->master_logits) || (q->net_mask && !q->sub_logits)))) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
   if (const int rc = check_dst(h, dst, who, true)) return rc;
-  const char* const bad = "cygym_hmarl_decode: bad layout (%s)";
+  char bad[96];
+  snprintf(bad, sizeof(bad), "%s: bad layout (%%s)", who);
   if ((q->master != 0 && q->master != 1) || (q->role != 1 && q->role != 2)) return fail(h, CYGYM_EINVAL, bad, "master 0 or 1, role 1 or 2");
   if (q->n_skills < 1 || q->n_skills > CG_HMARL_MAX_SKILLS || q->n_types < 1 || q->n_types > CG_HMARL_MAX_TYPES)
     return fail(h, CYGYM_EINVAL, bad, "1 to 8 skills, 1 to 32 action types");
-  if (q->net_mask && (q->n_logits < 1 || q->n_logits > HM_MAX_LOGITS || (q->net_mask >> q->n_skills))) return fail(h, CYGYM_EINVAL, bad, "1 to 32 logits per skill, net_mask within the skills");
+  if ((q->net_mask || tr) && (q->n_logits < 1 || q->n_logits > HM_MAX_LOGITS || (q->net_mask >> q->n_skills))) return fail(h, CYGYM_EINVAL, bad, "1 to 32 logits per skill, net_mask within the skills");
   if (q->master == 0 && (q->cheap_idx < 0 || q->cheap_idx >= q->n_skills || q->costly_idx < 0 || q->costly_idx >= q->n_skills || q->global_idx < 0 || q->global_idx >= q->n_skills))
     return fail(h, CYGYM_EINVAL, bad, "the expert master's indices must name skills");
   for (int s = 0; s < q->n_skills; ++s) {
@@ -970,9 +1014,25 @@ int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_action
   for (int t = 0; t < q->n_types; ++t)
     if (q->kind[t] > CG_HMARL_SHUFFLE || q->batch_len[t] < 0 || !(q->cost_comp[t] >= 0.0) || !(q->cost_comp[t] < 1e300) || !(q->cost_not[t] >= 0.0) || !(q->cost_not[t] < 1e300))
       return fail(h, CYGYM_EINVAL, bad, "a kind above CG_HMARL_SHUFFLE, a negative batch length, or a cost that is negative or not finite");
+  if (tr) {
+    if (!tr->h0 || !tr->v_w2 || !tr->v_b2 || !tr->skill_out || !tr->idx_out || !tr->type_out || !tr->logp_out || !tr->value_out ||
+        (tr->force_skill < 0 && (!tr->pi_w2 || !tr->pi_b2)))
+      return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+    if (q->fanout > 64) return fail(h, CYGYM_EINVAL, bad, "fanout <= 64");
+    if (tr->force_skill >= q->n_skills || (tr->force_skill >= 0 && !((q->net_mask >> tr->force_skill) & 1u)))
+      return fail(h, CYGYM_EINVAL, bad, "force_skill must name a skill with a net");
+    const bool p2 = tr->force_skill < 0;
+    if (tr->Hv < 1 || (p2 && tr->Hp < 1)) return fail(h, CYGYM_EUNSUPPORTED, "%s: hidden widths from 1 to 256", who);
+    if (tr->Hv > 256 || (p2 && tr->Hp > 256)) return fail(h, CYGYM_EUNSUPPORTED, "%s: hidden widths from 1 to 256", who);
+    if ((int64_t)tr->ld < (int64_t)(p2 ? tr->Hp : 0) + tr->Hv + (int64_t)q->n_skills * q->n_logits) return fail(h, CYGYM_EINVAL, bad, "ld >= Hp + Hv + n_skills * n_logits");
+  }
   if (!h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (the decision reads the flag plane and the envs' rng ticks)", who);
   if (h->t.M > HM_MAX_M) return fail(h, CYGYM_EUNSUPPORTED, "%s: at most 2048 devices", who);
-  if (const int rc = check_rows(h, q->n, q->rows, 0, who)) return rc;
+  return check_rows(h, q->n, q->rows, 0, who);
+}
+
+int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_actions* dst, void* stream) {
+  if (const int rc = hmarl_check(h, q, nullptr, dst, "cygym_hmarl_decode")) return rc;
   if (q->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   const int wpb = hm_waves(h->t.M);
@@ -982,6 +1042,21 @@ int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_action
   const uint8_t* dstatic = h->t.dstatic;
   int M = h->t.M;
   return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &dstatic, &M});
+}
+
+int cygym_hmarl_sample_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_hmarl_train* tr, const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_hmarl_sample_decode";
+  if (h && !tr) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (const int rc = hmarl_check(h, q, tr, dst, who)) return rc;
+  if (q->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const int wpb = hm_waves(h->t.M);
+  const size_t lds = (size_t)wpb * hm_wave_bytes(h->t.M);
+  const void* k = (const void*)hmarl_kernel<true, true, cygym_hmarl_train>;
+  const uint8_t* live = (const uint8_t*)h->b.live;
+  const uint8_t* dstatic = h->t.dstatic;
+  int M = h->t.M;
+  return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &dstatic, &M, tr});
 }
 
 int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions* dst, void* stream) {

@@ -1226,6 +1226,44 @@ def _hmarl_walk(x, u32):
     return pick, clear
 
 
+def _hmarl_groups(f, dstatic, cfg, table, t, seed, e, tk):
+    """The groups of ONE row for action type t: the ordered targets of the type's kind (HMARL.py:139-154, :263-267), cut into cost
+    batches (:170-187) and at the fanout (:304-306) -- the part of the decision behind the type, shared by hmarl_decide and
+    hmarl_sample_decide."""
+    import numpy as np
+    from . import abi, rng as R, spec as S
+    kind, cc, cn = table
+    ids = np.arange(len(f))
+    comp, owned, reach, nya = (f & S.F_COMP) != 0, (f & S.F_OWNED) != 0, (f & S.F_REACH) != 0, (f & S.F_NYA) != 0
+    dc = (dstatic & S.D_DC) != 0
+    hot = comp & ~owned
+    order = []
+    if kind[t] == abi.HMARL_HIGH:                                # :139-154
+        score = np.where(hot & dc, 100, np.where(hot, 50, np.where(comp, 40, np.where(reach, 20, 0))))
+        vis = ids[~nya]
+        order = vis[np.argsort(-score[vis], kind="stable")].tolist()
+    elif kind[t] == abi.HMARL_SHUFFLE:                           # :263-267
+        seeds = ids[~nya & (owned | comp)]
+        if not len(seeds):
+            seeds = ids[~nya]
+        key = R.draw_np(seed, np.full(len(seeds), e, np.uint64), np.full(len(seeds), tk, np.uint64), S.SITE_HMARL_SHUFFLE, a=seeds)
+        order = seeds[np.lexsort((seeds, key))].tolist()
+    if kind[t] == abi.HMARL_EMPTY:
+        return [(int(t), [])]
+    if not order:                                                # :309-312
+        return [(cfg.fallback, [])]
+    batches, cur, cost = [], [], 0.0                             # :170-187, the float64 loop as it stands
+    for d in order:
+        dcost = float(cc[t]) if comp[d] else float(cn[t])
+        if cur and (cost + dcost) > cfg.budget:
+            batches.append(cur)
+            cur, cost = [], 0.0
+        cur.append(int(d))
+        cost += dcost
+    batches.append(cur)
+    return [(int(t), b[:cfg.fanout]) for b in batches]           # :304-306
+
+
 def hmarl_decide(flags, dstatic, role, cfg: HMARLConfig, master_logits, sub_logits, seed, env_ids, ticks):
     """BaseHMARLBR.execute (HMARL.py:595-607) for n rows in numpy, as include/cygym_abi.h restates it under cygym_hmarl_decode: the
     restatement the kernel is tested against.
@@ -1234,20 +1272,17 @@ def hmarl_decide(flags, dstatic, role, cfg: HMARLConfig, master_logits, sub_logi
     Returns (skill [n], atype [n] -- the sub-policy's type --, groups: per row the list of (type, [device ids]) in group order, clear [n]:
     False where the learned master's draw lies within the fp32 walk's error bound of a CDF boundary, such a row may differ)."""
     import numpy as np
-    from . import abi, rng as R, spec as S
+    from . import rng as R, spec as S
     if role != cfg.role:
         raise ValueError(f"the config belongs to the {cfg.role}")
     flags, dstatic = np.asarray(flags, np.uint8), np.asarray(dstatic, np.uint8)
-    n, M = flags.shape
+    n = flags.shape[0]
     kind, cc, cn, _ = cfg.table()
     thr = R.bernoulli_threshold(cfg.global_prob)
-    ids = np.arange(M)
     skill, atype, groups, clear = np.zeros(n, np.int64), np.zeros(n, np.int64), [], np.ones(n, bool)
     for i in range(n):
         f, e, tk = flags[i], int(env_ids[i]), int(ticks[i])
-        comp, owned, reach, nya = (f & S.F_COMP) != 0, (f & S.F_OWNED) != 0, (f & S.F_REACH) != 0, (f & S.F_NYA) != 0
-        dc = (dstatic & S.D_DC) != 0
-        hot = comp & ~owned
+        hot, dc = (f & (S.F_COMP | S.F_OWNED)) == S.F_COMP, (dstatic & S.D_DC) != 0
         if cfg.master == "expert":                                   # HMARL.py:336-354
             if (hot & dc).any():
                 sk = cfg.costly_idx
@@ -1264,34 +1299,54 @@ def hmarl_decide(flags, dstatic, role, cfg: HMARLConfig, master_logits, sub_logi
         else:
             t = allowed[int(R.draw_np(seed, e, tk, S.SITE_HMARL_TYPE)) % len(allowed)]
         skill[i], atype[i] = sk, t
-        order = []
-        if kind[t] == abi.HMARL_HIGH:                                # :139-154
-            score = np.where(hot & dc, 100, np.where(hot, 50, np.where(comp, 40, np.where(reach, 20, 0))))
-            vis = ids[~nya]
-            order = vis[np.argsort(-score[vis], kind="stable")].tolist()
-        elif kind[t] == abi.HMARL_SHUFFLE:                           # :263-267
-            seeds = ids[~nya & (owned | comp)]
-            if not len(seeds):
-                seeds = ids[~nya]
-            key = R.draw_np(seed, np.full(len(seeds), e, np.uint64), np.full(len(seeds), tk, np.uint64), S.SITE_HMARL_SHUFFLE, a=seeds)
-            order = seeds[np.lexsort((seeds, key))].tolist()
-        if kind[t] == abi.HMARL_EMPTY:
-            groups.append([(int(t), [])])
-            continue
-        if not order:                                                # :309-312
-            groups.append([(cfg.fallback, [])])
-            continue
-        batches, cur, cost = [], [], 0.0                             # :170-187, the float64 loop as it stands
-        for d in order:
-            dcost = float(cc[t]) if comp[d] else float(cn[t])
-            if cur and (cost + dcost) > cfg.budget:
-                batches.append(cur)
-                cur, cost = [], 0.0
-            cur.append(int(d))
-            cost += dcost
-        batches.append(cur)
-        groups.append([(int(t), b[:cfg.fanout]) for b in batches])   # :304-306
+        groups.append(_hmarl_groups(f, dstatic, cfg, (kind, cc, cn), t, seed, e, tk))
     return skill, atype, groups, clear
+
+
+def hmarl_sample_decide(flags, dstatic, role, cfg: HMARLConfig, master_logits, sub_logits, seed, env_ids, ticks, force_skill: int = -1):
+    """The TRAINING decision of HMARLMetaBestResponse.train for n rows in numpy / float64, taking logits and draws like hmarl_decide:
+      force_skill < 0 (phase 2, HMARL.py:848-852): the skill is drawn from the master's Categorical (_master_act, :759-765) by
+        sample_head's walk with the CG_SITE_HMARL_SKILL draw -- the eval decode's draw --, logp is its log-probability, and the type is
+        the drawn skill's GREEDY one (select_action, :229-244).  The stored index is the skill.
+      force_skill >= 0 (phase 1, :808-814): the type index is drawn from the skill's net over ALL n_logits outputs by the same walk with
+        the CG_SITE_HMARL_TYPE_SAMPLE draw, then clamped to n_allowed - 1 (:812); logp is log_prob of the CLAMPED index under the
+        unclamped distribution (:814), and the clamped index is what the buffer stores (:823).  The skill must have a net.
+    Returns (skill [n], idx [n] the stored index, atype [n], logp [n] float64, groups as hmarl_decide, clear [n]: False where the draw
+    lies within the fp32 walk's error bound of a CDF boundary).  The value estimate is the caller's (master.v / the skill's value head)."""
+    import numpy as np
+    from . import rng as R, spec as S
+    if role != cfg.role:
+        raise ValueError(f"the config belongs to the {cfg.role}")
+    flags, dstatic = np.asarray(flags, np.uint8), np.asarray(dstatic, np.uint8)
+    n = flags.shape[0]
+    if force_skill >= 0 and (force_skill >= cfg.n_skills or not cfg.has_net[force_skill]):
+        raise ValueError("force_skill must name a skill with a net")
+    if force_skill < 0 and cfg.master != "learned":
+        raise ValueError("the master's draw needs a learned master")
+    table = cfg.table()[:3]
+    skill, idx, atype, logp, groups, clear = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n), [], np.ones(n, bool)
+    lsm = lambda x: x - (np.log(np.exp(x - x.max()).sum()) + x.max())  # noqa: E731
+    for i in range(n):
+        e, tk = int(env_ids[i]), int(ticks[i])
+        subs = None if sub_logits is None else np.asarray(sub_logits[i], np.float32).reshape(cfg.n_skills, cfg.n_logits)
+        if force_skill < 0:
+            ml = np.asarray(master_logits[i], np.float32)
+            sk, clear[i] = _hmarl_walk(ml, int(R.draw_np(seed, e, tk, S.SITE_HMARL_SKILL)))
+            allowed = cfg.allowed[sk]
+            if cfg.has_net[sk]:
+                t = allowed[min(int(np.argmax(subs[sk])), len(allowed) - 1)]
+            else:
+                t = allowed[int(R.draw_np(seed, e, tk, S.SITE_HMARL_TYPE)) % len(allowed)]
+            idx[i], logp[i] = sk, lsm(ml.astype(np.float64))[sk]
+        else:
+            sk, allowed = force_skill, cfg.allowed[force_skill]
+            raw, clear[i] = _hmarl_walk(subs[sk], int(R.draw_np(seed, e, tk, S.SITE_HMARL_TYPE_SAMPLE)))
+            a = max(0, min(raw, len(allowed) - 1))
+            t = allowed[a]
+            idx[i], logp[i] = a, lsm(subs[sk].astype(np.float64))[a]
+        skill[i], atype[i] = sk, t
+        groups.append(_hmarl_groups(flags[i], dstatic, cfg, table, t, seed, e, tk))
+    return skill, idx, atype, logp, groups, clear
 
 
 class _HMARLMaster(nn.Module):
@@ -1426,6 +1481,50 @@ class HMARLPolicy:
                 pk.update(ws=w, bs=b)
             self._pk = pk
         return self._pk
+
+    @torch.no_grad()
+    def train_pack(self, device=None, skill: int = -1, v_head=None):
+        """What the training launch (cygym_hmarl_sample_decode) needs of the nets, following the `_packed` pattern -- rebuilt when a
+        parameter's version changes (an optimiser step), else the cached one.
+          skill < 0 (phase 2): w1 [state, Hp + Hv + S K] = pi_fc1 | v_fc1 | the skills' fc (transposed, ONE addmm), b1; pi_w2 [S, Hp],
+                               pi_b2 [S], v_w2 [Hv], v_b2 [1] of the learned master
+          skill >= 0 (phase 1): w1 [state, Hv + S K] = v_head[0] | the skills' fc, b1; v_w2 / v_b2 of `v_head`, the skill's value head
+                               (hmarl_rollout.skill_value_head: Linear - ReLU - Linear)"""
+        device = torch.device(device) if device is not None else next(m.fc.weight.device for m in self.subnets if m is not None)
+        p2 = skill < 0
+        if p2 and self.master is None:
+            raise ValueError("the training decision of phase 2 needs a learned master")
+        if not p2 and (v_head is None or self.subnets[skill] is None):
+            raise ValueError("phase 1 needs a skill with a net and its value head")
+        mods = ([self.master] if p2 else [v_head]) + [m for m in self.subnets if m is not None]
+        key = (device, skill, id(v_head), tuple(p._version for m in mods for p in m.parameters()), tuple(id(p) for m in mods for p in m.parameters()))
+        tp = getattr(self, "_tp", None)
+        if tp is not None and tp["key"] == key:
+            return tp
+        K, S_ = self.cfg.n_logits, self.cfg.n_skills
+        first = [(self.master.pi_fc1, self.master.v_fc1)] if p2 else [(v_head[0],)]
+        cols_w = [l.weight.t().to(device) for l in first[0]]
+        cols_b = [l.bias.to(device) for l in first[0]]
+        for net in self.subnets:
+            cols_w.append(net.fc.weight.t().to(device) if net is not None else torch.zeros((self.state_dim, K), dtype=torch.float32, device=device))
+            cols_b.append(net.fc.bias.to(device) if net is not None else torch.zeros((K,), dtype=torch.float32, device=device))
+        tp = {"key": key, "skill": skill, "w1": torch.cat(cols_w, dim=1).contiguous(), "b1": torch.cat(cols_b).contiguous()}
+        if p2:
+            m = self.master
+            tp.update(pi_w2=m.pi_fc2.weight.detach().to(device).contiguous().clone(), pi_b2=m.pi_fc2.bias.detach().to(device).clone(),
+                      v_w2=m.v_fc2.weight.detach().to(device).reshape(-1).contiguous().clone(), v_b2=m.v_fc2.bias.detach().to(device).reshape(1).clone(),
+                      Hp=int(m.pi_fc1.out_features), Hv=int(m.v_fc1.out_features))
+        else:
+            tp.update(v_w2=v_head[2].weight.detach().to(device).reshape(-1).contiguous().clone(), v_b2=v_head[2].bias.detach().to(device).reshape(1).clone(),
+                      Hp=0, Hv=int(v_head[0].out_features))
+        assert tp["w1"].shape == (self.state_dim, tp["Hp"] + tp["Hv"] + S_ * K)
+        self._tp = tp
+        return tp
+
+    @torch.no_grad()
+    def h0(self, obs, pack):
+        """The pre-activations the training launch reads, [n, Hp + Hv + S K]: ONE addmm over the concatenated first layers."""
+        return torch.addmm(pack["b1"], obs, pack["w1"])
 
     @torch.no_grad()
     def logits(self, obs):

@@ -59,6 +59,7 @@ SITE_HMARL_COIN = 73
 SITE_HMARL_SKILL = 74
 SITE_HMARL_TYPE = 75
 SITE_HMARL_SHUFFLE = 76
+SITE_HMARL_TYPE_SAMPLE = 77
 
 POISSON_TABLE = 16
 TRI_TABLE = 8

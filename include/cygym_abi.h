@@ -193,7 +193,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl; -1 for anything else, 13, 15 and 18 included: those indices stay unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train; -1 for anything else, 13, 15, 18, 22, 24 and 26 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -887,9 +887,54 @@ typedef struct cygym_hmarl {
  *   n_logits outside 1 .. 32 with net_mask != 0; an n_allowed outside 1 .. 32 or an allowed type >= n_types; an expert index outside
  *   0 .. n_skills - 1; a kind above CG_HMARL_SHUFFLE; fanout < 1; a negative batch_len; a budget or cost that is negative or not finite;
  *   a fallback outside 0 .. 31; a bad row count.  CYGYM_ENOTBOUND without cygym_bind.  M up to 2048.
- * Out of scope: training (_phase1 / _phase2, SubPolicyPPO, _master_update; skill_out is what that needs from this launch), the
- * sanitising of _step_env_grouped (:520-564), and building the logits on chip. */
+ * Out of scope: training (_phase1 / _phase2, SubPolicyPPO, _master_update) -- that is cygym_hmarl_sample_decode below with
+ * cygym_ppo_finish and cygym_cat_ppo_loss, driven by cygym_amd/hmarl_rollout.py --, the sanitising of _step_env_grouped (:520-564), and
+ * building the logits on chip. */
 int cygym_hmarl_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_actions* dst, void* stream);
+
+/* The TRAINING decision of HMARLMetaBestResponse.train (HMARL.py:792-872) for a batch: what cygym_hmarl_decode does, with the skill (phase 2)
+ * or the type index (phase 1) DRAWN, its log-probability and the value estimate stored -- one addmm of the caller plus ONE launch,
+ * where the reference runs _master_act (:759-765: pi, a Categorical, v) and select_action, or the skill's net, a Categorical and the
+ * value head (:808-815).  Rides along with a cygym_hmarl whose master_logits / sub_logits / skill_out / type_out are NOT read: the
+ * logits come from h0.  All DEVICE pointers. */
+typedef struct cygym_hmarl_train {
+  const float* h0;      /* [n][ld] the pre-activations of ONE addmm over the concatenated first layers, per source row:
+                           pi_fc1 (Hp columns; ABSENT when force_skill >= 0) | the value net's first layer (Hv columns) |
+                           the skills' fc logits (n_skills * n_logits columns, already final; zeros for a skill without a net)         */
+  const float* pi_w2;   /* [n_skills][Hp] pi_fc2.weight (force_skill < 0)                                                             */
+  const float* pi_b2;   /* [n_skills]     pi_fc2.bias   (force_skill < 0)                                                             */
+  const float* v_w2;    /* [Hv] the value net's second layer: v_fc2.weight, or the forced skill's value head (HMARL.py:416-419)       */
+  const float* v_b2;    /* [1]  its bias                                                                                              */
+  int32_t* skill_out;   /* [n] the skill: drawn, or force_skill                                                                      */
+  int32_t* idx_out;     /* [n] the index the PPO buffer stores: the skill (phase 2), the CLAMPED type index (phase 1, :812, :823)    */
+  int32_t* type_out;    /* [n] the action type                                                                                       */
+  float* logp_out;      /* [n] log-probability of idx_out under the distribution it was drawn from                                   */
+  float* value_out;     /* [n] the value estimate                                                                                    */
+  float* logits_out;    /* optional [n][n_skills] the master's logits (phase 2) / [n][n_logits] the forced skill's (phase 1)         */
+  int32_t ld, Hp, Hv;   /* row pitch of h0 in floats; widths of the two hidden layers, 1 .. 256 each, any value                      */
+  int32_t force_skill;  /* -1: phase 2, the master draws; >= 0: phase 1, this skill's net draws the type                              */
+} cygym_hmarl_train;
+/* One wave per source row, no workgroup barrier.  Per row:
+ *   second layers on chip: out = b + sum_c relu(h0[c]) w[c] -- lane j adds its columns j, j + 64, ... in ascending order with fmaf
+ *     (start 0), the 64 partial sums are added by the xor butterfly with offsets 32, 16, .., 1, then the bias.  value_out is that of
+ *     the value columns; in phase 2 the n_skills master logits likewise.
+ *   force_skill < 0: skill ~ Categorical(logits = master logits) by sample_head's walk (fp32, max-subtracted __expf, the first k whose
+ *     running sum exceeds (float)u32 2^-32 S, else the last) with u32 = the CG_SITE_HMARL_SKILL draw -- the eval decode's draw, so the
+ *     launch's own logits_out fed to cygym_hmarl_decode give the same skill and the same rows.  logp = l[skill] - max - __logf(S).  The
+ *     type is the eval decode's: the first maximum of the skill's logits, clamped into its allowed list, or the CG_SITE_HMARL_TYPE draw
+ *     for a skill without a net.  idx_out = skill.
+ *   force_skill >= 0: the type index is drawn by the same walk over ALL n_logits outputs of the skill's net with the
+ *     CG_SITE_HMARL_TYPE_SAMPLE draw, then clamped to n_allowed - 1 (:812); logp is that of the CLAMPED index under the unclamped
+ *     distribution (:814); idx_out = the clamped index (:823).  Every tick is the learner's and env.mode never changes: the caller
+ *     launches per tick.  The reference's `if not grouped` and the sanitising of _step_env_grouped (:520-564) never act on what
+ *     select_action returns -- a group holds at most fanout ids of existing devices -- and are restated as: fanout <= 64.
+ *   Targets, batches, groups, cuts and CG_DECODE_TRUNCATED: steps 3 to 5 of cygym_hmarl_decode, the same code.
+ * The rng tick is read, not advanced.  The same inputs and draws give the same bits.
+ * CYGYM_EINVAL (nothing is written): as cygym_hmarl_decode (without its logit pointers); a NULL `tr`, h0, v_w2, v_b2 or one of the five
+ *   mandatory outputs; pi_w2 / pi_b2 NULL with force_skill < 0; fanout > 64; force_skill >= n_skills or a forced skill without a net;
+ *   ld < Hp + Hv + n_skills * n_logits (Hp counted only with force_skill < 0); no skill with a net and n_logits outside 1 .. 32.
+ * CYGYM_EUNSUPPORTED (nothing is written): Hp (phase 2) or Hv outside 1 .. 256; more than 2048 devices.  CYGYM_ENOTBOUND as the decode. */
+int cygym_hmarl_sample_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_hmarl_train* tr, const cygym_actions* dst, void* stream);
 
 /* A MetaDOAR strategy (meta_hierarchical_br.py: MetaHierarchicalBestResponse, type_mapping["meta"]) and the role's DDPG critic in the
  * pieces the decode below reads, all fp32.  DEVICE pointers.  With id_dim, embed_dim = ED, proj_dim = P the controller is
@@ -1057,6 +1102,88 @@ typedef struct cygym_meta_select_desc {
  * Out of scope: train_controller itself (64 rows through state_proj: torch, cygym_amd/meta_rollout.py), next_state / done and
  *   target_state_proj (stored or updated by the reference, never read), M > 1000. */
 int cygym_meta_select(cygym_handle* h, const cygym_meta_select_desc* q, void* stream);
+
+/* The H-MARL PPO updates (HMARL.py: _master_update :767-789 for the master over the skills, SubPolicyPPO.update :427-447 for a skill's
+ * net) in the two pieces that are no GEMM, for a batch.  What the reference does there, restated because it is not what one expects:
+ *   - The bootstrap value is discarded.  _phase2_train_master calls buf.finish(last_value = master.v(last state)) (:868-870), and
+ *     _master_update then calls buf.finish(last_value = 0.0) (:770; SubPolicyPPO.update :430 alike), which recomputes adv and ret from
+ *     rew and val from scratch (:67-83).  The effective last_value is 0.  cygym_ppo_finish keeps the argument; a caller that follows the
+ *     reference passes NULL.
+ *   - finish ignores `done`: no episode cut in the GAE (:73-76).
+ *   - Advantages are normalised per BUFFER -- per env column of a [T, N] batch -- with the population standard deviation, and only when
+ *     T > 1 (:80-83).
+ *   - The learner sees reward 0.0 and done = False on every step as shipped: step_grouped returns a 6-tuple (volt_typhoon_env.py:779),
+ *     and _coerce_step_ret (:502-519) accepts 4- and 5-tuples only and falls back to (state, 0.0, False, {}).  What goes into `rew` is
+ *     the caller's decision (hmarl_rollout.train's required reward= keyword); nothing here depends on it.
+ * All DEVICE pointers, contiguous.  h may be NULL: the launch then goes to the caller's current device and an error text to
+ * cygym_last_error(NULL); with a handle, to the handle's device.
+ *
+ * cygym_ppo_finish: PPOBuffer.finish for N buffers of T steps each, stored [T][N] (step-major: the N envs of a batch tick in lock step). */
+typedef struct cygym_ppo_finish_desc {
+  const float* rew;         /* [T][N]                                                                                  */
+  const float* val;         /* [T][N] the value estimates stored with the steps                                        */
+  const float* last_value;  /* [N] the value behind the last step, or NULL = 0 (what the reference's updates use)      */
+  float* adv;               /* out [T][N]; must not overlap rew or val                                                 */
+  float* ret;               /* out [T][N]; must not overlap rew or val                                                 */
+  double gamma, lam;        /* the reference's Python floats (0.99, 0.95)                                              */
+  int32_t T, N;
+} cygym_ppo_finish_desc;
+/* ONE launch, one lane per column walking t = T - 1 .. 0 (loads and stores of a step are contiguous over the columns).  With
+ * g = (float)gamma, gl = (float)(gamma * lam) (the product formed in double, as Python forms it), v[T] = last_value, gae[T] = 0:
+ *     delta  = (rew[t] + g * v[t + 1]) - v[t]
+ *     gae[t] = delta + gl * gae[t + 1]
+ *     ret[t] = gae[t] + v[t]
+ * every operation rounding to fp32 on its own, no contraction: the reference's chain of 0-dim fp32 tensor ops, so `ret` is BIT-EQUAL to
+ * PPOBuffer.finish's.  T > 1: adv[t] = (gae[t] - m) / (s + 1e-8) with m the mean and s the population standard deviation of the column,
+ * both accumulated in float64 during the walk as sums of d = gae[t] - gae[T - 1] and d * d (a constant column has s = 0 and adv = 0
+ * exactly), the quotient formed in float64 and rounded once.  (The reference forms m, s and the quotient in fp32; float64 is the closer
+ * of the two to the exact value.)  T = 1: adv = gae, not normalised.
+ * CYGYM_EINVAL (nothing is written): a NULL struct or pointer other than last_value, T or N < 1, a NaN gamma or lam. */
+int cygym_ppo_finish(cygym_handle* h, const cygym_ppo_finish_desc* e, void* stream);
+
+/* The PPO loss head of a Categorical over K <= 32 classes (the master's S skills, a skill's n_logits types) behind the logits and the
+ * value prediction, and its backward.  The Linear layers, the three means, the coefficients, the gradient clipping and Adam stay with
+ * the caller (torch), as with cygym_hier_loss. */
+typedef struct cygym_cat_ppo_desc {
+  const float* logits;     /* [B][K] the net's output for the minibatch's rows                                                       */
+  const int64_t* act;      /* [B] the stored index, 0 .. K - 1 (an index outside selects no class: logp = 0, and is never used to address) */
+  const float* old_logp;   /* [B] its log-probability when it was drawn                                                                */
+  const float* adv;        /* [B]                                                                                                      */
+  const float* ret;        /* [B]                                                                                                      */
+  const float* v_pred;     /* [B] the value net's output                                                                               */
+  float* stats;            /* forward out [B][3]: surrogate, entropy, squared value error                                              */
+  const float* g_stats;    /* backward in [B][3]: gradient of the loss with respect to stats                                           */
+  float* d_logits;         /* backward out [B][K]                                                                                      */
+  float* d_v;              /* backward out [B]                                                                                         */
+  double clip;             /* the reference's Python float (0.2); lo = (float)(1.0 - clip), hi = (float)(1.0 + clip)                   */
+  int32_t B, K;
+} cygym_cat_ppo_desc;
+/* Forward, ONE launch, one lane per row, fp32 (expf / logf, not the fast forms), every sum over the classes in ASCENDING class order:
+ *     lse = log(sum_k exp(l[k] - max)) + max;  lp[k] = l[k] - lse;  p[k] = exp(l[k] - max) / sum       (Categorical(logits = l))
+ *     r = exp(lp[act] - old_logp)
+ *     stats[0] = min(r adv, clamp(r, lo, hi) adv)
+ *     stats[1] = -sum_k max(lp[k], -FLT_MAX) p[k]          (Categorical.entropy: the clamp at finfo.min matters for a -inf logit only;
+ *                                                           built from logits, the distribution never passes through probs_to_logits)
+ *     stats[2] = (v_pred - ret)^2
+ *   so that loss = -mean(stats[:, 0]) + vf_coef mean(stats[:, 2]) - ent_coef mean(stats[:, 1]) (:779-785, :437-443).
+ * Backward, ONE launch, recomputes the above:
+ *     d_logits[k] = g[0] w adv r (1[k = act] - p[k]) - g[1] p[k] (lp[k] + stats[1])          (second term 0 where p[k] = 0)
+ *     d_v         = 2 g[2] (v_pred - ret)
+ *   w is the tie rule of the minimum and of the clamp, as autograd has them: torch.min of two tensors gives the smaller operand the
+ *   whole gradient and each operand HALF at a tie; clamp passes the gradient for lo <= r <= hi, the ends included.  With s1 = r adv,
+ *   s2 = clamp(r) adv:  w = 1[s1 < s2] + 1/2 1[s1 = s2] + 1[lo <= r <= hi] (1[s2 < s1] + 1/2 1[s1 = s2]).  For r inside the range
+ *   s1 = s2 and the halves add up to the full gradient (w = 1) -- every first minibatch of an update sits there with r = 1.  Outside the
+ *   range a tie needs adv = 0, where the gradient is 0 whatever w is.
+ * Both directions are row-local: no partials, no atomics; the same inputs give the same bits.
+ * Non-finite values: a NaN ratio passes through the clamp and a NaN in either operand of the minimum gives stats[0] = NaN, as
+ *   torch.clamp / torch.min do (r = inf with adv = 0 included: s1 = NaN); the gradients of such a row are NaN or 0 and are not pinned
+ *   to autograd's.  The reference's updates carry no finite check and neither does this.
+ * An `act` outside 0 .. K - 1 selects no class (logp = 0), where Categorical.log_prob would gather out of bounds; it is never used to
+ *   address.  Stored indices are in range by construction (the buffer stores the clamped index).
+ * CYGYM_EUNSUPPORTED: K > 32.  CYGYM_EINVAL: a NULL struct or mandatory pointer (forward: the six inputs and stats; backward: the six
+ * inputs, g_stats, d_logits and d_v), B or K < 1, clip negative or NaN; nothing is written then. */
+int cygym_cat_ppo_loss(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream);
+int cygym_cat_ppo_loss_backward(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`

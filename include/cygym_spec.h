@@ -216,8 +216,11 @@ enum {
                                 u = word 0 / 2^32 walks the inverse CDF of the skills' softmax; same addressing    */
   CG_SITE_HMARL_TYPE = 75,   /* HMARL.py:233 random.choice(allowed_action_types) of a skill without a net: a = b = 0; the type is
                                 allowed[word 0 % len(allowed)]; same addressing                                   */
-  CG_SITE_HMARL_SHUFFLE = 76 /* HMARL.py:266 random.shuffle(seeds) of attacker type 1: a = device id (sort key): the seeds in
+  CG_SITE_HMARL_SHUFFLE = 76, /* HMARL.py:266 random.shuffle(seeds) of attacker type 1: a = device id (sort key): the seeds in
                                 ascending (word 0, id), the contract's reading of a shuffle as at CG_SITE_SHUFFLE; same addressing */
+  CG_SITE_HMARL_TYPE_SAMPLE = 77 /* HMARL.py:810-811 Categorical(logits = the skill's net).sample() of _phase1_train_subpolicies: a = b = 0;
+                                u = word 0 / 2^32 walks the inverse CDF over ALL n_logits outputs, the index is clamped afterwards
+                                (:812); same addressing (cygym_hmarl_sample_decode, force_skill >= 0)            */
 };
 
 /* ---- Philox4x32-10 (Salmon et al., SC'11), counter-based ----
