@@ -123,6 +123,15 @@ class Critic(C.Structure):
                 ("b3", C.c_float), ("H1", C.c_int32), ("H2", C.c_int32), ("h_stride", C.c_int32), ("top_k", C.c_int32), ("vec_stride", C.c_int32)]
 
 
+DNS_MAX_ITERS = 16
+
+
+class Dns(C.Structure):
+    _fields_ = [("dyn_eps", C.c_void_p), ("gate_out", C.c_void_p), ("trace_i", C.c_void_p), ("trace_q", C.c_void_p), ("trace_beta", C.c_void_p),
+                ("q_out", C.c_void_p), ("q0_out", C.c_void_p), ("dyn_eps_min", C.c_double), ("beta_init", C.c_double), ("c_beta", C.c_double),
+                ("sigma", C.c_double), ("max_iters", C.c_int32), ("n_samples", C.c_int32), ("k_seq", C.c_uint8 * DNS_MAX_ITERS)]
+
+
 class CommActor(C.Structure):
     _fields_ = [("tok_base", C.c_void_p), ("tok_dev", C.c_void_p), ("w_type", C.c_void_p), ("b_type", C.c_void_p), ("w_ctx", C.c_void_p),
                 ("b_ctx", C.c_void_p), ("w_v2", C.c_void_p), ("value_out", C.c_void_p), ("logits_out", C.c_void_p),

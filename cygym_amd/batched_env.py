@@ -656,6 +656,79 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_coord_ascent_decode(self._h, C.byref(cr), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_coord_ascent_decode")
 
+    def dns_decode(self, rows, raw: torch.Tensor, h_state: torch.Tensor, critic_pack, n_types: int, n_exploits: int | None = None,
+                   n_apps: int = 0, type_map=None, act=None, *, k_seq, beta_init: float, c_beta: float, n_samples: int = 75, sigma: float = 0.1,
+                   epsilon: float = 0.0, dyn_eps=None, dyn_eps_min: float = 0.0, gate_out=None, vec_out=None, trace_i=None, trace_q=None,
+                   trace_beta=None, q_out=None, q0_out=None):
+        """DoubleOracle.dynamic_neighborhood_search (do_agent.py:1204-1250) behind the gate of `--dynamic_search` (:1382-1391) for a
+        batch, fused with the scatter into rows `rows` of `act` (group 0): ONE launch (cygym_dns_decode; include/cygym_abi.h states
+        the search, its draws and its deviations).  Rows whose gate does not fall are left alone: decode them first.
+          raw          [n, >= n_out] float32 (unit inner stride): the actor's output the search starts from (not the noisy vec)
+          h_state, critic_pack   as coord_ascent_decode
+          k_seq        k of iteration 1 .. max_iters (policies.dns_k_sequence), each in 1..8; max_iters = len(k_seq) <= 16
+          beta_init, c_beta, n_samples (<= 80), sigma (<= 0.125), epsilon   the search's parameters
+          dyn_eps      optional [N] float64, one gate value per ENV, halved (floor dyn_eps_min) where the gate falls; None: every
+                       row is searched.  `rows` must not name an env twice
+          gate_out     optional [n] uint8: 1 = the search decided the source row
+          vec_out      optional [n, >= n_out] float32: encode_action of a_best on the searched rows
+          trace_i [n, I, 4] int32 (unique neighbours, best sample, branch, choice index), trace_q [n, I, 2] float32 (Q1, Q_bar after),
+          trace_beta [n, I] float64, q_out [n, I, n_samples] float32, q0_out [n] float32: optional, for tests and learners"""
+        dst = self.actions_struct(act)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not ok(h_state) or h_state.dim() != 2 or h_state.stride(1) != 1:
+            raise ValueError("h_state must be a [n, H1] float32 tensor on the batch's device with unit inner stride")
+        n, H1 = int(h_state.shape[0]), int(h_state.shape[1])
+        src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, epsilon)
+        if not ok(raw) or raw.dim() != 2 or int(raw.shape[0]) != n or int(raw.shape[1]) < n_out or raw.stride(1) != 1 \
+                or (n > 1 and raw.stride(0) < n_out):
+            raise ValueError(f"raw must be a float32 [{n}, >= {n_out}] tensor on {self.device} with unit inner stride")
+        src.vec, src.stride = raw.data_ptr(), int(raw.stride(0)) if n > 1 else int(raw.shape[1])
+        w1a_t, w2, b2, w3, b3 = critic_pack
+        H2 = int(w3.numel())
+        if not ok(w1a_t) or tuple(w1a_t.shape) != (n_out, H1) or not w1a_t.is_contiguous():
+            raise ValueError(f"critic_pack: w1a_t must be a contiguous float32 {[n_out, H1]} tensor (fc1.weight[:, W:].t())")
+        if not ok(w3) or not w3.is_contiguous() or H2 < 1:
+            raise ValueError("critic_pack: w3 must be a contiguous float32 [H2] tensor")
+        if not ok(w2) or not w2.is_contiguous() or w2.numel() != ((H2 + 15) // 16) * ((H1 + 15) // 16) * 256:
+            raise ValueError("critic_pack: packed fc2 weights have the wrong size (see pack_linear)")
+        if b2 is not None and (not ok(b2) or not b2.is_contiguous() or b2.numel() != H2):
+            raise ValueError(f"critic_pack: b2 must hold {H2} float32 values")
+        cr = abi.Critic()
+        cr.h_state, cr.h_stride, cr.w1a_t, cr.w2, cr.w3 = h_state.data_ptr(), int(h_state.stride(0)), w1a_t.data_ptr(), w2.data_ptr(), w3.data_ptr()
+        cr.b2 = b2.data_ptr() if b2 is not None else None
+        cr.b3, cr.H1, cr.H2, cr.top_k, cr.tau = float(b3), H1, H2, 1, 1.0
+        ks = [int(k) for k in k_seq]
+        I = len(ks)
+        if not 1 <= I <= abi.DNS_MAX_ITERS or not all(0 <= k <= 255 for k in ks):
+            raise ValueError(f"k_seq: 1 to {abi.DNS_MAX_ITERS} values (one k per iteration)")
+        q = abi.Dns()
+        q.max_iters, q.n_samples = I, int(n_samples)
+        q.beta_init, q.c_beta, q.sigma, q.dyn_eps_min = float(beta_init), float(c_beta), float(sigma), float(dyn_eps_min)
+        for i, k in enumerate(ks):
+            q.k_seq[i] = k
+        if dyn_eps is not None:
+            if dyn_eps.dtype != torch.float64 or dyn_eps.device != self.device or not dyn_eps.is_contiguous() or int(dyn_eps.numel()) != self.N:
+                raise ValueError(f"dyn_eps must be a contiguous float64 [{self.N}] tensor on {self.device}: one gate value per env")
+            q.dyn_eps = dyn_eps.data_ptr()
+        if gate_out is None:
+            gate_out = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        S_ = max(q.n_samples, 0)
+        for name, t, dt, shape in (("gate_out", gate_out, torch.uint8, (n,)), ("trace_i", trace_i, torch.int32, (n, I, 4)),
+                                   ("trace_q", trace_q, torch.float32, (n, I, 2)), ("trace_beta", trace_beta, torch.float64, (n, I)),
+                                   ("q_out", q_out, torch.float32, (n, I, S_)), ("q0_out", q0_out, torch.float32, (n,))):
+            if t is not None:
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
+                setattr(q, name, t.data_ptr())
+        if vec_out is not None:
+            if not ok(vec_out) or vec_out.dim() != 2 or int(vec_out.shape[0]) != n or int(vec_out.shape[1]) < n_out or vec_out.stride(1) != 1 \
+                    or (n > 1 and vec_out.stride(0) < int(vec_out.shape[1])):
+                raise ValueError(f"vec_out must be a float32 [{n}, >= {n_out}] tensor on {self.device} with unit inner stride")
+            cr.vec_out, cr.vec_stride = vec_out.data_ptr(), int(vec_out.stride(0)) if n > 1 else int(vec_out.shape[1])
+        _lib.check(self.lib.cygym_dns_decode(self._h, C.byref(cr), C.byref(q), C.byref(src), C.byref(dst), self._stream()),
+                   self._h, "cygym_dns_decode")
+        return gate_out
+
     def can_step_actor(self, n_out: int) -> bool:
         """May a tick and the next actor run as ONE launch (cygym_step_actor)?  Where both kernels share their launch shape: 256
         devices, a fixed topology without detector buffers, a multiple of 16 envs and at most 16 envs per CU, 257..384 outputs."""

@@ -48,7 +48,8 @@ def _parse_resources(text: str) -> dict:
 INST = os.path.join(HERE, "csrc", "cg_inst.hip")
 INST_ACTOR = os.path.join(HERE, "csrc", "cg_inst_actor.hip")
 INST_COORD = os.path.join(HERE, "csrc", "cg_inst_coord.hip")
-INST_COMM = os.path.join(HERE, "csrc", "cg_inst_comm.hip")
+INST_DNS = os.path.join(HERE, "csrc", "cg_inst_dns.hip")
+INST_COMM =os.path.join(HERE, "csrc", "cg_inst_comm.hip")
 INST_HIER = os.path.join(HERE, "csrc", "cg_inst_hier.hip")
 INST_HMARL = os.path.join(HERE, "csrc", "cg_inst_hmarl.hip")
 INST_HMARL_TRAIN = os.path.join(HERE, "csrc", "cg_inst_hmarl_train.hip")
@@ -81,6 +82,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         if dev_mt is None or dev_mt == 256:   # the tick + actor kernels (256 devices only)
             units.append(("inst_actor", base + ["-c", INST_ACTOR, "-o", os.path.join(tmp, "inst_actor.o")]))
         units.append(("inst_coord", base + ["-c", INST_COORD, "-o", os.path.join(tmp, "inst_coord.o")]))   # the coordinate-ascent decode
+        units.append(("inst_dns", base + ["-c", INST_DNS, "-o", os.path.join(tmp, "inst_dns.o")]))   # the dynamic neighbourhood search
         units.append(("inst_comm", base + ["-c", INST_COMM, "-o", os.path.join(tmp, "inst_comm.o")]))   # the per-device actor-critic decode
         units.append(("inst_hier", base + ["-c", INST_HIER, "-o", os.path.join(tmp, "inst_hier.o")]))   # the hierarchical (HAGS) decode
         units.append(("inst_hmarl", base + ["-c", INST_HMARL, "-o", os.path.join(tmp, "inst_hmarl.o")]))   # the H-MARL decode

@@ -71,9 +71,8 @@ __device__ __forceinline__ double ca_k(double c) {
 //   u1 = (word 0 + 1) / 2^32, u2 = word 1 / 2^32, z = sqrt(-2 ln u1) cos(2 pi u2)   in f64.
 // Both transcendentals are evaluated from the integer words with the reduced-argument polynomials of fdlibm, so neither needs a
 // general argument reduction: z agrees with the f64 library value of the formula to a few 1e-16.
-__device__ __forceinline__ double ca_normal(uint32_t env, uint32_t tick, int d, int c, uint64_t seed) {
-  const cg_u32x4 w = cg_philox4x32_10(env, tick, CG_SITE_COORD_NOISE, ((uint32_t)d & 0xFFFFu) | ((uint32_t)c << 16), (uint32_t)seed,
-                                      (uint32_t)(seed >> 32));
+// (ca_normal_words: the mapping alone, from the four words of any site's draw -- cygym_dns_decode addresses CG_SITE_DNS_NOISE with it)
+__device__ __forceinline__ double ca_normal_words(const cg_u32x4 w) {
   // ln u1 = ln(n) - 32 ln 2, n = word 0 + 1 = 2^e m exactly, m in [sqrt(1/2), sqrt(2)): ln m = f - hfsq + s (hfsq + R(s^2)), f = m - 1, s = f / (2 + f)
   const double n = (double)w.v[0] + 1.0;
   int e = __builtin_amdgcn_frexp_exp(n);
@@ -97,6 +96,10 @@ __device__ __forceinline__ double ca_normal(uint32_t env, uint32_t tick, int d, 
                     z * (ca_k(-2.75573143513906633035e-07) + z * (ca_k(2.08757232129817482790e-09) + z * ca_k(-1.13596475577881948265e-11)))))));
   const double c2 = k == 0u ? cs : k == 1u ? -sn : k == 2u ? -cs : sn;
   return sqrt(-2.0 * ln_u1) * c2;
+}
+__device__ __forceinline__ double ca_normal(uint32_t env, uint32_t tick, int d, int c, uint64_t seed) {
+  return ca_normal_words(cg_philox4x32_10(env, tick, CG_SITE_COORD_NOISE, ((uint32_t)d & 0xFFFFu) | ((uint32_t)c << 16), (uint32_t)seed,
+                                          (uint32_t)(seed >> 32)));
 }
 __device__ __forceinline__ float ca_order_bits_float(uint32_t b) {   // the inverse of float_order_bits
   return __uint_as_float((b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b);

@@ -163,6 +163,7 @@ __device__ __forceinline__ int sample_head(const float* l, const int K, const ui
 
 #include "cg_actor_mlp.hpp"
 #include "cg_coord_ascent.hpp"
+#include "cg_dns.hpp"
 #include "cg_hier.hpp"
 #include "cg_hmarl.hpp"
 #include "cg_meta.hpp"

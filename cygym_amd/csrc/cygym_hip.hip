@@ -64,6 +64,12 @@ extern template __global__ void coord_ascent_kernel<false, true, true>(cygym_cri
 extern template __global__ void coord_ascent_kernel<true, true, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
 }  // namespace cygym_k
 
+// the dynamic neighbourhood search lives in its own unit (cg_inst_dns.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void dns_kernel<false>(cygym_critic, cygym_dns, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void dns_kernel<true>(cygym_critic, cygym_dns, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+}  // namespace cygym_k
+
 // the per-device actor-critic decode lives in its own unit (cg_inst_comm.hip): declared, not instantiated, here
 namespace cygym_k {
 extern template __global__ void comm_actor_kernel<false>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
@@ -270,6 +276,7 @@ int cygym_sizeof(int32_t which) {
     case 27: return (int)sizeof(cygym_ppo_finish_desc);   // (index 26 stays unassigned: earlier bindings probe it for -1)
     case 28: return (int)sizeof(cygym_cat_ppo_desc);
     case 29: return (int)sizeof(cygym_hmarl_train);
+    case 31: return (int)sizeof(cygym_dns);   // (index 30 stays unassigned)
     default: return -1;
   }
 }
@@ -865,6 +872,40 @@ int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygy
   const void* k = kernels[(c->top_k > 1 ? 1 : 0) | (c->noise_std > 0.0 ? 2 : 0) | (c->vec_out ? 4 : 0)];
   if (const int rc = raise_lds_once(h, k)) return rc;
   return launch_decode(h, k, dim3(src->n), dim3(CA_THREADS), lds, stream, {c, src, dst});   // one workgroup per row
+}
+
+int cygym_dns_decode(cygym_handle* h, const cygym_critic* c, const cygym_dns* q, const cygym_action_vectors* src, const cygym_actions* dst,
+                     void* stream) {
+  const char* const who = "cygym_dns_decode";
+  const char* const bad_layout = "cygym_dns_decode: bad layout (types, exploits >= 1, the handle's device count, h_stride >= H1, stride >= n_out)%s";
+  if (h && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_dns_decode: handle not bound (the draws are addressed by the envs' rng ticks)%s", "");
+  if (const int rc = check_vectors(h, src, dst, who, c && q && c->h_state && c->w1a_t && c->w2 && c->w3 && src && src->vec && q->gate_out, 1, bad_layout))
+    return rc;
+  const int n_out = src->n_types + src->n_devices + src->n_exploits + src->n_apps;
+  if (c->h_stride < c->H1 || src->stride < n_out) return fail(h, CYGYM_EINVAL, bad_layout, "");
+  auto finite = [](double x) { return x == x && x < 1e300 && x > -1e300; };
+  if (!finite(q->beta_init) || !finite(q->c_beta) || !finite(q->sigma) || !finite(q->dyn_eps_min) || q->beta_init < 0.0)
+    return fail(h, CYGYM_EINVAL, "cygym_dns_decode: beta_init must be >= 0, and beta_init, c_beta, sigma, dyn_eps_min finite%s", "");
+  if (c->vec_out && c->vec_stride < n_out)
+    return fail(h, CYGYM_EINVAL, "cygym_dns_decode: vec_stride is smaller than n_out = n_types + n_devices + n_exploits + n_apps%s", "");
+  if (c->H1 < 16 || c->H1 > DN_MAX_H || (c->H1 & 15) || c->H2 < 16 || c->H2 > DN_MAX_H || (c->H2 & 15))
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_dns_decode: critic widths H1, H2 must be multiples of 16 in 16 .. 128%s", "");
+  if (src->n_devices > DN_MAX_M || src->n_types > DN_MAX_TYPES || src->n_exploits > CG_MAX_EXPLOITS || src->n_apps > DN_MAX_APPS)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_dns_decode: at most 256 devices, 32 action types, CG_MAX_EXPLOITS exploits, 32 apps%s", "");
+  if (q->n_samples < 1 || q->n_samples > DN_MAX_SAMPLES || q->max_iters < 1 || q->max_iters > CG_DNS_MAX_ITERS || !(q->sigma > 0.0) || q->sigma > 0.125)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_dns_decode: n_samples in 1 .. 80, max_iters in 1 .. 16, 0 < sigma <= 0.125%s", "");
+  for (int i = 0; i < q->max_iters; ++i)
+    if (q->k_seq[i] < 1 || q->k_seq[i] > DN_MAX_K) return fail(h, CYGYM_EUNSUPPORTED, "cygym_dns_decode: every k of k_seq must lie in 1 .. 8%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const DnsPlan pl = dn_plan(c->H1, c->H2, src->n_devices, q->n_samples);
+  const size_t lds = (size_t)pl.total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_dns_decode: the critic and the neighbours do not fit in LDS%s", "");
+  const bool trace = q->trace_i || q->trace_q || q->trace_beta || q->q_out || q->q0_out;
+  const void* k = trace ? (const void*)dns_kernel<true> : (const void*)dns_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  return launch_decode(h, k, dim3(src->n), dim3(DN_THREADS), lds, stream, {c, q, src, dst});   // one workgroup per row
 }
 
 int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst,

@@ -48,6 +48,7 @@ class Transitions:
                                # -- where the reference pushes the terminal state's view; `done` masks the bootstrap term either way
     done: torch.Tensor         # [T, N] bool
     noise_std: float           # where the exploration schedule ended
+    gate: torch.Tensor | None = None   # [T, N] uint8 with a policies.DynamicSearchPolicy decoder: 1 = the search decided the row (:1382)
 
 
 @torch.no_grad()
@@ -62,7 +63,11 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
     decoder: a policies.CoordAscentPolicy -- the reference's `Cord_asc` mode: on the learner's turn decoder.write(batch, act, rows,
     state, vec_out=...) decodes through the critic (with the policy's training-mode noise) and `action_vec` records the encoded
     action; `actor` may be None and is not evaluated; n_types / n_exploits / n_apps (and type_map, when given) must be the decoder's own
-    (ValueError otherwise).
+    (ValueError otherwise).  decoder: a policies.DynamicSearchPolicy -- the reference's `--dynamic_search` flag (:1381-1399): raw = actor(state)
+    (`actor`, or the policy's own when None); vec = clip(raw + noise) still advances the sigma schedule; the action comes from RAW --
+    behind the per-env gate the neighbourhood search, otherwise the policy's fallback decode --; `action_vec` records vec with the
+    plain fallback (`ddpg` mode, :1422) and encode_action of the action with a CoordAscentPolicy fallback (`Cord_asc` mode, :1424);
+    Transitions.gate records which rows the search decided.  The gate values live in the policy and carry over between calls.
     observer: an object with observe(batch, state) (meta_rollout.MetaController: the reference's meta_controller in observer mode,
     :1342-1361), called on the learner's turn BEFORE the decode and the step, so that it sees the flags of the state the decision is
     made on.  It writes no action and draws nothing: the transitions are the same with and without it."""
@@ -87,6 +92,9 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
     mode_word = {HL.DEFENDER: torch.full((N,), S.MODE_DEFENDER, dtype=torch.int32, device=dev),
                  HL.ATTACKER: torch.full((N,), S.MODE_ATTACKER, dtype=torch.int32, device=dev)}
     rec = {k: [] for k in ("state", "action_vec", "reward", "raw_reward", "next_state", "done")}
+    dns = decoder is not None and hasattr(decoder, "search_params")      # a policies.DynamicSearchPolicy
+    if dns:
+        rec["gate"] = []
     batch.prime_view(role)
     state = batch.role_obs[role].clone()
     t, sigma = int(t0), float(noise_std)
@@ -101,7 +109,21 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
         if turn == role:
             if observer is not None:
                 observer.observe(batch, state)
-            if decoder is not None:      # Cord_asc: the decode through the critic writes the action and its encoding; `raw + noise` is never read
+            if dns:                      # --dynamic_search (:1381-1399): the action comes from raw, the schedule and the replay keep vec
+                raw_vec = (actor if actor is not None else decoder.actor)(state).float()
+                vec = raw_vec
+                if sigma > 0.0:
+                    vec = vec + torch.randn(vec.shape, generator=generator, device=dev, dtype=torch.float32) * sigma
+                if clip is not None:
+                    vec = vec.clamp(clip[0], clip[1])
+                vec = vec.contiguous()
+                if decoder.fallback is None:      # `ddpg` mode: the replay stores vec (:1422)
+                    decoder.write(batch, act, rows_all, state, raw=raw_vec)
+                else:                             # `Cord_asc` mode: encode_action of the action that is stepped (:1424)
+                    vec = torch.empty((N, n_out), dtype=torch.float32, device=dev)
+                    decoder.write(batch, act, rows_all, state, raw=raw_vec, vec_out=vec)
+                rec["gate"].append(decoder.last_gate)
+            elif decoder is not None:    # Cord_asc: the decode through the critic writes the action and its encoding; `raw + noise` is never read
                 vec = torch.empty((N, n_out), dtype=torch.float32, device=dev)
                 decoder.write(batch, act, rows_all, state, vec_out=vec)
             else:
@@ -299,10 +321,12 @@ def best_response(batch, role: str, agent: DDPGAgent, opponent, n_decisions: int
     turn it selects devices for the state the decision is made on (collect's `observer`), after the step it stores (state, selection,
     raw reward) (meta.store), and it runs one train_controller when meta_rollout.trains_at(t, meta_period) holds for the learner's
     tick t ((t + 1) % 10 == 0 as shipped: never for a defender, whose ticks are even).  It changes neither the actions nor the agent.
-    Out of scope: dynamic_neighbor_search, exploit_override, the time budget, and leaving the loop at the first done (a batch goes
+    decoder: a policies.DynamicSearchPolicy over agent.actor and agent.critic -- the loop with `--dynamic_search` (:1381-1399): its gate starts
+    at dyn_eps0 when the policy is made (reset_gate() starts a new run) and halves at every use, per env.
+    Out of scope: exploit_override, the time budget, and leaving the loop at the first done (a batch goes
     on, as collect does)."""
     if decoder is not None and decoder.critic is not agent.critic:
-        raise ValueError("decoder: a CoordAscentPolicy over agent.critic (the critic the updates train)")
+        raise ValueError("decoder: a CoordAscentPolicy or DynamicSearchPolicy over agent.critic (the critic the updates train)")
     n_decisions = int(n_decisions)
     decay_rate = (sigma_min / noise_std) ** (1.0 / n_decisions) if noise_std > 0.0 and n_decisions > 0 else 1.0
     total = torch.zeros((batch.N,), dtype=torch.float64, device=batch.device)

@@ -12,6 +12,11 @@ decode_action does not read the actor at all but scores one-device candidate act
 (`DoubleOracle.greedy_device_coord_ascent`, do_agent.py:2137-2219); the batch does that in one launch
 (cygym_coord_ascent_decode).  `reference_critic` builds the reference's critic (do_agent.py:373-388).
 
+`DynamicSearchPolicy` is either of the two run with the reference's `--dynamic_search` flag: behind a per-env gate that halves at
+every use the decision is `DoubleOracle.dynamic_neighborhood_search` (do_agent.py:1204-1250), a simulated-annealing local search
+around the decoded actor output scored by the critic; the batch does it in one launch (cygym_dns_decode) that overwrites the gated
+rows after the fallback decode.  `dns_search` is the float64 restatement the fixtures and the kernel are checked against.
+
 `CommActorCritic` / `CommActorPolicy` are the third family: the per-device actor-critic of the reference's IPPO / MAPPO agents
 (IPPO.py:135-196 with USE_GAT off, as shipped) and its greedy executor (IPPOCommPolicy.select_action, IPPO.py:237-284), which
 answers with GROUPS of devices per action type; the batch evaluates the network, samples and groups in one launch
@@ -555,6 +560,259 @@ class CoordAscentPolicy:
         tm = self._map(obs.device)
         at = at.to(torch.int32) if tm is None else tm[at]
         return {"atype": at, "exploit": ex.to(torch.int32), "dev_mask": on, "app": torch.zeros_like(at)}
+
+
+DNS_TRAINING = dict(k_init=5, beta_init=1.0, c_k=1.0, c_beta=0.1, dyn_eps0=0.9, dyn_eps_min=0.001)    # do_agent.py:1388-1391
+DNS_EVALUATION = dict(k_init=3, beta_init=0.05, c_k=1.0, c_beta=0.2, dyn_eps0=0.99, dyn_eps_min=0.0)   # utils.py:1158-1165 (the defaults of :1208-1211)
+DNS_IMPROVE, DNS_ACCEPT, DNS_CHOICE, DNS_CHOICE_STAY = 0, 1, 2, 3      # the branch of step 5 an iteration took (trace)
+
+
+def dns_k_sequence(k_init: int, c_k: float, max_iters: int):
+    """k of iteration 1 .. max_iters of dynamic_neighborhood_search: k_init, then k = max(1, ceil(k - c_k)) (do_agent.py:1249)."""
+    import math
+    ks, k = [], int(k_init)
+    for _ in range(int(max_iters)):
+        ks.append(k)
+        k = max(1, int(math.ceil(k - c_k)))
+    return ks
+
+
+def dns_search(fc1, fc2, fc3, states, raw, T: int, E: int, A: int, *, seed: int, env_ids, ticks, k_init: int, beta_init: float, c_k: float,
+               c_beta: float, max_iters: int = 10, n_samples: int = 75, sigma: float = 0.1, epsilon: float = 0.0, dyn_eps=None,
+               dyn_eps_min: float = 0.0, keep_scored: bool = False, **_unused):
+    """DoubleOracle.dynamic_neighborhood_search (do_agent.py:1204-1250) behind its gate (:1382-1399) for every row, restated on the
+    CPU with numpy in float64 from the addressed draws of rng.py -- what the fixtures recorded from the reference
+    (tools/make_dns_golden.py) and cygym_dns_decode are checked against; include/cygym_abi.h states the procedure in full.
+      fc1, fc2, fc3   the critic's layers (float32 parameters, evaluated in float64)
+      states [n, W], raw [n, n_out] float32 (the actor's output, NOT the noisy vec), env_ids [n] GLOBAL env ids, ticks [n]
+      dyn_eps         None: every row is searched; else [n] float64, the rows' gate values (one per row, in row order)
+    Sets are read in first-insertion order.  Returns a dict of numpy arrays:
+      gate [n] bool, dyn_eps [n] f64 (after the gate)
+      atype [n] (the type INDEX), exploit [n], app [n], dev_mask [n, D] bool      a_best; -1 / False on rows the gate left out
+      eps_random [n, 1 + max_iters * n_samples] bool                             the epsilon coins that fell (column 0: plain(raw))
+      n_unique, best_s, branch, choice [n, I] int32; best_q, q_bar [n, I] f64; beta [n, I] f64      the per-iteration trace
+      q [n, I, n_samples] f64         Q of every sample (a duplicate's slot: the Q of its first occurrence)
+      q0 [n] f64                      Q of plain(raw)
+      margin [n] f64                  the smallest distance of any decision of the row from flipping, in units of Q (the acceptance
+                                      test also in units of probability): adjacent gaps of the sorted first k + 1, |Q1 - Q_bar| and
+                                      |Q1 - Q(a_best)| where the two are different tuples (equal tuples have equal Q), |prob - u|
+                                      and |(Q_bar - Q1) + beta ln u|
+      scored (keep_scored)            per row the list of every tuple the search scored: (type, mask [D] bool, exploit, app, Q)"""
+    import math
+    import numpy as np
+    from . import rng as R
+    from . import spec as S
+    st = np.asarray(states.detach().cpu() if torch.is_tensor(states) else states, np.float64)
+    rw = np.asarray(raw.detach().cpu() if torch.is_tensor(raw) else raw, np.float32)
+    n, W = st.shape
+    D = rw.shape[1] - (T + E + A)
+    n_out, I, NS = T + D + E + A, int(max_iters), int(n_samples)
+    w1 = fc1.weight.detach().double().cpu().numpy()
+    hs_all = st @ w1[:, :W].T + fc1.bias.detach().double().cpu().numpy()
+    wa = np.ascontiguousarray(w1[:, W:].T)                       # [n_out, H1]
+    w2t, b2 = fc2.weight.detach().double().cpu().numpy().T, fc2.bias.detach().double().cpu().numpy()
+    w3, b3 = fc3.weight.detach().double().cpu().numpy().reshape(-1), float(fc3.bias.detach().double().cpu().reshape(-1)[0])
+    thr = R.bernoulli_threshold(float(epsilon))
+    ks = dns_k_sequence(k_init, c_k, I)
+    out = dict(gate=np.ones(n, bool), dyn_eps=np.zeros(n) if dyn_eps is None else np.array(dyn_eps, np.float64),
+               atype=np.full(n, -1, np.int32), exploit=np.full(n, -1, np.int32), app=np.full(n, -1, np.int32), dev_mask=np.zeros((n, D), bool),
+               eps_random=np.zeros((n, 1 + I * NS), bool), n_unique=np.zeros((n, I), np.int32), best_s=np.zeros((n, I), np.int32),
+               branch=np.zeros((n, I), np.int32), choice=np.full((n, I), -1, np.int32), best_q=np.zeros((n, I)), q_bar=np.zeros((n, I)),
+               beta=np.zeros((n, I)), q=np.zeros((n, I, NS)), q0=np.zeros(n), margin=np.full(n, np.inf))
+    for i in range(n):
+        env, tick = int(env_ids[i]), int(ticks[i])
+        if dyn_eps is not None:
+            u = R.draw(seed, env, tick, S.SITE_DNS_GATE) / 4294967296.0
+            out["gate"][i] = u < out["dyn_eps"][i]
+            if not out["gate"][i]:
+                continue
+            out["dyn_eps"][i] = max(out["dyn_eps"][i] / 2, float(dyn_eps_min))
+        hs = hs_all[i]
+
+        key = lambda c: (c[0], c[1].tobytes(), c[2], c[3])      # noqa: E731
+        q_known = {}
+
+        def q_of(cands):      # one value per TUPLE, whatever batch it is asked in: the critic is deterministic (equal tuples compare equal)
+            new = [c for c in cands if key(c) not in q_known]
+            if new:
+                pre = np.stack([hs + wa[t] + wa[T + D + x] + (wa[T + D + E + a] if A > 0 else 0.0) + m.astype(np.float64) @ wa[T:T + D] for t, m, x, a in new])
+                h2 = np.maximum(np.maximum(pre, 0.0) @ w2t + b2, 0.0)
+                for c, qv in zip(new, np.nan_to_num(h2 @ w3 + b3, nan=-1e9, posinf=1e9, neginf=-1e9)):
+                    q_known[key(c)] = float(qv)
+            return np.array([q_known[key(c)] for c in cands])
+
+        # a_bar = plain(raw): the epsilon-greedy type at CG_SITE_EPS_TYPE, as cygym_decode_actions draws it
+        t0 = int(np.argmax(rw[i, :T]))
+        if thr:
+            w = R.philox4x32_10(env, tick, S.SITE_EPS_TYPE, 0, seed & R.MASK, (seed >> 32) & R.MASK)
+            if w[0] < thr:
+                t0, out["eps_random"][i, 0] = R.index(w[1], T), True
+        bar = (t0, rw[i, T:T + D] > 0, int(np.argmax(rw[i, T + D:T + D + E])), int(np.argmax(rw[i, T + D + E:])) if A > 0 else 0)
+        q_bar = float(q_of([bar])[0])
+        out["q0"][i] = q_bar
+        best, q_best, beta, margin = bar, q_bar, float(beta_init), np.inf
+        k_all, k_q = [], {}
+        for it in range(1, I + 1):
+            b = (it - 1) * NS + np.arange(NS)
+            base = np.zeros(n_out)
+            base[bar[0]] = 1.0
+            base[T:T + D] = bar[1]
+            base[T + D + bar[2]] = 1.0
+            if A > 0:
+                base[T + D + E + bar[3]] = 1.0
+            w0, w1_, _, _ = R.draw_words_np(seed, env, tick, S.SITE_DNS_NOISE, np.arange(n_out)[None, :], b[:, None])
+            v = np.clip(base[None, :] + float(sigma) * R.normal_from_words(w0, w1_), -1.0, 1.0)
+            pos = R.normal_positive_from_words(w0, w1_)                                # z > 0 from the integer words
+            on = bar[1][None, :] | pos[:, T:T + D]
+            ty = np.argmax(v[:, :T], axis=1)
+            if thr:
+                e0, e1, _, _ = R.draw_words_np(seed, env, tick, S.SITE_DNS_EPS, 0, b)
+                coin = e0 < np.uint64(thr)
+                ty = np.where(coin, (e1 * np.uint64(T)) >> np.uint64(32), ty).astype(np.int64)
+                out["eps_random"][i, 1 + b] = coin
+            ex = np.argmax(v[:, T + D:T + D + E], axis=1)
+            ap = np.argmax(v[:, T + D + E:], axis=1) if A > 0 else np.zeros(NS, np.int64)
+            cands, first_s, seen, slot = [], [], {}, np.zeros(NS, np.int64)      # `seen` in first-insertion order
+            for s in range(NS):
+                c = (int(ty[s]), on[s].copy(), int(ex[s]), int(ap[s]))
+                if key(c) not in seen:
+                    seen[key(c)] = len(cands)
+                    cands.append(c)
+                    first_s.append(s)
+                slot[s] = seen[key(c)]
+            q = q_of(cands)
+            out["q"][i, it - 1] = q[slot]
+            order = np.argsort(-q, kind="stable")
+            k = ks[it - 1]
+            for u_ in order[:k]:
+                if key(cands[u_]) not in k_q:
+                    k_q[key(cands[u_])] = float(q[u_])
+                    k_all.append(cands[u_])
+            srt = q[order[:k + 1]]
+            if len(srt) > 1:
+                margin = min(margin, float((srt[:-1] - srt[1:]).min()))
+            q1, a1 = float(q[order[0]]), cands[order[0]]
+            if key(a1) != key(bar):          # (the same tuple has the same Q: no decision to flip)
+                margin = min(margin, abs(q1 - q_bar))
+            choice = -1
+            if q1 > q_bar:
+                branch = DNS_IMPROVE
+                bar, q_bar = a1, q1
+                if key(a1) != key(best):
+                    margin = min(margin, abs(q1 - q_best))
+                if q1 > q_best:
+                    best, q_best = a1, q1
+            else:
+                prob = math.exp(-(q_bar - q1) / beta) if beta > 0 else 0.0
+                u = R.draw(seed, env, tick, S.SITE_DNS_ACCEPT, 0, it) / 4294967296.0
+                if beta > 0:
+                    margin = min(margin, abs(prob - u), abs((q_bar - q1) + beta * math.log(u)) if u > 0 else np.inf)
+                if u < prob:
+                    branch = DNS_ACCEPT
+                    bar, q_bar = a1, q1
+                    beta = max(0.0, beta - float(c_beta))
+                else:
+                    choice = R.index(R.draw(seed, env, tick, S.SITE_DNS_CHOICE, 0, it), len(k_all))
+                    branch = DNS_CHOICE_STAY if key(k_all[choice]) == key(bar) else DNS_CHOICE
+                    bar = k_all[choice]
+                    q_bar = k_q[key(bar)]
+            o = out
+            o["n_unique"][i, it - 1], o["best_s"][i, it - 1], o["best_q"][i, it - 1] = len(cands), first_s[int(order[0])], q1
+            o["branch"][i, it - 1], o["choice"][i, it - 1], o["q_bar"][i, it - 1], o["beta"][i, it - 1] = branch, choice, q_bar, beta
+        out["atype"][i], out["exploit"][i], out["app"][i], out["dev_mask"][i], out["margin"][i] = best[0], best[2], best[3], best[1], margin
+        if keep_scored:
+            out.setdefault("scored", [[] for _ in range(n)])[i] = [(t, np.frombuffer(m, bool).copy(), x, a, qv) for (t, m, x, a), qv in q_known.items()]
+    return out
+
+
+class DynamicSearchPolicy:
+    """A DDPG / `Cord_asc` strategy run with the reference's `--dynamic_search` flag (volt_typhoon_do.py:1235): behind a per-env gate
+    that halves at every use (dyn_eps, do_agent.py:1382-1391; utils.py:1158-1165) the decision is
+    DoubleOracle.dynamic_neighborhood_search (do_agent.py:1204-1250) -- a local search around plain(actor(state)) with
+    simulated-annealing moves, scored by the critic --, otherwise the fallback decode_action: the plain decode of the actor's
+    output (fallback=None, `ddpg` mode) or a CoordAscentPolicy over the same critic (`Cord_asc` mode).  include/cygym_abi.h
+    (cygym_dns_decode) states the search in full; dns_search is its float64 restatement.
+    write() is the actor forward, one addmm (the state part of fc1), the fallback decode of ALL rows and the search launch, which
+    overwrites the rows whose gate fell; nothing synchronises with the host.  The gate values live on the batch's device, one per
+    env ([batch.N] float64, made at the first write); reset_gate() refills them with dyn_eps0 -- the reference starts a new
+    dyn_eps per training run (:1322) and uses a constant per evaluation episode (utils.py:1158: call reset_gate() per episode, or
+    pass dyn_eps_min = dyn_eps0 for a gate that never decays).  Not tick_free: the gate state changes between decisions, so a
+    captured loop would have to own it; simulate_grid runs such a strategy eagerly.
+    DynamicSearchPolicy.training(...) / .evaluation(...) fill in the reference's two parameter sets (DNS_TRAINING, DNS_EVALUATION)."""
+
+    tick_free = False
+
+    def __init__(self, actor, critic, n_types: int, n_exploits: int, n_apps: int, *, fallback=None, k_init: int, beta_init: float, c_k: float,
+                 c_beta: float, max_iters: int = 10, n_samples: int = 75, sigma: float = 0.1, epsilon: float = 0.05, dyn_eps0: float,
+                 dyn_eps_min: float, type_map=None):
+        self._ca = CoordAscentPolicy(critic, n_types, n_exploits, n_apps, type_map=type_map, top_k=1)     # the critic's checks and its pack
+        if fallback is not None and not (isinstance(fallback, CoordAscentPolicy) and fallback.critic is critic
+                                         and (fallback.n_types, fallback.n_exploits, fallback.n_apps) == (int(n_types), int(n_exploits), int(n_apps))):
+            raise ValueError("fallback: None (the plain decode) or a CoordAscentPolicy over the same critic and layout")
+        self.actor, self.critic, self.fallback = actor, critic, fallback
+        self.n_types, self.n_exploits, self.n_apps = int(n_types), int(n_exploits), int(n_apps)
+        self.k_init, self.beta_init, self.c_k, self.c_beta = int(k_init), float(beta_init), float(c_k), float(c_beta)
+        self.max_iters, self.n_samples, self.sigma, self.epsilon = int(max_iters), int(n_samples), float(sigma), float(epsilon)
+        self.dyn_eps0, self.dyn_eps_min = float(dyn_eps0), float(dyn_eps_min)
+        self.k_seq = dns_k_sequence(self.k_init, self.c_k, self.max_iters)
+        if not (1 <= self.max_iters <= 16 and 1 <= self.n_samples <= 80 and 0.0 < self.sigma <= 0.125 and self.beta_init >= 0.0
+                and all(1 <= k <= 8 for k in self.k_seq) and 0.0 <= self.epsilon <= 1.0):
+            raise ValueError("max_iters in 1..16, n_samples in 1..80, 0 < sigma <= 0.125, beta_init >= 0, every k in 1..8, epsilon in [0, 1]")
+        self.type_map = self._ca.type_map
+        self.action_types = self._ca.action_types
+        self.dyn_eps = None
+        self.last_gate = None       # uint8 [n] of the last write: 1 = the search decided the row
+
+    @classmethod
+    def training(cls, actor, critic, n_types, n_exploits, n_apps, **kw):
+        """The parameters of the training loop (do_agent.py:1383-1391): k_init 5, beta 1.0, c_k 1.0, c_beta 0.1, gate 0.9 -> 0.001."""
+        return cls(actor, critic, n_types, n_exploits, n_apps, **{**DNS_TRAINING, **kw})
+
+    @classmethod
+    def evaluation(cls, actor, critic, n_types, n_exploits, n_apps, **kw):
+        """The parameters of evaluation (utils.py:1158-1165): k_init 3, beta 0.05, c_k 1.0, c_beta 0.2, gate 0.99, no floor."""
+        return cls(actor, critic, n_types, n_exploits, n_apps, **{**DNS_EVALUATION, **kw})
+
+    _map = ActorPolicy._map
+
+    def n_out(self, M):
+        return self.n_types + M + self.n_exploits + self.n_apps
+
+    def search_params(self) -> dict:
+        """The keyword arguments of dns_search / batch.dns_decode that describe the search."""
+        return dict(k_init=self.k_init, beta_init=self.beta_init, c_k=self.c_k, c_beta=self.c_beta, max_iters=self.max_iters,
+                    n_samples=self.n_samples, sigma=self.sigma, epsilon=self.epsilon, dyn_eps_min=self.dyn_eps_min)
+
+    def reset_gate(self):
+        """dyn_eps = dyn_eps0 in every env (a new training run; a new evaluation episode).  Returns self."""
+        if self.dyn_eps is not None:
+            self.dyn_eps.fill_(self.dyn_eps0)
+        return self
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, vec_out=None, raw=None, trace=None):
+        """raw = actor(obs) (or the caller's `raw`), h_state = one addmm, the fallback decode of all rows, the search launch.
+        vec_out [n, >= n_out] float32: encode_action of the action of every row the search decided, and -- with a CoordAscentPolicy
+        fallback -- of the others too (the plain fallback writes none: in `ddpg` mode the replay stores the noisy vec).
+        trace: dict of optional output tensors of batch.dns_decode (trace_i, trace_q, trace_beta, q_out)."""
+        if self.dyn_eps is None or self.dyn_eps.device != batch.device or int(self.dyn_eps.numel()) != batch.N:
+            self.dyn_eps = torch.full((batch.N,), self.dyn_eps0, dtype=torch.float64, device=batch.device)
+        w1s_t, b1, pack = self._ca._packed(batch, batch.M)
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != int(w1s_t.shape[0]):
+            raise ValueError(f"obs must be a float32 [n, {int(w1s_t.shape[0])}] role view")
+        if raw is None:
+            raw = self.actor(obs)
+        raw = raw.float().contiguous()
+        h_state = torch.addmm(b1, obs, w1s_t)
+        tm = self._map(obs.device)
+        if self.fallback is None:
+            batch.decode_actions(rows, raw, self.n_types, self.n_exploits, self.n_apps, tm, act, epsilon=self.epsilon)
+        else:
+            self.fallback.write(batch, act, rows, obs, vec_out=vec_out)
+        self.last_gate = torch.empty((int(raw.shape[0]),), dtype=torch.uint8, device=batch.device)
+        batch.dns_decode(rows, raw, h_state, pack, self.n_types, self.n_exploits, self.n_apps, tm, act, k_seq=self.k_seq,
+                         beta_init=self.beta_init, c_beta=self.c_beta, n_samples=self.n_samples, sigma=self.sigma, epsilon=self.epsilon,
+                         dyn_eps=self.dyn_eps, dyn_eps_min=self.dyn_eps_min, gate_out=self.last_gate, vec_out=vec_out, **(trace or {}))
 
 
 class _CriticTail(torch.autograd.Function):

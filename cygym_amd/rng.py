@@ -74,6 +74,13 @@ def normal_from_words(w0, w1) -> np.ndarray:
     return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
 
 
+def normal_positive_from_words(w0, w1) -> np.ndarray:
+    """normal_from_words(w0, w1) > 0, decided from the integer words without a transcendental (include/cygym_spec.h,
+    CG_SITE_DNS_NOISE): u1 != 1 and cos(2 pi u2) > 0, i.e. word 0 != 2^32 - 1 and word 1 outside [2^30, 3 * 2^30]."""
+    w0, w1 = np.asarray(w0, dtype=np.uint64), np.asarray(w1, dtype=np.uint64)
+    return (w0 != np.uint64(0xFFFFFFFF)) & ((w1 < np.uint64(1 << 30)) | (w1 > np.uint64(3 << 30)))
+
+
 def normal_np(seed: int, env, tick, site, a=0, b=0) -> np.ndarray:
     """Standard normal (float64) addressed (env, tick, site, a, b), vectorised over a / b: the contract's mapping of
     np.random.randn -- addressed like every other draw, never sequenced."""

@@ -60,6 +60,11 @@ SITE_HMARL_SKILL = 74
 SITE_HMARL_TYPE = 75
 SITE_HMARL_SHUFFLE = 76
 SITE_HMARL_TYPE_SAMPLE = 77
+SITE_DNS_GATE = 78
+SITE_DNS_NOISE = 79
+SITE_DNS_EPS = 80
+SITE_DNS_ACCEPT = 81
+SITE_DNS_CHOICE = 82
 
 POISSON_TABLE = 16
 TRI_TABLE = 8

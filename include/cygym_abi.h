@@ -475,6 +475,82 @@ typedef struct cygym_critic {
 int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* layout,
                               const cygym_actions* dst, void* stream);
 
+/* The search of cygym_dns_decode: its parameters, the per-env gate and the optional trace.  DEVICE pointers. */
+#define CG_DNS_MAX_ITERS 16
+typedef struct cygym_dns {
+  double*  dyn_eps;        /* optional [n_envs], one per ENV (indexed like the rows of the action tensors): the gate value, read and --
+                              where the gate falls -- replaced by max(dyn_eps / 2, dyn_eps_min).  NULL: every row is searched         */
+  uint8_t* gate_out;       /* [n] per source row: 1 = the search decided the row, 0 = the gate left it alone (nothing else is written) */
+  int32_t* trace_i;        /* optional [n][max_iters][4] per iteration: unique neighbours, the best neighbour's first sample s, the branch
+                              of step 5 (0 improve / 1 accept / 2 choice / 3 choice that lands on a_bar itself), the index
+                              random.choice took (-1: none)                                                                          */
+  float*   trace_q;        /* optional [n][max_iters][2]: Q1 (the best neighbour's Q) and Q_bar after the step                         */
+  double*  trace_beta;     /* optional [n][max_iters]: beta after the step                                                             */
+  float*   q_out;          /* optional [n][max_iters][n_samples]: Q of every sample's tuple (a duplicate's slot holds the Q of its first
+                              occurrence: the same number)                                                                           */
+  float*   q0_out;         /* optional [n]: Q of plain(raw), the search's starting point                                               */
+  double   dyn_eps_min;    /* the gate's floor: 0.001 in training (do_agent.py:1391), 0 in evaluation (utils.py:1158-1165)             */
+  double   beta_init;      /* >= 0 */
+  double   c_beta;
+  double   sigma;          /* generate_neighbors' sigma (do_agent.py:1168: 0.1), 0 < sigma <= 0.125                                    */
+  int32_t  max_iters;      /* 1 .. CG_DNS_MAX_ITERS (:1212: 10)                                                                        */
+  int32_t  n_samples;      /* 1 .. 80 (:1168: 75)                                                                                      */
+  uint8_t  k_seq[CG_DNS_MAX_ITERS];   /* k of iteration 1 .. max_iters, each 1 .. 8: k_init, then max(1, ceil(k - c_k)) (:1249), formed by
+                              the host so that c_k needs no device arithmetic                                                        */
+} cygym_dns;
+
+/* Replaces: DoubleOracle.dynamic_neighborhood_search (do_agent.py:1204-1250) with generate_neighbors (:1168-1187) and _Q_of (:1189-1202)
+ * behind the gate of `--dynamic_search` (do_agent.py:1382-1391 in training, utils.py:1158-1165 in evaluation) -- a local search around the
+ * decoded actor output with simulated-annealing moves, scored by the critic, up to 751 critic forwards per decision in the reference --
+ * for a batch, in ONE launch, fused with the scatter into the action tensors.  T = n_types, D = n_devices, E = n_exploits, A = n_apps,
+ * n_out = T + D + E + A; enc(t, mask, x, a) is encode_action's vector (:910-933; the exploit index is < E, so no field swap fires): ones
+ * at t, at T + d for every d of the mask, at T + D + x and, when A > 0, at T + D + E + a (the reference raises for A = 0; here: no app
+ * term, app 0, as in cygym_coord_ascent_decode).  plain(v) is the plain branch of decode_action (:970-998; inside the search it is always
+ * called without state_tensor): type = first argmax of v[:T], or a uniform type with probability epsilon; devices = the ascending ids
+ * with v > 0; exploit, app = first argmax.
+ * Gate: u = word 0 / 2^32 of the draw (global env id, the env's current rng tick, CG_SITE_DNS_GATE); the row is searched iff
+ * u < dyn_eps[env] (f64: both sides exact), and then dyn_eps[env] = max(dyn_eps[env] / 2, dyn_eps_min).  A row the gate leaves alone
+ * writes gate_out = 0 and nothing else: run the fallback decode (cygym_decode_actions of `raw`, or cygym_coord_ascent_decode) on all rows
+ * FIRST, this call overwrites the searched ones.  `rows` must not name an env twice.
+ * Per searched row, `raw` = the row of layout->vec (the actor's output, not the noisy vec):
+ *  1. a_bar = a_best = plain(raw), its epsilon draw at CG_SITE_EPS_TYPE exactly as cygym_decode_actions draws it; Q_bar = Q(a_bar);
+ *     beta = beta_init; K_all = {}.
+ *  2. for itr = 1 .. max_iters (the reference's k never reaches 0, so its loop always runs max_iters times), k = k_seq[itr - 1]:
+ *  3. neighbours: for s = 0 .. n_samples - 1, with z(j) the normal addressed (CG_SITE_DNS_NOISE, a = j, b = (itr - 1) n_samples + s),
+ *     v_j = min(max(enc(a_bar)_j + sigma z(j), -1), 1) in f64 and the neighbour is plain(v) with the epsilon coin and type of
+ *     (CG_SITE_DNS_EPS, a = 0, same b).  Device bits only grow: a bit of a_bar stays on (1 + sigma z > 0 for every z the mapping can
+ *     produce, |z| <= sqrt(64 ln 2) = 6.66, at sigma <= 0.125), an off bit turns on iff z > 0 -- decided from the draw's words
+ *     (cygym_spec.h), no transcendental; only the T + E + A other components evaluate the f64 normal.  Duplicates are dropped: the
+ *     unique neighbours in ascending s of their first occurrence (`seen` read in first-insertion order -- Python's set order is hash
+ *     order; the recording tool pins the reference to this reading).  After a few moves nearly every device is on and the
+ *     n_samples neighbours collapse to a handful of distinct tuples: the dedup decides what the top k and K_all hold.
+ *  4. every unique neighbour is scored: Q in fp32, layer 1 = (((h_state + sum of the mask's device columns in ASCENDING device id)
+ *     + type column) + exploit column) + app column -- one fixed order per tuple, so that equal tuples score bit-equal in every
+ *     iteration, as the reference's deterministic critic does --, fc2 on the matrix cores with fp32 inputs and accumulators, relu,
+ *     the fc3 dot, + b3; then nan_to_num (NaN -> -1e9, +-inf -> +-1e9: the reference has none here; non-finite Q is not pinned).
+ *     Stable descending sort (equal Q keeps the first-occurrence order); the first min(k, unique) join K_all in that order,
+ *     duplicates dropped (first-insertion order again), each with its Q.
+ *  5. (Q1, a1) the best neighbour.  Q1 > Q_bar: a_bar, Q_bar = a1, Q1, and if Q1 > Q(a_best): a_best = a1.  Otherwise
+ *     prob = exp(-(Q_bar - Q1) / beta) in f64 (0 when beta <= 0); u = word 0 / 2^32 of (CG_SITE_DNS_ACCEPT, a = 0, b = itr);
+ *     u < prob: a_bar, Q_bar = a1, Q1 and beta = max(0, beta - c_beta); else a_bar = K_all[cg_index(word 0 of (CG_SITE_DNS_CHOICE,
+ *     a = 0, b = itr), len(K_all))] with the Q it was scored with (the reference re-evaluates its deterministic critic; Q(a_best) is
+ *     the cached value likewise).  Comparisons on the fp32 Q values, exact in f64.
+ *  6. return a_best.
+ * Output: a_best is written as group 0 of the row exactly like cygym_decode_actions -- type through `type_map`, ascending devices,
+ * exploit [x], the app, CG_DECODE_TRUNCATED when the device list is cut at max_devs; critic->vec_out (optional) receives
+ * enc(a_best) with the type INDEX and the WHOLE mask (what the `Cord_asc` replay stores, :1424) on the searched rows.
+ * From `c`: h_state, w1a_t, w2, b2, w3, b3, H1, H2, h_stride, vec_out, vec_stride (tau, top_k, noise_std, pick_out, q_out are ignored).
+ * From `layout`: vec (= raw), stride, rows, type_map, the sizes, epsilon_thr, n, status.  Needs a bound handle (the rng ticks; they are
+ * read and never advanced).
+ * Limits (CYGYM_EUNSUPPORTED beyond): 1 <= n_devices <= 256; n_types <= 32; n_exploits <= CG_MAX_EXPLOITS; n_apps <= 32; H1, H2 multiples
+ * of 16 in 16 .. 128; n_samples 1 .. 80; max_iters 1 .. 16; every k 1 .. 8; 0 < sigma <= 0.125 (the "stays on" argument above).
+ * CYGYM_EINVAL (nothing is written): a NULL handle, struct or required pointer (h_state, w1a_t, w2, w3, vec, gate_out), beta_init < 0,
+ * a non-finite beta_init / c_beta / sigma / dyn_eps_min, stride or vec_stride < n_out, h_stride < H1, a bad row count.
+ * CYGYM_ENOTBOUND without cygym_bind.
+ * Out of scope: exploit_override and the `committee` mapping; building h_state or the actor forward on chip. */
+int cygym_dns_decode(cygym_handle* h, const cygym_critic* c, const cygym_dns* q, const cygym_action_vectors* layout,
+                     const cygym_actions* dst, void* stream);
+
 /* The per-device actor-critic of the reference's IPPO / MAPPO agents with USE_GAT off, as the reference ships it (IPPO.py:21,
  * MAPPO.py:21): CommActorCritic (IPPO.py:135-196, MAPPO.py the same) in the pieces the decode below reads, all fp32, DEVICE
  * pointers.  With s the role observation, hs = relu(state_proj(s)) and e_d = id_emb.weight[d] the network is

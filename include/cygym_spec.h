@@ -218,9 +218,21 @@ enum {
                                 allowed[word 0 % len(allowed)]; same addressing                                   */
   CG_SITE_HMARL_SHUFFLE = 76, /* HMARL.py:266 random.shuffle(seeds) of attacker type 1: a = device id (sort key): the seeds in
                                 ascending (word 0, id), the contract's reading of a shuffle as at CG_SITE_SHUFFLE; same addressing */
-  CG_SITE_HMARL_TYPE_SAMPLE = 77 /* HMARL.py:810-811 Categorical(logits = the skill's net).sample() of _phase1_train_subpolicies: a = b = 0;
+  CG_SITE_HMARL_TYPE_SAMPLE = 77, /* HMARL.py:810-811 Categorical(logits = the skill's net).sample() of _phase1_train_subpolicies: a = b = 0;
                                 u = word 0 / 2^32 walks the inverse CDF over ALL n_logits outputs, the index is clamped afterwards
                                 (:812); same addressing (cygym_hmarl_sample_decode, force_skill >= 0)            */
+  /* cygym_dns_decode: DoubleOracle.dynamic_neighborhood_search (do_agent.py:1204-1250) behind its gate (:1382).  All at the env's rng tick,
+   * read and not advanced; itr = 1 .. max_iters is the search iteration, s = 0 .. n_samples - 1 the sample of generate_neighbors (:1176). */
+  CG_SITE_DNS_GATE = 78,     /* do_agent.py:1382 / utils.py:1158 np.random.rand() < dyn_eps: a = b = 0; u = word 0 / 2^32, compared in f64 */
+  CG_SITE_DNS_NOISE = 79,    /* :1177 np.random.randn(n_out): a = component j, b = (itr - 1) * n_samples + s; the normal of
+                                CG_SITE_COORD_NOISE from words 0 and 1.  A device component (T <= j < T + D) needs only the SIGN of its
+                                normal: z > 0 iff word 0 != 2^32 - 1 and (word 1 < 2^30 or word 1 > 3 * 2^30), the exact reading of
+                                cos(2 pi u2) > 0                                                                   */
+  CG_SITE_DNS_EPS = 80,      /* :972-973 inside generate_neighbors: a = 0, b as above; word 0 the coin (u < ceil(eps * 2^32)), word 1 the
+                                uniform type index, as CG_SITE_EPS_TYPE                                           */
+  CG_SITE_DNS_ACCEPT = 81,   /* :1239 random.random() < prob: a = 0, b = itr; u = word 0 / 2^32, compared in f64      */
+  CG_SITE_DNS_CHOICE = 82    /* :1243 random.choice(list(K_all)): a = 0, b = itr; index = cg_index(word 0, len(K_all)) into K_all in
+                                first-insertion order                                                              */
 };
 
 /* ---- Philox4x32-10 (Salmon et al., SC'11), counter-based ----
