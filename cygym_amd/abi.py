@@ -132,6 +132,16 @@ class Dns(C.Structure):
                 ("sigma", C.c_double), ("max_iters", C.c_int32), ("n_samples", C.c_int32), ("k_seq", C.c_uint8 * DNS_MAX_ITERS)]
 
 
+MIXTURE_MAX_MEMBERS, MIXTURE_MAX_ENVS = 32, 65536
+
+
+class Mixture(C.Structure):
+    _fields_ = [("cdf", C.c_void_p), ("member_baseline", C.c_void_p), ("member_slot", C.c_void_p), ("baseline_state", C.c_void_p),
+                ("index_out", C.c_void_p), ("mode", C.c_void_p), ("rows_masked", C.c_void_p), ("rows_tiled", C.c_void_p),
+                ("tile_slot", C.c_void_p), ("counts", C.c_void_p), ("S", C.c_int32), ("role_mode", C.c_int32),
+                ("n_tiles_max", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CommActor(C.Structure):
     _fields_ = [("tok_base", C.c_void_p), ("tok_dev", C.c_void_p), ("w_type", C.c_void_p), ("b_type", C.c_void_p), ("w_ctx", C.c_void_p),
                 ("b_ctx", C.c_void_p), ("w_v2", C.c_void_p), ("value_out", C.c_void_p), ("logits_out", C.c_void_p),

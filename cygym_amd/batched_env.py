@@ -535,7 +535,8 @@ class BatchedCyberDefenseEnv:
 
     def actor_mlp_decode(self, rows, obs: torch.Tensor, hidden_layers, head, n_types: int, n_exploits: int | None = None,
                          n_apps: int = 0, type_map=None, act=None, epsilon: float = 0.0, tanh: bool = False, n_groups: int = 1,
-                         obs_by_env: bool = False, obs_role: str | None = None, rows_per_group: int | None = None, step: dict | None = None):
+                         obs_by_env: bool = False, obs_role: str | None = None, rows_per_group: int | None = None, step: dict | None = None,
+                         tile_slot: torch.Tensor | None = None):
         """The WHOLE actor (Linear-ReLU stack + last Linear layer, do_agent.py:357-370) fused with decode_actions
         (cygym_actor_mlp_decode): ONE launch per acting role -- hidden activations and action vectors never reach HBM.
           obs            [n, K] float32 (unit inner stride); with obs_by_env the batch's [N, K] role view, read at rows `rows`
@@ -550,8 +551,17 @@ class BatchedCyberDefenseEnv:
         rows_per_group: with n_groups = S, row r belongs to actor (r // rows_per_group) % S (default n // S: actor after actor);
         the grid layouts of rollout_grid in env order are (nA * n_mc, nD) for the defender and (n_mc, nA) for the attacker.
         step = {"act": tensors of the tick to run FIRST, "view", "full_obs", "returns" as in step()}: cygym_step_actor -- the
-        tick and this actor (on the state the tick leaves behind) as ONE launch; needs can_step_actor(...)."""
+        tick and this actor (on the state the tick leaves behind) as ONE launch; needs can_step_actor(...).
+        tile_slot [n_tiles] int32 (cygym_actor_mlp_decode_tiled): `rows` is the rows_tiled [16 * n_tiles] of mixture_draw and the
+        workgroup of tile t runs actor tile_slot[t] of the population (n_groups = number of slots); tiles of -1 do nothing.  Needs
+        obs_by_env or obs_role: the observation of a row is that of its env."""
         dst = self.actions_struct(act)
+        if tile_slot is not None:
+            if step is not None or rows is None or not (obs_by_env or obs_role is not None):
+                raise ValueError("tile_slot: rows = rows_tiled, obs_by_env or obs_role, and no fused tick")
+            tile_slot = _on_device(tile_slot, torch.int32, self.device, "tile_slot")
+            if int(rows.numel()) != 16 * int(tile_slot.numel()):
+                raise ValueError(f"tile_slot: rows must hold 16 entries per tile ({int(rows.numel())} rows, {int(tile_slot.numel())} tiles)")
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
         if not 1 <= len(hidden_layers) <= abi.MLP_MAX_HIDDEN:
             raise ValueError(f"1 to {abi.MLP_MAX_HIDDEN} hidden layers")
@@ -591,6 +601,11 @@ class BatchedCyberDefenseEnv:
         if bh is not None and (not ok(bh) or not bh.is_contiguous() or bh.numel() != S_ * n_out):
             raise ValueError(f"head: bias must hold {S_ * n_out} float32 values")
         ml.w_head, ml.b_head = wh.data_ptr(), (bh.data_ptr() if bh is not None else None)
+        if tile_slot is not None:      # the actor of a tile comes from the table: rows_per_group is not read
+            ml.n_groups, ml.rows_per_group = S_, 0
+            _lib.check(self.lib.cygym_actor_mlp_decode_tiled(self._h, C.byref(ml), C.byref(src), tile_slot.data_ptr(), int(tile_slot.numel()),
+                                                             C.byref(dst), self._stream()), self._h, "cygym_actor_mlp_decode_tiled")
+            return
         rpg = (n // S_ if rows_per_group is None else int(rows_per_group)) if S_ > 1 else 0
         if S_ > 1 and (rpg < 16 or rpg % 16 or (rows_per_group is None and n % S_)):
             raise ValueError("a population launch needs the same number of rows per actor, a multiple of 16")
@@ -603,6 +618,42 @@ class BatchedCyberDefenseEnv:
             return
         _lib.check(self.lib.cygym_actor_mlp_decode(self._h, C.byref(ml), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_actor_mlp_decode")
+
+    def mixture_draw(self, cdf: torch.Tensor, member_baseline: torch.Tensor, member_slot: torch.Tensor, baseline_state: torch.Tensor, role: str, *,
+                     index_out: torch.Tensor, mode: torch.Tensor, rows_masked=None, rows_tiled=None, tile_slot=None, counts=None):
+        """The opponent of a best-response trainer drawn from an equilibrium mixture, for every env in ONE launch (cygym_mixture_draw:
+        `np.random.choice(len(pool), p=equilibrium)` of do_agent.py:1447 / IPPO.py:392 / hierarchical_br.py:363 per env, site
+        CG_SITE_MIXTURE at the env's rng tick, which is read and not advanced).
+          cdf [S] float64 (policies.mixture_cdf), member_baseline / member_slot [S] int8, baseline_state [N] int8 (in/out),
+          index_out [N] uint8, mode [N] int32 = `role`'s mode word | (baseline_state + 1) << MODE_BASELINE_SHIFT;
+          optional rows_masked [S, N] int32, rows_tiled [16 * T] + tile_slot [T] int32 with T >= ceil(N / 16) + S, counts [S] int32.
+        1 <= S <= 32, N <= 65536.  Every tensor is checked here: the kernel indexes them by raw pointer."""
+        r = _role(role)
+        S_ = int(cdf.numel())
+        mx = abi.Mixture()
+        keep = [_exactly(S_, cdf, torch.float64, self.device, "cdf"), _exactly(S_, member_baseline, torch.int8, self.device, "member_baseline"),
+                _exactly(S_, member_slot, torch.int8, self.device, "member_slot")]
+        mx.cdf, mx.member_baseline, mx.member_slot = (t.data_ptr() for t in keep)
+        for name, t, dt, n in (("baseline_state", baseline_state, torch.int8, self.N), ("index_out", index_out, torch.uint8, self.N),
+                               ("mode", mode, torch.int32, self.N), ("rows_masked", rows_masked, torch.int32, S_ * self.N),
+                               ("counts", counts, torch.int32, S_)):
+            if t is None:
+                continue
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous() or int(t.numel()) != n:      # outputs: written in place, never a temporary
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of {n} entries on {self.device}")
+            setattr(mx, name, t.data_ptr())
+        if (rows_tiled is None) != (tile_slot is None):
+            raise ValueError("rows_tiled and tile_slot come together")
+        if rows_tiled is not None:
+            T = int(tile_slot.numel())
+            for name, t, n in (("rows_tiled", rows_tiled, 16 * T), ("tile_slot", tile_slot, T)):
+                if t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or int(t.numel()) != n:
+                    raise ValueError(f"{name} must be a contiguous int32 tensor of {n} entries on {self.device}")
+            if T < (self.N + 15) // 16 + S_:
+                raise ValueError(f"tile_slot must hold at least ceil(N / 16) + S = {(self.N + 15) // 16 + S_} tiles")
+            mx.rows_tiled, mx.tile_slot, mx.n_tiles_max = rows_tiled.data_ptr(), tile_slot.data_ptr(), T
+        mx.S, mx.role_mode = S_, (S.MODE_DEFENDER if r["code"] == 1 else S.MODE_ATTACKER)
+        _lib.check(self.lib.cygym_mixture_draw(self._h, C.byref(mx), self._stream()), self._h, "cygym_mixture_draw")
 
     def coord_ascent_decode(self, rows, h_state: torch.Tensor, critic_pack, n_types: int, n_exploits: int | None = None,
                             n_apps: int = 0, type_map=None, act=None, top_k: int = 5, tau: float = 0.5, pick_out=None, q_out=None,

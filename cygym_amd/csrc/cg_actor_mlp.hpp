@@ -138,10 +138,18 @@ __device__ __forceinline__ void mlp_finish_hidden(const float* part, const float
 
 // FROM_LDS (tick_actor_kernel, cg_tick_actor.hpp): the flag planes of the 16 envs are still in LDS where the tick left them --
 // row r's at lds_flags + r * lds_pitch -- and source row == env id; they are read before the observation tile overwrites them.
+// tile_slot (actor_mlp_tiled_kernel, cg_mixture.hpp; every other kernel passes the literal null and carries none of this): the
+// population's actor of this workgroup's 16 rows is tile_slot[blockIdx.x] instead of the arithmetic on the row number, and a
+// workgroup whose entry is negative leaves as a whole before its first barrier.
 template <int HEAD_OPL, int VW, bool FROM_LDS>
 __device__ __forceinline__ void actor_mlp_body(cygym_actor_mlp ml, const cygym_action_vectors& src, const cygym_actions& dst, const int n_envs,
                                                const int32_t* ienv, const uint64_t seed, const int64_t env_id_base, unsigned long long* st,
-                                               const MlpView& vw, const uint8_t* lds_flags, const int lds_pitch) {
+                                               const MlpView& vw, const uint8_t* lds_flags, const int lds_pitch, const int32_t* tile_slot = nullptr) {
+  int slot = 0;
+  if (tile_slot) {
+    slot = tile_slot[blockIdx.x];
+    if (slot < 0 || slot >= ml.n_groups) return;   // (uniform: an unused tile; a slot past the population never reaches the weights)
+  }
 #ifdef CG_STAMPS
 #define MSTAMP(k) do { if (st && threadIdx.x == 0) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); st[(size_t)blockIdx.x * 16 + (k)] = _t; } } while (0)
 #else
@@ -174,7 +182,7 @@ __device__ __forceinline__ void actor_mlp_body(cygym_actor_mlp ml, const cygym_a
   const float* w_head = ml.w_head;
   const float* b_head = ml.b_head;
   {
-    const size_t grp = ml.n_groups > 1 ? (size_t)((row0 / ml.rows_per_group) % ml.n_groups) : 0;   // a population of actors: this workgroup's 16 rows belong to ONE of them
+    const size_t grp = tile_slot ? (size_t)slot : ml.n_groups > 1 ? (size_t)((row0 / ml.rows_per_group) % ml.n_groups) : 0;   // a population of actors: this workgroup's 16 rows belong to ONE of them
     int kin = G0;
 #pragma unroll
     for (int l = 0; l < CG_MLP_MAX_HIDDEN; ++l) {

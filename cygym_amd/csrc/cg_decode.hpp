@@ -168,4 +168,5 @@ __device__ __forceinline__ int sample_head(const float* l, const int K, const ui
 #include "cg_hmarl.hpp"
 #include "cg_meta.hpp"
 #include "cg_meta_select.hpp"
+#include "cg_mixture.hpp"
 #endif  // CG_DECODE_HPP

@@ -133,6 +133,15 @@ extern template __global__ void cat_ppo_kernel<false>(cygym_cat_ppo_desc, float,
 extern template __global__ void cat_ppo_kernel<true>(cygym_cat_ppo_desc, float, float);
 }  // namespace cygym_k
 
+// the mixture draw and the whole-actor launch with a tile table live in their own unit (cg_inst_mixture.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void mixture_draw_kernel<false>(cygym_mixture, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void mixture_draw_kernel<true>(cygym_mixture, int, const int32_t*, uint64_t, int64_t);
+#define CG_DECL(O, V) extern template __global__ void actor_mlp_tiled_kernel<O, V>(cygym_actor_mlp, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, unsigned long long*, MlpView, const int32_t*);
+CG_MLP_TILED_KERNELS(CG_DECL)
+#undef CG_DECL
+}  // namespace cygym_k
+
 // =====================================================================
 // C ABI
 // =====================================================================
@@ -277,6 +286,7 @@ int cygym_sizeof(int32_t which) {
     case 28: return (int)sizeof(cygym_cat_ppo_desc);
     case 29: return (int)sizeof(cygym_hmarl_train);
     case 31: return (int)sizeof(cygym_dns);   // (index 30 stays unassigned)
+    case 33: return (int)sizeof(cygym_mixture);   // (index 32 stays unassigned)
     default: return -1;
   }
 }
@@ -797,8 +807,10 @@ int cygym_actor_head_decode(cygym_handle* h, const cygym_actor_head* head, const
   return launch_decode(h, k, dim3((src->n + rows_per_wg - 1) / rows_per_wg), dim3(16 * WAVE), lds, stream, {head, src, dst});
 }
 
-int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cygym_action_vectors* src, const cygym_actions* dst,
-                           void* stream) {
+}  // extern "C"
+// cygym_actor_mlp_decode and, with a tile table, cygym_actor_mlp_decode_tiled: the same checks, plan and launch.
+static int actor_mlp_decode_impl(cygym_handle* h, const cygym_actor_mlp* mlp, const cygym_action_vectors* src, const cygym_actions* dst,
+                                 void* stream, const int32_t* tile_slot) {
   const char* const who = "cygym_actor_mlp_decode";
   const char* const bad_layout = "cygym_actor_mlp_decode: bad layout%s";
   if (const int rc = check_vectors(h, src, dst, who, mlp && (mlp->obs || mlp->obs_role) && mlp->w_head, 0, bad_layout)) return rc;
@@ -818,7 +830,7 @@ int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cy
   const long long n_out = (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps;
   if (n_out > 8192) return fail(h, CYGYM_EUNSUPPORTED, "cygym_actor_mlp_decode: more than 8192 outputs%s", "");
   if (const int rc = check_rows(h, src->n, src->rows, src->epsilon_thr, who)) return rc;
-  if (mlp->n_groups > 1 && (mlp->rows_per_group < 16 || (mlp->rows_per_group & 15)))   // (row r: actor (r / rows_per_group) % n_groups)
+  if (!tile_slot && mlp->n_groups > 1 && (mlp->rows_per_group < 16 || (mlp->rows_per_group & 15)))   // (row r: actor (r / rows_per_group) % n_groups)
     return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode: rows_per_group must be a multiple of 16%s", "");
   if (!mlp->obs_role && (unsigned long long)(mlp->obs_by_env ? h->n_envs : src->n) * (unsigned long long)mlp->obs_stride >= (1ull << 32))
     return fail(h, CYGYM_EUNSUPPORTED, "cygym_actor_mlp_decode: observation matrices of 2^32 floats or more%s", "");   // (32-bit row offsets in the kernel)
@@ -832,14 +844,57 @@ int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cy
   // widest vector the observation rows allow (base address and row stride)
   const uintptr_t al = mlp->obs_role ? 0 : ((uintptr_t)mlp->obs | ((uintptr_t)mlp->obs_stride * 4));   // (K itself may be anything <= obs_stride)
   const int vw = mlp->obs_role ? 0 : (al & 15) == 0 ? 4 : (al & 7) == 0 ? 2 : 1;   // (0: the role view built on chip)
-  const void* k = kernel_by_opl<0>(wide_out ? 0 : n_out_p / WAVE, [vw](auto O) {
+  const void* k = tile_slot ? kernel_by_opl<0>(wide_out ? 0 : n_out_p / WAVE, [vw](auto O) {
+    constexpr int o = decltype(O)::value;
+    return vw == 0 ? (const void*)actor_mlp_tiled_kernel<o, 0> : vw == 4 ? (const void*)actor_mlp_tiled_kernel<o, 4> : vw == 2 ? (const void*)actor_mlp_tiled_kernel<o, 2> : (const void*)actor_mlp_tiled_kernel<o, 1>;
+  }) : kernel_by_opl<0>(wide_out ? 0 : n_out_p / WAVE, [vw](auto O) {
     constexpr int o = decltype(O)::value;
     return vw == 0 ? (const void*)actor_mlp_kernel<o, 0> : vw == 4 ? (const void*)actor_mlp_kernel<o, 4> : vw == 2 ? (const void*)actor_mlp_kernel<o, 2> : (const void*)actor_mlp_kernel<o, 1>;
   });
   if (const int rc = raise_lds_once(h, k)) return rc;
   unsigned long long* st = h->dbg;   // (diagnostic builds: cygym_set_debug)
   MlpView view = {h->b.live, h->t.os_val, h->t.version, h->t.anomaly, h->b.anomaly, h->t.M, h->t.X, h->c.max_exploits, mlp->obs_role};
+  if (tile_slot) return launch_decode(h, k, dim3((src->n + 15) / 16), dim3(MLP_THREADS), lds, stream, {mlp, src, dst}, {&st, &view, &tile_slot});
   return launch_decode(h, k, dim3((src->n + 15) / 16), dim3(MLP_THREADS), lds, stream, {mlp, src, dst}, {&st, &view});
+}
+extern "C" {
+int cygym_actor_mlp_decode(cygym_handle* h, const cygym_actor_mlp* mlp, const cygym_action_vectors* src, const cygym_actions* dst,
+                           void* stream) {
+  return actor_mlp_decode_impl(h, mlp, src, dst, stream, nullptr);
+}
+
+int cygym_actor_mlp_decode_tiled(cygym_handle* h, const cygym_actor_mlp* mlp, const cygym_action_vectors* src, const int32_t* tile_slot,
+                                 int32_t n_tiles, const cygym_actions* dst, void* stream) {
+  if (!h) return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode_tiled: null handle%s", "");
+  if (!mlp || !src || !dst || !tile_slot) return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode_tiled: null argument%s", "");
+  if (!mlp->obs_by_env && !mlp->obs_role)
+    return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode_tiled: the observation of a row is that of its env (obs_by_env or obs_role)%s", "");
+  if (n_tiles < 0 || !src->rows || (long long)src->n != 16ll * n_tiles || mlp->n_groups < 1)
+    return fail(h, CYGYM_EINVAL, "cygym_actor_mlp_decode_tiled: layout->rows = rows_tiled, layout->n = 16 * n_tiles, n_groups = the number of slots%s", "");
+  return actor_mlp_decode_impl(h, mlp, src, dst, stream, tile_slot);
+}
+
+int cygym_mixture_draw(cygym_handle* h, const cygym_mixture* mix, void* stream) {
+  if (!h) return fail(h, CYGYM_EINVAL, "cygym_mixture_draw: null handle%s", "");
+  if (!mix || !mix->cdf || !mix->member_baseline || !mix->member_slot || !mix->baseline_state || !mix->index_out || !mix->mode)
+    return fail(h, CYGYM_EINVAL, "cygym_mixture_draw: null pointer%s", "");
+  if (mix->S < 1 || mix->S > CG_MIXTURE_MAX_MEMBERS || h->n_envs > CG_MIXTURE_MAX_ENVS)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_mixture_draw: 1 to 32 members, at most 65536 envs%s", "");
+  const bool tiled = mix->rows_tiled != nullptr;
+  if (tiled != (mix->tile_slot != nullptr) || (tiled && (long long)mix->n_tiles_max < (h->n_envs + 15) / 16 + (long long)mix->S))
+    return fail(h, CYGYM_EINVAL, "cygym_mixture_draw: rows_tiled and tile_slot come together, with n_tiles_max >= ceil(n_envs / 16) + S%s", "");
+  if (!h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_mixture_draw: handle not bound (the draw is addressed by the envs' rng ticks)%s", "");
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const void* k = tiled ? (const void*)mixture_draw_kernel<true> : (const void*)mixture_draw_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  int n = h->n_envs;
+  const int32_t* ienv = h->b.ienv;
+  uint64_t seed = h->c.seed;
+  int64_t base = h->c.env_id_base;
+  void* args[] = {(void*)mix, (void*)&n, (void*)&ienv, (void*)&seed, (void*)&base};
+  HIPCHK(h, hipLaunchKernel(k, dim3(1), dim3(MIX_THREADS), args, mixture_lds_bytes(n), (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
 }
 
 int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* src, const cygym_actions* dst,

@@ -57,7 +57,8 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
             t0: int = 0, decoder=None, observer=None) -> Transitions:
     """Collect `n_decisions` transitions of `role` in every env of `batch` (the for-loop of do_agent.py:1334-1460 without the
     update).  actor(state [N, W]) -> [N, n_types + M + n_exploits + n_apps] action vectors; opponent: a baseline name / fixed
-    sequence, a policy(obs, t, M, L) -> action tensors, or an object with write(batch, act, rows, obs).  The loop's tick
+    sequence, a policy(obs, t, M, L) -> action tensors, or an object with write(batch, act, rows, obs) -- a policies.MixturePolicy over
+    such members draws one of them per env and opponent turn from an equilibrium (:1447).  The loop's tick
     counter starts at `t0` (turns follow t % 2 like the reference's, not the envs' step_num).  The reference leaves its loop
     at the first done (:1439); a batch goes on: with auto_reset the env restarts from its snapshot, and `done` marks the row.
     decoder: a policies.CoordAscentPolicy -- the reference's `Cord_asc` mode: on the learner's turn decoder.write(batch, act, rows,
@@ -86,6 +87,9 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
     opp = opponent if (callable(opponent) or hasattr(opponent, "write")) else SequencePolicy(opponent, other)
     bl_code = _baseline_code(opponent, other)      # a baseline opponent: env.base_line stays set from its first turn on
     cur_bl = None
+    mix = hasattr(opp, "mode_bits")                # policies.MixturePolicy: the opponent drawn per env and turn (:1447); it keeps base_line per env
+    if mix and getattr(opp, "role", other) != other:
+        raise ValueError(f"the opponent mixture plays {opp.role!r}, the learner's opponent is the {other}")
     tm = None if type_map is None else torch.as_tensor(type_map, dtype=torch.int32, device=dev)
     rows_all = torch.arange(N, dtype=torch.int32, device=dev)
     act = batch.act
@@ -105,6 +109,8 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
         act["mode"].copy_(mode_word[turn])
         if cur_bl is not None:
             act["mode"] |= (cur_bl + 1) << S.MODE_BASELINE_SHIFT
+        if mix:                  # every tick, the learner's too: nobody resets env.base_line (do_agent.py:718)
+            act["mode"] |= opp.mode_bits()
         act["n_groups"].zero_()
         if turn == role:
             if observer is not None:
@@ -141,6 +147,8 @@ def collect(batch, role: str, actor, opponent, n_decisions: int, n_types: int, n
             rec["next_state"].append(nxt); rec["done"].append(done != 0)
             state = nxt
         else:
+            if mix:
+                opp.set_tick(t)
             if hasattr(opp, "write"):
                 opp.write(batch, act, rows_all, batch.observe(1 if other == HL.DEFENDER else 2))
             else:

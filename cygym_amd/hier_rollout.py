@@ -7,8 +7,8 @@ with torch GEMMs around the fused loss head (HierarchicalNet.evaluate).  For one
 the same formulas with the mean over the rows.
 
 The loop's scaffolding (turn order, opponent, persisting base_line, cap, randomize) is ippo_rollout.Turns, shared with collect.
-Out of scope: drawing the opponent from an equilibrium mixture per turn (:363 -- one opponent per call, as ippo_rollout.collect), the
-`meta` and HMARL families, a fused backward of the Linear layers, and the printing / time-budget bookkeeping (:392-398).
+The opponent drawn from an equilibrium mixture per turn (:363) is a policies.MixturePolicy handed over as `opponent`.
+Out of scope: the `meta` and HMARL families, a fused backward of the Linear layers, and the printing / time-budget bookkeeping (:392-398).
 """
 from __future__ import annotations
 
@@ -59,8 +59,8 @@ def train(batch, role: str, net, partitions, opponent, n_decisions: int, *, fuse
       :338-348  update(): the mean over the envs of -adv (logp_hi + logp_at + beta logp_dev) - (1e-3 ent_hi + 1e-3 ent_at + 1e-4 ent_dev)
                 on the stored decision, a non-finite loss skips it, clip_grad_norm_(0.5) per net, Adam 3e-4 (two_stage) / 1e-3 (score_net)
       :350-359  the episode cap: auto_reset reloads the snapshot, batch.randomize() reshuffles compromise and ownership
-      :361-391  the opponent's turn: ONE opponent (a baseline name / sequence, a policy, or an object with write()); a baseline
-                opponent's env.base_line persists from its first turn on (:366-367)
+      :361-391  the opponent's turn: a baseline name / sequence, a policy, an object with write(), or a policies.MixturePolicy over
+                such members (one drawn per env and turn, :363); a baseline's env.base_line persists from its first turn on (:366-367)
       :401-416  returns {"hierarchical": {"score_net", "two_stage", "M", "partition_size"}}, what HierarchicalPolicy.from_strategy loads
 
     net: policies.HierarchicalNet on the batch's device; partitions: lists of device ids (Subnet.create_partitions).  fused: the loss

@@ -120,6 +120,10 @@ class Turns:
         # under that baseline (volt_typhoon_env.py:847-874, :913-914) -- carried in the mode word like the reference's loops do
         self.bl_code = _baseline_code(opponent, other)
         self.cur_bl = None
+        # an opponent drawn from a mixture per turn (policies.MixturePolicy) keeps that base_line itself, per env: mode_bits()
+        self.mix = hasattr(self.opp, "mode_bits")
+        if self.mix and getattr(self.opp, "role", other) != other:
+            raise ValueError(f"the opponent mixture plays {self.opp.role!r}, the learner's opponent is the {other}")
         step_num = batch.state["ienv"][:, S.I_STEP_NUM]
         s0 = int(step_num[0].item())
         if not bool((step_num == s0).all().item()):
@@ -143,11 +147,15 @@ class Turns:
         self.act["mode"].copy_(self.mode_word[turn])
         if self.cur_bl is not None:
             self.act["mode"] |= (self.cur_bl + 1) << S.MODE_BASELINE_SHIFT
+        if self.mix:      # every tick, the learner's too: nobody resets env.base_line (IPPO.py:395-397)
+            self.act["mode"] |= self.opp.mode_bits()
         return turn, obs
 
     def opponent(self, obs):
         batch, act, opp, s = self.batch, self.act, self.opp, self.s
         act["n_groups"].zero_()
+        if self.mix:
+            opp.set_tick(s)      # (a sequence member indexes with env.step_num, IPPO.py:400-401)
         if hasattr(opp, "write"):
             opp.write(batch, act, self.rows_all, obs)
         else:
@@ -179,7 +187,8 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
         "exp_logits" [N, E], "app_logits" [N, A] -- the outputs the reference's networks produce (:517-519, :541-555); how
         the net uses the mask (a GAT over masked_adjacency(vis), an MLP ...) is its own business.
     opponent: what plays the other role -- a baseline name / fixed sequence (rollout_grid.SequencePolicy semantics), a
-        policy(obs, t, M, L) -> action tensors, or an object with write(batch, act, rows, obs) (policies.ActorPolicy).
+        policy(obs, t, M, L) -> action tensors, or an object with write(batch, act, rows, obs) (policies.ActorPolicy);
+        a policies.MixturePolicy over such members draws one of them per env and opponent turn from an equilibrium (IPPO.py:385-430).
     The batch must have been created with max_groups >= the role's action types and max_devs >= M, and auto_reset on.
     fused_sampling (default): the Categoricals are sampled inside the grouping launch (cygym_sample_group_actions: addressed
     Philox draws, log-probabilities summed in the kernel); False: torch.multinomial with `generator`, then cygym_group_actions.

@@ -223,7 +223,8 @@ class MetaController:
 def train(batch, role: str, agent, controller: MetaController, opponent, n_decisions: int, return_meta: bool = False, **kw):
     """MetaHierarchicalBestResponse.train (:893-935): return_meta -> the controller as a strategy mapping (:916-921, to_strategy());
     else the normal branch (:924-935): ddpg_rollout.best_response with the controller observing, and what that returns.  **kw goes to
-    best_response (n_types, n_exploits, decoder, meta_period, ...)."""
+    best_response (n_types, n_exploits, decoder, meta_period, ...).  opponent: as ddpg_rollout.collect takes it -- the equilibrium
+    mixture the reference hands to the DDPG loop (:911-927) is a policies.MixturePolicy."""
     if return_meta:
         return controller.to_strategy()
     if controller.role != role:

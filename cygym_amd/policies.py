@@ -2182,3 +2182,218 @@ class MetaPolicy:
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("a MetaPolicy reads the flags and the graph of the env it decides for and answers with groups: it runs "
                                   "through write(), on a batch with cygym_meta_decode (MetaNet.decide is the torch form)")
+
+
+# ---- the opponent drawn from an equilibrium mixture (do_agent.py:1447, IPPO.py:385-430, hierarchical_br.py:363) -------------------------
+
+def mixture_cdf(probs):
+    """The cdf np.random.choice(n, p=probs) searches: p.cumsum() / p.cumsum()[-1] in float64 with numpy (include/cygym_spec.h,
+    CG_SITE_MIXTURE).  probs must be finite, non-negative and of positive sum (ValueError otherwise)."""
+    import numpy as np
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    if p.size < 1 or not np.isfinite(p).all() or (p < 0).any() or not float(p.sum()) > 0.0:
+        raise ValueError("probs must be finite, non-negative and of positive sum")
+    cdf = p.cumsum()
+    cdf /= cdf[-1]
+    return cdf
+
+
+def mixture_index_np(cdf, u):
+    """index = #{ j : cdf[j] <= u }: numpy's cdf.searchsorted(u, side='right'), counted the way the kernel counts it."""
+    import numpy as np
+    cdf, u = np.asarray(cdf, np.float64), np.asarray(u, np.float64)
+    return (cdf[None, :] <= u.reshape(-1, 1)).sum(axis=1).astype(np.int64).reshape(u.shape)
+
+
+def mixture_draw_np(cdf, seed: int, env_ids, ticks):
+    """The member every env draws (cygym_mixture_draw restated on rng.draw_np): u = word 0 / 2^32 of the draw addressed (global env
+    id, the env's rng tick, CG_SITE_MIXTURE, a = b = 0) in float64, then mixture_index_np."""
+    import numpy as np
+    from . import rng as R
+    from . import spec as S
+    w = R.draw_np(int(seed), np.asarray(env_ids, np.int64).astype(np.uint64), np.asarray(ticks, np.int64).astype(np.uint64), S.SITE_MIXTURE)
+    return mixture_index_np(cdf, w.astype(np.float64) / 4294967296.0)
+
+
+def mixture_rows_np(index, member_slot, n_tiles_max=None):
+    """The two row layouts of cygym_mixture_draw for the drawn members `index` [n]: (rows_masked [S, n], rows_tiled [16 T],
+    tile_slot [T], counts [S]) with T = n_tiles_max (default ceil(n / 16) + S).  rows_masked[s, e] = e where env e drew member s, else
+    -1.  rows_tiled: the envs whose member has a slot, by ascending slot and ascending env id, every slot's segment padded with -1 to
+    whole tiles of 16; tile_slot[t] = the slot of tile t, -1 for the unused tiles."""
+    import numpy as np
+    index, member_slot = np.asarray(index, np.int64), np.asarray(member_slot, np.int64)
+    n, S_ = index.size, member_slot.size
+    T = (n + 15) // 16 + S_ if n_tiles_max is None else int(n_tiles_max)
+    e = np.arange(n)
+    rows_masked = np.where(index[None, :] == np.arange(S_)[:, None], e[None, :], -1).astype(np.int32)
+    counts = np.bincount(index, minlength=S_).astype(np.int32)
+    rows_tiled, tile_slot = np.full(16 * T, -1, np.int32), np.full(T, -1, np.int32)
+    slot_of, t = member_slot[index], 0
+    for s in range(32):
+        ids = e[slot_of == s]
+        if ids.size:
+            nt = (ids.size + 15) // 16
+            rows_tiled[16 * t: 16 * t + ids.size] = ids
+            tile_slot[t: t + nt] = s
+            t += nt
+    return rows_masked, rows_tiled, tile_slot, counts
+
+
+class MixturePolicy:
+    """The opponent of a best-response trainer after the first double-oracle iteration: on every opponent turn each env draws ONE
+    strategy of the opponent's pool from the current equilibrium and lets it act (do_agent.py:1447; IPPO.py:385-430 `_opponent_action`,
+    MAPPO.py the same; hierarchical_br.py:363; meta_hierarchical_br.py:911-927 through the DDPG loop).
+        members  what the rollouts accept as `opponent`: a baseline name, a fixed action sequence, a callable policy(obs, t, M, L), or
+                 an object with write(batch, act, rows, obs)
+        probs    the equilibrium over them (mixture_cdf)
+        role     the role the mixture plays (the OTHER role of the learner)
+    write(batch, act, rows, obs), rows = all envs (ValueError otherwise):
+      1. one cygym_mixture_draw: the member of every env, the persisting env.base_line of baseline members (per env, in
+         baseline_state), this tick's mode word written straight into act["mode"], and the row lists of the members;
+      2. the members that are ActorPolicy of ONE architecture (ActorPolicyGroup.key) with fused_mlp(batch), two or more: ONE
+         cygym_actor_mlp_decode_tiled over the tiles of the draw, reading `obs` in place (tiled = False: off);
+      3. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
+         rollout_grid.SequencePolicy + write_actions with the tick the loop set (set_tick: the loop's tick counter; a callable without
+         uses_global_tick gets t // 2, as the loops call it).  A member of probability 0 never plays and is not launched.
+    act["n_groups"] is the caller's to clear before the call (Turns.opponent, ddpg_rollout.collect do); a member that writes groups sets
+    it for its rows.
+    mode_bits(): the per-env baseline bits of the mode word, zero until the first draw -- the loops OR them into EVERY tick, the
+    learner's too (the reference never resets env.base_line).  last_index: the [N] uint8 tensor of the last draw.  The state belongs to
+    one batch; reset() forgets it (a new run).
+    On a batch-like without mixture_draw (the tests' oracle harness) the draw is mixture_draw_np on the batch's seed, env ids and ticks
+    and the members write through rollout_grid._write_rows."""
+
+    tick_free = False
+
+    def __init__(self, members, probs, role: str, tiled: bool = True):
+        from . import host_logic as HL
+        from .rollout_grid import SequencePolicy, _baseline_code
+        if role not in (HL.DEFENDER, HL.ATTACKER):
+            raise ValueError("role must be 'attacker' or 'defender'")
+        members = list(members)
+        self.cdf = mixture_cdf(probs)
+        if len(members) != self.cdf.size or not 1 <= len(members) <= 32:
+            raise ValueError("1 to 32 members, one probability each")
+        self.role, self.tiled, self.tick = role, bool(tiled), 0
+        self.probs = [float(x) for x in list(probs)]
+        self.members, self.baseline = [], []
+        for m in members:
+            if callable(m) or hasattr(m, "write"):
+                self.members.append(m); self.baseline.append(-1)
+            elif isinstance(m, str) or (isinstance(m, (list, tuple)) and len(m) > 0):
+                self.baseline.append(_baseline_code(m, role)); self.members.append(SequencePolicy(m, role))
+            else:
+                raise ValueError("a member is a baseline name, a fixed action sequence, a callable policy or an object with write()")
+        types = [getattr(m, "action_types", None) for m in self.members]
+        self.action_types = None if any(t is None for t in types) else sorted({int(x) for t in types for x in t})
+        self.last_index = None
+        self._st = None
+
+    def set_tick(self, t: int):
+        """The calling loop's tick counter (do_agent.py:1335 `t`, env.step_num in IPPO.py:400): what a sequence member indexes with."""
+        self.tick = int(t)
+
+    def reset(self):
+        self._st, self.last_index = None, None
+
+    def mode_bits(self):
+        if self._st is None:
+            return 0
+        from . import spec as S
+        return (self._st["baseline_state"].to(torch.int32) + 1) << S.MODE_BASELINE_SHIFT
+
+    def _group(self, batch):
+        """(ActorPolicyGroup, member_slot list) of the largest set of same-shaped fused actors among the members, or (None, all -1)."""
+        slots = [-1] * len(self.members)
+        if not (self.tiled and hasattr(batch, "mixture_draw") and hasattr(batch, "actor_mlp_decode")):
+            return None, slots
+        by_key = {}
+        for s, m in enumerate(self.members):
+            k = ActorPolicyGroup.key(m, batch.M)
+            if k is not None and m.fused_mlp(batch):
+                by_key.setdefault(k, []).append(s)
+        best = max(by_key.values(), key=len, default=[])
+        if len(best) < 2:
+            return None, slots
+        for pos, s in enumerate(best):
+            slots[s] = pos
+        return ActorPolicyGroup([self.members[s] for s in best]), slots
+
+    def _state(self, batch):
+        st = self._st
+        if st is None or st["batch"] is not batch:
+            N, S_, dev = batch.N, len(self.members), batch.device
+            grp, slots = self._group(batch)
+            T = (N + 15) // 16 + S_
+            z = lambda shape, dt, v=0: torch.full(shape, v, dtype=dt, device=dev)  # noqa: E731
+            st = self._st = dict(batch=batch, group=grp, slots=slots, cdf=torch.from_numpy(self.cdf).to(dev),
+                                 member_baseline=torch.tensor(self.baseline, dtype=torch.int8, device=dev),
+                                 member_slot=torch.tensor(slots, dtype=torch.int8, device=dev), baseline_state=z((N,), torch.int8, -1),
+                                 index=z((N,), torch.uint8), rows_masked=z((S_, N), torch.int32, -1), rows_ok=None,
+                                 rows_tiled=z((16 * T,), torch.int32, -1) if grp is not None else None,
+                                 tile_slot=z((T,), torch.int32, -1) if grp is not None else None)
+        return st
+
+    def _check_rows(self, st, rows, N):
+        if rows is None:
+            return
+        key = (rows.data_ptr(), rows._version, tuple(rows.shape))
+        if st["rows_ok"] != key:      # one comparison per rows tensor (the loops hand over the same arange every turn)
+            if int(rows.numel()) != N or not bool((rows.reshape(-1).to(torch.int64) == torch.arange(N, device=rows.device)).all().item()):
+                raise ValueError("MixturePolicy.write: rows must be all envs of the batch, in order (the draw covers every env)")
+            st["rows_ok"] = key
+
+    def _member_tick(self, m):
+        return self.tick if getattr(m, "uses_global_tick", False) else self.tick // 2
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs):
+        st = self._state(batch)
+        N = batch.N
+        self._check_rows(st, rows, N)
+        if not hasattr(batch, "mixture_draw"):
+            return self._write_host(batch, act, obs, st)
+        batch.mixture_draw(st["cdf"], st["member_baseline"], st["member_slot"], st["baseline_state"], self.role, index_out=st["index"],
+                           mode=act["mode"], rows_masked=st["rows_masked"], rows_tiled=st["rows_tiled"], tile_slot=st["tile_slot"])
+        self.last_index = st["index"]
+        grp, slots = st["group"], st["slots"]
+        in_place = obs.dtype == torch.float32 and obs.dim() == 2 and obs.stride(1) == 1 and int(obs.shape[0]) >= N
+        if grp is not None and in_place:
+            hidden, head = grp._packed_all(batch)
+            p0 = grp.policies[0]
+            batch.actor_mlp_decode(st["rows_tiled"], obs, hidden, head, grp.n_types, grp.n_exploits, grp.n_apps, p0._map(batch.device), act,
+                                   epsilon=grp.epsilon, tanh=p0._split_mlp(batch.M)[2], n_groups=len(grp.policies), obs_by_env=True,
+                                   tile_slot=st["tile_slot"])
+        for s, m in enumerate(self.members):
+            if (grp is not None and in_place and slots[s] >= 0) or self.probs[s] == 0.0:
+                continue
+            r = st["rows_masked"][s]
+            if hasattr(m, "write"):
+                m.write(batch, act, r, obs)
+            else:
+                batch.write_actions(r, m(obs, self._member_tick(m), batch.M, batch.L), act)
+
+    def _write_host(self, batch, act, obs, st):
+        """The same on a batch-like without the library's launches: the numpy restatement of the draw, compact rows per member."""
+        import numpy as np
+        from . import spec as S
+        from .rollout_grid import _write_rows
+        N = batch.N
+        ienv = batch.state["ienv"]
+        ticks = (ienv.cpu().numpy() if isinstance(ienv, torch.Tensor) else np.asarray(ienv))[:, S.I_RNG_TICK]
+        idx = mixture_draw_np(self.cdf, int(batch.cfg.seed), int(batch.cfg.env_id_base) + np.arange(N), ticks)
+        idx_t = torch.from_numpy(idx).to(obs.device)
+        st["index"].copy_(idx_t.to(torch.uint8))
+        self.last_index = st["index"]
+        mb = st["member_baseline"].to(torch.int64)[idx_t]
+        st["baseline_state"].copy_(torch.where(mb >= 0, mb, st["baseline_state"].to(torch.int64)).to(torch.int8))
+        role_mode = S.MODE_DEFENDER if self.role == "defender" else S.MODE_ATTACKER
+        act["mode"].copy_((role_mode | self.mode_bits()).to(act["mode"].dtype))
+        for s, m in enumerate(self.members):
+            r = torch.nonzero(idx_t == s).reshape(-1)
+            if r.numel() == 0:
+                continue
+            if hasattr(m, "write"):
+                m.write(batch, act, r.to(torch.int32), obs[r])
+            else:
+                _write_rows(batch, act, r, m(obs[r], self._member_tick(m), batch.M, batch.L), batch.L)

@@ -65,6 +65,7 @@ SITE_DNS_NOISE = 79
 SITE_DNS_EPS = 80
 SITE_DNS_ACCEPT = 81
 SITE_DNS_CHOICE = 82
+SITE_MIXTURE = 83
 
 POISSON_TABLE = 16
 TRI_TABLE = 8

@@ -193,7 +193,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train; -1 for anything else, 13, 15, 18, 22, 24 and 26 included: those indices stay unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train, 31 cygym_dns, 33 cygym_mixture; -1 for anything else, 13, 15, 18, 22, 24, 26, 30 and 32 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -550,6 +550,54 @@ typedef struct cygym_dns {
  * Out of scope: exploit_override and the `committee` mapping; building h_state or the actor forward on chip. */
 int cygym_dns_decode(cygym_handle* h, const cygym_critic* c, const cygym_dns* q, const cygym_action_vectors* layout,
                      const cygym_actions* dst, void* stream);
+
+/* The opponent of a best-response trainer on a batch: one strategy of the opponent's pool per env and opponent turn, drawn from the
+ * equilibrium mixture.  DEVICE pointers; S members. */
+#define CG_MIXTURE_MAX_MEMBERS 32
+#define CG_MIXTURE_MAX_ENVS 65536
+typedef struct cygym_mixture {
+  const double* cdf;             /* [S] p.cumsum() / p.cumsum()[-1], formed by the host in f64 with numpy (CG_SITE_MIXTURE)            */
+  const int8_t* member_baseline; /* [S] the baseline code (0 Nash, 1 No Defense, 2 Preset, 3 No Attack) of a baseline-name member, else -1 */
+  const int8_t* member_slot;     /* [S] position of the member in a packed actor population (cygym_actor_mlp_decode_tiled), else -1    */
+  int8_t*   baseline_state;      /* [n_envs] in/out: env.base_line of the env as the mixture's baseline members have left it, -1 = none
+                                    was drawn yet                                                                                     */
+  uint8_t*  index_out;           /* [n_envs] the drawn member                                                                         */
+  int32_t*  mode;                /* [n_envs] role_mode | (baseline_state + 1) << CG_MODE_BASELINE_SHIFT, AFTER this draw's update      */
+  int32_t*  rows_masked;         /* optional [S][n_envs]: e where env e drew member s, else -1 (env order: source row == env id, what
+                                    every action writer takes as `rows`; they skip negative rows)                                     */
+  int32_t*  rows_tiled;          /* optional [16 * n_tiles_max], with tile_slot: the envs whose member has a slot, grouped by slot in
+                                    ascending slot, ascending env id inside a slot, every slot's segment padded with -1 to whole tiles
+                                    of 16 rows; -1 in the unused tiles at the end                                                     */
+  int32_t*  tile_slot;           /* optional [n_tiles_max], with rows_tiled: the slot of tile t, -1 for the unused tiles at the end    */
+  int32_t*  counts;              /* optional [S]: envs per member                                                                     */
+  int32_t S;                     /* 1 .. CG_MIXTURE_MAX_MEMBERS                                                                        */
+  int32_t role_mode;             /* the plain mode word of the opponent's role (CG_MODE_DEFENDER / CG_MODE_ATTACKER)                   */
+  int32_t n_tiles_max;           /* tiles rows_tiled / tile_slot hold: >= ceil(n_envs / 16) + S (an upper bound the host knows)        */
+  int32_t reserved;
+} cygym_mixture;
+
+/* Replaces: `idx = np.random.choice(len(opponent_strategies), p=opponent_equilibrium)` on every opponent turn of the reference's
+ * best-response trainers (do_agent.py:1447, IPPO.py:392, hierarchical_br.py:363) and the persisting `env.base_line =
+ * strat.baseline_name` of a baseline member (do_agent.py:718, IPPO.py:396, hierarchical_br.py:367), for ALL n_envs envs of the bound
+ * handle in ONE launch, together with the row lists the members' action writers need.
+ * Draw (CG_SITE_MIXTURE): u = word 0 / 2^32 of the draw addressed (global env id, the env's current rng tick, a = b = 0), in f64;
+ * index = #{ j : cdf[j] <= u }.  The rng tick is read, never advanced.  Where the drawn member is a baseline, baseline_state[e] is
+ * overwritten with its code BEFORE mode[e] is formed.
+ * One workgroup walks the envs in ascending chunks; counts, ranks and the scatter come from ballots and prefix sums, never from
+ * atomics: every output is the same on every run.  Nothing synchronises with the host.
+ * Limits: 1 <= S <= 32 and n_envs <= 65536 (CYGYM_EUNSUPPORTED otherwise, nothing is launched).  CYGYM_EINVAL: a NULL handle, struct or
+ * required pointer (cdf, member_baseline, member_slot, baseline_state, index_out, mode), rows_tiled without tile_slot or the other
+ * way round, n_tiles_max < ceil(n_envs / 16) + S with them.  CYGYM_ENOTBOUND without cygym_bind. */
+int cygym_mixture_draw(cygym_handle* h, const cygym_mixture* mix, void* stream);
+
+/* cygym_actor_mlp_decode for a population whose rows follow a DRAW instead of arithmetic: mlp->n_groups = number of slots (the packed
+ * matrices / biases of slot a follow those of slot a - 1, as in cygym_actor_mlp; rows_per_group is not read), layout->rows =
+ * rows_tiled and layout->n = 16 * n_tiles of cygym_mixture_draw.  The workgroup of tile t takes the weights of actor tile_slot[t]
+ * (DEVICE int32 [n_tiles]) and returns as a whole, before its first barrier, when tile_slot[t] is negative (or not below n_groups).
+ * The observation of a row is that of its env: mlp->obs_by_env or mlp->obs_role must be set (CYGYM_EINVAL otherwise).  Rows of -1 are
+ * skipped.  Every other check and limit is cygym_actor_mlp_decode's, the chunked head of more than 512 outputs included. */
+int cygym_actor_mlp_decode_tiled(cygym_handle* h, const cygym_actor_mlp* mlp, const cygym_action_vectors* layout,
+                                 const int32_t* tile_slot, int32_t n_tiles, const cygym_actions* dst, void* stream);
 
 /* The per-device actor-critic of the reference's IPPO / MAPPO agents with USE_GAT off, as the reference ships it (IPPO.py:21,
  * MAPPO.py:21): CommActorCritic (IPPO.py:135-196, MAPPO.py the same) in the pieces the decode below reads, all fp32, DEVICE

@@ -231,8 +231,14 @@ enum {
   CG_SITE_DNS_EPS = 80,      /* :972-973 inside generate_neighbors: a = 0, b as above; word 0 the coin (u < ceil(eps * 2^32)), word 1 the
                                 uniform type index, as CG_SITE_EPS_TYPE                                           */
   CG_SITE_DNS_ACCEPT = 81,   /* :1239 random.random() < prob: a = 0, b = itr; u = word 0 / 2^32, compared in f64      */
-  CG_SITE_DNS_CHOICE = 82    /* :1243 random.choice(list(K_all)): a = 0, b = itr; index = cg_index(word 0, len(K_all)) into K_all in
+  CG_SITE_DNS_CHOICE = 82,   /* :1243 random.choice(list(K_all)): a = 0, b = itr; index = cg_index(word 0, len(K_all)) into K_all in
                                 first-insertion order                                                              */
+  CG_SITE_MIXTURE = 83       /* do_agent.py:1447 / IPPO.py:392 / hierarchical_br.py:363 np.random.choice(n, p=equilibrium): the opponent
+                                strategy drawn from the equilibrium mixture on every opponent turn (cygym_mixture_draw): a = b = 0;
+                                numpy's own mapping -- cdf = p.cumsum(); cdf /= cdf[-1], formed by the HOST in f64 with numpy;
+                                u = word 0 / 2^32 in f64; index = #{ j : cdf[j] <= u } (searchsorted side='right').  A member of
+                                probability 0 is never drawn and u < 1 = cdf[-1] needs no clamp.  The env's rng tick, read and not
+                                advanced, like CG_SITE_COORD_PICK                                                  */
 };
 
 /* ---- Philox4x32-10 (Salmon et al., SC'11), counter-based ----
