@@ -149,6 +149,19 @@ class CommActor(C.Structure):
                 ("tok_stride", C.c_int32), ("reserved", C.c_int32)]
 
 
+GAT_MAX_LAYERS, GAT_MAX_DEVICES = 4, 1024
+
+
+class GatLayer(C.Structure):
+    _fields_ = [("w_q", C.c_void_p), ("w_k", C.c_void_p), ("w_v", C.c_void_p), ("w_proj", C.c_void_p), ("b_proj", C.c_void_p),
+                ("ln_w", C.c_void_p), ("ln_b", C.c_void_p)]
+
+
+class CommGat(C.Structure):
+    _fields_ = [("layer", GatLayer * GAT_MAX_LAYERS), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64), ("n_layers", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class CommEval(C.Structure):
     _fields_ = [("tok_base", C.c_void_p), ("tok_dev", C.c_void_p), ("w_type", C.c_void_p), ("w_type_rows", C.c_void_p), ("b_type", C.c_void_p),
                 ("types", C.c_void_p), ("vis", C.c_void_p), ("logp_dev", C.c_void_p), ("logp_lo", C.c_void_p), ("ent_dev", C.c_void_p), ("ctx", C.c_void_p),

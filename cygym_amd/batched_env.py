@@ -862,7 +862,7 @@ class BatchedCyberDefenseEnv:
         return types, exp_o, app_o, logp
 
     def comm_actor_decode(self, rows, tok_base: torch.Tensor, pack, role: str = "defender", noop: int | None = None, single_types=(11, 12),
-                          greedy: bool = False, act=None, logits_out=None, exp_logits_out=None, app_logits_out=None):
+                          greedy: bool = False, act=None, logits_out=None, exp_logits_out=None, app_logits_out=None, _gat=None):
         """The per-device actor-critic of IPPO / MAPPO (CommActorCritic.forward with USE_GAT off, IPPO.py:135-196), the sampling
         (:524-557) and the grouping (:560-572) for a batch in ONE launch (cygym_comm_actor_decode; include/cygym_abi.h states the
         arithmetic): tokens, pooled context, heads, value, one Categorical per VISIBLE device (the role's mask, read off the flag
@@ -907,8 +907,47 @@ class BatchedCyberDefenseEnv:
                     raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {self.device}")
                 setattr(net, name, t.data_ptr())
         r = _bind_rows(self, src, rows, n)   # noqa: F841 (alive until the call has returned)
+        if _gat is not None:   # (comm_gat_decode: the same marshalling, the launch with the attention layers)
+            _lib.check(self.lib.cygym_comm_gat_decode(self._h, C.byref(net), C.byref(_gat), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_gat_decode")
+            return types, exp_o, app_o, logp, value
         _lib.check(self.lib.cygym_comm_actor_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_actor_decode")
         return types, exp_o, app_o, logp, value
+
+    def comm_gat_workspace(self, H: int):
+        """The workspace cygym_comm_gat_decode needs on this batch for hidden width H (None when every row fits in LDS), allocated
+        once per width and kept: call it before a loop that is captured into a graph."""
+        cache = self.__dict__.setdefault("_gat_ws", {})
+        if int(H) not in cache:
+            nbytes = int(self.lib.cygym_comm_gat_workspace_bytes(self._h, int(H)))
+            cache[int(H)] = torch.empty((nbytes // 4,), dtype=torch.float32, device=self.device) if nbytes else None
+        return cache[int(H)]
+
+    def comm_gat_decode(self, rows, tok_base: torch.Tensor, pack, role: str = "defender", noop: int | None = None, single_types=(11, 12),
+                        greedy: bool = False, act=None, logits_out=None, exp_logits_out=None, app_logits_out=None, workspace=None):
+        """comm_actor_decode for a net WITH attention layers (CommActorCritic.forward with USE_GAT = True, IPPO.py:114-196) in ONE
+        launch (cygym_comm_gat_decode; include/cygym_abi.h states the arithmetic and the limits).  Arguments and results are those of
+        comm_actor_decode; `pack` (policies.CommActorCritic.packed() of a net with gat_layers > 0) also holds "gat": per layer a dict
+        with w_q, w_k, w_v, w_proj (pack_linear), b_proj, ln_w, ln_b [H].  workspace: a float32 tensor of comm_gat_workspace(H)'s
+        size (default: that cached tensor).  1 <= layers <= 4, M <= 1024."""
+        layers = pack.get("gat") or []
+        if not layers:
+            raise ValueError("pack['gat'] holds no layer: this net has no attention layers (comm_actor_decode)")
+        H = int(tok_base.shape[1]) if tok_base.dim() == 2 else 0
+        g = abi.CommGat()
+        g.n_layers = len(layers)
+        for l, ly in enumerate(layers[:abi.GAT_MAX_LAYERS]):   # (more than that: the library answers CYGYM_EUNSUPPORTED)
+            for name in ("w_q", "w_k", "w_v", "w_proj", "b_proj", "ln_w", "ln_b"):
+                t = ly[name]
+                want = H * H if name.startswith("w_") else H
+                if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or (H % 16 == 0 and int(t.numel()) != want):
+                    raise ValueError(f"pack['gat'][{l}][{name!r}] must be a contiguous float32 tensor of {want} values on {self.device}")
+                setattr(g.layer[l], name, t.data_ptr())
+        ws = self.comm_gat_workspace(H) if workspace is None and H % 16 == 0 and 16 <= H <= 128 else workspace
+        if ws is not None:
+            if ws.dtype != torch.float32 or ws.device != self.device or not ws.is_contiguous():
+                raise ValueError(f"workspace must be a contiguous float32 tensor on {self.device}")
+            g.workspace, g.workspace_bytes = ws.data_ptr(), int(ws.numel()) * 4
+        return self.comm_actor_decode(rows, tok_base, pack, role, noop, single_types, greedy, act, logits_out, exp_logits_out, app_logits_out, _gat=g)
 
     def hier_decode(self, rows, h0: torch.Tensor, pack, role: str = "defender", act=None, vis_fixed=None, type_map=None,
                     score_out=None, part_score_out=None, part_out=None, atype_logits_out=None, dev_logits_out=None):

@@ -32,6 +32,7 @@
 #define CG_MAIN_UNIT 1
 #include "cg_device.hpp"
 #include "cg_iforest.hpp"
+#include <map>
 #include <mutex>
 #include <set>
 #include <type_traits>
@@ -74,6 +75,13 @@ extern template __global__ void dns_kernel<true>(cygym_critic, cygym_dns, cygym_
 namespace cygym_k {
 extern template __global__ void comm_actor_kernel<false>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 extern template __global__ void comm_actor_kernel<true>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+}  // namespace cygym_k
+
+// ... and the same network with its attention layers (cg_inst_comm_gat.hip)
+namespace cygym_k {
+#include "cg_comm_gat.hpp"
+extern template __global__ void comm_gat_kernel<false>(cygym_comm_actor, cygym_comm_gat, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+extern template __global__ void comm_gat_kernel<true>(cygym_comm_actor, cygym_comm_gat, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 }  // namespace cygym_k
 
 // the hierarchical (HAGS) decode lives in its own unit (cg_inst_hier.hip): declared, not instantiated, here
@@ -287,6 +295,7 @@ int cygym_sizeof(int32_t which) {
     case 29: return (int)sizeof(cygym_hmarl_train);
     case 31: return (int)sizeof(cygym_dns);   // (index 30 stays unassigned)
     case 33: return (int)sizeof(cygym_mixture);   // (index 32 stays unassigned)
+    case 35: return (int)sizeof(cygym_comm_gat);   // (index 34 stays unassigned)
     default: return -1;
   }
 }
@@ -992,6 +1001,72 @@ int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const 
   const uint8_t* live = h->b.live;
   int M = h->t.M;
   return launch_decode(h, k, dim3((src->n + CM_WAVES - 1) / CM_WAVES), dim3(CM_THREADS), lds, stream, {net, src, dst}, {&live, &M});   // 16 rows per workgroup
+}
+
+// Workgroups of cygym_comm_gat_decode on this handle's device: one or two per CU (by the LDS a workgroup takes), never more than rows.
+static int gat_grid(cygym_handle* h, int lds_bytes, int n, int* grid) {
+  static std::mutex mu;
+  static std::map<int, int> cus;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!cus.count(h->device_id)) {
+    int c = 0;
+    HIPCHK(h, hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, h->device_id));
+    cus[h->device_id] = c < 1 ? 1 : c;
+  }
+  const int g = cus[h->device_id] * (2 * lds_bytes <= CG_LDS_BYTES ? 2 : 1);
+  *grid = n > 0 && n < g ? n : g;
+  return CYGYM_OK;
+}
+uint64_t cygym_comm_gat_workspace_bytes(cygym_handle* h, int32_t H) {
+  if (!h || H < 16 || H > CM_MAX_H || (H & 15) || h->t.M > GT_MAX_M) return 0;
+  const int M = h->t.M, n16 = (M + 15) & ~15;
+  const GtPlan pl = gt_plan(H, M);
+  if (gt_need(n16, H) <= pl.cap) return 0;
+  int grid = 0;
+  if (gat_grid(h, pl.total * (int)sizeof(float), 0, &grid)) return 0;
+  return (uint64_t)grid * (uint64_t)gt_need(n16, H) * sizeof(float);
+}
+int cygym_comm_gat_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_comm_gat* gat, const cygym_device_logits* src,
+                          const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_comm_gat_decode";
+  const char* const bad_layout = "cygym_comm_gat_decode: bad layout (types, exploit logits >= 1, tok_stride >= H, role 1 or 2, 16-byte aligned tok_dev / w_type / w_ctx / layer matrices / workspace)%s";
+  if (h && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_comm_gat_decode: handle not bound (the visibility mask is read off the flag plane, the draws at the envs' rng ticks)%s", "");
+  cygym_action_vectors lay;
+  memset(&lay, 0, sizeof(lay));
+  if (h && src) { lay.n_types = src->n_types; lay.n_devices = h->t.M; lay.n_exploits = src->n_exp; lay.n_apps = src->n_app; }
+  const bool own = net && gat && src && net->tok_base && net->tok_dev && net->w_type && net->b_type && net->w_ctx && net->b_ctx && net->w_v2 &&
+                   net->value_out && src->types_out;
+  if (const int rc = check_vectors(h, src ? &lay : nullptr, dst, who, own, 1, bad_layout)) return rc;
+  if (const int rc = check_dst(h, dst, who, true)) return rc;
+  if (net->H < 1 || net->tok_stride < net->H || (src->role != 1 && src->role != 2) ||
+      (((uintptr_t)net->tok_dev | (uintptr_t)net->w_type | (uintptr_t)net->w_ctx | (uintptr_t)gat->workspace) & 15))
+    return fail(h, CYGYM_EINVAL, bad_layout, "");
+  if (gat->n_layers < 1 || gat->n_layers > GT_MAX_L)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_gat_decode: 1 .. 4 attention layers%s", "");
+  for (int l = 0; l < gat->n_layers; ++l) {
+    const cygym_gat_layer& y = gat->layer[l];
+    if (!y.w_q || !y.w_k || !y.w_v || !y.w_proj || !y.b_proj || !y.ln_w || !y.ln_b) return fail(h, CYGYM_EINVAL, "%s: null layer pointer", who);
+    if (((uintptr_t)y.w_q | (uintptr_t)y.w_k | (uintptr_t)y.w_v | (uintptr_t)y.w_proj) & 15) return fail(h, CYGYM_EINVAL, bad_layout, "");
+  }
+  if (net->H < 16 || net->H > CM_MAX_H || (net->H & 15) || src->n_types > CM_MAX_HEAD || src->n_exp > CM_MAX_HEAD || src->n_app > CM_MAX_HEAD)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_gat_decode: H must be a multiple of 16 in 16 .. 128, at most 32 action types, exploit and app logits%s", "");
+  if (h->t.M > GT_MAX_M) return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_gat_decode: at most 1024 devices%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  int M = h->t.M;
+  const GtPlan pl = gt_plan(net->H, M);
+  const size_t lds = (size_t)pl.total * sizeof(float);
+  if (lds > CG_LDS_BYTES || pl.cap < gt_need(16, net->H)) return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_gat_decode: the per-row buffers do not fit in LDS%s", "");
+  int grid = 0;
+  if (const int rc = gat_grid(h, (int)lds, src->n, &grid)) return rc;
+  const uint64_t need = (uint64_t)gt_need((M + 15) & ~15, net->H);
+  if (need > (uint64_t)pl.cap && (!gat->workspace || gat->workspace_bytes < (uint64_t)grid * need * sizeof(float)))
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_gat_decode: an all-visible row does not fit in LDS at this size: pass a workspace of cygym_comm_gat_workspace_bytes()%s", "");
+  const void* k = net->logits_out ? (const void*)comm_gat_kernel<true> : (const void*)comm_gat_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const uint8_t* live = h->b.live;
+  return launch_decode(h, k, dim3(grid), dim3(GT_THREADS), lds, stream, {net, gat, src, dst}, {&live, &M});   // a workgroup per row, walking over the rows
 }
 
 // cygym_hier_decode (smp == NULL) and cygym_hier_sample_decode: one argument check, one launch shape.

@@ -214,8 +214,9 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
             vis = batch.visibility_mask(role)
             if fused:
                 pk = net.packed(batch)
-                t8, e32, a32, logp, value = batch.comm_actor_decode(None, net.tok_base(obs, pk), pk, role, noop=noop, single_types=SINGLE_DEVICE_TYPES,
-                                                                    greedy=greedy, act=act)
+                decode = batch.comm_gat_decode if net.gat_layers else batch.comm_actor_decode   # (attention layers: cygym_comm_gat_decode)
+                t8, e32, a32, logp, value = decode(None, net.tok_base(obs, pk), pk, role, noop=noop, single_types=SINGLE_DEVICE_TYPES,
+                                                   greedy=greedy, act=act)
                 types, exp_i, app_i, out = t8.to(torch.int64), e32.to(torch.int64), a32.to(torch.int64), {"value": value}
                 pdt = None
             else:
@@ -296,7 +297,7 @@ def ppo_loss(logp, entropy, value, old_logp, old_value, adv, ret, *, clip_eps: f
 
 def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minibatch_size: int = 256, generator=None, fused=None,
                gamma: float = 0.99, lam: float = 0.95, clip_eps: float = CLIP_EPS, ent_coef: float = ENT_COEF, vf_coef: float = VF_COEF,
-               max_grad_norm: float = MAX_GRAD_NORM):
+               max_grad_norm: float = MAX_GRAD_NORM, first_row_mask: bool = False):
     """The PPO update of IPPOCommBestResponse.train (IPPO.py:626-781) on a Rollout: the bootstrap value from rollout.last_state,
     `advantages`, then `epochs` passes over the T N rows, flattened and shuffled (torch.randperm with `generator`) into minibatches
     of `minibatch_size`; per minibatch net.evaluate (fused on `batch` by default, see CommActorCritic.evaluate), `ppo_loss`,
@@ -307,9 +308,18 @@ def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minib
 
     The reference's loop as shipped collects exactly ONE Step per update (`while len(local_batch) == 0`, :503): for T N = 1 this
     function is that update.  For more rows it is the same formulas, which the reference writes for a minibatch.  Out of scope:
-    USE_GAT, AMP, the budget bookkeeping and the progress prints."""
+    AMP, the budget bookkeeping and the progress prints.
+
+    A net with attention layers (CommActorCritic(gat_layers > 0), USE_GAT = True) is evaluated on the torch path, through autograd
+    (there is no fused backward through the attention).  Its layers read every row's OWN stored mask.  The reference's update
+    instead masks the adjacency of the WHOLE minibatch with the visibility of the minibatch's first row (`v0 = mb_vis[0]`,
+    IPPO.py:713-717) -- for its one-row updates the same thing; first_row_mask=True reproduces that for larger minibatches (the
+    log-probabilities are still selected by each row's own mask, :725-737)."""
+    gat = bool(getattr(net, "gat_layers", 0))
+    if gat and fused:
+        raise NotImplementedError("a net with attention layers has no fused evaluate: ppo_update runs its torch path")
     with torch.no_grad():
-        next_value = net(rollout.last_state)["value"].reshape(-1)
+        next_value = (net(rollout.last_state, rollout.last_vis) if gat else net(rollout.last_state))["value"].reshape(-1)
         adv, ret = advantages(rollout, next_value, gamma, lam)
     T, N = rollout.logp.shape
     B = T * N
@@ -322,7 +332,11 @@ def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minib
         for start in range(0, B, int(minibatch_size)):
             mb = perm[start: start + int(minibatch_size)]
             adv_mb, ret_mb = adv[mb], ret[mb].clamp(-VALUE_TARGET_CLIP, VALUE_TARGET_CLIP)
-            logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], batch=batch, fused=fused)
+            if gat:
+                ev = vis[mb][:1].expand(len(mb), -1) if first_row_mask else None
+                logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], fused=False, eval_vis=ev)
+            else:
+                logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], batch=batch, fused=fused)
             loss, pol, v_loss, ent_mean = ppo_loss(logp, ent, value, old_logp[mb], old_value[mb], adv_mb, ret_mb, clip_eps=clip_eps,
                                                    ent_coef=ent_coef, vf_coef=vf_coef)
             if not bool((torch.isfinite(adv_mb).all() & torch.isfinite(ret_mb).all() & torch.isfinite(loss)).item()):

@@ -42,6 +42,8 @@ observer's selection with the reference's frozen embedding cache and the kept de
 """
 from __future__ import annotations
 
+import math
+
 import torch
 from torch import nn
 
@@ -859,32 +861,64 @@ class _CommEvaluate(torch.autograd.Function):
         return None, None, None, ga, gp, gw, gb
 
 
+class GATLayer(nn.Module):
+    """The reference's attention layer (IPPO.py:114-130) under its parameter names: q, k, v without bias, proj, ln."""
+
+    def __init__(self, hidden: int):
+        super().__init__()
+        self.q = nn.Linear(hidden, hidden, bias=False)
+        self.k = nn.Linear(hidden, hidden, bias=False)
+        self.v = nn.Linear(hidden, hidden, bias=False)
+        self.proj = nn.Linear(hidden, hidden)
+        self.ln = nn.LayerNorm(hidden)
+
+    def forward(self, x, adj, dtype=None):
+        dt = x.dtype if dtype is None else dtype
+        lin = lambda m, t: torch.nn.functional.linear(t, m.weight.to(dt), None if m.bias is None else m.bias.to(dt))  # noqa: E731
+        q, k, v = lin(self.q, x), lin(self.k, x), lin(self.v, x)
+        scores = torch.matmul(q, k.transpose(1, 2)) / math.sqrt(x.shape[-1])
+        scores = scores.masked_fill(adj <= 0, -1e9)
+        out = lin(self.proj, torch.matmul(torch.softmax(scores, dim=-1), v))
+        return torch.nn.functional.layer_norm(x + out, (x.shape[-1],), self.ln.weight.to(dt), self.ln.bias.to(dt), self.ln.eps)
+
+
 class CommActorCritic(nn.Module):
     """The per-device actor-critic of the reference's IPPO / MAPPO agents as it runs with USE_GAT = False (IPPO.py:21, :135-196;
     MAPPO.py the same), with the reference's parameter names, so that a state dict saved there loads here:
         hs = relu(state_proj(state));  tok[d] = relu(merge([hs, id_emb[d]]));  ctx = mean over all D tokens
         per_dev_type_logits = dev_type_head(tok);  exp_logits = exp_head(ctx);  app_logits = app_head(ctx) (A > 0)
         value = v_head(ctx) (Linear - ReLU - Linear);  every output through nan_to_num(0, 0, 0)
-    The attention layers (`gats.*`) never influence these outputs while USE_GAT is off: they are not built, and their entries of
-    a state dict are accepted and ignored.
+    The attention layers (`gats.*`) never influence these outputs while USE_GAT is off: with gat_layers = 0 (the default) they are
+    not built, and their entries of a state dict are accepted and ignored.
+    gat_layers = n > 0 is the network with USE_GAT = True (IPPO.py:114-130, :173-175): `gats` holds n GATLayer under the reference's
+    names (the reference always builds 2), load_state_dict loads them, forward(state, vis) runs the tokens through them over
+    ippo_rollout.masked_adjacency(vis) -- the reference's dense function -- before the heads and the pooled context, packed() adds
+    the packed layers and the closed loop runs through cygym_comm_gat_decode.  evaluate() of such a net is the torch path
+    (fused=False, through autograd); a fused evaluate / backward through the attention is out of scope.
     forward() is the unfactorised network in torch -- the restatement the fused kernel is tested against (dtype=torch.float64)
     and the torch path of ippo_rollout.collect.  factors() / packed() give the form cygym_comm_actor_decode reads:
     tok[d] = relu(a + P[d]) with a = merge.bias + merge.weight[:, :H] hs (one vector per env) and the env-independent table
     P[d] = merge.weight[:, H:] id_emb[d]."""
 
-    def __init__(self, state_dim: int, n_types: int, D: int, E: int, A: int, hidden: int = 128):
+    def __init__(self, state_dim: int, n_types: int, D: int, E: int, A: int, hidden: int = 128, gat_layers: int = 0):
         super().__init__()
         self.state_dim, self.n_types, self.D, self.E, self.A, self.hidden = int(state_dim), int(n_types), int(D), int(E), int(A), int(hidden)
+        self.gat_layers = int(gat_layers)
+        if self.gat_layers < 0:
+            raise ValueError("gat_layers must be >= 0")
         self.state_proj = nn.Linear(self.state_dim, self.hidden)
         self.id_emb = nn.Embedding(self.D, self.hidden)
         self.merge = nn.Linear(2 * self.hidden, self.hidden)
+        if self.gat_layers:      # (registered between merge and the heads, like the reference's module: the same initialisation order)
+            self.gats = nn.ModuleList([GATLayer(self.hidden) for _ in range(self.gat_layers)])
         self.dev_type_head = nn.Linear(self.hidden, self.n_types)
         self.exp_head = nn.Linear(self.hidden, self.E)
         self.app_head = nn.Linear(self.hidden, self.A) if self.A > 0 else None
         self.v_head = nn.Sequential(nn.Linear(self.hidden, self.hidden), nn.ReLU(), nn.Linear(self.hidden, 1))
 
     def load_state_dict(self, state_dict, *args, **kwargs):
-        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("gats.")}, *args, **kwargs)
+        keep = tuple(f"gats.{l}." for l in range(self.gat_layers))   # (a reference dict carries 2 layers: those this net has are loaded)
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("gats.") or k.startswith(keep)}, *args, **kwargs)
 
     @staticmethod
     def _lin(m, x, dtype):
@@ -892,12 +926,20 @@ class CommActorCritic(nn.Module):
 
     def forward(self, state, vis=None, dtype=None):
         """state [B, state_dim] -> the reference's dict: per_dev_type_logits [B, D, K], exp_logits [B, E], app_logits [B, A] or
-        None, value [B].  `vis` (the role's visibility mask, what a GAT would read) is accepted and unused.  dtype: evaluate in
-        that precision from the same fp32 parameters (float64: the restatement)."""
+        None, value [B].  `vis` [B, D] (the role's visibility mask): unused without attention layers; with gat_layers > 0 it is
+        mandatory and the tokens pass through the layers over ippo_rollout.masked_adjacency(vis).  dtype: evaluate in that precision
+        from the same fp32 parameters (float64: the restatement)."""
         dt = state.dtype if dtype is None else dtype
         B = state.shape[0]
         hs = torch.relu(self._lin(self.state_proj, state.to(dt), dt))
         tok = torch.relu(self._lin(self.merge, torch.cat([hs[:, None, :].expand(B, self.D, -1), self.id_emb.weight.to(dt)[None].expand(B, -1, -1)], -1), dt))
+        if self.gat_layers:
+            if vis is None:
+                raise ValueError("a net with attention layers needs the visibility mask: forward(state, vis)")
+            from .ippo_rollout import masked_adjacency
+            adj = masked_adjacency(vis)
+            for gat in self.gats:
+                tok = gat(tok, adj, dt)
         ctx = tok.mean(dim=1)
         clean = lambda t: torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0)  # noqa: E731
         return {"per_dev_type_logits": clean(self._lin(self.dev_type_head, tok, dt)),
@@ -912,7 +954,7 @@ class CommActorCritic(nn.Module):
         hs = torch.relu(self._lin(self.state_proj, state.to(dt), dt))
         return hs @ w[:, :H].t() + self.merge.bias.to(dt), self.id_emb.weight.to(dt) @ w[:, H:].t()
 
-    def evaluate(self, state, types, vis, exp, app=None, *, batch=None, fused=None, dtype=None):
+    def evaluate(self, state, types, vis, exp, app=None, *, batch=None, fused=None, dtype=None, eval_vis=None):
         """The PPO update's evaluation of STORED decisions under the current weights (IPPO.py:719-749), vectorised over the batch:
             logp    [B] = sum over visible devices of log_softmax(type logits)[stored type] + the exploit's (+ the app's, A > 0),
                           accumulated and returned in float64 on both paths: the sum is some tens of nats, and one fp32 unit in its
@@ -928,7 +970,14 @@ class CommActorCritic(nn.Module):
         backward -- as the library's two launches (cygym_comm_actor_evaluate / _backward behind one autograd.Function; neither
         tokens nor logits reach HBM); the heads of ctx stay in torch ([B, H] products).
         fused=False: the same quantities from forward() with one log_softmax over [B, D, K]; runs anywhere, in `dtype`
-        (torch.float64: the restatement the fused path is tested against)."""
+        (torch.float64: the restatement the fused path is tested against).
+        eval_vis [B, D] (attention layers only): the mask the LAYERS read, where it differs from the stored `vis` that selects the
+        log-probabilities -- ippo_rollout.ppo_update(first_row_mask=True) reproduces the reference's update with it."""
+        if self.gat_layers:
+            if fused:
+                raise NotImplementedError("a net with attention layers has no fused evaluate (no backward through the attention in the "
+                                          "library): evaluate(fused=False) runs the torch path through autograd")
+            fused = False
         fused = batch is not None if fused is None else bool(fused)
         visb = vis > 0.5 if vis.dtype != torch.bool else vis
         tgt = torch.where(visb, types.long().clamp(0, self.n_types - 1), torch.zeros_like(types, dtype=torch.long))
@@ -947,7 +996,7 @@ class CommActorCritic(nn.Module):
             app_logits = clean(self._lin(self.app_head, ctx, dt)) if self.app_head is not None else None
             value = clean(self._lin(self.v_head[2], torch.relu(self._lin(self.v_head[0], ctx, dt)), dt).squeeze(-1))
         else:
-            out = self.forward(state, dtype=dtype)
+            out = self.forward(state, (visb if eval_vis is None else eval_vis).to(torch.float32), dtype=dtype)
             lp = torch.log_softmax(out["per_dev_type_logits"], dim=-1)                      # [B, D, K]
             m = visb.to(lp.dtype)
             logp = (lp.gather(-1, tgt[:, :, None])[:, :, 0] * m).sum(dim=1, dtype=torch.float64)
@@ -964,7 +1013,10 @@ class CommActorCritic(nn.Module):
         """What cygym_comm_actor_decode reads, as a dict (BatchedCyberDefenseEnv.comm_actor_decode): the table tok_dev, the packed
         heads, and the transposed matrices of the two addmm of tok_base().  Built once per parameter version."""
         mods = [self.state_proj, self.merge, self.dev_type_head, self.exp_head, self.v_head[0], self.v_head[2]] + ([self.app_head] if self.app_head is not None else [])
+        mods += [g.proj for g in self.gats] + [g.ln for g in self.gats] if self.gat_layers else []
         ver = tuple((m.weight._version, m.weight.data_ptr(), m.bias._version) for m in mods) + ((self.id_emb.weight._version, self.id_emb.weight.data_ptr()),)
+        if self.gat_layers:
+            ver += tuple((m.weight._version, m.weight.data_ptr()) for g in self.gats for m in (g.q, g.k, g.v))
         if getattr(self, "_pk_ver", None) != ver:
             from .batched_env import BatchedCyberDefenseEnv as B
             H = self.hidden
@@ -980,6 +1032,10 @@ class CommActorCritic(nn.Module):
                     "w_ctx": B.pack_linear(torch.cat([m.weight.detach() for m in heads])), "b_ctx": torch.cat([m.bias.detach() for m in heads]).contiguous(),
                     "w_v2": self.v_head[2].weight.detach().reshape(-1).contiguous(), "b_v2": float(self.v_head[2].bias.detach().reshape(-1)[0]),
                 }
+                if self.gat_layers:   # what cygym_comm_gat_decode reads on top (BatchedCyberDefenseEnv.comm_gat_decode)
+                    self._pk["gat"] = [{"w_q": B.pack_linear(g.q.weight), "w_k": B.pack_linear(g.k.weight), "w_v": B.pack_linear(g.v.weight),
+                                        "w_proj": B.pack_linear(g.proj.weight), "b_proj": g.proj.bias.detach().contiguous(),
+                                        "ln_w": g.ln.weight.detach().contiguous(), "ln_b": g.ln.bias.detach().contiguous()} for g in self.gats]
             self._pk_ver = ver
         return self._pk
 
@@ -1015,7 +1071,8 @@ class CommActorPolicy:
             raise ValueError(f"obs must be a float32 [n, {self.net.state_dim}] role view")
         if batch.M != self.net.D:
             raise ValueError(f"the net was built for {self.net.D} devices, the batch has {batch.M}")
-        batch.comm_actor_decode(rows, self.net.tok_base(obs, pk), pk, self.role, noop=self.noop, greedy=self.greedy, act=act)
+        decode = batch.comm_gat_decode if self.net.gat_layers else batch.comm_actor_decode   # (with the attention layers: cygym_comm_gat_decode)
+        decode(rows, self.net.tok_base(obs, pk), pk, self.role, noop=self.noop, greedy=self.greedy, act=act)
 
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("a CommActorPolicy answers with groups of devices per action type: a dict of single actions cannot "

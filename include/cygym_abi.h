@@ -650,10 +650,73 @@ typedef struct cygym_comm_actor {
  * Limits (CYGYM_EUNSUPPORTED beyond): H a multiple of 16 in 16 .. 128; K, E, A <= 32; any M of the handle whose per-row buffers fit in
  * LDS (every M <= 2048 does).  CYGYM_EINVAL (the argument check the decodes share): NULL mandatory pointers, K < 1, E < 1, A < 0,
  * tok_stride < H, a role other than 1 / 2, a packed matrix or tok_dev off 16-byte alignment.  CYGYM_ENOTBOUND without cygym_bind.
- * Out of scope: USE_GAT = True (the attention layers over masked_adjacency), populations of nets in one launch, and building the
- * observation on chip (tok_base comes from the caller).  The PPO update evaluates stored decisions with cygym_comm_actor_evaluate below. */
+ * Out of scope: populations of nets in one launch, and building the observation on chip (tok_base comes from the caller).  The
+ * attention layers of USE_GAT = True are cygym_comm_gat_decode below.  The PPO update evaluates stored decisions with
+ * cygym_comm_actor_evaluate below. */
 int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst,
                             void* stream);
+
+/* The attention layers of that network (USE_GAT = True: GATLayer, IPPO.py:114-130, over masked_adjacency, :98-109), fp32, DEVICE
+ * pointers.  q / k / v / proj weights [H][H] packed like w_type above (pack_linear), 16-byte aligned; q, k, v have no bias. */
+#define CYGYM_GAT_MAX_LAYERS 4
+#define CYGYM_GAT_MAX_DEVICES 1024
+typedef struct cygym_gat_layer {
+  const float* w_q;
+  const float* w_k;
+  const float* w_v;
+  const float* w_proj;
+  const float* b_proj;        /* [H] */
+  const float* ln_w;          /* [H] LayerNorm weight (eps 1e-5, biased variance) */
+  const float* ln_b;          /* [H] */
+} cygym_gat_layer;
+typedef struct cygym_comm_gat {
+  cygym_gat_layer layer[CYGYM_GAT_MAX_LAYERS];
+  float* workspace;           /* optional, 16-byte aligned: x | k | v^T of a row's visible devices when they do not fit in LDS        */
+  uint64_t workspace_bytes;   /* its size; at least cygym_comm_gat_workspace_bytes() when a row can need it                           */
+  int32_t n_layers;           /* L: 1 .. CYGYM_GAT_MAX_LAYERS (the reference: 2)                                                      */
+  int32_t reserved;
+} cygym_comm_gat;
+
+/* Replaces: CommActorCritic.forward with USE_GAT = True (IPPO.py:114-196), the sampling (:524-557) and the grouping (:560-572) for a
+ * batch in ONE launch -- cygym_comm_actor_decode with the L attention layers between the tokens and the heads.  `net`, `src`, `dst` are
+ * those of cygym_comm_actor_decode and mean the same.  The adjacency is what the reference produces: build_adjacency is all ones for its
+ * Subnet, so masked_adjacency is v v^T with the diagonal set to v, v the role's visibility mask (read off the bound flag plane).  Hence
+ *   a VISIBLE query attends to the visible keys only (a masked score is -1e9: its exponential is exactly 0 in fp32 beside any unmasked one);
+ *   an INVISIBLE query has a row of -1e9 only: its softmax is uniform over ALL M devices, its attention output is u = v.weight mean_all(x),
+ *   the same for every invisible device, and the layer is x_i <- LayerNorm(x_i + c), c = proj(u): no matrix product per device.
+ * One workgroup of 8 waves works on one source row and walks over the rows (grid = min(n, one or two workgroups per CU): the workspace is sized by the grid, not by n).
+ * Arithmetic, fp32 throughout:
+ *   x0[d]       = relu(a + P[d]) (x < 0 ? 0 : x).
+ *   mean_l      = sum over all devices of x_l / M, for l = 0 .. L (mean_L = ctx): wave w of 8 adds, in one running sum per column, first the
+ *                 invisible devices at the positions w, w + 8, .. of their ascending list -- each x_l[d] recomputed from x0 through the l
+ *                 LayerNorms -- then the visible devices at the positions w, w + 8, .. of theirs; the 8 partial sums are added w ascending,
+ *                 then one division by M.
+ *   u, c, heads = matrix-vector products with 4 partial fma chains per output (chain j takes k = 16 g + 4 j + i, g ascending, i = 0 .. 3),
+ *                 added as (p0 + p1) + (p2 + p3), the bias last.  The heads of ctx (exploit, app, v_head.0) are such products too; value as
+ *                 in cygym_comm_actor_decode.
+ *   LayerNorm   = two-pass: mean = sum / H, var = sum (y - mean)^2 / H, (y - mean) * (1 / sqrt(var + 1e-5)) * w + b; both sums: lane l of 64
+ *                 adds its columns 2 l, 2 l + 1, then an xor butterfly 32 .. 1 (visible and invisible devices alike).
+ *   attention   = among the visible devices (ascending), in tiles of 16 on the matrix cores (v_mfma_f32_16x16x4_f32), every product ONE fma
+ *                 chain per output in the k order of cygym_comm_actor_decode: k = x k.weight^T, v = x v.weight^T, q = x q.weight^T,
+ *                 s = (q k^T) * (1 / sqrt(H)); the softmax runs over the key tiles in ascending order with a running maximum m and running
+ *                 sums (p = exp(s - m), l = l exp(m_old - m) + sum of the tile's p by an xor butterfly 1, 2, 4, 8, o = o exp(m_old - m) + p v
+ *                 with the tile's 16 keys as one chain), then o / l; y = x + (proj.weight o + proj.bias); LayerNorm as above.
+ *   type logits = dev_type_head(x_L) as in cygym_comm_actor_decode (visible devices; with logits_out every device), nan_to_num everywhere.
+ * The decision IS cygym_sample_group_actions on those logits, exactly as for cygym_comm_actor_decode (draws, order of the logp sum --
+ * lane d % 64 adds its devices ascending, invisible ones contribute +0 --, grouping).  The rng tick is read, not advanced.
+ * Memory: tokens of invisible devices, scores and attention weights never leave the chip.  x / k / v^T of a row's visible devices live in
+ * LDS while 3 n16 (H + 4) + H (n16 + 4) floats (x, k, q, v^T) fit in what the plan leaves (n16 = n_vis rounded up to 16; at M = 256, H = 128: n_vis <= 32),
+ * in the workgroup's slice of `workspace` otherwise.
+ * Limits (CYGYM_EUNSUPPORTED beyond): H a multiple of 16 in 16 .. 128; K, E, A <= 32; 1 <= L <= 4; M <= CYGYM_GAT_MAX_DEVICES = 1024 (the
+ * per-device LDS arrays -- 8 bytes a device -- must leave room for two 16-row tiles of x / k / v^T beside the waves' tile buffers at
+ * H = 128); a handle whose all-visible row does not fit in LDS without a workspace of cygym_comm_gat_workspace_bytes().  CYGYM_EINVAL,
+ * CYGYM_ENOTBOUND: as for cygym_comm_actor_decode, plus NULL or misaligned layer pointers and a workspace off 16-byte alignment.
+ * Out of scope: a real graph adjacency (the reference never produces one), a fused evaluate / backward through the attention,
+ * populations of nets in one launch, and building the observation on chip. */
+int cygym_comm_gat_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_comm_gat* gat, const cygym_device_logits* src,
+                          const cygym_actions* dst, void* stream);
+/* Bytes of workspace cygym_comm_gat_decode may need for hidden width H on this handle (0: every row fits in LDS; also 0 on bad arguments). */
+uint64_t cygym_comm_gat_workspace_bytes(cygym_handle* h, int32_t H);
 
 /* The per-device part of the PPO update of those agents (IPPO.py:711-739: the log-probability and the entropy of a STORED decision
  * under the current weights) and its backward, for n rows (a flattened rollout: no env, no flag plane -- the visibility mask is an
