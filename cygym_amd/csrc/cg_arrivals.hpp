@@ -3,18 +3,34 @@
 #ifndef CG_ARRIVALS_HPP
 #define CG_ARRIVALS_HPP
 
+#include "cg_period.hpp"   // the period test of every tick: plain host-and-device code (tests/period_probe.cpp)
+
+// Diagnostic builds (-DCG_STAMPS): cycles of an arrival call by sub-phase -- 0 candidates, 1 key draws, 2 radix rounds, 3 select +
+// give -- summed over both roles, and the Philox draws and takers of the call (tools/arrivals_split.py reads slots 26 / 27).
+#ifdef CG_STAMPS
+struct ArrMarks {
+  unsigned long long t, t0;
+  uint32_t d[4] = {0, 0, 0, 0}, draws = 0, takers = 0;
+  __device__ __forceinline__ void begin() { SUBNOW(t); t0 = t; }
+  __device__ __forceinline__ void mark(int i) { unsigned long long n; SUBNOW(n); d[i] += (uint32_t)(n - t); t = n; }
+  __device__ __forceinline__ void count(int n_draws, int n_takers) { draws += n_draws; takers += n_takers; }
+};
+#define ARR_MARKS_OUT(am) do { \
+  SUBVAL(26, (unsigned long long)(am).d[0] | ((unsigned long long)(am).d[1] << 16) | ((unsigned long long)(am).d[2] << 32) | ((unsigned long long)(am).d[3] << 48)); \
+  SUBVAL(27, (((am).t - (am).t0) & 0xFFFFFFFFull) | ((unsigned long long)(am).draws << 32) | ((unsigned long long)(am).takers << 40)); } while (0)
+#else
+struct ArrMarks {
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void count(int, int) {}
+};
+#define ARR_MARKS_OUT(am) do {} while (0)
+#endif
+
 // ---------------- arrivals: CDSimulator.generate_workloads :244-348 ----------------
-// random.sample(candidates, k) as "the k smallest (philox key, id)": a radix select over the candidates' 32-bit keys, one
-// bit per round.  MCT = chunks of 64 devices when known at compile time (<= 4: 64 / 256 devices), 0 = run-time size.
-// Every env of a batch is due in the same tick (same step_num, same period), so an arrival tick is as slow as this
-// function: with the keys and candidate bits re-read from LDS in every round (384 dependent round trips per call at 256
-// devices) such a launch took twice as long as any other (profiles/r04_tail_hist.txt).  Compile-time sizes keep the keys
-// in registers and the candidate masks in SGPRs: a round is MCT ballots; run-time sizes keep the "still matches the
-// prefix" bits in one register per lane (bit c <-> chunk c) and read the keys in staged groups of eight.
-template <int MCT, class KP>
-__device__ __forceinline__ void gen_workloads(Env& e, const KP& P, int num, bool server, int n_active, int step_num) {
-  const int M = e.M, MC = MCT ? MCT : e.MC;
-  if (n_active <= 0) return;
+// The number of jobs one role is offered after the cap and the turbo throttle (<= 0: none).
+template <class KP>
+__device__ __forceinline__ int arrival_num(const KP& P, int num, bool server, int n_active, int step_num) {
   if (P.c.workload_cap >= 0 && num > P.c.workload_cap) num = P.c.workload_cap;
   if (COLD(P.c.turbo)) {   // turbo throttling: cap + ramp, never zero (volt_typhoon_env.py:219-231), in the reference's own f64 steps
     const double frac = server ? P.c.turbo_fraction_servers : P.c.turbo_fraction_clients;
@@ -27,7 +43,138 @@ __device__ __forceinline__ void gen_workloads(Env& e, const KP& P, int num, bool
     if (cap < 1) cap = 1;
     if (num > cap) num = cap;
   }
-  if (num > n_active) num = n_active;
+  return num < n_active ? num : n_active;
+}
+
+// random.sample(candidates, k) as "the k smallest (philox key, id)": a radix select over the candidates' 32-bit keys, one
+// bit per round.  Every env of a batch is due in the same tick (same step_num, same period), so an arrival tick is as slow as
+// this code: with the keys and candidate bits re-read from LDS in every round (384 dependent round trips per call at 256
+// devices) such a launch took twice as long as any other (profiles/r04_tail_hist.txt).
+//
+// Compile-time sizes (MCT = chunks of 64 devices, <= 4: 64 / 256 devices), both roles in one call.  A Philox draw costs a wave
+// the same whether one lane or 64 want its result, so the call is arranged to draw as rarely as it can:
+//   * ONE pass over the flag / wl / busy / static bytes gives the free devices and the servers, a bit per chunk in each lane;
+//     a role's candidates are `free & servers` or `free & ~servers`;
+//   * per role (a rolled loop of two trips: one copy of the select in the kernel's text), the takers: all candidates
+//     when k == n, else the radix select with the keys in registers, a round being MCT ballots;
+//   * the takers of BOTH roles -- disjoint device sets, and the job length is keyed by the device alone -- compacted in
+//     device-id order: the taker at (chunk c, lane) has rank (takers in lower chunks) + below(takers[c]) and writes its id to
+//     slot `rank` of the scratch row (16-bit ids, one LDS round trip); lane j of a dense block of 64 then draws the job length of
+//     the j-th taker and scatters it.  One CG_SITE_ARR_TIME draw per 64 takers, where a give() per chunk and role drew up to
+//     2 * MCT times for a handful of lanes each.  (At one chunk there is nothing to compact: the lanes give in place.)
+template <int MCT, class KP>
+__device__ __forceinline__ void gen_workloads_ct(ArrMarks& am, Env& e, const KP& P, int num_c, int num_s) {
+  static_assert(MCT > 0, "compile-time sizes only");
+  if (num_c <= 0 && num_s <= 0) return;
+  const int M = e.M;
+  auto give = [&](int d) {   // the sampled device receives a job: ceil(triangular(0, mode, high)) ticks (CDSimulator.py:308)
+    e.wl[d] = (uint8_t)(1 + cdf_lookup(e.draw(CG_SITE_ARR_TIME, d, 0), P.c.tri_thr, CG_TRI_TABLE));
+    e.flags[d] &= (uint8_t)~CG_F_WLADV;
+  };
+  // bit c of a lane's word <-> device c * 64 + lane: free (active, no job, not busy), server, taker of either role.  (As 3 * MCT
+  // uniform masks they stayed live across the select, and the tick kernels answered with spilled SGPRs in other phases.)
+  uint32_t freeb = 0u, srvb = 0u, takeb = 0u;
+  {
+    uint32_t f[MCT], w[MCT], b[MCT], s[MCT];
+#pragma unroll
+    for (int c = 0; c < MCT; ++c) {   // all 4 * MCT reads leave together
+      const int d = c * WAVE + e.lane, dc = d < M ? d : M - 1;
+      f[c] = e.flags[dc]; w[c] = e.wl[dc]; b[c] = e.busy[dc]; s[c] = e.dst[dc];
+    }
+#pragma unroll
+    for (int c = 0; c < MCT; ++c) {
+      const bool in = c * WAVE + e.lane < M;
+      freeb |= (in && ((f[c] & CG_F_NYA) | w[c] | b[c]) == 0u ? 1u : 0u) << c;
+      srvb |= ((s[c] & CG_D_SERVER) != 0u ? 1u : 0u) << c;
+    }
+  }
+  am.mark(0);
+#pragma nounroll
+  for (int role = 0; role < 2; ++role) {   // clients, then servers (the order cannot show: disjoint devices, draws keyed by site and device)
+    const bool server = role != 0;
+    const int num = server ? num_s : num_c;
+    if (num <= 0) continue;
+    const uint32_t candb = freeb & (server ? srvb : ~srvb);
+    int n = 0;
+#pragma unroll
+    for (int c = 0; c < MCT; ++c) n += __popcll(ballot((candb >> c) & 1u));
+    if (n == 0) continue;
+    const int k = num < n ? num : n;
+    am.count(0, k);
+    if (k == n) { takeb |= candb; continue; }
+    const uint32_t site = server ? CG_SITE_ARR_SERVER : CG_SITE_ARR_CLIENT;
+    uint32_t key[MCT];
+    bool alive[MCT];   // candidate whose key matches the prefix found so far
+#pragma unroll
+    for (int c = 0; c < MCT; ++c) {
+      alive[c] = (candb >> c) & 1u;
+      key[c] = alive[c] ? e.draw(site, c * WAVE + e.lane, 0) : 0u;
+    }
+    am.mark(1);
+    am.count(MCT, 0);
+    // One bit per round, most significant first.  `alive`: candidates whose key matches the k-th smallest key on the bits
+    // seen so far; `sure`: candidates already known to be smaller than it (selected whatever comes).  As soon as exactly
+    // as many candidates are alive as are still to be selected they are all in, and the rounds stop -- with random 32-bit
+    // keys after about log2(n) + 2 of the 32 rounds.
+    bool sure[MCT];
+#pragma unroll
+    for (int c = 0; c < MCT; ++c) sure[c] = false;
+    int kk = k, n_alive = n;   // kk: 1-based rank still to locate among the alive candidates
+#pragma nounroll
+    for (int bit = 31; bit >= 0 && n_alive > kk; --bit) {
+      int cnt0 = 0;
+#pragma unroll
+      for (int c = 0; c < MCT; ++c) cnt0 += __popcll(ballot(alive[c] && !((key[c] >> bit) & 1u)));
+      const bool one = kk > cnt0;   // the k-th smallest has this bit set: the alive keys with a 0 here are smaller
+      if (one) { kk -= cnt0; n_alive -= cnt0; } else n_alive = cnt0;
+#pragma unroll
+      for (int c = 0; c < MCT; ++c) {
+        const bool b1 = ((key[c] >> bit) & 1u) != 0;
+        sure[c] = sure[c] || (alive[c] && one && !b1);
+        alive[c] = alive[c] && b1 == one;
+      }
+    }
+    am.mark(2);
+    // select: the sure ones, plus the first kk alive candidates in id order (all of them unless keys collide)
+    int seen = 0;
+#pragma unroll
+    for (int c = 0; c < MCT; ++c) {
+      const uint64_t em = ballot(alive[c]);
+      takeb |= (sure[c] || (alive[c] && (seen + below(em)) < kk) ? 1u : 0u) << c;
+      seen += __popcll(em);
+    }
+  }
+  if (!__any(takeb != 0u)) return;
+  if constexpr (MCT == 1) {
+    am.count(1, 0);
+    if (takeb) give(e.lane);
+  } else {
+    uint16_t* ids = (uint16_t*)e.scr;   // [n_take] the takers' ids in id order (the scratch row is idle between the actions and evolve)
+    int n_take = 0;
+#pragma unroll
+    for (int c = 0; c < MCT; ++c) {
+      const uint64_t tk = ballot((takeb >> c) & 1u);
+      if ((takeb >> c) & 1u) ids[n_take + below(tk)] = (uint16_t)(c * WAVE + e.lane);
+      n_take += __popcll(tk);
+    }
+    am.count((n_take + WAVE - 1) / WAVE, 0);
+    wsync();
+#pragma nounroll
+    for (int r0 = 0; r0 < n_take; r0 += WAVE)   // more than 64 takers: further blocks of 64
+      if (r0 + e.lane < n_take) give(ids[r0 + e.lane]);
+  }
+  wsync();
+  am.mark(3);
+}
+
+// One role per call.  Run-time sizes (MCT = 0): the "still matches the prefix" bits in one register per lane (bit c <-> chunk c),
+// the keys in LDS, read in staged groups of eight.  Compile-time sizes: the form the tick kernels had before gen_workloads_ct --
+// candidate masks in SGPR pairs, a give() per chunk; the tick + actor kernels keep it (arrivals<MCT, false>, cg_tick_actor.hpp).
+template <int MCT, class KP>
+__device__ __forceinline__ void gen_workloads(Env& e, const KP& P, int num, bool server, int n_active, int step_num) {
+  const int M = e.M, MC = MCT ? MCT : e.MC;
+  if (n_active <= 0) return;
+  num = arrival_num(P, num, server, n_active, step_num);
   if (num <= 0) return;
   const uint32_t site = server ? CG_SITE_ARR_SERVER : CG_SITE_ARR_CLIENT;
   auto is_cand = [&](int d) -> bool {
@@ -148,16 +295,22 @@ __device__ __forceinline__ void gen_workloads(Env& e, const KP& P, int num, bool
   }
 }
 
-// volt_typhoon_env.py:575-596; the three counts come from the fused pass of the tick
-template <int MCT, class KP>
+// volt_typhoon_env.py:575-596; the three counts come from the fused pass of the tick.  JOINT: both roles in one gen_workloads_ct
+// call and the period test of cg_period.hpp (compile-time sizes); otherwise one gen_workloads call per role.
+template <int MCT, bool JOINT = (MCT > 0), class KP>
 __device__ __forceinline__ void arrivals(Env& e, const KP& P, int step_num, int n_active, int idle, int free_s) {
   int free_c = idle - free_s;
   int n1 = n_active > 1 ? n_active : 1;
-  const int half = half_isqrt(n1);   // int(0.5*sqrt(n)) (:141-145)
+  int half;   // int(0.5*sqrt(n)) (:141-145)
+  if constexpr (JOINT) half = cg_half_isqrt_upto<MCT * WAVE>(n1); else half = half_isqrt(n1);
   int period = P.c.workload_period_base + half;
   if (period < 10) period = 10;
   if (period > P.c.workload_period_max) period = P.c.workload_period_max;
-  if (step_num % period != 0) return;
+  if constexpr (JOINT) {   // every env pays this test in every tick: no division sequence on the usual path
+    const bool due = COLD((unsigned)step_num >= (unsigned)CG_MULTIPLE_X_MAX) ? step_num % period == 0
+                                                                             : cg_is_multiple_rcp(step_num, period, __builtin_amdgcn_rcpf((float)period));
+    if (!due) return;
+  } else if (step_num % period != 0) return;
   if (n_active == 0 || 10 * idle < n_active) return;   // _idle_fraction() < 0.10
   int nC, nS;
   if (P.c.scaling_vulnerability) {   // _scaled_numloads(100, 10), anchor 50 (:266-293)
@@ -178,8 +331,16 @@ __device__ __forceinline__ void arrivals(Env& e, const KP& P, int step_num, int 
       nS = (int)(nS * ratio); if (nS < 0) nS = 0;
     }
   }
-  gen_workloads<MCT>(e, P, nC, false, n_active, step_num);
-  gen_workloads<MCT>(e, P, nS, true, n_active, step_num);
+  if constexpr (JOINT) {
+    static_assert(MCT > 0, "compile-time sizes only");
+    ArrMarks am;
+    am.begin();
+    gen_workloads_ct<MCT>(am, e, P, arrival_num(P, nC, false, n_active, step_num), arrival_num(P, nS, true, n_active, step_num));
+    ARR_MARKS_OUT(am);
+  } else {
+    gen_workloads<MCT>(e, P, nC, false, n_active, step_num);
+    gen_workloads<MCT>(e, P, nS, true, n_active, step_num);
+  }
 }
 
 #endif  // CG_ARRIVALS_HPP

@@ -92,6 +92,7 @@ inline void fill_hot(KParams& P) {   // host side, once the rest of P is complet
 #define SUBSTAMP(k) do { if (P.dbg && e.lane == 0) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); P.dbg[(size_t)e.env * CG_DBG_W + (k)] = _t; } } while (0)
 #define SUBVAL(k, v) do { if (P.dbg && e.lane == 0) P.dbg[(size_t)e.env * CG_DBG_W + (k)] = (unsigned long long)(v); } while (0)
 #define STAMP(k) do { if (P.dbg && lane == 0) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); P.dbg[(size_t)env * CG_DBG_W + (k)] = _t; } } while (0)
+#define SUBNOW(t) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory")   // the counter into a local: sub-phases summed before they are stored
 #else
 #define STAMP(k) do {} while (0)
 #define SUBSTAMP(k) do {} while (0)

@@ -485,7 +485,8 @@
   const int n_comp = (int)(s_cd & 0xFFFFu), n_comp_dc = (int)(s_cd >> 16);
   ie[CG_I_WORK_DONE] += current_work;
   wsync();
-  if (!partial) arrivals<MT ? (MT + WAVE - 1) / WAVE : 0>(e, P, ie[CG_I_STEP_NUM], n_active, n_idle, n_fsrv);   // changes wl only: the counts above stand
+  // changes wl only: the counts above stand.  (ARRIVALS_JOINT: a constant of the kernel this text is included in)
+  if (!partial) arrivals<MT ? (MT + WAVE - 1) / WAVE : 0, ARRIVALS_JOINT>(e, P, ie[CG_I_STEP_NUM], n_active, n_idle, n_fsrv);
 
   STAMP(3);
   // ---- rewards (:1267-1304 / :732-748) ----
