@@ -170,6 +170,21 @@ class CommEval(C.Structure):
                 ("n", C.c_int32), ("M", C.c_int32), ("H", C.c_int32), ("K", C.c_int32), ("tok_stride", C.c_int32), ("n_partials", C.c_int32)]
 
 
+class GatEvalLayer(C.Structure):
+    _fields_ = [("w_q", C.c_void_p), ("w_k", C.c_void_p), ("w_v", C.c_void_p), ("w_proj", C.c_void_p), ("b_proj", C.c_void_p),
+                ("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("grad_q", C.c_void_p), ("grad_k", C.c_void_p), ("grad_v", C.c_void_p),
+                ("grad_proj", C.c_void_p), ("grad_proj_bias", C.c_void_p), ("grad_ln_weight", C.c_void_p), ("grad_ln_bias", C.c_void_p)]
+
+
+class CommGatEval(C.Structure):
+    _fields_ = [("layer", GatEvalLayer * GAT_MAX_LAYERS), ("tok_base", C.c_void_p), ("tok_dev", C.c_void_p), ("w_type", C.c_void_p),
+                ("b_type", C.c_void_p), ("types", C.c_void_p), ("vis", C.c_void_p), ("logp_hi", C.c_void_p), ("logp_lo", C.c_void_p),
+                ("entropy", C.c_void_p), ("ctx", C.c_void_p), ("logits_out", C.c_void_p), ("g_logp", C.c_void_p), ("g_ent", C.c_void_p),
+                ("g_ctx", C.c_void_p), ("grad_tok_base", C.c_void_p), ("grad_tok_dev", C.c_void_p), ("grad_w_type", C.c_void_p),
+                ("grad_b_type", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64),
+                ("n", C.c_int32), ("M", C.c_int32), ("H", C.c_int32), ("K", C.c_int32), ("tok_stride", C.c_int32), ("n_layers", C.c_int32)]
+
+
 class CriticTail(C.Structure):
     _fields_ = [("h1_pre", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p), ("b3", C.c_void_p), ("q", C.c_void_p),
                 ("grad_q", C.c_void_p), ("grad_h1_pre", C.c_void_p), ("grad_w2", C.c_void_p), ("grad_b2", C.c_void_p), ("grad_w3", C.c_void_p),

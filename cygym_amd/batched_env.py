@@ -182,6 +182,7 @@ class BatchedCyberDefenseEnv:
         self.state = _alloc_state(self.N, self.M, self.EW, self.device, self.K, self.detector, self.slow_scan)
         self._scratch = None   # cygym_randomize's shuffle keys, allocated on first use
         self._act_cache = {}   # id(action dict) -> (data pointers, shapes, validated C struct)
+        self._gat_eval_ws = {}   # (H, L) -> the workspace of comm_gat_evaluate / _backward (comm_gat_eval_workspace), freed by close()
         lead = int(np.asarray(init_state["flags"]).shape[0])
         if lead not in (1, self.N):
             raise ValueError("init_state must have leading dimension 1 or n_envs")
@@ -284,6 +285,7 @@ class BatchedCyberDefenseEnv:
         if getattr(self, "_h", None) is not None and self._h:
             self.lib.cygym_destroy(self._h)
             self._h = C.c_void_p()
+        self._gat_eval_ws = {}
 
     def __del__(self):
         try:
@@ -1278,9 +1280,10 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_hier_loss_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_hier_loss_backward")
         return gs, ga, gd
 
-    def _comm_eval(self, tok_base, tok_dev, w_type, b_type, types, vis, backward: bool):
+    def _comm_eval(self, tok_base, tok_dev, w_type, b_type, types, vis, backward: bool, checks_only: bool = False):
         """The CommEval struct of comm_actor_evaluate / comm_actor_evaluate_backward from the factorised inputs, and what has to
-        stay alive until the call has returned.  dev_type_head.weight is packed here, per call: the weights change every step."""
+        stay alive until the call has returned.  dev_type_head.weight is packed here, per call: the weights change every step.
+        checks_only: the argument checks and the sizes alone (comm_gat_evaluate reads the matrix as it lies)."""
         f32 = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
         if not f32(tok_base) or tok_base.dim() != 2 or tok_base.stride(1) != 1:
             raise ValueError("tok_base must be a [n, H] float32 tensor on the batch's device with unit inner stride")
@@ -1296,6 +1299,8 @@ class BatchedCyberDefenseEnv:
         for name, t in (("types", types), ("vis", vis)):
             if t.dtype != torch.uint8 or t.device != self.device or tuple(t.shape) != (n, M) or not t.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous uint8 [{n}, {M}] tensor on {self.device}")
+        if checks_only:
+            return None, (), (n, M, H, K)
         e = abi.CommEval()
         packed = self.pack_linear(w_type)
         e.tok_base, e.tok_dev, e.w_type, e.b_type, e.types, e.vis = (t.data_ptr() for t in (tok_base, tok_dev, packed, b_type, types, vis))
@@ -1354,6 +1359,92 @@ class BatchedCyberDefenseEnv:
         e.partials, e.n_partials = part.data_ptr(), nwg
         _lib.check(self.lib.cygym_comm_actor_evaluate_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_comm_actor_evaluate_backward")
         return ga, gp, gw, gb
+
+    def comm_gat_eval_workspace(self, H: int, L: int):
+        """The ONE workspace comm_gat_evaluate and comm_gat_evaluate_backward use on this batch for hidden width H and L attention
+        layers (the larger of the two calls' needs: the backward's, with the partial gradients), allocated on first use, kept per
+        (H, L) and released by close().  Its size depends on the batch's M, H and L, never on the number of rows.  The calls of one
+        batch share it, so they must be ordered on one stream (they are: the batch launches on torch's current stream); callers that
+        evaluate on several streams at once pass each call a `workspace` of their own.  None where the library refuses the sizes
+        (the call itself then says why)."""
+        key = (int(H), int(L))
+        if key not in self._gat_eval_ws:
+            nbytes = max(int(self.lib.cygym_comm_gat_eval_workspace_bytes(self._h, key[0], key[1], b)) for b in (0, 1))
+            self._gat_eval_ws[key] = torch.empty((nbytes // 4,), dtype=torch.float32, device=self.device) if nbytes else None
+        return self._gat_eval_ws[key]
+
+    GAT_EVAL_LAYER = ("w_q", "w_k", "w_v", "w_proj", "b_proj", "ln_w", "ln_b")
+
+    def _comm_gat_eval(self, tok_base, tok_dev, w_type, b_type, layers, types, vis, backward: bool, workspace):
+        """The CommGatEval struct of comm_gat_evaluate / comm_gat_evaluate_backward: the factorised inputs as _comm_eval checks
+        them, dev_type_head.weight and the layers' matrices as torch holds them, the workspace."""
+        _, _, (n, M, H, K) = self._comm_eval(tok_base, tok_dev, w_type, b_type, types, vis, False, checks_only=True)
+        e = abi.CommGatEval()
+        e.tok_base, e.tok_dev, e.w_type, e.b_type, e.types, e.vis = (t.data_ptr() for t in (tok_base, tok_dev, w_type, b_type, types, vis))
+        e.n, e.M, e.H, e.K, e.tok_stride, e.n_layers = n, M, H, K, int(tok_base.stride(0)) if n > 1 else H, len(layers)
+        for l, ly in enumerate(list(layers)[:abi.GAT_MAX_LAYERS]):   # (more than that: the library answers CYGYM_EUNSUPPORTED)
+            if len(ly) != 7:
+                raise ValueError("a layer is (q.weight, k.weight, v.weight, proj.weight, proj.bias, ln.weight, ln.bias)")
+            for name, t in zip(self.GAT_EVAL_LAYER, ly):
+                shape = (H, H) if name.startswith("w_") else (H,)
+                if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"layer {l}: {name} must be a contiguous float32 {list(shape)} tensor on {self.device}")
+                setattr(e.layer[l], name, t.data_ptr())
+        ws = workspace
+        if ws is None and H % 16 == 0 and 16 <= H <= 128 and 1 <= len(layers) <= abi.GAT_MAX_LAYERS and M == self.M <= abi.GAT_MAX_DEVICES:
+            ws = self.comm_gat_eval_workspace(H, len(layers))
+        if ws is None:   # (sizes the library refuses: it says so itself, and must see a non-null pointer to get that far)
+            ws = torch.empty((4,), dtype=torch.float32, device=self.device)
+        if ws.dtype != torch.float32 or ws.device != self.device or not ws.is_contiguous():
+            raise ValueError(f"workspace must be a contiguous float32 tensor on {self.device}")
+        e.workspace, e.workspace_bytes = ws.data_ptr(), int(ws.numel()) * 4
+        return e, ws, (n, M, H, K)
+
+    def comm_gat_evaluate(self, tok_base, tok_dev, w_type, b_type, layers, types, vis, logits_out=None, out=None, workspace=None):
+        """comm_actor_evaluate for a net WITH attention layers (USE_GAT = True) in ONE launch (cygym_comm_gat_evaluate;
+        include/cygym_abi.h states the arithmetic): the tokens x_0[d] = relu(tok_base + tok_dev[d]) pass through the L layers over
+        the stored mask `vis` (attention among the visible devices, one shared vector for the invisible ones), then the summed
+        log-probability of the stored types and the summed entropy of the visible devices, and ctx = the mean of x_L over all devices.
+          layers   per layer (q.weight, k.weight, v.weight, proj.weight [H, H], proj.bias, ln.weight, ln.bias [H]) as torch holds them
+          others   as comm_actor_evaluate; M must be the batch's
+          out      optional (logp_hi [n], logp_lo [n], entropy [n], ctx [n, H]) to write into
+        Returns (logp_hi, logp_lo, entropy, ctx); logp_hi + logp_lo in float64 is the compensated sum.  Scores, attention weights
+        and tokens stay in a workspace whose size does not depend on n (comm_gat_eval_workspace).
+        Limits: H a multiple of 16 in 16..128, K <= 32, 1..4 layers, M <= 1024 (CYGYM_EUNSUPPORTED)."""
+        e, ws, (n, M, H, K) = self._comm_gat_eval(tok_base, tok_dev, w_type, b_type, layers, types, vis, False, workspace)   # noqa: F841 (ws: alive until the call has returned)
+        hi, lo, ent, ctx = self._eval_out(out, ((n,), (n,), (n,), (n, H)), "logp_hi, logp_lo, entropy, ctx")
+        e.logp_hi, e.logp_lo, e.entropy, e.ctx = hi.data_ptr(), lo.data_ptr(), ent.data_ptr(), ctx.data_ptr()
+        if logits_out is not None:
+            if logits_out.dtype != torch.float32 or logits_out.device != self.device or tuple(logits_out.shape) != (n, M, K) or not logits_out.is_contiguous():
+                raise ValueError(f"logits_out must be a contiguous float32 {[n, M, K]} tensor on {self.device}")
+            e.logits_out = logits_out.data_ptr()
+        _lib.check(self.lib.cygym_comm_gat_evaluate(self._h, C.byref(e), self._stream()), self._h, "cygym_comm_gat_evaluate")
+        return hi, lo, ent, ctx
+
+    def comm_gat_evaluate_backward(self, tok_base, tok_dev, w_type, b_type, layers, types, vis, g_logp, g_ent, g_ctx, out=None, workspace=None):
+        """The backward of comm_gat_evaluate (cygym_comm_gat_evaluate_backward: one launch that recomputes the forward of every row
+        and walks the layers top down, plus the reduction of the workgroups' partials): given the gradients of a loss with respect to
+        logp [n], entropy [n] and ctx [n, H] it returns (grad_tok_base [n, H], grad_tok_dev [M, H], grad_w_type [K, H], grad_b_type
+        [K], layer gradients): per layer the seven gradients in the order of `layers`.  out: the same structure to write into.
+        No atomics: the same inputs give the same bits."""
+        e, ws, (n, M, H, K) = self._comm_gat_eval(tok_base, tok_dev, w_type, b_type, layers, types, vis, True, workspace)   # noqa: F841
+        gs = []
+        for name, t, shape in (("g_logp", g_logp, (n,)), ("g_ent", g_ent, (n,)), ("g_ctx", g_ctx, (n, H))):
+            if t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be a float32 {list(shape)} tensor on {self.device}")
+            gs.append(t.contiguous())
+        e.g_logp, e.g_ent, e.g_ctx = (t.data_ptr() for t in gs)
+        L = len(layers)
+        shapes = ((n, H), (M, H), (K, H), (K,)) + ((H, H), (H, H), (H, H), (H, H), (H,), (H,), (H,)) * L
+        flat = None if out is None else tuple(out[:4]) + tuple(t for ly in out[4] for t in ly)
+        flat = self._eval_out(flat, shapes, "grad_tok_base, grad_tok_dev, grad_w_type, grad_b_type, per layer the seven gradients")
+        e.grad_tok_base, e.grad_tok_dev, e.grad_w_type, e.grad_b_type = (t.data_ptr() for t in flat[:4])
+        names = ("grad_q", "grad_k", "grad_v", "grad_proj", "grad_proj_bias", "grad_ln_weight", "grad_ln_bias")
+        for l in range(min(L, abi.GAT_MAX_LAYERS)):
+            for i, name in enumerate(names):
+                setattr(e.layer[l], name, flat[4 + 7 * l + i].data_ptr())
+        _lib.check(self.lib.cygym_comm_gat_evaluate_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_comm_gat_evaluate_backward")
+        return flat[0], flat[1], flat[2], flat[3], [tuple(flat[4 + 7 * l: 11 + 7 * l]) for l in range(L)]
 
     def _critic_tail(self, h1_pre, w2, b2, w3, b3):
         """The CriticTail struct of critic_tail / critic_tail_backward from fc1's pre-activations and fc2 / fc3 as torch holds them

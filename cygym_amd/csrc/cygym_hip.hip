@@ -82,6 +82,11 @@ namespace cygym_k {
 #include "cg_comm_gat.hpp"
 extern template __global__ void comm_gat_kernel<false>(cygym_comm_actor, cygym_comm_gat, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 extern template __global__ void comm_gat_kernel<true>(cygym_comm_actor, cygym_comm_gat, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+// ... and its evaluate / backward for the PPO update (cg_inst_gat_eval.hip)
+#include "cg_comm_gat_eval.hpp"
+extern template __global__ void comm_gat_eval_kernel<0>(cygym_comm_gat_eval);
+extern template __global__ void comm_gat_eval_kernel<1>(cygym_comm_gat_eval);
+extern template __global__ void comm_gat_eval_kernel<2>(cygym_comm_gat_eval);
 }  // namespace cygym_k
 
 // the hierarchical (HAGS) decode lives in its own unit (cg_inst_hier.hip): declared, not instantiated, here
@@ -296,6 +301,7 @@ int cygym_sizeof(int32_t which) {
     case 31: return (int)sizeof(cygym_dns);   // (index 30 stays unassigned)
     case 33: return (int)sizeof(cygym_mixture);   // (index 32 stays unassigned)
     case 35: return (int)sizeof(cygym_comm_gat);   // (index 34 stays unassigned)
+    case 37: return (int)sizeof(cygym_comm_gat_eval);   // (index 36 stays unassigned)
     default: return -1;
   }
 }
@@ -1342,6 +1348,74 @@ int cygym_comm_actor_evaluate_backward(cygym_handle* h, const cygym_comm_eval* e
   HIPCHK(h, hipGetLastError());
   const size_t total = (size_t)e->M * e->H + (size_t)e->K * e->H + (size_t)e->K;
   hipLaunchKernelGGL(comm_eval_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *e, nwg);
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+// What the two evaluate calls of the net with attention layers check alike: handle, pointers, layout (CYGYM_EINVAL), then the
+// implemented range (CYGYM_EUNSUPPORTED); *grid: the workgroups of the launch.
+static int check_gat_eval(cygym_handle* h, const cygym_comm_gat_eval* e, const char* who, bool own_ptrs, bool bwd, int* grid, size_t* lds) {
+  if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
+  if (!e || !own_ptrs || !e->tok_base || !e->tok_dev || !e->w_type || !e->b_type || !e->types || !e->vis || !e->workspace)
+    return fail(h, CYGYM_EINVAL, "%s: null pointer", who);
+  if (e->n < 1 || e->K < 1 || e->M < 1 || e->M != h->t.M || e->H < 1 || e->tok_stride < e->H ||
+      (((uintptr_t)e->tok_dev | (uintptr_t)e->w_type | (uintptr_t)e->workspace) & 15))
+    return fail(h, CYGYM_EINVAL, "%s: bad layout (n, K >= 1, M the handle's, tok_stride >= H, 16-byte aligned tok_dev / w_type / workspace)", who);
+  if (e->n_layers < 1 || e->n_layers > GT_MAX_L) return fail(h, CYGYM_EUNSUPPORTED, "%s: 1 .. 4 attention layers", who);
+  for (int l = 0; l < e->n_layers; ++l) {
+    const cygym_gat_eval_layer& y = e->layer[l];
+    if (!y.w_q || !y.w_k || !y.w_v || !y.w_proj || !y.b_proj || !y.ln_w || !y.ln_b ||
+        (bwd && (!y.grad_q || !y.grad_k || !y.grad_v || !y.grad_proj || !y.grad_proj_bias || !y.grad_ln_weight || !y.grad_ln_bias)))
+      return fail(h, CYGYM_EINVAL, "%s: null layer pointer", who);
+    if (((uintptr_t)y.w_q | (uintptr_t)y.w_k | (uintptr_t)y.w_v | (uintptr_t)y.w_proj) & 15)
+      return fail(h, CYGYM_EINVAL, "%s: a layer matrix off 16-byte alignment", who);
+  }
+  if (e->H < 16 || e->H > CM_MAX_H || (e->H & 15) || e->K > CM_MAX_HEAD || e->M > GT_MAX_M)
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: H must be a multiple of 16 in 16 .. 128, at most 32 action types, at most 1024 devices", who);
+  const GtPlan pl = gt_plan(e->H, e->M);
+  *lds = (size_t)ge_lds(pl, e->H).total * sizeof(float);
+  if (*lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the per-row buffers do not fit in LDS", who);
+  const int cap = ge_grid_cap(e->H, e->M, e->n_layers, bwd);
+  if (e->workspace_bytes < (uint64_t)cap * ge_ws(e->H, e->M, e->n_layers, bwd).total * sizeof(float))
+    return fail(h, CYGYM_EINVAL, "%s: the workspace is smaller than cygym_comm_gat_eval_workspace_bytes()", who);
+  *grid = e->n < cap ? e->n : cap;
+  return CYGYM_OK;
+}
+
+uint64_t cygym_comm_gat_eval_workspace_bytes(cygym_handle* h, int32_t H, int32_t L, int32_t backward) {
+  if (!h || H < 16 || H > CM_MAX_H || (H & 15) || L < 1 || L > GT_MAX_L || h->t.M < 1 || h->t.M > GT_MAX_M) return 0;
+  const bool bwd = backward != 0;
+  return (uint64_t)ge_grid_cap(H, h->t.M, L, bwd) * ge_ws(H, h->t.M, L, bwd).total * sizeof(float);
+}
+
+int cygym_comm_gat_evaluate(cygym_handle* h, const cygym_comm_gat_eval* e, void* stream) {
+  const char* const who = "cygym_comm_gat_evaluate";
+  int grid = 0;
+  size_t lds = 0;
+  if (const int rc = check_gat_eval(h, e, who, e && e->logp_hi && e->logp_lo && e->entropy && e->ctx, false, &grid, &lds)) return rc;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const void* k = e->logits_out ? (const void*)comm_gat_eval_kernel<1> : (const void*)comm_gat_eval_kernel<0>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  void* args[] = {(void*)e};
+  HIPCHK(h, hipLaunchKernel(k, dim3(grid), dim3(GT_THREADS), args, lds, (hipStream_t)stream));   // a workgroup per row, walking over the rows
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+int cygym_comm_gat_evaluate_backward(cygym_handle* h, const cygym_comm_gat_eval* e, void* stream) {
+  const char* const who = "cygym_comm_gat_evaluate_backward";
+  int grid = 0;
+  size_t lds = 0;
+  if (const int rc = check_gat_eval(h, e, who, e && e->g_logp && e->g_ent && e->g_ctx && e->grad_tok_base && e->grad_tok_dev && e->grad_w_type &&
+                                                   e->grad_b_type, true, &grid, &lds)) return rc;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const void* k = (const void*)comm_gat_eval_kernel<2>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  void* args[] = {(void*)e};
+  HIPCHK(h, hipLaunchKernel(k, dim3(grid), dim3(GT_THREADS), args, lds, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  const GeWs ws = ge_ws(e->H, e->M, e->n_layers, true);
+  hipLaunchKernelGGL(comm_gat_eval_reduce_kernel, dim3((unsigned)((ws.ps + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *e, grid, ws.total, ws.part, ws.ps);
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
 }

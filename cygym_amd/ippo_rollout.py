@@ -310,14 +310,20 @@ def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minib
     function is that update.  For more rows it is the same formulas, which the reference writes for a minibatch.  Out of scope:
     AMP, the budget bookkeeping and the progress prints.
 
-    A net with attention layers (CommActorCritic(gat_layers > 0), USE_GAT = True) is evaluated on the torch path, through autograd
-    (there is no fused backward through the attention).  Its layers read every row's OWN stored mask.  The reference's update
+    A net with attention layers (CommActorCritic(gat_layers > 0), USE_GAT = True) is evaluated on the torch path, through autograd,
+    unless fused=True and `batch` are given: then the layers and their backward run in the library as well
+    (cygym_comm_gat_evaluate / _backward); fused=True without `batch` raises NotImplementedError.  Its layers read every row's OWN stored mask.  The reference's update
     instead masks the adjacency of the WHOLE minibatch with the visibility of the minibatch's first row (`v0 = mb_vis[0]`,
     IPPO.py:713-717) -- for its one-row updates the same thing; first_row_mask=True reproduces that for larger minibatches (the
-    log-probabilities are still selected by each row's own mask, :725-737)."""
+    log-probabilities are still selected by each row's own mask, :725-737) on the torch path; the fused path reads one mask per
+    row, so first_row_mask with fused=True is refused above one row per minibatch (with one row the two masks coincide)."""
     gat = bool(getattr(net, "gat_layers", 0))
-    if gat and fused:
-        raise NotImplementedError("a net with attention layers has no fused evaluate: ppo_update runs its torch path")
+    if gat and fused and batch is None:
+        raise NotImplementedError("the fused evaluate of a net with attention layers runs through a BatchedCyberDefenseEnv: pass batch= "
+                                  "(without it ppo_update runs the torch path, fused=False)")
+    if gat and fused and first_row_mask and int(minibatch_size) > 1:
+        raise NotImplementedError("first_row_mask with minibatches above one row needs the layers to read another mask than the stored "
+                                  "one: the fused evaluate does not (fused=False)")
     with torch.no_grad():
         next_value = (net(rollout.last_state, rollout.last_vis) if gat else net(rollout.last_state))["value"].reshape(-1)
         adv, ret = advantages(rollout, next_value, gamma, lam)
@@ -333,8 +339,8 @@ def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minib
             mb = perm[start: start + int(minibatch_size)]
             adv_mb, ret_mb = adv[mb], ret[mb].clamp(-VALUE_TARGET_CLIP, VALUE_TARGET_CLIP)
             if gat:
-                ev = vis[mb][:1].expand(len(mb), -1) if first_row_mask else None
-                logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], fused=False, eval_vis=ev)
+                ev = vis[mb][:1].expand(len(mb), -1) if first_row_mask and not fused else None   # (fused: one row, the same mask)
+                logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], batch=batch if fused else None, fused=bool(fused), eval_vis=ev)
             else:
                 logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], batch=batch, fused=fused)
             loss, pol, v_loss, ent_mean = ppo_loss(logp, ent, value, old_logp[mb], old_value[mb], adv_mb, ret_mb, clip_eps=clip_eps,

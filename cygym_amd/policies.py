@@ -861,6 +861,32 @@ class _CommEvaluate(torch.autograd.Function):
         return None, None, None, ga, gp, gw, gb
 
 
+class _CommGatEvaluate(torch.autograd.Function):
+    """cygym_comm_gat_evaluate and its backward as one differentiable op for a net with attention layers: (tok_base, tok_dev,
+    dev_type_head.weight, .bias, then per layer q / k / v / proj.weight, proj.bias, ln.weight, ln.bias) -> (logp_hi, entropy, ctx,
+    logp_lo) for stored types / visibility.  Nothing but the inputs is kept for backward: the kernel recomputes the forward."""
+
+    @staticmethod
+    def forward(ctx, batch, types, vis, tok_base, tok_dev, w_type, b_type, *layer_params):
+        ins = tuple(t.detach().contiguous() for t in (tok_base, tok_dev, w_type, b_type) + layer_params)
+        ctx.batch = batch
+        ctx.save_for_backward(*ins, types, vis)
+        layers = [ins[4 + 7 * l: 11 + 7 * l] for l in range(len(layer_params) // 7)]
+        hi, lo, ent, c = batch.comm_gat_evaluate(*ins[:4], layers, types, vis)
+        return hi, ent, c, lo
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logp, g_ent, g_ctx, g_lo):     # (g_lo is ignored: evaluate() adds logp_lo detached, as a correction of the value only)
+        *ins, types, vis = ctx.saved_tensors
+        a = ins[0]
+        z = lambda g, like: torch.zeros(like, dtype=torch.float32, device=a.device) if g is None else g.float()  # noqa: E731
+        n, H = a.shape
+        layers = [tuple(ins[4 + 7 * l: 11 + 7 * l]) for l in range((len(ins) - 4) // 7)]
+        ga, gp, gw, gb, gl = ctx.batch.comm_gat_evaluate_backward(*ins[:4], layers, types, vis, z(g_logp, (n,)), z(g_ent, (n,)), z(g_ctx, (n, H)))
+        return (None, None, None, ga, gp, gw, gb) + tuple(t for ly in gl for t in ly)
+
+
 class GATLayer(nn.Module):
     """The reference's attention layer (IPPO.py:114-130) under its parameter names: q, k, v without bias, proj, ln."""
 
@@ -893,8 +919,8 @@ class CommActorCritic(nn.Module):
     gat_layers = n > 0 is the network with USE_GAT = True (IPPO.py:114-130, :173-175): `gats` holds n GATLayer under the reference's
     names (the reference always builds 2), load_state_dict loads them, forward(state, vis) runs the tokens through them over
     ippo_rollout.masked_adjacency(vis) -- the reference's dense function -- before the heads and the pooled context, packed() adds
-    the packed layers and the closed loop runs through cygym_comm_gat_decode.  evaluate() of such a net is the torch path
-    (fused=False, through autograd); a fused evaluate / backward through the attention is out of scope.
+    the packed layers and the closed loop runs through cygym_comm_gat_decode.  evaluate(fused=True, batch=) of such a net runs the
+    layers and their backward in the library (cygym_comm_gat_evaluate / _backward); its default stays the torch path.
     forward() is the unfactorised network in torch -- the restatement the fused kernel is tested against (dtype=torch.float64)
     and the torch path of ippo_rollout.collect.  factors() / packed() give the form cygym_comm_actor_decode reads:
     tok[d] = relu(a + P[d]) with a = merge.bias + merge.weight[:, :H] hs (one vector per env) and the env-independent table
@@ -971,13 +997,23 @@ class CommActorCritic(nn.Module):
         tokens nor logits reach HBM); the heads of ctx stay in torch ([B, H] products).
         fused=False: the same quantities from forward() with one log_softmax over [B, D, K]; runs anywhere, in `dtype`
         (torch.float64: the restatement the fused path is tested against).
+        A net with attention layers: fused=True together with batch= runs tokens, layers, type head, the sums over devices and their
+        backward as cygym_comm_gat_evaluate / _backward (one autograd.Function; scores, attention weights and tokens stay in a
+        workspace whose size does not depend on B); fused=None means the TORCH path for such a net, whether or not `batch` is given
+        (measured, PERFLOG.md: the fused path saves the [B, D, D] memory, not time, so the default has not flipped); fused=True without batch
+        raises NotImplementedError.
         eval_vis [B, D] (attention layers only): the mask the LAYERS read, where it differs from the stored `vis` that selects the
-        log-probabilities -- ippo_rollout.ppo_update(first_row_mask=True) reproduces the reference's update with it."""
+        log-probabilities -- ippo_rollout.ppo_update(first_row_mask=True) reproduces the reference's update with it.  The fused path
+        reads one mask: eval_vis different from vis raises NotImplementedError there."""
         if self.gat_layers:
-            if fused:
-                raise NotImplementedError("a net with attention layers has no fused evaluate (no backward through the attention in the "
-                                          "library): evaluate(fused=False) runs the torch path through autograd")
-            fused = False
+            if fused and batch is None:
+                raise NotImplementedError("the fused evaluate of a net with attention layers runs through a BatchedCyberDefenseEnv "
+                                          "(pass batch=); evaluate(fused=False) runs the torch path through autograd")
+            if fused and eval_vis is not None and not torch.equal((eval_vis > 0.5) if eval_vis.dtype != torch.bool else eval_vis,
+                                                                  (vis > 0.5) if vis.dtype != torch.bool else vis):
+                raise NotImplementedError("the fused evaluate of a net with attention layers reads ONE mask: eval_vis different from "
+                                          "vis runs on the torch path only (fused=False)")
+            fused = bool(fused)   # (None: the torch path -- the fused one saves memory, not time)
         fused = batch is not None if fused is None else bool(fused)
         visb = vis > 0.5 if vis.dtype != torch.bool else vis
         tgt = torch.where(visb, types.long().clamp(0, self.n_types - 1), torch.zeros_like(types, dtype=torch.long))
@@ -988,8 +1024,13 @@ class CommActorCritic(nn.Module):
             if dtype not in (None, torch.float32):
                 raise ValueError("the fused evaluate is fp32")
             a, P = self.factors(state.float())
-            hi, ent, ctx, lo = _CommEvaluate.apply(batch, tgt.to(torch.uint8).contiguous(), visb.to(torch.uint8).contiguous(), a, P,
-                                                   self.dev_type_head.weight, self.dev_type_head.bias)
+            if self.gat_layers:
+                lp = tuple(p for g in self.gats for p in (g.q.weight, g.k.weight, g.v.weight, g.proj.weight, g.proj.bias, g.ln.weight, g.ln.bias))
+                hi, ent, ctx, lo = _CommGatEvaluate.apply(batch, tgt.to(torch.uint8).contiguous(), visb.to(torch.uint8).contiguous(), a, P,
+                                                          self.dev_type_head.weight, self.dev_type_head.bias, *lp)
+            else:
+                hi, ent, ctx, lo = _CommEvaluate.apply(batch, tgt.to(torch.uint8).contiguous(), visb.to(torch.uint8).contiguous(), a, P,
+                                                       self.dev_type_head.weight, self.dev_type_head.bias)
             logp = hi.double() + lo.detach().double()
             dt = torch.float32
             exp_logits = clean(self._lin(self.exp_head, ctx, dt))

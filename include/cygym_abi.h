@@ -711,8 +711,8 @@ typedef struct cygym_comm_gat {
  * per-device LDS arrays -- 8 bytes a device -- must leave room for two 16-row tiles of x / k / v^T beside the waves' tile buffers at
  * H = 128); a handle whose all-visible row does not fit in LDS without a workspace of cygym_comm_gat_workspace_bytes().  CYGYM_EINVAL,
  * CYGYM_ENOTBOUND: as for cygym_comm_actor_decode, plus NULL or misaligned layer pointers and a workspace off 16-byte alignment.
- * Out of scope: a real graph adjacency (the reference never produces one), a fused evaluate / backward through the attention,
- * populations of nets in one launch, and building the observation on chip. */
+ * Out of scope: a real graph adjacency (the reference never produces one), populations of nets in one launch, and building the
+ * observation on chip.  The PPO update of such a net evaluates stored decisions with cygym_comm_gat_evaluate below. */
 int cygym_comm_gat_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_comm_gat* gat, const cygym_device_logits* src,
                           const cygym_actions* dst, void* stream);
 /* Bytes of workspace cygym_comm_gat_decode may need for hidden width H on this handle (0: every row fits in LDS; also 0 on bad arguments). */
@@ -778,6 +778,102 @@ typedef struct cygym_comm_eval {
  * is written then.  Out of scope: the heads of ctx (exploit, app, value: [n][H] products of the caller) and the optimiser. */
 int cygym_comm_actor_evaluate(cygym_handle* h, const cygym_comm_eval* e, void* stream);
 int cygym_comm_actor_evaluate_backward(cygym_handle* h, const cygym_comm_eval* e, void* stream);
+
+/* The same evaluate and backward for the network WITH its attention layers (USE_GAT = True): the PPO update's evaluation of stored
+ * decisions (IPPO.py:711-739) through the L layers of cygym_comm_gat_decode, and the gradient of every parameter of them.  All fp32,
+ * DEVICE pointers; every matrix is read AS TORCH HOLDS IT ([out][in], contiguous, 16-byte aligned) -- no pack step, the weights change
+ * at every update.  M must be the handle's device count (the workspace query sizes by it); no cygym_bind needed. */
+typedef struct cygym_gat_eval_layer {
+  const float* w_q;           /* q.weight [H][H]                                                                                      */
+  const float* w_k;           /* k.weight [H][H]                                                                                      */
+  const float* w_v;           /* v.weight [H][H]                                                                                      */
+  const float* w_proj;        /* proj.weight [H][H]                                                                                   */
+  const float* b_proj;        /* proj.bias [H]                                                                                        */
+  const float* ln_w;          /* ln.weight [H] (eps 1e-5, biased variance)                                                            */
+  const float* ln_b;          /* ln.bias [H]                                                                                          */
+  float* grad_q;              /* backward out [H][H]                                                                                  */
+  float* grad_k;              /* backward out [H][H]                                                                                  */
+  float* grad_v;              /* backward out [H][H]                                                                                  */
+  float* grad_proj;           /* backward out [H][H]                                                                                  */
+  float* grad_proj_bias;      /* backward out [H]                                                                                     */
+  float* grad_ln_weight;      /* backward out [H]                                                                                     */
+  float* grad_ln_bias;        /* backward out [H]                                                                                     */
+} cygym_gat_eval_layer;
+typedef struct cygym_comm_gat_eval {
+  cygym_gat_eval_layer layer[CYGYM_GAT_MAX_LAYERS];
+  const float* tok_base;      /* [n][tok_stride] a of row b                                                                           */
+  const float* tok_dev;       /* [M][H] the table P, 16-byte aligned                                                                  */
+  const float* w_type;        /* dev_type_head.weight [K][H] as it lies, 16-byte aligned                                              */
+  const float* b_type;        /* [K]                                                                                                  */
+  const uint8_t* types;       /* [n][M] the stored action type per device (clamped to 0 .. K-1; not read where vis is 0)              */
+  const uint8_t* vis;         /* [n][M] the stored visibility mask, non-zero = visible: selects the log-probabilities AND is the mask
+                                 the layers read                                                                                      */
+  float* logp_hi;             /* forward out [n]: the compensated sum's rounded value                                                 */
+  float* logp_lo;             /* forward out [n]: what that rounding dropped (logp_hi + logp_lo in wider arithmetic)                  */
+  float* entropy;             /* forward out [n]                                                                                      */
+  float* ctx;                 /* forward out [n][H]: mean_L                                                                           */
+  float* logits_out;          /* forward out, optional [n][M][K]: the clean type logits of EVERY device (tests)                       */
+  const float* g_logp;        /* backward in [n]                                                                                      */
+  const float* g_ent;         /* backward in [n]                                                                                      */
+  const float* g_ctx;         /* backward in [n][H]                                                                                   */
+  float* grad_tok_base;       /* backward out [n][H]                                                                                  */
+  float* grad_tok_dev;        /* backward out [M][H]                                                                                  */
+  float* grad_w_type;         /* backward out [K][H]                                                                                  */
+  float* grad_b_type;         /* backward out [K]                                                                                     */
+  float* workspace;           /* 16-byte aligned, cygym_comm_gat_eval_workspace_bytes() bytes; it need not be cleared                 */
+  uint64_t workspace_bytes;
+  int32_t n, M, H, K;         /* rows, devices, hidden width, action types                                                            */
+  int32_t tok_stride;         /* floats per row of tok_base, >= H                                                                     */
+  int32_t n_layers;           /* L: 1 .. CYGYM_GAT_MAX_LAYERS                                                                         */
+} cygym_comm_gat_eval;
+
+/* Per row b the function is the reduced form of cygym_comm_gat_decode.  V: the devices visible in the row's stored mask, ascending;
+ * s = 1 / sqrt(H); x_0[d] = relu(a_b + P[d]).  Per layer l: m_l = mean over ALL M devices of x_l, u_l = Wv m_l, c_l = Wp u_l + bp;
+ * an invisible d has y[d] = x_l[d] + c_l; the visible rows X = x_l[V] have Q = X Wq^T, K = X Wk^T, Vv = X Wv^T, A = softmax_rows(s Q K^T),
+ * O = A Vv, y[V] = X + O Wp^T + bp; x_(l+1) = LayerNorm_l(y).  ctx = m_L; z[d] = nan_to_num(Wt x_L[d] + bt) for d in V; lp, p and the
+ * entropy Hent of a device as in cygym_comm_actor_evaluate, t_d = min(types, K - 1); logp = sum over V of lp[d][t_d], entropy = sum
+ * over V of Hent[d].
+ * One workgroup of 8 waves works on ONE row and walks over the rows b = blockIdx, + grid, ... (grid = min(n, a cap that depends on M,
+ * H and L only: the workspace and the partials are sized by the cap, never by n).  Every matrix product runs on the matrix cores
+ * (v_mfma_f32_16x16x4_f32, fp32 in and out) as 16 x 16 output tiles, ONE fused-multiply-add chain per output over the contraction
+ * index k in the order g ascending, i = 0 .. 3, j = 0 .. 3 with k = 16 g + 4 j + i.
+ * Forward, ONE launch.  Arithmetic and orders:
+ *   mean_l     wave w of 8 adds, in one running sum per column, the invisible devices at the positions w, w + 8, .. of their ascending
+ *              list (x_l recomputed from x_0 through the l LayerNorms), then the visible ones at w, w + 8, ..; the 8 sums are added w
+ *              ascending, then one division by M.
+ *   u, c       per output, lane l of 64 multiplies its columns 2 l, 2 l + 1 (one fma), then an xor butterfly 32 .. 1; the bias last.
+ *              (Backward, du and dm: thread group q of ng = min(8, 512 / H) one fma chain over the rows q, q + ng, .., the ng sums
+ *              added q ascending.)
+ *   LayerNorm  as in cygym_comm_gat_decode (two-pass, lane l of 64 its columns 2 l, 2 l + 1, then an xor butterfly 32 .. 1).
+ *   softmax    of a row of s Q K^T: the maximum over all keys first (lane r of the row's 16 takes the keys 16 t + r, t ascending, then
+ *              an xor butterfly 1, 2, 4, 8), then p = exp(. - max), their sum the same way, then p / sum; O = p Vv with the keys as
+ *              the contraction index.
+ *   logp       lane i of 64 adds the visible positions i, i + 64, .. (two-sum), then the 64 (high, low) pairs are added ascending
+ *              and the pair is normalised; the entropy the same way, its low part added at the end.
+ * Backward, TWO launches (the second adds the workgroups' partials in ascending workgroup order).  It RECOMPUTES the forward of the row
+ * (nothing is handed over from the forward launch): x_l[V] of every layer is kept in the workgroup's slice of the workspace, the
+ * invisible devices' tokens are recomputed from x_0 wherever they are needed, and per layer, top down, q / k / v / the scores are
+ * formed again.  With G the gradient with respect to x_(l+1) (G_L[d] = g_ctx / M, plus Wt^T dz[d] for d in V, dz as in
+ * cygym_comm_actor_evaluate_backward): LayerNorm backward gives dy; dc = sum over invisible d of dy[d]; du = Wp^T dc; dm = Wv^T du;
+ * dO = dy_V Wp; dA = dO Vv^T; dS = A (dA - rowsum(dA A)); dQ = s dS K; dK = s dS^T Q; dVv = A^T dO;
+ * G_l = dy + dm / M (+ dQ Wq + dK Wk + dVv Wv on V);  the weight gradients are dQ^T X, dK^T X, dVv^T X + du m_l^T, dy_V^T O + dc u_l^T,
+ * sum of dy (proj.bias), sum of G xhat and of G (ln).  At the bottom dpre = G_0 where a + P[d] > 0; grad_tok_base[b] = sum_d dpre,
+ * grad_tok_dev[d] = sum_b dpre.  Orders: over the devices of a row, the matrix-core chain (contraction over V ascending) or wave w
+ * of 8 its positions w, w + 8, .. ascending and the 8 sums w ascending; over the rows of a workgroup ascending; over workgroups
+ * ascending.  No atomics: the same inputs give the same bits.
+ * Memory: nothing of size n M H, n M M or n M K is written (logits_out aside).  The workspace holds, per WORKGROUP, the row in flight:
+ * (L + 1) x_l[V], q, k, v, o, y and -- backward -- G, dy, do, dq, dk, dv: [M16][H + 4] floats each (M16 = M rounded up to 16), two
+ * strips [16][M16 + 4] of scores per wave, some [M16] vectors, and the partial gradients M H + 32 H + 32 + L (4 H H + 3 H) floats.
+ * Limits (CYGYM_EUNSUPPORTED beyond): H a multiple of 16 in 16 .. 128, K <= 32, 1 <= L <= CYGYM_GAT_MAX_LAYERS,
+ * M <= CYGYM_GAT_MAX_DEVICES (forward and backward).  CYGYM_EINVAL: a NULL handle, struct or mandatory pointer (forward: the inputs
+ * and the four outputs; backward: every input, g_*, every gradient), n < 1, K < 1, M < 1 or not the handle's, tok_stride < H, a matrix,
+ * tok_dev or the workspace off 16-byte alignment, a workspace smaller than the query's answer; nothing is written then.
+ * Out of scope: the layers reading a mask other than the stored one, the heads of ctx and the optimiser (the caller's), AMP. */
+int cygym_comm_gat_evaluate(cygym_handle* h, const cygym_comm_gat_eval* e, void* stream);
+int cygym_comm_gat_evaluate_backward(cygym_handle* h, const cygym_comm_gat_eval* e, void* stream);
+/* Bytes of workspace the two calls need on this handle (its M) for hidden width H and L layers; backward != 0: with the backward's
+ * buffers and partials.  0 on bad arguments.  It does not depend on n. */
+uint64_t cygym_comm_gat_eval_workspace_bytes(cygym_handle* h, int32_t H, int32_t L, int32_t backward);
 
 /* The tail of the reference's DDPG critic (do_agent.py:373-388: Q = fc3(relu(fc2(relu(fc1([s, a])))))) for n rows, and its backward:
  * what train_ddpg (do_agent.py:391-450) evaluates three times (:427 the target, :430 the critic loss, :441 the actor loss) and
