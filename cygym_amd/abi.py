@@ -266,6 +266,24 @@ class CatPpo(C.Structure):
                 ("clip", C.c_double), ("B", C.c_int32), ("K", C.c_int32)]
 
 
+class IppoAdv(C.Structure):
+    _fields_ = [("rew", C.c_void_p), ("val", C.c_void_p), ("done", C.c_void_p), ("next_value", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p),
+                ("gamma", C.c_float), ("gamma_lam", C.c_float), ("reward_scale", C.c_float), ("adv_clip", C.c_float), ("ret_clip", C.c_float),
+                ("T", C.c_int32), ("N", C.c_int32), ("norm_min_n", C.c_int32)]
+
+
+IPPO_HEAD_MAX_K = 32
+
+
+class IppoHead(C.Structure):
+    _fields_ = [("logp_hi", C.c_void_p), ("logp_lo", C.c_void_p), ("ent_dev", C.c_void_p), ("exp_logits", C.c_void_p), ("app_logits", C.c_void_p),
+                ("value", C.c_void_p), ("exp", C.c_void_p), ("app", C.c_void_p), ("old_logp", C.c_void_p), ("old_value", C.c_void_p),
+                ("adv", C.c_void_p), ("ret", C.c_void_p), ("stats", C.c_void_p), ("g_stats", C.c_void_p), ("d_logp_hi", C.c_void_p),
+                ("d_ent_dev", C.c_void_p), ("d_exp_logits", C.c_void_p), ("d_app_logits", C.c_void_p), ("d_value", C.c_void_p),
+                ("clip_eps", C.c_double), ("B", C.c_int32), ("E", C.c_int32), ("A", C.c_int32), ("exp_stride", C.c_int32), ("app_stride", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

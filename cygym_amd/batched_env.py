@@ -1507,6 +1507,100 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_critic_tail_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_critic_tail_backward")
         return gh, gw2, gb2, gw3, gb3
 
+    def ippo_advantages(self, rew, val, done, next_value, *, gamma: float = 0.99, lam: float = 0.95, reward_scale: float = 1e-1,
+                        adv_clip: float = 1e4, ret_clip: float = 1e4, norm_min_n: int = 8, out=None):
+        """The advantages of an IPPO / MAPPO rollout (IPPO.py:634-652) for a [T, N] step-major buffer in ONE launch
+        (cygym_ippo_advantages; include/cygym_abi.h states the arithmetic): rew, val float32 [T, N], done bool / uint8 [T, N],
+        next_value float32 [N].  Returns (adv, ret) float32 [T, N]: bit-equal to ippo_rollout.advantages' fp32 tensor ops up to the
+        normalisation, which (T N >= norm_min_n) uses float64 moments summed in a fixed order.  out: (adv, ret) to write into."""
+        f32 = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not f32(rew) or rew.dim() != 2:
+            raise ValueError("rew must be a float32 [T, N] tensor on the batch's device")
+        T, N = (int(x) for x in rew.shape)
+        if T < 1 or N < 1:
+            raise ValueError("ippo_advantages needs at least one step and one column")
+        if not f32(val) or tuple(val.shape) != (T, N):
+            raise ValueError(f"val must be a float32 [{T}, {N}] tensor on {self.device}")
+        if done.dtype not in (torch.bool, torch.uint8) or done.device != self.device or tuple(done.shape) != (T, N):
+            raise ValueError(f"done must be a bool or uint8 [{T}, {N}] tensor on {self.device}")
+        if not f32(next_value) or tuple(next_value.shape) != (N,):
+            raise ValueError(f"next_value must be a float32 [{N}] tensor on {self.device}")
+        keep = (rew.contiguous(), val.contiguous(), done.contiguous().view(torch.uint8), next_value.contiguous())
+        adv, ret = self._eval_out(out, ((T, N), (T, N)), "adv, ret")
+        e = abi.IppoAdv()
+        e.rew, e.val, e.done, e.next_value = (t.data_ptr() for t in keep)
+        e.adv, e.ret = adv.data_ptr(), ret.data_ptr()
+        e.gamma, e.gamma_lam = float(gamma), float(gamma) * float(lam)   # (the product in double, then fp32: as ippo_rollout.gae's tensor ops receive it)
+        e.reward_scale, e.adv_clip, e.ret_clip = float(reward_scale), float(adv_clip), float(ret_clip)
+        e.T, e.N, e.norm_min_n = T, N, int(min(max(int(norm_min_n), 0), 2 ** 31 - 1))
+        _lib.check(self.lib.cygym_ippo_advantages(self._h, C.byref(e), self._stream()), self._h, "cygym_ippo_advantages")
+        return adv, ret
+
+    def _ippo_head(self, logp_hi, logp_lo, ent_dev, exp_logits, app_logits, value, exp, app, old_logp, old_value, adv, ret, clip_eps):
+        """The IppoHead struct of ippo_ppo_loss / ippo_ppo_loss_backward, and what has to stay alive until the call has returned."""
+        if logp_hi.dtype != torch.float32 or logp_hi.device != self.device or logp_hi.dim() != 1 or int(logp_hi.shape[0]) < 1:
+            raise ValueError("logp_hi must be a float32 [B] tensor on the batch's device, B >= 1")
+        B = int(logp_hi.shape[0])
+        keep = {}
+        for name, t in (("logp_hi", logp_hi), ("logp_lo", logp_lo), ("ent_dev", ent_dev), ("value", value), ("old_logp", old_logp),
+                        ("old_value", old_value), ("adv", adv), ("ret", ret)):
+            if t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != (B,):
+                raise ValueError(f"{name} must be a float32 [{B}] tensor on {self.device}")
+            keep[name] = t.contiguous()
+        e = abi.IppoHead()
+        widths = []
+        for name, logits, idx in (("exp", exp_logits, exp), ("app", app_logits, app)):
+            K = 0 if logits is None else int(logits.shape[-1])
+            widths.append(K)
+            if K == 0:
+                continue
+            if K > abi.IPPO_HEAD_MAX_K:
+                raise ValueError(f"at most {abi.IPPO_HEAD_MAX_K} classes per head ({name}_logits has {K})")
+            if logits.dtype != torch.float32 or logits.device != self.device or logits.dim() != 2 or int(logits.shape[0]) != B or logits.stride(1) != 1:
+                raise ValueError(f"{name}_logits must be a float32 [{B}, K] tensor on {self.device} with unit inner stride")
+            if idx is None or idx.dtype != torch.int64 or idx.device != self.device or tuple(idx.shape) != (B,):
+                raise ValueError(f"{name} must be an int64 [{B}] tensor on {self.device}")
+            if B > 1 and logits.stride(0) < K:
+                logits = logits.contiguous()
+            keep[name + "_logits"], keep[name] = logits, idx.contiguous()
+            setattr(e, name + "_logits", logits.data_ptr())
+            setattr(e, name, keep[name].data_ptr())
+            setattr(e, name + "_stride", int(logits.stride(0)) if B > 1 else K)
+        for name in ("logp_hi", "logp_lo", "ent_dev", "value", "old_logp", "old_value", "adv", "ret"):
+            setattr(e, name, keep[name].data_ptr())
+        e.clip_eps, e.B, e.E, e.A = float(clip_eps), B, widths[0], widths[1]
+        return e, keep, (B, widths[0], widths[1])
+
+    def ippo_ppo_loss(self, logp_hi, logp_lo, ent_dev, exp_logits, app_logits, value, exp, app, old_logp, old_value, adv, ret,
+                      clip_eps: float = 0.2):
+        """What follows the network in an IPPO / MAPPO minibatch, in ONE launch (cygym_ippo_ppo_loss; include/cygym_abi.h states the
+        formulas): from the fused evaluate's (logp_hi, logp_lo, ent_dev) [B], the two heads' clean logits ([B, E], [B, A]; None or
+        zero columns: no such head) with the stored picks exp, app int64 [B], the clean value [B] and the stored old_logp, old_value,
+        adv, ret [B] (ret already clamped): stats [B, 4] = clipped surrogate, entropy, squared value error, squared clipped value
+        error per row.  The means, the maximum of the two value means and the coefficients stay with the caller."""
+        e, keep, (B, E, A) = self._ippo_head(logp_hi, logp_lo, ent_dev, exp_logits, app_logits, value, exp, app, old_logp, old_value, adv, ret, clip_eps)   # noqa: F841
+        stats = torch.empty((B, 4), dtype=torch.float32, device=self.device)
+        e.stats = stats.data_ptr()
+        _lib.check(self.lib.cygym_ippo_ppo_loss(self._h, C.byref(e), self._stream()), self._h, "cygym_ippo_ppo_loss")
+        return stats
+
+    def ippo_ppo_loss_backward(self, logp_hi, logp_lo, ent_dev, exp_logits, app_logits, value, exp, app, old_logp, old_value, adv, ret, g_stats,
+                               clip_eps: float = 0.2):
+        """The backward of ippo_ppo_loss (cygym_ippo_ppo_loss_backward, one launch, row-local, recomputes the forward): g_stats [B, 4]
+        float32 -> (d_logp_hi [B], d_ent_dev [B], d_exp_logits [B, E] or None, d_app_logits [B, A] or None, d_value [B])."""
+        e, keep, (B, E, A) = self._ippo_head(logp_hi, logp_lo, ent_dev, exp_logits, app_logits, value, exp, app, old_logp, old_value, adv, ret, clip_eps)   # noqa: F841
+        if g_stats.dtype != torch.float32 or g_stats.device != self.device or tuple(g_stats.shape) != (B, 4):
+            raise ValueError(f"g_stats must be a float32 [{B}, 4] tensor on {self.device}")
+        g = g_stats.contiguous()
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)  # noqa: E731
+        d_hi, d_ent, d_v = new(B), new(B), new(B)
+        d_el, d_al = (new(B, E) if E else None), (new(B, A) if A else None)
+        e.g_stats, e.d_logp_hi, e.d_ent_dev, e.d_value = g.data_ptr(), d_hi.data_ptr(), d_ent.data_ptr(), d_v.data_ptr()
+        e.d_exp_logits = None if d_el is None else d_el.data_ptr()
+        e.d_app_logits = None if d_al is None else d_al.data_ptr()
+        _lib.check(self.lib.cygym_ippo_ppo_loss_backward(self._h, C.byref(e), self._stream()), self._h, "cygym_ippo_ppo_loss_backward")
+        return d_hi, d_ent, d_el, d_al, d_v
+
     def take_status(self) -> int:
         """Read and clear the batch's status word: the OR of CG_E_TOPO_OVF | CG_E_BUSY_SAT | CG_E_DET_PENDING |
         CG_E_UNPINNED over the envs ticked since the last call (one 4-byte device-to-host copy; synchronises)."""

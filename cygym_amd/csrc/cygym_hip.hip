@@ -146,6 +146,14 @@ extern template __global__ void cat_ppo_kernel<false>(cygym_cat_ppo_desc, float,
 extern template __global__ void cat_ppo_kernel<true>(cygym_cat_ppo_desc, float, float);
 }  // namespace cygym_k
 
+// the IPPO / MAPPO update kernels live in their own unit (cg_inst_ippo.hip): declared, not instantiated, here
+namespace cygym_k {
+extern template __global__ void ippo_adv_kernel<false>(cygym_ippo_adv_desc);
+extern template __global__ void ippo_adv_kernel<true>(cygym_ippo_adv_desc);
+extern template __global__ void ippo_head_kernel<false>(cygym_ippo_head_desc, float, float);
+extern template __global__ void ippo_head_kernel<true>(cygym_ippo_head_desc, float, float);
+}  // namespace cygym_k
+
 // the mixture draw and the whole-actor launch with a tile table live in their own unit (cg_inst_mixture.hip): declared, not instantiated, here
 namespace cygym_k {
 extern template __global__ void mixture_draw_kernel<false>(cygym_mixture, int, const int32_t*, uint64_t, int64_t);
@@ -302,6 +310,8 @@ int cygym_sizeof(int32_t which) {
     case 33: return (int)sizeof(cygym_mixture);   // (index 32 stays unassigned)
     case 35: return (int)sizeof(cygym_comm_gat);   // (index 34 stays unassigned)
     case 37: return (int)sizeof(cygym_comm_gat_eval);   // (index 36 stays unassigned)
+    case 39: return (int)sizeof(cygym_ippo_adv_desc);   // (index 38 stays unassigned)
+    case 40: return (int)sizeof(cygym_ippo_head_desc);
     default: return -1;
   }
 }
@@ -1167,6 +1177,43 @@ static int cat_ppo_launch(cygym_handle* h, const cygym_cat_ppo_desc* e, void* st
 }
 int cygym_cat_ppo_loss(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream) { return cat_ppo_launch(h, e, stream, false, "cygym_cat_ppo_loss"); }
 int cygym_cat_ppo_loss_backward(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream) { return cat_ppo_launch(h, e, stream, true, "cygym_cat_ppo_loss_backward"); }
+
+int cygym_ippo_advantages(cygym_handle* h, const cygym_ippo_adv_desc* e, void* stream) {
+  const char* const who = "cygym_ippo_advantages";
+  if (!e || !e->rew || !e->val || !e->done || !e->next_value || !e->adv || !e->ret) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (e->T < 1 || e->N < 1 || !(e->gamma == e->gamma) || !(e->gamma_lam == e->gamma_lam) || !(e->reward_scale == e->reward_scale) ||
+      !(e->adv_clip == e->adv_clip) || !(e->ret_clip == e->ret_clip))
+    return fail(h, CYGYM_EINVAL, "%s: bad layout (T, N >= 1, the five scalars numbers)", who);
+  if (h) HIPCHK(h, hipSetDevice(h->device_id));
+  cygym_ippo_adv_desc arg = *e;
+  void* args[1] = {&arg};
+  const bool norm = (long long)e->T * (long long)e->N >= (long long)e->norm_min_n;
+  const void* k = norm ? (const void*)ippo_adv_kernel<true> : (const void*)ippo_adv_kernel<false>;
+  HIPCHK(h, hipLaunchKernel(k, dim3(1), dim3(IA_TPB), args, 0, (hipStream_t)stream));   // ONE workgroup: the fixed summation order
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+static int ippo_head_launch(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream, bool bwd, const char* who) {
+  if (!e || !e->logp_hi || !e->logp_lo || !e->ent_dev || !e->value || !e->old_logp || !e->old_value || !e->adv || !e->ret)
+    return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (e->B < 1 || e->E < 0 || e->A < 0 || !(e->clip_eps >= 0.0)) return fail(h, CYGYM_EINVAL, "%s: bad layout (B >= 1, E, A >= 0, clip_eps >= 0)", who);
+  if (e->E > IH_MAX_K || e->A > IH_MAX_K) return fail(h, CYGYM_EUNSUPPORTED, "%s: at most 32 classes per head", who);
+  if ((e->E > 0 && !(e->exp_logits && e->exp && (!bwd || e->d_exp_logits))) || (e->A > 0 && !(e->app_logits && e->app && (!bwd || e->d_app_logits))) ||
+      (bwd ? !(e->g_stats && e->d_logp_hi && e->d_ent_dev && e->d_value) : !e->stats))
+    return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (e->exp_stride < e->E || e->app_stride < e->A) return fail(h, CYGYM_EINVAL, "%s: rows closer than their width (exp_stride >= E, app_stride >= A)", who);
+  if (h) HIPCHK(h, hipSetDevice(h->device_id));
+  cygym_ippo_head_desc arg = *e;
+  float lo = (float)(1.0 - e->clip_eps), hi = (float)(1.0 + e->clip_eps);   // torch.clamp's Python-float bounds as fp32
+  void* args[3] = {&arg, &lo, &hi};
+  const void* k = bwd ? (const void*)ippo_head_kernel<true> : (const void*)ippo_head_kernel<false>;
+  HIPCHK(h, hipLaunchKernel(k, dim3((e->B + IH_TPB - 1) / IH_TPB), dim3(IH_TPB), args, 0, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+int cygym_ippo_ppo_loss(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream) { return ippo_head_launch(h, e, stream, false, "cygym_ippo_ppo_loss"); }
+int cygym_ippo_ppo_loss_backward(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream) { return ippo_head_launch(h, e, stream, true, "cygym_ippo_ppo_loss_backward"); }
 
 // What cygym_hmarl_decode and cygym_hmarl_sample_decode check alike (tr: the training launch, whose logits come from h0).
 static int hmarl_check(cygym_handle* h, const cygym_hmarl* q, const cygym_hmarl_train* tr, const cygym_actions* dst, const char* who) {

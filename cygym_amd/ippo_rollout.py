@@ -21,6 +21,11 @@ for every env; the cap's auto-reset reloads the snapshot the batch was created w
 bootstrap value, the clips and the normalisation of the advantages, the minibatch loop with the clipped-surrogate loss, gradient
 clipping and the optimiser step -- the evaluation of the stored decisions through CommActorCritic.evaluate, which on a batch runs
 the per-device part and its backward in the library (cygym_comm_actor_evaluate).
+
+`train` is IPPOCommBestResponse.train itself (:433-805) on a batch: one-decision rollouts on ONE persisting Turns object, the
+reference's step / update budgets, ppo_update after every rollout -- with fused_head the advantages and what follows the network in a
+minibatch's loss are launches of the library too (cygym_ippo_advantages, cygym_ippo_ppo_loss / _backward) -- and a strategy that
+policies.CommActorPolicy.from_strategy loads back.
 """
 from __future__ import annotations
 
@@ -196,18 +201,37 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
     is two addmm plus ONE launch (cygym_comm_actor_decode), tokens and logits never reach HBM, and `value` comes from the kernel.
     The decisions are those of the torch forward + fused sampling wherever the fp32 logits agree (the draws are the same).
     """
+    fused = _fused_net(net, fused_net, n_types)
+    ro = _collect(Turns(batch, role, opponent), net, n_decisions, greedy=greedy, generator=generator, n_types=n_types,
+                  randomize_on_reset=randomize_on_reset, tick_limit=max_ticks if max_ticks is not None else 4 * n_decisions + 8,
+                  fused_sampling=fused_sampling, fused=fused)
+    if ro is None:
+        raise RuntimeError("no decision of the role within the tick limit")
+    return ro
+
+
+def _fused_net(net, fused_net, n_types=None) -> bool:
     from .policies import CommActorCritic
     fused = isinstance(net, CommActorCritic) if fused_net is None else bool(fused_net)
     if fused and not isinstance(net, CommActorCritic):
         raise ValueError("fused_net needs a policies.CommActorCritic")
     if fused and n_types is not None and int(n_types) != net.n_types:
         raise ValueError(f"the net has {net.n_types} action types, n_types = {n_types}")
-    turns = Turns(batch, role, opponent)
+    return fused
+
+
+@torch.no_grad()
+def _collect(turns: Turns, net, n_decisions: int, *, greedy: bool = False, generator=None, n_types=None, randomize_on_reset: bool = True,
+             tick_limit: int, fused_sampling: bool = True, fused: bool = True):
+    """The loop of collect() on a Turns object that outlives it (train keeps ONE across its rollouts: the opponent's persisting
+    base_line and a mixture's state carry over): at most `tick_limit` ticks from where `turns` stands, until the role has decided
+    `n_decisions` times.  Returns the Rollout, or None when the role did not decide."""
+    batch, role = turns.batch, turns.role
     N, dev = batch.N, batch.device
     noop = DEFENDER_NOOP if role == HL.DEFENDER else ATTACKER_NOOP
     act = turns.act
     rec = {k: [] for k in ("state", "logp", "value", "reward", "raw_reward", "done", "per_dev_types", "exp", "app", "vis_mask")}
-    limit = max_ticks if max_ticks is not None else 4 * n_decisions + 8
+    limit = turns.ticks + int(tick_limit)
     while len(rec["logp"]) < n_decisions and turns.ticks < limit:
         turn, obs = turns.begin()
         if turn == role:
@@ -257,7 +281,7 @@ def collect(batch, role: str, net, opponent, n_decisions: int, *, greedy: bool =
             rec["vis_mask"].append(vis)
         turns.advance(randomize_on_reset)
     if not rec["logp"]:
-        raise RuntimeError("no decision of the role within the tick limit")
+        return None
     last_state = batch.observe(1 if role == HL.DEFENDER else 2)
     st = {k: torch.stack(v) for k, v in rec.items()}
     return Rollout(last_state=last_state, last_vis=batch.visibility_mask(role), **st)
@@ -295,9 +319,42 @@ def ppo_loss(logp, entropy, value, old_logp, old_value, adv, ret, *, clip_eps: f
     return pol - ent_coef * ent + vf_coef * v_loss, pol, v_loss, ent
 
 
+class _IppoHead(torch.autograd.Function):
+    """cygym_ippo_ppo_loss and its backward as one differentiable op: (logp_hi, ent_dev, exp_logits, app_logits, value) -> stats [B, 4]
+    (clipped surrogate, entropy, squared value error, squared clipped value error) for the stored (exp, app, old_logp, old_value, adv,
+    ret); logp_lo is a correction of the value and receives no gradient.  Saves only its inputs: the backward launch recomputes."""
+
+    @staticmethod
+    def forward(ctx, batch, clip_eps, hi, lo, ent, el, al, value, exp, app, old_logp, old_value, adv, ret):
+        det = lambda t: None if t is None else t.detach()  # noqa: E731
+        ins = tuple(det(t) for t in (hi, lo, ent, el, al, value, exp, app, old_logp, old_value, adv, ret))
+        ctx.batch, ctx.clip_eps, ctx.ins = batch, float(clip_eps), ins
+        return batch.ippo_ppo_loss(*ins, clip_eps=float(clip_eps))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_stats):
+        d_hi, d_ent, d_el, d_al, d_v = ctx.batch.ippo_ppo_loss_backward(*ctx.ins, g_stats.float(), clip_eps=ctx.clip_eps)
+        el, al = ctx.ins[3], ctx.ins[4]
+        if d_el is None and el is not None:
+            d_el = torch.zeros_like(el)   # (a head without classes: [B, 0])
+        if d_al is None and al is not None:
+            d_al = torch.zeros_like(al)
+        return None, None, d_hi, None, d_ent, d_el, d_al, d_v, None, None, None, None, None, None
+
+
+def head_loss(stats, *, ent_coef: float = ENT_COEF, vf_coef: float = VF_COEF):
+    """What stays in torch behind the head kernel (IPPO.py:751-767 on the columns' means): (loss, policy loss, value loss, mean
+    entropy) from stats [B, 4]; the maximum of the two value means keeps torch's rule at a tie."""
+    m = stats.mean(dim=0)
+    pol, v_loss = -m[0], torch.max(m[2], m[3])
+    ent = torch.nan_to_num(m[1], nan=0.0, posinf=0.0, neginf=0.0)
+    return pol - ent_coef * ent + vf_coef * v_loss, pol, v_loss, ent
+
+
 def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minibatch_size: int = 256, generator=None, fused=None,
                gamma: float = 0.99, lam: float = 0.95, clip_eps: float = CLIP_EPS, ent_coef: float = ENT_COEF, vf_coef: float = VF_COEF,
-               max_grad_norm: float = MAX_GRAD_NORM, first_row_mask: bool = False):
+               max_grad_norm: float = MAX_GRAD_NORM, first_row_mask: bool = False, fused_head: bool = False, max_updates: int | None = None):
     """The PPO update of IPPOCommBestResponse.train (IPPO.py:626-781) on a Rollout: the bootstrap value from rollout.last_state,
     `advantages`, then `epochs` passes over the T N rows, flattened and shuffled (torch.randperm with `generator`) into minibatches
     of `minibatch_size`; per minibatch net.evaluate (fused on `batch` by default, see CommActorCritic.evaluate), `ppo_loss`,
@@ -316,8 +373,19 @@ def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minib
     instead masks the adjacency of the WHOLE minibatch with the visibility of the minibatch's first row (`v0 = mb_vis[0]`,
     IPPO.py:713-717) -- for its one-row updates the same thing; first_row_mask=True reproduces that for larger minibatches (the
     log-probabilities are still selected by each row's own mask, :725-737) on the torch path; the fused path reads one mask per
-    row, so first_row_mask with fused=True is refused above one row per minibatch (with one row the two masks coincide)."""
+    row, so first_row_mask with fused=True is refused above one row per minibatch (with one row the two masks coincide).
+
+    fused_head=True (needs `batch` and the fused evaluate: fused=True for a net with attention layers): the advantages come from ONE
+    launch (cygym_ippo_advantages) and each minibatch's loss from net.evaluate_pieces plus ONE launch each way (cygym_ippo_ppo_loss /
+    _backward behind one autograd.Function) and the six small ops of `head_loss`, instead of some forty element-wise launches each
+    way.  The default is the torch head.  max_updates: stop before the optimiser step that would exceed it (train's update budget,
+    IPPO.py:691)."""
     gat = bool(getattr(net, "gat_layers", 0))
+    if fused_head:
+        if batch is None:
+            raise ValueError("fused_head runs through a BatchedCyberDefenseEnv: pass batch=")
+        if fused is False or (gat and not fused):
+            raise ValueError("fused_head reads the fused evaluate's pieces: fused=True" + (" (a net with attention layers defaults to the torch path)" if gat else ""))
     if gat and fused and batch is None:
         raise NotImplementedError("the fused evaluate of a net with attention layers runs through a BatchedCyberDefenseEnv: pass batch= "
                                   "(without it ppo_update runs the torch path, fused=False)")
@@ -326,7 +394,11 @@ def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minib
                                   "one: the fused evaluate does not (fused=False)")
     with torch.no_grad():
         next_value = (net(rollout.last_state, rollout.last_vis) if gat else net(rollout.last_state))["value"].reshape(-1)
-        adv, ret = advantages(rollout, next_value, gamma, lam)
+        if fused_head:
+            adv, ret = batch.ippo_advantages(rollout.reward.to(torch.float32), rollout.value.to(torch.float32), rollout.done, next_value.to(torch.float32),
+                                             gamma=gamma, lam=lam, reward_scale=REWARD_SCALE, adv_clip=ADV_CLIP, ret_clip=RET_CLIP, norm_min_n=ADV_NORM_MIN_N)
+        else:
+            adv, ret = advantages(rollout, next_value, gamma, lam)
     T, N = rollout.logp.shape
     B = T * N
     flat = lambda t: t.reshape(B, *t.shape[2:])  # noqa: E731
@@ -336,15 +408,22 @@ def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minib
     for _ in range(int(epochs)):
         perm = torch.randperm(B, generator=generator).to(state.device)
         for start in range(0, B, int(minibatch_size)):
+            if max_updates is not None and updates >= int(max_updates):
+                break
             mb = perm[start: start + int(minibatch_size)]
             adv_mb, ret_mb = adv[mb], ret[mb].clamp(-VALUE_TARGET_CLIP, VALUE_TARGET_CLIP)
-            if gat:
+            if fused_head:
+                hi, lo, ent_dev, el, al, value = net.evaluate_pieces(state[mb], types[mb], vis[mb], batch)
+                stats = _IppoHead.apply(batch, clip_eps, hi, lo, ent_dev, el, al, value, exp[mb], app[mb], old_logp[mb], old_value[mb], adv_mb, ret_mb)
+                loss, pol, v_loss, ent_mean = head_loss(stats, ent_coef=ent_coef, vf_coef=vf_coef)
+            elif gat:
                 ev = vis[mb][:1].expand(len(mb), -1) if first_row_mask and not fused else None   # (fused: one row, the same mask)
                 logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], batch=batch if fused else None, fused=bool(fused), eval_vis=ev)
             else:
                 logp, ent, value = net.evaluate(state[mb], types[mb], vis[mb], exp[mb], app[mb], batch=batch, fused=fused)
-            loss, pol, v_loss, ent_mean = ppo_loss(logp, ent, value, old_logp[mb], old_value[mb], adv_mb, ret_mb, clip_eps=clip_eps,
-                                                   ent_coef=ent_coef, vf_coef=vf_coef)
+            if not fused_head:
+                loss, pol, v_loss, ent_mean = ppo_loss(logp, ent, value, old_logp[mb], old_value[mb], adv_mb, ret_mb, clip_eps=clip_eps,
+                                                       ent_coef=ent_coef, vf_coef=vf_coef)
             if not bool((torch.isfinite(adv_mb).all() & torch.isfinite(ret_mb).all() & torch.isfinite(loss)).item()):
                 continue
             opt.zero_grad(set_to_none=True)
@@ -354,3 +433,74 @@ def ppo_update(net, rollout: Rollout, opt, *, batch=None, epochs: int = 1, minib
             updates += 1
             last = {"loss": loss.detach(), "policy_loss": pol.detach(), "value_loss": v_loss.detach(), "entropy": ent_mean.detach(), "grad_norm": norm.detach()}
     return dict(last, updates=updates)
+
+
+POLICY_LR = 1e-4                             # IPPO.py:30
+
+
+def update_plan(budget_type: str, remaining, rows: int, ppo_epochs: int, minibatch_size: int, single_update_per_rollout: bool):
+    """(epochs, minibatch size) of one rollout's update (IPPO.py:666-678): single_update_per_rollout forces one epoch and one
+    minibatch of all rows; under an update budget with fewer updates left than the nominal epochs x minibatches, ONE epoch whose
+    minibatches are sized so that at most the remaining updates are made."""
+    if single_update_per_rollout:
+        return 1, int(rows)
+    epochs, mb = int(ppo_epochs), int(minibatch_size)
+    if budget_type == "updates":
+        nominal = epochs * ((rows + mb - 1) // mb)
+        if remaining < nominal:
+            epochs, mb = 1, max(1, (rows + int(remaining) - 1) // int(remaining))
+    return epochs, mb
+
+
+def train(batch, role: str, net, opponent, *, T: int = 15_000, rollout_len: int = 1, ppo_epochs: int = 1, minibatch_size: int = 256,
+          budget_type: str = "steps", budget=None, single_update_per_rollout: bool = False, opt=None, lr: float = POLICY_LR, fused=None,
+          fused_head=None, generator=None):
+    """IPPOCommBestResponse.train (IPPO.py:433-805; MAPPO.py the same) on a batch: one-decision rollouts of `role` against
+    `opponent` (what collect() accepts), each followed by ppo_update, under the reference's budget accounting.
+
+    ONE Turns object lives across all rollouts: the opponent's persisting base_line and a MixturePolicy's state carry over, as the
+    reference's one env does.  Each rollout runs until the role has decided once (`while len(local_batch) == 0`, :503 -- rollout_len
+    only enters the reference's unused max_collect, and is accepted and ignored alike), then updates.
+    steps counts ticks of the batch, both players: the reference's steps_done of each env, which tick in lock step.
+    budget (default T) with budget_type="steps": never exceeded; the collection stops in mid-rollout as :605 does, and a rollout cut
+    before the role decided ends the training without an update (:625).  budget_type="updates": optimiser steps, with the shrink rule
+    of :672-678 on N = the rollout's rows (`update_plan`).  single_update_per_rollout: one epoch, one minibatch of all rows.
+    opt defaults to Adam at `lr`.  fused: the evaluate's path as in ppo_update (None: fused for a net without attention layers);
+    fused_head=None: the fused head whenever the evaluate is fused.
+    Returns {"strategy" (CommActorPolicy(net, role).to_strategy()), "net", "opt", "steps", "updates", "rollouts", "total_reward" ([N]
+    float64: the sum of the learner's raw rewards, :581), "last" (the last update's loss pieces as 0-dim tensors)}.
+    Out of scope: AMP, the progress prints, the wall-clock budget."""
+    from .policies import CommActorPolicy
+    if budget_type not in ("steps", "updates"):
+        raise ValueError("budget_type must be 'steps' or 'updates'")
+    budget = int(T if budget is None else budget)
+    if single_update_per_rollout:
+        ppo_epochs = 1
+    gat = bool(getattr(net, "gat_layers", 0))
+    eval_fused = (not gat) if fused is None else bool(fused)
+    fused_head = eval_fused if fused_head is None else bool(fused_head)
+    if opt is None:
+        opt = torch.optim.Adam(net.parameters(), lr=lr)
+    fused_net = _fused_net(net, None)
+    turns = Turns(batch, role, opponent)
+    steps = updates = rollouts = 0
+    total_reward = torch.zeros(batch.N, dtype=torch.float64, device=batch.device)
+    last = {}
+    exhausted = lambda: (steps if budget_type == "steps" else updates) >= budget  # noqa: E731
+    while not exhausted():
+        rollouts += 1
+        t0 = turns.ticks
+        ro = _collect(turns, net, 1, generator=generator, tick_limit=(budget - steps) if budget_type == "steps" else 4 * (turns.cap + 2), fused=fused_net)
+        steps += turns.ticks - t0
+        if ro is None:
+            break
+        total_reward += ro.raw_reward.sum(dim=0)
+        rows = int(ro.logp.numel())
+        epochs, mb = update_plan(budget_type, budget - updates, rows, ppo_epochs, minibatch_size, single_update_per_rollout)
+        out = ppo_update(net, ro, opt, batch=batch, epochs=epochs, minibatch_size=mb, generator=generator, fused=eval_fused if (gat or fused is not None) else None,
+                         fused_head=fused_head, max_updates=(budget - updates) if budget_type == "updates" else None)
+        updates += out.pop("updates")
+        if out:
+            last = out
+    return {"strategy": CommActorPolicy(net, role).to_strategy(), "net": net, "opt": opt, "steps": steps, "updates": updates, "rollouts": rollouts,
+            "total_reward": total_reward, "last": last}

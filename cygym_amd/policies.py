@@ -1023,19 +1023,8 @@ class CommActorCritic(nn.Module):
                 raise ValueError("the fused evaluate runs through a BatchedCyberDefenseEnv: pass batch=")
             if dtype not in (None, torch.float32):
                 raise ValueError("the fused evaluate is fp32")
-            a, P = self.factors(state.float())
-            if self.gat_layers:
-                lp = tuple(p for g in self.gats for p in (g.q.weight, g.k.weight, g.v.weight, g.proj.weight, g.proj.bias, g.ln.weight, g.ln.bias))
-                hi, ent, ctx, lo = _CommGatEvaluate.apply(batch, tgt.to(torch.uint8).contiguous(), visb.to(torch.uint8).contiguous(), a, P,
-                                                          self.dev_type_head.weight, self.dev_type_head.bias, *lp)
-            else:
-                hi, ent, ctx, lo = _CommEvaluate.apply(batch, tgt.to(torch.uint8).contiguous(), visb.to(torch.uint8).contiguous(), a, P,
-                                                       self.dev_type_head.weight, self.dev_type_head.bias)
+            hi, lo, ent, exp_logits, app_logits, value = self.evaluate_pieces(state, tgt, visb, batch)
             logp = hi.double() + lo.detach().double()
-            dt = torch.float32
-            exp_logits = clean(self._lin(self.exp_head, ctx, dt))
-            app_logits = clean(self._lin(self.app_head, ctx, dt)) if self.app_head is not None else None
-            value = clean(self._lin(self.v_head[2], torch.relu(self._lin(self.v_head[0], ctx, dt)), dt).squeeze(-1))
         else:
             out = self.forward(state, (visb if eval_vis is None else eval_vis).to(torch.float32), dtype=dtype)
             lp = torch.log_softmax(out["per_dev_type_logits"], dim=-1)                      # [B, D, K]
@@ -1049,6 +1038,31 @@ class CommActorCritic(nn.Module):
                 logp = logp + lp.gather(-1, pick.long()[:, None])[:, 0].double()
                 ent = ent - (lp.exp() * lp).sum(dim=-1)
         return logp, ent, value
+
+    def evaluate_pieces(self, state, types, vis, batch):
+        """The fused evaluate up to where the Categoricals of the two heads begin -- what cygym_ippo_ppo_loss reads: (logp_hi, logp_lo,
+        ent_dev) [B] from cygym_comm_actor_evaluate (cygym_comm_gat_evaluate for a net with attention layers) behind its
+        autograd.Function, and the heads of the pooled context in torch: exp_logits [B, E], app_logits [B, A] or None, value [B], all
+        through nan_to_num.  logp_hi + logp_lo in float64 is the devices' summed log-probability; logp_lo carries no gradient.
+        types [B, D] integer (clamped here as evaluate clamps them), vis [B, D] (visible where > 0.5, or bool)."""
+        if batch is None:
+            raise ValueError("the fused evaluate runs through a BatchedCyberDefenseEnv: pass batch=")
+        visb = vis > 0.5 if vis.dtype != torch.bool else vis
+        tgt = torch.where(visb, types.long().clamp(0, self.n_types - 1), torch.zeros_like(types, dtype=torch.long))
+        clean = lambda t: torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0)  # noqa: E731
+        a, P = self.factors(state.float())
+        if self.gat_layers:
+            lp = tuple(p for g in self.gats for p in (g.q.weight, g.k.weight, g.v.weight, g.proj.weight, g.proj.bias, g.ln.weight, g.ln.bias))
+            hi, ent, ctx, lo = _CommGatEvaluate.apply(batch, tgt.to(torch.uint8).contiguous(), visb.to(torch.uint8).contiguous(), a, P,
+                                                      self.dev_type_head.weight, self.dev_type_head.bias, *lp)
+        else:
+            hi, ent, ctx, lo = _CommEvaluate.apply(batch, tgt.to(torch.uint8).contiguous(), visb.to(torch.uint8).contiguous(), a, P,
+                                                   self.dev_type_head.weight, self.dev_type_head.bias)
+        dt = torch.float32
+        exp_logits = clean(self._lin(self.exp_head, ctx, dt))
+        app_logits = clean(self._lin(self.app_head, ctx, dt)) if self.app_head is not None else None
+        value = clean(self._lin(self.v_head[2], torch.relu(self._lin(self.v_head[0], ctx, dt)), dt).squeeze(-1))
+        return hi, lo, ent, exp_logits, app_logits, value
 
     def packed(self, batch=None):
         """What cygym_comm_actor_decode reads, as a dict (BatchedCyberDefenseEnv.comm_actor_decode): the table tok_dev, the packed
@@ -1104,6 +1118,53 @@ class CommActorPolicy:
         self.noop = 8 if role == "defender" else 3      # DEFENDER_NOOP, ATTACKER_NOOP (IPPO.py:25-26)
         self.n_types = net.n_types
         self.action_types = [t for t in range(net.n_types) if t != self.noop]
+
+    STRATEGY_KEYS = ("ippo", "mappo", "marl")      # the keys do_agent.py:733-735 reads, in its order
+
+    @classmethod
+    def from_strategy(cls, mapping, batch, role: str, greedy: bool = True):
+        """From a reference strategy's type_mapping (its "ippo", "mappo" or "marl" entry, or that entry itself).  The entry is an
+        object with a `.net` whose state_dict() carries CommActorCritic's parameter names (what the reference's IPPOCommPolicy is;
+        nothing of the reference is imported), a dict {"state_dict": ...} (what to_strategy() writes), or a plain state dict of
+        tensors / arrays.  The dimensions are read off the shapes; `gats.*` entries mean attention layers (USE_GAT = True)."""
+        import numpy as np
+        entry = mapping
+        if isinstance(mapping, dict) and any(k in mapping for k in cls.STRATEGY_KEYS):
+            entry = next(mapping[k] for k in cls.STRATEGY_KEYS if mapping.get(k) is not None)
+        if hasattr(entry, "net") and hasattr(entry.net, "state_dict"):
+            sd = entry.net.state_dict()
+        elif isinstance(entry, dict) and "state_dict" in entry:
+            sd = entry["state_dict"]
+        elif hasattr(entry, "state_dict") and not isinstance(entry, dict):
+            sd = entry.state_dict()
+        else:
+            sd = entry
+        if not isinstance(sd, dict) and not hasattr(sd, "items"):
+            raise ValueError("the strategy entry holds neither a .net, a 'state_dict' nor a state dict")
+        sd = {k: (v.detach().clone() if torch.is_tensor(v) else torch.from_numpy(np.array(v))).to(torch.float32) for k, v in sd.items()}
+        need = ("state_proj.weight", "id_emb.weight", "merge.weight", "dev_type_head.weight", "exp_head.weight", "v_head.0.weight", "v_head.2.weight")
+        missing = [k for k in need if k not in sd]
+        if missing:
+            raise ValueError(f"the state dict lacks {missing}: not a per-device actor-critic (IPPO / MAPPO) strategy")
+        hidden, state_dim = (int(x) for x in sd["state_proj.weight"].shape)
+        D, n_types, E = int(sd["id_emb.weight"].shape[0]), int(sd["dev_type_head.weight"].shape[0]), int(sd["exp_head.weight"].shape[0])
+        A = int(sd["app_head.weight"].shape[0]) if "app_head.weight" in sd else 0
+        layers = {int(k.split(".")[1]) for k in sd if k.startswith("gats.")}
+        if layers and layers != set(range(len(layers))):
+            raise ValueError(f"the attention layers of the state dict are numbered {sorted(layers)}")
+        if D != batch.M:
+            raise ValueError(f"the strategy was trained on D = {D} devices, the batch has {batch.M}")
+        if state_dim != batch.role_width(role):
+            raise ValueError(f"the strategy reads {state_dim} state columns, the {role} view has {batch.role_width(role)}")
+        net = CommActorCritic(state_dim, n_types, D, E, A, hidden=hidden, gat_layers=len(layers))
+        net.load_state_dict(sd)
+        return cls(net.eval().to(batch.device), role, greedy=greedy)
+
+    def to_strategy(self, key: str = "ippo"):
+        """The dict form of the strategy, {"ippo": {"state_dict": {name: CPU tensor}}}, which from_strategy reads back."""
+        if key not in self.STRATEGY_KEYS:
+            raise ValueError(f"key must be one of {self.STRATEGY_KEYS}")
+        return {key: {"state_dict": {k: v.detach().to("cpu").clone() for k, v in self.net.state_dict().items()}}}
 
     @torch.no_grad()
     def write(self, batch, act, rows, obs):

@@ -1468,6 +1468,99 @@ typedef struct cygym_cat_ppo_desc {
 int cygym_cat_ppo_loss(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream);
 int cygym_cat_ppo_loss_backward(cygym_handle* h, const cygym_cat_ppo_desc* e, void* stream);
 
+/* The two pieces of an IPPO / MAPPO update (IPPOCommBestResponse.train, IPPO.py:626-781; MAPPO.py the same) that are chains of
+ * element-wise ops: the advantages of the rollout (:634-652) and, per minibatch, what follows the network in evaluate plus the per-row
+ * terms of the loss (:740-767).  All DEVICE pointers, contiguous unless a stride is named.  h may be NULL, as for cygym_ppo_finish.
+ *
+ * cygym_ippo_advantages: a [T][N] step-major buffer (the N envs of a batch tick in lock step) in ONE launch. */
+typedef struct cygym_ippo_adv_desc {
+  const float* rew;          /* [T][N] the stored (shaped, clipped) rewards                                              */
+  const float* val;          /* [T][N] the value estimates stored with the steps                                         */
+  const uint8_t* done;       /* [T][N] 1 where the episode ended with the step                                           */
+  const float* next_value;   /* [N] the value of the state the rollout ended in (:626-632)                               */
+  float* adv;                /* out [T][N]; must not overlap an input                                                    */
+  float* ret;                /* out [T][N]; must not overlap an input                                                    */
+  float gamma;               /* g  = (float)gamma                                                                        */
+  float gamma_lam;           /* gl = (float)(gamma * lam), the product formed in double as Python forms it               */
+  float reward_scale;        /* REWARD_SCALE (1e-1)                                                                      */
+  float adv_clip;            /* ADV_CLIP (1e4)                                                                           */
+  float ret_clip;            /* RET_CLIP (1e4)                                                                           */
+  int32_t T, N;
+  int32_t norm_min_n;        /* ADV_NORM_MIN_N (8): the advantages are normalised iff T N >= norm_min_n                  */
+} cygym_ippo_adv_desc;
+/* With v[T] = clean(next_value), last[T] = 0, clean(x) = x where x is finite and 0 elsewhere, for t = T - 1 .. 0 per column:
+ *     r       = nan_to_num(rew[t], nan = 0, +-inf = +-1e6) * reward_scale
+ *     v[t]    = clean(val[t]);   nt = 1 - done[t]
+ *     delta   = (r + (g * v[t + 1]) * nt) - v[t]
+ *     last[t] = delta + ((gl * nt) * last[t + 1])
+ *     adv[t]  = clamp(nan_to_num(last[t], nan = 0, +-inf = +-adv_clip), +-adv_clip)
+ *     ret[t]  = clamp(nan_to_num(last[t] + v[t], nan = 0, +-inf = +-ret_clip), +-ret_clip)
+ * every operation rounding to fp32 on its own, no contraction, in the operation order of compute_gae (:301-310): without the
+ * normalisation adv and ret are BIT-EQUAL to the reference's fp32 tensor ops.
+ * T N >= norm_min_n: with n = T N, x[i] the clipped advantages in memory order, d[i] = x[i] - x[0] in float64,
+ *     mean = (float)(x[0] + sum d / n);   std = max((float)sqrt(max((sum d^2 - (sum d)^2 / n) / (n - 1), 0)), 1e-3)   (n = 1: std = 1)
+ *     adv[i] = clamp((x[i] - mean) / std, +-3)                  (two fp32 operations)
+ *   the sums in float64 in a FIXED order (lane j of the one workgroup sums i = j, j + 1024, ... in ascending order, the lanes are folded
+ *   in a binary tree), no atomics: the same inputs give the same bits.  A constant buffer has both sums 0 exactly: adv = 0 exactly.
+ *   (The reference forms mean and std in fp32; the float64 sums are the closer of the two to the exact value.)
+ * CYGYM_EINVAL (nothing is written): a NULL struct or pointer, T or N < 1, a NaN among the five scalars. */
+int cygym_ippo_advantages(cygym_handle* h, const cygym_ippo_adv_desc* e, void* stream);
+
+/* cygym_ippo_ppo_loss / _backward: for the B rows of a minibatch, from what cygym_comm_actor_evaluate / cygym_comm_gat_evaluate
+ * returned (logp_hi, logp_lo, ent_dev), the two heads of the pooled context and the value (through nan_to_num already, as evaluate
+ * leaves them), the stored decision and the stored quantities. */
+typedef struct cygym_ippo_head_desc {
+  const float* logp_hi;      /* [B] the compensated sum of the devices' log-probabilities, high part                              */
+  const float* logp_lo;      /* [B] ... low part (a correction of the value: it receives no gradient)                             */
+  const float* ent_dev;      /* [B] the summed entropy of the visible devices' Categoricals                                       */
+  const float* exp_logits;   /* [B] rows of E floats, exp_stride apart; NULL when E = 0                                           */
+  const float* app_logits;   /* [B] rows of A floats, app_stride apart; NULL when A = 0                                           */
+  const float* value;        /* [B]                                                                                               */
+  const int64_t* exp;        /* [B] the stored exploit index (outside 0 .. E - 1: selects no class, never used to address); NULL when E = 0 */
+  const int64_t* app;        /* [B] the stored app index; NULL when A = 0                                                         */
+  const float* old_logp;     /* [B] the log-probability stored with the decision                                                  */
+  const float* old_value;    /* [B] the value stored with the decision                                                            */
+  const float* adv;          /* [B]                                                                                               */
+  const float* ret;          /* [B] clamped to +-VALUE_TARGET_CLIP by the caller                                                  */
+  float* stats;              /* forward out [B][4]: surrogate, entropy, squared value error, squared clipped value error         */
+  const float* g_stats;      /* backward in [B][4]: gradient of the loss with respect to stats                                    */
+  float* d_logp_hi;          /* backward out [B]                                                                                  */
+  float* d_ent_dev;          /* backward out [B]                                                                                  */
+  float* d_exp_logits;       /* backward out [B][E] contiguous; NULL when E = 0                                                   */
+  float* d_app_logits;       /* backward out [B][A] contiguous; NULL when A = 0                                                   */
+  float* d_value;            /* backward out [B]                                                                                  */
+  double clip_eps;           /* the reference's Python float (0.2); lo = (float)(1.0 - clip_eps), hi = (float)(1.0 + clip_eps)    */
+  int32_t B, E, A;
+  int32_t exp_stride;        /* floats between two rows of exp_logits (>= E)                                                      */
+  int32_t app_stride;        /* floats between two rows of app_logits (>= A)                                                      */
+  int32_t reserved;          /* 0                                                                                                 */
+} cygym_ippo_head_desc;
+/* Forward, ONE launch, one lane per row, fp32 (expf / logf, not the fast forms), every sum over classes in ASCENDING class order.  For
+ * each head with K > 0 classes l[0 .. K - 1] and stored index a:
+ *     lp[k] = (l[k] - max) - log(sum_k exp(l[k] - max));   lp_a = lp[a];   S = sum_k exp(lp[k]) lp[k]          (log_softmax, :741-749)
+ *   then, with clean(x) = x where x is finite and 0 elsewhere,
+ *     s   = (double)logp_hi + (double)logp_lo + (double)lp_a(exp) + (double)lp_a(app)                           (float64, in this order)
+ *     rho = expf((float)clamp(clean(s) - (double)clean(old_logp), +-20))
+ *     stats[0] = min(rho adv, clamp(rho, lo, hi) adv)
+ *     stats[1] = (ent_dev - S(exp)) - S(app)
+ *     stats[2] = (v - ret)^2,   v = clean(value)
+ *     stats[3] = ((old_value + clamp(v - old_value, +-0.2)) - ret)^2
+ *   so that, as ippo_rollout.ppo_loss forms it from the columns' means (:751-767),
+ *     loss = -mean(stats[:, 0]) - ent_coef nan_to_num(mean(stats[:, 1])) + vf_coef max(mean(stats[:, 2]), mean(stats[:, 3])).
+ * Backward, ONE launch, recomputes the above from the same inputs; g = g_stats[row]:
+ *     d_s          = g[0] w adv rho   where s is finite and |clean(s) - clean(old_logp)| <= 20, else 0
+ *     d_logp_hi    = d_s;   d_ent_dev = g[1]
+ *     d_logits[k]  = d_s (1[k = a] - p[k]) - g[1] p[k] (lp[k] - S)     for each head, p[k] = exp(lp[k]) (second term 0 where p[k] = 0)
+ *     d_value      = 2 g[2] (v - ret) + 2 g[3] (v_clipped - ret) 1[|v - old_value| <= 0.2]   where value is finite, else 0
+ *   w is the tie rule of the minimum and of the clamp as stated for cygym_cat_ppo_loss; every clamp passes the gradient inside its
+ *   range, the ends included; nan_to_num passes it only where its input was finite.
+ * Both directions are row-local: no partials, no atomics; the same inputs give the same bits.
+ * CYGYM_EUNSUPPORTED: E or A > 32.  CYGYM_EINVAL: a NULL struct or mandatory pointer (forward: the inputs a head with classes needs
+ * and stats; backward: the inputs, g_stats and the outputs a head with classes needs), B < 1, E or A < 0, clip_eps negative or NaN,
+ * exp_stride < E or app_stride < A; nothing is written then. */
+int cygym_ippo_ppo_loss(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream);
+int cygym_ippo_ppo_loss_backward(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream);
+
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`
  * (outputs `o`, as cygym_step), then, in the same workgroups, build the role view mlp->obs_role of the state the tick left
