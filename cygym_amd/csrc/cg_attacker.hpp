@@ -3,6 +3,8 @@
 #ifndef CG_ATTACKER_HPP
 #define CG_ATTACKER_HPP
 
+#include "cg_spread_words.hpp"   // the spread's device-major passes on packed words: plain host-and-device integer code (tests/spread_words_probe.cpp)
+
 // ---------------- attacker ----------------
 #define T_INF 0xFFFFFFFFu
 constexpr int LONG_ROW = 8;
@@ -627,7 +629,13 @@ __device__ __forceinline__ void opaque_uniform(T& v) {
 // on it belong to the rare iteration that draws.  (Spill slots of the WIDE kernel 68 -> 25, v_writelane in the spread 57 -> 17;
 // tests/test_spread_parking_isa_cpu.py.  Not re-formed, each tried and dropped, PERFLOG.md (r12_spread_parking): the lane id per iteration,
 // the last blocked word's index, the tick's header scalars.)
-template <int MCT, bool WIDE, class KP>
+// WORDS (256 devices, the per-tick kernels; a constant of the kernel like ARRIVALS_JOINT): the source compaction and the T / candidate
+// pass work on ONE dword of the byte planes per lane, four devices, through the host-and-device helpers of cg_spread_words.hpp
+// (tests/spread_words_probe.cpp): the sources' places from a popcount and a wave scan, the four T words by sign-extending a
+// three-bit field and stored as 128 bits, the candidate masks as one byte per lane pair, the two lowest candidates from the ballot
+// of the lanes' nibbles.  Set-up of the slowest 1 % of spread envs 5.5 k -> 3.85 k cycles (PERFLOG.md, r14_spread_words); the apply
+// pass in word form measured -0.3 k on its phase and was dropped on the assembly (v_readlane in the spread over the bound).
+template <int MCT, bool WIDE, bool WORDS, class KP>
 __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const int32_t* expl, int ex0, int n_expl) {
   const int M = e.M, E1 = P.t.E > 0 ? P.t.E - 1 : 0;
   const int lane = e.lane;
@@ -636,7 +644,17 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
   uint64_t* cand = (uint64_t*)e.marks;          // [MC] candidate-device bitmask (LDS copy for the per-lane rescans)
   // :1127 snapshot of the sources, once per action: compact list in id order
   int n_src = 0;
-  {
+  static_assert(!WORDS || MCT == 4, "one dword of a byte plane per lane: 256 devices");
+  if constexpr (WORDS) {
+    // lane l owns the devices 4 l .. 4 l + 3: lane-major, byte-minor order IS ascending device id
+    const uint32_t sb = cg_sw_sources(((const uint32_t*)e.flags)[lane]);
+    const int cnt = __popc(sb);
+    const int incl = wave_incl_scan(cnt, lane);
+    n_src = __builtin_amdgcn_readlane(incl, 63);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if ((sb >> (8 * j)) & 1u) slist[incl - cnt + cg_sw_sources_below(sb, j)] = (uint16_t)(4 * lane + j);
+  } else {
     uint32_t fj[MCT];
 #pragma unroll
     for (int c = 0; c < MCT; ++c) fj[c] = e.flags[c * WAVE + lane < M ? c * WAVE + lane : 0];
@@ -667,7 +685,21 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
     const uint8_t ebit = (uint8_t)(1u << raw);
     // ---- T words and candidate masks from the flag / vulnerability bytes (device-major, one round trip) ----
     int u1 = -1, u2 = -1;   // the two lowest candidates (uniform): a full row's first pick is the lowest one that is not itself
-    {
+    if constexpr (WORDS) {
+      // one flag word and one vulnerability word per lane; T[4 l .. 4 l + 3] leaves as one 128-bit store
+      const uint32_t y = cg_sw_elig(((const uint32_t*)e.flags)[lane], ((const uint32_t*)e.vul)[lane], raw);
+      ((uint4*)T)[lane] = make_uint4(cg_sw_tword(y, 0), cg_sw_tword(y, 1), cg_sw_tword(y, 2), cg_sw_tword(y, 3));
+      // cand[] keeps its layout (bit i of cand[c] <-> device 64 c + i): lane l's four bits are the nibble at bit 4 l of its 32 bytes.
+      // Both lanes of a pair store the pair's byte -- its own half or-ed with the neighbour's (DPP quad_perm [1, 0, 3, 2]): an
+      // unconditional store.  Stored from the even lanes only, the lane mask was one more scalar pair parked across the exploit loop
+      // (spilled SGPRs of the WIDE kernel 27 -> 44, v_writelane in the spread 16 -> 23).
+      const uint32_t nib = cg_sw_cand_nibble(y);
+      const uint32_t half = cg_sw_cand_half(nib, lane);
+      ((uint8_t*)cand)[lane >> 1] = (uint8_t)(half | (uint32_t)__builtin_amdgcn_update_dpp(0, (int)half, 0xB1, 0xf, 0xf, false));
+      const uint64_t bm = ballot(nib != 0u);
+      cg_sw_two_lowest(bm, (uint32_t)__builtin_amdgcn_readlane((int)nib, cg_sw_first_lane(bm)),
+                       (uint32_t)__builtin_amdgcn_readlane((int)nib, cg_sw_second_lane(bm)), u1, u2);
+    } else {
       uint32_t fj[MCT], vj[MCT];
 #pragma unroll
       for (int c = 0; c < MCT; ++c) { const int d = c * WAVE + lane, dc = d < M ? d : 0; fj[c] = e.flags[dc]; vj[c] = e.vul[dc]; }

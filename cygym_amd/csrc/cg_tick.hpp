@@ -352,6 +352,9 @@ template <int WPB, int MT, bool FUSED, bool XE, bool WIDE>
 // (80 VGPRs, no spills): batches that oversubscribe the chip (16384 envs) step 9 % faster than at 5.
 __global__ __launch_bounds__(WPB * WAVE, FUSED ? CG_FUSED_LB : (XE ? (WPB == 1 && MT == 0 ? 3 : CG_LB) : (WIDE ? 4 : (MT && MT <= 256 ? (WPB > 1 && WPB <= 8 ? CG_LEAN_LB : CG_LEAN_LB - 1) : 1)))) void step_kernel([[maybe_unused]] const KParams P0) {   // (read through the kernarg pointer, cg_tick_body.inc)
   constexpr bool ARRIVALS_JOINT = MT != 0;   // both roles' arrivals in one call at compile-time sizes (cg_arrivals.hpp)
+  // the spread's source compaction and T / candidate pass on one dword per lane (cg_spread_words.hpp): the per-tick kernels at 256
+  // devices; the rollout kernels keep the byte-wise passes (with the word form their VGPRs went 107 -> 112)
+  constexpr bool SPREAD_WORDS = MT == 256 && !FUSED;
 #include "cg_tick_body.inc"
 }
 

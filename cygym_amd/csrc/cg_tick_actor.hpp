@@ -15,6 +15,7 @@ __global__ __launch_bounds__(16 * WAVE, 4) void tick_actor_kernel(const KParams 
 // The tick here keeps one arrivals call per role: with the joint call this kernel's spilled SGPRs go 154 -> 161, and its resource
 // figures are pinned to the build that introduced the tiled actor launch (tests/test_mixture_cpu.py).
       constexpr bool ARRIVALS_JOINT = false;
+      constexpr bool SPREAD_WORDS = false;   // (the same pin: the byte-wise spread)
 #include "cg_tick_body.inc"
     };
     tick();

@@ -387,7 +387,8 @@ int cygym_create(const cygym_topology* topo, const cygym_config* cfg, int32_t n_
   t.o_os = L.o_os; t.o_ver = L.o_ver; t.o_ano = L.o_ano; t.o_icol = L.o_icol; t.o_ieid = L.o_ieid; t.o_oeid = L.o_oeid;
   {  // env_setup (cg_tick.hpp) derives every section offset from o_dst at the compile-time sizes: hold the layout to that
     const int A_M = (M + 15) & ~15, A_P = (2 * (M + 1) + 15) & ~15, A_F = (4 * M + 15) & ~15, a_e = t.o_dst - A_P;
-    if (t.o_optr != 0 || t.o_ocol != A_P || t.o_vul != t.o_dst + A_M || t.o_nap != t.o_dst + 2 * A_M || t.o_iptr != t.o_dst + 3 * A_M ||
+    // (o_dst % 16: the word passes of the tick and of the spread read the static and the vulnerability bytes as dwords)
+    if (t.o_optr != 0 || t.o_dst % 16 != 0 || t.o_ocol != A_P || t.o_vul != t.o_dst + A_M || t.o_nap != t.o_dst + 2 * A_M || t.o_iptr != t.o_dst + 3 * A_M ||
         t.o_os != t.o_iptr + A_P || t.o_ver != t.o_os + A_F || t.o_ano != t.o_ver + A_F || t.o_icol != t.o_ano + A_F ||
         t.o_ieid != t.o_icol + a_e || t.o_oeid != t.o_ieid + a_e) { delete h; return fail(nullptr, CYGYM_EINVAL, "internal: blob layout%s", ""); }
   }
