@@ -123,6 +123,15 @@ class Critic(C.Structure):
                 ("b3", C.c_float), ("H1", C.c_int32), ("H2", C.c_int32), ("h_stride", C.c_int32), ("top_k", C.c_int32), ("vec_stride", C.c_int32)]
 
 
+COMMITTEE_MAX = 8
+
+
+class Committee(C.Structure):
+    _fields_ = [("actor", ActorMlp), ("h_state", C.c_void_p), ("w1a", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("w3", C.c_void_p),
+                ("b3", C.c_void_p), ("expert_out", C.c_void_p), ("q_out", C.c_void_p), ("vec_out", C.c_void_p), ("n_experts", C.c_int32),
+                ("H1", C.c_int32), ("H2", C.c_int32), ("h_stride", C.c_int32), ("vec_stride", C.c_int32), ("reserved", C.c_int32)]
+
+
 DNS_MAX_ITERS = 16
 
 

@@ -709,6 +709,112 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_coord_ascent_decode(self._h, C.byref(cr), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_coord_ascent_decode")
 
+    def committee_decode(self, rows, obs: torch.Tensor, h_state: torch.Tensor, hidden_layers, head, critic_pack, n_experts: int, n_types: int,
+                         n_exploits: int | None = None, n_apps: int = 0, type_map=None, act=None, epsilon: float = 0.0, tanh: bool = True,
+                         obs_by_env: bool = False, expert_out=None, q_out=None, vec_out=None):
+        """CommitteeStrategy.select_action (do_agent.py:453-495) for a batch, fused with the scatter into rows `rows` of `act`
+        (group 0): ONE launch (cygym_committee_decode; include/cygym_abi.h states the rules).  K = n_experts same-shaped experts,
+        every stacked tensor holds expert k behind expert k - 1:
+          obs            [n, W] float32 role view (unit inner stride); with obs_by_env the batch's [N, W] view, read at rows `rows`
+          h_state        [n, >= K * H1] float32: b1_k + W1_k[:, :W] s at columns k * H1 .. of source row r -- one addmm
+          hidden_layers  [(packed weights of the K actors, biases [K * width] or None, width), ...] 1 to 3 of them (pack_linear)
+          head           (pack_linear(last.weight, 64) of the K actors, biases [K * n_out] or None)
+          critic_pack    (w1a, w2, b2, w3, b3): w1a = pack_linear(fc1.weight[:, W:]) per expert, w2 = pack_linear(fc2.weight) per
+                         expert, b2 [K * H2] or None, w3 [K, H2], b3 [K] -- all float32 on the batch's device
+          expert_out     optional [n] int32: the winning expert;  q_out optional [n, K] float32: every expert's Q
+          vec_out        optional [n, >= n_out] float32 (unit inner stride): encode_action of the winner's tuple
+        Limits: K <= 8, n_out <= 512, H1, H2 multiples of 16 in 16..128, n_types <= 32 (the library answers CYGYM_EUNSUPPORTED)."""
+        dst = self.actions_struct(act)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        Kx = int(n_experts)
+        if not ok(obs) or obs.dim() != 2 or obs.stride(1) != 1:
+            raise ValueError("obs must be a [n, W] float32 tensor on the batch's device with unit inner stride")
+        if obs_by_env and int(obs.shape[0]) < self.N:
+            raise ValueError("obs_by_env needs the batch's [N, W] role view")
+        W = int(obs.shape[1])
+        n = int(rows.shape[0]) if (obs_by_env and rows is not None) else int(obs.shape[0])
+        if not ok(h_state) or h_state.dim() != 2 or h_state.stride(1) != 1 or int(h_state.shape[0]) != n:
+            raise ValueError(f"h_state must be a [{n}, K * H1] float32 tensor on the batch's device with unit inner stride")
+        src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, epsilon)
+        w1a, w2, b2, w3, b3 = critic_pack
+        if not ok(w3) or not w3.is_contiguous() or w3.dim() != 2 or int(w3.shape[0]) != Kx:
+            raise ValueError("critic_pack: w3 must be a contiguous float32 [K, H2] tensor")
+        H2 = int(w3.shape[1])
+        if Kx < 1 or int(h_state.shape[1]) % Kx:
+            raise ValueError("h_state must hold K * H1 columns")
+        H1 = int(h_state.shape[1]) // Kx
+        cm = abi.Committee()
+        ml = cm.actor
+        ml.obs, ml.obs_stride, ml.K = obs.data_ptr(), int(obs.stride(0)) if int(obs.shape[0]) > 1 else W, W
+        ml.n_hidden, ml.tanh_out, ml.obs_by_env, ml.n_groups = len(hidden_layers), int(bool(tanh)), int(bool(obs_by_env)), 1
+        if not 1 <= len(hidden_layers) <= abi.MLP_MAX_HIDDEN:
+            raise ValueError(f"1 to {abi.MLP_MAX_HIDDEN} hidden layers")
+        kin = (W + 15) // 16
+        for l, (w, b, width) in enumerate(hidden_layers):
+            width = int(width)
+            if width % 16 or not 16 <= width <= 256:
+                raise ValueError("hidden widths must be multiples of 16 up to 256")
+            if not ok(w) or not w.is_contiguous() or w.numel() != Kx * (width // 16) * kin * 256:
+                raise ValueError(f"hidden layer {l}: packed weights have the wrong size (pack_linear per expert, stacked)")
+            if b is not None and (not ok(b) or not b.is_contiguous() or b.numel() != Kx * width):
+                raise ValueError(f"hidden layer {l}: bias must hold {Kx * width} float32 values")
+            ml.w[l], ml.b[l], ml.width[l] = w.data_ptr(), (b.data_ptr() if b is not None else None), width
+            kin = width // 16
+        wh, bh = head
+        if not ok(wh) or not wh.is_contiguous() or wh.numel() != Kx * (_pad64(n_out) // 16) * kin * 256:
+            raise ValueError("head: packed weights have the wrong size (pack_linear(weight, 64) per expert, stacked)")
+        if bh is not None and (not ok(bh) or not bh.is_contiguous() or bh.numel() != Kx * n_out):
+            raise ValueError(f"head: bias must hold {Kx * n_out} float32 values")
+        ml.w_head, ml.b_head = wh.data_ptr(), (bh.data_ptr() if bh is not None else None)
+        for name, t, numel in (("w1a", w1a, Kx * ((H1 + 15) // 16) * ((n_out + 15) // 16) * 256), ("w2", w2, Kx * ((H2 + 15) // 16) * ((H1 + 15) // 16) * 256),
+                               ("b2", b2, Kx * H2), ("b3", b3, Kx)):
+            if t is None and name == "b2":
+                continue
+            if not ok(t) or not t.is_contiguous() or int(t.numel()) != numel:
+                raise ValueError(f"critic_pack: {name} must be a contiguous float32 tensor of {numel} values on {self.device}")
+            setattr(cm, name, t.data_ptr())
+        cm.h_state, cm.h_stride, cm.w3 = h_state.data_ptr(), int(h_state.stride(0)) if n > 1 else int(h_state.shape[1]), w3.data_ptr()
+        cm.n_experts, cm.H1, cm.H2 = Kx, H1, H2
+        for name, t, dt, shape in (("expert_out", expert_out, torch.int32, (n,)), ("q_out", q_out, torch.float32, (n, Kx))):
+            if t is not None:
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
+                setattr(cm, name, t.data_ptr())
+        if vec_out is not None:
+            if not ok(vec_out) or vec_out.dim() != 2 or int(vec_out.shape[0]) != n or int(vec_out.shape[1]) < n_out or vec_out.stride(1) != 1 \
+                    or (n > 1 and vec_out.stride(0) < int(vec_out.shape[1])):
+                raise ValueError(f"vec_out must be a float32 [{n}, >= {n_out}] tensor on {self.device} with unit inner stride")
+            cm.vec_out, cm.vec_stride = vec_out.data_ptr(), int(vec_out.stride(0)) if n > 1 else int(vec_out.shape[1])
+        _lib.check(self.lib.cygym_committee_decode(self._h, C.byref(cm), C.byref(src), C.byref(dst), self._stream()),
+                   self._h, "cygym_committee_decode")
+
+    def override_decode(self, rows, raw: torch.Tensor, exploit_override: int, n_types: int, n_exploits: int | None = None, n_apps: int = 0,
+                        type_map=None, act=None, vec_out=None):
+        """decode_action(..., exploit_override=z) in the `Cord_asc` mode (do_agent.py:2147-2149) for a batch, fused with the scatter into
+        rows `rows` of `act` (group 0): ONE launch (cygym_override_decode).  raw [n, >= n_out] float32: the actor's outputs; the row's
+        action is (arg-max of its first n_types values, [z], [], 0).  vec_out optional [n, >= n_out] float32: encode_action of that
+        tuple -- for z >= n_exploits the fields swap (device bit z, exploit one-hot at 0).  z outside 0 .. M - 1 is a ValueError (the
+        reference raises there)."""
+        dst = self.actions_struct(act)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        z = int(exploit_override)
+        if not 0 <= z < self.M:
+            raise ValueError(f"exploit_override must lie in 0 .. {self.M - 1} (encode_action sets device bit z when z >= n_exploits)")
+        if not ok(raw) or raw.dim() != 2 or raw.stride(1) != 1:
+            raise ValueError("raw must be a [n, width] float32 tensor on the batch's device with unit inner stride")
+        n = int(raw.shape[0])
+        src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, 0.0)
+        if int(raw.shape[1]) < n_out:
+            raise ValueError("raw rows are narrower than n_types + n_devices + n_exploits + n_apps")
+        src.vec, src.stride = raw.data_ptr(), int(raw.stride(0)) if n > 1 else int(raw.shape[1])
+        vp, vs = None, 0
+        if vec_out is not None:
+            if not ok(vec_out) or vec_out.dim() != 2 or int(vec_out.shape[0]) != n or int(vec_out.shape[1]) < n_out or vec_out.stride(1) != 1 \
+                    or (n > 1 and vec_out.stride(0) < int(vec_out.shape[1])):
+                raise ValueError(f"vec_out must be a float32 [{n}, >= {n_out}] tensor on {self.device} with unit inner stride")
+            vp, vs = vec_out.data_ptr(), int(vec_out.stride(0)) if n > 1 else int(vec_out.shape[1])
+        _lib.check(self.lib.cygym_override_decode(self._h, C.byref(src), z, vp, vs, C.byref(dst), self._stream()), self._h, "cygym_override_decode")
+
     def dns_decode(self, rows, raw: torch.Tensor, h_state: torch.Tensor, critic_pack, n_types: int, n_exploits: int | None = None,
                    n_apps: int = 0, type_map=None, act=None, *, k_seq, beta_init: float, c_beta: float, n_samples: int = 75, sigma: float = 0.1,
                    epsilon: float = 0.0, dyn_eps=None, dyn_eps_min: float = 0.0, gate_out=None, vec_out=None, trace_i=None, trace_q=None,

@@ -1,5 +1,5 @@
 // cg_decode.hpp -- device code shared by the consumer-side kernels of the C-ABI unit (cg_aux_kernels.hpp), the tick + actor unit
-// (cg_inst_actor.hip), the coordinate-ascent unit (cg_inst_coord.hip), the hierarchical unit (cg_inst_hier.hip), the H-MARL unit (cg_inst_hmarl.hip) the MetaDOAR unit (cg_inst_meta.hip) and its observer's unit (cg_inst_meta_select.hip).  Templates and force-inlined device functions only
+// (cg_inst_actor.hip), the coordinate-ascent unit (cg_inst_coord.hip), the hierarchical unit (cg_inst_hier.hip), the H-MARL unit (cg_inst_hmarl.hip) the MetaDOAR unit (cg_inst_meta.hip), its observer's unit (cg_inst_meta_select.hip) and the committee unit (cg_inst_committee.hip).  Templates and force-inlined device functions only
 // (included in more than one translation unit, inside namespace cygym_k).  What every writer of group 0 of an action row shares:
 //   dpp_pair_max, float_order_bits   wave-wide lexicographic max of (order bits, ~index) pairs
 //   wave_first_max                   ... read back as "index of the first maximum, 0 if none": decode_row_regs, the chunked decode of
@@ -8,7 +8,7 @@
 //   RowGroups                        the group arrays of a row and the raise of CG_DECODE_TRUNCATED: RowList, hmarl_kernel, meta_kernel
 //   RowList                          compaction of the ascending device list, cut at max_devs, zero fill, the row's scalars and
 //                                    CG_DECODE_TRUNCATED: write_actions_kernel, decode_actions_kernel, decode_row_regs, the chunked
-//                                    decode, the merge of coord_ascent_kernel, hier_kernel (group_row writes several groups: its own code, cg_aux_kernels.hpp)
+//                                    decode, the merge of coord_ascent_kernel, the winner of committee_kernel, hier_kernel (group_row writes several groups: its own code, cg_aux_kernels.hpp)
 //   decode_row_regs                  decode of a row held in registers: actor_head_kernel, and through head_decode_row (row from LDS)
 //                                    actor_head_mfma_kernel, actor_mlp_kernel, tick_actor_kernel
 #ifndef CG_DECODE_HPP
@@ -169,4 +169,5 @@ __device__ __forceinline__ int sample_head(const float* l, const int K, const ui
 #include "cg_meta.hpp"
 #include "cg_meta_select.hpp"
 #include "cg_mixture.hpp"
+#include "cg_committee.hpp"
 #endif  // CG_DECODE_HPP

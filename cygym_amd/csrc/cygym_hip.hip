@@ -65,6 +65,15 @@ extern template __global__ void coord_ascent_kernel<false, true, true>(cygym_cri
 extern template __global__ void coord_ascent_kernel<true, true, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
 }  // namespace cygym_k
 
+// the committee decode lives in its own unit (cg_inst_committee.hip): declared, not instantiated, here
+namespace cygym_k {
+#define CG_CM_DECL(O) extern template __global__ void committee_kernel<O>(cygym_committee, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+CG_CM_DECL(2) CG_CM_DECL(3) CG_CM_DECL(4) CG_CM_DECL(5) CG_CM_DECL(6) CG_CM_DECL(7) CG_CM_DECL(8)
+#undef CG_CM_DECL
+extern template __global__ void override_decode_kernel<false>(cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, int, float*, int);
+extern template __global__ void override_decode_kernel<true>(cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, int, float*, int);
+}  // namespace cygym_k
+
 // the dynamic neighbourhood search lives in its own unit (cg_inst_dns.hip): declared, not instantiated, here
 namespace cygym_k {
 extern template __global__ void dns_kernel<false>(cygym_critic, cygym_dns, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
@@ -312,6 +321,7 @@ int cygym_sizeof(int32_t which) {
     case 37: return (int)sizeof(cygym_comm_gat_eval);   // (index 36 stays unassigned)
     case 39: return (int)sizeof(cygym_ippo_adv_desc);   // (index 38 stays unassigned)
     case 40: return (int)sizeof(cygym_ippo_head_desc);
+    case 42: return (int)sizeof(cygym_committee);   // (index 41 stays unassigned: earlier bindings probe it for -1)
     default: return -1;
   }
 }
@@ -953,6 +963,61 @@ int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygy
   const void* k = kernels[(c->top_k > 1 ? 1 : 0) | (c->noise_std > 0.0 ? 2 : 0) | (c->vec_out ? 4 : 0)];
   if (const int rc = raise_lds_once(h, k)) return rc;
   return launch_decode(h, k, dim3(src->n), dim3(CA_THREADS), lds, stream, {c, src, dst});   // one workgroup per row
+}
+
+int cygym_committee_decode(cygym_handle* h, const cygym_committee* cm, const cygym_action_vectors* src, const cygym_actions* dst,
+                           void* stream) {
+  const char* const who = "cygym_committee_decode";
+  const char* const bad_layout = "cygym_committee_decode: bad layout (types, exploits >= 1, the handle's device count, K <= obs_stride, h_stride >= n_experts H1)%s";
+  const cygym_actor_mlp* mlp = cm ? &cm->actor : nullptr;
+  if (const int rc = check_vectors(h, src, dst, who, cm && mlp->obs && mlp->w_head && cm->h_state && cm->w1a && cm->w2 && cm->w3 && cm->b3, 1, bad_layout))
+    return rc;
+  if (cm->n_experts < 1 || cm->n_experts > CG_COMMITTEE_MAX)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_committee_decode: 1 to CG_COMMITTEE_MAX experts%s", "");
+  if (mlp->obs_role) return fail(h, CYGYM_EUNSUPPORTED, "cygym_committee_decode: the role view is read, not built on chip (obs_role must be 0)%s", "");
+  if (cm->H1 < 16 || cm->H1 > CA_MAX_H || (cm->H1 & 15) || cm->H2 < 16 || cm->H2 > CA_MAX_H || (cm->H2 & 15))
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_committee_decode: critic widths H1, H2 must be multiples of 16 in 16 .. 128%s", "");
+  if (mlp->n_hidden < 1 || mlp->n_hidden > CG_MLP_MAX_HIDDEN) return fail(h, CYGYM_EUNSUPPORTED, "cygym_committee_decode: 1 to 3 hidden layers%s", "");
+  for (int l = 0; l < mlp->n_hidden; ++l) {
+    if (!mlp->w[l]) return fail(h, CYGYM_EINVAL, "cygym_committee_decode: null weight pointer%s", "");
+    if (mlp->width[l] < 16 || mlp->width[l] > 256 || (mlp->width[l] & 15))
+      return fail(h, CYGYM_EUNSUPPORTED, "cygym_committee_decode: hidden widths must be multiples of 16 up to 256%s", "");
+  }
+  const long long n_out = (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps;
+  if (src->n_types > CA_MAX_TYPES || src->n_exploits > CG_MAX_EXPLOITS || n_out > (long long)HEAD_OPL_MAX * WAVE)
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_committee_decode: at most 32 action types, CG_MAX_EXPLOITS exploits, 512 outputs%s", "");
+  if (mlp->K < 1 || mlp->obs_stride < mlp->K || cm->h_stride < (long long)cm->n_experts * cm->H1) return fail(h, CYGYM_EINVAL, bad_layout, "");
+  if (cm->vec_out && cm->vec_stride < n_out)
+    return fail(h, CYGYM_EINVAL, "cygym_committee_decode: vec_stride is smaller than n_out = n_types + n_devices + n_exploits + n_apps%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, src->epsilon_thr, who)) return rc;
+  if ((unsigned long long)(mlp->obs_by_env ? h->n_envs : src->n) * (unsigned long long)mlp->obs_stride >= (1ull << 32))
+    return fail(h, CYGYM_EUNSUPPORTED, "cygym_committee_decode: observation matrices of 2^32 floats or more%s", "");
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const int n_out_p = n_out <= 2 * WAVE ? 2 * WAVE : (((int)n_out + 63) & ~63);   // (the narrowest instantiation holds 128 outputs)
+  const CteePlan pl = cttee_plan(mlp->K, mlp->n_hidden, mlp->width, n_out_p, cm->H1);
+  const size_t lds = (size_t)pl.total * sizeof(float);
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_committee_decode: the layer shapes do not fit in LDS%s", "");
+  const void* k = kernel_by_opl<2>(n_out_p / WAVE, [](auto O) { return (const void*)committee_kernel<decltype(O)::value>; });
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  return launch_decode(h, k, dim3((src->n + 15) / 16), dim3(MLP_THREADS), lds, stream, {cm, src, dst});
+}
+
+int cygym_override_decode(cygym_handle* h, const cygym_action_vectors* src, int32_t exploit_override, float* vec_out, int32_t vec_stride,
+                          const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_override_decode";
+  const char* const bad_layout = "cygym_override_decode: bad layout (types, exploits >= 1, the handle's device count, stride >= n_out, 0 <= exploit_override < n_devices)%s";
+  if (const int rc = check_vectors(h, src, dst, who, src && src->vec, 1, bad_layout)) return rc;
+  const long long n_out = (long long)src->n_types + src->n_devices + src->n_exploits + src->n_apps;
+  if (src->stride < n_out || exploit_override < 0 || exploit_override >= src->n_devices) return fail(h, CYGYM_EINVAL, bad_layout, "");
+  if (vec_out && vec_stride < n_out)
+    return fail(h, CYGYM_EINVAL, "cygym_override_decode: vec_stride is smaller than n_out = n_types + n_devices + n_exploits + n_apps%s", "");
+  if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const void* k = vec_out ? (const void*)override_decode_kernel<true> : (const void*)override_decode_kernel<false>;
+  int z = exploit_override;
+  return launch_decode(h, k, dim3((src->n + 3) / 4), dim3(256), 0, stream, {src, dst}, {&z, &vec_out, &vec_stride});
 }
 
 int cygym_dns_decode(cygym_handle* h, const cygym_critic* c, const cygym_dns* q, const cygym_action_vectors* src, const cygym_actions* dst,

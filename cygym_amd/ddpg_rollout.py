@@ -316,7 +316,7 @@ def train_ddpg(agent: DDPGAgent, *, batch=None, batch_size: int = 512, gamma: fl
 def best_response(batch, role: str, agent: DDPGAgent, opponent, n_decisions: int, n_types: int, n_exploits: int | None = None, n_apps: int = 0, *,
                   type_map=None, decoder=None, updates_per_decision: int = 1, noise_std: float = 1.0, sigma_min: float = 1e-5,
                   batch_size: int = 512, gamma: float = 0.99, tau: float = 1e-2, generator=None, fused=None, t0: int = 0, meta=None,
-                  meta_period: int = 10):
+                  meta_period: int = 10, exploit_override=None):
     """The training loop of DoubleOracle.ddpg_best_response (do_agent.py:1334-1460) for every env of a batch: per decision
     collect(n_decisions=1) from the loop's tick counter -- the opponent's tick first where the parity of t is theirs (:1335) --,
     push the N transitions (:1422 / :1424-1425), then `updates_per_decision` calls of train_ddpg (:1427-1431).  The exploration
@@ -331,8 +331,18 @@ def best_response(batch, role: str, agent: DDPGAgent, opponent, n_decisions: int
     tick t ((t + 1) % 10 == 0 as shipped: never for a defender, whose ticks are even).  It changes neither the actions nor the agent.
     decoder: a policies.DynamicSearchPolicy over agent.actor and agent.critic -- the loop with `--dynamic_search` (:1381-1399): its gate starts
     at dyn_eps0 when the policy is made (reset_gate() starts a new run) and halves at every use, per env.
-    Out of scope: exploit_override, the time budget, and leaving the loop at the first done (a batch goes
-    on, as collect does)."""
+    exploit_override=z: the loop train_exploit_committee runs per private exploit (do_agent.py:1253-1277, :2147-2149): every decision is
+    (arg-max of the actor's first n_types raw outputs, [z], [], 0) and the replay stores encode_action of it (for z >= n_exploits with the
+    exploit and device fields swapped) -- a policies.CoordAscentPolicy(agent.critic, ..., exploit_override=z, actor=agent.actor) is made
+    here when no decoder is given; 0 <= z < M.
+    Out of scope: the time budget, and leaving the loop at the first done (a batch goes on, as collect does)."""
+    if exploit_override is not None:
+        if decoder is None:
+            from .policies import CoordAscentPolicy
+            decoder = CoordAscentPolicy(agent.critic, n_types, batch.cfg.max_exploits if n_exploits is None else int(n_exploits), n_apps,
+                                        type_map=type_map, exploit_override=exploit_override, actor=agent.actor)
+        elif getattr(decoder, "exploit_override", None) != int(exploit_override):
+            raise ValueError("decoder: its exploit_override differs from the one best_response() was called with")
     if decoder is not None and decoder.critic is not agent.critic:
         raise ValueError("decoder: a CoordAscentPolicy or DynamicSearchPolicy over agent.critic (the critic the updates train)")
     n_decisions = int(n_decisions)
@@ -359,3 +369,23 @@ def best_response(batch, role: str, agent: DDPGAgent, opponent, n_decisions: int
             out = train_ddpg(agent, batch=batch, batch_size=batch_size, gamma=gamma, tau=tau, generator=generator, fused=fused)
             last = out if out is not None else last
     return total, last
+
+
+def train_committee(batch, zs, role: str, opponent, n_decisions: int, n_types: int, n_exploits: int | None = None, n_apps: int = 0, *, type_map=None,
+                    seed: int = 0, capacity: int = 100_000, **kw):
+    """DoubleOracle.train_exploit_committee (do_agent.py:1253-1277) on a batch: one fresh DDPG agent per private exploit z of `zs`
+    (init_ddpg with seed + its position), trained by best_response(..., exploit_override=z) against `opponent` for `n_decisions`
+    decisions (`kw`: best_response's other arguments).  Returns the mapping policies.CommitteePolicy.to_strategy() writes,
+    {"committee": {"experts": [{"z", "actor_state_dict", "critic_state_dict"}, ...]}}: CommitteePolicy.from_strategy loads it and
+    simulate_grid plays it."""
+    from .policies import CommitteePolicy
+    zs = [int(z) for z in zs]
+    if not zs:
+        raise ValueError("train_committee: at least one exploit id")
+    n_exploits = batch.cfg.max_exploits if n_exploits is None else int(n_exploits)
+    experts = []
+    for i, z in enumerate(zs):
+        agent = init_ddpg(batch.role_width(role), n_types, batch.M, n_exploits, n_apps, seed=int(seed) + i, device=batch.device, capacity=capacity)
+        best_response(batch, role, agent, opponent, n_decisions, n_types, n_exploits, n_apps, type_map=type_map, exploit_override=z, **kw)
+        experts.append((agent.actor.eval(), agent.critic.eval()))
+    return CommitteePolicy(experts, role, n_types, n_exploits, n_apps, type_map=type_map, zs=zs).to_strategy()

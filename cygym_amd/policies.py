@@ -12,6 +12,11 @@ decode_action does not read the actor at all but scores one-device candidate act
 (`DoubleOracle.greedy_device_coord_ascent`, do_agent.py:2137-2219); the batch does that in one launch
 (cygym_coord_ascent_decode).  `reference_critic` builds the reference's critic (do_agent.py:373-388).
 
+`CommitteePolicy` is the fifth typed family of the loop, `"committee"` (CommitteeStrategy.select_action, do_agent.py:453-495): one DDPG
+expert per private exploit; every expert's actor proposes, the plain decode and encode_action turn the proposal into the critic's input,
+the expert's own critic scores it and the first best Q wins -- one addmm plus one launch for the batch (cygym_committee_decode).
+`committee_decide` is the torch restatement the fixtures and the kernel are checked against.
+
 `DynamicSearchPolicy` is either of the two run with the reference's `--dynamic_search` flag: behind a per-env gate that halves at
 every use the decision is `DoubleOracle.dynamic_neighborhood_search` (do_agent.py:1204-1250), a simulated-annealing local search
 around the decoded actor output scored by the critic; the batch does it in one launch (cygym_dns_decode) that overwrites the gated
@@ -483,12 +488,21 @@ class CoordAscentPolicy:
     candidate but the no-op before the sort.  `noise_std` is that coord_noise_std (do_agent.py:528: 0.1); it applies while
     train_mode(True) -- mirror `critic.training` with train_mode(critic.training) -- and write() then decodes on the noisy scores
     (addressed normals, SITE_COORD_NOISE) and merges on the clean Q.  write(vec_out=...) also returns encode_action of the merged
-    tuple, what the reference's replay buffer stores in this mode (:1424).  Not restated: exploit_override."""
+    tuple, what the reference's replay buffer stores in this mode (:1424).
+    exploit_override=z (with actor=): the mode train_exploit_committee trains an expert in (:2147-2149): the decision is (arg-max of the
+    actor's first T RAW outputs, [z], [], 0) -- the critic is not consulted, the device list is empty, z is an exploit id handed through
+    as it is; write() is the actor's forward plus ONE launch (cygym_override_decode), and vec_out receives encode_action of that tuple,
+    where for z >= n_exploits the fields swap (device bit z, exploit one-hot at 0).  z must lie in 0 .. M - 1 (the reference raises
+    beyond).  Default None: every row as before."""
 
     tick_free = True
 
     def __init__(self, critic, n_types: int, n_exploits: int, n_apps: int, type_map=None, top_k: int = 5, tau: float = 0.5,
-                 noise_std: float = 0.0):
+                 noise_std: float = 0.0, exploit_override=None, actor=None):
+        self.exploit_override = None if exploit_override is None else int(exploit_override)
+        self.actor = actor
+        if self.exploit_override is not None and (actor is None or self.exploit_override < 0):
+            raise ValueError("exploit_override: an exploit id >= 0, and actor= (the decision is the arg-max of the actor's type outputs)")
         lins = [critic.fc1, critic.fc2, critic.fc3] if hasattr(critic, "fc1") else list(critic)
         if len(lins) != 3 or not all(isinstance(m, nn.Linear) and m.bias is not None and m.weight.dtype == torch.float32 for m in lins):
             raise ValueError("critic: a module with fc1 / fc2 / fc3 or three nn.Linear layers (float32, with biases)")
@@ -540,6 +554,14 @@ class CoordAscentPolicy:
     def write(self, batch, act, rows, obs, pick_out=None, q_out=None, vec_out=None):
         """h_state = one addmm, then the whole decode + scatter into rows `rows` of the action tensors in ONE launch; vec_out
         [n, >= n_out] float32 receives the encoded merged action of every source row."""
+        if self.exploit_override is not None:
+            if pick_out is not None or q_out is not None:
+                raise ValueError("exploit_override: no candidate is scored, so there is no pick_out / q_out")
+            if self.exploit_override >= batch.M:
+                raise ValueError(f"exploit_override must lie in 0 .. {batch.M - 1} (encode_action sets device bit z when z >= n_exploits)")
+            batch.override_decode(rows, self.actor(obs).float().contiguous(), self.exploit_override, self.n_types, self.n_exploits, self.n_apps,
+                                  self._map(obs.device), act, vec_out=vec_out)
+            return
         w1s_t, b1, pack = self._packed(batch, batch.M)
         if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != int(w1s_t.shape[0]):
             raise ValueError(f"obs must be a float32 [n, {int(w1s_t.shape[0])}] role view")
@@ -550,6 +572,12 @@ class CoordAscentPolicy:
     @torch.no_grad()
     def __call__(self, obs, t, M, L):
         """The same decode with torch ops in float64 (batch-likes without cygym_coord_ascent_decode: the tests' oracle harness)."""
+        if self.exploit_override is not None:
+            at = torch.argmax(self.actor(obs)[:, :self.n_types], dim=1)
+            tm = self._map(obs.device)
+            at = at.to(torch.int32) if tm is None else tm[at]
+            return {"atype": at, "exploit": torch.full_like(at, self.exploit_override), "dev_mask": torch.zeros((obs.shape[0], M), dtype=torch.bool, device=obs.device),
+                    "app": torch.zeros_like(at)}
         if self.top_k != 1:
             raise NotImplementedError("a pick among the top K is drawn in cygym_coord_ascent_decode (needs the envs' rng ticks)")
         if self.active_noise_std > 0.0:
@@ -562,6 +590,288 @@ class CoordAscentPolicy:
         tm = self._map(obs.device)
         at = at.to(torch.int32) if tm is None else tm[at]
         return {"atype": at, "exploit": ex.to(torch.int32), "dev_mask": on, "app": torch.zeros_like(at)}
+
+
+def _net_forward(net, x, dtype):
+    """A Linear / ReLU / Tanh stack evaluated in `dtype` from its fp32 parameters (float32: the module's own forward)."""
+    if dtype in (None, torch.float32) and x.dtype == torch.float32:
+        return net(x)
+    x = x.to(dtype)
+    for m in net:
+        if isinstance(m, nn.Linear):
+            x = torch.addmm(m.bias.detach().to(dtype), x, m.weight.detach().to(dtype).t()) if m.bias is not None else x @ m.weight.detach().to(dtype).t()
+        elif isinstance(m, nn.ReLU):
+            x = torch.relu(x)
+        elif isinstance(m, nn.Tanh):
+            x = torch.tanh(x)
+        else:
+            raise ValueError(f"an actor is a stack of nn.Linear, nn.ReLU and nn.Tanh, not {type(m).__name__}")
+    return x
+
+
+def encode_action(at, dev_mask, ex, app, T: int, E: int, A: int, dtype=torch.float32):
+    """encode_action (do_agent.py:910-933) of a batch of tuples whose exploit index is < E (no field swap): at [n] type INDEX, dev_mask
+    [n, D] bool, ex [n], app [n] -> [n, T + D + E + A] with ones at at, T + d for every chosen device, T + D + ex and, when A > 0,
+    T + D + E + app."""
+    n, D = dev_mask.shape
+    e = torch.zeros((n, T + D + E + A), dtype=dtype, device=dev_mask.device)
+    i = torch.arange(n, device=dev_mask.device)
+    e[i, at.long()] = 1
+    e[:, T:T + D] = dev_mask.to(dtype)
+    e[i, T + D + ex.long()] = 1
+    if A > 0:
+        e[i, T + D + E + app.long()] = 1
+    return e
+
+
+def encode_override(at, z: int, T: int, D: int, E: int, A: int, dtype=torch.float32):
+    """encode_action (do_agent.py:910-933) of the tuples (at, [z], [], 0) the decode with exploit_override returns (:2147-2149): for
+    z >= E the exploit and device fields swap (:919-920) -- device bit z, exploit one-hot at 0 --, for z < E the exploit one-hot at z and
+    no device bit; app one-hot at 0 when A > 0.  z >= D is a ValueError (the reference raises there)."""
+    z = int(z)
+    if not 0 <= z < D:
+        raise ValueError(f"exploit_override must lie in 0 .. {D - 1}")
+    n = int(at.shape[0])
+    e = torch.zeros((n, T + D + E + A), dtype=dtype, device=at.device)
+    e[torch.arange(n, device=at.device), at.long()] = 1
+    if z >= E:
+        e[:, T + z] = 1
+        e[:, T + D] = 1
+    else:
+        e[:, T + D + z] = 1
+    if A > 0:
+        e[:, T + D + E] = 1
+    return e
+
+
+@torch.no_grad()
+def committee_decide(experts, obs, T: int, E: int, A: int = 0, *, dtype=torch.float64, epsilon: float = 0.0, seed: int = 0, env_ids=None, ticks=None):
+    """CommitteeStrategy.select_action (do_agent.py:453-495) for a batch with torch ops in `dtype` (float64: the restatement the
+    kernel is checked against; float32: what the reference computes), steps 1-5 of cygym_committee_decode (include/cygym_abi.h):
+    every expert (actor, critic) of the list proposes the PLAIN decode of its actor's output, encodes it, its own critic scores it,
+    and the first expert whose Q is strictly greater than every earlier one wins.  epsilon > 0: expert k's type index gives way to a
+    uniform one when word 0 of the draw addressed (seed, env_ids[r], ticks[r], SITE_EPS_TYPE, a = k) is below ceil(epsilon 2^32);
+    the index is rng.index(word 1, T).
+    Returns a dict: per expert at [n, K] (type INDEX, before any type map), ex, app [n, K], dev_mask [n, K, D] bool, vec [n, K, n_out],
+    q [n, K] in `dtype`; expert [n]; and the winner's atype (index), exploit, app, dev_mask [n, D], enc [n, n_out]."""
+    n = int(obs.shape[0])
+    K = len(experts)
+    if K < 1:
+        raise ValueError("a committee needs at least one expert")
+    if epsilon > 0.0:
+        import numpy as np
+        from . import rng as R
+        from . import spec as S
+        if env_ids is None or ticks is None:
+            raise ValueError("epsilon > 0 needs seed, env_ids and ticks (the draws are addressed)")
+        thr = R.bernoulli_threshold(float(epsilon))
+        envs, tks = np.asarray(env_ids, dtype=np.uint64).reshape(-1), np.asarray(ticks, dtype=np.uint64).reshape(-1)
+    ats, exs, apps, masks, vecs, qs = [], [], [], [], [], []
+    for k, (actor, critic) in enumerate(experts):
+        v = _net_forward(actor, obs, dtype)
+        D = int(v.shape[1]) - T - E - A
+        at = torch.argmax(v[:, :T], dim=1)
+        if epsilon > 0.0:
+            w = R.draw_words_np(int(seed), envs, tks, S.SITE_EPS_TYPE, a=k)
+            coin = torch.from_numpy((w[0] < np.uint64(thr))).to(at.device)
+            uni = torch.from_numpy(((w[1] * np.uint64(T)) >> np.uint64(32)).astype(np.int64)).to(at.device)
+            at = torch.where(coin, uni, at)
+        mask = v[:, T:T + D] > 0
+        ex = torch.argmax(v[:, T + D:T + D + E], dim=1)
+        app = torch.argmax(v[:, T + D + E:], dim=1) if A > 0 else torch.zeros_like(at)
+        e = encode_action(at, mask, ex, app, T, E, A, dtype=obs.dtype if dtype is None else dtype)
+        if dtype in (None, torch.float32) and obs.dtype == torch.float32:
+            q = critic(obs, e)[:, 0]
+        else:
+            q = critic.evaluate(obs, e, fused=False, dtype=dtype)[:, 0]
+        ats.append(at); exs.append(ex); apps.append(app); masks.append(mask); vecs.append(e); qs.append(q)
+    at, ex, app, mask, vec, q = (torch.stack(t, 1) for t in (ats, exs, apps, masks, vecs, qs))
+    best = torch.zeros(n, dtype=torch.long, device=obs.device)
+    bq = q[:, 0].clone()
+    for k in range(1, K):                      # (`q_val > best_Q` in list order, do_agent.py:493-494)
+        take = q[:, k] > bq
+        best = torch.where(take, torch.full_like(best, k), best)
+        bq = torch.where(take, q[:, k], bq)
+    i = torch.arange(n, device=obs.device)
+    return {"at": at, "ex": ex, "app": app, "dev_mask": mask, "vec": vec, "q": q, "expert": best,
+            "atype": at[i, best], "exploit": ex[i, best], "app_index": app[i, best], "mask": mask[i, best], "enc": vec[i, best]}
+
+
+class CommitteePolicy:
+    """A `"committee"` strategy of the reference's rollout loop (do_agent.py:222-236): CommitteeStrategy.select_action (:453-495), the
+    zero-day best response built by committee_best_response / train_exploit_committee (:1253-1277) -- one DDPG expert per private
+    exploit z; at decision time every expert proposes the plain decode of its actor's output, its own critic scores the encoded
+    proposal, and the best Q wins (the first among equals).  include/cygym_abi.h (cygym_committee_decode) states it in full.
+    `experts`: a list of (actor, critic) -- reference_actor / mlp_actor(tanh=True) stacks of ONE architecture and policies.Critic
+    modules of one shape.  write() is ONE addmm (the state part of every expert's fc1, against the K stacked matrices) plus ONE
+    launch; __call__ is committee_decide in float64 for batch-likes without the kernel (epsilon = 0 only).  `zs`: the experts'
+    exploit ids, kept for to_strategy() (the decision does not read them: decode_action ignores exploit_override on this path)."""
+
+    def __init__(self, experts, role: str, n_types: int, n_exploits: int, n_apps: int = 0, type_map=None, epsilon: float = 0.0, zs=None):
+        self.experts = [(a, c) for a, c in experts]
+        self.role = str(role)
+        self.n_types, self.n_exploits, self.n_apps, self.epsilon = int(n_types), int(n_exploits), int(n_apps), float(epsilon)
+        K = len(self.experts)
+        if not 1 <= K <= 8:
+            raise ValueError("a committee holds 1 to 8 experts")
+        self.zs = list(range(K)) if zs is None else [None if z is None else int(z) for z in zs]
+        if len(self.zs) != K:
+            raise ValueError("zs: one exploit id per expert")
+        from . import spec as S
+        if not (1 <= self.n_types <= 32 and 1 <= self.n_exploits <= S.MAX_EXPLOITS and self.n_apps >= 0):
+            raise ValueError(f"1..32 action types, 1..{S.MAX_EXPLOITS} exploits, n_apps >= 0")
+        shapes = set()
+        for a, c in self.experts:
+            if not isinstance(a, nn.Sequential) or not all(isinstance(m, (nn.Linear, nn.ReLU, nn.Tanh)) for m in a):
+                raise ValueError("actors: nn.Sequential stacks of Linear / ReLU / Tanh (reference_actor, mlp_actor)")
+            if any(isinstance(m, nn.Linear) and m.bias is None for m in a):
+                raise ValueError("actors: every Linear layer with a bias (the reference's Actor; the `committee` mapping stores one per layer)")
+            if not all(hasattr(c, f) and isinstance(getattr(c, f), nn.Linear) and getattr(c, f).bias is not None for f in ("fc1", "fc2", "fc3")):
+                raise ValueError("critics: modules with fc1 / fc2 / fc3 (policies.Critic)")
+            shapes.add((tuple((type(m).__name__, getattr(m, "in_features", 0), getattr(m, "out_features", 0), getattr(m, "bias", None) is not None) for m in a),
+                        tuple((getattr(c, f).in_features, getattr(c, f).out_features) for f in ("fc1", "fc2", "fc3"))))
+        if len(shapes) != 1:
+            raise ValueError("every expert of a committee has the same actor and critic architecture")
+        c0 = self.experts[0][1]
+        H1, H2 = c0.fc1.out_features, c0.fc2.out_features
+        if H1 % 16 or H2 % 16 or not (16 <= H1 <= 128 and 16 <= H2 <= 128) or c0.fc2.in_features != H1 or c0.fc3.in_features != H2 or c0.fc3.out_features != 1:
+            raise ValueError("critic widths: fc1 -> H1 -> H2 -> 1 with H1, H2 multiples of 16 in 16..128")
+        self.type_map = None if type_map is None else torch.as_tensor(type_map, dtype=torch.int32)
+        self.action_types = list(range(self.n_types)) if type_map is None else sorted({int(x) for x in self.type_map.tolist()})
+        self._actor0 = ActorPolicy(self.experts[0][0], n_types, n_exploits, n_apps)      # (the split of the shared architecture)
+
+    _map = ActorPolicy._map
+
+    @property
+    def tick_free(self) -> bool:
+        return self.epsilon == 0.0
+
+    def n_out(self, M):
+        return self.n_types + M + self.n_exploits + self.n_apps
+
+    def _params(self):
+        for a, c in self.experts:
+            yield from a.parameters()
+            yield from c.parameters()
+
+    def _packed(self, batch, M):
+        """The stacked, fragment-ordered weights of cygym_committee_decode, redone when a parameter's version changes."""
+        ver = (int(M),) + tuple((p._version, p.data_ptr()) for p in self._params())
+        if getattr(self, "_pk_ver", None) != ver:
+            split = self._actor0._split_mlp(M)
+            if split is None:
+                raise ValueError("actors: 1 to 3 hidden Linear-ReLU layers of widths that are multiples of 16 up to 256, ending in a Linear "
+                                 f"layer of {self.n_out(M)} outputs [+ Tanh]")
+            n_hidden, tanh = len(split[0]), split[2]
+            n_out = self.n_out(M)
+            W = self.experts[0][1].fc1.in_features - n_out
+            if W < 1 or W != split[0][0].in_features:
+                raise ValueError(f"fc1 of the critics takes {self.experts[0][1].fc1.in_features} inputs: not the actors' {split[0][0].in_features} + {n_out}")
+            lins = [[m for m in a if isinstance(m, nn.Linear)] for a, _ in self.experts]
+            cat = lambda ts: torch.cat([t.detach().reshape(-1) for t in ts]).contiguous()  # noqa: E731
+            hidden = [(cat([batch.pack_linear(ls[l].weight) for ls in lins]), None if lins[0][l].bias is None else cat([ls[l].bias for ls in lins]),
+                       lins[0][l].out_features) for l in range(n_hidden)]
+            head = (cat([batch.pack_linear(ls[-1].weight, 64) for ls in lins]), None if lins[0][-1].bias is None else cat([ls[-1].bias for ls in lins]))
+            cs = [c for _, c in self.experts]
+            w1s_t = torch.cat([c.fc1.weight.detach()[:, :W].t() for c in cs], 1).contiguous()          # [W, K H1]
+            b1 = cat([c.fc1.bias for c in cs])
+            critic = (cat([batch.pack_linear(c.fc1.weight.detach()[:, W:]) for c in cs]), cat([batch.pack_linear(c.fc2.weight) for c in cs]),
+                      cat([c.fc2.bias for c in cs]), torch.stack([c.fc3.weight.detach().reshape(-1) for c in cs]).contiguous(), cat([c.fc3.bias for c in cs]))
+            self._pk, self._pk_ver = (w1s_t, b1, hidden, head, critic, tanh), ver
+        return self._pk
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, expert_out=None, q_out=None, vec_out=None):
+        """h_state of all K experts = one addmm, then actors, decodes, encodes, critics, the arg-max and the scatter into rows `rows`
+        of the action tensors in ONE launch (cygym_committee_decode)."""
+        w1s_t, b1, hidden, head, critic, tanh = self._packed(batch, batch.M)
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != int(w1s_t.shape[0]):
+            raise ValueError(f"obs must be a float32 [n, {int(w1s_t.shape[0])}] role view")
+        h_state = torch.addmm(b1, obs, w1s_t)
+        batch.committee_decode(rows, obs, h_state, hidden, head, critic, len(self.experts), self.n_types, self.n_exploits, self.n_apps,
+                               self._map(obs.device), act, epsilon=self.epsilon, tanh=tanh, expert_out=expert_out, q_out=q_out, vec_out=vec_out)
+
+    @torch.no_grad()
+    def __call__(self, obs, t, M, L):
+        """The same decision with torch ops in float64 (batch-likes without cygym_committee_decode: the tests' oracle harness)."""
+        if self.epsilon > 0.0:
+            raise NotImplementedError("epsilon-greedy types are drawn in cygym_committee_decode (needs the envs' rng ticks)")
+        d = committee_decide(self.experts, obs, self.n_types, self.n_exploits, self.n_apps, dtype=torch.float64)
+        tm = self._map(obs.device)
+        at = d["atype"].to(torch.int32) if tm is None else tm[d["atype"]]
+        return {"atype": at, "exploit": d["exploit"].to(torch.int32), "dev_mask": d["mask"], "app": d["app_index"].to(torch.int32)}
+
+    # ---- the reference's mapping {"committee": ...} ----
+    @staticmethod
+    def _expert_entries(value):
+        """[(z, actor_state_dict, critic_state_dict), ...] from an object with .experts = [(z, strategy_like), ...] (what
+        committee_best_response returns) or a dict {"experts": [{"z", "actor_state_dict", "critic_state_dict"}, ...]}."""
+        get = lambda o, k: o[k] if isinstance(o, dict) else getattr(o, k)  # noqa: E731
+        has = lambda o, k: (k in o) if isinstance(o, dict) else hasattr(o, k)  # noqa: E731
+        if not has(value, "experts"):
+            raise KeyError("a committee value needs `experts`")
+        out = []
+        for i, ent in enumerate(get(value, "experts")):
+            if isinstance(ent, (tuple, list)):
+                z, strat = ent
+            else:
+                if not has(ent, "z"):
+                    raise KeyError(f"committee expert {i}: missing `z`")
+                z, strat = get(ent, "z"), ent
+            for key in ("actor_state_dict", "critic_state_dict"):
+                if not has(strat, key) or get(strat, key) is None:
+                    raise KeyError(f"committee expert {i}: missing `{key}` (a missing network is not initialised at random here)")
+            out.append((z, get(strat, "actor_state_dict"), get(strat, "critic_state_dict")))
+        if not out:
+            raise ValueError("a committee needs at least one expert")
+        return out
+
+    @classmethod
+    def from_strategy(cls, mapping, batch, role: str, n_types: int, n_exploits=None, n_apps: int = 0, type_map=None, epsilon: float = 0.0):
+        """Load `mapping["committee"]` for `batch` (its device count, role-view width and device).  Actor state dicts use the
+        reference's names (fc1 / fc2 / fc3, do_agent.py:357-370) or a Sequential's ("0.weight", ...); every key is required."""
+        if "committee" not in mapping:
+            raise KeyError('the strategy mapping has no "committee" entry')
+        n_exploits = batch.cfg.max_exploits if n_exploits is None else int(n_exploits)
+        W, n_out = batch.role_width(role), int(n_types) + batch.M + n_exploits + int(n_apps)
+        experts, zs = [], []
+        for i, (z, asd, csd) in enumerate(cls._expert_entries(mapping["committee"])):
+            asd = {k: torch.as_tensor(v) for k, v in asd.items()}
+            csd = {k: torch.as_tensor(v) for k, v in csd.items()}
+            names = sorted({k.rsplit(".", 1)[0] for k in asd}, key=lambda s: (len(s), s))
+            for nm in names:
+                for suffix in ("weight", "bias"):
+                    if f"{nm}.{suffix}" not in asd:
+                        raise KeyError(f"committee expert {i}: actor_state_dict has no {nm}.{suffix}")
+            for nm in ("fc1", "fc2", "fc3"):
+                for suffix in ("weight", "bias"):
+                    if f"{nm}.{suffix}" not in csd:
+                        raise KeyError(f"committee expert {i}: critic_state_dict has no {nm}.{suffix}")
+            ws = [asd[f"{nm}.weight"] for nm in names]
+            if len(ws) < 2 or int(ws[0].shape[1]) != W or int(ws[-1].shape[0]) != n_out:
+                raise ValueError(f"committee expert {i}: the actor maps {int(ws[0].shape[1])} -> {int(ws[-1].shape[0])}, the batch needs {W} -> {n_out}")
+            actor = mlp_actor(W, n_out, hidden=tuple(int(w.shape[0]) for w in ws[:-1]), tanh=True)
+            lins = [m for m in actor if isinstance(m, nn.Linear)]
+            critic = Critic(W, n_out, hidden=(int(csd["fc1.weight"].shape[0]), int(csd["fc2.weight"].shape[0])))
+            with torch.no_grad():
+                for m, nm in zip(lins, names):
+                    m.weight.copy_(asd[f"{nm}.weight"]); m.bias.copy_(asd[f"{nm}.bias"])
+                critic.load_state_dict({k: csd[k] for k in critic.state_dict()})
+            experts.append((actor.to(batch.device).eval(), critic.to(batch.device).eval()))
+            zs.append(z)
+        return cls(experts, role, n_types, n_exploits, n_apps, type_map=type_map, epsilon=epsilon, zs=zs)
+
+    def to_strategy(self):
+        """{"committee": {"experts": [{"z", "actor_state_dict", "critic_state_dict"}, ...]}} with the reference's parameter names
+        (fc1 / fc2 / fc3), CPU tensors: what from_strategy loads bit for bit."""
+        out = []
+        for z, (a, c) in zip(self.zs, self.experts):
+            lins = [m for m in a if isinstance(m, nn.Linear)]
+            asd = {}
+            for i, m in enumerate(lins):
+                asd[f"fc{i + 1}.weight"], asd[f"fc{i + 1}.bias"] = m.weight.detach().cpu().clone(), m.bias.detach().cpu().clone()
+            out.append({"z": z, "actor_state_dict": asd, "critic_state_dict": {k: v.detach().cpu().clone() for k, v in c.state_dict().items()}})
+        return {"committee": {"experts": out}}
 
 
 DNS_TRAINING = dict(k_init=5, beta_init=1.0, c_k=1.0, c_beta=0.1, dyn_eps0=0.9, dyn_eps_min=0.001)    # do_agent.py:1388-1391

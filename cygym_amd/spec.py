@@ -47,7 +47,7 @@ DET_APL_N = 257
  SITE_EVO_POISSON, SITE_EVO_COIN, SITE_EVO_PICK_IN, SITE_EVO_PICK_ACT,
  SITE_EVO_ATT, SITE_EVO_PA, SITE_SHUFFLE, SITE_DET_COIN, SITE_LAZY, SITE_DET_FIT) = range(1, 23)
 SITE_ACTGEN = 64
-SITE_EPS_TYPE = 65
+SITE_EPS_TYPE = 65       # (a = 0 in the plain decode; expert k of a committee reads a = k: cygym_committee_decode)
 SITE_GROUP_PICK = 66
 SITE_SAMPLE = 67
 SITE_COORD_PICK = 68

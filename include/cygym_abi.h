@@ -471,7 +471,7 @@ typedef struct cygym_critic {
  * rng ticks).  Limits (CYGYM_EUNSUPPORTED beyond): H1, H2 multiples of 16 in 16 .. 128, 1 <= n_types <= 32,
  * 1 <= n_exploits <= CG_MAX_EXPLOITS (and <= n_devices), top_k <= 8.
  * CYGYM_EINVAL for a negative or non-finite noise_std and for vec_out with vec_stride < n_out.
- * Out of scope: exploit_override (:2147-2149), and building the observation on chip (h_state comes from the caller). */
+ * exploit_override (:2147-2149) is cygym_override_decode.  Out of scope: building the observation on chip (h_state comes from the caller). */
 int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* layout,
                               const cygym_actions* dst, void* stream);
 
@@ -547,9 +547,80 @@ typedef struct cygym_dns {
  * CYGYM_EINVAL (nothing is written): a NULL handle, struct or required pointer (h_state, w1a_t, w2, w3, vec, gate_out), beta_init < 0,
  * a non-finite beta_init / c_beta / sigma / dyn_eps_min, stride or vec_stride < n_out, h_stride < H1, a bad row count.
  * CYGYM_ENOTBOUND without cygym_bind.
- * Out of scope: exploit_override and the `committee` mapping; building h_state or the actor forward on chip. */
+ * Out of scope: building h_state or the actor forward on chip.  (exploit_override: cygym_override_decode; the `committee` mapping:
+ * cygym_committee_decode.) */
 int cygym_dns_decode(cygym_handle* h, const cygym_critic* c, const cygym_dns* q, const cygym_action_vectors* layout,
                      const cygym_actions* dst, void* stream);
+
+/* A committee of K DDPG experts of ONE architecture (do_agent.py:453-495: one expert per private exploit z), DEVICE pointers.  Every
+ * stacked array holds expert k behind expert k - 1, contiguously. */
+#define CG_COMMITTEE_MAX 8
+typedef struct cygym_committee {
+  cygym_actor_mlp actor;   /* the K stacked actors in the population layout of that struct: packed matrices and biases of expert k
+                              follow those of expert k - 1; obs, obs_stride, K, obs_by_env, n_hidden, width, tanh_out are read;
+                              obs_role must be 0 (the view is read, not built on chip); n_groups / rows_per_group are not read     */
+  const float* h_state;    /* [n][h_stride] state part of every expert's fc1 per SOURCE row, expert k at columns k H1 .. k H1 + H1 - 1:
+                              b1_k + W1_k[:, :W] s -- ONE addmm of the role view against the K stacked matrices, [n, W] x [W, K H1] */
+  const float* w1a;        /* [K] action part of fc1, W1_k[:, W:] ([H1][n_out]), PACKED like a hidden layer of cygym_actor_mlp with
+                              n_out inputs: [H1 / 16][ceil(n_out / 16)][64][4] per expert                                        */
+  const float* w2;         /* [K] fc2.weight packed: [H2 / 16][H1 / 16][64][4] per expert                                         */
+  const float* b2;         /* [K][H2] or NULL                                                                                    */
+  const float* w3;         /* [K][H2] fc3.weight                                                                                 */
+  const float* b3;         /* [K] fc3.bias                                                                                       */
+  int32_t* expert_out;     /* optional [n]: the winning expert of source row r                                                   */
+  float*   q_out;          /* optional [n][K]: every expert's Q                                                                  */
+  float*   vec_out;        /* optional [n][vec_stride]: encode_action of the winner's tuple; the first n_out floats are written  */
+  int32_t  n_experts;      /* K, 1 .. CG_COMMITTEE_MAX                                                                           */
+  int32_t  H1, H2;         /* multiples of 16, 16 .. 128                                                                         */
+  int32_t  h_stride;       /* floats per row of h_state, >= K H1                                                                 */
+  int32_t  vec_stride;     /* floats per row of vec_out, >= n_out (read only when vec_out is set)                                */
+  int32_t  reserved;
+} cygym_committee;
+
+/* Replaces: CommitteeStrategy.select_action (do_agent.py:453-495) for a batch, fused with the scatter into the action tensors: ONE
+ * launch per acting role and tick.  For source row r with role view s and the experts k = 0 .. K - 1 in list order:
+ *   1. v_k = actor_k(s), exactly the network cygym_actor_mlp describes (a committee of one writes bit for bit what
+ *      cygym_actor_mlp_decode writes).
+ *   2. a_k = the PLAIN decode of v_k (:970-998).  The committee calls decode_action without state, actor or critic, so the `Cord_asc`
+ *      branch is never taken and exploit_override is passed but never read on this path.  action type = first maximum of the type
+ *      logits (the INDEX; `type_map` is applied to the written row only), devices = ascending ids with value > 0, exploit and app =
+ *      argmax (app 0 when n_apps == 0).  Epsilon-greedy (:972-973, layout->epsilon_thr): expert k reads the Philox draw addressed
+ *      (global env id, the env's current rng tick, CG_SITE_EPS_TYPE, a = k) -- the counter word that is 0 in cygym_decode_actions
+ *      carries k, so expert 0 draws exactly what the plain decode draws; word 0 < epsilon_thr: the type index is
+ *      cg_index(word 1, n_types).
+ *   3. e_k = encode_action(a_k) (:910-933): 1.0 at the type index, at T + d for EVERY chosen device (the whole mask, also where the
+ *      written list is cut at max_devs), at T + D + x and, when n_apps > 0, at T + D + E + app; the exploit index is < E, so the field
+ *      swap of :919-920 cannot occur.
+ *   4. q_k = critic_k(s, e_k) in fp32: fc1 = h_state + the action part as one more matrix-core layer over the 0 / 1 vector (every
+ *      product exact: the sum of the set columns, k-groups of 16 outputs ascending in two accumulator chains, k-slices in order),
+ *      relu, fc2 on the matrix cores (v_mfma_f32_16x16x4_f32), relu(. + b2), the fc3 dot (per lane c = lane, lane + 64; a butterfly
+ *      over the wave), + b3.
+ *   5. the winner is the first k whose q_k is strictly greater than every earlier one (:493-494); its tuple is written as group 0 of
+ *      the row exactly like cygym_decode_actions, CG_DECODE_TRUNCATED included.
+ * Values must be finite (the reference returns None when every Q is NaN: not restated; such a row keeps expert 0).
+ * From `layout`: rows, type_map, n_types, n_devices (= the handle's), n_exploits, n_apps, n, epsilon_thr, status.
+ * Limits (CYGYM_EUNSUPPORTED beyond): 1 <= K <= CG_COMMITTEE_MAX; 1 to 3 hidden actor layers of widths that are multiples of 16 up
+ * to 256; n_out = n_types + n_devices + n_exploits + n_apps <= 512 (the chunked decode of wider vectors is not built here);
+ * obs_role == 0; H1, H2 multiples of 16 in 16 .. 128; 1 <= n_types <= 32; 1 <= n_exploits <= CG_MAX_EXPLOITS; the plan must fit LDS.
+ * CYGYM_EINVAL (nothing is written): a NULL handle, struct or required pointer, h_stride < K H1, vec_out with vec_stride < n_out, a
+ * bad row count.  CYGYM_ENOTBOUND: epsilon_thr > 0 without cygym_bind.
+ * Out of scope: building h_state or the role view on chip. */
+int cygym_committee_decode(cygym_handle* h, const cygym_committee* cm, const cygym_action_vectors* layout, const cygym_actions* dst,
+                           void* stream);
+
+/* Replaces: decode_action(..., exploit_override = z) in the `Cord_asc` mode (do_agent.py:2147-2149, reached from :1398) for a batch, fused
+ * with the scatter into the action tensors -- what train_exploit_committee (:1253-1277) trains every expert of a committee with.  `src->vec`
+ * holds the actor's RAW outputs; the decision of a row is (arg-max of its first n_types values -- first maximum --, [z], [], 0): the critic
+ * is not consulted, the device list is empty, and z is an exploit ID handed through as it is (the tick ignores an id outside the
+ * topology's exploits).  Written as group 0 of the rows like cygym_decode_actions (the type through `type_map`).  No draw is read.
+ * vec_out (optional, [n][vec_stride]): row r receives encode_action of that tuple (:910-933 as :1424 calls it), where the field swap of
+ * :919-920 matters: for z >= n_exploits the fields swap -- 1.0 at T + z (DEVICE bit z) and the exploit one-hot at T + D + 0 --, for
+ * z < n_exploits 1.0 at T + D + z and no device bit; 1.0 at the type INDEX (before type_map) and, when n_apps > 0, at T + D + E; 0.0
+ * elsewhere among the first n_out floats.
+ * CYGYM_EINVAL (nothing is written): z < 0 or z >= n_devices (the reference raises there), stride or vec_stride < n_out, a NULL pointer,
+ * a bad row count. */
+int cygym_override_decode(cygym_handle* h, const cygym_action_vectors* src, int32_t exploit_override, float* vec_out, int32_t vec_stride,
+                          const cygym_actions* dst, void* stream);
 
 /* The opponent of a best-response trainer on a batch: one strategy of the opponent's pool per env and opponent turn, drawn from the
  * equilibrium mixture.  DEVICE pointers; S members. */
