@@ -123,6 +123,13 @@ class Critic(C.Structure):
                 ("b3", C.c_float), ("H1", C.c_int32), ("H2", C.c_int32), ("h_stride", C.c_int32), ("top_k", C.c_int32), ("vec_stride", C.c_int32)]
 
 
+CRITIC_POP_MAX = 32
+
+
+class CriticPop(C.Structure):
+    _fields_ = [("slot_of_row", C.c_void_p), ("b3s", C.c_void_p), ("h_group_stride", C.c_int64), ("n_slots", C.c_int32), ("reserved", C.c_int32)]
+
+
 COMMITTEE_MAX = 8
 
 

@@ -709,6 +709,62 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_coord_ascent_decode(self._h, C.byref(cr), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_coord_ascent_decode")
 
+    def _coord_pop_structs(self, rows, h_state, slot_of_row, critic_pack, n_types, n_exploits, n_apps, type_map, act, top_k, tau, pick_out, q_out):
+        """Argument checks and marshalling of coord_ascent_decode_pop: (Critic, CriticPop, ActionVectors, Actions, tensors to keep)."""
+        dst = self.actions_struct(act)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        if not ok(h_state) or h_state.dim() not in (2, 3) or h_state.stride(-1) != 1:
+            raise ValueError("h_state must be a [n, H1] or [S, n, H1] float32 tensor on the batch's device with unit inner stride")
+        n, H1 = int(h_state.shape[-2]), int(h_state.shape[-1])
+        src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, 0.0)
+        w1a_t, w2, b2, w3, b3s = critic_pack
+        if not ok(b3s) or b3s.dim() != 1 or not b3s.is_contiguous():
+            raise ValueError("critic_pack: b3s must be a contiguous float32 [S] tensor (fc3.bias of every critic)")
+        S_ = int(b3s.numel())
+        if not ok(w3) or not w3.is_contiguous() or w3.dim() != 2 or int(w3.shape[0]) != S_ or int(w3.shape[1]) < 1:
+            raise ValueError(f"critic_pack: w3 must be a contiguous float32 [{S_}, H2] tensor")
+        H2 = int(w3.shape[1])
+        if not ok(w1a_t) or tuple(w1a_t.shape) != (S_, n_out, H1) or not w1a_t.is_contiguous():
+            raise ValueError(f"critic_pack: w1a_t must be a contiguous float32 {[S_, n_out, H1]} tensor (fc1.weight[:, W:].t() of every critic)")
+        if not ok(w2) or not w2.is_contiguous() or w2.numel() != S_ * ((H2 + 15) // 16) * ((H1 + 15) // 16) * 256:
+            raise ValueError("critic_pack: packed fc2 weights have the wrong size (pack_linear of every critic, critic after critic)")
+        if b2 is not None and (not ok(b2) or not b2.is_contiguous() or b2.numel() != S_ * H2):
+            raise ValueError(f"critic_pack: b2 must hold {S_ * H2} float32 values")
+        if h_state.dim() == 3 and (int(h_state.shape[0]) != S_ or (n > 1 and h_state.stride(0) < (n - 1) * h_state.stride(1) + H1)):
+            raise ValueError(f"h_state [S, n, H1] must hold one block per critic ({S_}), block after block")
+        slot_of_row = _exactly(n, slot_of_row, torch.int32, self.device, "slot_of_row")
+        keep.append(slot_of_row)
+        cr, pop = abi.Critic(), abi.CriticPop()
+        cr.h_state, cr.h_stride = h_state.data_ptr(), int(h_state.stride(-2)) if n > 1 else H1
+        cr.w1a_t, cr.w2, cr.w3, cr.b2 = w1a_t.data_ptr(), w2.data_ptr(), w3.data_ptr(), (b2.data_ptr() if b2 is not None else None)
+        cr.H1, cr.H2, cr.top_k, cr.tau = H1, H2, int(top_k), float(tau)
+        pop.slot_of_row, pop.b3s, pop.n_slots = slot_of_row.data_ptr(), b3s.data_ptr(), S_
+        pop.h_group_stride = (int(h_state.stride(0)) if S_ > 1 else n * cr.h_stride) if h_state.dim() == 3 else 0
+        for name, t, dt in (("pick_out", pick_out, torch.int16), ("q_out", q_out, torch.float32)):
+            if t is not None:
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n, self.M):
+                    raise ValueError(f"{name} must be a contiguous {dt} {[n, self.M]} tensor on {self.device}")
+                setattr(cr, name, t.data_ptr())
+        return cr, pop, src, dst, keep
+
+    def coord_ascent_decode_pop(self, rows, h_state: torch.Tensor, slot_of_row: torch.Tensor, critic_pack, n_types: int,
+                                n_exploits: int | None = None, n_apps: int = 0, type_map=None, act=None, top_k: int = 5, tau: float = 0.5,
+                                pick_out=None, q_out=None):
+        """coord_ascent_decode in eval mode for a POPULATION of S same-shaped critics (1 <= S <= 32), each deciding for some of the
+        rows: ONE launch (cygym_coord_ascent_decode_pop) -- source row r is decoded exactly as coord_ascent_decode would with critic
+        slot_of_row[r].
+          slot_of_row  [n] int32 on the device; a row whose entry is negative or >= S is left alone (nothing of it is written)
+          h_state      [n, H1]: row r formed with ITS critic;  or [S, n, H1]: block s formed with critic s, row r reads block
+                       slot_of_row[r] (the caller does not know on the host which row plays whom)
+          critic_pack  (w1a_t [S, n_out, H1], w2 = the S pack_linear(fc2.weight) critic after critic, b2 [S, H2] or None,
+                        w3 [S, H2], b3s [S]) -- policies.CoordAscentPolicyGroup stacks them
+          top_k, tau   common to the population (the oracle's coord_K, coord_tau)
+        There is no noise_std / vec_out: a critic in training decides through coord_ascent_decode."""
+        cr, pop, src, dst, keep = self._coord_pop_structs(rows, h_state, slot_of_row, critic_pack, n_types, n_exploits, n_apps, type_map, act,
+                                                          top_k, tau, pick_out, q_out)
+        _lib.check(self.lib.cygym_coord_ascent_decode_pop(self._h, C.byref(cr), C.byref(pop), C.byref(src), C.byref(dst), self._stream()),
+                   self._h, "cygym_coord_ascent_decode_pop")
+
     def committee_decode(self, rows, obs: torch.Tensor, h_state: torch.Tensor, hidden_layers, head, critic_pack, n_experts: int, n_types: int,
                          n_exploits: int | None = None, n_apps: int = 0, type_map=None, act=None, epsilon: float = 0.0, tanh: bool = True,
                          obs_by_env: bool = False, expert_out=None, q_out=None, vec_out=None):

@@ -48,6 +48,7 @@ def _parse_resources(text: str) -> dict:
 INST = os.path.join(HERE, "csrc", "cg_inst.hip")
 INST_ACTOR = os.path.join(HERE, "csrc", "cg_inst_actor.hip")
 INST_COORD = os.path.join(HERE, "csrc", "cg_inst_coord.hip")
+INST_COORD_POP = os.path.join(HERE, "csrc", "cg_inst_coord_pop.hip")
 INST_COMMITTEE = os.path.join(HERE, "csrc", "cg_inst_committee.hip")
 INST_DNS = os.path.join(HERE, "csrc", "cg_inst_dns.hip")
 INST_MIXTURE = os.path.join(HERE, "csrc", "cg_inst_mixture.hip")
@@ -87,6 +88,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         if dev_mt is None or dev_mt == 256:   # the tick + actor kernels (256 devices only)
             units.append(("inst_actor", base + ["-c", INST_ACTOR, "-o", os.path.join(tmp, "inst_actor.o")]))
         units.append(("inst_coord", base + ["-c", INST_COORD, "-o", os.path.join(tmp, "inst_coord.o")]))   # the coordinate-ascent decode
+        units.append(("inst_coord_pop", base + ["-c", INST_COORD_POP, "-o", os.path.join(tmp, "inst_coord_pop.o")]))   # ... for a population of critics
         units.append(("inst_committee", base + ["-c", INST_COMMITTEE, "-o", os.path.join(tmp, "inst_committee.o")]))   # the committee of DDPG experts
         units.append(("inst_dns", base + ["-c", INST_DNS, "-o", os.path.join(tmp, "inst_dns.o")]))   # the dynamic neighbourhood search
         units.append(("inst_mixture", base + ["-c", INST_MIXTURE, "-o", os.path.join(tmp, "inst_mixture.o")]))   # the mixture draw and the tiled whole-actor decode

@@ -1,5 +1,5 @@
 // cg_decode.hpp -- device code shared by the consumer-side kernels of the C-ABI unit (cg_aux_kernels.hpp), the tick + actor unit
-// (cg_inst_actor.hip), the coordinate-ascent unit (cg_inst_coord.hip), the hierarchical unit (cg_inst_hier.hip), the H-MARL unit (cg_inst_hmarl.hip) the MetaDOAR unit (cg_inst_meta.hip), its observer's unit (cg_inst_meta_select.hip) and the committee unit (cg_inst_committee.hip).  Templates and force-inlined device functions only
+// (cg_inst_actor.hip), the coordinate-ascent units (cg_inst_coord.hip, cg_inst_coord_pop.hip), the hierarchical unit (cg_inst_hier.hip), the H-MARL unit (cg_inst_hmarl.hip) the MetaDOAR unit (cg_inst_meta.hip), its observer's unit (cg_inst_meta_select.hip) and the committee unit (cg_inst_committee.hip).  Templates and force-inlined device functions only
 // (included in more than one translation unit, inside namespace cygym_k).  What every writer of group 0 of an action row shares:
 //   dpp_pair_max, float_order_bits   wave-wide lexicographic max of (order bits, ~index) pairs
 //   wave_first_max                   ... read back as "index of the first maximum, 0 if none": decode_row_regs, the chunked decode of

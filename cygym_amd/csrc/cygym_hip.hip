@@ -63,6 +63,9 @@ extern template __global__ void coord_ascent_kernel<false, true, false>(cygym_cr
 extern template __global__ void coord_ascent_kernel<true, true, false>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
 extern template __global__ void coord_ascent_kernel<false, true, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
 extern template __global__ void coord_ascent_kernel<true, true, true>(cygym_critic, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+// ... and for a population of critics (cg_inst_coord_pop.hip)
+extern template __global__ void coord_pop_kernel<false>(cygym_critic, cygym_critic_pop, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
+extern template __global__ void coord_pop_kernel<true>(cygym_critic, cygym_critic_pop, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t);
 }  // namespace cygym_k
 
 // the committee decode lives in its own unit (cg_inst_committee.hip): declared, not instantiated, here
@@ -322,6 +325,7 @@ int cygym_sizeof(int32_t which) {
     case 39: return (int)sizeof(cygym_ippo_adv_desc);   // (index 38 stays unassigned)
     case 40: return (int)sizeof(cygym_ippo_head_desc);
     case 42: return (int)sizeof(cygym_committee);   // (index 41 stays unassigned: earlier bindings probe it for -1)
+    case 44: return (int)sizeof(cygym_critic_pop);   // (index 43 stays unassigned)
     default: return -1;
   }
 }
@@ -933,27 +937,34 @@ int cygym_mixture_draw(cygym_handle* h, const cygym_mixture* mix, void* stream) 
   return CYGYM_OK;
 }
 
+// What cygym_coord_ascent_decode and cygym_coord_ascent_decode_pop check alike, in the order a caller sees (own_ptrs: the pointers
+// of the function's own descriptors are there), and the LDS the row kernel needs.
+static int check_coord_ascent(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* src, const cygym_actions* dst, const char* who,
+                              const char* bad_layout, bool own_ptrs, size_t* lds) {
+  if (h && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (the picks are drawn at the envs' rng ticks)", who);
+  if (const int rc = check_vectors(h, src, dst, who, c && c->h_state && c->w1a_t && c->w2 && c->w3 && own_ptrs, 1, bad_layout)) return rc;
+  if (c->h_stride < c->H1 || c->top_k < 1 || !(c->tau > 0.0) || !(c->tau < 1e300)) return fail(h, CYGYM_EINVAL, bad_layout, "");
+  if (c->H1 < 16 || c->H1 > CA_MAX_H || (c->H1 & 15) || c->H2 < 16 || c->H2 > CA_MAX_H || (c->H2 & 15))
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: critic widths H1, H2 must be multiples of 16 in 16 .. 128", who);
+  if (src->n_types > CA_MAX_TYPES || src->n_exploits > CG_MAX_EXPLOITS || src->n_exploits > src->n_devices || c->top_k > CA_MAX_TOPK)
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: at most 32 action types, CG_MAX_EXPLOITS exploits (and no more than devices), top_k <= 8", who);
+  if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
+  if (!(c->noise_std >= 0.0) || !(c->noise_std < 1e300)) return fail(h, CYGYM_EINVAL, "%s: noise_std must be finite and >= 0", who);
+  if (c->vec_out && c->vec_stride < src->n_types + src->n_devices + src->n_exploits + src->n_apps)
+    return fail(h, CYGYM_EINVAL, "%s: vec_stride is smaller than n_out = n_types + n_devices + n_exploits + n_apps", who);
+  *lds = (size_t)ca_plan(c->H1, c->H2, src->n_types, src->n_exploits, src->n_devices).total * sizeof(float);
+  if (*lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the critic does not fit in LDS", who);
+  return CYGYM_OK;
+}
+
 int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* src, const cygym_actions* dst,
                               void* stream) {
   const char* const who = "cygym_coord_ascent_decode";
   const char* const bad_layout = "cygym_coord_ascent_decode: bad layout (types, exploits >= 1, the handle's device count, h_stride >= H1, top_k >= 1, tau > 0)%s";
-  if (h && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_coord_ascent_decode: handle not bound (the picks are drawn at the envs' rng ticks)%s", "");
-  if (const int rc = check_vectors(h, src, dst, who, c && c->h_state && c->w1a_t && c->w2 && c->w3, 1, bad_layout)) return rc;
-  if (c->h_stride < c->H1 || c->top_k < 1 || !(c->tau > 0.0) || !(c->tau < 1e300)) return fail(h, CYGYM_EINVAL, bad_layout, "");
-  if (c->H1 < 16 || c->H1 > CA_MAX_H || (c->H1 & 15) || c->H2 < 16 || c->H2 > CA_MAX_H || (c->H2 & 15))
-    return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: critic widths H1, H2 must be multiples of 16 in 16 .. 128%s", "");
-  if (src->n_types > CA_MAX_TYPES || src->n_exploits > CG_MAX_EXPLOITS || src->n_exploits > src->n_devices || c->top_k > CA_MAX_TOPK)
-    return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: at most 32 action types, CG_MAX_EXPLOITS exploits (and no more than devices), top_k <= 8%s", "");
-  if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
-  if (!(c->noise_std >= 0.0) || !(c->noise_std < 1e300))
-    return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: noise_std must be finite and >= 0%s", "");
-  if (c->vec_out && c->vec_stride < src->n_types + src->n_devices + src->n_exploits + src->n_apps)
-    return fail(h, CYGYM_EINVAL, "cygym_coord_ascent_decode: vec_stride is smaller than n_out = n_types + n_devices + n_exploits + n_apps%s", "");
+  size_t lds = 0;
+  if (const int rc = check_coord_ascent(h, c, src, dst, who, bad_layout, true, &lds)) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  const CaPlan pl = ca_plan(c->H1, c->H2, src->n_types, src->n_exploits, src->n_devices);
-  const size_t lds = (size_t)pl.total * sizeof(float);
-  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_coord_ascent_decode: the critic does not fit in LDS%s", "");
   // <SAMPLE, NOISE, VEC>: noise_std == 0 and vec_out == NULL select the eval-mode kernels
   static const void* const kernels[8] = {
       (const void*)coord_ascent_kernel<false, false, false>, (const void*)coord_ascent_kernel<true, false, false>,
@@ -963,6 +974,24 @@ int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygy
   const void* k = kernels[(c->top_k > 1 ? 1 : 0) | (c->noise_std > 0.0 ? 2 : 0) | (c->vec_out ? 4 : 0)];
   if (const int rc = raise_lds_once(h, k)) return rc;
   return launch_decode(h, k, dim3(src->n), dim3(CA_THREADS), lds, stream, {c, src, dst});   // one workgroup per row
+}
+
+int cygym_coord_ascent_decode_pop(cygym_handle* h, const cygym_critic* c, const cygym_critic_pop* pop, const cygym_action_vectors* src,
+                                  const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_coord_ascent_decode_pop";
+  const char* const bad_layout = "cygym_coord_ascent_decode_pop: bad layout (types, exploits >= 1, the handle's device count, h_stride >= H1, top_k >= 1, tau > 0)%s";
+  size_t lds = 0;
+  if (const int rc = check_coord_ascent(h, c, src, dst, who, bad_layout, pop && pop->slot_of_row && pop->b3s, &lds)) return rc;
+  if (pop->n_slots < 1 || pop->n_slots > CG_CRITIC_POP_MAX) return fail(h, CYGYM_EUNSUPPORTED, "%s: 1 to CG_CRITIC_POP_MAX critics", who);
+  if (c->noise_std != 0.0 || c->vec_out)
+    return fail(h, CYGYM_EINVAL, "%s: eval mode only (noise_std = 0, no vec_out): a critic in training decides through cygym_coord_ascent_decode", who);
+  if (pop->h_group_stride < 0 || (pop->h_group_stride > 0 && src->n > 0 && pop->h_group_stride < (int64_t)(src->n - 1) * c->h_stride + c->H1))
+    return fail(h, CYGYM_EINVAL, "%s: h_group_stride is 0 (h_state by source row) or at least one block, (n - 1) h_stride + H1", who);
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const void* k = c->top_k > 1 ? (const void*)coord_pop_kernel<true> : (const void*)coord_pop_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  return launch_decode(h, k, dim3(src->n), dim3(CA_THREADS), lds, stream, {c, pop, src, dst});   // one workgroup per row
 }
 
 int cygym_committee_decode(cygym_handle* h, const cygym_committee* cm, const cygym_action_vectors* src, const cygym_actions* dst,

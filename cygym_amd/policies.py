@@ -10,7 +10,9 @@ architecture (do_agent.py:357-370); `mlp_actor` a smaller one.
 `CoordAscentPolicy` is the same loop in the reference's DEFAULT best-response mode (`--BR_type Cord_asc`): there
 decode_action does not read the actor at all but scores one-device candidate actions with the CRITIC
 (`DoubleOracle.greedy_device_coord_ascent`, do_agent.py:2137-2219); the batch does that in one launch
-(cygym_coord_ascent_decode).  `reference_critic` builds the reference's critic (do_agent.py:373-388).
+(cygym_coord_ascent_decode).  `reference_critic` builds the reference's critic (do_agent.py:373-388).  `CoordAscentPolicyGroup` is a
+population of such strategies of one shape decided in one launch (cygym_coord_ascent_decode_pop): the payoff grid and the mixture
+opponent of that mode hold several critics, each deciding for a few envs.
 
 `CommitteePolicy` is the fifth typed family of the loop, `"committee"` (CommitteeStrategy.select_action, do_agent.py:453-495): one DDPG
 expert per private exploit; every expert's actor proposes, the plain decode and encode_action turn the proposal into the critic's input,
@@ -590,6 +592,109 @@ class CoordAscentPolicy:
         tm = self._map(obs.device)
         at = at.to(torch.int32) if tm is None else tm[at]
         return {"atype": at, "exploit": ex.to(torch.int32), "dev_mask": on, "app": torch.zeros_like(at)}
+
+
+class CoordAscentPolicyGroup:
+    """A population of CoordAscentPolicy strategies of ONE shape in eval mode (key) decided together: the state parts of fc1 are one
+    batched GEMM and the decode + scatter of all of them is ONE launch (cygym_coord_ascent_decode_pop), the critic of a source row
+    taken from a slot table.  The decode runs a workgroup per row, so a launch per strategy over that strategy's few rows leaves most
+    of the chip idle; the |D| x |A| grid of a Double-Oracle population in the reference's default mode and the opponent drawn per env
+    from an equilibrium (MixturePolicy) hold several critics of one shape, each deciding for a few envs.
+    counts: the rows of every member when the rows arrive ordered member after member (simulate_grid builds that; any counts, equal
+    or not) -- the slot table is then made once, and h_state is formed per source row.  Without counts write() takes the caller's
+    slot table."""
+
+    tick_free = True
+
+    def __init__(self, policies, counts=None):
+        self.policies = list(policies)
+        p0 = self.policies[0]
+        if not 1 <= len(self.policies) <= 32:
+            raise ValueError("1 to 32 critics")
+        self.n_types, self.n_exploits, self.n_apps, self.top_k, self.tau = p0.n_types, p0.n_exploits, p0.n_apps, p0.top_k, p0.tau
+        self.action_types = sorted({t for p in self.policies for t in p.action_types})
+        self.counts = None if counts is None else [int(c) for c in counts]
+        if self.counts is not None and len(self.counts) != len(self.policies):
+            raise ValueError("counts: one row count per member")
+        self._pk = self._pk_ver = self._slots = None
+
+    @staticmethod
+    def key(p, M):
+        """What must agree across the members of a population -- state width, T, E, A, H1, H2, top_k, tau, type_map -- or None when
+        `p` cannot be one: not a CoordAscentPolicy, in training mode (the noise belongs to one critic's launch) or with exploit_override."""
+        if not isinstance(p, CoordAscentPolicy) or p.exploit_override is not None or p.active_noise_std != 0.0:
+            return None
+        W = p.fc1.in_features - p.n_out(M)
+        if W < 1:
+            return None
+        tm = None if p.type_map is None else tuple(int(x) for x in p.type_map.tolist())
+        return (W, p.n_types, p.n_exploits, p.n_apps, p.fc1.out_features, p.fc2.out_features, p.top_k, p.tau, tm)
+
+    def n_out(self, M):
+        return self.policies[0].n_out(M)
+
+    def _stacked(self, batch):
+        """(w1s_t [S, W, H1], b1 [S, 1, H1], critic pack of coord_ascent_decode_pop): the members' packs slot after slot, redone when a
+        member's parameter changes (the members' own _packed versions)."""
+        packs = [p._packed(batch, batch.M) for p in self.policies]
+        ver = tuple(p._pk_ver for p in self.policies)
+        if self._pk_ver != ver:
+            b2s = [pk[2][2] for pk in packs]
+            self._pk = (torch.stack([pk[0] for pk in packs]).contiguous(), torch.stack([pk[1] for pk in packs])[:, None, :].contiguous(),
+                        (torch.stack([pk[2][0] for pk in packs]).contiguous(), torch.cat([pk[2][1].reshape(-1) for pk in packs]).contiguous(),
+                         None if b2s[0] is None else torch.stack(b2s).contiguous(), torch.stack([pk[2][3] for pk in packs]).contiguous(),
+                         torch.cat([p.fc3.bias.detach().reshape(1) for p in self.policies]).contiguous()))      # (b3s: no host read)
+            self._pk_ver = ver
+        return self._pk
+
+    def slot_table(self, device):
+        """[sum(counts)] int32: the member of every source row when the rows come member after member."""
+        if self._slots is None or self._slots.device != device:
+            self._slots = torch.repeat_interleave(torch.arange(len(self.counts), dtype=torch.int32), torch.tensor(self.counts)).to(device)
+        return self._slots
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, slot_of_row=None, pick_out=None, q_out=None, shared_obs=False):
+        """ONE decode launch for all members.  Default: obs [n, W] holds the members' rows member after member (counts) and h_state is
+        formed per source row -- one baddbmm when the counts are equal, else one addmm per member on its slice.  shared_obs: every
+        row may play any member (slot_of_row is the caller's, made on the device): h_state is one baddbmm to [S, n, H1] and the
+        kernel reads the block of the row's slot."""
+        w1s_t, b1, pack = self._stacked(batch)
+        S_, W, H1 = (int(x) for x in w1s_t.shape)
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != W:
+            raise ValueError(f"obs must be a float32 [n, {W}] role view")
+        n = int(obs.shape[0])
+        if shared_obs:
+            if slot_of_row is None:
+                raise ValueError("shared_obs: the caller says which row plays whom (slot_of_row)")
+            h_state = torch.baddbmm(b1, obs[None].expand(S_, n, W), w1s_t)
+        else:
+            if self.counts is None or sum(self.counts) != n:
+                raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
+            if slot_of_row is None:
+                slot_of_row = self.slot_table(obs.device)
+            if len(set(self.counts)) == 1:
+                h_state = torch.baddbmm(b1, obs.reshape(S_, n // S_, W), w1s_t).reshape(n, H1)
+            else:
+                h_state, lo = torch.empty((n, H1), dtype=torch.float32, device=obs.device), 0
+                for s, c in enumerate(self.counts):
+                    if c:
+                        torch.addmm(b1[s, 0], obs[lo:lo + c], w1s_t[s], out=h_state[lo:lo + c])
+                    lo += c
+        batch.coord_ascent_decode_pop(rows, h_state, slot_of_row, pack, self.n_types, self.n_exploits, self.n_apps,
+                                      self.policies[0]._map(obs.device), act, top_k=self.top_k, tau=self.tau, pick_out=pick_out, q_out=q_out)
+
+    @torch.no_grad()
+    def __call__(self, obs, t, M, L):
+        """The members' own torch decode on their slices (batch-likes without the library; top_k = 1 only, as CoordAscentPolicy)."""
+        if self.counts is None or sum(self.counts) != int(obs.shape[0]):
+            raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
+        outs, lo = [], 0
+        for p, c in zip(self.policies, self.counts):
+            if c:
+                outs.append(p(obs[lo:lo + c], t, M, L))
+            lo += c
+        return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
 
 
 def _net_forward(net, x, dtype):
@@ -2721,7 +2826,10 @@ class MixturePolicy:
          baseline_state), this tick's mode word written straight into act["mode"], and the row lists of the members;
       2. the members that are ActorPolicy of ONE architecture (ActorPolicyGroup.key) with fused_mlp(batch), two or more: ONE
          cygym_actor_mlp_decode_tiled over the tiles of the draw, reading `obs` in place (tiled = False: off);
-      3. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
+      3. among the other members, the CoordAscentPolicy of ONE shape in eval mode (CoordAscentPolicyGroup.key) that can play, two or
+         more: one index op turns the drawn members into critic slots (-1 for everyone else's envs), one baddbmm forms h_state for
+         every (critic, env), and ONE cygym_coord_ascent_decode_pop decodes all envs in order (tiled = False: off);
+      4. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
          rollout_grid.SequencePolicy + write_actions with the tick the loop set (set_tick: the loop's tick counter; a callable without
          uses_global_tick gets t // 2, as the loops call it).  A member of probability 0 never plays and is not launched.
     act["n_groups"] is the caller's to clear before the call (Turns.opponent, ddpg_rollout.collect do); a member that writes groups sets
@@ -2788,11 +2896,30 @@ class MixturePolicy:
             slots[s] = pos
         return ActorPolicyGroup([self.members[s] for s in best]), slots
 
+    def _critic_group(self, batch):
+        """(CoordAscentPolicyGroup, critic slot of every member or -1) of the largest set of same-key CoordAscentPolicy members that can
+        play, or (None, all -1)."""
+        slots = [-1] * len(self.members)
+        if not (self.tiled and hasattr(batch, "mixture_draw") and hasattr(batch, "coord_ascent_decode_pop")):
+            return None, slots
+        by_key = {}
+        for s, m in enumerate(self.members):
+            k = CoordAscentPolicyGroup.key(m, batch.M)
+            if k is not None and self.probs[s] > 0.0:
+                by_key.setdefault(k, []).append(s)
+        best = max(by_key.values(), key=len, default=[])
+        if len(best) < 2:
+            return None, slots
+        for pos, s in enumerate(best):
+            slots[s] = pos
+        return CoordAscentPolicyGroup([self.members[s] for s in best]), slots
+
     def _state(self, batch):
         st = self._st
         if st is None or st["batch"] is not batch:
             N, S_, dev = batch.N, len(self.members), batch.device
             grp, slots = self._group(batch)
+            cgrp, cslots = self._critic_group(batch)
             T = (N + 15) // 16 + S_
             z = lambda shape, dt, v=0: torch.full(shape, v, dtype=dt, device=dev)  # noqa: E731
             st = self._st = dict(batch=batch, group=grp, slots=slots, cdf=torch.from_numpy(self.cdf).to(dev),
@@ -2800,7 +2927,9 @@ class MixturePolicy:
                                  member_slot=torch.tensor(slots, dtype=torch.int8, device=dev), baseline_state=z((N,), torch.int8, -1),
                                  index=z((N,), torch.uint8), rows_masked=z((S_, N), torch.int32, -1), rows_ok=None,
                                  rows_tiled=z((16 * T,), torch.int32, -1) if grp is not None else None,
-                                 tile_slot=z((T,), torch.int32, -1) if grp is not None else None)
+                                 tile_slot=z((T,), torch.int32, -1) if grp is not None else None,
+                                 critics=cgrp, critic_slots=cslots, critic_slot_of=torch.tensor(cslots, dtype=torch.int32, device=dev),
+                                 slot_of_row=z((N,), torch.int32, -1) if cgrp is not None else None)
         return st
 
     def _check_rows(self, st, rows, N):
@@ -2833,8 +2962,13 @@ class MixturePolicy:
             batch.actor_mlp_decode(st["rows_tiled"], obs, hidden, head, grp.n_types, grp.n_exploits, grp.n_apps, p0._map(batch.device), act,
                                    epsilon=grp.epsilon, tanh=p0._split_mlp(batch.M)[2], n_groups=len(grp.policies), obs_by_env=True,
                                    tile_slot=st["tile_slot"])
+        cgrp, cslots = st["critics"], st["critic_slots"]
+        if cgrp is not None and in_place:
+            # the critic slot of every env's member (-1: another member's env), then ONE decode launch over all envs in order
+            torch.index_select(st["critic_slot_of"], 0, st["index"].to(torch.int32), out=st["slot_of_row"])
+            cgrp.write(batch, act, None, obs[:N], slot_of_row=st["slot_of_row"], shared_obs=True)
         for s, m in enumerate(self.members):
-            if (grp is not None and in_place and slots[s] >= 0) or self.probs[s] == 0.0:
+            if (grp is not None and in_place and slots[s] >= 0) or (cgrp is not None and in_place and cslots[s] >= 0) or self.probs[s] == 0.0:
                 continue
             r = st["rows_masked"][s]
             if hasattr(m, "write"):
@@ -2862,7 +2996,7 @@ class MixturePolicy:
             r = torch.nonzero(idx_t == s).reshape(-1)
             if r.numel() == 0:
                 continue
-            if hasattr(m, "write"):
+            if hasattr(m, "write") and (hasattr(batch, "write_actions") or not callable(m)):      # (no library: a member that is also a torch callable decodes itself)
                 m.write(batch, act, r.to(torch.int32), obs[r])
             else:
                 _write_rows(batch, act, r, m(obs[r], self._member_tick(m), batch.M, batch.L), batch.L)

@@ -225,6 +225,41 @@ def _group_actors(batch, items, M, env_order_rpg=None):
     return [(grp, r64, r64.to(torch.int32), sl, rpg)]
 
 
+def _group_critics(batch, items, M):
+    """Strategies of one role and sub-batch that are CoordAscentPolicy of ONE shape in eval mode (policies.CoordAscentPolicyGroup.key), two
+    or more, become one item: their decode is one launch over all their rows (a row is a workgroup there: any row counts, equal or
+    not), the slot table and the concatenated row ids made here, once.  On a batch-like without the library the item decodes with the
+    members' torch code."""
+    from .policies import CoordAscentPolicyGroup
+    if len(items) < 2 or (hasattr(batch, "role_obs") and not hasattr(batch, "coord_ascent_decode_pop")):
+        return items
+    by_key = {}
+    for i, it in enumerate(items):
+        k = CoordAscentPolicyGroup.key(it[0], M)
+        if k is not None:
+            by_key.setdefault(k, []).append(i)
+    first = {}
+    for members in by_key.values():
+        for lo in range(0, len(members), 32):      # (a population holds at most 32 critics)
+            chunk = members[lo:lo + 32]
+            if len(chunk) >= 2:
+                first[chunk[0]] = chunk
+    taken = {i for chunk in first.values() for i in chunk[1:]}
+    out = []
+    for i, it in enumerate(items):
+        if i in taken:
+            continue
+        if i not in first:
+            out.append(it)
+            continue
+        chunk = [items[j] for j in first[i]]
+        r64 = torch.cat([c[1] for c in chunk])
+        ids = r64.cpu().numpy()
+        sl = slice(int(ids[0]), int(ids[-1]) + 1) if (np.diff(ids) == 1).all() else None
+        out.append((CoordAscentPolicyGroup([c[0] for c in chunk], counts=[int(c[1].numel()) for c in chunk]), r64, r64.to(torch.int32), sl, None))
+    return out
+
+
 def _role_actions(batch, pol, M, L):
     """One action dict per role: the roles share every tensor but the mode words (no per-tick copy in steady state).  A role
     with a strategy that writes groups (`writes_groups`: policies.CommActorPolicy, policies.HMARLPolicy, policies.MetaPolicy) also gets an n_groups tensor of its own: the
@@ -336,7 +371,7 @@ def simulate_grid(batch, def_policies, att_policies, n_mc: int, T: int, randomiz
                 items.append((p, t64, t64.to(torch.int32), sl, None))
             # the whole grid in env order: env e plays defender strategy e // (nA n_mc) and attacker strategy (e // n_mc) % nA
             rpg = (nA * n_mc if r == HL.DEFENDER else n_mc) if (S_sub == 1 and cell_offset == 0 and N == cells) else None
-            plan[r].append(_group_actors(batch, items, M, rpg) if fused else items)
+            plan[r].append(_group_critics(batch, _group_actors(batch, items, M, rpg) if fused else items, M))
     bl = baseline_schedule(def_policies, att_policies, cell_np, n_mc, min(T, 4), _cfg_baseline_code(batch))
     # (ticks >= 2 repeat with period 2: rows 2 / 3 of the schedule; shorter runs only have the first rows)
     mode_words = [torch.from_numpy(((bl[t] + 1) << S.MODE_BASELINE_SHIFT) | (t % 2)).to(device=dev, dtype=torch.int32)

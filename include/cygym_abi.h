@@ -475,6 +475,36 @@ typedef struct cygym_critic {
 int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygym_action_vectors* layout,
                               const cygym_actions* dst, void* stream);
 
+/* A population of same-shaped critics for cygym_coord_ascent_decode_pop.  DEVICE pointers. */
+#define CG_CRITIC_POP_MAX 32
+typedef struct cygym_critic_pop {
+  const int32_t* slot_of_row;  /* [n] the critic of SOURCE row r: 0 .. n_slots - 1; any other value: the row is left alone          */
+  const float*   b3s;          /* [n_slots] fc3.bias of every slot (cygym_critic.b3 is not read)                                     */
+  int64_t  h_group_stride;     /* floats.  0: cygym_critic.h_state is [n][h_stride] by source row, each row formed with ITS critic.
+                                  > 0: h_state is [n_slots][n][h_stride], block s at s * h_group_stride formed with critic s, and
+                                  row r reads block slot_of_row[r] (which row plays whom is then known on the device only)          */
+  int32_t  n_slots;            /* 1 .. CG_CRITIC_POP_MAX                                                                             */
+  int32_t  reserved;
+} cygym_critic_pop;
+
+/* cygym_coord_ascent_decode in eval mode for a population of critics of ONE shape, in ONE launch: the decode of source row r -- the
+ * candidates, encodings and quirks, nan_to_num, the stable top K', the f64 softmax pick on the draw addressed CG_SITE_COORD_PICK, the
+ * `best_q` merge, group 0 written like cygym_decode_actions, CG_DECODE_TRUNCATED -- is exactly that of cygym_coord_ascent_decode,
+ * with the weights of critic s = pop->slot_of_row[r].  Where several critics each decide for a few rows (the payoff grid of a
+ * double-oracle population, the opponent drawn per env from an equilibrium) one launch fills the chip that a launch per critic
+ * leaves mostly idle: the kernel runs one workgroup per row.
+ * `c` describes slot 0: w1a_t, w2 (packed), b2 and w3 of slot s follow those of slot s - 1 contiguously, as the actors of a
+ * cygym_actor_mlp population do; b2 is NULL or there for every slot; b3 is not read (pop->b3s); H1, H2, h_stride, top_k, tau,
+ * pick_out and q_out are common to the population (top_k / tau: the oracle's coord_K / coord_tau).
+ * A row whose slot is negative or >= n_slots writes NOTHING: not its action row, not pick_out, not q_out (like a negative entry
+ * of layout->rows).
+ * CYGYM_EUNSUPPORTED: n_slots outside 1 .. CG_CRITIC_POP_MAX.  CYGYM_EINVAL: NULL slot_of_row or b3s; noise_std != 0 or a set
+ * vec_out (training mode belongs to one critic: cygym_coord_ascent_decode); h_group_stride < 0, or > 0 and smaller than one
+ * block, (n - 1) h_stride + H1.  Every other check, limit and message convention is that of cygym_coord_ascent_decode.  Nothing
+ * is written on a refusal. */
+int cygym_coord_ascent_decode_pop(cygym_handle* h, const cygym_critic* c, const cygym_critic_pop* pop, const cygym_action_vectors* layout,
+                                  const cygym_actions* dst, void* stream);
+
 /* The search of cygym_dns_decode: its parameters, the per-env gate and the optional trace.  DEVICE pointers. */
 #define CG_DNS_MAX_ITERS 16
 typedef struct cygym_dns {

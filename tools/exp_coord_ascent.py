@@ -4,7 +4,11 @@ the 155 TF the fp32 matrix instructions reach (layer 2 alone: 2 * M * T * E * H1
 and, at a size the torch path can hold (256 envs, chunked), the same decode with torch ops in float32 on the device.
 --noise-std S: the training-mode launch (noise on the scores, do_agent.py:2177-2178) instead of the eval-mode one; --vec-out: with
 the encoded action written; --collect K: decisions per second of ddpg_rollout.collect(decoder=...) over K decisions of the
-defender against a fixed attacker sequence; --no-torch skips the torch path.  One JSON line per measurement."""
+defender against a fixed attacker sequence; --no-torch skips the torch path.  One JSON line per measurement.
+--pop: the population leg alone -- one defender turn of an S x S grid with N_MC = 5 (S = 2, 4, 8: every strategy decides for 5 S
+rows) as S CoordAscentPolicy.write calls and as the one launch of CoordAscentPolicyGroup, and one MixturePolicy turn at --envs envs
+with four critics, members written one by one (tiled=False) and through the population launch.  On a tree without the group the
+separate calls are timed alone: that is the baseline."""
 import argparse
 import json
 import os
@@ -27,6 +31,7 @@ ap.add_argument("--vec-out", action="store_true")
 ap.add_argument("--collect", type=int, default=0)
 ap.add_argument("--no-torch", action="store_true")
 ap.add_argument("--label", default="")
+ap.add_argument("--pop", action="store_true")
 args = ap.parse_args()
 
 M, T, E, A, H = 256, 14, 6, 3, 128
@@ -53,6 +58,34 @@ def timed(fn, reps, warmup):
         ms.append(e0.elapsed_time(e1))
     return sorted(ms)
 
+
+if args.pop:
+    from cygym_amd import policies as P
+    Group = getattr(P, "CoordAscentPolicyGroup", None)
+    N_MC = 5
+
+    def report(what, ms, **kw):
+        print(json.dumps({"what": what, "label": args.label, "grouped_path": Group is not None, "ms": round(ms[len(ms) // 2], 3),
+                          "ms_min_max": [round(ms[0], 3), round(ms[-1], 3)], **kw}), flush=True)
+    pols = [CoordAscentPolicy(reference_critic(6 * M, T + M + E + A, seed=1 + s, device=dev, hidden=(H, H)), T, E, A, top_k=5) for s in range(8)]
+    for S_ in (2, 4, 8):
+        per = S_ * N_MC                                   # rows of one defender strategy: |A| x N_MC
+        n = S_ * per
+        rows = [torch.arange(s * per, (s + 1) * per, dtype=torch.int32, device=dev) for s in range(S_)]
+
+        def separate():
+            for s in range(S_):
+                pols[s].write(env, env.act, rows[s], obs[s * per:(s + 1) * per])
+        report("grid turn, S separate CoordAscentPolicy.write", timed(separate, args.reps, args.warmup), S=S_, rows=n)
+        if Group is not None:
+            grp, r_all, o_all = Group(pols[:S_], counts=[per] * S_), torch.cat(rows), obs[:n]
+            report("grid turn, one CoordAscentPolicyGroup.write", timed(lambda: grp.write(env, env.act, r_all, o_all), args.reps, args.warmup), S=S_, rows=n)
+    for tiled in ((False, True) if Group is not None else (False,)):
+        mix = P.MixturePolicy(pols[:4], [0.25] * 4, "defender", tiled=tiled)
+        report("mixture turn, four critics, " + ("one population launch" if tiled else "members one by one"),
+               timed(lambda: mix.write(env, env.act, None, obs), args.reps, args.warmup), S=4, envs=args.envs)
+    assert env.take_status() & abi.DECODE_TRUNCATED == 0
+    sys.exit(0)
 
 extra = {}
 if args.noise_std > 0.0:
