@@ -165,6 +165,13 @@ class CommActor(C.Structure):
                 ("tok_stride", C.c_int32), ("reserved", C.c_int32)]
 
 
+COMM_POP_MAX = 32
+
+
+class CommActorPop(C.Structure):
+    _fields_ = [("tile_slot", C.c_void_p), ("b_v2s", C.c_void_p), ("tok_group_stride", C.c_int64), ("n_slots", C.c_int32), ("n_tiles", C.c_int32)]
+
+
 GAT_MAX_LAYERS, GAT_MAX_DEVICES = 4, 1024
 
 

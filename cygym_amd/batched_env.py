@@ -1077,6 +1077,84 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_comm_actor_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_actor_decode")
         return types, exp_o, app_o, logp, value
 
+    def _comm_pop_structs(self, rows_tiled, tile_slot, tok_base, pack, role, noop, single_types, greedy, act, logits_out, exp_logits_out,
+                          app_logits_out):
+        """Argument checks and marshalling of comm_actor_decode_pop: (CommActor, CommActorPop, DeviceLogits, Actions, the five result
+        tensors, tensors to keep)."""
+        dst = self.actions_struct(act)
+        src = abi.DeviceLogits()
+        self._group_rule(src, role, noop, single_types)
+        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
+        for name, t in (("rows_tiled", rows_tiled), ("tile_slot", tile_slot)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError(f"{name} must be a contiguous 1-d int32 tensor on {self.device}")
+        T = int(tile_slot.numel())
+        n = 16 * T
+        if int(rows_tiled.numel()) != n:
+            raise ValueError(f"rows_tiled must hold 16 entries per tile: {n} for the {T} tiles of tile_slot (it has {int(rows_tiled.numel())})")
+        b_v2s = pack["b_v2s"]
+        if not ok(b_v2s) or b_v2s.dim() != 1 or not b_v2s.is_contiguous() or int(b_v2s.numel()) < 1:
+            raise ValueError("pack['b_v2s'] must be a contiguous float32 [S] tensor (v_head.2.bias of every net)")
+        S_ = int(b_v2s.numel())
+        if not ok(tok_base) or tok_base.dim() not in (2, 3) or tok_base.stride(-1) != 1:
+            raise ValueError("tok_base must be a [16 T, H] or [S, N, H] float32 tensor on the batch's device with unit inner stride")
+        H = int(tok_base.shape[-1])
+        nb = int(tok_base.shape[-2])
+        if tok_base.dim() == 2 and nb != n:
+            raise ValueError(f"tok_base by source row must hold one row per entry of rows_tiled ({n}), it has {nb}")
+        if tok_base.dim() == 3 and (int(tok_base.shape[0]) != S_ or nb != self.N or
+                                    (nb > 1 and S_ > 1 and tok_base.stride(0) < (nb - 1) * tok_base.stride(1) + H)):
+            raise ValueError(f"tok_base [S, N, H] must hold one block of all {self.N} envs per net ({S_}), block after block")
+        K, E, A = int(pack["K"]), int(pack["E"]), int(pack["A"])
+        sizes = {"tok_dev": self.M * H, "w_type": (K + 15) // 16 * 16 * H, "b_type": K, "w_ctx": (E + A + H + 15) // 16 * 16 * H,
+                 "b_ctx": E + A + H, "w_v2": H}
+        if H % 16:
+            sizes["w_type"] = sizes["w_ctx"] = -1   # (the library refuses such an H anyway)
+        net, pop = abi.CommActor(), abi.CommActorPop()
+        for name, want in sizes.items():
+            t = pack[name]
+            if not ok(t) or not t.is_contiguous() or (want >= 0 and int(t.numel()) != S_ * want):
+                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {S_} x {want} values on {self.device} "
+                                 "(CommActorPolicyGroup stacks the members' packs)")
+            setattr(net, name, t.data_ptr())
+        row_stride = int(tok_base.stride(-2)) if nb > 1 else H
+        net.tok_base, net.tok_stride, net.H = tok_base.data_ptr(), row_stride, H
+        pop.tile_slot, pop.b_v2s, pop.n_slots, pop.n_tiles = tile_slot.data_ptr(), b_v2s.data_ptr(), S_, T
+        pop.tok_group_stride = (int(tok_base.stride(0)) if S_ > 1 else nb * row_stride) if tok_base.dim() == 3 else 0
+        outs = (torch.empty((n, self.M), dtype=torch.uint8, device=self.device), torch.empty((n,), dtype=torch.int32, device=self.device),
+                torch.empty((n,), dtype=torch.int32, device=self.device), torch.empty((n,), dtype=torch.float32, device=self.device),
+                torch.empty((n,), dtype=torch.float32, device=self.device))
+        src.types_out, src.exp_out, src.app_out, src.logp_out, net.value_out = (t.data_ptr() for t in outs)
+        src.n_types, src.n_exp, src.n_app, src.greedy = K, E, A, int(bool(greedy))
+        for name, t, shape in (("logits_out", logits_out, (n, self.M, K)), ("exp_logits_out", exp_logits_out, (n, E)), ("app_logits_out", app_logits_out, (n, A))):
+            if t is not None:
+                if not ok(t) or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {self.device}")
+                setattr(net, name, t.data_ptr())
+        src.n, src.rows = n, rows_tiled.data_ptr()
+        return net, pop, src, dst, outs, [rows_tiled, tile_slot, tok_base, b_v2s]
+
+    def comm_actor_decode_pop(self, rows_tiled: torch.Tensor, tile_slot: torch.Tensor, tok_base: torch.Tensor, pack, role: str = "defender",
+                              noop: int | None = None, single_types=(11, 12), greedy: bool = False, act=None, logits_out=None,
+                              exp_logits_out=None, app_logits_out=None):
+        """comm_actor_decode for a POPULATION of S same-shaped nets without attention layers (1 <= S <= 32), each deciding for some of
+        the rows: ONE launch (cygym_comm_actor_decode_pop) -- source row r is decoded exactly as comm_actor_decode would with the net
+        of its tile.
+          rows_tiled   [16 T] int32 on the device: the env of every source row, 16 per tile, -1 = no row (the layout mixture_draw
+                       writes and policies.mixture_rows_np restates)
+          tile_slot    [T] int32 on the device: the net of tile t; a tile whose entry is negative or >= S is left alone
+          tok_base     [16 T, H]: source row r formed with ITS net;  or [S, N, H]: block s formed with net s for every env, the row of
+                       env e in tile t reads block tile_slot[t] at row e (the caller does not know on the host who plays whom)
+          pack         the dict of comm_actor_decode with every tensor holding the S nets one after the other, and b_v2s [S] float32
+                       in place of b_v2 -- policies.CommActorPolicyGroup stacks them
+        Returns what comm_actor_decode returns, by SOURCE row (16 T of them); the rows of skipped tiles and of -1 are not written.
+        Every tensor is checked here: the kernel indexes them by raw pointer."""
+        net, pop, src, dst, outs, keep = self._comm_pop_structs(rows_tiled, tile_slot, tok_base, pack, role, noop, single_types, greedy, act,   # noqa: F841
+                                                                logits_out, exp_logits_out, app_logits_out)
+        _lib.check(self.lib.cygym_comm_actor_decode_pop(self._h, C.byref(net), C.byref(pop), C.byref(src), C.byref(dst), self._stream()),
+                   self._h, "cygym_comm_actor_decode_pop")
+        return outs
+
     def comm_gat_workspace(self, H: int):
         """The workspace cygym_comm_gat_decode needs on this batch for hidden width H (None when every row fits in LDS), allocated
         once per width and kept: call it before a loop that is captured into a graph."""

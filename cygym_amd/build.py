@@ -53,6 +53,7 @@ INST_COMMITTEE = os.path.join(HERE, "csrc", "cg_inst_committee.hip")
 INST_DNS = os.path.join(HERE, "csrc", "cg_inst_dns.hip")
 INST_MIXTURE = os.path.join(HERE, "csrc", "cg_inst_mixture.hip")
 INST_COMM =os.path.join(HERE, "csrc", "cg_inst_comm.hip")
+INST_COMM_POP = os.path.join(HERE, "csrc", "cg_inst_comm_pop.hip")
 INST_COMM_GAT = os.path.join(HERE, "csrc", "cg_inst_comm_gat.hip")
 INST_GAT_EVAL = os.path.join(HERE, "csrc", "cg_inst_gat_eval.hip")
 INST_HIER = os.path.join(HERE, "csrc", "cg_inst_hier.hip")
@@ -93,6 +94,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         units.append(("inst_dns", base + ["-c", INST_DNS, "-o", os.path.join(tmp, "inst_dns.o")]))   # the dynamic neighbourhood search
         units.append(("inst_mixture", base + ["-c", INST_MIXTURE, "-o", os.path.join(tmp, "inst_mixture.o")]))   # the mixture draw and the tiled whole-actor decode
         units.append(("inst_comm", base + ["-c", INST_COMM, "-o", os.path.join(tmp, "inst_comm.o")]))   # the per-device actor-critic decode
+        units.append(("inst_comm_pop", base + ["-c", INST_COMM_POP, "-o", os.path.join(tmp, "inst_comm_pop.o")]))   # ... for a population of nets
         units.append(("inst_comm_gat", base + ["-c", INST_COMM_GAT, "-o", os.path.join(tmp, "inst_comm_gat.o")]))   # ... with its attention layers
         units.append(("inst_gat_eval", base + ["-c", INST_GAT_EVAL, "-o", os.path.join(tmp, "inst_gat_eval.o")]))   # ... and their evaluate / backward (the PPO update)
         units.append(("inst_hier", base + ["-c", INST_HIER, "-o", os.path.join(tmp, "inst_hier.o")]))   # the hierarchical (HAGS) decode

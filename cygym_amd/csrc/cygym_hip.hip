@@ -87,6 +87,9 @@ extern template __global__ void dns_kernel<true>(cygym_critic, cygym_dns, cygym_
 namespace cygym_k {
 extern template __global__ void comm_actor_kernel<false>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 extern template __global__ void comm_actor_kernel<true>(cygym_comm_actor, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+// ... and for a population of nets (cg_inst_comm_pop.hip)
+extern template __global__ void comm_pop_kernel<false>(cygym_comm_actor, cygym_comm_actor_pop, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+extern template __global__ void comm_pop_kernel<true>(cygym_comm_actor, cygym_comm_actor_pop, cygym_device_logits, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 }  // namespace cygym_k
 
 // ... and the same network with its attention layers (cg_inst_comm_gat.hip)
@@ -326,6 +329,7 @@ int cygym_sizeof(int32_t which) {
     case 40: return (int)sizeof(cygym_ippo_head_desc);
     case 42: return (int)sizeof(cygym_committee);   // (index 41 stays unassigned: earlier bindings probe it for -1)
     case 44: return (int)sizeof(cygym_critic_pop);   // (index 43 stays unassigned)
+    case 46: return (int)sizeof(cygym_comm_actor_pop);   // (index 45 stays unassigned)
     default: return -1;
   }
 }
@@ -1083,35 +1087,64 @@ int cygym_dns_decode(cygym_handle* h, const cygym_critic* c, const cygym_dns* q,
   return launch_decode(h, k, dim3(src->n), dim3(DN_THREADS), lds, stream, {c, q, src, dst});   // one workgroup per row
 }
 
-int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst,
-                            void* stream) {
-  const char* const who = "cygym_comm_actor_decode";
-  const char* const bad_layout = "cygym_comm_actor_decode: bad layout (types, exploit logits >= 1, tok_stride >= H, role 1 or 2, 16-byte aligned tok_dev / w_type / w_ctx)%s";
-  if (h && !h->bound) return fail(h, CYGYM_ENOTBOUND, "cygym_comm_actor_decode: handle not bound (the visibility mask is read off the flag plane, the draws at the envs' rng ticks)%s", "");
+// What cygym_comm_actor_decode and cygym_comm_actor_decode_pop check alike, in the order a caller sees (own_ptrs: the pointers of the
+// function's own descriptors are there), and the LDS a workgroup of 16 rows needs.
+static int check_comm_actor(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst, const char* who,
+                            const char* bad_layout, bool own_ptrs, size_t* lds) {
+  if (h && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (the visibility mask is read off the flag plane, the draws at the envs' rng ticks)", who);
   // the checks the decodes share, on this call's layout: K types, the handle's devices, E exploit and A app logits
   cygym_action_vectors lay;
   memset(&lay, 0, sizeof(lay));
   if (h && src) { lay.n_types = src->n_types; lay.n_devices = h->t.M; lay.n_exploits = src->n_exp; lay.n_apps = src->n_app; }
   const bool own = net && src && net->tok_base && net->tok_dev && net->w_type && net->b_type && net->w_ctx && net->b_ctx && net->w_v2 &&
-                   net->value_out && src->types_out;
+                   net->value_out && src->types_out && own_ptrs;
   if (const int rc = check_vectors(h, src ? &lay : nullptr, dst, who, own, 1, bad_layout)) return rc;
   if (const int rc = check_dst(h, dst, who, true)) return rc;
   if (net->H < 1 || net->tok_stride < net->H || (src->role != 1 && src->role != 2) ||
       (((uintptr_t)net->tok_dev | (uintptr_t)net->w_type | (uintptr_t)net->w_ctx) & 15))
     return fail(h, CYGYM_EINVAL, bad_layout, "");
   if (net->H < 16 || net->H > CM_MAX_H || (net->H & 15) || src->n_types > CM_MAX_HEAD || src->n_exp > CM_MAX_HEAD || src->n_app > CM_MAX_HEAD)
-    return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_actor_decode: H must be a multiple of 16 in 16 .. 128, at most 32 action types, exploit and app logits%s", "");
+    return fail(h, CYGYM_EUNSUPPORTED, "%s: H must be a multiple of 16 in 16 .. 128, at most 32 action types, exploit and app logits", who);
   if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
+  *lds = (size_t)cm_plan(net->H, src->n_types, src->n_exp, src->n_app, h->t.M).total * sizeof(float);
+  return CYGYM_OK;
+}
+
+int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst,
+                            void* stream) {
+  const char* const who = "cygym_comm_actor_decode";
+  const char* const bad_layout = "cygym_comm_actor_decode: bad layout (types, exploit logits >= 1, tok_stride >= H, role 1 or 2, 16-byte aligned tok_dev / w_type / w_ctx)%s";
+  size_t lds = 0;
+  if (const int rc = check_comm_actor(h, net, src, dst, who, bad_layout, true, &lds)) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  const CmPlan pl = cm_plan(net->H, src->n_types, src->n_exp, src->n_app, h->t.M);
-  const size_t lds = (size_t)pl.total * sizeof(float);
-  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "cygym_comm_actor_decode: the per-row buffers do not fit in LDS%s", "");
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the per-row buffers do not fit in LDS", who);
   const void* k = net->logits_out ? (const void*)comm_actor_kernel<true> : (const void*)comm_actor_kernel<false>;
   if (const int rc = raise_lds_once(h, k)) return rc;
   const uint8_t* live = h->b.live;
   int M = h->t.M;
   return launch_decode(h, k, dim3((src->n + CM_WAVES - 1) / CM_WAVES), dim3(CM_THREADS), lds, stream, {net, src, dst}, {&live, &M});   // 16 rows per workgroup
+}
+
+int cygym_comm_actor_decode_pop(cygym_handle* h, const cygym_comm_actor* net, const cygym_comm_actor_pop* pop, const cygym_device_logits* src,
+                                const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_comm_actor_decode_pop";
+  const char* const bad_layout = "cygym_comm_actor_decode_pop: bad layout (types, exploit logits >= 1, tok_stride >= H, role 1 or 2, 16-byte aligned tok_dev / w_type / w_ctx)%s";
+  size_t lds = 0;
+  if (const int rc = check_comm_actor(h, net, src, dst, who, bad_layout, pop && pop->tile_slot && pop->b_v2s && src && src->rows, &lds)) return rc;
+  if (pop->n_slots < 1 || pop->n_slots > CG_COMM_POP_MAX) return fail(h, CYGYM_EUNSUPPORTED, "%s: 1 to CG_COMM_POP_MAX nets", who);
+  if (pop->n_tiles < 0 || (int64_t)src->n != 16 * (int64_t)pop->n_tiles)
+    return fail(h, CYGYM_EINVAL, "%s: the row list holds 16 rows per tile (layout->n = 16 n_tiles)", who);
+  if (pop->tok_group_stride < 0 || (pop->tok_group_stride > 0 && pop->tok_group_stride < (int64_t)(h->n_envs - 1) * net->tok_stride + net->H))
+    return fail(h, CYGYM_EINVAL, "%s: tok_group_stride is 0 (tok_base by source row) or at least one block, (n_envs - 1) tok_stride + H", who);
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the per-row buffers do not fit in LDS", who);
+  const void* k = net->logits_out ? (const void*)comm_pop_kernel<true> : (const void*)comm_pop_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const uint8_t* live = h->b.live;
+  int M = h->t.M;
+  return launch_decode(h, k, dim3(pop->n_tiles), dim3(CM_THREADS), lds, stream, {net, pop, src, dst}, {&live, &M});   // a tile of 16 rows per workgroup
 }
 
 // Workgroups of cygym_comm_gat_decode on this handle's device: one or two per CU (by the LDS a workgroup takes), never more than rows.

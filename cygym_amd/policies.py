@@ -1596,6 +1596,129 @@ class CommActorPolicy:
                                   "carry them (it runs through write(), on a batch with cygym_comm_actor_decode)")
 
 
+class CommActorPolicyGroup:
+    """A population of CommActorPolicy strategies of ONE shape without attention layers (key) decided together: tok_base of all of
+    them is two batched GEMMs and the decode + grouping of all of them is ONE launch (cygym_comm_actor_decode_pop), the net of a tile
+    of 16 rows taken from a slot table.  The decode gives a workgroup 16 rows, so a launch per strategy over that strategy's few rows
+    leaves most of the chip idle; the |D| x |A| grid of a Double-Oracle population with --BR_type ippo / mappo and the opponent drawn
+    per env from an equilibrium (MixturePolicy) hold several such nets, each deciding for a few envs.
+    counts: the rows of every member when the rows arrive ordered member after member (any counts, equal or not, multiples of 16 or
+    not).  Every member's segment is padded to the same number of tiles (tile_plan), so that the padded observations are one
+    [S, 16 Tm, W] operand; the tiles past a member's rows carry slot -1 and cost nothing.  in_tile_order: the caller's rows and
+    observations are ALREADY in that padded order (rollout_grid._group_comm builds its gather that way, once, at plan time): write()
+    then gathers nothing.  Without counts write() takes the caller's tiles (shared_obs)."""
+
+    tick_free = True
+    writes_groups = True
+    MIN_MEMBERS = 2      # the smallest population that is grouped (simulate_grid, MixturePolicy): PERFLOG.md has the measurement
+
+    def __init__(self, policies, counts=None, in_tile_order: bool = False):
+        self.policies = list(policies)
+        if not 1 <= len(self.policies) <= 32:
+            raise ValueError("1 to 32 nets")
+        p0 = self.policies[0]
+        if any(not isinstance(p, CommActorPolicy) or p.net.gat_layers for p in self.policies):
+            raise ValueError("the members are CommActorPolicy without attention layers")
+        self.role, self.greedy, self.noop, self.n_types = p0.role, p0.greedy, p0.noop, p0.n_types
+        self.action_types = list(p0.action_types)
+        self.counts = None if counts is None else [int(c) for c in counts]
+        if self.counts is not None and len(self.counts) != len(self.policies):
+            raise ValueError("counts: one row count per member")
+        self.in_tile_order = bool(in_tile_order)
+        self._pk = self._pk_ver = self._tiles = None
+
+    @staticmethod
+    def key(p, M):
+        """What must agree across the members of a population -- role, state width, H, K, D, E, A, greedy, noop -- or None when `p`
+        cannot be one: not a CommActorPolicy, or a net with attention layers (those keep their own launch)."""
+        if not isinstance(p, CommActorPolicy) or p.net.gat_layers > 0:
+            return None
+        n = p.net
+        return (p.role, n.state_dim, n.hidden, n.n_types, n.D, n.E, n.A, p.greedy, p.noop)
+
+    @staticmethod
+    def tile_plan(counts):
+        """The padded tile order of rows that come member after member, as numpy: (pos [S 16 Tm] int64 -- the position in the
+        member-after-member order of every padded row, 0 on the padding --, valid [S 16 Tm] bool, tile_slot [S Tm] int32) with Tm =
+        the tiles of the longest member (at least 1).  Member s owns padded rows s 16 Tm ..: its rows in order, then padding; its
+        tiles without a row carry slot -1.  mixture_rows_np's layout with every slot's segment at a fixed place."""
+        import numpy as np
+        counts = np.asarray(counts, np.int64)
+        S_, Tm = counts.size, max(1, int((counts.max() + 15) // 16))
+        j = np.arange(16 * Tm)[None, :]
+        valid = j < counts[:, None]
+        start = np.concatenate([[0], np.cumsum(counts)[:-1]])
+        pos = np.where(valid, start[:, None] + j, 0).astype(np.int64).reshape(-1)
+        tile_slot = np.where(np.arange(Tm)[None, :] * 16 < counts[:, None], np.arange(S_)[:, None], -1).astype(np.int32).reshape(-1)
+        return pos, valid.reshape(-1), tile_slot
+
+    def _stacked(self, batch=None):
+        """The members' packs (CommActorCritic.packed) slot after slot, as the dict comm_actor_decode_pop reads plus the batched
+        operands of tok_base: w_sp_t [S, W, H], b_sp [S, 1, H], w_m_t [S, H, H], b_m [S, 1, H].  Redone when a member's parameter
+        changes (the members' own packed() versions)."""
+        packs = [p.net.packed(batch) for p in self.policies]
+        ver = tuple(p.net._pk_ver for p in self.policies)
+        if self._pk_ver != ver:
+            st = lambda k: torch.stack([pk[k] for pk in packs]).contiguous()  # noqa: E731
+            pk0 = packs[0]
+            self._pk = {"K": pk0["K"], "E": pk0["E"], "A": pk0["A"], "S": len(packs),
+                        "w_sp_t": st("w_sp_t"), "b_sp": st("b_sp")[:, None, :].contiguous(), "w_m_t": st("w_m_t"), "b_m": st("b_m")[:, None, :].contiguous(),
+                        "tok_dev": st("tok_dev"), "w_type": st("w_type"), "b_type": st("b_type"), "w_ctx": st("w_ctx"), "b_ctx": st("b_ctx"),
+                        "w_v2": st("w_v2"),
+                        "b_v2s": torch.cat([p.net.v_head[2].bias.detach().reshape(1) for p in self.policies]).contiguous()}      # (no host read)
+            self._pk_ver = ver
+        return self._pk
+
+    def tok_base(self, obs_s, pack):
+        """[S, n, H]: a = merge.bias + merge.weight[:, :H] relu(state_proj(state)) of every (net, row) of obs_s [S, n, W] (or an
+        expanded [n, W]): two baddbmm."""
+        return torch.baddbmm(pack["b_m"], torch.relu_(torch.baddbmm(pack["b_sp"], obs_s, pack["w_sp_t"])), pack["w_m_t"])
+
+    def _tile_tensors(self, device):
+        if self._tiles is None or self._tiles[0].device != device:
+            pos, valid, tile_slot = self.tile_plan(self.counts)
+            self._tiles = (torch.from_numpy(pos).to(device), torch.from_numpy(valid).to(device), torch.from_numpy(tile_slot).to(device),
+                           bool(valid.all()))
+        return self._tiles
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, tile_slot=None, shared_obs=False, logits_out=None):
+        """ONE decode launch for all members; returns what comm_actor_decode_pop returns (by source row, in tile order).
+        Default: `rows` / `obs` [n, W] hold the members' rows member after member (counts); they are gathered once into the padded
+        tile order (not at all when in_tile_order, or when every count is the same multiple of 16) and tok_base is formed per source
+        row.  shared_obs: `rows` [16 T] and tile_slot [T] are the caller's tiles, made on the device (the draw of a mixture), obs
+        [N, W] holds every env once: tok_base is [S, N, H] and the kernel reads the block of the tile's slot."""
+        pack = self._stacked(batch)
+        S_, W, H = (int(x) for x in pack["w_sp_t"].shape)
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != W:
+            raise ValueError(f"obs must be a float32 [n, {W}] role view")
+        if batch.M != self.policies[0].net.D:
+            raise ValueError(f"the nets were built for {self.policies[0].net.D} devices, the batch has {batch.M}")
+        if shared_obs:
+            if tile_slot is None or rows is None:
+                raise ValueError("shared_obs: the caller says which tile plays whom (rows = rows_tiled, tile_slot)")
+            tok = self.tok_base(obs[None].expand(S_, int(obs.shape[0]), W), pack)
+        else:
+            if self.counts is None:
+                raise ValueError("rows ordered member after member need counts")
+            pos, valid, tile_slot, dense = self._tile_tensors(obs.device)
+            n_pad = int(pos.numel())
+            if self.in_tile_order or (dense and int(obs.shape[0]) == n_pad):
+                if int(obs.shape[0]) != n_pad or rows is None or int(rows.numel()) != n_pad:
+                    raise ValueError(f"rows in tile order: {n_pad} padded rows (tile_plan)")
+            else:
+                if sum(self.counts) != int(obs.shape[0]) or rows is None or int(rows.numel()) != int(obs.shape[0]):
+                    raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
+                obs = obs.index_select(0, pos)
+                rows = torch.where(valid, rows.index_select(0, pos), torch.full_like(rows[:1], -1))
+            tok = self.tok_base(obs.reshape(S_, n_pad // S_, W), pack).reshape(n_pad, H)
+        return batch.comm_actor_decode_pop(rows, tile_slot, tok, pack, self.role, noop=self.noop, greedy=self.greedy, act=act, logits_out=logits_out)
+
+    def __call__(self, obs, t, M, L):
+        raise NotImplementedError("a CommActorPolicyGroup answers with groups of devices per action type: it runs through write(), on a "
+                                  "batch with cygym_comm_actor_decode_pop")
+
+
 class _ScoreNet(nn.Module):
     def __init__(self, state_dim, M, hidden):
         super().__init__()
@@ -2829,7 +2952,11 @@ class MixturePolicy:
       3. among the other members, the CoordAscentPolicy of ONE shape in eval mode (CoordAscentPolicyGroup.key) that can play, two or
          more: one index op turns the drawn members into critic slots (-1 for everyone else's envs), one baddbmm forms h_state for
          every (critic, env), and ONE cygym_coord_ascent_decode_pop decodes all envs in order (tiled = False: off);
-      4. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
+      4. among the other members, the CommActorPolicy of ONE shape without attention layers (CommActorPolicyGroup.key) that can play,
+         two or more: the draw's rows_tiled / tile_slot carry THEIR slots, two baddbmm on `obs` in place form tok_base for every
+         (net, env), and ONE cygym_comm_actor_decode_pop decodes the tiles (tiled = False: off).  cygym_mixture_draw has one
+         member_slot table: when step 2 formed an ActorPolicyGroup, that group keeps the tiles and the comm members play one by one;
+      5. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
          rollout_grid.SequencePolicy + write_actions with the tick the loop set (set_tick: the loop's tick counter; a callable without
          uses_global_tick gets t // 2, as the loops call it).  A member of probability 0 never plays and is not launched.
     act["n_groups"] is the caller's to clear before the call (Turns.opponent, ddpg_rollout.collect do); a member that writes groups sets
@@ -2914,20 +3041,42 @@ class MixturePolicy:
             slots[s] = pos
         return CoordAscentPolicyGroup([self.members[s] for s in best]), slots
 
+    def _comm_group(self, batch, taken: bool):
+        """(CommActorPolicyGroup, slot of every member or -1) of the largest set of same-key CommActorPolicy members (no attention
+        layers) that can play, or (None, all -1).  taken: the draw's one member_slot table already serves an ActorPolicyGroup."""
+        slots = [-1] * len(self.members)
+        if taken or not (self.tiled and hasattr(batch, "mixture_draw") and hasattr(batch, "comm_actor_decode_pop")):
+            return None, slots
+        by_key = {}
+        for s, m in enumerate(self.members):
+            k = CommActorPolicyGroup.key(m, batch.M)
+            if k is not None and self.probs[s] > 0.0:
+                by_key.setdefault(k, []).append(s)
+        best = max(by_key.values(), key=len, default=[])
+        if len(best) < max(2, CommActorPolicyGroup.MIN_MEMBERS):
+            return None, slots
+        for pos, s in enumerate(best):
+            slots[s] = pos
+        return CommActorPolicyGroup([self.members[s] for s in best]), slots
+
     def _state(self, batch):
         st = self._st
         if st is None or st["batch"] is not batch:
             N, S_, dev = batch.N, len(self.members), batch.device
             grp, slots = self._group(batch)
             cgrp, cslots = self._critic_group(batch)
+            mgrp, mslots = self._comm_group(batch, grp is not None)
+            if mgrp is not None:      # (the draw's tiles go to the comm nets: `group` stays None, `slots` is the table the draw reads)
+                slots = mslots
             T = (N + 15) // 16 + S_
             z = lambda shape, dt, v=0: torch.full(shape, v, dtype=dt, device=dev)  # noqa: E731
             st = self._st = dict(batch=batch, group=grp, slots=slots, cdf=torch.from_numpy(self.cdf).to(dev),
                                  member_baseline=torch.tensor(self.baseline, dtype=torch.int8, device=dev),
                                  member_slot=torch.tensor(slots, dtype=torch.int8, device=dev), baseline_state=z((N,), torch.int8, -1),
                                  index=z((N,), torch.uint8), rows_masked=z((S_, N), torch.int32, -1), rows_ok=None,
-                                 rows_tiled=z((16 * T,), torch.int32, -1) if grp is not None else None,
-                                 tile_slot=z((T,), torch.int32, -1) if grp is not None else None,
+                                 rows_tiled=z((16 * T,), torch.int32, -1) if (grp is not None or mgrp is not None) else None,
+                                 tile_slot=z((T,), torch.int32, -1) if (grp is not None or mgrp is not None) else None,
+                                 comm=mgrp, comm_slots=mslots,
                                  critics=cgrp, critic_slots=cslots, critic_slot_of=torch.tensor(cslots, dtype=torch.int32, device=dev),
                                  slot_of_row=z((N,), torch.int32, -1) if cgrp is not None else None)
         return st
@@ -2967,8 +3116,13 @@ class MixturePolicy:
             # the critic slot of every env's member (-1: another member's env), then ONE decode launch over all envs in order
             torch.index_select(st["critic_slot_of"], 0, st["index"].to(torch.int32), out=st["slot_of_row"])
             cgrp.write(batch, act, None, obs[:N], slot_of_row=st["slot_of_row"], shared_obs=True)
+        mgrp, mslots = st["comm"], st["comm_slots"]
+        if mgrp is not None and in_place:
+            # the draw's tiles carry the comm nets' slots: tok_base for every (net, env), then ONE decode launch over the tiles
+            mgrp.write(batch, act, st["rows_tiled"], obs[:N], tile_slot=st["tile_slot"], shared_obs=True)
         for s, m in enumerate(self.members):
-            if (grp is not None and in_place and slots[s] >= 0) or (cgrp is not None and in_place and cslots[s] >= 0) or self.probs[s] == 0.0:
+            if (grp is not None and in_place and slots[s] >= 0) or (cgrp is not None and in_place and cslots[s] >= 0) or \
+                    (mgrp is not None and in_place and mslots[s] >= 0) or self.probs[s] == 0.0:
                 continue
             r = st["rows_masked"][s]
             if hasattr(m, "write"):

@@ -193,7 +193,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train, 31 cygym_dns, 33 cygym_mixture; -1 for anything else, 13, 15, 18, 22, 24, 26, 30 and 32 included: those indices stay unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train, 31 cygym_dns, 33 cygym_mixture, 46 cygym_comm_actor_pop; -1 for anything else, 13, 15, 18, 22, 24, 26, 30 and 32 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -751,11 +751,45 @@ typedef struct cygym_comm_actor {
  * Limits (CYGYM_EUNSUPPORTED beyond): H a multiple of 16 in 16 .. 128; K, E, A <= 32; any M of the handle whose per-row buffers fit in
  * LDS (every M <= 2048 does).  CYGYM_EINVAL (the argument check the decodes share): NULL mandatory pointers, K < 1, E < 1, A < 0,
  * tok_stride < H, a role other than 1 / 2, a packed matrix or tok_dev off 16-byte alignment.  CYGYM_ENOTBOUND without cygym_bind.
- * Out of scope: populations of nets in one launch, and building the observation on chip (tok_base comes from the caller).  The
- * attention layers of USE_GAT = True are cygym_comm_gat_decode below.  The PPO update evaluates stored decisions with
- * cygym_comm_actor_evaluate below. */
+ * Out of scope: building the observation on chip (tok_base comes from the caller).  A population of nets in one launch is
+ * cygym_comm_actor_decode_pop below, the attention layers of USE_GAT = True are cygym_comm_gat_decode.  The PPO update evaluates
+ * stored decisions with cygym_comm_actor_evaluate below. */
 int cygym_comm_actor_decode(cygym_handle* h, const cygym_comm_actor* net, const cygym_device_logits* src, const cygym_actions* dst,
                             void* stream);
+
+/* A population of same-shaped nets for cygym_comm_actor_decode_pop.  DEVICE pointers. */
+#define CG_COMM_POP_MAX 32   /* = CG_MIXTURE_MAX_MEMBERS */
+typedef struct cygym_comm_actor_pop {
+  const int32_t* tile_slot;    /* [n_tiles] the net of tile t (source rows 16 t .. 16 t + 15): 0 .. n_slots - 1; any other value: the
+                                  tile is left alone                                                                                  */
+  const float*   b_v2s;        /* [n_slots] v_head.2.bias of every slot (cygym_comm_actor.b_v2 is not read)                            */
+  int64_t  tok_group_stride;   /* floats.  0: cygym_comm_actor.tok_base is [n][tok_stride] by source row, each row formed with ITS net.
+                                  > 0: tok_base is [n_slots][n_envs][tok_stride], block s at s * tok_group_stride formed with net s,
+                                  and the row of env e in tile t reads block tile_slot[t] at row e (who plays whom is then known on
+                                  the device only)                                                                                    */
+  int32_t  n_slots;            /* 1 .. CG_COMM_POP_MAX                                                                                 */
+  int32_t  n_tiles;            /* layout->n = 16 * n_tiles                                                                             */
+} cygym_comm_actor_pop;
+
+/* cygym_comm_actor_decode for a population of nets of ONE shape (H, K, E, A, role, noop, single_mask, greedy in common; no attention
+ * layers), in ONE launch: source row r -- ctx, the heads on the matrix cores, nan_to_num, the addressed Philox draws, the order of the
+ * logp sum, the grouping, CG_DECODE_TRUNCATED -- is decoded exactly as cygym_comm_actor_decode decodes it, with the weights of net
+ * s = pop->tile_slot[r / 16].  The rows of a workgroup are independent of each other, so a row's result is bit-identical whatever
+ * else shares its tile.  Where several nets each decide for a few rows (the payoff grid of a double-oracle population with
+ * --BR_type ippo / mappo, the opponent drawn per env from an equilibrium) one launch fills the chip that a launch per net of a few
+ * workgroups leaves mostly idle.
+ * `net` describes slot 0: tok_dev [M][H], w_type, b_type, w_ctx, b_ctx and w_v2 of slot s follow those of slot s - 1 contiguously,
+ * in the packed forms of that struct -- every per-slot matrix is a multiple of 16 bytes, so the alignment of slot 0 carries
+ * over; b_v2 is not read (pop->b_v2s).  layout->rows is MANDATORY: a tiled row list [16 n_tiles], 16 rows per tile, -1 = no row
+ * (skipped as in cygym_comm_actor_decode) -- the layout cygym_mixture_draw writes as rows_tiled / tile_slot.  The outputs by source
+ * row (value_out, types_out, exp_out, app_out, logp_out, the optional logits) stay indexed by source row: [16 n_tiles] of them.
+ * A tile whose slot is negative or >= n_slots writes NOTHING: its workgroup returns before its first barrier.
+ * CYGYM_EUNSUPPORTED: n_slots outside 1 .. CG_COMM_POP_MAX.  CYGYM_EINVAL: NULL tile_slot, b_v2s or layout->rows; layout->n !=
+ * 16 n_tiles; tok_group_stride < 0, or > 0 and smaller than one block, (n_envs - 1) tok_stride + H.  Every other check, limit and
+ * message convention is that of cygym_comm_actor_decode.  Nothing is launched and nothing is written on a refusal.
+ * Out of scope: nets with attention layers in a population (they keep cygym_comm_gat_decode), building the observation on chip. */
+int cygym_comm_actor_decode_pop(cygym_handle* h, const cygym_comm_actor* net, const cygym_comm_actor_pop* pop,
+                                const cygym_device_logits* layout, const cygym_actions* dst, void* stream);
 
 /* The attention layers of that network (USE_GAT = True: GATLayer, IPPO.py:114-130, over masked_adjacency, :98-109), fp32, DEVICE
  * pointers.  q / k / v / proj weights [H][H] packed like w_type above (pack_linear), 16-byte aligned; q, k, v have no bias. */

@@ -5,7 +5,11 @@
   (b) two addmm + cygym_comm_actor_decode (the fused launch; also timed alone, and with logits_out)
   (c) ippo_rollout.collect for --collect defender decisions both ways, in env-decisions per second
   (d) torch.cuda.max_memory_allocated of both
-One JSON line per measurement: median and min..max over --reps repetitions."""
+One JSON line per measurement: median and min..max over --reps repetitions.
+--pop: the population leg alone (at least 20 repetitions) -- one defender turn of a grid whose --envs envs are shared evenly by S = 2,
+4, 8 same-key strategies, as S CommActorPolicy.write calls (two addmm + cygym_comm_actor_decode each: the ungrouped path) and as the
+one launch of CommActorPolicyGroup (two baddbmm + cygym_comm_actor_decode_pop); and one MixturePolicy turn at --envs envs with four
+same-key members, written one by one (tiled=False) and through the population launch."""
 import argparse
 import json
 import os
@@ -28,6 +32,7 @@ ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--collect", type=int, default=20)
 ap.add_argument("--label", default="")
+ap.add_argument("--pop", action="store_true")
 args = ap.parse_args()
 
 M, K, E, A, H, N = args.devices, 14, 6, 3, args.hidden, args.envs
@@ -42,6 +47,46 @@ net = CommActorCritic(6 * M, K, M, E, A, hidden=H).to(dev).eval()
 pk = net.packed(env)
 vis = env.visibility_mask("defender")
 base = {"label": args.label, "envs": N, "devices": M, "hidden": H, "types": K, "visible_share": round(float(vis.mean()), 4)}
+
+if args.pop:
+    from cygym_amd import policies as P
+    reps = max(args.reps, 20)
+
+    def timed(fn):
+        ms = []
+        for rep in range(args.warmup + reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            e1.synchronize()
+            if rep >= args.warmup:
+                ms.append(e0.elapsed_time(e1))
+        return sorted(ms)
+
+    def report(what, ms, **kw):
+        print(json.dumps({"what": what, **base, "ms": round(ms[len(ms) // 2], 4), "ms_min_max": [round(ms[0], 4), round(ms[-1], 4)], "reps": len(ms), **kw}), flush=True)
+    pols = []
+    for s in range(8):
+        torch.manual_seed(1 + s)
+        pols.append(P.CommActorPolicy(CommActorCritic(6 * M, K, M, E, A, hidden=H).to(dev).eval(), "defender", greedy=True))
+    for S_ in (2, 4, 8):
+        per = N // S_
+        rows = [torch.arange(s * per, (s + 1) * per, dtype=torch.int32, device=dev) for s in range(S_)]
+
+        def separate():
+            for s in range(S_):
+                pols[s].write(env, env.act, rows[s], obs[s * per:(s + 1) * per])
+        grp, r_all, o_all = P.CommActorPolicyGroup(pols[:S_], counts=[per] * S_), torch.cat(rows), obs[:S_ * per]
+        # the two paths alternate, twice each: the second pair shows the spread between runs
+        for run in (1, 2):
+            report("grid turn, S separate CommActorPolicy.write", timed(separate), S=S_, rows=S_ * per, run=run)
+            report("grid turn, one CommActorPolicyGroup.write", timed(lambda: grp.write(env, env.act, r_all, o_all)), S=S_, rows=S_ * per, run=run)
+    for run in (1, 2):
+        for tiled in (False, True):
+            mix = P.MixturePolicy(pols[:4], [0.25] * 4, "defender", tiled=tiled)
+            report("mixture turn, four nets, " + ("one population launch" if tiled else "members one by one"),
+                   timed(lambda: mix.write(env, env.act, None, obs)), S=4, run=run)
+    assert env.take_status() & abi.DECODE_TRUNCATED == 0
+    sys.exit(0)
 
 
 @torch.no_grad()
