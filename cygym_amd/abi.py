@@ -223,6 +223,13 @@ class HierNet(C.Structure):
                 ("dev_logits_out", C.c_void_p), ("n_parts", C.c_int32), ("role", C.c_int32), ("H", C.c_int32), ("h0_stride", C.c_int32)]
 
 
+HIER_POP_MAX = 32
+
+
+class HierPop(C.Structure):
+    _fields_ = [("tile_slot", C.c_void_p), ("vis_fixeds", C.c_void_p), ("h0_group_stride", C.c_int64), ("n_slots", C.c_int32), ("n_tiles", C.c_int32)]
+
+
 class HierSample(C.Structure):
     _fields_ = [("part_out", C.c_void_p), ("atype_out", C.c_void_p), ("dec_out", C.c_void_p)]
 

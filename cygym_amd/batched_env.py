@@ -1207,17 +1207,73 @@ class BatchedCyberDefenseEnv:
         self._hier(None, rows, h0, pack, role, act, vis_fixed, type_map, score_out=score_out, part_score_out=part_score_out, part_out=part_out,
                    atype_logits_out=atype_logits_out, dev_logits_out=dev_logits_out)
 
-    def _hier(self, sample, rows, h0, pack, role, act, vis_fixed, type_map, score_out=None, part_score_out=None, part_out=None,
-              atype_logits_out=None, dev_logits_out=None):
-        """The marshalling hier_decode and hier_sample_decode share: the cygym_hier_net of the arguments, then cygym_hier_decode
-        (sample is None) or cygym_hier_sample_decode with the abi.HierSample `sample`."""
+    def hier_decode_pop(self, rows_tiled: torch.Tensor, tile_slot: torch.Tensor, h0: torch.Tensor, pack, role: str = "defender", act=None,
+                        vis_fixeds=None, type_map=None, score_out=None, part_score_out=None, part_out=None, atype_logits_out=None,
+                        dev_logits_out=None):
+        """hier_decode for a POPULATION of S same-shaped HAGS nets (1 <= S <= 32), eval mode, each deciding for some of the rows: ONE
+        launch (cygym_hier_decode_pop) -- source row r is decoded exactly as hier_decode would with the net of its tile.
+          rows_tiled   [16 T] int32 on the device: the env of every source row, 16 per tile, -1 = no row (the layout mixture_draw
+                       writes and policies.mixture_rows_np restates)
+          tile_slot    [T] int32 on the device: the net of tile t; a tile whose entry is negative or >= S is left alone
+          h0           [16 T, >= 3 H]: source row r formed with ITS net;  or [S, N, >= 3 H]: block s formed with net s for every env, the
+                       row of env e in tile t reads block tile_slot[t] at row e (the caller does not know on the host who plays whom)
+          pack         the dict of hier_decode with every weight and bias tensor holding the S nets one after the other, and "S" --
+                       policies.HierarchicalPolicyGroup stacks them; part_of / n_parts / H / T are the population's
+          vis_fixeds   None: the flag plane; a contiguous uint8 [S, M] tensor: the ONE mask of every net
+          outputs      as hier_decode, by SOURCE row (16 T of them); the rows of skipped tiles and of -1 are not written
+        Every tensor is checked here: the kernel indexes them by raw pointer."""
+        self._hier(None, rows_tiled, h0, pack, role, act, vis_fixeds, type_map, score_out=score_out, part_score_out=part_score_out,
+                   part_out=part_out, atype_logits_out=atype_logits_out, dev_logits_out=dev_logits_out, tile_slot=tile_slot)
+
+    def _hier(self, sample, rows, h0, pack, role, act, vis_fixed, type_map, tile_slot=None, **outs):
+        """The path hier_decode, hier_sample_decode and hier_decode_pop share: the structs of the arguments (_hier_structs), then
+        cygym_hier_decode (sample is None), cygym_hier_sample_decode with the abi.HierSample `sample`, or -- with `tile_slot`, the
+        population form -- cygym_hier_decode_pop."""
+        net, hp, src, dst, keep = self._hier_structs(rows, h0, pack, role, act, vis_fixed, type_map, tile_slot=tile_slot, **outs)   # noqa: F841
+        if sample is not None:
+            _lib.check(self.lib.cygym_hier_sample_decode(self._h, C.byref(net), C.byref(sample), C.byref(src), C.byref(dst), self._stream()), self._h,
+                       "cygym_hier_sample_decode")
+        elif hp is not None:
+            _lib.check(self.lib.cygym_hier_decode_pop(self._h, C.byref(net), C.byref(hp), C.byref(src), C.byref(dst), self._stream()), self._h,
+                       "cygym_hier_decode_pop")
+        else:
+            _lib.check(self.lib.cygym_hier_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_hier_decode")
+
+    def _hier_structs(self, rows, h0, pack, role, act, vis_fixed, type_map, score_out=None, part_score_out=None, part_out=None,
+                      atype_logits_out=None, dev_logits_out=None, tile_slot=None):
+        """Argument checks and marshalling of the three hier decodes: (HierNet, HierPop or None, ActionVectors, Actions, tensors to
+        keep).  With `tile_slot` the population form: `rows` tiled, every weight and bias tensor of `pack` stacked over pack["S"] nets,
+        `h0` by source row or [S, N, >= 3 H], `vis_fixed` one mask per net."""
         dst = self.actions_struct(act)
+        hp = None
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
-        if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
-            raise ValueError("h0 must be a [n, >= 3 H] float32 tensor on the batch's device with unit inner stride")
-        n, H, T, P = int(h0.shape[0]), int(pack["H"]), int(pack["T"]), int(pack["n_parts"])
-        if int(h0.shape[1]) < 3 * H:
-            raise ValueError(f"h0 rows hold {int(h0.shape[1])} floats: fewer than the three {H}-wide blocks")
+        pop = tile_slot is not None
+        H, T, P = int(pack["H"]), int(pack["T"]), int(pack["n_parts"])
+        S_ = int(pack["S"]) if pop else 1
+        if pop:
+            for name, t in (("rows_tiled", rows), ("tile_slot", tile_slot)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or t.dim() != 1:
+                    raise ValueError(f"{name} must be a contiguous 1-d int32 tensor on {self.device}")
+            n = 16 * int(tile_slot.numel())
+            if int(rows.numel()) != n:
+                raise ValueError(f"rows_tiled must hold 16 entries per tile: {n} for the {n // 16} tiles of tile_slot (it has {int(rows.numel())})")
+            if S_ < 1:
+                raise ValueError("pack['S'] is the number of stacked nets, at least 1")
+            if not isinstance(h0, torch.Tensor) or not ok(h0) or h0.dim() not in (2, 3) or h0.stride(-1) != 1:
+                raise ValueError("h0 must be a [16 T, >= 3 H] or [S, N, >= 3 H] float32 tensor on the batch's device with unit inner stride")
+            nb = int(h0.shape[-2])
+            if h0.dim() == 2 and nb != n:
+                raise ValueError(f"h0 by source row must hold one row per entry of rows_tiled ({n}), it has {nb}")
+            if h0.dim() == 3 and (int(h0.shape[0]) != S_ or nb != self.N or
+                                  (nb > 1 and h0.stride(1) < int(h0.shape[2])) or
+                                  (S_ > 1 and h0.stride(0) < (nb - 1) * (h0.stride(1) if nb > 1 else 0) + int(h0.shape[2]))):
+                raise ValueError(f"h0 [S, N, >= 3 H] must hold one block of all {self.N} envs per net ({S_}), block after block")
+        else:
+            if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
+                raise ValueError("h0 must be a [n, >= 3 H] float32 tensor on the batch's device with unit inner stride")
+            n, nb = int(h0.shape[0]), int(h0.shape[0])
+        if int(h0.shape[-1]) < 3 * H:
+            raise ValueError(f"h0 rows hold {int(h0.shape[-1])} floats: fewer than the three {H}-wide blocks")
         src, _, keep = _action_vectors(self, rows, n, T, 0, 0, type_map, 0.0)
         Hp = (H + 15) // 16 * 16
         sizes = {"w_mask_t": self.M * H, "w_score": (self.M + 15) // 16 * 16 * Hp, "b_score": self.M, "w_act2": Hp * Hp, "b_act2": H,
@@ -1226,15 +1282,27 @@ class BatchedCyberDefenseEnv:
         net = abi.HierNet()
         for name, want in sizes.items():
             t = pack[name]
-            if not ok(t) or not t.is_contiguous() or int(t.numel()) != want:
-                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device} (HierarchicalNet.packed)")
+            if not ok(t) or not t.is_contiguous() or int(t.numel()) != S_ * want:
+                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {S_} x {want} values on {self.device} (HierarchicalPolicyGroup "
+                                 "stacks the members' packs)" if pop else
+                                 f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device} (HierarchicalNet.packed)")
             setattr(net, name, t.data_ptr())
         po = pack["part_of"]
         if po.dtype != torch.uint8 or po.device != self.device or not po.is_contiguous() or int(po.numel()) != self.M:
             raise ValueError(f"pack['part_of'] must be a contiguous uint8 [{self.M}] tensor on {self.device}")
         net.part_of, net.n_parts, net.role, net.H = po.data_ptr(), P, _role(role)["code"], H
-        net.h0, net.h0_stride = h0.data_ptr(), int(h0.stride(0)) if n > 1 else int(h0.shape[1])
-        if vis_fixed is not None:
+        net.h0, net.h0_stride = h0.data_ptr(), int(h0.stride(-2)) if nb > 1 else int(h0.shape[-1])
+        if pop:
+            hp = abi.HierPop()
+            hp.tile_slot, hp.n_slots, hp.n_tiles = tile_slot.data_ptr(), S_, n // 16
+            hp.h0_group_stride = (int(h0.stride(0)) if S_ > 1 else nb * net.h0_stride) if h0.dim() == 3 else 0
+            keep += [tile_slot, h0]
+            if vis_fixed is not None:
+                if not isinstance(vis_fixed, torch.Tensor) or vis_fixed.dtype != torch.uint8 or vis_fixed.device != self.device or \
+                        not vis_fixed.is_contiguous() or tuple(vis_fixed.shape) != (S_, self.M):
+                    raise ValueError(f"vis_fixeds must be a contiguous uint8 [{S_}, {self.M}] tensor on {self.device}")
+                hp.vis_fixeds = vis_fixed.data_ptr()
+        elif vis_fixed is not None:
             if int(vis_fixed.numel()) != self.M:
                 raise ValueError(f"vis_fixed must hold {self.M} entries")
             if vis_fixed.dtype != torch.uint8:
@@ -1248,11 +1316,8 @@ class BatchedCyberDefenseEnv:
                 if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
                     raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
                 setattr(net, name, t.data_ptr())
-        if sample is not None:
-            _lib.check(self.lib.cygym_hier_sample_decode(self._h, C.byref(net), C.byref(sample), C.byref(src), C.byref(dst), self._stream()), self._h,
-                       "cygym_hier_sample_decode")
-            return
-        _lib.check(self.lib.cygym_hier_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_hier_decode")
+                keep.append(t)
+        return net, hp, src, dst, keep
 
     def hier_sample_decode(self, rows, h0: torch.Tensor, pack, role: str = "defender", act=None, vis_fixed=None, type_map=None, out=None, **logit_outs):
         """The learner's SAMPLED decision of HierarchicalBestResponse.train (hierarchical_br.py:285-323, :172-231) for a batch, fused with

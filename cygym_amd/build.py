@@ -57,6 +57,7 @@ INST_COMM_POP = os.path.join(HERE, "csrc", "cg_inst_comm_pop.hip")
 INST_COMM_GAT = os.path.join(HERE, "csrc", "cg_inst_comm_gat.hip")
 INST_GAT_EVAL = os.path.join(HERE, "csrc", "cg_inst_gat_eval.hip")
 INST_HIER = os.path.join(HERE, "csrc", "cg_inst_hier.hip")
+INST_HIER_POP = os.path.join(HERE, "csrc", "cg_inst_hier_pop.hip")
 INST_HMARL = os.path.join(HERE, "csrc", "cg_inst_hmarl.hip")
 INST_HMARL_TRAIN = os.path.join(HERE, "csrc", "cg_inst_hmarl_train.hip")
 INST_META = os.path.join(HERE, "csrc", "cg_inst_meta.hip")
@@ -98,6 +99,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         units.append(("inst_comm_gat", base + ["-c", INST_COMM_GAT, "-o", os.path.join(tmp, "inst_comm_gat.o")]))   # ... with its attention layers
         units.append(("inst_gat_eval", base + ["-c", INST_GAT_EVAL, "-o", os.path.join(tmp, "inst_gat_eval.o")]))   # ... and their evaluate / backward (the PPO update)
         units.append(("inst_hier", base + ["-c", INST_HIER, "-o", os.path.join(tmp, "inst_hier.o")]))   # the hierarchical (HAGS) decode
+        units.append(("inst_hier_pop", base + ["-c", INST_HIER_POP, "-o", os.path.join(tmp, "inst_hier_pop.o")]))   # ... for a population of nets
         units.append(("inst_hmarl", base + ["-c", INST_HMARL, "-o", os.path.join(tmp, "inst_hmarl.o")]))   # the H-MARL decode
         units.append(("inst_hmarl_train", base + ["-c", INST_HMARL_TRAIN, "-o", os.path.join(tmp, "inst_hmarl_train.o")]))   # its training decision
         units.append(("inst_meta", base + ["-c", INST_META, "-o", os.path.join(tmp, "inst_meta.o")]))   # the MetaDOAR decode

@@ -110,6 +110,9 @@ extern template __global__ void hier_kernel<false>(cygym_hier_net, cygym_action_
 extern template __global__ void hier_kernel<true>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 extern template __global__ void hier_kernel<false, true>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int, cygym_hier_sample);
 extern template __global__ void hier_kernel<true, true>(cygym_hier_net, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int, cygym_hier_sample);
+// ... and for a population of nets (cg_inst_hier_pop.hip)
+extern template __global__ void hier_pop_kernel<false>(cygym_hier_net, cygym_hier_pop, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
+extern template __global__ void hier_pop_kernel<true>(cygym_hier_net, cygym_hier_pop, cygym_action_vectors, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, int);
 extern template __global__ void hier_loss_kernel<false>(cygym_hier_loss_desc);
 extern template __global__ void hier_loss_kernel<true>(cygym_hier_loss_desc);
 }  // namespace cygym_k
@@ -330,6 +333,7 @@ int cygym_sizeof(int32_t which) {
     case 42: return (int)sizeof(cygym_committee);   // (index 41 stays unassigned: earlier bindings probe it for -1)
     case 44: return (int)sizeof(cygym_critic_pop);   // (index 43 stays unassigned)
     case 46: return (int)sizeof(cygym_comm_actor_pop);   // (index 45 stays unassigned)
+    case 48: return (int)sizeof(cygym_hier_pop);   // (index 47 stays unassigned)
     default: return -1;
   }
 }
@@ -1213,12 +1217,13 @@ int cygym_comm_gat_decode(cygym_handle* h, const cygym_comm_actor* net, const cy
   return launch_decode(h, k, dim3(grid), dim3(GT_THREADS), lds, stream, {net, gat, src, dst}, {&live, &M});   // a workgroup per row, walking over the rows
 }
 
-// cygym_hier_decode (smp == NULL) and cygym_hier_sample_decode: one argument check, one launch shape.
-static int hier_launch(cygym_handle* h, const cygym_hier_net* net, const cygym_hier_sample* smp, bool sample, const cygym_action_vectors* src,
-                       const cygym_actions* dst, void* stream, const char* who, const char* bad_layout) {
+// What cygym_hier_decode, cygym_hier_sample_decode and cygym_hier_decode_pop check alike, in the order a caller sees (own_ptrs: the
+// pointers of the function's own descriptors are there; fixed_vis: the visibility is a given mask, the flag plane is not read), and the
+// LDS a workgroup of 16 rows needs.
+static int check_hier(cygym_handle* h, const cygym_hier_net* net, bool sample, const cygym_action_vectors* src, const cygym_actions* dst,
+                      const char* who, const char* bad_layout, bool own_ptrs, bool fixed_vis, size_t* lds) {
   const bool own = net && net->h0 && net->w_mask_t && net->w_score && net->b_score && net->w_act2 && net->b_act2 && net->w_dev2 && net->b_dev2 &&
-                   net->w_act_head && net->b_act_head && net->w_dev_head && net->b_dev_head && net->part_of &&
-                   (!sample || (smp && smp->part_out && smp->atype_out && smp->dec_out));
+                   net->w_act_head && net->b_act_head && net->w_dev_head && net->b_dev_head && net->part_of && own_ptrs;
   if (const int rc = check_vectors(h, src, dst, who, own, 0, bad_layout)) return rc;
   if (src->n_types < 1 || net->n_parts < 1 || net->n_parts > HR_MAX_PARTS || (net->role != 1 && net->role != 2) || net->H < 1 ||
       (long long)net->h0_stride < 3ll * net->H ||
@@ -1227,12 +1232,21 @@ static int hier_launch(cygym_handle* h, const cygym_hier_net* net, const cygym_h
   if (net->H < 16 || net->H > HR_MAX_H || (net->H & 15) || src->n_types > HR_MAX_T || h->t.M > HR_MAX_M)
     return fail(h, CYGYM_EUNSUPPORTED, "%s: H must be a multiple of 16 in 16 .. 256, at most 32 action types, at most 2048 devices", who);
   if (sample && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (the draws are addressed by the envs' rng ticks)", who);
-  if (!net->vis_fixed && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (without vis_fixed the visibility mask is read off the flag plane)", who);
+  if (!fixed_vis && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (without vis_fixed the visibility mask is read off the flag plane)", who);
   if (const int rc = check_rows(h, src->n, src->rows, 0, who)) return rc;
+  *lds = (size_t)hr_plan(net->H, h->t.M).total * sizeof(float);
+  return CYGYM_OK;
+}
+
+// cygym_hier_decode (smp == NULL) and cygym_hier_sample_decode: one launch shape.
+static int hier_launch(cygym_handle* h, const cygym_hier_net* net, const cygym_hier_sample* smp, bool sample, const cygym_action_vectors* src,
+                       const cygym_actions* dst, void* stream, const char* who, const char* bad_layout) {
+  size_t lds = 0;
+  if (const int rc = check_hier(h, net, sample, src, dst, who, bad_layout, !sample || (smp && smp->part_out && smp->atype_out && smp->dec_out),
+                                net && net->vis_fixed, &lds))
+    return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  const HrPlan pl = hr_plan(net->H, h->t.M);
-  const size_t lds = (size_t)pl.total * sizeof(float);
   if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the tiles do not fit in LDS", who);
   const bool outs = net->score_out || net->part_score_out || net->part_out || net->atype_logits_out || net->dev_logits_out;
   const void* k = sample ? (outs ? (const void*)hier_kernel<true, true, cygym_hier_sample> : (const void*)hier_kernel<false, true, cygym_hier_sample>)
@@ -1254,6 +1268,29 @@ int cygym_hier_sample_decode(cygym_handle* h, const cygym_hier_net* net, const c
                              const cygym_actions* dst, void* stream) {
   return hier_launch(h, net, smp, true, src, dst, stream, "cygym_hier_sample_decode",
                      "cygym_hier_sample_decode: bad layout (types >= 1, the handle's device count, 1 .. 255 parts, role 1 or 2, h0_stride >= 3 H, 16-byte aligned packed matrices / w_mask_t)%s");
+}
+
+int cygym_hier_decode_pop(cygym_handle* h, const cygym_hier_net* net, const cygym_hier_pop* pop, const cygym_action_vectors* src,
+                          const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_hier_decode_pop";
+  const char* const bad_layout = "cygym_hier_decode_pop: bad layout (types >= 1, the handle's device count, 1 .. 255 parts, role 1 or 2, h0_stride >= 3 H, 16-byte aligned packed matrices / w_mask_t)%s";
+  size_t lds = 0;
+  if (const int rc = check_hier(h, net, false, src, dst, who, bad_layout, pop && pop->tile_slot && src && src->rows, pop && pop->vis_fixeds, &lds))
+    return rc;
+  if (pop->n_slots < 1 || pop->n_slots > CG_HIER_POP_MAX) return fail(h, CYGYM_EUNSUPPORTED, "%s: 1 to CG_HIER_POP_MAX nets", who);
+  if (pop->n_tiles < 0 || (int64_t)src->n != 16 * (int64_t)pop->n_tiles)
+    return fail(h, CYGYM_EINVAL, "%s: the row list holds 16 rows per tile (layout->n = 16 n_tiles)", who);
+  if (pop->h0_group_stride < 0 || (pop->h0_group_stride > 0 && pop->h0_group_stride < (int64_t)(h->n_envs - 1) * net->h0_stride + 3ll * net->H))
+    return fail(h, CYGYM_EINVAL, "%s: h0_group_stride is 0 (h0 by source row) or at least one block, (n_envs - 1) h0_stride + 3 H", who);
+  if (src->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the tiles do not fit in LDS", who);
+  const bool outs = net->score_out || net->part_score_out || net->part_out || net->atype_logits_out || net->dev_logits_out;
+  const void* k = outs ? (const void*)hier_pop_kernel<true> : (const void*)hier_pop_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const uint8_t* live = h->bound ? (const uint8_t*)h->b.live : nullptr;
+  int M = h->t.M;
+  return launch_decode(h, k, dim3(pop->n_tiles), dim3(HR_THREADS), lds, stream, {net, pop, src, dst}, {&live, &M});   // a tile of 16 rows per workgroup
 }
 
 static int hier_loss_launch(cygym_handle* h, const cygym_hier_loss_desc* e, void* stream, bool bwd, const char* who) {

@@ -1970,6 +1970,11 @@ class HierarchicalPolicy:
         self.n_types = net.n_types
         self.type_map = None if type_map is None else torch.as_tensor(type_map, dtype=torch.int32)
         self.action_types = list(range(self.n_types)) if type_map is None else sorted({int(x) for x in self.type_map.tolist()})
+        # what HierarchicalPolicyGroup.key compares, taken here on the host (part_table builds the table there): the planner and
+        # write() never read the device for it
+        import hashlib
+        self.part_digest = hashlib.sha1(bytes(self.part_of.tolist())).hexdigest()
+        self.type_map_key = None if type_map is None else tuple(int(x) for x in self.type_map.tolist())
 
     _map = ActorPolicy._map
 
@@ -2021,6 +2026,114 @@ class HierarchicalPolicy:
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("a HierarchicalPolicy reads the visibility of the env it decides for off the batch's flag plane: it "
                                   "runs through write(), on a batch with cygym_hier_decode (HierarchicalNet.decide is the torch form)")
+
+
+class HierarchicalPolicyGroup:
+    """A population of HierarchicalPolicy (HAGS) strategies of ONE shape (key) decided together: h0 of all of them is one batched
+    GEMM and the decode of all of them is ONE launch (cygym_hier_decode_pop), the net of a tile of 16 rows taken from a slot table.
+    The decode gives a workgroup 16 rows and about 100 KB of LDS at H = 256, so a launch per strategy over that strategy's few rows
+    leaves most of the chip idle; the |D| x |A| grid of a Double-Oracle population with --BR_type hierarchical and the opponent drawn
+    per env from an equilibrium (MixturePolicy) hold several such nets, each deciding for a few envs.
+    counts / in_tile_order / shared_obs: the three row conventions of CommActorPolicyGroup, whose tile_plan lays the rows out."""
+
+    tick_free = True
+    MIN_MEMBERS = 2           # the smallest population simulate_grid groups (PERFLOG.md has the measurement)
+    MIN_MEMBERS_MIXTURE = 4   # ... and the smallest MixturePolicy groups: there h0 is formed for every (net, env), which at two
+    #                           members costs more than the launch it saves and at three as much (measured, PERFLOG.md)
+    tile_plan = staticmethod(CommActorPolicyGroup.tile_plan)
+
+    def __init__(self, policies, counts=None, in_tile_order: bool = False):
+        self.policies = list(policies)
+        if not 1 <= len(self.policies) <= 32:
+            raise ValueError("1 to 32 nets")
+        p0 = self.policies[0]
+        k0 = self.key(p0, getattr(getattr(p0, "net", None), "M", 0))
+        if k0 is None or any(self.key(p, p0.net.M) != k0 for p in self.policies):
+            raise ValueError("the members are HierarchicalPolicy of one key (HierarchicalPolicyGroup.key)")
+        self.role, self.n_types, self.action_types = p0.role, p0.n_types, list(p0.action_types)
+        self.counts = None if counts is None else [int(c) for c in counts]
+        if self.counts is not None and len(self.counts) != len(self.policies):
+            raise ValueError("counts: one row count per member")
+        self.in_tile_order = bool(in_tile_order)
+        self._pk = self._pk_ver = self._tiles = None
+
+    @staticmethod
+    def key(p, M):
+        """What must agree across the members of a population -- role, state width, H, T, M, the number of parts and the part table
+        (its digest), the type map, fixed against env visibility -- or None when `p` is no HierarchicalPolicy.  Host values only."""
+        if not isinstance(p, HierarchicalPolicy):
+            return None
+        n = p.net
+        return (p.role, n.state_dim, n.hidden, n.n_types, n.M, p.n_parts, p.part_digest, p.type_map_key, p.vis is None)
+
+    def _stacked(self, device=None):
+        """The members' packs (HierarchicalNet.packed) slot after slot, as the dict hier_decode_pop reads, plus the batched operands
+        of h0 -- w0_t [S, W, 3 H], b0 [S, 1, 3 H] -- and vis_fixeds [S, M] when the members carry fixed masks.  Redone when a member's
+        parameter changes (the members' own packed() versions) or the device does."""
+        device = self.policies[0].net.score_net.fc1.weight.device if device is None else torch.device(device)
+        packs = [p._packed(device) for p in self.policies]
+        ver = (device,) + tuple(p.net._pk_ver for p in self.policies)
+        if self._pk_ver != ver:
+            st = lambda k: torch.stack([pk[k] for pk in packs]).contiguous()  # noqa: E731
+            pk0 = packs[0]
+            self._pk = {"H": pk0["H"], "T": pk0["T"], "S": len(packs), "part_of": pk0["part_of"], "n_parts": pk0["n_parts"],
+                        "w0_t": st("w0_t"), "b0": st("b0")[:, None, :].contiguous()}
+            for k in ("w_mask_t", "w_score", "b_score", "w_act2", "b_act2", "w_dev2", "b_dev2", "w_act_head", "b_act_head", "w_dev_head", "b_dev_head"):
+                self._pk[k] = st(k)
+            if self.policies[0].vis is not None:
+                self._pk["vis_fixeds"] = torch.stack([p.vis for p in self.policies]).contiguous()
+            self._pk_ver = ver
+        return self._pk
+
+    def h0(self, obs_s, pack):
+        """[S, n, 3 H]: the three first-layer pre-activations of every (net, row) of obs_s [S, n, W] (or an expanded [n, W]): one baddbmm."""
+        return torch.baddbmm(pack["b0"], obs_s, pack["w0_t"])
+
+    def _tile_tensors(self, device):
+        if self._tiles is None or self._tiles[0].device != device:
+            pos, valid, tile_slot = self.tile_plan(self.counts)
+            self._tiles = (torch.from_numpy(pos).to(device), torch.from_numpy(valid).to(device), torch.from_numpy(tile_slot).to(device),
+                           bool(valid.all()))
+        return self._tiles
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, tile_slot=None, shared_obs=False, **outs):
+        """One baddbmm, then ONE decode launch for all members (the optional outputs of hier_decode_pop by keyword: by source row, in
+        tile order).
+        Default: `rows` / `obs` [n, W] hold the members' rows member after member (counts); they are gathered once into the padded
+        tile order (not at all when in_tile_order, or when every count is the same multiple of 16) and h0 is formed per source row.
+        shared_obs: `rows` [16 T] and tile_slot [T] are the caller's tiles, made on the device (the draw of a mixture), obs [N, W]
+        holds every env once: h0 is [S, N, 3 H] and the kernel reads the block of the tile's slot."""
+        p0 = self.policies[0]
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != p0.net.state_dim:
+            raise ValueError(f"obs must be a float32 [n, {p0.net.state_dim}] role view")
+        if batch.M != p0.net.M:
+            raise ValueError(f"the nets were built for {p0.net.M} devices, the batch has {batch.M}")
+        pack = self._stacked(obs.device)
+        S_, W, H3 = (int(x) for x in pack["w0_t"].shape)
+        if shared_obs:
+            if tile_slot is None or rows is None:
+                raise ValueError("shared_obs: the caller says which tile plays whom (rows = rows_tiled, tile_slot)")
+            h0 = self.h0(obs[None].expand(S_, int(obs.shape[0]), W), pack)
+        else:
+            if self.counts is None:
+                raise ValueError("rows ordered member after member need counts")
+            pos, valid, tile_slot, dense = self._tile_tensors(obs.device)
+            n_pad = int(pos.numel())
+            if self.in_tile_order or (dense and int(obs.shape[0]) == n_pad):
+                if int(obs.shape[0]) != n_pad or rows is None or int(rows.numel()) != n_pad:
+                    raise ValueError(f"rows in tile order: {n_pad} padded rows (tile_plan)")
+            else:
+                if sum(self.counts) != int(obs.shape[0]) or rows is None or int(rows.numel()) != int(obs.shape[0]):
+                    raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
+                obs = obs.index_select(0, pos)
+                rows = torch.where(valid, rows.index_select(0, pos), torch.full_like(rows[:1], -1))
+            h0 = self.h0(obs.reshape(S_, n_pad // S_, W), pack).reshape(n_pad, H3)
+        batch.hier_decode_pop(rows, tile_slot, h0, pack, self.role, act=act, vis_fixeds=pack.get("vis_fixeds"), type_map=p0._map(obs.device), **outs)
+
+    def __call__(self, obs, t, M, L):
+        raise NotImplementedError("a HierarchicalPolicyGroup reads the visibility of the envs it decides for off the batch's flag plane: it "
+                                  "runs through write(), on a batch with cygym_hier_decode_pop")
 
 
 @torch.no_grad()
@@ -2956,7 +3069,10 @@ class MixturePolicy:
          two or more: the draw's rows_tiled / tile_slot carry THEIR slots, two baddbmm on `obs` in place form tok_base for every
          (net, env), and ONE cygym_comm_actor_decode_pop decodes the tiles (tiled = False: off).  cygym_mixture_draw has one
          member_slot table: when step 2 formed an ActorPolicyGroup, that group keeps the tiles and the comm members play one by one;
-      5. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
+      5. among the other members, the HierarchicalPolicy (HAGS) of ONE key (HierarchicalPolicyGroup.key) that can play,
+         HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE or more, when neither step 2 nor step 4 holds the member_slot table: one baddbmm
+         forms h0 for every (net, env) and ONE cygym_hier_decode_pop decodes the draw's tiles (tiled = False: off);
+      6. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
          rollout_grid.SequencePolicy + write_actions with the tick the loop set (set_tick: the loop's tick counter; a callable without
          uses_global_tick gets t // 2, as the loops call it).  A member of probability 0 never plays and is not launched.
     act["n_groups"] is the caller's to clear before the call (Turns.opponent, ddpg_rollout.collect do); a member that writes groups sets
@@ -3044,20 +3160,30 @@ class MixturePolicy:
     def _comm_group(self, batch, taken: bool):
         """(CommActorPolicyGroup, slot of every member or -1) of the largest set of same-key CommActorPolicy members (no attention
         layers) that can play, or (None, all -1).  taken: the draw's one member_slot table already serves an ActorPolicyGroup."""
+        return self._tile_group(batch, taken, CommActorPolicyGroup, "comm_actor_decode_pop", CommActorPolicyGroup.MIN_MEMBERS)
+
+    def _hier_group(self, batch, taken: bool):
+        """(HierarchicalPolicyGroup, slot of every member or -1) of the largest set of same-key HierarchicalPolicy members that can
+        play, HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE or more, or (None, all -1).  taken: the draw's one member_slot table already
+        serves an ActorPolicyGroup or a CommActorPolicyGroup (the HAGS members then play one by one)."""
+        return self._tile_group(batch, taken, HierarchicalPolicyGroup, "hier_decode_pop", HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE)
+
+    def _tile_group(self, batch, taken, Group, entry, min_members):
+        """What _comm_group and _hier_group share: the largest same-key set (Group.key) of members of probability > 0."""
         slots = [-1] * len(self.members)
-        if taken or not (self.tiled and hasattr(batch, "mixture_draw") and hasattr(batch, "comm_actor_decode_pop")):
+        if taken or not (self.tiled and hasattr(batch, "mixture_draw") and hasattr(batch, entry)):
             return None, slots
         by_key = {}
         for s, m in enumerate(self.members):
-            k = CommActorPolicyGroup.key(m, batch.M)
+            k = Group.key(m, batch.M)
             if k is not None and self.probs[s] > 0.0:
                 by_key.setdefault(k, []).append(s)
         best = max(by_key.values(), key=len, default=[])
-        if len(best) < max(2, CommActorPolicyGroup.MIN_MEMBERS):
+        if len(best) < max(2, min_members):
             return None, slots
         for pos, s in enumerate(best):
             slots[s] = pos
-        return CommActorPolicyGroup([self.members[s] for s in best]), slots
+        return Group([self.members[s] for s in best]), slots
 
     def _state(self, batch):
         st = self._st
@@ -3068,15 +3194,19 @@ class MixturePolicy:
             mgrp, mslots = self._comm_group(batch, grp is not None)
             if mgrp is not None:      # (the draw's tiles go to the comm nets: `group` stays None, `slots` is the table the draw reads)
                 slots = mslots
+            hgrp, hslots = self._hier_group(batch, grp is not None or mgrp is not None)
+            if hgrp is not None:      # (... or to the HAGS nets, when nobody else holds the table)
+                slots = hslots
+            tiles = grp is not None or mgrp is not None or hgrp is not None
             T = (N + 15) // 16 + S_
             z = lambda shape, dt, v=0: torch.full(shape, v, dtype=dt, device=dev)  # noqa: E731
             st = self._st = dict(batch=batch, group=grp, slots=slots, cdf=torch.from_numpy(self.cdf).to(dev),
                                  member_baseline=torch.tensor(self.baseline, dtype=torch.int8, device=dev),
                                  member_slot=torch.tensor(slots, dtype=torch.int8, device=dev), baseline_state=z((N,), torch.int8, -1),
                                  index=z((N,), torch.uint8), rows_masked=z((S_, N), torch.int32, -1), rows_ok=None,
-                                 rows_tiled=z((16 * T,), torch.int32, -1) if (grp is not None or mgrp is not None) else None,
-                                 tile_slot=z((T,), torch.int32, -1) if (grp is not None or mgrp is not None) else None,
-                                 comm=mgrp, comm_slots=mslots,
+                                 rows_tiled=z((16 * T,), torch.int32, -1) if tiles else None,
+                                 tile_slot=z((T,), torch.int32, -1) if tiles else None,
+                                 comm=mgrp, comm_slots=mslots, hier=hgrp, hier_slots=hslots,
                                  critics=cgrp, critic_slots=cslots, critic_slot_of=torch.tensor(cslots, dtype=torch.int32, device=dev),
                                  slot_of_row=z((N,), torch.int32, -1) if cgrp is not None else None)
         return st
@@ -3120,9 +3250,14 @@ class MixturePolicy:
         if mgrp is not None and in_place:
             # the draw's tiles carry the comm nets' slots: tok_base for every (net, env), then ONE decode launch over the tiles
             mgrp.write(batch, act, st["rows_tiled"], obs[:N], tile_slot=st["tile_slot"], shared_obs=True)
+        hgrp, hslots = st["hier"], st["hier_slots"]
+        if hgrp is not None and in_place:
+            # the draw's tiles carry the HAGS nets' slots: h0 for every (net, env), then ONE decode launch over the tiles
+            hgrp.write(batch, act, st["rows_tiled"], obs[:N], tile_slot=st["tile_slot"], shared_obs=True)
         for s, m in enumerate(self.members):
             if (grp is not None and in_place and slots[s] >= 0) or (cgrp is not None and in_place and cslots[s] >= 0) or \
-                    (mgrp is not None and in_place and mslots[s] >= 0) or self.probs[s] == 0.0:
+                    (mgrp is not None and in_place and mslots[s] >= 0) or (hgrp is not None and in_place and hslots[s] >= 0) or \
+                    self.probs[s] == 0.0:
                 continue
             r = st["rows_masked"][s]
             if hasattr(m, "write"):

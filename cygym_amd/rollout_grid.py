@@ -268,18 +268,32 @@ def _group_comm(batch, items, M):
     item's env ids ARE that padded order (env 0 on the padding, -1 in the row list), so the tick gathers the observations once, in
     the order tok_base is formed in.  Row counts may be unequal and need not be multiples of 16."""
     from .policies import CommActorPolicyGroup
-    if len(items) < 2 or not hasattr(batch, "comm_actor_decode_pop"):
+    return _group_tiled(batch, items, M, CommActorPolicyGroup, "comm_actor_decode_pop")
+
+
+def _group_hier(batch, items, M):
+    """The same step for the HAGS strategies (policies.HierarchicalPolicy) of ONE key (policies.HierarchicalPolicyGroup.key: shape,
+    part table, type map, kind of visibility), HierarchicalPolicyGroup.MIN_MEMBERS or more: one baddbmm and one
+    cygym_hier_decode_pop per role and tick over all their rows, in the padded tile order of _group_comm."""
+    from .policies import HierarchicalPolicyGroup
+    return _group_tiled(batch, items, M, HierarchicalPolicyGroup, "hier_decode_pop")
+
+
+def _group_tiled(batch, items, M, Group, entry):
+    """What _group_comm and _group_hier share: the same-key items (Group.key), Group.MIN_MEMBERS or more in chunks of at most 32,
+    become one item of Group in padded tile order; on a batch without the entry point `entry` the items stay as they are."""
+    if len(items) < 2 or not hasattr(batch, entry):
         return items
     by_key = {}
     for i, it in enumerate(items):
-        k = CommActorPolicyGroup.key(it[0], M)
+        k = Group.key(it[0], M)
         if k is not None:
             by_key.setdefault(k, []).append(i)
     first = {}
     for members in by_key.values():
         for lo in range(0, len(members), 32):      # (a population holds at most 32 nets)
             chunk = members[lo:lo + 32]
-            if len(chunk) >= max(2, CommActorPolicyGroup.MIN_MEMBERS):
+            if len(chunk) >= max(2, Group.MIN_MEMBERS):
                 first[chunk[0]] = chunk
     taken = {i for chunk in first.values() for i in chunk[1:]}
     out = []
@@ -291,12 +305,12 @@ def _group_comm(batch, items, M):
             continue
         chunk = [items[j] for j in first[i]]
         counts = [int(c[1].numel()) for c in chunk]
-        pos, valid, _ = CommActorPolicyGroup.tile_plan(counts)
+        pos, valid, _ = Group.tile_plan(counts)
         ids = torch.cat([c[1] for c in chunk]).cpu().numpy()[pos]
         r64 = torch.from_numpy(ids).to(chunk[0][1].device)
         r32 = torch.from_numpy(np.where(valid, ids, -1).astype(np.int32)).to(chunk[0][1].device)
         sl = slice(int(ids[0]), int(ids[-1]) + 1) if (valid.all() and (np.diff(ids) == 1).all()) else None
-        out.append((CommActorPolicyGroup([c[0] for c in chunk], counts=counts, in_tile_order=True), r64, r32, sl, None))
+        out.append((Group([c[0] for c in chunk], counts=counts, in_tile_order=True), r64, r32, sl, None))
     return out
 
 
@@ -411,7 +425,7 @@ def simulate_grid(batch, def_policies, att_policies, n_mc: int, T: int, randomiz
                 items.append((p, t64, t64.to(torch.int32), sl, None))
             # the whole grid in env order: env e plays defender strategy e // (nA n_mc) and attacker strategy (e // n_mc) % nA
             rpg = (nA * n_mc if r == HL.DEFENDER else n_mc) if (S_sub == 1 and cell_offset == 0 and N == cells) else None
-            plan[r].append(_group_comm(batch, _group_critics(batch, _group_actors(batch, items, M, rpg) if fused else items, M), M))
+            plan[r].append(_group_hier(batch, _group_comm(batch, _group_critics(batch, _group_actors(batch, items, M, rpg) if fused else items, M), M), M))
     bl = baseline_schedule(def_policies, att_policies, cell_np, n_mc, min(T, 4), _cfg_baseline_code(batch))
     # (ticks >= 2 repeat with period 2: rows 2 / 3 of the schedule; shorter runs only have the first rows)
     mode_words = [torch.from_numpy(((bl[t] + 1) << S.MODE_BASELINE_SHIFT) | (t % 2)).to(device=dev, dtype=torch.int32)

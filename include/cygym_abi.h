@@ -193,7 +193,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train, 31 cygym_dns, 33 cygym_mixture, 46 cygym_comm_actor_pop; -1 for anything else, 13, 15, 18, 22, 24, 26, 30 and 32 included: those indices stay unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train, 31 cygym_dns, 33 cygym_mixture, 46 cygym_comm_actor_pop, 48 cygym_hier_pop; -1 for anything else, 13, 15, 18, 22, 24, 26, 30 and 32 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -1132,11 +1132,51 @@ typedef struct cygym_hier_net {
  * kernel, and the Python layer (policies.HierarchicalPolicy) refuses such a table when it builds it.  CYGYM_ENOTBOUND only when the flag
  * plane is needed (vis_fixed == NULL) and the handle is not bound.
  * Out of scope (the sampled mode of train() and the head of its REINFORCE update are the calls below): `meta`
- * (meta_hierarchical_br.py) and the HMARL families; populations of nets in one launch;
+ * (meta_hierarchical_br.py) and the HMARL families;
  * building h0 from the flag planes on chip; non-finite score logits (torch.argmax treats NaN as the maximum: here a valid row is
- * still written, which part wins is unspecified). */
+ * still written, which part wins is unspecified).  A population of nets in one launch is cygym_hier_decode_pop below. */
 int cygym_hier_decode(cygym_handle* h, const cygym_hier_net* net, const cygym_action_vectors* layout, const cygym_actions* dst,
                       void* stream);
+
+/* A population of same-shaped HAGS nets for cygym_hier_decode_pop.  DEVICE pointers. */
+#define CG_HIER_POP_MAX 32   /* = CG_MIXTURE_MAX_MEMBERS */
+typedef struct cygym_hier_pop {
+  const int32_t* tile_slot;    /* [n_tiles] the net of tile t (source rows 16 t .. 16 t + 15): 0 .. n_slots - 1; any other value: the
+                                  tile is left alone                                                                                  */
+  const uint8_t* vis_fixeds;   /* optional [n_slots][M], non-zero = visible: the ONE mask of every slot, used for all of its rows; NULL:
+                                  every row reads the flag plane of its env.  cygym_hier_net.vis_fixed is not read                    */
+  int64_t  h0_group_stride;    /* floats.  0: cygym_hier_net.h0 is [n][h0_stride] by source row, each row formed with ITS net.
+                                  > 0: h0 is [n_slots][n_envs][h0_stride], block s at s * h0_group_stride formed with net s, and the
+                                  row of env e in tile t reads block tile_slot[t] at row e (who plays whom is then known on the
+                                  device only)                                                                                        */
+  int32_t  n_slots;            /* 1 .. CG_HIER_POP_MAX                                                                                 */
+  int32_t  n_tiles;            /* layout->n = 16 * n_tiles                                                                             */
+} cygym_hier_pop;
+
+/* cygym_hier_decode for a population of nets of ONE shape (H, T, M, role, part_of / n_parts, type_map in common), eval mode, in ONE
+ * launch: source row r -- visibility, the score pass and the parts' sums, the chosen part and its subset, the two fallbacks, the
+ * two-stage net on the matrix cores in chunks of 512 columns, nan_to_num, the decision, the shared row writer, CG_DECODE_TRUNCATED,
+ * every summation order -- is decoded exactly as cygym_hier_decode decodes it, with the weights of net s = pop->tile_slot[r / 16].
+ * The rows of a workgroup are independent of each other, so a row's result is bit-identical whatever else shares its tile.  Where
+ * several nets each decide for a few rows (the payoff grid of a double-oracle population with --BR_type hierarchical, the opponent
+ * drawn per env from an equilibrium) one launch fills the chip that a launch per net of a few workgroups leaves mostly idle.
+ * `net` describes slot 0: w_mask_t [M][H], the packed w_score / w_dev_head [ceil(M / 16)][H / 16][64][4], w_act2 / w_dev2 [H][H],
+ * w_act_head [ceil(T / 16)][H / 16][64][4] and the biases b_score [M], b_act2 [H], b_dev2 [H], b_act_head [T], b_dev_head [M] of slot s
+ * follow those of slot s - 1 contiguously -- every per-slot matrix is a multiple of 16 bytes, so the alignment of slot 0 carries
+ * over.  part_of, n_parts, role, H and h0_stride are the population's; vis_fixed is not read (pop->vis_fixeds: ONE form of visibility
+ * for the whole population).  layout->rows is MANDATORY: a tiled row list [16 n_tiles], 16 rows per tile, -1 = no row (skipped as in
+ * cygym_hier_decode) -- the layout cygym_mixture_draw writes as rows_tiled / tile_slot.  The optional outputs of cygym_hier_net stay
+ * indexed by source row: [16 n_tiles] rows of them.  A tile whose slot is negative or >= n_slots writes NOTHING -- no action row, no
+ * optional output, no status bit: its workgroup returns before its first barrier.  No Philox draw; the rng tick is neither read
+ * nor advanced; no atomics.
+ * CYGYM_EUNSUPPORTED: n_slots outside 1 .. CG_HIER_POP_MAX.  CYGYM_EINVAL: NULL pop, tile_slot or layout->rows; layout->n !=
+ * 16 n_tiles; h0_group_stride < 0, or > 0 and smaller than one block, (n_envs - 1) h0_stride + 3 H.  CYGYM_ENOTBOUND only when the
+ * flag plane is needed (vis_fixeds == NULL) and the handle is not bound.  Every other check, limit and message convention is that of
+ * cygym_hier_decode.  Nothing is launched and nothing is written on a refusal.
+ * Out of scope: the sampled (training) decision for a population; populations of `meta`, H-MARL and committee strategies; building
+ * h0 on chip. */
+int cygym_hier_decode_pop(cygym_handle* h, const cygym_hier_net* net /* slot 0 */, const cygym_hier_pop* pop,
+                          const cygym_action_vectors* layout, const cygym_actions* dst, void* stream);
 
 /* What the SAMPLED decision of the HAGS training loop hands back per source row (all three mandatory, DEVICE pointers): what the
  * REINFORCE update needs to evaluate the decision again under later weights (cygym_hier_loss). */

@@ -6,7 +6,12 @@
   (c) the existing yardstick for a whole-network decode: cygym_actor_mlp_decode of a three-hidden-layer 256-wide ActorPolicy
   (d) a simulate_grid turn (two ticks: both roles decide once) with HierarchicalPolicy on both sides, from --ticks ticks of a
       1 x 1 grid, eager and with graph=True
-One JSON line per measurement: median and min..max over --reps repetitions."""
+One JSON line per measurement: median and min..max over --reps repetitions.
+--pop: the population leg alone (at least 21 repetitions after a warm-up of every shape) -- one defender turn of a grid whose --envs
+envs are shared evenly by S = 2, 4, 8, 16 same-key strategies, as S HierarchicalPolicy.write calls (one addmm + cygym_hier_decode
+each: the ungrouped path, measured twice per repetition -- the difference of its two medians is the yardstick's own spread) and as
+the one launch of HierarchicalPolicyGroup (one baddbmm + cygym_hier_decode_pop); and one MixturePolicy turn at --envs envs with two,
+three, four and eight same-key members, written one by one (tiled=False) and through the population launch."""
 import argparse
 import json
 import math
@@ -30,6 +35,7 @@ ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--ticks", type=int, default=40)
 ap.add_argument("--label", default="")
+ap.add_argument("--pop", action="store_true")
 args = ap.parse_args()
 
 M, T, H, N = args.devices, 14, args.hidden, args.envs
@@ -54,6 +60,56 @@ net, pk = pol.net, pol._packed(torch.device(dev))
 vis = env.visibility_mask("defender")
 base = {"label": args.label, "envs": N, "devices": M, "hidden": H, "types": T, "parts": pol.n_parts, "visible_share": round(float(vis.mean()), 4)}
 zero = torch.zeros(N, dtype=torch.int32, device=dev)
+
+if args.pop:
+    from cygym_amd import policies as P
+    P.HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE = 2      # (measure the grouped mixture whatever the shipped threshold says)
+    reps = max(args.reps, 21)
+    pols = [policy("defender", 1 + s, T) for s in range(16)]
+
+    def median(v):
+        v = sorted(v)
+        return {"ms": round(v[len(v) // 2], 4), "ms_min_max": [round(v[0], 4), round(v[-1], 4)], "reps": len(v)}
+
+    def alternate(what, legs, **kw):
+        """The legs one after the other inside every repetition, HIP events around each; one JSON line per leg."""
+        ms = {k: [] for k in legs}
+        for rep in range(args.warmup + reps):
+            for k, fn in legs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); fn(); e1.record()
+                e1.synchronize()
+                if rep >= args.warmup:
+                    ms[k].append(e0.elapsed_time(e1))
+        for k, v in ms.items():
+            print(json.dumps({"what": f"{what}, {k}", **base, **median(v), **kw}), flush=True)
+
+    shapes = []
+    for S_ in (2, 4, 8, 16):
+        per = N // S_
+        rows = [torch.arange(s * per, (s + 1) * per, dtype=torch.int32, device=dev) for s in range(S_)]
+
+        def separate(S_=S_, per=per, rows=rows):
+            for s in range(S_):
+                pols[s].write(env, None, rows[s], obs[s * per:(s + 1) * per])
+        grp, r_all, o_all = P.HierarchicalPolicyGroup(pols[:S_], counts=[per] * S_), torch.cat(rows), obs[:S_ * per]
+        # the ungrouped leg twice per repetition: the difference of its two medians is the yardstick's own spread
+        shapes.append((f"grid turn over {S_ * per} rows", {"S separate HierarchicalPolicy.write": separate,
+                                                          "one HierarchicalPolicyGroup.write": lambda grp=grp, r=r_all, o=o_all: grp.write(env, None, r, o),
+                                                          "S separate HierarchicalPolicy.write, again": separate}, {"S": S_}))
+    for S_ in (2, 3, 4, 8):
+        mixes = {tiled: P.MixturePolicy(pols[:S_], [1.0 / S_] * S_, "defender", tiled=tiled) for tiled in (False, True)}
+        shapes.append(("mixture turn", {"members one by one": lambda m=mixes[False]: m.write(env, env.act, None, obs),
+                                        "one population launch": lambda m=mixes[True]: m.write(env, env.act, None, obs),
+                                        "members one by one, again": lambda m=mixes[False]: m.write(env, env.act, None, obs)}, {"S": S_}))
+    for _, legs, _ in shapes:      # every shape warm before the first measurement
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    for what, legs, kw in shapes:
+        alternate(what, legs, **kw)
+    assert env.take_status() & abi.DECODE_TRUNCATED == 0
+    sys.exit(0)
 
 
 @torch.no_grad()
