@@ -675,77 +675,66 @@ class BatchedCyberDefenseEnv:
           vec_out      optional [n, >= n_out] float32 (unit inner stride): row r receives encode_action of the merged tuple
                        (what the reference's replay buffer stores in this mode, :1424); columns past n_out stay untouched
         Limits: H1, H2 multiples of 16 in 16..128, n_types <= 32, top_k <= 8 (the library answers CYGYM_EUNSUPPORTED)."""
-        dst = self.actions_struct(act)
-        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
-        if not ok(h_state) or h_state.dim() != 2 or h_state.stride(1) != 1:
-            raise ValueError("h_state must be a [n, H1] float32 tensor on the batch's device with unit inner stride")
-        n, H1 = int(h_state.shape[0]), int(h_state.shape[1])
-        src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, 0.0)
-        w1a_t, w2, b2, w3, b3 = critic_pack
-        H2 = int(w3.numel())
-        if not ok(w1a_t) or tuple(w1a_t.shape) != (n_out, H1) or not w1a_t.is_contiguous():
-            raise ValueError(f"critic_pack: w1a_t must be a contiguous float32 {[n_out, H1]} tensor (fc1.weight[:, W:].t())")
-        if not ok(w3) or not w3.is_contiguous() or H2 < 1:
-            raise ValueError("critic_pack: w3 must be a contiguous float32 [H2] tensor")
-        if not ok(w2) or not w2.is_contiguous() or w2.numel() != ((H2 + 15) // 16) * ((H1 + 15) // 16) * 256:
-            raise ValueError("critic_pack: packed fc2 weights have the wrong size (see pack_linear)")
-        if b2 is not None and (not ok(b2) or not b2.is_contiguous() or b2.numel() != H2):
-            raise ValueError(f"critic_pack: b2 must hold {H2} float32 values")
-        cr = abi.Critic()
-        cr.h_state, cr.h_stride, cr.w1a_t, cr.w2, cr.w3 = h_state.data_ptr(), int(h_state.stride(0)), w1a_t.data_ptr(), w2.data_ptr(), w3.data_ptr()
-        cr.b2 = b2.data_ptr() if b2 is not None else None
-        cr.b3, cr.H1, cr.H2, cr.top_k, cr.tau = float(b3), H1, H2, int(top_k), float(tau)
-        for name, t, dt in (("pick_out", pick_out, torch.int16), ("q_out", q_out, torch.float32)):
-            if t is not None:
-                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n, self.M):
-                    raise ValueError(f"{name} must be a contiguous {dt} {[n, self.M]} tensor on {self.device}")
-                setattr(cr, name, t.data_ptr())
+        cr, _, src, dst, keep = self._coord_structs(rows, h_state, critic_pack, n_types, n_exploits, n_apps, type_map, act, top_k, tau,   # noqa: F841
+                                                    pick_out, q_out)
+        n, n_out = int(h_state.shape[0]), int(critic_pack[0].shape[0])
         cr.noise_std = float(noise_std)
         if vec_out is not None:
-            if not ok(vec_out) or vec_out.dim() != 2 or int(vec_out.shape[0]) != n or int(vec_out.shape[1]) < n_out or vec_out.stride(1) != 1 \
-                    or (n > 1 and vec_out.stride(0) < int(vec_out.shape[1])):
+            if vec_out.dtype != torch.float32 or vec_out.device != self.device or vec_out.dim() != 2 or int(vec_out.shape[0]) != n \
+                    or int(vec_out.shape[1]) < n_out or vec_out.stride(1) != 1 or (n > 1 and vec_out.stride(0) < int(vec_out.shape[1])):
                 raise ValueError(f"vec_out must be a float32 [{n}, >= {n_out}] tensor on {self.device} with unit inner stride")
             cr.vec_out, cr.vec_stride = vec_out.data_ptr(), int(vec_out.stride(0)) if n > 1 else int(vec_out.shape[1])
         _lib.check(self.lib.cygym_coord_ascent_decode(self._h, C.byref(cr), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_coord_ascent_decode")
 
-    def _coord_pop_structs(self, rows, h_state, slot_of_row, critic_pack, n_types, n_exploits, n_apps, type_map, act, top_k, tau, pick_out, q_out):
-        """Argument checks and marshalling of coord_ascent_decode_pop: (Critic, CriticPop, ActionVectors, Actions, tensors to keep)."""
+    def _coord_structs(self, rows, h_state, critic_pack, n_types, n_exploits, n_apps, type_map, act, top_k, tau, pick_out, q_out, slot_of_row=None):
+        """Argument checks and marshalling of coord_ascent_decode and, with `slot_of_row`, of coord_ascent_decode_pop (every tensor of the
+        pack then holds the S critics one after the other, b3s [S] in place of b3, h_state by source row or [S, n, H1]): (Critic,
+        CriticPop or None, ActionVectors, Actions, tensors to keep)."""
         dst = self.actions_struct(act)
+        pop = slot_of_row is not None
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
-        if not ok(h_state) or h_state.dim() not in (2, 3) or h_state.stride(-1) != 1:
-            raise ValueError("h_state must be a [n, H1] or [S, n, H1] float32 tensor on the batch's device with unit inner stride")
+        if not ok(h_state) or h_state.dim() not in ((2, 3) if pop else (2,)) or h_state.stride(-1) != 1:
+            raise ValueError(f"h_state must be a [n, H1]{' or [S, n, H1]' if pop else ''} float32 tensor on the batch's device with unit inner stride")
         n, H1 = int(h_state.shape[-2]), int(h_state.shape[-1])
         src, n_out, keep = _action_vectors(self, rows, n, n_types, n_exploits, n_apps, type_map, 0.0)
-        w1a_t, w2, b2, w3, b3s = critic_pack
-        if not ok(b3s) or b3s.dim() != 1 or not b3s.is_contiguous():
-            raise ValueError("critic_pack: b3s must be a contiguous float32 [S] tensor (fc3.bias of every critic)")
-        S_ = int(b3s.numel())
-        if not ok(w3) or not w3.is_contiguous() or w3.dim() != 2 or int(w3.shape[0]) != S_ or int(w3.shape[1]) < 1:
-            raise ValueError(f"critic_pack: w3 must be a contiguous float32 [{S_}, H2] tensor")
-        H2 = int(w3.shape[1])
-        if not ok(w1a_t) or tuple(w1a_t.shape) != (S_, n_out, H1) or not w1a_t.is_contiguous():
-            raise ValueError(f"critic_pack: w1a_t must be a contiguous float32 {[S_, n_out, H1]} tensor (fc1.weight[:, W:].t() of every critic)")
+        w1a_t, w2, b2, w3, b3 = critic_pack
+        S_ = 1
+        if pop:
+            if not ok(b3) or b3.dim() != 1 or not b3.is_contiguous():
+                raise ValueError("critic_pack: b3s must be a contiguous float32 [S] tensor (fc3.bias of every critic)")
+            S_ = int(b3.numel())
+        sh = lambda *d: "[" + ", ".join(str(x) for x in ((S_,) if pop else ()) + d) + "]"  # noqa: E731
+        every = " of every critic" if pop else ""
+        if not ok(w3) or not w3.is_contiguous() or (pop and (w3.dim() != 2 or int(w3.shape[0]) != S_)) or int(w3.numel()) < max(S_, 1):
+            raise ValueError(f"critic_pack: w3 must be a contiguous float32 {sh('H2')} tensor")
+        H2 = int(w3.numel()) // max(S_, 1)
+        if not ok(w1a_t) or tuple(w1a_t.shape) != ((S_,) if pop else ()) + (n_out, H1) or not w1a_t.is_contiguous():
+            raise ValueError(f"critic_pack: w1a_t must be a contiguous float32 {sh(n_out, H1)} tensor (fc1.weight[:, W:].t(){every})")
         if not ok(w2) or not w2.is_contiguous() or w2.numel() != S_ * ((H2 + 15) // 16) * ((H1 + 15) // 16) * 256:
-            raise ValueError("critic_pack: packed fc2 weights have the wrong size (pack_linear of every critic, critic after critic)")
+            raise ValueError(f"critic_pack: packed fc2 weights have the wrong size ({'pack_linear' + every + ', critic after critic' if pop else 'see pack_linear'})")
         if b2 is not None and (not ok(b2) or not b2.is_contiguous() or b2.numel() != S_ * H2):
             raise ValueError(f"critic_pack: b2 must hold {S_ * H2} float32 values")
-        if h_state.dim() == 3 and (int(h_state.shape[0]) != S_ or (n > 1 and h_state.stride(0) < (n - 1) * h_state.stride(1) + H1)):
-            raise ValueError(f"h_state [S, n, H1] must hold one block per critic ({S_}), block after block")
-        slot_of_row = _exactly(n, slot_of_row, torch.int32, self.device, "slot_of_row")
-        keep.append(slot_of_row)
-        cr, pop = abi.Critic(), abi.CriticPop()
-        cr.h_state, cr.h_stride = h_state.data_ptr(), int(h_state.stride(-2)) if n > 1 else H1
+        cr, cp = abi.Critic(), None
+        cr.h_state, cr.h_stride = h_state.data_ptr(), int(h_state.stride(-2)) if (n > 1 or not pop) else H1
         cr.w1a_t, cr.w2, cr.w3, cr.b2 = w1a_t.data_ptr(), w2.data_ptr(), w3.data_ptr(), (b2.data_ptr() if b2 is not None else None)
         cr.H1, cr.H2, cr.top_k, cr.tau = H1, H2, int(top_k), float(tau)
-        pop.slot_of_row, pop.b3s, pop.n_slots = slot_of_row.data_ptr(), b3s.data_ptr(), S_
-        pop.h_group_stride = (int(h_state.stride(0)) if S_ > 1 else n * cr.h_stride) if h_state.dim() == 3 else 0
+        if pop:
+            if h_state.dim() == 3 and (int(h_state.shape[0]) != S_ or (n > 1 and h_state.stride(0) < (n - 1) * h_state.stride(1) + H1)):
+                raise ValueError(f"h_state [S, n, H1] must hold one block per critic ({S_}), block after block")
+            slot_of_row = _exactly(n, slot_of_row, torch.int32, self.device, "slot_of_row")
+            keep.append(slot_of_row)
+            cp = abi.CriticPop()
+            cp.slot_of_row, cp.b3s, cp.n_slots = slot_of_row.data_ptr(), b3.data_ptr(), S_
+            cp.h_group_stride = (int(h_state.stride(0)) if S_ > 1 else n * cr.h_stride) if h_state.dim() == 3 else 0
+        else:
+            cr.b3 = float(b3)
         for name, t, dt in (("pick_out", pick_out, torch.int16), ("q_out", q_out, torch.float32)):
             if t is not None:
                 if t.dtype != dt or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n, self.M):
                     raise ValueError(f"{name} must be a contiguous {dt} {[n, self.M]} tensor on {self.device}")
                 setattr(cr, name, t.data_ptr())
-        return cr, pop, src, dst, keep
+        return cr, cp, src, dst, keep
 
     def coord_ascent_decode_pop(self, rows, h_state: torch.Tensor, slot_of_row: torch.Tensor, critic_pack, n_types: int,
                                 n_exploits: int | None = None, n_apps: int = 0, type_map=None, act=None, top_k: int = 5, tau: float = 0.5,
@@ -760,10 +749,18 @@ class BatchedCyberDefenseEnv:
                         w3 [S, H2], b3s [S]) -- policies.CoordAscentPolicyGroup stacks them
           top_k, tau   common to the population (the oracle's coord_K, coord_tau)
         There is no noise_std / vec_out: a critic in training decides through coord_ascent_decode."""
-        cr, pop, src, dst, keep = self._coord_pop_structs(rows, h_state, slot_of_row, critic_pack, n_types, n_exploits, n_apps, type_map, act,
+        cr, pop, src, dst, keep = self._coord_pop_structs(rows, h_state, slot_of_row, critic_pack, n_types, n_exploits, n_apps, type_map, act,   # noqa: F841
                                                           top_k, tau, pick_out, q_out)
         _lib.check(self.lib.cygym_coord_ascent_decode_pop(self._h, C.byref(cr), C.byref(pop), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_coord_ascent_decode_pop")
+
+    def _coord_pop_structs(self, rows, h_state, slot_of_row, critic_pack, n_types, n_exploits, n_apps, type_map, act, top_k, tau, pick_out, q_out):
+        """_coord_structs in its population form (the tests mutate what it returns): (Critic, CriticPop, ActionVectors, Actions, tensors
+        to keep)."""
+        if slot_of_row is None:
+            raise ValueError("slot_of_row must be an int32 tensor: the critic of every source row")
+        return self._coord_structs(rows, h_state, critic_pack, n_types, n_exploits, n_apps, type_map, act, top_k, tau, pick_out, q_out,
+                                   slot_of_row=slot_of_row)
 
     def committee_decode(self, rows, obs: torch.Tensor, h_state: torch.Tensor, hidden_layers, head, critic_pack, n_experts: int, n_types: int,
                          n_exploits: int | None = None, n_apps: int = 0, type_map=None, act=None, epsilon: float = 0.0, tanh: bool = True,
@@ -1039,13 +1036,64 @@ class BatchedCyberDefenseEnv:
                        exp_logits_out [n, E], app_logits_out [n, A] likewise
         Returns (types [n, M] uint8 -- 0 where invisible --, exploit [n] int32, app [n] int32, logp [n] float32, value [n] float32).
         Limits: H a multiple of 16 in 16..128, K, E, A <= 32, E >= 1 (the library answers CYGYM_EUNSUPPORTED / CYGYM_EINVAL)."""
+        net, _, src, dst, outs, keep = self._comm_structs(rows, tok_base, pack, role, noop, single_types, greedy, act, logits_out,   # noqa: F841
+                                                          exp_logits_out, app_logits_out)
+        if _gat is not None:   # (comm_gat_decode: the same marshalling, the launch with the attention layers)
+            _lib.check(self.lib.cygym_comm_gat_decode(self._h, C.byref(net), C.byref(_gat), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_gat_decode")
+        else:
+            _lib.check(self.lib.cygym_comm_actor_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_actor_decode")
+        return outs
+
+    def _tiled_rows(self, rows_tiled, tile_slot) -> int:
+        """The row list and the slot table of a population decode that gives a workgroup a tile of 16 rows: contiguous 1-d int32
+        tensors on the device, 16 rows per tile.  Returns the number of source rows, 16 T."""
+        for name, t in (("rows_tiled", rows_tiled), ("tile_slot", tile_slot)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError(f"{name} must be a contiguous 1-d int32 tensor on {self.device}")
+        T = int(tile_slot.numel())
+        if int(rows_tiled.numel()) != 16 * T:
+            raise ValueError(f"rows_tiled must hold 16 entries per tile: {16 * T} for the {T} tiles of tile_slot (it has {int(rows_tiled.numel())})")
+        return 16 * T
+
+    def _pop_first_layer(self, x, name: str, width: str, n: int, S_: int, wider: bool = False):
+        """The first-layer operand of such a decode in either form: by source row, [16 T, w], or [S, N, w] -- block s formed with net s
+        for every env, block after block.  wider: a row may hold more than the kernel reads (w >= `width`), so rows must not overlap
+        either.  Returns (row stride, group stride: 0 by source row)."""
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != self.device or x.dim() not in (2, 3) or x.stride(-1) != 1:
+            raise ValueError(f"{name} must be a [16 T, {width}] or [S, N, {width}] float32 tensor on the batch's device with unit inner stride")
+        w, nb = int(x.shape[-1]), int(x.shape[-2])
+        row_stride = int(x.stride(-2)) if nb > 1 else w
+        if x.dim() == 2:
+            if nb != n:
+                raise ValueError(f"{name} by source row must hold one row per entry of rows_tiled ({n}), it has {nb}")
+            return row_stride, 0
+        one_block = (nb - 1) * (x.stride(1) if nb > 1 else 0) + w
+        if int(x.shape[0]) != S_ or nb != self.N or (wider and nb > 1 and x.stride(1) < w) or (S_ > 1 and (wider or nb > 1) and x.stride(0) < one_block):
+            raise ValueError(f"{name} [S, N, {width}] must hold one block of all {self.N} envs per net ({S_}), block after block")
+        return row_stride, int(x.stride(0)) if S_ > 1 else nb * row_stride
+
+    def _comm_structs(self, rows, tok_base, pack, role, noop, single_types, greedy, act, logits_out, exp_logits_out, app_logits_out, tile_slot=None):
+        """Argument checks and marshalling of comm_actor_decode, comm_gat_decode and, with `tile_slot`, of comm_actor_decode_pop (`rows`
+        tiled, every tensor of `pack` stacked over the S nets, b_v2s [S] in place of b_v2, tok_base by source row or [S, N, H]):
+        (CommActor, CommActorPop or None, DeviceLogits, Actions, the five result tensors, tensors to keep)."""
         dst = self.actions_struct(act)
         src = abi.DeviceLogits()
         self._group_rule(src, role, noop, single_types)
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
-        if not ok(tok_base) or tok_base.dim() != 2 or tok_base.stride(1) != 1:
-            raise ValueError("tok_base must be a [n, H] float32 tensor on the batch's device with unit inner stride")
-        n, H = int(tok_base.shape[0]), int(tok_base.shape[1])
+        pop, S_ = None, 1
+        if tile_slot is not None:
+            n = self._tiled_rows(rows, tile_slot)
+            b_v2s = pack["b_v2s"]
+            if not ok(b_v2s) or b_v2s.dim() != 1 or not b_v2s.is_contiguous() or int(b_v2s.numel()) < 1:
+                raise ValueError("pack['b_v2s'] must be a contiguous float32 [S] tensor (v_head.2.bias of every net)")
+            S_ = int(b_v2s.numel())
+            row_stride, group_stride = self._pop_first_layer(tok_base, "tok_base", "H", n, S_)
+        else:
+            if not ok(tok_base) or tok_base.dim() != 2 or tok_base.stride(1) != 1:
+                raise ValueError("tok_base must be a [n, H] float32 tensor on the batch's device with unit inner stride")
+            n = int(tok_base.shape[0])
+            row_stride = int(tok_base.stride(0)) if n > 1 else int(tok_base.shape[1])
+        H = int(tok_base.shape[-1])
         K, E, A = int(pack["K"]), int(pack["E"]), int(pack["A"])
         sizes = {"tok_dev": self.M * H, "w_type": (K + 15) // 16 * 16 * H, "b_type": K, "w_ctx": (E + A + H + 15) // 16 * 16 * H,
                  "b_ctx": E + A + H, "w_v2": H}
@@ -1054,73 +1102,12 @@ class BatchedCyberDefenseEnv:
         net = abi.CommActor()
         for name, want in sizes.items():
             t = pack[name]
-            if not ok(t) or not t.is_contiguous() or (want >= 0 and int(t.numel()) != want):
-                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device} (CommActorCritic.packed)")
-            setattr(net, name, t.data_ptr())
-        net.tok_base, net.tok_stride, net.H, net.b_v2 = tok_base.data_ptr(), int(tok_base.stride(0)) if n > 1 else H, H, float(pack["b_v2"])
-        types = torch.empty((n, self.M), dtype=torch.uint8, device=self.device)
-        exp_o = torch.empty((n,), dtype=torch.int32, device=self.device)
-        app_o = torch.empty((n,), dtype=torch.int32, device=self.device)
-        logp = torch.empty((n,), dtype=torch.float32, device=self.device)
-        value = torch.empty((n,), dtype=torch.float32, device=self.device)
-        src.types_out, src.exp_out, src.app_out, src.logp_out, net.value_out = (t.data_ptr() for t in (types, exp_o, app_o, logp, value))
-        src.n_types, src.n_exp, src.n_app, src.greedy = K, E, A, int(bool(greedy))
-        for name, t, shape in (("logits_out", logits_out, (n, self.M, K)), ("exp_logits_out", exp_logits_out, (n, E)), ("app_logits_out", app_logits_out, (n, A))):
-            if t is not None:
-                if not ok(t) or not t.is_contiguous() or tuple(t.shape) != shape:
-                    raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {self.device}")
-                setattr(net, name, t.data_ptr())
-        r = _bind_rows(self, src, rows, n)   # noqa: F841 (alive until the call has returned)
-        if _gat is not None:   # (comm_gat_decode: the same marshalling, the launch with the attention layers)
-            _lib.check(self.lib.cygym_comm_gat_decode(self._h, C.byref(net), C.byref(_gat), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_gat_decode")
-            return types, exp_o, app_o, logp, value
-        _lib.check(self.lib.cygym_comm_actor_decode(self._h, C.byref(net), C.byref(src), C.byref(dst), self._stream()), self._h, "cygym_comm_actor_decode")
-        return types, exp_o, app_o, logp, value
-
-    def _comm_pop_structs(self, rows_tiled, tile_slot, tok_base, pack, role, noop, single_types, greedy, act, logits_out, exp_logits_out,
-                          app_logits_out):
-        """Argument checks and marshalling of comm_actor_decode_pop: (CommActor, CommActorPop, DeviceLogits, Actions, the five result
-        tensors, tensors to keep)."""
-        dst = self.actions_struct(act)
-        src = abi.DeviceLogits()
-        self._group_rule(src, role, noop, single_types)
-        ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
-        for name, t in (("rows_tiled", rows_tiled), ("tile_slot", tile_slot)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or t.dim() != 1:
-                raise ValueError(f"{name} must be a contiguous 1-d int32 tensor on {self.device}")
-        T = int(tile_slot.numel())
-        n = 16 * T
-        if int(rows_tiled.numel()) != n:
-            raise ValueError(f"rows_tiled must hold 16 entries per tile: {n} for the {T} tiles of tile_slot (it has {int(rows_tiled.numel())})")
-        b_v2s = pack["b_v2s"]
-        if not ok(b_v2s) or b_v2s.dim() != 1 or not b_v2s.is_contiguous() or int(b_v2s.numel()) < 1:
-            raise ValueError("pack['b_v2s'] must be a contiguous float32 [S] tensor (v_head.2.bias of every net)")
-        S_ = int(b_v2s.numel())
-        if not ok(tok_base) or tok_base.dim() not in (2, 3) or tok_base.stride(-1) != 1:
-            raise ValueError("tok_base must be a [16 T, H] or [S, N, H] float32 tensor on the batch's device with unit inner stride")
-        H = int(tok_base.shape[-1])
-        nb = int(tok_base.shape[-2])
-        if tok_base.dim() == 2 and nb != n:
-            raise ValueError(f"tok_base by source row must hold one row per entry of rows_tiled ({n}), it has {nb}")
-        if tok_base.dim() == 3 and (int(tok_base.shape[0]) != S_ or nb != self.N or
-                                    (nb > 1 and S_ > 1 and tok_base.stride(0) < (nb - 1) * tok_base.stride(1) + H)):
-            raise ValueError(f"tok_base [S, N, H] must hold one block of all {self.N} envs per net ({S_}), block after block")
-        K, E, A = int(pack["K"]), int(pack["E"]), int(pack["A"])
-        sizes = {"tok_dev": self.M * H, "w_type": (K + 15) // 16 * 16 * H, "b_type": K, "w_ctx": (E + A + H + 15) // 16 * 16 * H,
-                 "b_ctx": E + A + H, "w_v2": H}
-        if H % 16:
-            sizes["w_type"] = sizes["w_ctx"] = -1   # (the library refuses such an H anyway)
-        net, pop = abi.CommActor(), abi.CommActorPop()
-        for name, want in sizes.items():
-            t = pack[name]
             if not ok(t) or not t.is_contiguous() or (want >= 0 and int(t.numel()) != S_ * want):
                 raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {S_} x {want} values on {self.device} "
-                                 "(CommActorPolicyGroup stacks the members' packs)")
+                                 "(CommActorPolicyGroup stacks the members' packs)" if tile_slot is not None else
+                                 f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device} (CommActorCritic.packed)")
             setattr(net, name, t.data_ptr())
-        row_stride = int(tok_base.stride(-2)) if nb > 1 else H
         net.tok_base, net.tok_stride, net.H = tok_base.data_ptr(), row_stride, H
-        pop.tile_slot, pop.b_v2s, pop.n_slots, pop.n_tiles = tile_slot.data_ptr(), b_v2s.data_ptr(), S_, T
-        pop.tok_group_stride = (int(tok_base.stride(0)) if S_ > 1 else nb * row_stride) if tok_base.dim() == 3 else 0
         outs = (torch.empty((n, self.M), dtype=torch.uint8, device=self.device), torch.empty((n,), dtype=torch.int32, device=self.device),
                 torch.empty((n,), dtype=torch.int32, device=self.device), torch.empty((n,), dtype=torch.float32, device=self.device),
                 torch.empty((n,), dtype=torch.float32, device=self.device))
@@ -1131,8 +1118,13 @@ class BatchedCyberDefenseEnv:
                 if not ok(t) or not t.is_contiguous() or tuple(t.shape) != shape:
                     raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {self.device}")
                 setattr(net, name, t.data_ptr())
-        src.n, src.rows = n, rows_tiled.data_ptr()
-        return net, pop, src, dst, outs, [rows_tiled, tile_slot, tok_base, b_v2s]
+        if tile_slot is None:
+            net.b_v2 = float(pack["b_v2"])
+            return net, None, src, dst, outs, [_bind_rows(self, src, rows, n)]
+        pop = abi.CommActorPop()
+        pop.tile_slot, pop.b_v2s, pop.n_slots, pop.n_tiles, pop.tok_group_stride = tile_slot.data_ptr(), b_v2s.data_ptr(), S_, n // 16, group_stride
+        src.n, src.rows = n, rows.data_ptr()
+        return net, pop, src, dst, outs, [rows, tile_slot, tok_base, b_v2s]
 
     def comm_actor_decode_pop(self, rows_tiled: torch.Tensor, tile_slot: torch.Tensor, tok_base: torch.Tensor, pack, role: str = "defender",
                               noop: int | None = None, single_types=(11, 12), greedy: bool = False, act=None, logits_out=None,
@@ -1154,6 +1146,15 @@ class BatchedCyberDefenseEnv:
         _lib.check(self.lib.cygym_comm_actor_decode_pop(self._h, C.byref(net), C.byref(pop), C.byref(src), C.byref(dst), self._stream()),
                    self._h, "cygym_comm_actor_decode_pop")
         return outs
+
+    def _comm_pop_structs(self, rows_tiled, tile_slot, tok_base, pack, role, noop, single_types, greedy, act, logits_out, exp_logits_out,
+                          app_logits_out):
+        """_comm_structs in its population form (the tests mutate what it returns): (CommActor, CommActorPop, DeviceLogits, Actions, the
+        five result tensors, tensors to keep)."""
+        if tile_slot is None:
+            raise ValueError("tile_slot must be a contiguous 1-d int32 tensor: the net of every tile")
+        return self._comm_structs(rows_tiled, tok_base, pack, role, noop, single_types, greedy, act, logits_out, exp_logits_out, app_logits_out,
+                                  tile_slot=tile_slot)
 
     def comm_gat_workspace(self, H: int):
         """The workspace cygym_comm_gat_decode needs on this batch for hidden width H (None when every row fits in LDS), allocated
@@ -1251,27 +1252,15 @@ class BatchedCyberDefenseEnv:
         H, T, P = int(pack["H"]), int(pack["T"]), int(pack["n_parts"])
         S_ = int(pack["S"]) if pop else 1
         if pop:
-            for name, t in (("rows_tiled", rows), ("tile_slot", tile_slot)):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or t.dim() != 1:
-                    raise ValueError(f"{name} must be a contiguous 1-d int32 tensor on {self.device}")
-            n = 16 * int(tile_slot.numel())
-            if int(rows.numel()) != n:
-                raise ValueError(f"rows_tiled must hold 16 entries per tile: {n} for the {n // 16} tiles of tile_slot (it has {int(rows.numel())})")
+            n = self._tiled_rows(rows, tile_slot)
             if S_ < 1:
                 raise ValueError("pack['S'] is the number of stacked nets, at least 1")
-            if not isinstance(h0, torch.Tensor) or not ok(h0) or h0.dim() not in (2, 3) or h0.stride(-1) != 1:
-                raise ValueError("h0 must be a [16 T, >= 3 H] or [S, N, >= 3 H] float32 tensor on the batch's device with unit inner stride")
-            nb = int(h0.shape[-2])
-            if h0.dim() == 2 and nb != n:
-                raise ValueError(f"h0 by source row must hold one row per entry of rows_tiled ({n}), it has {nb}")
-            if h0.dim() == 3 and (int(h0.shape[0]) != S_ or nb != self.N or
-                                  (nb > 1 and h0.stride(1) < int(h0.shape[2])) or
-                                  (S_ > 1 and h0.stride(0) < (nb - 1) * (h0.stride(1) if nb > 1 else 0) + int(h0.shape[2]))):
-                raise ValueError(f"h0 [S, N, >= 3 H] must hold one block of all {self.N} envs per net ({S_}), block after block")
+            row_stride, group_stride = self._pop_first_layer(h0, "h0", ">= 3 H", n, S_, wider=True)
         else:
             if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
                 raise ValueError("h0 must be a [n, >= 3 H] float32 tensor on the batch's device with unit inner stride")
-            n, nb = int(h0.shape[0]), int(h0.shape[0])
+            n = int(h0.shape[0])
+            row_stride = int(h0.stride(0)) if n > 1 else int(h0.shape[1])
         if int(h0.shape[-1]) < 3 * H:
             raise ValueError(f"h0 rows hold {int(h0.shape[-1])} floats: fewer than the three {H}-wide blocks")
         src, _, keep = _action_vectors(self, rows, n, T, 0, 0, type_map, 0.0)
@@ -1291,11 +1280,10 @@ class BatchedCyberDefenseEnv:
         if po.dtype != torch.uint8 or po.device != self.device or not po.is_contiguous() or int(po.numel()) != self.M:
             raise ValueError(f"pack['part_of'] must be a contiguous uint8 [{self.M}] tensor on {self.device}")
         net.part_of, net.n_parts, net.role, net.H = po.data_ptr(), P, _role(role)["code"], H
-        net.h0, net.h0_stride = h0.data_ptr(), int(h0.stride(-2)) if nb > 1 else int(h0.shape[-1])
+        net.h0, net.h0_stride = h0.data_ptr(), row_stride
         if pop:
             hp = abi.HierPop()
-            hp.tile_slot, hp.n_slots, hp.n_tiles = tile_slot.data_ptr(), S_, n // 16
-            hp.h0_group_stride = (int(h0.stride(0)) if S_ > 1 else nb * net.h0_stride) if h0.dim() == 3 else 0
+            hp.tile_slot, hp.n_slots, hp.n_tiles, hp.h0_group_stride = tile_slot.data_ptr(), S_, n // 16, group_stride
             keep += [tile_slot, h0]
             if vis_fixed is not None:
                 if not isinstance(vis_fixed, torch.Tensor) or vis_fixed.dtype != torch.uint8 or vis_fixed.device != self.device or \

@@ -984,17 +984,30 @@ int cygym_coord_ascent_decode(cygym_handle* h, const cygym_critic* c, const cygy
   return launch_decode(h, k, dim3(src->n), dim3(CA_THREADS), lds, stream, {c, src, dst});   // one workgroup per row
 }
 
+// What the *_decode_pop entry points check of their population struct alike, in the order a caller sees: 1 .. max_slots slots
+// (`slots_msg` names the limit), then the entry point's own EINVAL `also_bad` (NULL: none), then the tiled row list (n_tiles = -1:
+// the rows are not tiled), then the group stride: 0 (the first layer by source row) or at least one `block`.
+static int check_pop(cygym_handle* h, const char* who, int n_slots, int max_slots, const char* slots_msg, const char* also_bad,
+                     int64_t n_tiles, bool tiled, int64_t n, int64_t group_stride, int64_t block, const char* stride_msg) {
+  if (n_slots < 1 || n_slots > max_slots) return fail(h, CYGYM_EUNSUPPORTED, slots_msg, who);
+  if (also_bad) return fail(h, CYGYM_EINVAL, also_bad, who);
+  if (tiled && (n_tiles < 0 || n != 16 * n_tiles))
+    return fail(h, CYGYM_EINVAL, "%s: the row list holds 16 rows per tile (layout->n = 16 n_tiles)", who);
+  if (group_stride < 0 || (group_stride > 0 && group_stride < block)) return fail(h, CYGYM_EINVAL, stride_msg, who);
+  return CYGYM_OK;
+}
+
 int cygym_coord_ascent_decode_pop(cygym_handle* h, const cygym_critic* c, const cygym_critic_pop* pop, const cygym_action_vectors* src,
                                   const cygym_actions* dst, void* stream) {
   const char* const who = "cygym_coord_ascent_decode_pop";
   const char* const bad_layout = "cygym_coord_ascent_decode_pop: bad layout (types, exploits >= 1, the handle's device count, h_stride >= H1, top_k >= 1, tau > 0)%s";
   size_t lds = 0;
   if (const int rc = check_coord_ascent(h, c, src, dst, who, bad_layout, pop && pop->slot_of_row && pop->b3s, &lds)) return rc;
-  if (pop->n_slots < 1 || pop->n_slots > CG_CRITIC_POP_MAX) return fail(h, CYGYM_EUNSUPPORTED, "%s: 1 to CG_CRITIC_POP_MAX critics", who);
-  if (c->noise_std != 0.0 || c->vec_out)
-    return fail(h, CYGYM_EINVAL, "%s: eval mode only (noise_std = 0, no vec_out): a critic in training decides through cygym_coord_ascent_decode", who);
-  if (pop->h_group_stride < 0 || (pop->h_group_stride > 0 && src->n > 0 && pop->h_group_stride < (int64_t)(src->n - 1) * c->h_stride + c->H1))
-    return fail(h, CYGYM_EINVAL, "%s: h_group_stride is 0 (h_state by source row) or at least one block, (n - 1) h_stride + H1", who);
+  const char* const training = (c->noise_std != 0.0 || c->vec_out)
+      ? "%s: eval mode only (noise_std = 0, no vec_out): a critic in training decides through cygym_coord_ascent_decode" : nullptr;
+  if (const int rc = check_pop(h, who, pop->n_slots, CG_CRITIC_POP_MAX, "%s: 1 to CG_CRITIC_POP_MAX critics", training, 0, false, src->n,
+                               pop->h_group_stride, src->n > 0 ? (int64_t)(src->n - 1) * c->h_stride + c->H1 : 0,
+                               "%s: h_group_stride is 0 (h_state by source row) or at least one block, (n - 1) h_stride + H1")) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   const void* k = c->top_k > 1 ? (const void*)coord_pop_kernel<true> : (const void*)coord_pop_kernel<false>;
@@ -1136,11 +1149,9 @@ int cygym_comm_actor_decode_pop(cygym_handle* h, const cygym_comm_actor* net, co
   const char* const bad_layout = "cygym_comm_actor_decode_pop: bad layout (types, exploit logits >= 1, tok_stride >= H, role 1 or 2, 16-byte aligned tok_dev / w_type / w_ctx)%s";
   size_t lds = 0;
   if (const int rc = check_comm_actor(h, net, src, dst, who, bad_layout, pop && pop->tile_slot && pop->b_v2s && src && src->rows, &lds)) return rc;
-  if (pop->n_slots < 1 || pop->n_slots > CG_COMM_POP_MAX) return fail(h, CYGYM_EUNSUPPORTED, "%s: 1 to CG_COMM_POP_MAX nets", who);
-  if (pop->n_tiles < 0 || (int64_t)src->n != 16 * (int64_t)pop->n_tiles)
-    return fail(h, CYGYM_EINVAL, "%s: the row list holds 16 rows per tile (layout->n = 16 n_tiles)", who);
-  if (pop->tok_group_stride < 0 || (pop->tok_group_stride > 0 && pop->tok_group_stride < (int64_t)(h->n_envs - 1) * net->tok_stride + net->H))
-    return fail(h, CYGYM_EINVAL, "%s: tok_group_stride is 0 (tok_base by source row) or at least one block, (n_envs - 1) tok_stride + H", who);
+  if (const int rc = check_pop(h, who, pop->n_slots, CG_COMM_POP_MAX, "%s: 1 to CG_COMM_POP_MAX nets", nullptr, pop->n_tiles, true, src->n,
+                               pop->tok_group_stride, (int64_t)(h->n_envs - 1) * net->tok_stride + net->H,
+                               "%s: tok_group_stride is 0 (tok_base by source row) or at least one block, (n_envs - 1) tok_stride + H")) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the per-row buffers do not fit in LDS", who);
@@ -1277,11 +1288,9 @@ int cygym_hier_decode_pop(cygym_handle* h, const cygym_hier_net* net, const cygy
   size_t lds = 0;
   if (const int rc = check_hier(h, net, false, src, dst, who, bad_layout, pop && pop->tile_slot && src && src->rows, pop && pop->vis_fixeds, &lds))
     return rc;
-  if (pop->n_slots < 1 || pop->n_slots > CG_HIER_POP_MAX) return fail(h, CYGYM_EUNSUPPORTED, "%s: 1 to CG_HIER_POP_MAX nets", who);
-  if (pop->n_tiles < 0 || (int64_t)src->n != 16 * (int64_t)pop->n_tiles)
-    return fail(h, CYGYM_EINVAL, "%s: the row list holds 16 rows per tile (layout->n = 16 n_tiles)", who);
-  if (pop->h0_group_stride < 0 || (pop->h0_group_stride > 0 && pop->h0_group_stride < (int64_t)(h->n_envs - 1) * net->h0_stride + 3ll * net->H))
-    return fail(h, CYGYM_EINVAL, "%s: h0_group_stride is 0 (h0 by source row) or at least one block, (n_envs - 1) h0_stride + 3 H", who);
+  if (const int rc = check_pop(h, who, pop->n_slots, CG_HIER_POP_MAX, "%s: 1 to CG_HIER_POP_MAX nets", nullptr, pop->n_tiles, true, src->n,
+                               pop->h0_group_stride, (int64_t)(h->n_envs - 1) * net->h0_stride + 3ll * net->H,
+                               "%s: h0_group_stride is 0 (h0 by source row) or at least one block, (n_envs - 1) h0_stride + 3 H")) return rc;
   if (src->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
   if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the tiles do not fit in LDS", who);

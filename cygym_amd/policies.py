@@ -594,7 +594,119 @@ class CoordAscentPolicy:
         return {"atype": at, "exploit": ex.to(torch.int32), "dev_mask": on, "app": torch.zeros_like(at)}
 
 
-class CoordAscentPolicyGroup:
+class _PolicyPopulation:
+    """What the populations of same-shaped strategies decided in ONE launch per turn share: the member list (1 to 32), the rows of
+    every member (`counts`) when the rows arrive ordered member after member, and the stacked pack, kept until a member's own pack
+    version changes (_cached).  rollout_grid plans them (its _group_* steps) and MixturePolicy finds them among its members by `key`.
+    A new family writes four things:
+      key(p, M)   static: what must agree across the members, as a hashable value, or None when `p` cannot be a member;
+      _stacked    the members' packs slot after slot, through _cached(version, build);
+      the first-layer op on [S, n, W] observations -- one batched GEMM (or two) on the stacked operands;
+      the launch  of its batch.*_decode_pop.
+    A family whose kernel gives a workgroup a tile of 16 rows of one net derives from _TiledPopulation, which owns the row
+    conventions, and writes the last two as _first_layer and _launch."""
+
+    tick_free = True
+    NOUN = "nets"      # what the members are called when there are too many of them
+
+    def __init__(self, policies, counts=None):
+        self.policies = list(policies)
+        if not 1 <= len(self.policies) <= 32:
+            raise ValueError(f"1 to 32 {self.NOUN}")
+        self.counts = None if counts is None else [int(c) for c in counts]
+        if self.counts is not None and len(self.counts) != len(self.policies):
+            raise ValueError("counts: one row count per member")
+        self._pk = self._pk_ver = None
+
+    def _cached(self, ver, build):
+        """The stacked pack of version `ver` (the tuple of the members' pack versions, read AFTER their packs were asked for): build()
+        when it differs from the kept one's."""
+        if self._pk_ver != ver:
+            self._pk, self._pk_ver = build(), ver
+        return self._pk
+
+    def _check_counts(self, n, rows_ok=True):
+        if self.counts is None or sum(self.counts) != n or not rows_ok:
+            raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
+
+
+class _TiledPopulation(_PolicyPopulation):
+    """A population whose decode gives a workgroup a tile of 16 rows of ONE net, the net of a tile taken from a slot table.
+    counts: the rows of every member when the rows arrive ordered member after member (any counts, equal or not, multiples of 16 or
+    not).  Every member's segment is padded to the same number of tiles (tile_plan), so that the padded observations are one
+    [S, 16 Tm, W] operand; the tiles past a member's rows carry slot -1 and cost nothing.  in_tile_order: the caller's rows and
+    observations are ALREADY in that padded order (rollout_grid builds its gather that way, once, at plan time): write() then gathers
+    nothing.  Without counts write() takes the caller's tiles (shared_obs).
+    A subclass sets MIN_MEMBERS (the smallest population worth grouping: measured), state_dim and n_devices (what obs and the batch
+    must have) and writes
+      _stacked(batch=None, device=None)                        the stacked pack, a dict
+      _first_layer(obs_s, pack)                                [S, n, w] from obs_s [S, n, W] (or an expanded [n, W])
+      _launch(batch, act, rows, tile_slot, x, pack, **outs)    its batch.*_decode_pop on the first layer's result x."""
+
+    def __init__(self, policies, counts=None, in_tile_order: bool = False):
+        super().__init__(policies, counts)
+        self.in_tile_order = bool(in_tile_order)
+        self._tiles = None
+
+    @staticmethod
+    def tile_plan(counts):
+        """The padded tile order of rows that come member after member, as numpy: (pos [S 16 Tm] int64 -- the position in the
+        member-after-member order of every padded row, 0 on the padding --, valid [S 16 Tm] bool, tile_slot [S Tm] int32) with Tm =
+        the tiles of the longest member (at least 1).  Member s owns padded rows s 16 Tm ..: its rows in order, then padding; its
+        tiles without a row carry slot -1.  mixture_rows_np's layout with every slot's segment at a fixed place."""
+        import numpy as np
+        counts = np.asarray(counts, np.int64)
+        S_, Tm = counts.size, max(1, int((counts.max() + 15) // 16))
+        j = np.arange(16 * Tm)[None, :]
+        valid = j < counts[:, None]
+        start = np.concatenate([[0], np.cumsum(counts)[:-1]])
+        pos = np.where(valid, start[:, None] + j, 0).astype(np.int64).reshape(-1)
+        tile_slot = np.where(np.arange(Tm)[None, :] * 16 < counts[:, None], np.arange(S_)[:, None], -1).astype(np.int32).reshape(-1)
+        return pos, valid.reshape(-1), tile_slot
+
+    def _tile_tensors(self, device):
+        if self._tiles is None or self._tiles[0].device != device:
+            pos, valid, tile_slot = self.tile_plan(self.counts)
+            self._tiles = (torch.from_numpy(pos).to(device), torch.from_numpy(valid).to(device), torch.from_numpy(tile_slot).to(device),
+                           bool(valid.all()))
+        return self._tiles
+
+    @torch.no_grad()
+    def write(self, batch, act, rows, obs, tile_slot=None, shared_obs=False, **outs):
+        """The first layer as batched GEMMs, then ONE decode launch for all members; returns what the family's decode_pop returns, its
+        optional outputs (by keyword) by source row, in tile order.
+        Default: `rows` / `obs` [n, W] hold the members' rows member after member (counts); they are gathered once into the padded
+        tile order (not at all when in_tile_order, or when every count is the same multiple of 16) and the first layer is formed per
+        source row.  shared_obs: `rows` [16 T] and tile_slot [T] are the caller's tiles, made on the device (the draw of a mixture), obs
+        [N, W] holds every env once: the first layer is [S, N, w] and the kernel reads the block of the tile's slot."""
+        S_, W = len(self.policies), self.state_dim
+        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != W:
+            raise ValueError(f"obs must be a float32 [n, {W}] role view")
+        if batch.M != self.n_devices:
+            raise ValueError(f"the nets were built for {self.n_devices} devices, the batch has {batch.M}")
+        pack = self._stacked(batch, obs.device)
+        if shared_obs:
+            if tile_slot is None or rows is None:
+                raise ValueError("shared_obs: the caller says which tile plays whom (rows = rows_tiled, tile_slot)")
+            x = self._first_layer(obs[None].expand(S_, int(obs.shape[0]), W), pack)
+        else:
+            if self.counts is None:
+                raise ValueError("rows ordered member after member need counts")
+            pos, valid, tile_slot, dense = self._tile_tensors(obs.device)
+            n, n_pad = int(obs.shape[0]), int(pos.numel())
+            if self.in_tile_order or (dense and n == n_pad):
+                if n != n_pad or rows is None or int(rows.numel()) != n_pad:
+                    raise ValueError(f"rows in tile order: {n_pad} padded rows (tile_plan)")
+            else:
+                self._check_counts(n, rows is not None and int(rows.numel()) == n)
+                obs = obs.index_select(0, pos)
+                rows = torch.where(valid, rows.index_select(0, pos), torch.full_like(rows[:1], -1))
+            x = self._first_layer(obs.reshape(S_, n_pad // S_, W), pack)
+            x = x.reshape(n_pad, int(x.shape[2]))
+        return self._launch(batch, act, rows, tile_slot, x, pack, **outs)
+
+
+class CoordAscentPolicyGroup(_PolicyPopulation):
     """A population of CoordAscentPolicy strategies of ONE shape in eval mode (key) decided together: the state parts of fc1 are one
     batched GEMM and the decode + scatter of all of them is ONE launch (cygym_coord_ascent_decode_pop), the critic of a source row
     taken from a slot table.  The decode runs a workgroup per row, so a launch per strategy over that strategy's few rows leaves most
@@ -604,19 +716,14 @@ class CoordAscentPolicyGroup:
     or not) -- the slot table is then made once, and h_state is formed per source row.  Without counts write() takes the caller's
     slot table."""
 
-    tick_free = True
+    NOUN = "critics"
 
     def __init__(self, policies, counts=None):
-        self.policies = list(policies)
+        super().__init__(policies, counts)
         p0 = self.policies[0]
-        if not 1 <= len(self.policies) <= 32:
-            raise ValueError("1 to 32 critics")
         self.n_types, self.n_exploits, self.n_apps, self.top_k, self.tau = p0.n_types, p0.n_exploits, p0.n_apps, p0.top_k, p0.tau
         self.action_types = sorted({t for p in self.policies for t in p.action_types})
-        self.counts = None if counts is None else [int(c) for c in counts]
-        if self.counts is not None and len(self.counts) != len(self.policies):
-            raise ValueError("counts: one row count per member")
-        self._pk = self._pk_ver = self._slots = None
+        self._slots = None
 
     @staticmethod
     def key(p, M):
@@ -637,15 +744,14 @@ class CoordAscentPolicyGroup:
         """(w1s_t [S, W, H1], b1 [S, 1, H1], critic pack of coord_ascent_decode_pop): the members' packs slot after slot, redone when a
         member's parameter changes (the members' own _packed versions)."""
         packs = [p._packed(batch, batch.M) for p in self.policies]
-        ver = tuple(p._pk_ver for p in self.policies)
-        if self._pk_ver != ver:
+
+        def build():
             b2s = [pk[2][2] for pk in packs]
-            self._pk = (torch.stack([pk[0] for pk in packs]).contiguous(), torch.stack([pk[1] for pk in packs])[:, None, :].contiguous(),
-                        (torch.stack([pk[2][0] for pk in packs]).contiguous(), torch.cat([pk[2][1].reshape(-1) for pk in packs]).contiguous(),
-                         None if b2s[0] is None else torch.stack(b2s).contiguous(), torch.stack([pk[2][3] for pk in packs]).contiguous(),
-                         torch.cat([p.fc3.bias.detach().reshape(1) for p in self.policies]).contiguous()))      # (b3s: no host read)
-            self._pk_ver = ver
-        return self._pk
+            return (torch.stack([pk[0] for pk in packs]).contiguous(), torch.stack([pk[1] for pk in packs])[:, None, :].contiguous(),
+                    (torch.stack([pk[2][0] for pk in packs]).contiguous(), torch.cat([pk[2][1].reshape(-1) for pk in packs]).contiguous(),
+                     None if b2s[0] is None else torch.stack(b2s).contiguous(), torch.stack([pk[2][3] for pk in packs]).contiguous(),
+                     torch.cat([p.fc3.bias.detach().reshape(1) for p in self.policies]).contiguous()))      # (b3s: no host read)
+        return self._cached(tuple(p._pk_ver for p in self.policies), build)
 
     def slot_table(self, device):
         """[sum(counts)] int32: the member of every source row when the rows come member after member."""
@@ -669,8 +775,7 @@ class CoordAscentPolicyGroup:
                 raise ValueError("shared_obs: the caller says which row plays whom (slot_of_row)")
             h_state = torch.baddbmm(b1, obs[None].expand(S_, n, W), w1s_t)
         else:
-            if self.counts is None or sum(self.counts) != n:
-                raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
+            self._check_counts(n)
             if slot_of_row is None:
                 slot_of_row = self.slot_table(obs.device)
             if len(set(self.counts)) == 1:
@@ -687,8 +792,7 @@ class CoordAscentPolicyGroup:
     @torch.no_grad()
     def __call__(self, obs, t, M, L):
         """The members' own torch decode on their slices (batch-likes without the library; top_k = 1 only, as CoordAscentPolicy)."""
-        if self.counts is None or sum(self.counts) != int(obs.shape[0]):
-            raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
+        self._check_counts(int(obs.shape[0]))
         outs, lo = [], 0
         for p, c in zip(self.policies, self.counts):
             if c:
@@ -1596,36 +1700,26 @@ class CommActorPolicy:
                                   "carry them (it runs through write(), on a batch with cygym_comm_actor_decode)")
 
 
-class CommActorPolicyGroup:
+class CommActorPolicyGroup(_TiledPopulation):
     """A population of CommActorPolicy strategies of ONE shape without attention layers (key) decided together: tok_base of all of
     them is two batched GEMMs and the decode + grouping of all of them is ONE launch (cygym_comm_actor_decode_pop), the net of a tile
     of 16 rows taken from a slot table.  The decode gives a workgroup 16 rows, so a launch per strategy over that strategy's few rows
     leaves most of the chip idle; the |D| x |A| grid of a Double-Oracle population with --BR_type ippo / mappo and the opponent drawn
     per env from an equilibrium (MixturePolicy) hold several such nets, each deciding for a few envs.
-    counts: the rows of every member when the rows arrive ordered member after member (any counts, equal or not, multiples of 16 or
-    not).  Every member's segment is padded to the same number of tiles (tile_plan), so that the padded observations are one
-    [S, 16 Tm, W] operand; the tiles past a member's rows carry slot -1 and cost nothing.  in_tile_order: the caller's rows and
-    observations are ALREADY in that padded order (rollout_grid._group_comm builds its gather that way, once, at plan time): write()
-    then gathers nothing.  Without counts write() takes the caller's tiles (shared_obs)."""
+    counts / in_tile_order / shared_obs: the three row conventions of _TiledPopulation.  write() takes logits_out by keyword and
+    returns what comm_actor_decode_pop returns (by source row, in tile order)."""
 
-    tick_free = True
     writes_groups = True
     MIN_MEMBERS = 2      # the smallest population that is grouped (simulate_grid, MixturePolicy): PERFLOG.md has the measurement
 
     def __init__(self, policies, counts=None, in_tile_order: bool = False):
-        self.policies = list(policies)
-        if not 1 <= len(self.policies) <= 32:
-            raise ValueError("1 to 32 nets")
+        super().__init__(policies, counts, in_tile_order)
         p0 = self.policies[0]
         if any(not isinstance(p, CommActorPolicy) or p.net.gat_layers for p in self.policies):
             raise ValueError("the members are CommActorPolicy without attention layers")
         self.role, self.greedy, self.noop, self.n_types = p0.role, p0.greedy, p0.noop, p0.n_types
         self.action_types = list(p0.action_types)
-        self.counts = None if counts is None else [int(c) for c in counts]
-        if self.counts is not None and len(self.counts) != len(self.policies):
-            raise ValueError("counts: one row count per member")
-        self.in_tile_order = bool(in_tile_order)
-        self._pk = self._pk_ver = self._tiles = None
+        self.state_dim, self.n_devices = p0.net.state_dim, p0.net.D
 
     @staticmethod
     def key(p, M):
@@ -1636,83 +1730,31 @@ class CommActorPolicyGroup:
         n = p.net
         return (p.role, n.state_dim, n.hidden, n.n_types, n.D, n.E, n.A, p.greedy, p.noop)
 
-    @staticmethod
-    def tile_plan(counts):
-        """The padded tile order of rows that come member after member, as numpy: (pos [S 16 Tm] int64 -- the position in the
-        member-after-member order of every padded row, 0 on the padding --, valid [S 16 Tm] bool, tile_slot [S Tm] int32) with Tm =
-        the tiles of the longest member (at least 1).  Member s owns padded rows s 16 Tm ..: its rows in order, then padding; its
-        tiles without a row carry slot -1.  mixture_rows_np's layout with every slot's segment at a fixed place."""
-        import numpy as np
-        counts = np.asarray(counts, np.int64)
-        S_, Tm = counts.size, max(1, int((counts.max() + 15) // 16))
-        j = np.arange(16 * Tm)[None, :]
-        valid = j < counts[:, None]
-        start = np.concatenate([[0], np.cumsum(counts)[:-1]])
-        pos = np.where(valid, start[:, None] + j, 0).astype(np.int64).reshape(-1)
-        tile_slot = np.where(np.arange(Tm)[None, :] * 16 < counts[:, None], np.arange(S_)[:, None], -1).astype(np.int32).reshape(-1)
-        return pos, valid.reshape(-1), tile_slot
-
-    def _stacked(self, batch=None):
+    def _stacked(self, batch=None, device=None):
         """The members' packs (CommActorCritic.packed) slot after slot, as the dict comm_actor_decode_pop reads plus the batched
         operands of tok_base: w_sp_t [S, W, H], b_sp [S, 1, H], w_m_t [S, H, H], b_m [S, 1, H].  Redone when a member's parameter
         changes (the members' own packed() versions)."""
         packs = [p.net.packed(batch) for p in self.policies]
-        ver = tuple(p.net._pk_ver for p in self.policies)
-        if self._pk_ver != ver:
+
+        def build():
             st = lambda k: torch.stack([pk[k] for pk in packs]).contiguous()  # noqa: E731
             pk0 = packs[0]
-            self._pk = {"K": pk0["K"], "E": pk0["E"], "A": pk0["A"], "S": len(packs),
-                        "w_sp_t": st("w_sp_t"), "b_sp": st("b_sp")[:, None, :].contiguous(), "w_m_t": st("w_m_t"), "b_m": st("b_m")[:, None, :].contiguous(),
-                        "tok_dev": st("tok_dev"), "w_type": st("w_type"), "b_type": st("b_type"), "w_ctx": st("w_ctx"), "b_ctx": st("b_ctx"),
-                        "w_v2": st("w_v2"),
-                        "b_v2s": torch.cat([p.net.v_head[2].bias.detach().reshape(1) for p in self.policies]).contiguous()}      # (no host read)
-            self._pk_ver = ver
-        return self._pk
+            return {"K": pk0["K"], "E": pk0["E"], "A": pk0["A"], "S": len(packs),
+                    "w_sp_t": st("w_sp_t"), "b_sp": st("b_sp")[:, None, :].contiguous(), "w_m_t": st("w_m_t"), "b_m": st("b_m")[:, None, :].contiguous(),
+                    "tok_dev": st("tok_dev"), "w_type": st("w_type"), "b_type": st("b_type"), "w_ctx": st("w_ctx"), "b_ctx": st("b_ctx"),
+                    "w_v2": st("w_v2"),
+                    "b_v2s": torch.cat([p.net.v_head[2].bias.detach().reshape(1) for p in self.policies]).contiguous()}      # (no host read)
+        return self._cached(tuple(p.net._pk_ver for p in self.policies), build)
 
     def tok_base(self, obs_s, pack):
         """[S, n, H]: a = merge.bias + merge.weight[:, :H] relu(state_proj(state)) of every (net, row) of obs_s [S, n, W] (or an
         expanded [n, W]): two baddbmm."""
         return torch.baddbmm(pack["b_m"], torch.relu_(torch.baddbmm(pack["b_sp"], obs_s, pack["w_sp_t"])), pack["w_m_t"])
 
-    def _tile_tensors(self, device):
-        if self._tiles is None or self._tiles[0].device != device:
-            pos, valid, tile_slot = self.tile_plan(self.counts)
-            self._tiles = (torch.from_numpy(pos).to(device), torch.from_numpy(valid).to(device), torch.from_numpy(tile_slot).to(device),
-                           bool(valid.all()))
-        return self._tiles
+    _first_layer = tok_base
 
-    @torch.no_grad()
-    def write(self, batch, act, rows, obs, tile_slot=None, shared_obs=False, logits_out=None):
-        """ONE decode launch for all members; returns what comm_actor_decode_pop returns (by source row, in tile order).
-        Default: `rows` / `obs` [n, W] hold the members' rows member after member (counts); they are gathered once into the padded
-        tile order (not at all when in_tile_order, or when every count is the same multiple of 16) and tok_base is formed per source
-        row.  shared_obs: `rows` [16 T] and tile_slot [T] are the caller's tiles, made on the device (the draw of a mixture), obs
-        [N, W] holds every env once: tok_base is [S, N, H] and the kernel reads the block of the tile's slot."""
-        pack = self._stacked(batch)
-        S_, W, H = (int(x) for x in pack["w_sp_t"].shape)
-        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != W:
-            raise ValueError(f"obs must be a float32 [n, {W}] role view")
-        if batch.M != self.policies[0].net.D:
-            raise ValueError(f"the nets were built for {self.policies[0].net.D} devices, the batch has {batch.M}")
-        if shared_obs:
-            if tile_slot is None or rows is None:
-                raise ValueError("shared_obs: the caller says which tile plays whom (rows = rows_tiled, tile_slot)")
-            tok = self.tok_base(obs[None].expand(S_, int(obs.shape[0]), W), pack)
-        else:
-            if self.counts is None:
-                raise ValueError("rows ordered member after member need counts")
-            pos, valid, tile_slot, dense = self._tile_tensors(obs.device)
-            n_pad = int(pos.numel())
-            if self.in_tile_order or (dense and int(obs.shape[0]) == n_pad):
-                if int(obs.shape[0]) != n_pad or rows is None or int(rows.numel()) != n_pad:
-                    raise ValueError(f"rows in tile order: {n_pad} padded rows (tile_plan)")
-            else:
-                if sum(self.counts) != int(obs.shape[0]) or rows is None or int(rows.numel()) != int(obs.shape[0]):
-                    raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
-                obs = obs.index_select(0, pos)
-                rows = torch.where(valid, rows.index_select(0, pos), torch.full_like(rows[:1], -1))
-            tok = self.tok_base(obs.reshape(S_, n_pad // S_, W), pack).reshape(n_pad, H)
-        return batch.comm_actor_decode_pop(rows, tile_slot, tok, pack, self.role, noop=self.noop, greedy=self.greedy, act=act, logits_out=logits_out)
+    def _launch(self, batch, act, rows, tile_slot, x, pack, logits_out=None):
+        return batch.comm_actor_decode_pop(rows, tile_slot, x, pack, self.role, noop=self.noop, greedy=self.greedy, act=act, logits_out=logits_out)
 
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("a CommActorPolicyGroup answers with groups of devices per action type: it runs through write(), on a "
@@ -2028,34 +2070,27 @@ class HierarchicalPolicy:
                                   "runs through write(), on a batch with cygym_hier_decode (HierarchicalNet.decide is the torch form)")
 
 
-class HierarchicalPolicyGroup:
+class HierarchicalPolicyGroup(_TiledPopulation):
     """A population of HierarchicalPolicy (HAGS) strategies of ONE shape (key) decided together: h0 of all of them is one batched
     GEMM and the decode of all of them is ONE launch (cygym_hier_decode_pop), the net of a tile of 16 rows taken from a slot table.
     The decode gives a workgroup 16 rows and about 100 KB of LDS at H = 256, so a launch per strategy over that strategy's few rows
     leaves most of the chip idle; the |D| x |A| grid of a Double-Oracle population with --BR_type hierarchical and the opponent drawn
     per env from an equilibrium (MixturePolicy) hold several such nets, each deciding for a few envs.
-    counts / in_tile_order / shared_obs: the three row conventions of CommActorPolicyGroup, whose tile_plan lays the rows out."""
+    counts / in_tile_order / shared_obs: the three row conventions of _TiledPopulation.  write() takes the optional outputs of
+    hier_decode_pop by keyword."""
 
-    tick_free = True
     MIN_MEMBERS = 2           # the smallest population simulate_grid groups (PERFLOG.md has the measurement)
     MIN_MEMBERS_MIXTURE = 4   # ... and the smallest MixturePolicy groups: there h0 is formed for every (net, env), which at two
     #                           members costs more than the launch it saves and at three as much (measured, PERFLOG.md)
-    tile_plan = staticmethod(CommActorPolicyGroup.tile_plan)
 
     def __init__(self, policies, counts=None, in_tile_order: bool = False):
-        self.policies = list(policies)
-        if not 1 <= len(self.policies) <= 32:
-            raise ValueError("1 to 32 nets")
+        super().__init__(policies, counts, in_tile_order)
         p0 = self.policies[0]
         k0 = self.key(p0, getattr(getattr(p0, "net", None), "M", 0))
         if k0 is None or any(self.key(p, p0.net.M) != k0 for p in self.policies):
             raise ValueError("the members are HierarchicalPolicy of one key (HierarchicalPolicyGroup.key)")
         self.role, self.n_types, self.action_types = p0.role, p0.n_types, list(p0.action_types)
-        self.counts = None if counts is None else [int(c) for c in counts]
-        if self.counts is not None and len(self.counts) != len(self.policies):
-            raise ValueError("counts: one row count per member")
-        self.in_tile_order = bool(in_tile_order)
-        self._pk = self._pk_ver = self._tiles = None
+        self.state_dim, self.n_devices = p0.net.state_dim, p0.net.M
 
     @staticmethod
     def key(p, M):
@@ -2066,70 +2101,34 @@ class HierarchicalPolicyGroup:
         n = p.net
         return (p.role, n.state_dim, n.hidden, n.n_types, n.M, p.n_parts, p.part_digest, p.type_map_key, p.vis is None)
 
-    def _stacked(self, device=None):
+    def _stacked(self, batch=None, device=None):
         """The members' packs (HierarchicalNet.packed) slot after slot, as the dict hier_decode_pop reads, plus the batched operands
         of h0 -- w0_t [S, W, 3 H], b0 [S, 1, 3 H] -- and vis_fixeds [S, M] when the members carry fixed masks.  Redone when a member's
         parameter changes (the members' own packed() versions) or the device does."""
         device = self.policies[0].net.score_net.fc1.weight.device if device is None else torch.device(device)
         packs = [p._packed(device) for p in self.policies]
-        ver = (device,) + tuple(p.net._pk_ver for p in self.policies)
-        if self._pk_ver != ver:
+
+        def build():
             st = lambda k: torch.stack([pk[k] for pk in packs]).contiguous()  # noqa: E731
             pk0 = packs[0]
-            self._pk = {"H": pk0["H"], "T": pk0["T"], "S": len(packs), "part_of": pk0["part_of"], "n_parts": pk0["n_parts"],
-                        "w0_t": st("w0_t"), "b0": st("b0")[:, None, :].contiguous()}
+            pack = {"H": pk0["H"], "T": pk0["T"], "S": len(packs), "part_of": pk0["part_of"], "n_parts": pk0["n_parts"],
+                    "w0_t": st("w0_t"), "b0": st("b0")[:, None, :].contiguous()}
             for k in ("w_mask_t", "w_score", "b_score", "w_act2", "b_act2", "w_dev2", "b_dev2", "w_act_head", "b_act_head", "w_dev_head", "b_dev_head"):
-                self._pk[k] = st(k)
+                pack[k] = st(k)
             if self.policies[0].vis is not None:
-                self._pk["vis_fixeds"] = torch.stack([p.vis for p in self.policies]).contiguous()
-            self._pk_ver = ver
-        return self._pk
+                pack["vis_fixeds"] = torch.stack([p.vis for p in self.policies]).contiguous()
+            return pack
+        return self._cached((device,) + tuple(p.net._pk_ver for p in self.policies), build)
 
     def h0(self, obs_s, pack):
         """[S, n, 3 H]: the three first-layer pre-activations of every (net, row) of obs_s [S, n, W] (or an expanded [n, W]): one baddbmm."""
         return torch.baddbmm(pack["b0"], obs_s, pack["w0_t"])
 
-    def _tile_tensors(self, device):
-        if self._tiles is None or self._tiles[0].device != device:
-            pos, valid, tile_slot = self.tile_plan(self.counts)
-            self._tiles = (torch.from_numpy(pos).to(device), torch.from_numpy(valid).to(device), torch.from_numpy(tile_slot).to(device),
-                           bool(valid.all()))
-        return self._tiles
+    _first_layer = h0
 
-    @torch.no_grad()
-    def write(self, batch, act, rows, obs, tile_slot=None, shared_obs=False, **outs):
-        """One baddbmm, then ONE decode launch for all members (the optional outputs of hier_decode_pop by keyword: by source row, in
-        tile order).
-        Default: `rows` / `obs` [n, W] hold the members' rows member after member (counts); they are gathered once into the padded
-        tile order (not at all when in_tile_order, or when every count is the same multiple of 16) and h0 is formed per source row.
-        shared_obs: `rows` [16 T] and tile_slot [T] are the caller's tiles, made on the device (the draw of a mixture), obs [N, W]
-        holds every env once: h0 is [S, N, 3 H] and the kernel reads the block of the tile's slot."""
-        p0 = self.policies[0]
-        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != p0.net.state_dim:
-            raise ValueError(f"obs must be a float32 [n, {p0.net.state_dim}] role view")
-        if batch.M != p0.net.M:
-            raise ValueError(f"the nets were built for {p0.net.M} devices, the batch has {batch.M}")
-        pack = self._stacked(obs.device)
-        S_, W, H3 = (int(x) for x in pack["w0_t"].shape)
-        if shared_obs:
-            if tile_slot is None or rows is None:
-                raise ValueError("shared_obs: the caller says which tile plays whom (rows = rows_tiled, tile_slot)")
-            h0 = self.h0(obs[None].expand(S_, int(obs.shape[0]), W), pack)
-        else:
-            if self.counts is None:
-                raise ValueError("rows ordered member after member need counts")
-            pos, valid, tile_slot, dense = self._tile_tensors(obs.device)
-            n_pad = int(pos.numel())
-            if self.in_tile_order or (dense and int(obs.shape[0]) == n_pad):
-                if int(obs.shape[0]) != n_pad or rows is None or int(rows.numel()) != n_pad:
-                    raise ValueError(f"rows in tile order: {n_pad} padded rows (tile_plan)")
-            else:
-                if sum(self.counts) != int(obs.shape[0]) or rows is None or int(rows.numel()) != int(obs.shape[0]):
-                    raise ValueError("rows ordered member after member: counts must add up to the rows of obs")
-                obs = obs.index_select(0, pos)
-                rows = torch.where(valid, rows.index_select(0, pos), torch.full_like(rows[:1], -1))
-            h0 = self.h0(obs.reshape(S_, n_pad // S_, W), pack).reshape(n_pad, H3)
-        batch.hier_decode_pop(rows, tile_slot, h0, pack, self.role, act=act, vis_fixeds=pack.get("vis_fixeds"), type_map=p0._map(obs.device), **outs)
+    def _launch(self, batch, act, rows, tile_slot, x, pack, **outs):
+        batch.hier_decode_pop(rows, tile_slot, x, pack, self.role, act=act, vis_fixeds=pack.get("vis_fixeds"),
+                              type_map=self.policies[0]._map(x.device), **outs)
 
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("a HierarchicalPolicyGroup reads the visibility of the envs it decides for off the batch's flag plane: it "
@@ -3122,61 +3121,20 @@ class MixturePolicy:
         from . import spec as S
         return (self._st["baseline_state"].to(torch.int32) + 1) << S.MODE_BASELINE_SHIFT
 
-    def _group(self, batch):
-        """(ActorPolicyGroup, member_slot list) of the largest set of same-shaped fused actors among the members, or (None, all -1)."""
-        slots = [-1] * len(self.members)
-        if not (self.tiled and hasattr(batch, "mixture_draw") and hasattr(batch, "actor_mlp_decode")):
-            return None, slots
-        by_key = {}
-        for s, m in enumerate(self.members):
-            k = ActorPolicyGroup.key(m, batch.M)
-            if k is not None and m.fused_mlp(batch):
-                by_key.setdefault(k, []).append(s)
-        best = max(by_key.values(), key=len, default=[])
-        if len(best) < 2:
-            return None, slots
-        for pos, s in enumerate(best):
-            slots[s] = pos
-        return ActorPolicyGroup([self.members[s] for s in best]), slots
-
-    def _critic_group(self, batch):
-        """(CoordAscentPolicyGroup, critic slot of every member or -1) of the largest set of same-key CoordAscentPolicy members that can
-        play, or (None, all -1)."""
-        slots = [-1] * len(self.members)
-        if not (self.tiled and hasattr(batch, "mixture_draw") and hasattr(batch, "coord_ascent_decode_pop")):
-            return None, slots
-        by_key = {}
-        for s, m in enumerate(self.members):
-            k = CoordAscentPolicyGroup.key(m, batch.M)
-            if k is not None and self.probs[s] > 0.0:
-                by_key.setdefault(k, []).append(s)
-        best = max(by_key.values(), key=len, default=[])
-        if len(best) < 2:
-            return None, slots
-        for pos, s in enumerate(best):
-            slots[s] = pos
-        return CoordAscentPolicyGroup([self.members[s] for s in best]), slots
-
-    def _comm_group(self, batch, taken: bool):
-        """(CommActorPolicyGroup, slot of every member or -1) of the largest set of same-key CommActorPolicy members (no attention
-        layers) that can play, or (None, all -1).  taken: the draw's one member_slot table already serves an ActorPolicyGroup."""
-        return self._tile_group(batch, taken, CommActorPolicyGroup, "comm_actor_decode_pop", CommActorPolicyGroup.MIN_MEMBERS)
-
-    def _hier_group(self, batch, taken: bool):
-        """(HierarchicalPolicyGroup, slot of every member or -1) of the largest set of same-key HierarchicalPolicy members that can
-        play, HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE or more, or (None, all -1).  taken: the draw's one member_slot table already
-        serves an ActorPolicyGroup or a CommActorPolicyGroup (the HAGS members then play one by one)."""
-        return self._tile_group(batch, taken, HierarchicalPolicyGroup, "hier_decode_pop", HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE)
-
-    def _tile_group(self, batch, taken, Group, entry, min_members):
-        """What _comm_group and _hier_group share: the largest same-key set (Group.key) of members of probability > 0."""
+    def _same_key_group(self, batch, Group, entry, min_members=2, taken=False, can_play=None):
+        """(Group of them, slot of every member or -1) for the largest set of members of one Group.key that can_play(s, m) -- default:
+        of probability > 0 --, min_members or more (at least two), or (None, all -1): also when tiled is off, when the batch lacks
+        mixture_draw or the entry point `entry`, and when `taken` (the population would need the draw's one member_slot table, and
+        another population holds it)."""
         slots = [-1] * len(self.members)
         if taken or not (self.tiled and hasattr(batch, "mixture_draw") and hasattr(batch, entry)):
             return None, slots
+        if can_play is None:
+            can_play = lambda s, m: self.probs[s] > 0.0  # noqa: E731
         by_key = {}
         for s, m in enumerate(self.members):
             k = Group.key(m, batch.M)
-            if k is not None and self.probs[s] > 0.0:
+            if k is not None and can_play(s, m):
                 by_key.setdefault(k, []).append(s)
         best = max(by_key.values(), key=len, default=[])
         if len(best) < max(2, min_members):
@@ -3185,18 +3143,28 @@ class MixturePolicy:
             slots[s] = pos
         return Group([self.members[s] for s in best]), slots
 
+    def _comm_group(self, batch, taken: bool):
+        """_same_key_group for the CommActorPolicy members (no attention layers).  taken: the draw's one member_slot table already
+        serves an ActorPolicyGroup."""
+        return self._same_key_group(batch, CommActorPolicyGroup, "comm_actor_decode_pop", CommActorPolicyGroup.MIN_MEMBERS, taken)
+
+    def _hier_group(self, batch, taken: bool):
+        """_same_key_group for the HierarchicalPolicy members, HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE or more.  taken: the draw's
+        one member_slot table already serves an ActorPolicyGroup or a CommActorPolicyGroup (the HAGS members then play one by one)."""
+        return self._same_key_group(batch, HierarchicalPolicyGroup, "hier_decode_pop", HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE, taken)
+
     def _state(self, batch):
         st = self._st
         if st is None or st["batch"] is not batch:
             N, S_, dev = batch.N, len(self.members), batch.device
-            grp, slots = self._group(batch)
-            cgrp, cslots = self._critic_group(batch)
+            # the fused actors of one architecture (whatever their probability: the tiles of a member that never plays stay empty)
+            grp, aslots = self._same_key_group(batch, ActorPolicyGroup, "actor_mlp_decode", can_play=lambda s, m: m.fused_mlp(batch))
+            cgrp, cslots = self._same_key_group(batch, CoordAscentPolicyGroup, "coord_ascent_decode_pop")
             mgrp, mslots = self._comm_group(batch, grp is not None)
-            if mgrp is not None:      # (the draw's tiles go to the comm nets: `group` stays None, `slots` is the table the draw reads)
-                slots = mslots
             hgrp, hslots = self._hier_group(batch, grp is not None or mgrp is not None)
-            if hgrp is not None:      # (... or to the HAGS nets, when nobody else holds the table)
-                slots = hslots
+            # the draw reads ONE member_slot table: the actors', else the comm nets', else the HAGS nets' (at most one of the three lives)
+            slots = mslots if mgrp is not None else hslots if hgrp is not None else aslots
+            live = [(g, sl) for g, sl in ((grp, aslots), (cgrp, cslots), (mgrp, mslots), (hgrp, hslots)) if g is not None]
             tiles = grp is not None or mgrp is not None or hgrp is not None
             T = (N + 15) // 16 + S_
             z = lambda shape, dt, v=0: torch.full(shape, v, dtype=dt, device=dev)  # noqa: E731
@@ -3208,7 +3176,8 @@ class MixturePolicy:
                                  tile_slot=z((T,), torch.int32, -1) if tiles else None,
                                  comm=mgrp, comm_slots=mslots, hier=hgrp, hier_slots=hslots,
                                  critics=cgrp, critic_slots=cslots, critic_slot_of=torch.tensor(cslots, dtype=torch.int32, device=dev),
-                                 slot_of_row=z((N,), torch.int32, -1) if cgrp is not None else None)
+                                 slot_of_row=z((N,), torch.int32, -1) if cgrp is not None else None,
+                                 live=[g for g, _ in live], held=[any(sl[s] >= 0 for _, sl in live) for s in range(S_)])
         return st
 
     def _check_rows(self, st, rows, N):
@@ -3233,31 +3202,23 @@ class MixturePolicy:
         batch.mixture_draw(st["cdf"], st["member_baseline"], st["member_slot"], st["baseline_state"], self.role, index_out=st["index"],
                            mode=act["mode"], rows_masked=st["rows_masked"], rows_tiled=st["rows_tiled"], tile_slot=st["tile_slot"])
         self.last_index = st["index"]
-        grp, slots = st["group"], st["slots"]
         in_place = obs.dtype == torch.float32 and obs.dim() == 2 and obs.stride(1) == 1 and int(obs.shape[0]) >= N
-        if grp is not None and in_place:
-            hidden, head = grp._packed_all(batch)
-            p0 = grp.policies[0]
-            batch.actor_mlp_decode(st["rows_tiled"], obs, hidden, head, grp.n_types, grp.n_exploits, grp.n_apps, p0._map(batch.device), act,
-                                   epsilon=grp.epsilon, tanh=p0._split_mlp(batch.M)[2], n_groups=len(grp.policies), obs_by_env=True,
-                                   tile_slot=st["tile_slot"])
-        cgrp, cslots = st["critics"], st["critic_slots"]
-        if cgrp is not None and in_place:
-            # the critic slot of every env's member (-1: another member's env), then ONE decode launch over all envs in order
-            torch.index_select(st["critic_slot_of"], 0, st["index"].to(torch.int32), out=st["slot_of_row"])
-            cgrp.write(batch, act, None, obs[:N], slot_of_row=st["slot_of_row"], shared_obs=True)
-        mgrp, mslots = st["comm"], st["comm_slots"]
-        if mgrp is not None and in_place:
-            # the draw's tiles carry the comm nets' slots: tok_base for every (net, env), then ONE decode launch over the tiles
-            mgrp.write(batch, act, st["rows_tiled"], obs[:N], tile_slot=st["tile_slot"], shared_obs=True)
-        hgrp, hslots = st["hier"], st["hier_slots"]
-        if hgrp is not None and in_place:
-            # the draw's tiles carry the HAGS nets' slots: h0 for every (net, env), then ONE decode launch over the tiles
-            hgrp.write(batch, act, st["rows_tiled"], obs[:N], tile_slot=st["tile_slot"], shared_obs=True)
+        for g in (st["live"] if in_place else []):      # (in the order actors, critics, comm nets, HAGS nets)
+            if isinstance(g, ActorPolicyGroup):
+                hidden, head = g._packed_all(batch)
+                p0 = g.policies[0]
+                batch.actor_mlp_decode(st["rows_tiled"], obs, hidden, head, g.n_types, g.n_exploits, g.n_apps, p0._map(batch.device), act,
+                                       epsilon=g.epsilon, tanh=p0._split_mlp(batch.M)[2], n_groups=len(g.policies), obs_by_env=True,
+                                       tile_slot=st["tile_slot"])
+            elif isinstance(g, CoordAscentPolicyGroup):
+                # the critic slot of every env's member (-1: another member's env), then ONE decode launch over all envs in order
+                torch.index_select(st["critic_slot_of"], 0, st["index"].to(torch.int32), out=st["slot_of_row"])
+                g.write(batch, act, None, obs[:N], slot_of_row=st["slot_of_row"], shared_obs=True)
+            else:
+                # the draw's tiles carry this population's slots: its first layer for every (net, env), then ONE decode launch over the tiles
+                g.write(batch, act, st["rows_tiled"], obs[:N], tile_slot=st["tile_slot"], shared_obs=True)
         for s, m in enumerate(self.members):
-            if (grp is not None and in_place and slots[s] >= 0) or (cgrp is not None and in_place and cslots[s] >= 0) or \
-                    (mgrp is not None and in_place and mslots[s] >= 0) or (hgrp is not None and in_place and hslots[s] >= 0) or \
-                    self.probs[s] == 0.0:
+            if (in_place and st["held"][s]) or self.probs[s] == 0.0:      # (some live population holds it, or it never plays)
                 continue
             r = st["rows_masked"][s]
             if hasattr(m, "write"):

@@ -225,64 +225,12 @@ def _group_actors(batch, items, M, env_order_rpg=None):
     return [(grp, r64, r64.to(torch.int32), sl, rpg)]
 
 
-def _group_critics(batch, items, M):
-    """Strategies of one role and sub-batch that are CoordAscentPolicy of ONE shape in eval mode (policies.CoordAscentPolicyGroup.key), two
-    or more, become one item: their decode is one launch over all their rows (a row is a workgroup there: any row counts, equal or
-    not), the slot table and the concatenated row ids made here, once.  On a batch-like without the library the item decodes with the
-    members' torch code."""
-    from .policies import CoordAscentPolicyGroup
-    if len(items) < 2 or (hasattr(batch, "role_obs") and not hasattr(batch, "coord_ascent_decode_pop")):
-        return items
-    by_key = {}
-    for i, it in enumerate(items):
-        k = CoordAscentPolicyGroup.key(it[0], M)
-        if k is not None:
-            by_key.setdefault(k, []).append(i)
-    first = {}
-    for members in by_key.values():
-        for lo in range(0, len(members), 32):      # (a population holds at most 32 critics)
-            chunk = members[lo:lo + 32]
-            if len(chunk) >= 2:
-                first[chunk[0]] = chunk
-    taken = {i for chunk in first.values() for i in chunk[1:]}
-    out = []
-    for i, it in enumerate(items):
-        if i in taken:
-            continue
-        if i not in first:
-            out.append(it)
-            continue
-        chunk = [items[j] for j in first[i]]
-        r64 = torch.cat([c[1] for c in chunk])
-        ids = r64.cpu().numpy()
-        sl = slice(int(ids[0]), int(ids[-1]) + 1) if (np.diff(ids) == 1).all() else None
-        out.append((CoordAscentPolicyGroup([c[0] for c in chunk], counts=[int(c[1].numel()) for c in chunk]), r64, r64.to(torch.int32), sl, None))
-    return out
-
-
-def _group_comm(batch, items, M):
-    """Strategies of one role and sub-batch that are CommActorPolicy of ONE shape without attention layers
-    (policies.CommActorPolicyGroup.key), CommActorPolicyGroup.MIN_MEMBERS or more, become one item: their decode is one launch over all
-    their rows.  The kernel gives a workgroup a tile of 16 rows of one net, so the rows are laid out here, once, in the tiled form of
-    policies.mixture_rows_np with every member's segment padded to the same number of tiles (CommActorPolicyGroup.tile_plan): the
-    item's env ids ARE that padded order (env 0 on the padding, -1 in the row list), so the tick gathers the observations once, in
-    the order tok_base is formed in.  Row counts may be unequal and need not be multiples of 16."""
-    from .policies import CommActorPolicyGroup
-    return _group_tiled(batch, items, M, CommActorPolicyGroup, "comm_actor_decode_pop")
-
-
-def _group_hier(batch, items, M):
-    """The same step for the HAGS strategies (policies.HierarchicalPolicy) of ONE key (policies.HierarchicalPolicyGroup.key: shape,
-    part table, type map, kind of visibility), HierarchicalPolicyGroup.MIN_MEMBERS or more: one baddbmm and one
-    cygym_hier_decode_pop per role and tick over all their rows, in the padded tile order of _group_comm."""
-    from .policies import HierarchicalPolicyGroup
-    return _group_tiled(batch, items, M, HierarchicalPolicyGroup, "hier_decode_pop")
-
-
-def _group_tiled(batch, items, M, Group, entry):
-    """What _group_comm and _group_hier share: the same-key items (Group.key), Group.MIN_MEMBERS or more in chunks of at most 32,
-    become one item of Group in padded tile order; on a batch without the entry point `entry` the items stay as they are."""
-    if len(items) < 2 or not hasattr(batch, entry):
+def _group_same_key(batch, items, M, Group, min_chunk, gate, layout):
+    """What the planner's population steps share: the items of one Group.key, in chunks of at most 32 (a population holds no more)
+    and of at least min_chunk (at least two), become ONE item each, at the place of the chunk's first member; every other item stays
+    the item it was.  gate: may this batch decode such a population at all?  layout(Group, chunk) -> (group, env ids int64, env ids
+    int32, slice or None) lays the rows of a chunk of items out the way the family's kernel reads them."""
+    if len(items) < 2 or not gate:
         return items
     by_key = {}
     for i, it in enumerate(items):
@@ -291,27 +239,65 @@ def _group_tiled(batch, items, M, Group, entry):
             by_key.setdefault(k, []).append(i)
     first = {}
     for members in by_key.values():
-        for lo in range(0, len(members), 32):      # (a population holds at most 32 nets)
+        for lo in range(0, len(members), 32):
             chunk = members[lo:lo + 32]
-            if len(chunk) >= max(2, Group.MIN_MEMBERS):
+            if len(chunk) >= max(2, min_chunk):
                 first[chunk[0]] = chunk
     taken = {i for chunk in first.values() for i in chunk[1:]}
     out = []
     for i, it in enumerate(items):
-        if i in taken:
-            continue
-        if i not in first:
+        if i in first:
+            out.append(layout(Group, [items[j] for j in first[i]]) + (None,))
+        elif i not in taken:
             out.append(it)
-            continue
-        chunk = [items[j] for j in first[i]]
-        counts = [int(c[1].numel()) for c in chunk]
-        pos, valid, _ = Group.tile_plan(counts)
-        ids = torch.cat([c[1] for c in chunk]).cpu().numpy()[pos]
-        r64 = torch.from_numpy(ids).to(chunk[0][1].device)
-        r32 = torch.from_numpy(np.where(valid, ids, -1).astype(np.int32)).to(chunk[0][1].device)
-        sl = slice(int(ids[0]), int(ids[-1]) + 1) if (valid.all() and (np.diff(ids) == 1).all()) else None
-        out.append((Group([c[0] for c in chunk], counts=counts, in_tile_order=True), r64, r32, sl, None))
     return out
+
+
+def _rows_concatenated(Group, chunk):
+    """A workgroup per row: the members' rows one after the other, any counts (the group makes its slot table from them)."""
+    r64 = torch.cat([c[1] for c in chunk])
+    ids = r64.cpu().numpy()
+    sl = slice(int(ids[0]), int(ids[-1]) + 1) if (np.diff(ids) == 1).all() else None
+    return Group([c[0] for c in chunk], counts=[int(c[1].numel()) for c in chunk]), r64, r64.to(torch.int32), sl
+
+
+def _rows_tiled(Group, chunk):
+    """A workgroup per tile of 16 rows of one net: the tiled form of policies.mixture_rows_np with every member's segment padded to the
+    same number of tiles (Group.tile_plan).  The item's env ids ARE that padded order (the chunk's first env on the padding, -1 in the
+    row list), so the tick gathers the observations once, in the order the first layer is formed in."""
+    counts = [int(c[1].numel()) for c in chunk]
+    pos, valid, _ = Group.tile_plan(counts)
+    ids = torch.cat([c[1] for c in chunk]).cpu().numpy()[pos]
+    r64 = torch.from_numpy(ids).to(chunk[0][1].device)
+    r32 = torch.from_numpy(np.where(valid, ids, -1).astype(np.int32)).to(chunk[0][1].device)
+    sl = slice(int(ids[0]), int(ids[-1]) + 1) if (valid.all() and (np.diff(ids) == 1).all()) else None
+    return Group([c[0] for c in chunk], counts=counts, in_tile_order=True), r64, r32, sl
+
+
+def _group_critics(batch, items, M):
+    """Strategies of one role and sub-batch that are CoordAscentPolicy of ONE shape in eval mode (policies.CoordAscentPolicyGroup.key), two
+    or more, become one item: their decode is one launch over all their rows (a row is a workgroup there: any row counts, equal or
+    not), the slot table and the concatenated row ids made here, once.  On a batch-like without the library (no role_obs) the item
+    decodes with the members' torch code."""
+    from .policies import CoordAscentPolicyGroup as G
+    return _group_same_key(batch, items, M, G, 2, not hasattr(batch, "role_obs") or hasattr(batch, "coord_ascent_decode_pop"), _rows_concatenated)
+
+
+def _group_comm(batch, items, M):
+    """Strategies of one role and sub-batch that are CommActorPolicy of ONE shape without attention layers
+    (policies.CommActorPolicyGroup.key), CommActorPolicyGroup.MIN_MEMBERS or more, become one item in padded tile order (_rows_tiled):
+    their decode is one launch over all their rows.  Row counts may be unequal and need not be multiples of 16.  On a batch without
+    cygym_comm_actor_decode_pop the items stay as they are."""
+    from .policies import CommActorPolicyGroup as G
+    return _group_same_key(batch, items, M, G, G.MIN_MEMBERS, hasattr(batch, "comm_actor_decode_pop"), _rows_tiled)
+
+
+def _group_hier(batch, items, M):
+    """The same step for the HAGS strategies (policies.HierarchicalPolicy) of ONE key (policies.HierarchicalPolicyGroup.key: shape,
+    part table, type map, kind of visibility), HierarchicalPolicyGroup.MIN_MEMBERS or more: one baddbmm and one
+    cygym_hier_decode_pop per role and tick over all their rows, in the padded tile order of _group_comm."""
+    from .policies import HierarchicalPolicyGroup as G
+    return _group_same_key(batch, items, M, G, G.MIN_MEMBERS, hasattr(batch, "hier_decode_pop"), _rows_tiled)
 
 
 def _role_actions(batch, pol, M, L):
