@@ -274,6 +274,14 @@ class Meta(C.Structure):
                 ("H1", C.c_int32), ("H2", C.c_int32), ("h0_stride", C.c_int32)]
 
 
+META_POP_MAX = 32
+
+
+class MetaPop(C.Structure):
+    _fields_ = [("tile_slot", C.c_void_p), ("flags_fixeds", C.c_void_p), ("b3s", C.c_void_p), ("h0_group_stride", C.c_int64),
+                ("n_slots", C.c_int32), ("n_tiles", C.c_int32)]
+
+
 class MetaSelect(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("h0", C.c_void_p), ("sp_w2_t", C.c_void_p), ("sp_b2", C.c_void_p), ("base", C.c_void_p), ("w_feat", C.c_void_p),
                 ("np_w2", C.c_void_p), ("np_b2", C.c_void_p), ("nbr_ptr", C.c_void_p), ("nbr_col", C.c_void_p), ("snap_degn", C.c_void_p),

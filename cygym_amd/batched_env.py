@@ -1428,27 +1428,75 @@ class BatchedCyberDefenseEnv:
         Needs max_groups >= k and max_devs >= k, else the row is cut and abi.DECODE_TRUNCATED raised.  No draw: the rng tick is
         neither read nor advanced.  Limits: M <= 1000, k, n_types <= 32, id_dim <= 32, embed_dim, proj_dim <= 64, Hp <= 256, the
         critic's widths multiples of 16 in 16..128 (the library answers CYGYM_EUNSUPPORTED / CYGYM_EINVAL)."""
+        self._meta(rows, h0, pack, role, act, flags_fixed, type_map, score_out=score_out, selected_out=selected_out, q_out=q_out, deg_out=deg_out)
+
+    def meta_decode_pop(self, rows_tiled: torch.Tensor, tile_slot: torch.Tensor, h0: torch.Tensor, pack, role: str = "defender", act=None,
+                        flags_fixeds=None, type_map=None, score_out=None, selected_out=None, q_out=None, deg_out=None):
+        """meta_decode for a POPULATION of S same-shaped MetaDOAR strategies (1 <= S <= 32: controller and critic per slot), each
+        deciding for some of the rows: ONE launch (cygym_meta_decode_pop) -- source row r is decoded exactly as meta_decode would with
+        the tables of its tile's strategy.
+          rows_tiled   [16 T] int32 on the device: the env of every source row, 16 per tile, -1 = no row (the layout mixture_draw
+                       writes and policies.mixture_rows_np restates)
+          tile_slot    [T] int32 on the device: the strategy of tile t; a tile whose entry is negative or >= S is left alone
+          h0           [16 T, >= Hp + H1]: source row r formed with ITS strategy;  or [S, N, >= Hp + H1]: block s formed with strategy s
+                       for every env, the row of env e in tile t reads block tile_slot[t] at row e
+          pack         the dict of meta_decode with sp_w2_t, sp_b2, base, w_feat, np_w2, np_b2, w1a_t, w2, b2 and w3 holding the S
+                       strategies one after the other, "b3s" [S] float32 in place of b3, and "S" -- policies.MetaPolicyGroup stacks
+                       them; nbr_ptr / nbr_col, k, the layout and every width are the population's
+          flags_fixeds None: every row reads the flags and the added edges of its env; a contiguous uint8 [S, M] tensor: the ONE
+                       snapshot of every strategy, base graph only
+          outputs      as meta_decode, by SOURCE row (16 T of them); the rows of skipped tiles and of -1 are not written
+        Every tensor is checked here: the kernel indexes them by raw pointer."""
+        self._meta(rows_tiled, h0, pack, role, act, flags_fixeds, type_map, tile_slot=tile_slot, score_out=score_out, selected_out=selected_out,
+                   q_out=q_out, deg_out=deg_out)
+
+    def _meta(self, rows, h0, pack, role, act, flags_fixed, type_map, tile_slot=None, **outs):
+        """The path meta_decode and meta_decode_pop share: the structs of the arguments (_meta_structs), then cygym_meta_decode or --
+        with `tile_slot`, the population form -- cygym_meta_decode_pop."""
+        q, mp, dst, keep = self._meta_structs(rows, h0, pack, role, act, flags_fixed, type_map, tile_slot=tile_slot, **outs)   # noqa: F841
+        if mp is not None:
+            _lib.check(self.lib.cygym_meta_decode_pop(self._h, C.byref(q), C.byref(mp), C.byref(dst), self._stream()), self._h, "cygym_meta_decode_pop")
+        else:
+            _lib.check(self.lib.cygym_meta_decode(self._h, C.byref(q), C.byref(dst), self._stream()), self._h, "cygym_meta_decode")
+
+    def _meta_structs(self, rows, h0, pack, role, act, flags_fixed, type_map, score_out=None, selected_out=None, q_out=None, deg_out=None,
+                      tile_slot=None):
+        """Argument checks and marshalling of the two meta decodes: (Meta, MetaPop or None, Actions, tensors to keep).  With
+        `tile_slot` the population form: `rows` tiled, every table of `pack` stacked over pack["S"] strategies, b3s [S] in place of b3,
+        `h0` by source row or [S, N, >= Hp + H1], `flags_fixed` one snapshot per strategy."""
         dst = self.actions_struct(act)
+        mp = None
         ok = lambda t: t.dtype == torch.float32 and t.device == self.device  # noqa: E731
-        if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
-            raise ValueError("h0 must be a [n, >= Hp + H1] float32 tensor on the batch's device with unit inner stride")
-        n, M = int(h0.shape[0]), self.M
+        pop = tile_slot is not None
+        M = self.M
         T, E, A, k = int(pack["n_types"]), int(pack["n_exploits"]), int(pack["n_apps"]), int(pack["k"])
         ID, ED, P, Hp, H1, H2 = (int(pack[x]) for x in ("id_dim", "embed_dim", "proj_dim", "Hp", "H1", "H2"))
-        if int(h0.shape[1]) < Hp + H1:
-            raise ValueError(f"h0 rows hold {int(h0.shape[1])} floats: fewer than Hp + H1 = {Hp + H1}")
+        S_ = int(pack["S"]) if pop else 1
+        if pop:
+            n = self._tiled_rows(rows, tile_slot)
+            if S_ < 1:
+                raise ValueError("pack['S'] is the number of stacked strategies, at least 1")
+            row_stride, group_stride = self._pop_first_layer(h0, "h0", ">= Hp + H1", n, S_, wider=True)
+        else:
+            if not ok(h0) or h0.dim() != 2 or h0.stride(1) != 1:
+                raise ValueError("h0 must be a [n, >= Hp + H1] float32 tensor on the batch's device with unit inner stride")
+            n = int(h0.shape[0])
+            row_stride = int(h0.stride(0)) if n > 1 else int(h0.shape[1])
+        if int(h0.shape[-1]) < Hp + H1:
+            raise ValueError(f"h0 rows hold {int(h0.shape[-1])} floats: fewer than Hp + H1 = {Hp + H1}")
         ed4 = (ED + 3) // 4 * 4
         sizes = {"sp_w2_t": Hp * P, "sp_b2": P, "base": M * ed4, "w_feat": 3 * ed4, "np_w2": P * ED, "np_b2": P,
                  "w1a_t": (T + M + E + A) * H1, "w2": (H2 + 15) // 16 * ((H1 + 15) // 16) * 256, "w3": H2}
+        many = f"{S_} x " if pop else ""
         q = abi.Meta()
         for name, want in sizes.items():
             t = pack[name]
-            if not ok(t) or not t.is_contiguous() or int(t.numel()) != want:
-                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {want} values on {self.device}")
+            if not ok(t) or not t.is_contiguous() or int(t.numel()) != S_ * want:
+                raise ValueError(f"pack[{name!r}] must be a contiguous float32 tensor of {many}{want} values on {self.device}")
             setattr(q, name, t.data_ptr())
         if pack.get("b2") is not None:
-            if not ok(pack["b2"]) or not pack["b2"].is_contiguous() or int(pack["b2"].numel()) != H2:
-                raise ValueError(f"pack['b2'] must hold {H2} float32 values on {self.device}")
+            if not ok(pack["b2"]) or not pack["b2"].is_contiguous() or int(pack["b2"].numel()) != S_ * H2:
+                raise ValueError(f"pack['b2'] must hold {many}{H2} float32 values on {self.device}")
             q.b2 = pack["b2"].data_ptr()
         ptr, col = pack["nbr_ptr"], pack["nbr_col"]
         if ptr.dtype != torch.int32 or ptr.device != self.device or not ptr.is_contiguous() or int(ptr.numel()) != M + 1:
@@ -1456,13 +1504,27 @@ class BatchedCyberDefenseEnv:
         if col.dtype != torch.int16 or col.device != self.device or not col.is_contiguous() or int(col.numel()) != int(pack["nbr_len"]):
             raise ValueError(f"pack['nbr_col'] must be a contiguous int16 [{int(pack['nbr_len'])}] tensor on {self.device} (policies.meta_neighbours)")
         q.nbr_ptr, q.nbr_col = ptr.data_ptr(), col.data_ptr()
-        q.b3, q.role, q.k, q.n_types, q.n_exploits, q.n_apps = float(pack["b3"]), _role(role)["code"], k, T, E, A
+        q.role, q.k, q.n_types, q.n_exploits, q.n_apps = _role(role)["code"], k, T, E, A
         q.id_dim, q.embed_dim, q.proj_dim, q.Hp, q.H1, q.H2 = ID, ED, P, Hp, H1, H2
-        q.h0, q.h0_stride = h0.data_ptr(), int(h0.stride(0)) if n > 1 else int(h0.shape[1])
+        q.h0, q.h0_stride = h0.data_ptr(), row_stride
         keep = []
-        if flags_fixed is not None:
-            keep.append(_exactly(M, flags_fixed.reshape(-1), torch.uint8, self.device, "flags_fixed"))
-            q.flags_fixed = keep[-1].data_ptr()
+        if pop:
+            b3s = pack["b3s"]
+            if not isinstance(b3s, torch.Tensor) or not ok(b3s) or not b3s.is_contiguous() or int(b3s.numel()) != S_:
+                raise ValueError(f"pack['b3s'] must be a contiguous float32 [{S_}] tensor on {self.device}")
+            mp = abi.MetaPop()
+            mp.tile_slot, mp.b3s, mp.n_slots, mp.n_tiles, mp.h0_group_stride = tile_slot.data_ptr(), b3s.data_ptr(), S_, n // 16, group_stride
+            keep += [tile_slot, h0]
+            if flags_fixed is not None:
+                if not isinstance(flags_fixed, torch.Tensor) or flags_fixed.dtype != torch.uint8 or flags_fixed.device != self.device or \
+                        not flags_fixed.is_contiguous() or tuple(flags_fixed.shape) != (S_, M):
+                    raise ValueError(f"flags_fixeds must be a contiguous uint8 [{S_}, {M}] tensor on {self.device}")
+                mp.flags_fixeds = flags_fixed.data_ptr()
+        else:
+            q.b3 = float(pack["b3"])
+            if flags_fixed is not None:
+                keep.append(_exactly(M, flags_fixed.reshape(-1), torch.uint8, self.device, "flags_fixed"))
+                q.flags_fixed = keep[-1].data_ptr()
         if type_map is not None:
             keep.append(_exactly(T, type_map, torch.int32, self.device, "type_map"))
             q.type_map = keep[-1].data_ptr()
@@ -1473,8 +1535,8 @@ class BatchedCyberDefenseEnv:
                     raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on {self.device}")
                 setattr(q, name, t.data_ptr())
         q.status = self.status.data_ptr()
-        r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
-        _lib.check(self.lib.cygym_meta_decode(self._h, C.byref(q), C.byref(dst), self._stream()), self._h, "cygym_meta_decode")
+        keep.append(_bind_rows(self, q, rows, n))   # (alive until the call has returned)
+        return q, mp, dst, keep
 
     def meta_select(self, rows, h0: torch.Tensor, pack, role: str = "defender", snapshot=None, selected_out=None, ebar_out=None,
                     score_out=None, deg_out=None):

@@ -61,6 +61,7 @@ INST_HIER_POP = os.path.join(HERE, "csrc", "cg_inst_hier_pop.hip")
 INST_HMARL = os.path.join(HERE, "csrc", "cg_inst_hmarl.hip")
 INST_HMARL_TRAIN = os.path.join(HERE, "csrc", "cg_inst_hmarl_train.hip")
 INST_META = os.path.join(HERE, "csrc", "cg_inst_meta.hip")
+INST_META_POP = os.path.join(HERE, "csrc", "cg_inst_meta_pop.hip")
 INST_META_SELECT = os.path.join(HERE, "csrc", "cg_inst_meta_select.hip")
 INST_EVAL = os.path.join(HERE, "csrc", "cg_inst_eval.hip")
 INST_DDPG = os.path.join(HERE, "csrc", "cg_inst_ddpg.hip")
@@ -103,6 +104,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         units.append(("inst_hmarl", base + ["-c", INST_HMARL, "-o", os.path.join(tmp, "inst_hmarl.o")]))   # the H-MARL decode
         units.append(("inst_hmarl_train", base + ["-c", INST_HMARL_TRAIN, "-o", os.path.join(tmp, "inst_hmarl_train.o")]))   # its training decision
         units.append(("inst_meta", base + ["-c", INST_META, "-o", os.path.join(tmp, "inst_meta.o")]))   # the MetaDOAR decode
+        units.append(("inst_meta_pop", base + ["-c", INST_META_POP, "-o", os.path.join(tmp, "inst_meta_pop.o")]))   # ... for a population of strategies
         units.append(("inst_meta_select", base + ["-c", INST_META_SELECT, "-o", os.path.join(tmp, "inst_meta_select.o")]))   # its observer's selection
         units.append(("inst_eval", base + ["-c", INST_EVAL, "-o", os.path.join(tmp, "inst_eval.o")]))   # its evaluate / backward (the PPO update)
         units.append(("inst_ddpg", base + ["-c", INST_DDPG, "-o", os.path.join(tmp, "inst_ddpg.o")]))   # the critic's tail and its backward (the DDPG update)

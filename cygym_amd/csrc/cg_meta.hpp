@@ -1,7 +1,8 @@
 // cg_meta.hpp -- cygym_meta_decode: MetaHierarchicalBestResponse.execute (meta_hierarchical_br.py:660-790, the MetaDOAR best response:
 // a controller scores every device from a structural embedding and a projection of the state, keeps the best `k` visible ones, and the
 // role's DDPG critic picks one action type per kept device) for a batch, in ONE launch.  Included through cg_decode.hpp; instantiated in
-// cg_inst_meta.hip.  cygym_abi.h states the contract.
+// cg_inst_meta.hip (meta_pop_kernel, the same decode for a population of strategies: cg_inst_meta_pop.hip; the staging and the steps
+// below are cg_meta_body.inc, the text both kernels include).  cygym_abi.h states the contract.
 //
 // One wave per source row, `mt_waves` rows per workgroup: the workgroup stages what every row reads of the critic -- packed W2 (up to
 // 64 KB), the type columns, the exploit-0 column, b2, w3 -- and the three feature columns of node_proj.0 into LDS ONCE, behind the only
@@ -90,202 +91,56 @@ __global__ __launch_bounds__(MT_THREADS_MAX) void meta_kernel(cygym_meta q, cygy
   const MtPlan pl = mt_plan(H1, H2, T, ED, Hp, M);
   const int hp = pl.hp, ed4 = pl.ed4, nw = pl.mp >> 6;
   const float* w1a = q.w1a_t;
-  // ---------------- stage what every row of the workgroup reads ----------------
+  auto h0_row = [&](const int srow_, const int) -> const float* { return q.h0 + (size_t)srow_ * q.h0_stride; };
+#include "cg_meta_body.inc"
+}
+
+// cygym_meta_decode_pop: the same decode for a POPULATION of same-shaped strategies (controller + critic) in one launch -- source row r
+// reads the tables of strategy s = pop.tile_slot[r / 16].  The work shape is meta_kernel's, unchanged: one wave per source row,
+// wpb = mt_waves(...) rows per workgroup behind ONE staged critic, a grid of 16 n_tiles / wpb workgroups.  wpb is 8, 4, 2 or 1 and every
+// one of them divides 16, so the wpb rows of a workgroup lie in one tile and the slot is uniform over the workgroup: it is read once
+// into a scalar, the per-slot pointers (every table of slot s behind that of slot s - 1, sized from M, T, E, A and the widths as the
+// host sizes them) are rebased ahead of the staging, and from there on the staging and steps 1-6 are the text of meta_kernel<OUTS>
+// (cg_meta_body.inc) with `q` pointing at the slot's tables: LDS plan mt_plan unchanged, no atomics beyond the degree pass's, no draw.
+// A workgroup whose slot is outside 0 .. n_slots - 1 returns before the barrier: it writes nothing.  Flags: the env's, or the slot's
+// row of pop.flags_fixeds (q.flags_fixed is not read; the host passes neither `live` nor `extra` then).  h0_group_stride > 0: h0 is
+// [n_slots][n_envs][h0_stride] and the wave of env `row` reads block `slot` at row `row`.  (Staging the critic once per 16-row tile with
+// several rows per wave is a different work shape and not attempted here.)  Instantiated in cg_inst_meta_pop.hip.
+template <bool OUTS>
+__global__ __launch_bounds__(MT_THREADS_MAX) void meta_pop_kernel(cygym_meta q, cygym_meta_pop pop, cygym_actions dst, int n_envs, const int32_t* ienv,
+                                                                  uint64_t seed, int64_t env_id_base, const uint8_t* live, const uint32_t* extra,
+                                                                  int K, int M) {
+  (void)seed; (void)env_id_base;   // (the decode makes no draw)
+  extern __shared__ __align__(16) uint8_t smem[];
+  float* lds = reinterpret_cast<float*>(smem);
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nthreads = (int)blockDim.x;
+  const int r = lane & 15, kk = lane >> 4;
+  const int tile = (int)(blockIdx.x * (uint32_t)(nthreads >> 6)) >> 4;   // (the host launches 16 n_tiles / wpb workgroups: tile < n_tiles)
+  const int slot = __builtin_amdgcn_readfirstlane(pop.tile_slot[tile]);
+  if (slot < 0 || slot >= pop.n_slots) return;   // (uniform over the workgroup: before the barrier)
+  const int T = q.n_types, H1 = q.H1, H2 = q.H2, ED = q.embed_dim, P = q.proj_dim, Hp = q.Hp;
+  const int G1 = H1 >> 4, nt2 = H2 >> 4;
+  const MtPlan pl = mt_plan(H1, H2, T, ED, Hp, M);
+  const int hp = pl.hp, ed4 = pl.ed4, nw = pl.mp >> 6;
   {
-    const float4* s = reinterpret_cast<const float4*>(q.w2);
-    float4* d = reinterpret_cast<float4*>(lds + pl.w2);
-    for (int i = tid; i < (H1 * H2) >> 2; i += nthreads) d[i] = s[i];
-    for (int i = tid; i < T * H1; i += nthreads) {
-      const int t = i / H1, k = i - t * H1;
-      lds[pl.col_t + t * hp + k] = w1a[i];
-    }
-    for (int k = tid; k < H1; k += nthreads) lds[pl.col_x + k] = w1a[(size_t)(T + M) * H1 + k];   // exploit 0
-    for (int k = tid; k < H2; k += nthreads) {
-      lds[pl.b2 + k] = q.b2 ? q.b2[k] : 0.f;
-      lds[pl.w3 + k] = q.w3[k];
-    }
-    for (int i = tid; i < 3 * ed4; i += nthreads) lds[pl.wf + i] = q.w_feat[i];
+    const size_t s = (size_t)slot;
+    q.sp_w2_t += s * (size_t)Hp * P;
+    q.sp_b2 += s * P;
+    q.base += s * (size_t)M * ed4;
+    q.w_feat += s * 3 * ed4;
+    q.np_w2 += s * (size_t)P * ED;
+    q.np_b2 += s * P;
+    q.w1a_t += s * (size_t)(T + M + q.n_exploits + q.n_apps) * H1;
+    q.w2 += s * (size_t)H1 * H2;
+    if (q.b2) q.b2 += s * H2;
+    q.w3 += s * H2;
+    q.b3 = pop.b3s[slot];
+    q.flags_fixed = pop.flags_fixeds ? pop.flags_fixeds + s * M : nullptr;
   }
-  __syncthreads();
-  const int srow = blockIdx.x * (nthreads >> 6) + wave;
-  if (srow >= q.n) return;   // (uniform per wave; no workgroup barrier below)
-  const int row = q.rows ? q.rows[srow] : srow;
-  if (row < 0 || row >= n_envs) return;
-  float* wl = lds + pl.wave0 + wave * pl.wave_pitch;
-  float *hs = wl + pl.hs, *bw = wl + pl.bw, *hr = wl + pl.hr, *proj = wl + pl.proj, *uu = wl + pl.u, *qrow = wl + pl.q;
-  uint32_t* sd = reinterpret_cast<uint32_t*>(wl + pl.sd);
-  uint64_t *vm = reinterpret_cast<uint64_t*>(wl + pl.vm), *sm = reinterpret_cast<uint64_t*>(wl + pl.sm);
-  int* ids = reinterpret_cast<int*>(wl + pl.ids);
-  const bool fixed = q.flags_fixed != nullptr, att = q.role == 2;
-  const uint8_t* fl = fixed ? q.flags_fixed : live + (size_t)row * 4 * M;   // plane 0 of the env's live planes = the flags
-  auto vis_of = [&](const int d) -> bool { return (vm[d >> 6] >> (d & 63)) & 1ull; };
-  // ---------------- 1. visibility (meta_hierarchical_br.py:122-137) ----------------
-  int nvis = 0;
-  for (int c = 0; c < nw; ++c) {
-    const int d = WAVE * c + lane;
-    const uint32_t f = d < M ? fl[d] : CG_F_NYA;
-    const bool v = att ? (f & (CG_F_KNOWN | CG_F_OWNED | CG_F_NYA)) == (CG_F_KNOWN | CG_F_OWNED) : (f & (CG_F_NYA | CG_F_OWNED)) == 0u;
-    const uint64_t m = __ballot(d < M && v);
-    if (lane == 0) { vm[c] = m; sm[c] = 0ull; }
-    nvis += __popcll(m);
-  }
-  wsync();
-  // ---------------- 2. degrees (:25-68, :74-119) ----------------
-  for (int c = 0; c < nw; ++c) {
-    const int d = WAVE * c + lane;
-    int deg = 0;
-    if (d < M) {
-      const int p0 = q.nbr_ptr[d], p1 = q.nbr_ptr[d + 1];
-      if (!att) deg = p1 - p0;
-      else if (vis_of(d))
-        for (int p = p0; p < p1; ++p) deg += vis_of((int)q.nbr_col[p]) ? 1 : 0;
-    }
-    sd[d] = (uint32_t)deg;
-  }
-  wsync();
-  if (extra && !fixed) {   // (uniform) the edges evolve_network added to this env
-    const uint32_t* xk = extra + (size_t)row * (size_t)CG_X_WORDS(K);
-    int nx = (int)CG_E_NX(ienv[(size_t)row * CG_I_COUNT + CG_I_FLAGS]);
-    nx = nx < K ? nx : K;
-    for (int j = lane; j < nx; j += WAVE) {
-      const uint32_t key = xk[j], a = key >> 16, b = key & 0xFFFFu;
-      bool on = a != b && a < (uint32_t)M && b < (uint32_t)M && (j == 0 || xk[j - 1] != key);   // a repeated key counts once
-      const uint32_t rk = (b << 16) | a;
-      if (on && rk < key && mt_has_key(xk, nx, rk)) on = false;                                 // ... and so does a reciprocal pair
-      if (on && mt_has(q.nbr_col + q.nbr_ptr[a], q.nbr_ptr[a + 1] - q.nbr_ptr[a], b)) on = false;   // already an edge of the base graph
-      if (on && att && !(vis_of((int)a) && vis_of((int)b))) on = false;
-      if (on) { atomicAdd(&sd[a], 1u); atomicAdd(&sd[b], 1u); }
-    }
-    wsync();
-  }
-  int dmax = 0;
-  for (int c = 0; c < nw; ++c) {
-    const int d = WAVE * c + lane;
-    const int deg = (int)sd[d];
-    dmax = deg > dmax ? deg : dmax;
-    if (OUTS && q.deg_out && d < M) q.deg_out[(size_t)srow * M + d] = deg;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(dmax, off); dmax = o > dmax ? o : dmax; }
-  // ---------------- 3. proj (:190-199) and the fold of node_proj.2 ----------------
-  {
-    const float* hrow = q.h0 + (size_t)srow * q.h0_stride;
-    for (int j = lane; j < Hp; j += WAVE) hr[j] = hr_relu(hrow[j]);
-    for (int k = lane; k < H1; k += WAVE) hs[k] = hrow[Hp + k];
-  }
-  wsync();
-  if (lane < P) {
-    float acc = q.sp_b2[lane];
-    for (int j = 0; j < Hp; ++j) acc = fmaf(q.sp_w2_t[(size_t)j * P + lane], hr[j], acc);
-    proj[lane] = acc;
-  }
-  wsync();
-  float c0 = 0.f;
-  for (int p = 0; p < P; ++p) c0 = fmaf(q.np_b2[p], proj[p], c0);
-  {
-    float acc = 0.f;
-    if (lane < ED)
-      for (int p = 0; p < P; ++p) acc = fmaf(q.np_w2[(size_t)p * ED + lane], proj[p], acc);
-    uu[lane] = acc;   // (0 past embed_dim: the padding of base adds nothing)
-  }
-  wsync();
-  // ---------------- 4. scores (:150-185, :314-318, :427) ----------------
-  const float fmax_deg = (float)dmax;
-  const float *wdeg = lds + pl.wf, *wkn = wdeg + ed4, *wow = wkn + ed4;
-  for (int c = 0; c < nw; ++c) {
-    const int d = WAVE * c + lane;
-    uint32_t ob = 0u;
-    if (d < M) {
-      const float fd = (float)(int)sd[d];
-      const float degn = dmax > 0 ? __fdiv_rn(fd, fmax_deg) : fd;   // :163-164, the correctly rounded quotient
-      const uint32_t f = fl[d];
-      const bool kn = (f & CG_F_KNOWN) != 0u, ow = (f & CG_F_OWNED) != 0u;
-      const float4* brow = reinterpret_cast<const float4*>(q.base + (size_t)d * ed4);
-      float acc = c0;
-      for (int e4 = 0; e4 < ed4; e4 += 4) {
-        const float4 b = brow[e4 >> 2];
-        const float xb[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float x = fmaf(wdeg[e4 + i], degn, xb[i]);
-          x = kn ? x + wkn[e4 + i] : x;
-          x = ow ? x + wow[e4 + i] : x;
-          acc = fmaf(hr_relu(x), uu[e4 + i], acc);
-        }
-      }
-      if (OUTS && q.score_out) q.score_out[(size_t)srow * M + d] = acc;
-      if (vis_of(d)) { ob = float_order_bits(acc); ob = ob ? ob : 1u; }   // (0 is "not a candidate")
-    }
-    sd[d] = ob;
-  }
-  wsync();
-  // ---------------- 5. the min(k, |V|) best visible devices (:435-446) ----------------
-  const int kx = q.k < nvis ? q.k : nvis;
-  for (int rnd = 0; rnd < kx; ++rnd) {
-    uint32_t bh = 0u, bl = 0u;
-    for (int c = 0; c < nw; ++c) {
-      const int d = WAVE * c + lane;
-      const uint32_t ob = sd[d];
-      if (ob > bh) { bh = ob; bl = ~(uint32_t)d; }   // ascending d per lane: the lowest id among equals
-    }
-    const int w = wave_first_max(bh, bl);   // (never empty: rnd < the visible devices left)
-    if (lane == 0) { sd[w] = 0u; sm[w >> 6] |= 1ull << (w & 63); }
-    wsync();
-  }
-  {
-    int cnt = 0;
-    for (int c = 0; c < nw; ++c) {
-      const bool on = (sm[c] >> lane) & 1ull;
-      const uint64_t m = __ballot(on);
-      if (on) ids[cnt + below(m)] = WAVE * c + lane;   // (cnt + prefix < kx <= 32)
-      cnt += __popcll(m);
-    }
-    wsync();
-  }
-  if (OUTS && q.selected_out && lane < q.k) q.selected_out[(size_t)srow * q.k + lane] = lane < kx ? ids[lane] : -1;
-  // ---------------- 6. the critic's type per kept device (:516-523, :638-655), the groups (:759-763) ----------------
-  const int G = dst.max_groups, L = dst.max_devs;
-  const RowGroups og(dst, row);
-  int16_t* out = const_cast<int16_t*>(dst.dev_idx) + (size_t)row * L;
-  if (kx == 0) {   // (uniform) nothing visible (:699-717): [(0, [0], [], 0)], the literal type 0
-    if (lane == 0) {
-      og.set(0, 0, 0, 1, 0);
-      og.dev_cnt[0] = 0;
-      const_cast<int32_t*>(dst.n_groups)[row] = 1;
-    }
-    return;
-  }
-  const float4* w2l = reinterpret_cast<const float4*>(lds + pl.w2) + lane;
-  for (int i = 0; i < kx; ++i) {
-    const int d = __builtin_amdgcn_readfirstlane(ids[i]);
-    for (int k = lane; k < H1; k += WAVE) bw[k] = hs[k] + w1a[(size_t)(T + d) * H1 + k];
-    wsync();
-    for (int j = 0; 16 * j < T; ++j) {
-      const int t = 16 * j + r, tc = t < T ? t : T - 1;   // (rows past the last type: the last one again, never stored)
-      const float *p0 = bw + 4 * kk, *p1 = lds + pl.col_t + tc * hp + 4 * kk, *p2 = lds + pl.col_x + 4 * kk;
-#include "cg_critic_tile.inc"
-      const int to = 16 * j + 4 * kk + r;   // lanes r < 4 store row 4 kk + r
-      const float qv = r == 0 ? part[0] : r == 1 ? part[1] : r == 2 ? part[2] : part[3];
-      if (r < 4 && to < T) {
-        const float qq = ca_nan_to_num(qv + q.b3);
-        qrow[to] = qq;
-        if (OUTS && q.q_out) q.q_out[((size_t)srow * q.k + i) * T + to] = qq;
-      }
-    }
-    wsync();
-    uint32_t bh = 0u, bl = 0u;
-    if (lane < T && i * T + lane < CG_META_MAX_CANDIDATES) { bh = float_order_bits(qrow[lane]); bl = ~(uint32_t)lane; }   // :575-577
-    int at = wave_first_max(bh, bl);
-    if (q.type_map) at = q.type_map[at];
-    if (lane == 0 && i < G) {
-      og.set(i, at, 0, 1, 0);
-      og.dev_cnt[i] = i < L ? 1 : 0;
-      if (i < L) out[i] = (int16_t)d;
-    }
-    wsync();   // (the next device rewrites the base row and the Q row)
-  }
-  if (lane == 0) {
-    const_cast<int32_t*>(dst.n_groups)[row] = kx < G ? kx : G;
-    if (kx > G || kx > L) RowGroups::truncated(q.status);
-  }
+  const float* w1a = q.w1a_t;
+  const int64_t h0_block = (int64_t)slot * pop.h0_group_stride;
+  auto h0_row = [&](const int srow_, const int row_) -> const float* {
+    return pop.h0_group_stride > 0 ? q.h0 + h0_block + (size_t)row_ * q.h0_stride : q.h0 + (size_t)srow_ * q.h0_stride;
+  };
+#include "cg_meta_body.inc"
 }

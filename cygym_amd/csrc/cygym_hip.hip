@@ -128,6 +128,9 @@ extern template __global__ void hmarl_kernel<true, true>(cygym_hmarl, cygym_acti
 namespace cygym_k {
 extern template __global__ void meta_kernel<false>(cygym_meta, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
 extern template __global__ void meta_kernel<true>(cygym_meta, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
+// ... and for a population of strategies (cg_inst_meta_pop.hip)
+extern template __global__ void meta_pop_kernel<false>(cygym_meta, cygym_meta_pop, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
+extern template __global__ void meta_pop_kernel<true>(cygym_meta, cygym_meta_pop, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint32_t*, int, int);
 }  // namespace cygym_k
 
 // the MetaDOAR observer's selection lives in its own unit (cg_inst_meta_select.hip): declared, not instantiated, here
@@ -334,6 +337,7 @@ int cygym_sizeof(int32_t which) {
     case 44: return (int)sizeof(cygym_critic_pop);   // (index 43 stays unassigned)
     case 46: return (int)sizeof(cygym_comm_actor_pop);   // (index 45 stays unassigned)
     case 48: return (int)sizeof(cygym_hier_pop);   // (index 47 stays unassigned)
+    case 50: return (int)sizeof(cygym_meta_pop);   // (index 49 stays unassigned)
     default: return -1;
   }
 }
@@ -1457,15 +1461,17 @@ int cygym_hmarl_sample_decode(cygym_handle* h, const cygym_hmarl* q, const cygym
   return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &dstatic, &M, tr});
 }
 
-int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions* dst, void* stream) {
-  const char* const who = "cygym_meta_decode";
-  const char* const bad_layout = "cygym_meta_decode: bad layout (types, exploits >= 1, role 1 or 2, h0_stride >= Hp + H1, 16-byte aligned base / w_feat / packed w2)%s";
+// What cygym_meta_decode and cygym_meta_decode_pop check alike, in the order a caller sees (own_ptrs: the pointers of the function's
+// own descriptors are there; fixed_flags: the flags are a given snapshot, the bound state is not read), then the rows per workgroup
+// and the LDS of the launch.
+static int check_meta(cygym_handle* h, const cygym_meta* q, const cygym_actions* dst, const char* who, const char* bad_layout, bool own_ptrs,
+                      bool fixed_flags, int* wpb, size_t* lds) {
   // the checks the decodes share, on this call's layout: T types, the handle's devices, E exploits, A apps
   cygym_action_vectors lay;
   memset(&lay, 0, sizeof(lay));
   if (h && q) { lay.n_types = q->n_types; lay.n_devices = h->t.M; lay.n_exploits = q->n_exploits; lay.n_apps = q->n_apps; }
   const bool own = q && q->h0 && q->sp_w2_t && q->sp_b2 && q->base && q->w_feat && q->np_w2 && q->np_b2 && q->nbr_ptr && q->nbr_col && q->w1a_t &&
-                   q->w2 && q->w3;
+                   q->w2 && q->w3 && own_ptrs;
   if (const int rc = check_vectors(h, q ? &lay : nullptr, dst, who, own, 1, bad_layout)) return rc;
   if (const int rc = check_dst(h, dst, who, true)) return rc;
   if ((q->role != 1 && q->role != 2) || q->Hp < 1 || q->H1 < 1 || (long long)q->h0_stride < (long long)q->Hp + q->H1 ||
@@ -1477,13 +1483,22 @@ int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions*
     return fail(h, CYGYM_EUNSUPPORTED, "%s: k, action types 1 .. 32, at most CG_MAX_EXPLOITS exploits, id_dim 1 .. 32, embed_dim, proj_dim 1 .. 64, Hp 1 .. 256", who);
   if (q->H1 < 16 || q->H1 > MT_MAX_H || (q->H1 & 15) || q->H2 < 16 || q->H2 > MT_MAX_H || (q->H2 & 15))
     return fail(h, CYGYM_EUNSUPPORTED, "%s: critic widths H1, H2 must be multiples of 16 in 16 .. 128", who);
-  if (!q->flags_fixed && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (without flags_fixed the flags and the added edges are read off the bound state)", who);
+  if (!fixed_flags && !h->bound) return fail(h, CYGYM_ENOTBOUND, "%s: handle not bound (without flags_fixed the flags and the added edges are read off the bound state)", who);
   if (const int rc = check_rows(h, q->n, q->rows, 0, who)) return rc;
+  const MtPlan pl = mt_plan(q->H1, q->H2, q->n_types, q->embed_dim, q->Hp, h->t.M);
+  *wpb = mt_waves(pl, CG_LDS_BYTES);
+  *lds = (size_t)(pl.wave0 + *wpb * pl.wave_pitch) * sizeof(float);
+  return CYGYM_OK;
+}
+
+int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_meta_decode";
+  const char* const bad_layout = "cygym_meta_decode: bad layout (types, exploits >= 1, role 1 or 2, h0_stride >= Hp + H1, 16-byte aligned base / w_feat / packed w2)%s";
+  int wpb = 0;
+  size_t lds = 0;
+  if (const int rc = check_meta(h, q, dst, who, bad_layout, true, q && q->flags_fixed, &wpb, &lds)) return rc;
   if (q->n == 0) return CYGYM_OK;
   HIPCHK(h, hipSetDevice(h->device_id));
-  const MtPlan pl = mt_plan(q->H1, q->H2, q->n_types, q->embed_dim, q->Hp, h->t.M);
-  const int wpb = mt_waves(pl, CG_LDS_BYTES);
-  const size_t lds = (size_t)(pl.wave0 + wpb * pl.wave_pitch) * sizeof(float);
   if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the critic and a row's buffers do not fit in LDS", who);
   const void* k = (q->score_out || q->selected_out || q->q_out || q->deg_out) ? (const void*)meta_kernel<true> : (const void*)meta_kernel<false>;
   if (const int rc = raise_lds_once(h, k)) return rc;
@@ -1492,6 +1507,29 @@ int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions*
   const uint32_t* extra = env_mode && h->t.K > 0 ? (const uint32_t*)h->b.extra : nullptr;
   int K = h->t.K, M = h->t.M;
   return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &extra, &K, &M});
+}
+
+int cygym_meta_decode_pop(cygym_handle* h, const cygym_meta* q, const cygym_meta_pop* pop, const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_meta_decode_pop";
+  const char* const bad_layout = "cygym_meta_decode_pop: bad layout (types, exploits >= 1, role 1 or 2, h0_stride >= Hp + H1, 16-byte aligned base / w_feat / packed w2)%s";
+  int wpb = 0;
+  size_t lds = 0;
+  if (const int rc = check_meta(h, q, dst, who, bad_layout, pop && pop->tile_slot && pop->b3s && q && q->rows, pop && pop->flags_fixeds, &wpb, &lds))
+    return rc;
+  if (const int rc = check_pop(h, who, pop->n_slots, CG_META_POP_MAX, "%s: 1 to CG_META_POP_MAX strategies", nullptr, pop->n_tiles, true, q->n,
+                               pop->h0_group_stride, (int64_t)(h->n_envs - 1) * q->h0_stride + q->Hp + q->H1,
+                               "%s: h0_group_stride is 0 (h0 by source row) or at least one block, (n_envs - 1) h0_stride + Hp + H1")) return rc;
+  if (q->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  if (lds > CG_LDS_BYTES) return fail(h, CYGYM_EUNSUPPORTED, "%s: the critic and a row's buffers do not fit in LDS", who);
+  const void* k = (q->score_out || q->selected_out || q->q_out || q->deg_out) ? (const void*)meta_pop_kernel<true> : (const void*)meta_pop_kernel<false>;
+  if (const int rc = raise_lds_once(h, k)) return rc;
+  const bool env_mode = !pop->flags_fixeds;
+  const uint8_t* live = env_mode ? (const uint8_t*)h->b.live : nullptr;
+  const uint32_t* extra = env_mode && h->t.K > 0 ? (const uint32_t*)h->b.extra : nullptr;
+  int K = h->t.K, M = h->t.M;
+  // wpb rows per workgroup as in cygym_meta_decode; wpb divides 16, so a workgroup's rows lie in one tile
+  return launch_decode(h, k, dim3(16 * pop->n_tiles / wpb), dim3(wpb * WAVE), lds, stream, {q, pop, dst}, {&live, &extra, &K, &M});
 }
 
 int cygym_meta_select(cygym_handle* h, const cygym_meta_select_desc* q, void* stream) {

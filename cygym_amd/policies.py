@@ -2916,6 +2916,8 @@ class MetaPolicy:
             self.flags = flags.reshape(-1).to(torch.uint8).contiguous()
         self.type_map = None if type_map is None else torch.as_tensor(type_map, dtype=torch.int32)
         self.action_types = sorted({0} | (set(range(self.n_types)) if type_map is None else {int(x) for x in self.type_map.tolist()}))
+        # what MetaPolicyGroup.key compares, taken here on the host: the planner and write() never read the device for it
+        self.type_map_key = None if type_map is None else tuple(int(x) for x in self.type_map.tolist())
 
     _map = ActorPolicy._map
 
@@ -2991,6 +2993,87 @@ class MetaPolicy:
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("a MetaPolicy reads the flags and the graph of the env it decides for and answers with groups: it runs "
                                   "through write(), on a batch with cygym_meta_decode (MetaNet.decide is the torch form)")
+
+
+class MetaPolicyGroup(_TiledPopulation):
+    """A population of MetaPolicy (MetaDOAR) strategies of ONE shape (key) decided together: h0 of all of them is one batched GEMM and
+    the decode of all of them is ONE launch (cygym_meta_decode_pop), the controller and the critic of a tile of 16 rows taken from a
+    slot table.  The decode gives a workgroup 8 rows (4 at the upper limits) behind 64 KB and more of staged critic, so a launch per
+    strategy over that strategy's few rows leaves most of the chip idle; the |D| x |A| grid of a Double-Oracle population with
+    --BR_type meta and the opponent drawn per env from an equilibrium (MixturePolicy) hold several such strategies, each deciding for a
+    few envs.  The members may carry different critics or all the same one: the stack holds one critic per slot either way.
+    counts / in_tile_order / shared_obs: the three row conventions of _TiledPopulation.  write() takes the optional outputs of
+    meta_decode_pop by keyword.  It writes GROUPS, like its members."""
+
+    NOUN = "strategies"
+    MIN_MEMBERS = 4           # the smallest population simulate_grid groups: at two members the single launches already fill the
+    #                           chip once each and the grouped turn is slower (measured at S = 2 / 4 / 8 / 16, PERFLOG.md)
+    MIN_MEMBERS_MIXTURE = 2   # ... and the smallest MixturePolicy groups: one by one every member's launch walks ALL envs' masked
+    #                           rows, so the one launch over the draw's tiles wins from two members on (measured, PERFLOG.md)
+    writes_groups = True
+
+    def __init__(self, policies, counts=None, in_tile_order: bool = False):
+        super().__init__(policies, counts, in_tile_order)
+        p0 = self.policies[0]
+        k0 = self.key(p0, getattr(getattr(p0, "net", None), "M", 0))
+        if k0 is None or any(self.key(p, p0.net.M) != k0 for p in self.policies):
+            raise ValueError("the members are MetaPolicy of one key (MetaPolicyGroup.key)")
+        self.role, self.n_types, self.k, self.action_types = p0.role, p0.n_types, p0.k, list(p0.action_types)
+        self.state_dim, self.n_devices = p0.net.state_dim, p0.net.M
+
+    @staticmethod
+    def key(p, M):
+        """What must agree across the members of a population -- role, state width, M, id_dim / embed_dim / proj_dim / hidden, the
+        critic's H1 and H2, n_types, n_exploits, n_apps, k, the type map, env flags against a fixed snapshot -- or None when `p` is no
+        MetaPolicy.  Weights and critics may differ.  Host values only."""
+        if not isinstance(p, MetaPolicy):
+            return None
+        n = p.net
+        return (p.role, n.state_dim, n.M, n.id_dim, n.embed_dim, n.proj_dim, n.hidden, p.fc1.out_features, p.fc2.out_features,
+                p.n_types, p.n_exploits, p.n_apps, p.k, p.type_map_key, p.flags is None)
+
+    def groups_needed(self, M: int) -> int:
+        """The most groups (and list entries) a row can have: the members' select_k."""
+        return self.k
+
+    STACKED = ("sp_w2_t", "sp_b2", "base", "w_feat", "np_w2", "np_b2", "w1a_t", "w2", "b2", "w3")      # one table per slot, slot after slot
+
+    def _stacked(self, batch, device=None):
+        """The members' merged tables (MetaPolicy._packed) slot after slot, as the dict meta_decode_pop reads -- the STACKED tables,
+        b3s [S], the batched operands of h0: w0_t [S, W, Hp + H1], b0 [S, 1, Hp + H1] -- the population's neighbour lists and sizes, and
+        flags_fixeds [S, M] when the members carry snapshots.  Redone when a member's parameter changes (the members' own pack
+        versions, read after the packs were asked for) or the device does."""
+        packs = [p._packed(batch) for p in self.policies]
+
+        def build():
+            st = lambda k: torch.stack([pk[k] for pk in packs]).contiguous()  # noqa: E731
+            pk0 = packs[0]
+            dev = pk0["w0_t"].device
+            pack = {k: pk0[k] for k in ("id_dim", "embed_dim", "proj_dim", "Hp", "H1", "H2", "n_types", "n_exploits", "n_apps", "k",
+                                        "nbr_ptr", "nbr_col", "nbr_len")}
+            pack.update(S=len(packs), w0_t=st("w0_t"), b0=st("b0")[:, None, :].contiguous(),
+                        b3s=torch.cat([p.fc3.bias.detach().reshape(1).to(dev) for p in self.policies]).contiguous())      # (b3s: no host read)
+            for k in self.STACKED:
+                pack[k] = st(k)
+            if self.policies[0].flags is not None:
+                pack["flags_fixeds"] = torch.stack([p.flags for p in self.policies]).contiguous()
+            return pack
+        return self._cached(tuple((p.net._pk_ver, p._pk_ver) for p in self.policies), build)
+
+    def h0(self, obs_s, pack):
+        """[S, n, Hp + H1]: state_proj.fc1 | the critic's state part of every (strategy, row) of obs_s [S, n, W] (or an expanded
+        [n, W]), before the relu: one baddbmm."""
+        return torch.baddbmm(pack["b0"], obs_s, pack["w0_t"])
+
+    _first_layer = h0
+
+    def _launch(self, batch, act, rows, tile_slot, x, pack, **outs):
+        batch.meta_decode_pop(rows, tile_slot, x, pack, self.role, act=act, flags_fixeds=pack.get("flags_fixeds"),
+                              type_map=self.policies[0]._map(x.device), **outs)
+
+    def __call__(self, obs, t, M, L):
+        raise NotImplementedError("a MetaPolicyGroup reads the flags and the graph of the envs it decides for and answers with groups: it "
+                                  "runs through write(), on a batch with cygym_meta_decode_pop")
 
 
 # ---- the opponent drawn from an equilibrium mixture (do_agent.py:1447, IPPO.py:385-430, hierarchical_br.py:363) -------------------------
@@ -3071,7 +3154,10 @@ class MixturePolicy:
       5. among the other members, the HierarchicalPolicy (HAGS) of ONE key (HierarchicalPolicyGroup.key) that can play,
          HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE or more, when neither step 2 nor step 4 holds the member_slot table: one baddbmm
          forms h0 for every (net, env) and ONE cygym_hier_decode_pop decodes the draw's tiles (tiled = False: off);
-      6. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
+      6. among the other members, the MetaPolicy (MetaDOAR) of ONE key (MetaPolicyGroup.key) that can play,
+         MetaPolicyGroup.MIN_MEMBERS_MIXTURE or more, when none of steps 2, 4 and 5 holds the member_slot table: one baddbmm forms h0
+         for every (strategy, env) and ONE cygym_meta_decode_pop decodes the draw's tiles (tiled = False: off);
+      7. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
          rollout_grid.SequencePolicy + write_actions with the tick the loop set (set_tick: the loop's tick counter; a callable without
          uses_global_tick gets t // 2, as the loops call it).  A member of probability 0 never plays and is not launched.
     act["n_groups"] is the caller's to clear before the call (Turns.opponent, ddpg_rollout.collect do); a member that writes groups sets
@@ -3153,6 +3239,11 @@ class MixturePolicy:
         one member_slot table already serves an ActorPolicyGroup or a CommActorPolicyGroup (the HAGS members then play one by one)."""
         return self._same_key_group(batch, HierarchicalPolicyGroup, "hier_decode_pop", HierarchicalPolicyGroup.MIN_MEMBERS_MIXTURE, taken)
 
+    def _meta_group(self, batch, taken: bool):
+        """_same_key_group for the MetaPolicy members, MetaPolicyGroup.MIN_MEMBERS_MIXTURE or more.  taken: the draw's one member_slot
+        table already serves another population (the MetaDOAR members then play one by one)."""
+        return self._same_key_group(batch, MetaPolicyGroup, "meta_decode_pop", MetaPolicyGroup.MIN_MEMBERS_MIXTURE, taken)
+
     def _state(self, batch):
         st = self._st
         if st is None or st["batch"] is not batch:
@@ -3162,10 +3253,12 @@ class MixturePolicy:
             cgrp, cslots = self._same_key_group(batch, CoordAscentPolicyGroup, "coord_ascent_decode_pop")
             mgrp, mslots = self._comm_group(batch, grp is not None)
             hgrp, hslots = self._hier_group(batch, grp is not None or mgrp is not None)
-            # the draw reads ONE member_slot table: the actors', else the comm nets', else the HAGS nets' (at most one of the three lives)
-            slots = mslots if mgrp is not None else hslots if hgrp is not None else aslots
-            live = [(g, sl) for g, sl in ((grp, aslots), (cgrp, cslots), (mgrp, mslots), (hgrp, hslots)) if g is not None]
-            tiles = grp is not None or mgrp is not None or hgrp is not None
+            tgrp, tslots = self._meta_group(batch, grp is not None or mgrp is not None or hgrp is not None)
+            # the draw reads ONE member_slot table: the actors', else the comm nets', else the HAGS nets', else the MetaDOAR
+            # strategies' (at most one of the four lives)
+            slots = mslots if mgrp is not None else hslots if hgrp is not None else tslots if tgrp is not None else aslots
+            live = [(g, sl) for g, sl in ((grp, aslots), (cgrp, cslots), (mgrp, mslots), (hgrp, hslots), (tgrp, tslots)) if g is not None]
+            tiles = grp is not None or mgrp is not None or hgrp is not None or tgrp is not None
             T = (N + 15) // 16 + S_
             z = lambda shape, dt, v=0: torch.full(shape, v, dtype=dt, device=dev)  # noqa: E731
             st = self._st = dict(batch=batch, group=grp, slots=slots, cdf=torch.from_numpy(self.cdf).to(dev),
@@ -3174,7 +3267,7 @@ class MixturePolicy:
                                  index=z((N,), torch.uint8), rows_masked=z((S_, N), torch.int32, -1), rows_ok=None,
                                  rows_tiled=z((16 * T,), torch.int32, -1) if tiles else None,
                                  tile_slot=z((T,), torch.int32, -1) if tiles else None,
-                                 comm=mgrp, comm_slots=mslots, hier=hgrp, hier_slots=hslots,
+                                 comm=mgrp, comm_slots=mslots, hier=hgrp, hier_slots=hslots, meta=tgrp, meta_slots=tslots,
                                  critics=cgrp, critic_slots=cslots, critic_slot_of=torch.tensor(cslots, dtype=torch.int32, device=dev),
                                  slot_of_row=z((N,), torch.int32, -1) if cgrp is not None else None,
                                  live=[g for g, _ in live], held=[any(sl[s] >= 0 for _, sl in live) for s in range(S_)])
@@ -3203,7 +3296,7 @@ class MixturePolicy:
                            mode=act["mode"], rows_masked=st["rows_masked"], rows_tiled=st["rows_tiled"], tile_slot=st["tile_slot"])
         self.last_index = st["index"]
         in_place = obs.dtype == torch.float32 and obs.dim() == 2 and obs.stride(1) == 1 and int(obs.shape[0]) >= N
-        for g in (st["live"] if in_place else []):      # (in the order actors, critics, comm nets, HAGS nets)
+        for g in (st["live"] if in_place else []):      # (in the order actors, critics, comm nets, HAGS nets, MetaDOAR strategies)
             if isinstance(g, ActorPolicyGroup):
                 hidden, head = g._packed_all(batch)
                 p0 = g.policies[0]

@@ -1173,8 +1173,8 @@ typedef struct cygym_hier_pop {
  * 16 n_tiles; h0_group_stride < 0, or > 0 and smaller than one block, (n_envs - 1) h0_stride + 3 H.  CYGYM_ENOTBOUND only when the
  * flag plane is needed (vis_fixeds == NULL) and the handle is not bound.  Every other check, limit and message convention is that of
  * cygym_hier_decode.  Nothing is launched and nothing is written on a refusal.
- * Out of scope: the sampled (training) decision for a population; populations of `meta`, H-MARL and committee strategies; building
- * h0 on chip. */
+ * Out of scope: the sampled (training) decision for a population; populations of H-MARL and committee strategies (`meta`
+ * strategies: cygym_meta_decode_pop); building h0 on chip. */
 int cygym_hier_decode_pop(cygym_handle* h, const cygym_hier_net* net /* slot 0 */, const cygym_hier_pop* pop,
                           const cygym_action_vectors* layout, const cygym_actions* dst, void* stream);
 
@@ -1500,6 +1500,50 @@ typedef struct cygym_meta {
  *   ddpg_best_response -- select_devices with the frozen embedding cache -- is cygym_meta_select below; train_controller is a 64-row
  *   update of state_proj and stays with the caller, cygym_amd/meta_rollout.py.) */
 int cygym_meta_decode(cygym_handle* h, const cygym_meta* q, const cygym_actions* dst, void* stream);
+
+/* A population of same-shaped MetaDOAR strategies (controller + critic) for cygym_meta_decode_pop.  DEVICE pointers. */
+#define CG_META_POP_MAX 32   /* = CG_MIXTURE_MAX_MEMBERS */
+typedef struct cygym_meta_pop {
+  const int32_t* tile_slot;     /* [n_tiles] the strategy of tile t (source rows 16 t .. 16 t + 15): 0 .. n_slots - 1; any other value:
+                                   the tile is left alone                                                                             */
+  const uint8_t* flags_fixeds;  /* optional [n_slots][M] flag bytes: the ONE snapshot of every slot, used for all of its rows, base lists
+                                   only; NULL: every row reads the flags and the added edges of its env.  cygym_meta.flags_fixed is
+                                   not read                                                                                           */
+  const float*   b3s;           /* [n_slots] fc3.bias of every slot's critic (cygym_meta.b3 is not read)                              */
+  int64_t  h0_group_stride;     /* floats.  0: cygym_meta.h0 is [n][h0_stride] by source row, each row formed with ITS strategy.
+                                   > 0: h0 is [n_slots][n_envs][h0_stride], block s at s * h0_group_stride formed with strategy s, and
+                                   the row of env e in tile t reads block tile_slot[t] at row e                                       */
+  int32_t  n_slots;             /* 1 .. CG_META_POP_MAX                                                                               */
+  int32_t  n_tiles;             /* q->n = 16 * n_tiles                                                                                */
+} cygym_meta_pop;
+
+/* cygym_meta_decode for a population of strategies of ONE shape (role, k, every width, n_types / n_exploits / n_apps, M, the neighbour
+ * lists and type_map in common), in ONE launch: source row r -- visibility, the degrees with the env's added edges, proj and the
+ * fold, the scores, the min(k, |V|) arg-max rounds, the critic tile per kept device, CG_META_MAX_CANDIDATES, the literal type 0 of
+ * the empty row, the groups, CG_DECODE_TRUNCATED, every summation order -- is decoded exactly as cygym_meta_decode decodes it, with
+ * the controller and the critic of slot s = pop->tile_slot[r / 16].  A wave owns a row and shares nothing but the staged critic with
+ * the other rows of its workgroup, so a row's result is bit-identical whatever else shares its tile.  Where several strategies each
+ * decide for a few rows (the payoff grid of a double-oracle population with --BR_type meta, the opponent drawn per env from an
+ * equilibrium) one launch fills the chip that a launch per strategy of a few workgroups leaves mostly idle.
+ * The work shape is cygym_meta_decode's: mt_waves rows (8, 4, 2 or 1: a divisor of 16) per workgroup behind one staged critic, 16
+ * n_tiles / mt_waves workgroups; the rows of a workgroup lie in one tile.
+ * `q` describes slot 0: sp_w2_t [Hp][P], sp_b2 [P], base [M][ED4], w_feat [3][ED4], np_w2 [P][ED], np_b2 [P], w1a_t [n_out][H1], the
+ * packed w2 [H2 / 16][H1 / 16][64][4], b2 [H2] (NULL for all slots or given for all) and w3 [H2] of slot s follow those of slot s - 1
+ * contiguously -- base, w_feat and w2 are multiples of 16 bytes per slot, so the alignment of slot 0 carries over.  nbr_ptr, nbr_col,
+ * type_map, k, role and all widths are the population's; b3 and flags_fixed are not read (pop->b3s, pop->flags_fixeds: ONE form of
+ * flags for the whole population).  q->rows is MANDATORY: a tiled row list [16 n_tiles], 16 rows per tile, -1 = no row (skipped as in
+ * cygym_meta_decode, as is a row >= n_envs) -- the layout cygym_mixture_draw writes as rows_tiled / tile_slot.  The optional outputs
+ * of cygym_meta stay indexed by source row: [16 n_tiles] rows of them.  A tile whose slot is negative or >= n_slots writes NOTHING --
+ * no action row, no optional output, no status bit: its workgroups return before their barrier.  No draw; the rng tick is neither
+ * read nor advanced; no atomics beyond the degree pass's in LDS.
+ * CYGYM_EUNSUPPORTED: n_slots outside 1 .. CG_META_POP_MAX.  CYGYM_EINVAL: NULL pop, tile_slot, q->rows or b3s; q->n != 16 n_tiles;
+ * h0_group_stride < 0, or > 0 and smaller than one block, (n_envs - 1) h0_stride + Hp + H1.  CYGYM_ENOTBOUND only when the flags are
+ * needed (flags_fixeds == NULL) and the handle is not bound.  Every other check, limit and message convention is that of
+ * cygym_meta_decode.  Nothing is launched and nothing is written on a refusal.
+ * Out of scope: the sampled or observer decision (cygym_meta_select) for a population; populations of H-MARL and committee
+ * strategies; staging the critic once per tile with several rows per wave; building h0 on chip; M > 1000. */
+int cygym_meta_decode_pop(cygym_handle* h, const cygym_meta* q /* slot 0 */, const cygym_meta_pop* pop, const cygym_actions* dst,
+                          void* stream);
 
 /* The controller of a MetaDOAR strategy as cygym_meta carries it, WITHOUT the critic, plus the observer's own arrays.  DEVICE pointers;
  * the fields shared with cygym_meta mean what they mean there. */
