@@ -618,7 +618,16 @@ __device__ __forceinline__ void opaque_uniform(T& v) {
 //     ascending) rides in the same stages -- its first candidate comes from the candidate masks (uniform), so its
 //     stage-3 / 4 reads are the blocked word and T word of that one slot;
 //   * a verification sweep (only after a conflict) is ONE round trip for all blocks -- the T words of the picks -- and
-//     only the sources that lost theirs rescan, a short row with one staged slot (spread_scan_lane_st<1>).
+//     only the sources that lost theirs rescan, a short row with one staged slot (spread_scan_lane_st<1>);
+//   * MERGE (a constant of the kernel like WORDS: the per-tick kernels at 256 devices): the losers of blocks 0 and 1 -- up to 128
+//     sources, all there are in nearly every spread -- rescan as ONE group instead of block after block with a wsync between: a lane
+//     serves its loser of block 0, or else its loser of block 1, its packed registers picked by a select, so one staged chain
+//     (blocked pair + next neighbour, T word, take) and one copy of the full-row and cooperative rescans serve both blocks; a lane
+//     with a loser in both goes round again.  A take is then seen by the other block's rescans a sweep later than in the serial
+//     order -- it reports its conflict like any other take and the next sweep repairs it: 1 spread env-tick in 67 077 of the bench
+//     script takes one sweep more, the picks are the same (tests/spread_fixpoint_probe.cpp: never more than one extra sweep).
+//     Blocks 2 and 3 keep the serial text.  Staged for both blocks in every lane (two sets of reads, two takes, no branch) the sweep
+//     measured 140-340 cycles SLOWER than the serial one: most sweeps have losers in one block only (PERFLOG.md, r15_spread_verify).
 // Nothing derived from `n_src` is carried across the exploit loop or a block loop: the count is made opaque (an empty asm on its
 // SGPR) at the top of every exploit iteration and in front of the `b * 64 >= n_src` test of sweep 0, of the verification sweep
 // and of the log counts, so the per-block lane masks `lane + 64 b < n_src` with their complements, the clamped slist addresses
@@ -635,10 +644,20 @@ __device__ __forceinline__ void opaque_uniform(T& v) {
 // three-bit field and stored as 128 bits, the candidate masks as one byte per lane pair, the two lowest candidates from the ballot
 // of the lanes' nibbles.  Set-up of the slowest 1 % of spread envs 5.5 k -> 3.85 k cycles (PERFLOG.md, r14_spread_words); the apply
 // pass in word form measured -0.3 k on its phase and was dropped on the assembly (v_readlane in the spread over the bound).
-template <int MCT, bool WIDE, bool WORDS, class KP>
+template <int MCT, bool WIDE, bool WORDS, bool MERGE, int NS, class KP>
 __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const int32_t* expl, int ex0, int n_expl) {
   const int M = e.M, E1 = P.t.E > 0 ? P.t.E - 1 : 0;
   const int lane = e.lane;
+  // MERGE, the header words: the two that every exploit iteration tests are read ONCE, with the exploit row's address, in the batch of
+  // loads at the top -- left to the compiler they were read again from the argument block inside the loop, a scalar-cache round trip
+  // each, once the sweeps' registers had changed (set-up +180 cycles)
+  [[maybe_unused]] int zday = 0, nX = 0;
+  if constexpr (MERGE) { zday = P.c.zero_day; nX = P.t.X; opaque_uniform(zday); opaque_uniform(nX); asm volatile("" :: "s"(expl)); }
+  // ... and the last allocated word of the blocked mask and the log's running total are held in a VGPR: live across the sweeps as
+  // scalars they were parked in a spill VGPR and read back at every use (the total: one v_readfirstlane where the ring needs it)
+  [[maybe_unused]] int wlv = MERGE ? ((P.t.EW + 3) & ~3) - 1 : 0;   // (formed only where it is held: the other kernels' code stays as it was)
+  [[maybe_unused]] int logv = MERGE ? e.log_total : 0;   // NOTE: under MERGE e.log_total is STALE inside this function (written back at its end, the only exit): read logv
+  if constexpr (MERGE) asm volatile("" : "+v"(wlv), "+v"(logv));
   uint32_t* T = e.scr;                          // [Mp] first-compromise time (source id + 1) << 2 | eligibility bits
   uint16_t* slist = e.lsrc;                     // [Mp] the sources in id order (snapshot :1127)
   uint64_t* cand = (uint64_t*)e.marks;          // [MC] candidate-device bitmask (LDS copy for the per-lane rescans)
@@ -670,7 +689,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
   for (int jx = 0; jx < n_expl; ++jx) {
     opaque_uniform(n_src);   // (opaque per iteration: see above)
     int raw = jx == 0 ? ex0 : expl[jx];   // expl[0] was fetched with the tick's header
-    if (P.c.zero_day) {  // :1131-1146
+    if (MERGE ? zday : P.c.zero_day) {  // :1131-1146
       uint32_t mask = (uint32_t)P.c.zero_day_owned_mask;
       opaque_uniform(mask);   // its popcount and the tests on it are formed in this arm, by the iteration that draws
       bool in = raw >= 0 && raw < 32 && ((mask >> raw) & 1u);
@@ -681,7 +700,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
         raw = nth_bit32(mask, r);
       }
     }
-    if (raw < 0 || raw >= P.t.X) continue;
+    if (raw < 0 || raw >= (MERGE ? nX : P.t.X)) continue;
     const uint8_t ebit = (uint8_t)(1u << raw);
     // ---- T words and candidate masks from the flag / vulnerability bytes (device-major, one round trip) ----
     int u1 = -1, u2 = -1;   // the two lowest candidates (uniform): a full row's first pick is the lowest one that is not itself
@@ -728,7 +747,8 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
 #pragma unroll
     for (int b = 0; b < MCT; ++b) { sst[b] = 0; row[b] = 0; pkv[b] = 0; }
     bool lost_any = false;     // some take hit a target another source had taken in this tick: a verification sweep is due
-    constexpr int NS = 4;      // slots staged per row
+    // (NS: slots staged per row -- 2 in the kernels that merge, "the usual row has two slots": there `sweeps` measured -600 cycles against 4 and
+    // -320 against 3; slots from NS on are walked one by one; the other kernels keep 4)
     constexpr int BP = (WIDE && MCT >= 2) ? 2 : 1;   // blocks per staged group (two where the registers allow it: the kernels capped at 80 VGPRs spill with two)
 #pragma unroll
     for (int b0 = 0; b0 < MCT; b0 += BP) {
@@ -753,7 +773,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
         v0[q] = u1 == sv[q] ? u2 : u1;                                  // a full row's first candidate ...
         kf[q] = o0[q] + (v0[q] > 0 ? v0[q] : 0) - (v0[q] > sv[q] ? 1 : 0);   // ... sits at this slot
         const int base = full[q] ? kf[q] : o0[q];
-        const int w0 = base >> 5, wl = ((P.t.EW + 3) & ~3) - 1;
+        const int w0 = base >> 5, wl = MERGE ? wlv : ((P.t.EW + 3) & ~3) - 1;
         b_lo[q] = e.blk[w0]; b_hi[q] = e.blk[w0 < wl ? w0 + 1 : w0];
 #pragma unroll
         for (int j = 0; j < NS; ++j) { const int k = o0[q] + j; vv[q][j] = e.ocol[k < E1 ? k : E1]; }
@@ -786,7 +806,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
             const bool okv = (t & 1u) || ((t & 2u) && ((t >> 2) >= (uint32_t)(s + 1)));
             if (!found && j < len && !((bits >> j) & 1ull) && (dc || okv)) { found = true; k = o0[q] + j; v = vv[q][j]; low = t & 3u; }
           }
-          if (!found && len > NS) {   // slots 4..7 of a short row: one by one (few rows are that long)
+          if (!found && len > NS) {   // slots NS..7 of a short row: one by one
             uint64_t b2 = bits >> NS;
             for (int kk = o0[q] + NS; kk < o1[q]; ++kk, b2 >>= 1) {
               if (b2 & 1ull) continue;
@@ -830,8 +850,58 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
       uint32_t tv[MCT];
 #pragma unroll
       for (int b = 0; b < MCT; ++b) tv[b] = T[pkv[b] >> 16];
+      // MERGE: the losers of blocks 0 and 1 (up to 128 sources) rescan as ONE group: a lane serves the loser it owns in block 0, or else
+      // the one it owns in block 1 -- its packed registers picked by a select -- so both blocks' blocked pairs and next neighbours are one
+      // trip, their T words one trip, their takes one trip, and the full-row and cooperative rescans stand once for both blocks.  A lane
+      // that owns a loser in both blocks goes round a second time (rare).  One wsync at the end: a take of this group is seen by the
+      // other lanes' NEXT verification (it reports its conflict like any other take).  Blocks 2 and 3 keep the serial text.
+      constexpr int B0 = (MERGE && MCT >= 2) ? 2 : 0;   // the blocks the merged group serves
+      if constexpr (B0 == 2) {
+        opaque_uniform(n_src);
+        uint32_t pend = 0;   // bit b: this lane's source of block b lost its pick (an earlier source holds the target; reachable targets and dc sources never lose)
 #pragma unroll
-      for (int b = 0; b < MCT; ++b) {
+        for (int b = 0; b < 2; ++b) {
+          const int s = (int)(sst[b] & 0xFFFFu), o1 = (int)(row[b] >> 16), k0 = (int)(pkv[b] & 0xFFFFu);
+          if (b * WAVE + lane < n_src && k0 < o1 && !((sst[b] >> 16) & CG_D_DC) && !(tv[b] & 1u) && (tv[b] >> 2) < (uint32_t)(s + 1)) pend |= 1u << b;
+        }
+        if (ballot(pend != 0u) != 0ull) {
+          do {
+            const bool lost = pend != 0u, q1 = !(pend & 1u);   // block 0's loser first
+            const uint32_t sstq = q1 ? sst[1] : sst[0], rowq = q1 ? row[1] : row[0], pkvq = q1 ? pkv[1] : pkv[0];
+            const int s = (int)(sstq & 0xFFFFu), o0 = (int)(rowq & 0xFFFFu), o1 = (int)(rowq >> 16), k0 = (int)(pkvq & 0xFFFFu);
+            const bool shortrow = o1 - o0 <= LONG_ROW;
+            const bool full = !shortrow && ((sstq >> 16) & CG_D_FULLROW);
+            int k = k0, v = (int)(pkvq >> 16);
+            if (lost && (shortrow || full)) {   // (the stages of the serial text below)
+              uint32_t low = 0;
+              if (shortrow) { v = 0; k = spread_scan_lane_st<1>(e, T, s, false, k0 + 1, o1, v, low); }
+              else {
+                k = spread_scan_full(e, T, cand, s, k0 + 1, o0, o1); v = k < o1 ? (k - o0) + ((k - o0) >= s ? 1 : 0) : 0;
+                if (k < o1) low = T[v] & 3u;
+              }
+              if (k < o1 && spread_take_c(T, v, s, low)) lost_any = true;
+            }
+            uint64_t nm = ballot(lost && !shortrow && !full);
+            while (nm) {
+              const int sl = __builtin_ctzll(nm);
+              nm &= nm - 1;
+              const int rs = __builtin_amdgcn_readlane(s, sl), ro1 = __builtin_amdgcn_readlane(o1, sl), rk = __builtin_amdgcn_readlane(k0, sl);
+              const int kc = spread_scan_coop(e, T, rs, false, rk + 1, ro1);
+              if (lane == sl) {
+                k = kc; v = 0;
+                if (kc < ro1) { v = e.ocol[kc]; if (spread_take_c(T, v, rs, T[v] & 3u)) lost_any = true; }
+              }
+            }
+            const uint32_t nw = (uint32_t)k | ((uint32_t)v << 16);
+            pkv[0] = lost && !q1 ? nw : pkv[0];
+            pkv[1] = lost && q1 ? nw : pkv[1];
+            pend &= pend - 1u;
+          } while (__any(pend != 0u));
+          wsync();   // the next sweep's verification (and the serial blocks behind) see these takes
+        }
+      }
+#pragma unroll
+      for (int b = B0; b < MCT; ++b) {
         opaque_uniform(n_src);
         if (b * WAVE >= n_src) break;
         const int s = (int)(sst[b] & 0xFFFFu), o0 = (int)(row[b] & 0xFFFFu), o1 = (int)(row[b] >> 16), k0 = (int)(pkv[b] & 0xFFFFu);
@@ -908,7 +978,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
       // at most two words of the blocked bitmask: two reads and one 64-bit popcount; the nine-word form only where some lane needs it
       const bool far = mine && end - o0 > 33;
       if (mine && !far) {
-        const int w0 = o0 >> 5, wl = ((P.t.EW + 3) & ~3) - 1;
+        const int w0 = o0 >> 5, wl = MERGE ? wlv : ((P.t.EW + 3) & ~3) - 1;
         const uint64_t bits = ((uint64_t)e.blk[w0] | ((uint64_t)e.blk[w0 < wl ? w0 + 1 : w0] << 32)) >> (o0 & 31);
         const int len = end - o0;   // 0..33
         n = len - __popcll(len > 0 ? bits & (~0ull >> (64 - len)) : 0ull);
@@ -923,7 +993,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
     SUBSTAMP(12);
     // ring: only the last CG_LOG_RING entries (global order: source id, then row order) matter
     if (total_new > 0) {
-      const uint32_t base = (uint32_t)e.log_total;
+      const uint32_t base = (uint32_t)(MERGE ? __builtin_amdgcn_readfirstlane(logv) : e.log_total);
       const uint32_t end = base + (uint32_t)total_new;
       const uint32_t lo = end > CG_LOG_RING ? end - CG_LOG_RING : 0;
       uint32_t after = end;   // global index just past the current block of sources
@@ -948,7 +1018,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
           uint64_t bits;
           if (b < KB) bits = bitsv[b < KB ? b : 0];   // (not long => not `far` in the counts: the pair was read there)
           else {
-            const int w0 = o0 >> 5, wl = ((P.t.EW + 3) & ~3) - 1;
+            const int w0 = o0 >> 5, wl = MERGE ? wlv : ((P.t.EW + 3) & ~3) - 1;
             bits = ((uint64_t)e.blk[w0] | ((uint64_t)e.blk[w0 < wl ? w0 + 1 : w0] << 32)) >> (o0 & 31);
           }
           uint64_t z = ~bits & (~0ull >> (63 - (last - o0)));   // slots o0 .. last (rows of <= LONG_ROW slots)
@@ -983,7 +1053,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
         }
         after = cbase;
       }
-      e.log_total = (int)end;
+      if constexpr (MERGE) { logv = (int)end; asm volatile("" : "+v"(logv)); } else e.log_total = (int)end;
       e.ring_dirty = true;
     }
     wsync();
@@ -991,6 +1061,7 @@ __device__ __forceinline__ void attacker_spread_ct(Env& e, const KP& P, const in
     SUBSTAMP(14);
     SUBVAL(16, n_src); SUBVAL(17, 0); SUBVAL(18, 0);
   }
+  if constexpr (MERGE) e.log_total = __builtin_amdgcn_readfirstlane(logv);
 }
 
 template <bool XE>

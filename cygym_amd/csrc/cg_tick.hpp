@@ -355,6 +355,10 @@ __global__ __launch_bounds__(WPB * WAVE, FUSED ? CG_FUSED_LB : (XE ? (WPB == 1 &
   // the spread's source compaction and T / candidate pass on one dword per lane (cg_spread_words.hpp): the per-tick kernels at 256
   // devices; the rollout kernels keep the byte-wise passes (with the word form their VGPRs went 107 -> 112)
   constexpr bool SPREAD_WORDS = MT == 256 && !FUSED;
+  // the spread's verification sweeps serve the losers of both source blocks as one group, and sweep 0 stages two slots per row: the
+  // same kernels (the 64-device kernels have one block of sources; the rollout kernels keep the serial sweeps and four slots)
+  constexpr bool SPREAD_MERGE = MT == 256 && !FUSED;
+  constexpr int SPREAD_NS = (MT == 256 && !FUSED) ? 2 : 4;   // slots staged per row in sweep 0 (a switch of its own: measured in the same kernels)
 #include "cg_tick_body.inc"
 }
 

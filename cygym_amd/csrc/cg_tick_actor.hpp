@@ -16,6 +16,8 @@ __global__ __launch_bounds__(16 * WAVE, 4) void tick_actor_kernel(const KParams 
 // figures are pinned to the build that introduced the tiled actor launch (tests/test_mixture_cpu.py).
       constexpr bool ARRIVALS_JOINT = false;
       constexpr bool SPREAD_WORDS = false;   // (the same pin: the byte-wise spread)
+      constexpr bool SPREAD_MERGE = false;   // (and the serial verification sweeps)
+      constexpr int SPREAD_NS = 4;           // (and four staged slots in sweep 0)
 #include "cg_tick_body.inc"
     };
     tick();

@@ -387,7 +387,7 @@
           int ne = nexp0;
           if (ne > CG_MAX_EXPLOITS) ne = CG_MAX_EXPLOITS;
           __builtin_amdgcn_s_setprio(3);   // the spread bounds the launch: win issue arbitration over short envs
-          attacker_spread_ct<(MT + WAVE - 1) / WAVE, WIDE, SPREAD_WORDS && MT == 256>(e, P, P.a.exploit + te * G * CG_MAX_EXPLOITS, ex0, ne);
+          attacker_spread_ct<(MT + WAVE - 1) / WAVE, WIDE, SPREAD_WORDS && MT == 256, SPREAD_MERGE && MT == 256, SPREAD_NS>(e, P, P.a.exploit + te * G * CG_MAX_EXPLOITS, ex0, ne);
           __builtin_amdgcn_s_setprio(0);
         }
       } else {
