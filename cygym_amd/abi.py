@@ -322,6 +322,17 @@ class IppoHead(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+NASH_MAX = 16          # strategies per side of cygym_nash_support_enum
+NASH_MAX_BLOCKS = 1024
+
+
+class NashDesc(C.Structure):
+    _fields_ = [("D", C.c_void_p), ("B", C.c_void_p), ("best_p", C.c_void_p), ("best_q", C.c_void_p), ("best_value", C.c_void_p),
+                ("best_seq", C.c_void_p), ("count", C.c_void_p), ("list_pq", C.c_void_p), ("list_seq", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_uint64), ("tol_prob", C.c_double), ("tol_br", C.c_double), ("n", C.c_int32), ("m", C.c_int32),
+                ("k_max", C.c_int32), ("cap", C.c_int32), ("blocks", C.c_int32), ("reserved", C.c_int32)]
+
+
 DECODE_TRUNCATED = 0x10000
 
 BASELINES = {"Nash": 0, "No Defense": 1, "Preset": 2, "No Attack": 3}

@@ -67,6 +67,7 @@ INST_EVAL = os.path.join(HERE, "csrc", "cg_inst_eval.hip")
 INST_DDPG = os.path.join(HERE, "csrc", "cg_inst_ddpg.hip")
 INST_PPO = os.path.join(HERE, "csrc", "cg_inst_ppo.hip")
 INST_IPPO = os.path.join(HERE, "csrc", "cg_inst_ippo.hip")
+INST_NASH = os.path.join(HERE, "csrc", "cg_inst_nash.hip")
 N_GROUPS = 8   # CG_INST_GROUPS of csrc/cg_device.hpp
 GROUP_MT = {0: 256, 1: 256, 2: 64, 3: 64, 4: 0, 5: 0, 6: 0, 7: 0}   # device-count class each instantiation group holds
 
@@ -110,6 +111,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         units.append(("inst_ddpg", base + ["-c", INST_DDPG, "-o", os.path.join(tmp, "inst_ddpg.o")]))   # the critic's tail and its backward (the DDPG update)
         units.append(("inst_ppo", base + ["-c", INST_PPO, "-o", os.path.join(tmp, "inst_ppo.o")]))   # the GAE walk and the Categorical PPO loss head (the H-MARL updates)
         units.append(("inst_ippo", base + ["-c", INST_IPPO, "-o", os.path.join(tmp, "inst_ippo.o")]))   # the advantages and the PPO head of the IPPO / MAPPO update
+        units.append(("inst_nash", base + ["-c", INST_NASH, "-o", os.path.join(tmp, "inst_nash.o")]))   # the support enumeration of the restricted game, a kernel per support size
 
         def run(unit):
             name, cmd = unit

@@ -526,5 +526,6 @@ __global__ void gen_actions_kernel(KParams P, int tick, int32_t* mode, int32_t* 
 #include "cg_critic_tail.hpp"  // cygym_critic_tail / _backward (templates: instantiated in cg_inst_ddpg.hip)
 #include "cg_ppo.hpp"          // cygym_ppo_finish, cygym_cat_ppo_loss / _backward (templates: instantiated in cg_inst_ppo.hip)
 #include "cg_ippo_head.hpp"    // cygym_ippo_advantages, cygym_ippo_ppo_loss / _backward (templates: instantiated in cg_inst_ippo.hip)
+#include "cg_nash.hpp"         // cygym_nash_support_enum (a template per support size: instantiated in cg_inst_nash.hip; its last pass is plain)
 
 #endif  // CG_AUX_KERNELS_HPP

@@ -175,6 +175,14 @@ extern template __global__ void ippo_head_kernel<false>(cygym_ippo_head_desc, fl
 extern template __global__ void ippo_head_kernel<true>(cygym_ippo_head_desc, float, float);
 }  // namespace cygym_k
 
+// the support enumeration lives in its own unit (cg_inst_nash.hip): declared, not instantiated, here
+namespace cygym_k {
+#define CG_NASH_KS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+#define CG_DECL(K) extern template __global__ void nash_enum_kernel<K>(cygym_nash_desc, NashLaunch);
+CG_NASH_KS(CG_DECL)
+#undef CG_DECL
+}  // namespace cygym_k
+
 // the mixture draw and the whole-actor launch with a tile table live in their own unit (cg_inst_mixture.hip): declared, not instantiated, here
 namespace cygym_k {
 extern template __global__ void mixture_draw_kernel<false>(cygym_mixture, int, const int32_t*, uint64_t, int64_t);
@@ -338,6 +346,7 @@ int cygym_sizeof(int32_t which) {
     case 46: return (int)sizeof(cygym_comm_actor_pop);   // (index 45 stays unassigned)
     case 48: return (int)sizeof(cygym_hier_pop);   // (index 47 stays unassigned)
     case 50: return (int)sizeof(cygym_meta_pop);   // (index 49 stays unassigned)
+    case 52: return (int)sizeof(cygym_nash_desc);   // (index 51 stays unassigned)
     default: return -1;
   }
 }
@@ -1335,6 +1344,71 @@ int cygym_ppo_finish(cygym_handle* h, const cygym_ppo_finish_desc* e, void* stre
   void* args[3] = {&arg, &g, &gl};
   const void* k = e->T > 1 ? (const void*)ppo_finish_kernel<true> : (const void*)ppo_finish_kernel<false>;
   HIPCHK(h, hipLaunchKernel(k, dim3((e->N + PF_TPB - 1) / PF_TPB), dim3(PF_TPB), args, 0, (hipStream_t)stream));
+  HIPCHK(h, hipGetLastError());
+  return CYGYM_OK;
+}
+
+// Pairs of support size k and their sum up to k_max, in 64 bits (C(16, 8)^2 = 1.7e8; the sum over every size of 16 x 16 is C(32, 16) = 6e8).
+static long long nash_binom(int a, int b) {
+  long long c = 1;
+  for (int i = 0; i < b; ++i) c = c * (a - i) / (i + 1);
+  return b < 0 || b > a ? 0 : c;
+}
+static bool nash_shape_ok(const cygym_nash_desc* e) {
+  return e && e->n >= 1 && e->n <= NASH_MAX && e->m >= 1 && e->m <= NASH_MAX && e->k_max >= 1 && e->k_max <= (e->n < e->m ? e->n : e->m) &&
+         e->blocks >= 0 && e->blocks <= NASH_MAX_BLOCKS;
+}
+// The workgroups of support size k's launch: `blocks` when the caller forces it, else enough for four pairs per group, at most NASH_MAX_BLOCKS.
+static int nash_blocks(const cygym_nash_desc* e, int k) {
+  if (e->blocks > 0) return e->blocks;
+  const long long pairs = nash_binom(e->n, k) * nash_binom(e->m, k), per_block = 4ll * (NASH_TPB / nash_gw(k));
+  const long long b = (pairs + per_block - 1) / per_block;
+  return (int)(b < 1 ? 1 : (b > NASH_MAX_BLOCKS ? NASH_MAX_BLOCKS : b));
+}
+uint64_t cygym_nash_workspace_bytes(const cygym_nash_desc* e) {
+  if (!nash_shape_ok(e)) return 0;
+  uint64_t parts = 0;
+  for (int k = 1; k <= e->k_max; ++k) parts += (uint64_t)nash_blocks(e, k);
+  return parts * NASH_PARTIAL * sizeof(double);
+}
+int cygym_nash_support_enum(cygym_handle* h, const cygym_nash_desc* e, void* stream) {
+  const char* const who = "cygym_nash_support_enum";
+  if (!e) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (!nash_shape_ok(e) || e->cap < 0 || (e->cap > 0 && !(e->list_pq && e->list_seq)) || !(e->tol_prob == e->tol_prob) || !(e->tol_br == e->tol_br))
+    return fail(h, CYGYM_EINVAL, "%s: bad layout (n, m in 1 .. 16, k_max in 1 .. min(n, m), cap >= 0 with both lists, blocks in 0 .. 1024, tolerances numbers)", who);
+  if (!e->D || !e->B || !e->best_p || !e->best_q || !e->best_value || !e->best_seq || !e->count || !e->workspace) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (e->workspace_bytes < cygym_nash_workspace_bytes(e) || ((uintptr_t)e->workspace & 7)) return fail(h, CYGYM_EINVAL, "%s: workspace smaller than cygym_nash_workspace_bytes, or not 8-byte aligned", who);
+  long long total = 0;
+  for (int k = 1; k <= e->k_max; ++k) total += nash_binom(e->n, k) * nash_binom(e->m, k);
+  if (total > (1ll << 31)) return fail(h, CYGYM_EUNSUPPORTED, "%s: more than 2^31 support pairs", who);
+  if (h) HIPCHK(h, hipSetDevice(h->device_id));
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(h, hipMemsetAsync(e->count, 0, sizeof(int64_t), st));
+  cygym_nash_desc arg = *e;
+  if (arg.cap == 0) { arg.list_pq = nullptr; arg.list_seq = nullptr; }
+  static const void* const kernels[NASH_MAX] = {
+#define CG_K(K) (const void*)nash_enum_kernel<K>,
+      CG_NASH_KS(CG_K)
+#undef CG_K
+  };
+  NashLaunch L;
+  L.partials = (double*)e->workspace;
+  L.off = 0;
+  int parts = 0;
+  for (int k = 1; k <= e->k_max; ++k) {   // one launch per support size: each stays short
+    const long long cn = nash_binom(e->n, k), cm = nash_binom(e->m, k);
+    const int blocks = nash_blocks(e, k);
+    L.total = (unsigned)(cn * cm);
+    L.cm = (unsigned)cm;
+    void* args[2] = {&arg, &L};
+    HIPCHK(h, hipLaunchKernel(kernels[k - 1], dim3(blocks), dim3(NASH_TPB), args, 0, st));
+    L.partials += (size_t)blocks * NASH_PARTIAL;
+    L.off += cn * cm;
+    parts += blocks;
+  }
+  const double* all = (const double*)e->workspace;
+  void* fargs[3] = {&arg, &all, &parts};
+  HIPCHK(h, hipLaunchKernel((const void*)nash_finish_kernel, dim3(1), dim3(NASH_TPB), fargs, 0, st));
   HIPCHK(h, hipGetLastError());
   return CYGYM_OK;
 }

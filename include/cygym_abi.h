@@ -193,7 +193,7 @@ typedef struct cygym_handle cygym_handle;
 
 int cygym_version(void);
 /* sizeof of the ABI structs as this library was compiled (which: 0 cygym_topology, 1 cygym_config, 2 cygym_buffers,
- * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train, 31 cygym_dns, 33 cygym_mixture, 46 cygym_comm_actor_pop, 48 cygym_hier_pop; -1 for anything else, 13, 15, 18, 22, 24, 26, 30 and 32 included: those indices stay unassigned): lets a
+ * 3 cygym_actions, 4 cygym_outputs, 5 cygym_action_rows, 6 cygym_action_vectors, 7 cygym_actor_head, 8 cygym_actor_mlp, 9 cygym_device_types, 10 cygym_device_logits, 11 cygym_critic, 12 cygym_comm_actor, 14 cygym_comm_eval, 16 cygym_critic_tail_desc, 17 cygym_hier_net, 19 cygym_hier_sample, 20 cygym_hier_loss_desc, 21 cygym_hmarl, 23 cygym_meta, 25 cygym_meta_select_desc, 27 cygym_ppo_finish_desc, 28 cygym_cat_ppo_desc, 29 cygym_hmarl_train, 31 cygym_dns, 33 cygym_mixture, 46 cygym_comm_actor_pop, 48 cygym_hier_pop, 50 cygym_meta_pop, 52 cygym_nash_desc; -1 for anything else, 13, 15, 18, 22, 24, 26, 30 and 32 included: those indices stay unassigned): lets a
  * binding check its own struct layouts at load time. */
 int cygym_sizeof(int32_t which);
 const char* cygym_last_error(const cygym_handle* h);  /* h may be NULL */
@@ -1779,6 +1779,55 @@ typedef struct cygym_ippo_head_desc {
  * exp_stride < E or app_stride < A; nothing is written then. */
 int cygym_ippo_ppo_loss(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream);
 int cygym_ippo_ppo_loss_backward(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream);
+
+/* The restricted game of a double-oracle iteration by support enumeration (DoubleOracle.solve_nash_equilibrium, do_agent.py:1122-1135:
+ * `list(game.support_enumeration())`, then np.argmax over the defender's value p D q).  Only equal-sized support pairs give square
+ * systems, so the work is sum_k C(n, k) C(m, k) independent small float64 solves and one reduction.  The reference's enumeration is
+ * nashpy's; its iteration order and thresholds are NOT what is pinned here (cygym_amd/equilibrium.py): the contract below is
+ * the project's own, and cygym_amd/equilibrium.support_enumeration_np restates it in numpy.
+ * All DEVICE pointers, float64, row-major, contiguous.  h may be NULL, as for cygym_ppo_finish. */
+typedef struct cygym_nash_desc {
+  const double* D;          /* [n][m] the defender's payoff: row i a defender strategy, column j an attacker strategy               */
+  const double* B;          /* [n][m] the attacker's payoff in the same orientation (the transpose of the reference's A_mat)        */
+  double* best_p;           /* out [n] the defender's mix of the equilibrium of largest value; untouched when count = 0             */
+  double* best_q;           /* out [m] the attacker's; untouched when count = 0                                                     */
+  double* best_value;       /* out [1] p D q of that equilibrium; untouched when count = 0                                          */
+  int64_t* best_seq;        /* out [1] its sequence number, -1 when count = 0                                                       */
+  int64_t* count;           /* out [1] the number of equilibria found (cleared by the call; exact beyond cap)                       */
+  double* list_pq;          /* optional out [cap][n + m]: p then q of the first `cap` equilibria that claimed a slot (order          */
+  int64_t* list_seq;        /* optional out [cap]: their sequence numbers   unspecified: sort by list_seq); unclaimed slots stay    */
+  void* workspace;          /* cygym_nash_workspace_bytes(e) bytes, 8-byte aligned: the workgroups' partial results                 */
+  uint64_t workspace_bytes; /* what the caller allocated                                                                            */
+  double tol_prob;          /* a probability on the support must be > tol_prob                                                      */
+  double tol_br;            /* a best response may beat the support by at most tol_br                                               */
+  int32_t n, m;             /* 1 .. 16 each                                                                                         */
+  int32_t k_max;            /* the largest support size, 1 .. min(n, m)                                                             */
+  int32_t cap;              /* rows of list_pq / list_seq (0: no list)                                                              */
+  int32_t blocks;           /* workgroups per launch, 1 .. 1024; 0 = planned from the pair count.  The result does not depend on it */
+  int32_t reserved;         /* 0                                                                                                    */
+} cygym_nash_desc;
+/* Enumeration order: support size k ascending; within k the sequence number is off_k + ri C(m, k) + ci with off_k = sum_{j < k}
+ * C(n, j) C(m, j) and ri, ci the lexicographic ranks of the row support I and the column support J (itertools.combinations order),
+ * unranked on the device from a binomial table.  Per pair, in float64:
+ *     q on J: rows D[I[t], J] - D[I[t + 1], J] (t < k - 1) = 0 and sum q = 1      (the defender indifferent over I)
+ *     p on I: rows B[I, J[t]] - B[I, J[t + 1]] (t < k - 1) = 0 and sum p = 1      (the attacker indifferent over J)
+ *   each by elimination with partial pivoting (the first row of largest magnitude; every other row is reduced at each step, so no
+ *   back substitution: the pivots are those of Gaussian elimination).  A pivot of magnitude <= 1e-12 times the largest magnitude of
+ *   its system: the pair is singular and skipped.  Non-finite q, p or value: skipped.  Feasible: every probability on the support
+ *   > tol_prob (p is not formed for an infeasible q).  Equilibrium: max_i (D q)_i <= max_{i in I} (D q)_i + tol_br and
+ *   max_j (p B)_j <= max_{j in J} (p B)_j + tol_br.  Its value is sum_{t} p[t] (D q)_{I[t]}.
+ * best_*: the equilibrium of largest value, ties to the smallest sequence number (np.argmax over a list in that order).
+ * ONE launch per support size (nash_enum_kernel<K> of csrc/cg_nash.hpp, K = 1 .. k_max: a pair per group of 4, 8 or 16 lanes, a row of the system
+ * per lane in registers) and one that finishes the reduction, all stream-ordered.  No floating-point atomics: every workgroup writes
+ * one partial (value, sequence number, p, q) into `workspace`, the last launch reduces them by (value, then the smaller sequence
+ * number) -- the outputs are the same bits for any `blocks`.  The integer atomics on `count` decide only which slot of the list an
+ * equilibrium takes.
+ * CYGYM_EINVAL (nothing is launched): a NULL struct, D, B, best_p, best_q, best_value, best_seq, count or workspace; n or m outside
+ * 1 .. 16; k_max outside 1 .. min(n, m); cap < 0, or cap > 0 without list_pq and list_seq; blocks outside 0 .. 1024; NaN tolerances;
+ * workspace_bytes below cygym_nash_workspace_bytes(e).  CYGYM_EUNSUPPORTED: more than 2^31 pairs in all. */
+int cygym_nash_support_enum(cygym_handle* h, const cygym_nash_desc* e, void* stream);
+/* Bytes of cygym_nash_desc.workspace for e's k_max and blocks (the pointers are not read); 0 for a desc the call would refuse. */
+uint64_t cygym_nash_workspace_bytes(const cygym_nash_desc* e);
 
 /* cygym_step and the NEXT acting role's cygym_actor_mlp_decode as ONE launch -- a whole turn of a closed loop
  * (do_agent.py:206-272: act on the observation, step) per launch instead of two.  Tick the whole batch with the actions `a`
