@@ -16,7 +16,7 @@ SO = os.environ.get("CYGYM_SO") or os.path.join(HERE, "libcygym_hip.so")   # CYG
 EXPORTS = [
     "cygym_version", "cygym_sizeof", "cygym_last_error", "cygym_create", "cygym_destroy", "cygym_set_config", "cygym_bind", "cygym_derive",
     "cygym_set_snapshot", "cygym_reset", "cygym_randomize", "cygym_step", "cygym_step_range", "cygym_rollout", "cygym_observe",
-    "cygym_gen_actions", "cygym_write_actions", "cygym_decode_actions", "cygym_actor_head_decode", "cygym_actor_mlp_decode", "cygym_actor_mlp_decode_tiled", "cygym_mixture_draw", "cygym_coord_ascent_decode", "cygym_coord_ascent_decode_pop", "cygym_dns_decode", "cygym_committee_decode", "cygym_override_decode", "cygym_comm_actor_decode", "cygym_comm_actor_decode_pop", "cygym_comm_gat_decode", "cygym_comm_gat_workspace_bytes", "cygym_hier_decode", "cygym_hier_decode_pop", "cygym_hier_sample_decode", "cygym_hier_loss", "cygym_hier_loss_backward", "cygym_hmarl_decode", "cygym_hmarl_sample_decode", "cygym_meta_decode", "cygym_meta_decode_pop", "cygym_meta_select", "cygym_comm_actor_evaluate", "cygym_comm_actor_evaluate_backward", "cygym_comm_gat_evaluate", "cygym_comm_gat_evaluate_backward", "cygym_comm_gat_eval_workspace_bytes", "cygym_critic_tail", "cygym_critic_tail_backward", "cygym_ppo_finish", "cygym_cat_ppo_loss", "cygym_cat_ppo_loss_backward", "cygym_ippo_advantages", "cygym_ippo_ppo_loss", "cygym_ippo_ppo_loss_backward", "cygym_nash_support_enum", "cygym_nash_workspace_bytes", "cygym_step_actor", "cygym_group_actions", "cygym_sample_group_actions", "cygym_fit_forests",
+    "cygym_gen_actions", "cygym_write_actions", "cygym_decode_actions", "cygym_actor_head_decode", "cygym_actor_mlp_decode", "cygym_actor_mlp_decode_tiled", "cygym_mixture_draw", "cygym_coord_ascent_decode", "cygym_coord_ascent_decode_pop", "cygym_dns_decode", "cygym_committee_decode", "cygym_override_decode", "cygym_comm_actor_decode", "cygym_comm_actor_decode_pop", "cygym_comm_gat_decode", "cygym_comm_gat_workspace_bytes", "cygym_hier_decode", "cygym_hier_decode_pop", "cygym_hier_sample_decode", "cygym_hier_loss", "cygym_hier_loss_backward", "cygym_hmarl_decode", "cygym_hmarl_sample_decode", "cygym_hmarl_pack_slots", "cygym_hmarl_decode_pop", "cygym_meta_decode", "cygym_meta_decode_pop", "cygym_meta_select", "cygym_comm_actor_evaluate", "cygym_comm_actor_evaluate_backward", "cygym_comm_gat_evaluate", "cygym_comm_gat_evaluate_backward", "cygym_comm_gat_eval_workspace_bytes", "cygym_critic_tail", "cygym_critic_tail_backward", "cygym_ppo_finish", "cygym_cat_ppo_loss", "cygym_cat_ppo_loss_backward", "cygym_ippo_advantages", "cygym_ippo_ppo_loss", "cygym_ippo_ppo_loss_backward", "cygym_nash_support_enum", "cygym_nash_workspace_bytes", "cygym_step_actor", "cygym_group_actions", "cygym_sample_group_actions", "cygym_fit_forests",
     "cygym_timer_start", "cygym_timer_stop", "cygym_launch_plan",
 ]
 
@@ -84,6 +84,8 @@ def load():
     L.cygym_hier_loss_backward.argtypes = [H, C.POINTER(abi.HierLoss), C.c_void_p]
     L.cygym_hmarl_decode.argtypes = [H, C.POINTER(abi.Hmarl), C.POINTER(abi.Actions), C.c_void_p]
     L.cygym_hmarl_sample_decode.argtypes = [H, C.POINTER(abi.Hmarl), C.POINTER(abi.HmarlTrain), C.POINTER(abi.Actions), C.c_void_p]
+    L.cygym_hmarl_pack_slots.argtypes = [H, C.POINTER(abi.Hmarl), C.c_int32, C.POINTER(abi.HmarlSlot)]
+    L.cygym_hmarl_decode_pop.argtypes = [H, C.POINTER(abi.Hmarl), C.POINTER(abi.HmarlPop), C.POINTER(abi.Actions), C.c_void_p]
     L.cygym_meta_decode.argtypes = [H, C.POINTER(abi.Meta), C.POINTER(abi.Actions), C.c_void_p]
     L.cygym_meta_decode_pop.argtypes = [H, C.POINTER(abi.Meta), C.POINTER(abi.MetaPop), C.POINTER(abi.Actions), C.c_void_p]
     L.cygym_meta_select.argtypes =[H, C.POINTER(abi.MetaSelect), C.c_void_p]
@@ -127,7 +129,8 @@ def load():
         raise CygymError(f"ABI struct HierNet: library {L.cygym_sizeof(17)} bytes vs python {C.sizeof(abi.HierNet)}")
     for which, st in ((19, abi.HierSample), (20, abi.HierLoss), (21, abi.Hmarl), (23, abi.Meta), (25, abi.MetaSelect), (27, abi.PpoFinish), (28, abi.CatPpo), (29, abi.HmarlTrain),
                       (31, abi.Dns), (33, abi.Mixture), (35, abi.CommGat), (37, abi.CommGatEval),
-                      (39, abi.IppoAdv), (40, abi.IppoHead), (42, abi.Committee), (44, abi.CriticPop), (46, abi.CommActorPop), (48, abi.HierPop), (50, abi.MetaPop), (52, abi.NashDesc)):   # (indices 18, 22, 24, 26, 30, 32, 34, 36, 38, 41, 43, 45, 47, 49 and 51 are unassigned)
+                      (39, abi.IppoAdv), (40, abi.IppoHead), (42, abi.Committee), (44, abi.CriticPop), (46, abi.CommActorPop), (48, abi.HierPop), (50, abi.MetaPop), (52, abi.NashDesc),
+                      (54, abi.HmarlPop), (55, abi.HmarlSlot)):   # (indices 18, 22, 24, 26, 30, 32, 34, 36, 38, 41, 43, 45, 47, 49, 51 and 53 are unassigned)
         if L.cygym_sizeof(which) != C.sizeof(st):
             raise CygymError(f"ABI struct {st.__name__}: library {L.cygym_sizeof(which)} bytes vs python {C.sizeof(st)}")
     _lib = L

@@ -262,6 +262,21 @@ class HmarlTrain(C.Structure):
 
 
 HMARL_MAX_HIDDEN = 256
+HMARL_POP_MAX = 32
+
+
+class HmarlSlot(C.Structure):
+    _fields_ = [("coin_thr", C.c_uint64), ("budget", C.c_double), ("cost_comp", C.c_double * HMARL_MAX_TYPES), ("cost_not", C.c_double * HMARL_MAX_TYPES),
+                ("batch_len", C.c_int32 * HMARL_MAX_TYPES), ("kind", C.c_uint8 * HMARL_MAX_TYPES),
+                ("allowed", C.c_uint8 * (HMARL_MAX_SKILLS * HMARL_MAX_TYPES)), ("n_allowed", C.c_uint8 * HMARL_MAX_SKILLS),
+                ("cheap_idx", C.c_int32), ("costly_idx", C.c_int32), ("global_idx", C.c_int32), ("net_mask", C.c_uint32),
+                ("fanout", C.c_int32), ("fallback", C.c_int32)]
+
+
+class HmarlPop(C.Structure):
+    _fields_ = [("tile_slot", C.c_void_p), ("slots", C.c_void_p), ("h0", C.c_void_p), ("pi_w2", C.c_void_p), ("pi_b2", C.c_void_p),
+                ("logits_out", C.c_void_p), ("h0_group_stride", C.c_int64), ("ld", C.c_int32), ("Hp", C.c_int32), ("n_slots", C.c_int32),
+                ("n_tiles", C.c_int32)]
 
 
 class Meta(C.Structure):

@@ -1366,6 +1366,80 @@ class BatchedCyberDefenseEnv:
         r = _bind_rows(self, q, rows, n)   # noqa: F841 (alive until the call has returned)
         _lib.check(self.lib.cygym_hmarl_decode(self._h, C.byref(q), C.byref(dst), self._stream()), self._h, "cygym_hmarl_decode")
 
+    def hmarl_decode_pop(self, rows_tiled: torch.Tensor, tile_slot: torch.Tensor, h0, pack, cfgs, act=None, skill_out=None, type_out=None,
+                         logits_out=None):
+        """hmarl_decode for a POPULATION of S H-MARL strategies of one role, master kind, n_skills, n_logits and n_types (1 <= S <= 32),
+        each deciding for some of the rows: ONE launch (cygym_hmarl_decode_pop) -- source row r is decided exactly as hmarl_decode would
+        with the tables of its tile's strategy; a learned master's second layer is formed on chip.
+          rows_tiled   [16 T] int32 on the device: the env of every source row, 16 per tile, -1 = no row (the layout mixture_draw
+                       writes and policies.mixture_rows_np restates)
+          tile_slot    [T] int32 on the device: the strategy of tile t; a tile whose entry is negative or >= S is left alone
+          h0           [16 T, >= Hp + n_skills * n_logits]: source row r formed with ITS strategy;  or [S, N, >= ...]: block s formed
+                       with strategy s for every env, the row of env e in tile t reads block tile_slot[t] at row e.  A row is the
+                       pre-activations of pi_fc1 (Hp of them, learned master only) | every skill's fc logits (absent when no member
+                       has a net).  None when the master is the expert's and no member has a net
+          pack         policies.HMARLPolicyGroup's stacked pack: "S", "slots" (uint8 [S, sizeof cygym_hmarl_slot] on the device: what
+                       cygym_hmarl_pack_slots wrote for `cfgs`), and with a learned master "Hp", "pi_w2" [S, n_skills, Hp], "pi_b2"
+                       [S, n_skills]
+          cfgs         the members' policies.HMARLConfig, slot after slot
+          outputs      skill_out / type_out [16 T] int32, logits_out [16 T, n_skills] float32 (learned master), by SOURCE row; the
+                       rows of skipped tiles and of -1 are not written
+        Every tensor is checked here: the kernel indexes them by raw pointer."""
+        q, pop, dst, keep = self._hmarl_pop_structs(rows_tiled, tile_slot, h0, pack, cfgs, act, skill_out, type_out, logits_out)   # noqa: F841
+        _lib.check(self.lib.cygym_hmarl_decode_pop(self._h, C.byref(q), C.byref(pop), C.byref(dst), self._stream()), self._h, "cygym_hmarl_decode_pop")
+
+    def _hmarl_pop_structs(self, rows_tiled, tile_slot, h0, pack, cfgs, act=None, skill_out=None, type_out=None, logits_out=None):
+        """Argument checks and marshalling of hmarl_decode_pop through the population decodes' shared checks (_tiled_rows,
+        _pop_first_layer): (Hmarl of slot 0 with the union of the net masks, HmarlPop, Actions, tensors to keep)."""
+        dst = self.actions_struct(act)
+        cfgs = list(cfgs)
+        S_ = int(pack["S"])
+        if S_ < 1 or len(cfgs) != S_:
+            raise ValueError("pack['S'] is the number of stacked strategies, at least 1, one config each")
+        cfg = cfgs[0]
+        if cfg.role_code != _role(cfg.role)["code"]:
+            raise ValueError("cfg.role must be 'attacker' or 'defender'")
+        q = cfg.to_c()
+        q.net_mask = 0
+        for c in cfgs:      # the UNION of the members' masks: what h0 must hold
+            q.net_mask |= c.net_mask
+        n = self._tiled_rows(rows_tiled, tile_slot)
+        K_, NS = cfg.n_logits, cfg.n_skills
+        learned = q.master == 1
+        f32 = lambda t, shape: isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous() and tuple(t.shape) == shape  # noqa: E731
+        slots = pack["slots"]
+        if not isinstance(slots, torch.Tensor) or slots.dtype != torch.uint8 or slots.device != self.device or not slots.is_contiguous() or \
+                tuple(slots.shape) != (S_, C.sizeof(abi.HmarlSlot)):
+            raise ValueError(f"pack['slots'] must be a contiguous uint8 [{S_}, {C.sizeof(abi.HmarlSlot)}] tensor on {self.device} (policies.hmarl_pack_slots)")
+        pop = abi.HmarlPop()
+        pop.tile_slot, pop.slots, pop.n_slots, pop.n_tiles = tile_slot.data_ptr(), slots.data_ptr(), S_, n // 16
+        Hp = int(pack["Hp"]) if learned else 0
+        width = Hp + (NS * K_ if q.net_mask else 0)
+        if learned:
+            for name, shape in (("pi_w2", (S_, NS, Hp)), ("pi_b2", (S_, NS))):
+                if name not in pack or not f32(pack[name], shape):
+                    raise ValueError(f"pack[{name!r}] must be a contiguous float32 {list(shape)} tensor on {self.device}")
+                setattr(pop, name, pack[name].data_ptr())
+            pop.Hp = Hp
+        if width > 0:
+            row_stride, group_stride = self._pop_first_layer(h0, "h0", ">= Hp + n_skills * n_logits", n, S_, wider=True)
+            if int(h0.shape[-1]) < width:
+                raise ValueError(f"h0 rows hold {int(h0.shape[-1])} floats: fewer than Hp + n_skills * n_logits = {width}")
+            pop.h0, pop.ld, pop.h0_group_stride = h0.data_ptr(), row_stride, group_stride
+        elif h0 is not None:
+            raise ValueError("h0 must be None: the master is the expert's and no member has a net")
+        for name, t in (("skill_out", skill_out), ("type_out", type_out)):
+            if t is not None:
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (n,):
+                    raise ValueError(f"{name} must be a contiguous int32 [{n}] tensor on {self.device}")
+                setattr(q, name, t.data_ptr())
+        if logits_out is not None:
+            if not learned or not f32(logits_out, (n, NS)):
+                raise ValueError(f"logits_out must be a contiguous float32 [{n}, {NS}] tensor on {self.device}, with a learned master")
+            pop.logits_out = logits_out.data_ptr()
+        q.status = self.status.data_ptr()
+        return q, pop, dst, [_bind_rows(self, q, rows_tiled, n), tile_slot, h0, slots]   # (alive until the call has returned)
+
     def hmarl_sample_decode(self, rows, cfg, h0: torch.Tensor, pack, force_skill: int = -1, act=None, logits_out=None, out=None):
         """The TRAINING decision of HMARLMetaBestResponse.train (HMARL.py:792-872) for a batch, written as GROUPS into rows `rows` of `act`:
         ONE launch (cygym_hmarl_sample_decode; include/cygym_abi.h states the decision).

@@ -60,6 +60,7 @@ INST_HIER = os.path.join(HERE, "csrc", "cg_inst_hier.hip")
 INST_HIER_POP = os.path.join(HERE, "csrc", "cg_inst_hier_pop.hip")
 INST_HMARL = os.path.join(HERE, "csrc", "cg_inst_hmarl.hip")
 INST_HMARL_TRAIN = os.path.join(HERE, "csrc", "cg_inst_hmarl_train.hip")
+INST_HMARL_POP = os.path.join(HERE, "csrc", "cg_inst_hmarl_pop.hip")
 INST_META = os.path.join(HERE, "csrc", "cg_inst_meta.hip")
 INST_META_POP = os.path.join(HERE, "csrc", "cg_inst_meta_pop.hip")
 INST_META_SELECT = os.path.join(HERE, "csrc", "cg_inst_meta_select.hip")
@@ -104,6 +105,7 @@ def build_to(so: str, resources: str | None = None, flags: list[str] | None = No
         units.append(("inst_hier_pop", base + ["-c", INST_HIER_POP, "-o", os.path.join(tmp, "inst_hier_pop.o")]))   # ... for a population of nets
         units.append(("inst_hmarl", base + ["-c", INST_HMARL, "-o", os.path.join(tmp, "inst_hmarl.o")]))   # the H-MARL decode
         units.append(("inst_hmarl_train", base + ["-c", INST_HMARL_TRAIN, "-o", os.path.join(tmp, "inst_hmarl_train.o")]))   # its training decision
+        units.append(("inst_hmarl_pop", base + ["-c", INST_HMARL_POP, "-o", os.path.join(tmp, "inst_hmarl_pop.o")]))   # ... for a population of strategies
         units.append(("inst_meta", base + ["-c", INST_META, "-o", os.path.join(tmp, "inst_meta.o")]))   # the MetaDOAR decode
         units.append(("inst_meta_pop", base + ["-c", INST_META_POP, "-o", os.path.join(tmp, "inst_meta_pop.o")]))   # ... for a population of strategies
         units.append(("inst_meta_select", base + ["-c", INST_META_SELECT, "-o", os.path.join(tmp, "inst_meta_select.o")]))   # its observer's selection

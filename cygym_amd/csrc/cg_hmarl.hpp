@@ -1,6 +1,7 @@
 // cg_hmarl.hpp -- cygym_hmarl_decode: BaseHMARLBR.execute (HMARL.py:595-607: a master picks a skill, the skill's frozen sub-policy picks
 // an action type, chooses and orders its target devices and cuts them into cost batches) for a batch, in ONE launch.  Included through
-// cg_decode.hpp; instantiated in cg_inst_hmarl.hip.  cygym_abi.h states the contract.
+// cg_decode.hpp; instantiated in cg_inst_hmarl.hip (hmarl_pop_kernel, the same decision for a population of strategies:
+// cg_inst_hmarl_pop.hip; steps 3 to 5 below are cg_hmarl_body.inc, the text both kernels include).  cygym_abi.h states the contract.
 //
 // One wave per row, no workgroup barrier anywhere; integer, bit, rank and RNG work on the env's flag plane:
 //   1. skill: the expert master's count of compromised, not owned devices and its DC bit (ballots over ALL devices), the coin; or the
@@ -164,131 +165,94 @@ __global__ __launch_bounds__(HM_THREADS_MAX) void hmarl_kernel(cygym_hmarl q, cy
     if (q.skill_out) q.skill_out[srow] = skill;
     if (q.type_out) q.type_out[srow] = t;
   }
-  // ---------------- 3. the ordered target list ----------------
-  int kind = hm_byte(q.kind, t);
-  int n = 0;   // length of the list (uniform)
-  if (kind == CG_HMARL_HIGH) {   // _high_value_targets (:139-154): the !NYA devices by descending score, ties in ascending id
-    auto cls_of = [&](const int d) -> int {   // 0: score 100 | 1: 50 | 2: 40 | 3: 20 | 4: 0 | -1: not in the list
-      if (d >= M) return -1;
-      const uint32_t f = fl[d];
-      if (f & CG_F_NYA) return -1;
-      if (f & CG_F_COMP) return (f & CG_F_OWNED) ? 2 : ((dstatic[d] & CG_D_DC) ? 0 : 1);
-      return (f & CG_F_REACH) ? 3 : 4;
-    };
-    int c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
-    for (int d0 = 0; d0 < M; d0 += WAVE) {
-      const int c = cls_of(d0 + lane);
-      c0 += __popcll(__ballot(c == 0)); c1 += __popcll(__ballot(c == 1)); c2 += __popcll(__ballot(c == 2));
-      c3 += __popcll(__ballot(c == 3)); c4 += __popcll(__ballot(c == 4));
-    }
-    int b0 = 0, b1 = c0, b2 = b1 + c1, b3 = b2 + c2, b4 = b3 + c3;   // class bases, then running
-    n = b4 + c4;
-    for (int d0 = 0; d0 < M; d0 += WAVE) {
-      const int d = d0 + lane, c = cls_of(d);
-      const uint64_t m0 = __ballot(c == 0), m1 = __ballot(c == 1), m2 = __ballot(c == 2), m3 = __ballot(c == 3), m4 = __ballot(c == 4);
-      const uint64_t mine = c == 0 ? m0 : c == 1 ? m1 : c == 2 ? m2 : c == 3 ? m3 : m4;
-      const int base = c == 0 ? b0 : c == 1 ? b1 : c == 2 ? b2 : c == 3 ? b3 : b4;
-      if (c >= 0) ord[base + below(mine)] = (uint16_t)(d | (c <= 2 ? 0x8000 : 0));   // (base + prefix < n <= M)
-      b0 += __popcll(m0); b1 += __popcll(m1); b2 += __popcll(m2); b3 += __popcll(m3); b4 += __popcll(m4);
-    }
-    wsync();
-  } else if (kind == CG_HMARL_SHUFFLE) {   // attacker type 1 (:263-267): the seeds, or every !NYA device when there is none, shuffled
-    bool any = false;
-    for (int d0 = 0; d0 < M; d0 += WAVE) {
+  const cygym_hmarl& tb = q;   // (the tables are the struct's own)
+#include "cg_hmarl_body.inc"
+}
+
+// cygym_hmarl_decode_pop: the same decision for a POPULATION of H-MARL strategies of one role, master kind, n_skills, n_logits and
+// n_types in one launch -- source row r is decoded with the tables (cygym_hmarl_slot) and the master's head of slot tile_slot[r / 16].
+// The work shape is hmarl_kernel's: one wave per source row, hm_waves(M) rows (4 or 2: both divide 16) per workgroup, so a workgroup's
+// rows lie in one tile; the same per-wave LDS block, no workgroup barrier, no atomics, no draw beyond the single kernel's.  The slot is
+// read once into a scalar; a slot outside 0 .. n_slots - 1 returns the wave before it reads or writes anything else.  The slot's tables
+// live in GLOBAL memory: the byte tables are still read through hm_byte, as aligned 32-bit words (the record is a multiple of 16 bytes
+// and its byte tables start on multiples of 4, so every component of a uniform address is a multiple of 4).  What indexes inside a
+// record is masked (skill & 7, type & 31, 0 <= idx < min(n_allowed, 32)): a damaged table never reads outside its own record.
+//   step 1, expert master: hmarl_kernel's text with the slot's indices and coin_thr.
+//   step 1, learned master: the second layer on chip as the training kernel's phase 2 does it -- hm_dot_relu over the Hp pre-activations
+//     of the row's h0, pi_w2 / pi_b2 of the slot, the logits in the wave's LDS block, sample_head with the CG_SITE_HMARL_SKILL draw.
+//   step 2: the skill's fc logits are the second part of the h0 row, already final.
+//   steps 3 to 5: cg_hmarl_body.inc, the text of hmarl_kernel, with `tb` the slot's record.
+// h0 row of source row srow deciding for env `row`: h0 + srow * ld (h0_group_stride == 0) or h0 + slot * h0_group_stride + row * ld.
+template <bool OUTS>
+__global__ __launch_bounds__(HM_THREADS_MAX) void hmarl_pop_kernel(cygym_hmarl q, cygym_hmarl_pop pop, cygym_actions dst, int n_envs, const int32_t* ienv,
+                                                                   uint64_t seed, int64_t env_id_base, const uint8_t* live, const uint8_t* dstatic, int M) {
+  extern __shared__ __align__(16) uint8_t smem[];
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int srow = blockIdx.x * (int)(blockDim.x >> 6) + wv;
+  if (srow >= q.n) return;   // (uniform per wave; no workgroup barrier below)
+  const int slot = __builtin_amdgcn_readfirstlane(pop.tile_slot[srow >> 4]);
+  if (slot < 0 || slot >= pop.n_slots) return;   // the tile is left alone: no action row, no optional output, no status bit
+  const int row = q.rows[srow];
+  if (row < 0 || row >= n_envs) return;
+  const cygym_hmarl_slot& tb = pop.slots[slot];
+  const int mp = (M + 63) & ~63;
+  uint64_t* keys = reinterpret_cast<uint64_t*>(smem + (size_t)wv * hm_wave_bytes(M));
+  uint16_t* ord = reinterpret_cast<uint16_t*>(keys + mp);
+  const uint8_t* fl = live + (size_t)row * 4 * M;   // plane 0 of the env's live planes = the flags
+  const uint32_t tick = (uint32_t)ienv[(size_t)row * CG_I_COUNT + CG_I_RNG_TICK];   // read, not advanced
+  const uint32_t env_g = (uint32_t)(env_id_base + row), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const int S = q.n_skills, K = q.n_logits;
+  const int Hp = q.master == 0 ? 0 : pop.Hp;
+  const float* hrow = nullptr;   // [Hp pre-activations of pi_fc1 | S * K fc logits]
+  if (pop.h0) hrow = pop.h0 + (pop.h0_group_stride > 0 ? (size_t)slot * (size_t)pop.h0_group_stride + (size_t)row * pop.ld : (size_t)srow * pop.ld);
+  int skill, idx;
+  // ---------------- 1. the skill ----------------
+  if (q.master == 0) {   // ExpertRuleMaster.select_skill_index (HMARL.py:336-354)
+    int cnt = 0;
+    bool dc = false;
+    for (int d0 = 0; d0 < M; d0 += WAVE) {   // ALL devices, Not_yet_added ones included (:339 does not filter)
       const int d = d0 + lane;
-      const uint32_t f = d < M ? fl[d] : CG_F_NYA;
-      any = any || __ballot(!(f & CG_F_NYA) && (f & (CG_F_OWNED | CG_F_COMP))) != 0ull;
+      const bool on = d < M && (fl[d] & (CG_F_COMP | CG_F_OWNED)) == CG_F_COMP;
+      cnt += __popcll(__ballot(on));
+      dc = dc || __ballot(on && (dstatic[d] & CG_D_DC)) != 0ull;
     }
-    for (int d0 = 0; d0 < M; d0 += WAVE) {
-      const int d = d0 + lane;
-      const uint32_t f = d < M ? fl[d] : CG_F_NYA;
-      const bool on = !(f & CG_F_NYA) && (!any || (f & (CG_F_OWNED | CG_F_COMP)));
-      const uint64_t m = __ballot(on);
-      if (on) keys[n + below(m)] = ((uint64_t)cg_philox4x32_10(env_g, tick, CG_SITE_HMARL_SHUFFLE, (uint32_t)d & 0xFFFFu, k0, k1).v[0] << 32) | (uint32_t)d;
-      n += __popcll(m);
-    }
-    wsync();
-    for (int i0 = 0; i0 < n; i0 += WAVE) {   // rank = the number of smaller (key, id) pairs; the pairs are distinct
-      const int i = i0 + lane;
-      const uint64_t mine = i < n ? keys[i] : 0ull;
-      int rank = 0;
-      for (int j = 0; j < n; ++j) rank += keys[j] < mine ? 1 : 0;   // (uniform address: a broadcast read)
-      if (i < n) {
-        const int d = (int)(uint32_t)mine;
-        ord[rank] = (uint16_t)(d | ((fl[d] & CG_F_COMP) ? 0x8000 : 0));   // (rank < n <= M)
-      }
+    if (dc) skill = tb.costly_idx;
+    else if (cnt >= 3) skill = tb.cheap_idx;
+    else skill = (uint64_t)cg_philox4x32_10(env_g, tick, CG_SITE_HMARL_COIN, 0u, k0, k1).v[0] < tb.coin_thr ? tb.global_idx : tb.cheap_idx;
+  } else {   // LearnedMasterPolicy.select_skill_index (:381-389): pi_fc2 on chip, then every lane walks the same S entries
+    float* ml = reinterpret_cast<float*>(keys);          // the master's logits in the wave's LDS block (>= 640 bytes; step 3 reuses it)
+    const float* w2 = pop.pi_w2 + (size_t)slot * S * Hp;
+    for (int s = 0; s < S; ++s) {
+      const float z = hm_dot_relu(hrow, w2 + (size_t)s * Hp, Hp, lane) + pop.pi_b2[slot * S + s];
+      if (lane == 0) ml[s] = z;
     }
     wsync();
+    float lp;
+    skill = sample_head(ml, S, cg_philox4x32_10(env_g, tick, CG_SITE_HMARL_SKILL, 0u, k0, k1).v[0], false, lp);
+    if (OUTS && pop.logits_out && lane < S) pop.logits_out[(size_t)srow * S + lane] = ml[lane];
+    wsync();                                             // (the block is free again before step 3 writes it)
   }
-  if (kind >= CG_HMARL_HIGH && n == 0) kind = CG_HMARL_FALLBACK;   // a per-device type whose list is empty (:309-312)
-  const int G = dst.max_groups, L = dst.max_devs;
-  int16_t* out = const_cast<int16_t*>(dst.dev_idx) + (size_t)row * L;
-  const RowGroups og(dst, row);
-  if (kind < CG_HMARL_HIGH) {   // (uniform) ONE empty group: [(t, [0], [], 0)], the fallback's type for the fallback (G >= 1)
-    if (kind == CG_HMARL_FALLBACK) t = q.fallback;
-    if (lane == 0) {
-      og.set(0, t, 0, 1, 0);
-      og.dev_cnt[0] = 0;
-      const_cast<int32_t*>(dst.n_groups)[row] = 1;
+  skill = __builtin_amdgcn_readfirstlane(skill) & (HM_MAX_SKILLS - 1);
+  // ---------------- 2. the type (FrozenSubPolicy._pick_action_type, :229-244) ----------------
+  const int na = hm_byte(tb.n_allowed, skill);
+  if (hrow && skill < S && (((tb.net_mask & q.net_mask) >> skill) & 1u)) {   // (q.net_mask: the union the host sized ld for)
+    uint32_t bh = 0u, bl = 0u;
+    if (lane < K) {
+      bh = float_order_bits(hrow[Hp + skill * K + lane]);
+      bl = ~(uint32_t)lane;
     }
-    return;
+    idx = wave_first_max(bh, bl);
+    idx = idx < na - 1 ? idx : na - 1;   // :241
+  } else {
+    idx = (int)(cg_philox4x32_10(env_g, tick, CG_SITE_HMARL_TYPE, 0u, k0, k1).v[0] % (uint32_t)(na > 0 ? na : 1));   // random.choice (:233)
   }
-  // ---------------- 4. + 5. batches (_batch_devices_by_cost, :170-187) and groups (_batchify, :297-308) ----------------
-  const double cc = q.cost_comp[t], cn = q.cost_not[t], budget = q.budget;
-  const int blen = q.batch_len[t], fan = q.fanout;
-  double cur = 0.0;      // the sequential walk's running cost
-  int inb = 0;           // ... and the devices of its current batch
-  int nb = 0;            // batches started before this block of 64 positions
-  int last_s = 0;        // position of the last batch start before this block
-  int kept = 0;          // list entries written (or cut at L) before this block
-  for (int p0 = 0; p0 < n; p0 += WAVE) {
-    const int pos = p0 + lane;
-    const bool valid = pos < n;
-    const uint32_t e = valid ? ord[pos] : 0u;
-    uint64_t m;   // batch starts among the block's positions
-    if (blen > 0) {
-      m = __ballot(valid && pos % blen == 0);
-    } else {   // the reference's loop, in its order and in float64; every lane walks alike
-      const uint64_t cm = __ballot((e & 0x8000u) != 0u);
-      const int nv = n - p0 < WAVE ? n - p0 : WAVE;
-      m = p0 == 0 ? 1ull : 0ull;
-      for (int j = 0; j < nv; ++j) {
-        const double dcost = ((cm >> j) & 1ull) ? cc : cn;
-        if (inb > 0 && cur + dcost > budget) { m |= 1ull << j; cur = 0.0; inb = 0; }
-        cur += dcost;
-        ++inb;
-      }
-    }
-    const uint64_t incl = m & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull)), excl = m & ((1ull << lane) - 1ull);
-    const int my_s = incl ? p0 + hm_top(incl) : last_s;
-    const int b = nb + __popcll(incl) - 1;   // (position 0 is a start: b >= 0)
-    const bool keep = valid && pos - my_s < fan;   // MAX_FANOUT (:304-306): the batch keeps its first ids and DROPS the rest
-    const uint64_t km = __ballot(keep);
-    const int opos = kept + below(km);
-    if (keep && b < G && opos < L) out[opos] = (int16_t)(e & 0x7FFFu);
-    if (valid && ((m >> lane) & 1ull)) {
-      if (b < G) og.set(b, t, 0, 1, 0);
-      if (b >= 1 && b - 1 < G) {   // the batch that ends here: its count, cut to what is left of the row's L entries
-        const int len = pos - (excl ? p0 + hm_top(excl) : last_s);
-        int c = len < fan ? len : fan;
-        const int ob = opos - c;   // (opos = the entries of all earlier batches)
-        c = ob >= L ? 0 : (ob + c > L ? L - ob : c);
-        og.dev_cnt[b - 1] = c;
-      }
-    }
-    nb += __popcll(m);
-    if (m) last_s = p0 + hm_top(m);
-    kept += __popcll(km);
+  idx = __builtin_amdgcn_readfirstlane(idx);
+  const int nal = na < 1 ? 1 : (na > HM_MAX_TYPES ? HM_MAX_TYPES : na);   // a damaged n_allowed: the index stays inside the skill's list
+  idx = idx < 0 ? 0 : (idx < nal ? idx : nal - 1);
+  int t = __builtin_amdgcn_readfirstlane(hm_byte(tb.allowed, skill * HM_MAX_TYPES + idx)) & (HM_MAX_TYPES - 1);
+  if (OUTS && lane == 0) {
+    if (q.skill_out) q.skill_out[srow] = skill;
+    if (q.type_out) q.type_out[srow] = t;
   }
-  if (lane == 0) {
-    if (nb - 1 < G) {   // the last batch
-      const int len = n - last_s;
-      int c = len < fan ? len : fan;
-      const int ob = kept - c;
-      c = ob >= L ? 0 : (ob + c > L ? L - ob : c);
-      og.dev_cnt[nb - 1] = c;
-    }
-    const_cast<int32_t*>(dst.n_groups)[row] = nb < G ? nb : G;
-    if (nb > G || kept > L) RowGroups::truncated(q.status);
-  }
+#include "cg_hmarl_body.inc"
 }

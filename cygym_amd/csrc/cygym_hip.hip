@@ -122,6 +122,9 @@ namespace cygym_k {
 extern template __global__ void hmarl_kernel<false>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
 extern template __global__ void hmarl_kernel<true>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
 extern template __global__ void hmarl_kernel<true, true>(cygym_hmarl, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int, cygym_hmarl_train);
+// ... and for a population of strategies (cg_inst_hmarl_pop.hip)
+extern template __global__ void hmarl_pop_kernel<false>(cygym_hmarl, cygym_hmarl_pop, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
+extern template __global__ void hmarl_pop_kernel<true>(cygym_hmarl, cygym_hmarl_pop, cygym_actions, int, const int32_t*, uint64_t, int64_t, const uint8_t*, const uint8_t*, int);
 }  // namespace cygym_k
 
 // the MetaDOAR decode lives in its own unit (cg_inst_meta.hip): declared, not instantiated, here
@@ -347,6 +350,8 @@ int cygym_sizeof(int32_t which) {
     case 48: return (int)sizeof(cygym_hier_pop);   // (index 47 stays unassigned)
     case 50: return (int)sizeof(cygym_meta_pop);   // (index 49 stays unassigned)
     case 52: return (int)sizeof(cygym_nash_desc);   // (index 51 stays unassigned)
+    case 54: return (int)sizeof(cygym_hmarl_pop);   // (index 53 stays unassigned)
+    case 55: return (int)sizeof(cygym_hmarl_slot);
     default: return -1;
   }
 }
@@ -1467,29 +1472,37 @@ static int ippo_head_launch(cygym_handle* h, const cygym_ippo_head_desc* e, void
 int cygym_ippo_ppo_loss(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream) { return ippo_head_launch(h, e, stream, false, "cygym_ippo_ppo_loss"); }
 int cygym_ippo_ppo_loss_backward(cygym_handle* h, const cygym_ippo_head_desc* e, void* stream) { return ippo_head_launch(h, e, stream, true, "cygym_ippo_ppo_loss_backward"); }
 
-// What cygym_hmarl_decode and cygym_hmarl_sample_decode check alike (tr: the training launch, whose logits come from h0).
-static int hmarl_check(cygym_handle* h, const cygym_hmarl* q, const cygym_hmarl_train* tr, const cygym_actions* dst, const char* who) {
+// The table rules of a cygym_hmarl, in the order a caller sees them: what is wrong with `q`, or NULL.  No pointer is read.  logits: the
+// number of logits is needed whether or not a skill has a net (the training launch).  hmarl_check and cygym_hmarl_pack_slots share them.
+static const char* hmarl_table_rules(const cygym_hmarl* q, bool logits) {
+  if ((q->master != 0 && q->master != 1) || (q->role != 1 && q->role != 2)) return "master 0 or 1, role 1 or 2";
+  if (q->n_skills < 1 || q->n_skills > CG_HMARL_MAX_SKILLS || q->n_types < 1 || q->n_types > CG_HMARL_MAX_TYPES)
+    return "1 to 8 skills, 1 to 32 action types";
+  if ((q->net_mask || logits) && (q->n_logits < 1 || q->n_logits > HM_MAX_LOGITS || (q->net_mask >> q->n_skills))) return "1 to 32 logits per skill, net_mask within the skills";
+  if (q->master == 0 && (q->cheap_idx < 0 || q->cheap_idx >= q->n_skills || q->costly_idx < 0 || q->costly_idx >= q->n_skills || q->global_idx < 0 || q->global_idx >= q->n_skills))
+    return "the expert master's indices must name skills";
+  for (int s = 0; s < q->n_skills; ++s) {
+    if (q->n_allowed[s] < 1 || q->n_allowed[s] > CG_HMARL_MAX_TYPES) return "a skill allows 1 to 32 action types";
+    for (int i = 0; i < q->n_allowed[s]; ++i)
+      if (q->allowed[s * CG_HMARL_MAX_TYPES + i] >= q->n_types) return "an allowed action type is not below n_types";
+  }
+  if (q->fanout < 1 || q->fallback < 0 || q->fallback >= CG_HMARL_MAX_TYPES || !(q->budget >= 0.0) || !(q->budget < 1e300))
+    return "fanout >= 1, fallback 0 .. 31, a finite budget >= 0";
+  for (int t = 0; t < q->n_types; ++t)
+    if (q->kind[t] > CG_HMARL_SHUFFLE || q->batch_len[t] < 0 || !(q->cost_comp[t] >= 0.0) || !(q->cost_comp[t] < 1e300) || !(q->cost_not[t] >= 0.0) || !(q->cost_not[t] < 1e300))
+      return "a kind above CG_HMARL_SHUFFLE, a negative batch length, or a cost that is negative or not finite";
+  return nullptr;
+}
+
+// What cygym_hmarl_decode, cygym_hmarl_sample_decode and cygym_hmarl_decode_pop check alike (tr: the training launch, whose logits come
+// from h0; own_logits: master_logits / sub_logits are read -- not so for the training launch and the population, whose logits come from h0).
+static int hmarl_check(cygym_handle* h, const cygym_hmarl* q, const cygym_hmarl_train* tr, const cygym_actions* dst, const char* who, bool own_logits = true) {
   if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
-  if (!q || !dst || (!tr && ((q->master == 1 && !q->master_logits) || (q->net_mask && !q->sub_logits)))) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (!q || !dst || (!tr && own_logits && ((q->master == 1 && !q->master_logits) || (q->net_mask && !q->sub_logits)))) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
   if (const int rc = check_dst(h, dst, who, true)) return rc;
   char bad[96];
   snprintf(bad, sizeof(bad), "%s: bad layout (%%s)", who);
-  if ((q->master != 0 && q->master != 1) || (q->role != 1 && q->role != 2)) return fail(h, CYGYM_EINVAL, bad, "master 0 or 1, role 1 or 2");
-  if (q->n_skills < 1 || q->n_skills > CG_HMARL_MAX_SKILLS || q->n_types < 1 || q->n_types > CG_HMARL_MAX_TYPES)
-    return fail(h, CYGYM_EINVAL, bad, "1 to 8 skills, 1 to 32 action types");
-  if ((q->net_mask || tr) && (q->n_logits < 1 || q->n_logits > HM_MAX_LOGITS || (q->net_mask >> q->n_skills))) return fail(h, CYGYM_EINVAL, bad, "1 to 32 logits per skill, net_mask within the skills");
-  if (q->master == 0 && (q->cheap_idx < 0 || q->cheap_idx >= q->n_skills || q->costly_idx < 0 || q->costly_idx >= q->n_skills || q->global_idx < 0 || q->global_idx >= q->n_skills))
-    return fail(h, CYGYM_EINVAL, bad, "the expert master's indices must name skills");
-  for (int s = 0; s < q->n_skills; ++s) {
-    if (q->n_allowed[s] < 1 || q->n_allowed[s] > CG_HMARL_MAX_TYPES) return fail(h, CYGYM_EINVAL, bad, "a skill allows 1 to 32 action types");
-    for (int i = 0; i < q->n_allowed[s]; ++i)
-      if (q->allowed[s * CG_HMARL_MAX_TYPES + i] >= q->n_types) return fail(h, CYGYM_EINVAL, bad, "an allowed action type is not below n_types");
-  }
-  if (q->fanout < 1 || q->fallback < 0 || q->fallback >= CG_HMARL_MAX_TYPES || !(q->budget >= 0.0) || !(q->budget < 1e300))
-    return fail(h, CYGYM_EINVAL, bad, "fanout >= 1, fallback 0 .. 31, a finite budget >= 0");
-  for (int t = 0; t < q->n_types; ++t)
-    if (q->kind[t] > CG_HMARL_SHUFFLE || q->batch_len[t] < 0 || !(q->cost_comp[t] >= 0.0) || !(q->cost_comp[t] < 1e300) || !(q->cost_not[t] >= 0.0) || !(q->cost_not[t] < 1e300))
-      return fail(h, CYGYM_EINVAL, bad, "a kind above CG_HMARL_SHUFFLE, a negative batch length, or a cost that is negative or not finite");
+  if (const char* const why = hmarl_table_rules(q, tr != nullptr)) return fail(h, CYGYM_EINVAL, bad, why);
   if (tr) {
     if (!tr->h0 || !tr->v_w2 || !tr->v_b2 || !tr->skill_out || !tr->idx_out || !tr->type_out || !tr->logp_out || !tr->value_out ||
         (tr->force_skill < 0 && (!tr->pi_w2 || !tr->pi_b2)))
@@ -1533,6 +1546,68 @@ int cygym_hmarl_sample_decode(cygym_handle* h, const cygym_hmarl* q, const cygym
   const uint8_t* dstatic = h->t.dstatic;
   int M = h->t.M;
   return launch_decode(h, k, dim3((q->n + wpb - 1) / wpb), dim3(wpb * WAVE), lds, stream, {q, dst}, {&live, &dstatic, &M, tr});
+}
+
+int cygym_hmarl_pack_slots(cygym_handle* h, const cygym_hmarl* cfgs, int32_t n, cygym_hmarl_slot* out) {
+  const char* const who = "cygym_hmarl_pack_slots";
+  if (!cfgs || !out) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (n < 1 || n > CG_HMARL_POP_MAX) return fail(h, CYGYM_EINVAL, "%s: 1 to CG_HMARL_POP_MAX strategies", who);
+  char msg[200];
+  for (int s = 0; s < n; ++s) {
+    const cygym_hmarl* q = cfgs + s;
+    const char* why = hmarl_table_rules(q, false);
+    if (!why && (q->role != cfgs->role || q->master != cfgs->master || q->n_skills != cfgs->n_skills || q->n_logits != cfgs->n_logits || q->n_types != cfgs->n_types))
+      why = "role, master, n_skills, n_logits and n_types must agree with slot 0";
+    if (why) {
+      snprintf(msg, sizeof(msg), "%s: slot %d: bad layout (%s)", who, s, why);
+      return fail(h, CYGYM_EINVAL, "%s", msg);
+    }
+  }
+  for (int s = 0; s < n; ++s) {
+    const cygym_hmarl* q = cfgs + s;
+    cygym_hmarl_slot* o = out + s;
+    memset(o, 0, sizeof(*o));
+    o->coin_thr = q->coin_thr;
+    o->budget = q->budget;
+    memcpy(o->cost_comp, q->cost_comp, sizeof(o->cost_comp));
+    memcpy(o->cost_not, q->cost_not, sizeof(o->cost_not));
+    memcpy(o->batch_len, q->batch_len, sizeof(o->batch_len));
+    memcpy(o->kind, q->kind, sizeof(o->kind));
+    memcpy(o->allowed, q->allowed, sizeof(o->allowed));
+    memcpy(o->n_allowed, q->n_allowed, sizeof(o->n_allowed));
+    o->cheap_idx = q->cheap_idx; o->costly_idx = q->costly_idx; o->global_idx = q->global_idx;
+    o->net_mask = q->net_mask; o->fanout = q->fanout; o->fallback = q->fallback;
+  }
+  return CYGYM_OK;
+}
+
+int cygym_hmarl_decode_pop(cygym_handle* h, const cygym_hmarl* q, const cygym_hmarl_pop* pop, const cygym_actions* dst, void* stream) {
+  const char* const who = "cygym_hmarl_decode_pop";
+  if (!h) return fail(h, CYGYM_EINVAL, "%s: null handle", who);
+  if (!q || !pop || !pop->tile_slot || !pop->slots || !q->rows) return fail(h, CYGYM_EINVAL, "%s: null source pointer", who);
+  if (const int rc = hmarl_check(h, q, nullptr, dst, who, false)) return rc;
+  const bool learned = q->master == 1;
+  if (learned && (pop->Hp < 1 || pop->Hp > 256)) return fail(h, CYGYM_EUNSUPPORTED, "%s: the master's hidden width from 1 to 256", who);
+  const int64_t width = (int64_t)(learned ? pop->Hp : 0) + (q->net_mask ? (int64_t)q->n_skills * q->n_logits : 0);   // what a row of h0 holds
+  const char* also_bad = nullptr;
+  if ((width > 0 && !pop->h0) || (learned && (!pop->pi_w2 || !pop->pi_b2)))
+    also_bad = "%s: null source pointer (h0 with a learned master or a skill with a net, pi_w2 / pi_b2 with a learned master)";
+  else if (width == 0 && pop->h0)
+    also_bad = "%s: h0 must be NULL when the master is the expert's and no slot has a net (nothing of it would be read)";
+  else if (width > 0 && (int64_t)pop->ld < width)
+    also_bad = "%s: bad layout (ld >= Hp + n_skills * n_logits; Hp with a learned master only, the logits when a slot has a net)";
+  if (const int rc = check_pop(h, who, pop->n_slots, CG_HMARL_POP_MAX, "%s: 1 to CG_HMARL_POP_MAX strategies", also_bad, pop->n_tiles, true, q->n,
+                               pop->h0_group_stride, width > 0 ? (int64_t)(h->n_envs - 1) * pop->ld + width : 0,
+                               "%s: h0_group_stride is 0 (h0 by source row) or at least one block, (n_envs - 1) ld + Hp + n_skills n_logits")) return rc;
+  if (q->n == 0) return CYGYM_OK;
+  HIPCHK(h, hipSetDevice(h->device_id));
+  const int wpb = hm_waves(h->t.M);   // 4 or 2 (M <= 2048): wpb divides 16, so a workgroup's rows lie in one tile
+  const size_t lds = (size_t)wpb * hm_wave_bytes(h->t.M);
+  const void* k = (q->skill_out || q->type_out || pop->logits_out) ? (const void*)hmarl_pop_kernel<true> : (const void*)hmarl_pop_kernel<false>;
+  const uint8_t* live = (const uint8_t*)h->b.live;
+  const uint8_t* dstatic = h->t.dstatic;
+  int M = h->t.M;
+  return launch_decode(h, k, dim3(16 * pop->n_tiles / wpb), dim3(wpb * WAVE), lds, stream, {q, pop, dst}, {&live, &dstatic, &M});
 }
 
 // What cygym_meta_decode and cygym_meta_decode_pop check alike, in the order a caller sees (own_ptrs: the pointers of the function's

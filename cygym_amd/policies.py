@@ -638,7 +638,8 @@ class _TiledPopulation(_PolicyPopulation):
     observations are ALREADY in that padded order (rollout_grid builds its gather that way, once, at plan time): write() then gathers
     nothing.  Without counts write() takes the caller's tiles (shared_obs).
     A subclass sets MIN_MEMBERS (the smallest population worth grouping: measured), state_dim and n_devices (what obs and the batch
-    must have) and writes
+    must have; n_devices None: any batch; state_dim None: no member reads the state -- no first layer, obs is not checked, _launch gets
+    x = None: only HMARLPolicyGroup uses either None, the other families always set both) and writes
       _stacked(batch=None, device=None)                        the stacked pack, a dict
       _first_layer(obs_s, pack)                                [S, n, w] from obs_s [S, n, W] (or an expanded [n, W])
       _launch(batch, act, rows, tile_slot, x, pack, **outs)    its batch.*_decode_pop on the first layer's result x."""
@@ -679,16 +680,16 @@ class _TiledPopulation(_PolicyPopulation):
         tile order (not at all when in_tile_order, or when every count is the same multiple of 16) and the first layer is formed per
         source row.  shared_obs: `rows` [16 T] and tile_slot [T] are the caller's tiles, made on the device (the draw of a mixture), obs
         [N, W] holds every env once: the first layer is [S, N, w] and the kernel reads the block of the tile's slot."""
-        S_, W = len(self.policies), self.state_dim
-        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != W:
+        S_, W = len(self.policies), self.state_dim      # (W None: no member reads the state -- no first layer, x is None)
+        if W is not None and (obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != W):
             raise ValueError(f"obs must be a float32 [n, {W}] role view")
-        if batch.M != self.n_devices:
+        if self.n_devices is not None and batch.M != self.n_devices:
             raise ValueError(f"the nets were built for {self.n_devices} devices, the batch has {batch.M}")
         pack = self._stacked(batch, obs.device)
         if shared_obs:
             if tile_slot is None or rows is None:
                 raise ValueError("shared_obs: the caller says which tile plays whom (rows = rows_tiled, tile_slot)")
-            x = self._first_layer(obs[None].expand(S_, int(obs.shape[0]), W), pack)
+            x = None if W is None else self._first_layer(obs[None].expand(S_, int(obs.shape[0]), W), pack)
         else:
             if self.counts is None:
                 raise ValueError("rows ordered member after member need counts")
@@ -699,10 +700,12 @@ class _TiledPopulation(_PolicyPopulation):
                     raise ValueError(f"rows in tile order: {n_pad} padded rows (tile_plan)")
             else:
                 self._check_counts(n, rows is not None and int(rows.numel()) == n)
-                obs = obs.index_select(0, pos)
+                obs = obs.index_select(0, pos) if W is not None else obs
                 rows = torch.where(valid, rows.index_select(0, pos), torch.full_like(rows[:1], -1))
-            x = self._first_layer(obs.reshape(S_, n_pad // S_, W), pack)
-            x = x.reshape(n_pad, int(x.shape[2]))
+            x = None
+            if W is not None:
+                x = self._first_layer(obs.reshape(S_, n_pad // S_, W), pack)
+                x = x.reshape(n_pad, int(x.shape[2]))
         return self._launch(batch, act, rows, tile_slot, x, pack, **outs)
 
 
@@ -2207,6 +2210,7 @@ class HMARLConfig:
         if not (0.0 <= self.budget < 1e300) or self.fanout < 1:
             raise ValueError("budget must be finite and >= 0, fanout >= 1")
         self.fallback = 8 if role == "defender" else 3      # HMARL.py:311
+        self.net_mask = sum(1 << s for s, h in enumerate(self.has_net) if h)      # bit s: skill s has a net
         self._c = None
 
     def table(self):
@@ -2264,7 +2268,7 @@ class HMARLConfig:
             q.coin_thr, q.budget, q.role, q.master = R.bernoulli_threshold(self.global_prob), self.budget, self.role_code, int(self.master == "learned")
             q.cheap_idx, q.costly_idx, q.global_idx = self.cheap_idx, self.costly_idx, self.global_idx
             q.n_skills, q.n_logits, q.n_types = self.n_skills, self.n_logits, abi.HMARL_MAX_TYPES
-            q.net_mask = sum(1 << s for s, h in enumerate(self.has_net) if h)
+            q.net_mask = self.net_mask
             q.fanout, q.fallback = self.fanout, self.fallback
             self._c = q
         import ctypes as C
@@ -2612,6 +2616,135 @@ class HMARLPolicy:
     def __call__(self, obs, t, M, L):
         raise NotImplementedError("an HMARLPolicy answers with groups of devices in cost batches: a dict of single actions cannot "
                                   "carry them (it runs through write(), on a batch with cygym_hmarl_decode)")
+
+
+def hmarl_pack_slots(cfgs):
+    """The slot table of a population of H-MARL strategies, uint8 [S, sizeof cygym_hmarl_slot] on the host: cygym_hmarl_pack_slots on
+    the configs' to_c(), the only producer of the table.  It validates every config with the table rules of the decode and checks that
+    role, master, n_skills, n_logits and n_types agree; a refusal raises ValueError with the library's message, which names the slot."""
+    import ctypes as C
+    from . import _lib, abi
+    cfgs = list(cfgs)
+    n = len(cfgs)
+    arr = (abi.Hmarl * max(n, 1))()
+    for s, c in enumerate(cfgs):
+        q = c.to_c() if hasattr(c, "to_c") else c
+        C.memmove(C.byref(arr, s * C.sizeof(abi.Hmarl)), C.byref(q), C.sizeof(abi.Hmarl))
+    out = (abi.HmarlSlot * max(n, 1))()
+    lib = _lib.load()
+    rc = lib.cygym_hmarl_pack_slots(None, arr, n, out)
+    if rc != 0:
+        msg = lib.cygym_last_error(None)
+        raise ValueError(f"cygym_hmarl_pack_slots failed ({rc}): {msg.decode() if msg else ''}")
+    import numpy as np
+    return torch.from_numpy(np.frombuffer(bytes(out), dtype=np.uint8).reshape(n, C.sizeof(abi.HmarlSlot)).copy())
+
+
+class HMARLPolicyGroup(_TiledPopulation):
+    """A population of HMARLPolicy (`hmarl_expert` / `hmarl_meta`) strategies of ONE key decided together: the first layers of all of
+    them -- pi_fc1 of a learned master and every skill's fc -- are one batched GEMM and the decision of all of them is ONE launch
+    (cygym_hmarl_decode_pop), the tables and the master's head of a tile of 16 rows taken from a slot table; the master's second layer
+    is formed on chip.  A member's own turn is up to three addmm and a launch of a wave per row, so a launch per strategy over that
+    strategy's few rows leaves most of the chip idle; the |D| x |A| grid of a Double-Oracle population with --BR_type hmarlmeta /
+    hmarlexpert and the opponent drawn per env from an equilibrium (MixturePolicy) hold several such strategies, each deciding for a
+    few envs.  Members may differ in weights, allowed lists, which skills have a net (zero columns, as HMARLPolicy._packed has them),
+    budget, fanout, the expert's indices and global_prob.  A population in which no member reads the state forms no first layer and
+    passes no h0: still one launch.
+    counts / in_tile_order / shared_obs: the three row conventions of _TiledPopulation.  write() takes skill_out / type_out /
+    logits_out of hmarl_decode_pop by keyword.  It writes GROUPS, like its members."""
+
+    NOUN = "strategies"
+    MIN_MEMBERS = 2           # the smallest population simulate_grid groups: at S = 2, 4, 8, 16, 32 members with 8, 64 and 512 rows each the
+    #                           grouped turn was faster than the members one by one at every row count, with both masters (PERFLOG.md,
+    #                           "The H-MARL decode for a population of strategies": 0.074 against 0.093 ms in the narrowest case)
+    MIN_MEMBERS_MIXTURE = 2   # ... and the smallest MixturePolicy groups: the same finding for the mixture turn, h0 formed for every
+    #                           (member, env) included (0.086 against 0.106 ms in the narrowest case)
+    writes_groups = True
+
+    def __init__(self, policies, counts=None, in_tile_order: bool = False):
+        super().__init__(policies, counts, in_tile_order)
+        p0 = self.policies[0]
+        k0 = self.key(p0, 0)
+        if k0 is None or any(self.key(p, 0) != k0 for p in self.policies):
+            raise ValueError("the members are HMARLPolicy of one key (HMARLPolicyGroup.key)")
+        self.role, self.state_dim, self.n_devices, self._plist = p0.role, p0.state_dim, None, None
+        self.cfgs = [p.cfg for p in self.policies]
+        self.action_types = sorted({t for p in self.policies for t in p.action_types})
+        self.n_types = max(p.n_types for p in self.policies)
+
+    @staticmethod
+    def key(p, M):
+        """What must agree across the members of a population -- role, master kind, state width (None: the state is not read), the
+        master's hidden width (0: expert), n_skills, n_logits, whether any skill has a net -- or None when `p` is no HMARLPolicy.
+        Host values only."""
+        if not isinstance(p, HMARLPolicy):
+            return None
+        c = p.cfg
+        return (p.role, c.master, p.state_dim, int(p.master.pi_fc1.out_features) if p.master is not None else 0, c.n_skills, c.n_logits,
+                any(c.has_net))
+
+    def groups_needed(self, M: int) -> int:
+        """The most groups a row can have: the members' maximum."""
+        return max(p.groups_needed(M) for p in self.policies)
+
+    def _params(self):
+        """The parameters the stacked pack is made of (the members' modules are fixed: the list is made once)."""
+        if self._plist is None:
+            lins = [l for p in self.policies for l in ([p.master.pi_fc1, p.master.pi_fc2] if p.master is not None else []) + [n.fc for n in p.subnets if n is not None]]
+            self._plist = [q for l in lins for q in (l.weight, l.bias)]
+        return self._plist
+
+    @torch.no_grad()
+    def _stacked(self, batch=None, device=None):
+        """The members' tables slot after slot, as the dict hmarl_decode_pop reads: "slots" (cygym_hmarl_pack_slots' records, uploaded
+        once per stacked pack), with a learned master pi_w2 [S, n_skills, Hp] / pi_b2 [S, n_skills] / Hp, and the batched operands of
+        the first layer w0_t [S, W, Hp + n_skills K] / b0 [S, 1, Hp + n_skills K] (pi_fc1 | every skill's fc, zero columns for a skill
+        without a net; absent when no member reads the state).  Redone when a member's parameter changes in place (the parameters'
+        own versions) or the device does."""
+        params = self._params()
+        if device is None:
+            device = params[0].device if params else getattr(batch, "device", "cpu")
+        device = torch.device(device)
+
+        def build():
+            p0 = self.policies[0]
+            c0 = p0.cfg
+            S_, NS, K = len(self.policies), c0.n_skills, c0.n_logits
+            learned, nets = p0.master is not None, any(c0.has_net)
+            pack = {"S": S_, "slots": hmarl_pack_slots(self.cfgs).to(device), "Hp": 0}
+            if learned:
+                pack.update(Hp=int(p0.master.pi_fc1.out_features),
+                            pi_w2=torch.stack([p.master.pi_fc2.weight.detach().to(device) for p in self.policies]).contiguous(),
+                            pi_b2=torch.stack([p.master.pi_fc2.bias.detach().to(device) for p in self.policies]).contiguous())
+            if self.state_dim is not None:
+                W = self.state_dim
+                ws, bs = [], []
+                for p in self.policies:
+                    cw = [p.master.pi_fc1.weight.detach().t().to(device)] if learned else []
+                    cb = [p.master.pi_fc1.bias.detach().to(device)] if learned else []
+                    for net in (p.subnets if nets else []):
+                        cw.append(net.fc.weight.detach().t().to(device) if net is not None else torch.zeros((W, K), dtype=torch.float32, device=device))
+                        cb.append(net.fc.bias.detach().to(device) if net is not None else torch.zeros((K,), dtype=torch.float32, device=device))
+                    ws.append(torch.cat(cw, dim=1))
+                    bs.append(torch.cat(cb))
+                pack.update(w0_t=torch.stack(ws).contiguous(), b0=torch.stack(bs)[:, None, :].contiguous())
+                assert tuple(pack["w0_t"].shape) == (S_, W, pack["Hp"] + (NS * K if nets else 0))
+            return pack
+        return self._cached((device, tuple(id(q) for q in params), tuple(q._version for q in params)), build)
+
+    def h0(self, obs_s, pack):
+        """[S, n, Hp + n_skills K]: pi_fc1's pre-activations | the skills' fc logits of every (strategy, row) of obs_s [S, n, W] (or an
+        expanded [n, W]): one baddbmm."""
+        return torch.baddbmm(pack["b0"], obs_s, pack["w0_t"])
+
+    _first_layer = h0
+
+    def _launch(self, batch, act, rows, tile_slot, x, pack, **outs):
+        batch.hmarl_decode_pop(rows, tile_slot, x, pack, self.cfgs, act=act, **outs)
+
+    def __call__(self, obs, t, M, L):
+        raise NotImplementedError("an HMARLPolicyGroup answers with groups of devices in cost batches: it runs through write(), on a "
+                                  "batch with cygym_hmarl_decode_pop")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -3157,7 +3290,11 @@ class MixturePolicy:
       6. among the other members, the MetaPolicy (MetaDOAR) of ONE key (MetaPolicyGroup.key) that can play,
          MetaPolicyGroup.MIN_MEMBERS_MIXTURE or more, when none of steps 2, 4 and 5 holds the member_slot table: one baddbmm forms h0
          for every (strategy, env) and ONE cygym_meta_decode_pop decodes the draw's tiles (tiled = False: off);
-      7. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
+      7. among the other members, the HMARLPolicy (H-MARL) of ONE key (HMARLPolicyGroup.key) that can play,
+         HMARLPolicyGroup.MIN_MEMBERS_MIXTURE or more, when none of steps 2, 4, 5 and 6 holds the member_slot table: one baddbmm forms
+         the first layer for every (strategy, env) -- none when no member reads the state -- and ONE cygym_hmarl_decode_pop decodes
+         the draw's tiles (tiled = False: off);
+      8. every other member on the path it has today, over rows_masked[s] (the writers skip negative rows); names and sequences run as
          rollout_grid.SequencePolicy + write_actions with the tick the loop set (set_tick: the loop's tick counter; a callable without
          uses_global_tick gets t // 2, as the loops call it).  A member of probability 0 never plays and is not launched.
     act["n_groups"] is the caller's to clear before the call (Turns.opponent, ddpg_rollout.collect do); a member that writes groups sets
@@ -3244,6 +3381,11 @@ class MixturePolicy:
         table already serves another population (the MetaDOAR members then play one by one)."""
         return self._same_key_group(batch, MetaPolicyGroup, "meta_decode_pop", MetaPolicyGroup.MIN_MEMBERS_MIXTURE, taken)
 
+    def _hmarl_group(self, batch, taken: bool):
+        """_same_key_group for the HMARLPolicy members, HMARLPolicyGroup.MIN_MEMBERS_MIXTURE or more.  taken: the draw's one
+        member_slot table already serves another population (the H-MARL members then play one by one)."""
+        return self._same_key_group(batch, HMARLPolicyGroup, "hmarl_decode_pop", HMARLPolicyGroup.MIN_MEMBERS_MIXTURE, taken)
+
     def _state(self, batch):
         st = self._st
         if st is None or st["batch"] is not batch:
@@ -3254,11 +3396,12 @@ class MixturePolicy:
             mgrp, mslots = self._comm_group(batch, grp is not None)
             hgrp, hslots = self._hier_group(batch, grp is not None or mgrp is not None)
             tgrp, tslots = self._meta_group(batch, grp is not None or mgrp is not None or hgrp is not None)
+            lgrp, lslots = self._hmarl_group(batch, grp is not None or mgrp is not None or hgrp is not None or tgrp is not None)
             # the draw reads ONE member_slot table: the actors', else the comm nets', else the HAGS nets', else the MetaDOAR
-            # strategies' (at most one of the four lives)
-            slots = mslots if mgrp is not None else hslots if hgrp is not None else tslots if tgrp is not None else aslots
-            live = [(g, sl) for g, sl in ((grp, aslots), (cgrp, cslots), (mgrp, mslots), (hgrp, hslots), (tgrp, tslots)) if g is not None]
-            tiles = grp is not None or mgrp is not None or hgrp is not None or tgrp is not None
+            # strategies', else the H-MARL strategies' (at most one of the five lives)
+            slots = mslots if mgrp is not None else hslots if hgrp is not None else tslots if tgrp is not None else lslots if lgrp is not None else aslots
+            live = [(g, sl) for g, sl in ((grp, aslots), (cgrp, cslots), (mgrp, mslots), (hgrp, hslots), (tgrp, tslots), (lgrp, lslots)) if g is not None]
+            tiles = grp is not None or mgrp is not None or hgrp is not None or tgrp is not None or lgrp is not None
             T = (N + 15) // 16 + S_
             z = lambda shape, dt, v=0: torch.full(shape, v, dtype=dt, device=dev)  # noqa: E731
             st = self._st = dict(batch=batch, group=grp, slots=slots, cdf=torch.from_numpy(self.cdf).to(dev),
@@ -3268,6 +3411,7 @@ class MixturePolicy:
                                  rows_tiled=z((16 * T,), torch.int32, -1) if tiles else None,
                                  tile_slot=z((T,), torch.int32, -1) if tiles else None,
                                  comm=mgrp, comm_slots=mslots, hier=hgrp, hier_slots=hslots, meta=tgrp, meta_slots=tslots,
+                                 hmarl=lgrp, hmarl_slots=lslots,
                                  critics=cgrp, critic_slots=cslots, critic_slot_of=torch.tensor(cslots, dtype=torch.int32, device=dev),
                                  slot_of_row=z((N,), torch.int32, -1) if cgrp is not None else None,
                                  live=[g for g, _ in live], held=[any(sl[s] >= 0 for _, sl in live) for s in range(S_)])
@@ -3296,7 +3440,7 @@ class MixturePolicy:
                            mode=act["mode"], rows_masked=st["rows_masked"], rows_tiled=st["rows_tiled"], tile_slot=st["tile_slot"])
         self.last_index = st["index"]
         in_place = obs.dtype == torch.float32 and obs.dim() == 2 and obs.stride(1) == 1 and int(obs.shape[0]) >= N
-        for g in (st["live"] if in_place else []):      # (in the order actors, critics, comm nets, HAGS nets, MetaDOAR strategies)
+        for g in (st["live"] if in_place else []):      # (in the order actors, critics, comm nets, HAGS nets, MetaDOAR, H-MARL strategies)
             if isinstance(g, ActorPolicyGroup):
                 hidden, head = g._packed_all(batch)
                 p0 = g.policies[0]

@@ -308,6 +308,15 @@ def _group_meta(batch, items, M):
     return _group_same_key(batch, items, M, G, G.MIN_MEMBERS, hasattr(batch, "meta_decode_pop"), _rows_tiled)
 
 
+def _group_hmarl(batch, items, M):
+    """The same step for the H-MARL strategies (policies.HMARLPolicy) of ONE key (policies.HMARLPolicyGroup.key: role, master kind,
+    widths, skills, nets or none), HMARLPolicyGroup.MIN_MEMBERS or more: one baddbmm (none when no member reads the state) and one
+    cygym_hmarl_decode_pop per role and tick over all their rows, in the padded tile order of _group_comm.  The item writes groups,
+    as its members do."""
+    from .policies import HMARLPolicyGroup as G
+    return _group_same_key(batch, items, M, G, G.MIN_MEMBERS, hasattr(batch, "hmarl_decode_pop"), _rows_tiled)
+
+
 def _role_actions(batch, pol, M, L):
     """One action dict per role: the roles share every tensor but the mode words (no per-tick copy in steady state).  A role
     with a strategy that writes groups (`writes_groups`: policies.CommActorPolicy and its populations, policies.HMARLPolicy, policies.MetaPolicy) also gets an n_groups tensor of its own: the
@@ -419,7 +428,7 @@ def simulate_grid(batch, def_policies, att_policies, n_mc: int, T: int, randomiz
                 items.append((p, t64, t64.to(torch.int32), sl, None))
             # the whole grid in env order: env e plays defender strategy e // (nA n_mc) and attacker strategy (e // n_mc) % nA
             rpg = (nA * n_mc if r == HL.DEFENDER else n_mc) if (S_sub == 1 and cell_offset == 0 and N == cells) else None
-            plan[r].append(_group_meta(batch, _group_hier(batch, _group_comm(batch, _group_critics(batch, _group_actors(batch, items, M, rpg) if fused else items, M), M), M), M))
+            plan[r].append(_group_hmarl(batch, _group_meta(batch, _group_hier(batch, _group_comm(batch, _group_critics(batch, _group_actors(batch, items, M, rpg) if fused else items, M), M), M), M), M))
     bl = baseline_schedule(def_policies, att_policies, cell_np, n_mc, min(T, 4), _cfg_baseline_code(batch))
     # (ticks >= 2 repeat with period 2: rows 2 / 3 of the schedule; shorter runs only have the first rows)
     mode_words = [torch.from_numpy(((bl[t] + 1) << S.MODE_BASELINE_SHIFT) | (t % 2)).to(device=dev, dtype=torch.int32)

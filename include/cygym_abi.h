@@ -1173,8 +1173,8 @@ typedef struct cygym_hier_pop {
  * 16 n_tiles; h0_group_stride < 0, or > 0 and smaller than one block, (n_envs - 1) h0_stride + 3 H.  CYGYM_ENOTBOUND only when the
  * flag plane is needed (vis_fixeds == NULL) and the handle is not bound.  Every other check, limit and message convention is that of
  * cygym_hier_decode.  Nothing is launched and nothing is written on a refusal.
- * Out of scope: the sampled (training) decision for a population; populations of H-MARL and committee strategies (`meta`
- * strategies: cygym_meta_decode_pop); building h0 on chip. */
+ * Out of scope: the sampled (training) decision for a population; populations of committee strategies (`meta` strategies:
+ * cygym_meta_decode_pop; H-MARL strategies: cygym_hmarl_decode_pop); building h0 on chip. */
 int cygym_hier_decode_pop(cygym_handle* h, const cygym_hier_net* net /* slot 0 */, const cygym_hier_pop* pop,
                           const cygym_action_vectors* layout, const cygym_actions* dst, void* stream);
 
@@ -1394,6 +1394,79 @@ typedef struct cygym_hmarl_train {
  * CYGYM_EUNSUPPORTED (nothing is written): Hp (phase 2) or Hv outside 1 .. 256; more than 2048 devices.  CYGYM_ENOTBOUND as the decode. */
 int cygym_hmarl_sample_decode(cygym_handle* h, const cygym_hmarl* q, const cygym_hmarl_train* tr, const cygym_actions* dst, void* stream);
 
+/* One strategy of a population of H-MARL strategies: the fields of cygym_hmarl that are no pointers and may differ between the members,
+ * with the meaning they have there.  The 8-byte fields come first, the byte tables start on multiples of 4 and the record is a multiple
+ * of 16 bytes: the kernel reads the byte tables as aligned 32-bit words.  Written by cygym_hmarl_pack_slots only. */
+#define CG_HMARL_POP_MAX 32   /* = CG_MIXTURE_MAX_MEMBERS */
+typedef struct cygym_hmarl_slot {
+  uint64_t coin_thr;
+  double   budget;
+  double   cost_comp[CG_HMARL_MAX_TYPES];
+  double   cost_not[CG_HMARL_MAX_TYPES];
+  int32_t  batch_len[CG_HMARL_MAX_TYPES];
+  uint8_t  kind[CG_HMARL_MAX_TYPES];
+  uint8_t  allowed[CG_HMARL_MAX_SKILLS * CG_HMARL_MAX_TYPES];
+  uint8_t  n_allowed[CG_HMARL_MAX_SKILLS];
+  int32_t  cheap_idx;
+  int32_t  costly_idx;
+  int32_t  global_idx;
+  uint32_t net_mask;
+  int32_t  fanout;
+  int32_t  fallback;
+} cygym_hmarl_slot;
+
+/* A population of H-MARL strategies of ONE role, master kind, n_skills, n_logits and n_types for cygym_hmarl_decode_pop.  DEVICE pointers. */
+typedef struct cygym_hmarl_pop {
+  const int32_t* tile_slot;      /* [n_tiles] the strategy of tile t (source rows 16 t .. 16 t + 15): 0 .. n_slots - 1; any other value:
+                                    the tile is left alone                                                                             */
+  const cygym_hmarl_slot* slots; /* [n_slots] the members' tables, as cygym_hmarl_pack_slots wrote them (uploaded by the caller)         */
+  const float* h0;               /* rows of ld floats: [Hp pre-activations of pi_fc1 (learned master only) | n_skills * n_logits fc logits
+                                    of the skills, already final, zeros for a skill without a net].  MANDATORY when the master is learned
+                                    or ANY slot has a net (cygym_hmarl.net_mask of `q` is the UNION of the slots' masks: the host knows
+                                    it); NULL otherwise                                                                                */
+  const float* pi_w2;            /* [n_slots][n_skills][Hp] pi_fc2.weight of every slot (learned master)                                */
+  const float* pi_b2;            /* [n_slots][n_skills]     pi_fc2.bias                                                                 */
+  float*   logits_out;           /* optional [16 n_tiles][n_skills]: the master's logits of source row r (learned master)               */
+  int64_t  h0_group_stride;      /* floats.  0: h0 is [16 n_tiles][ld] by source row, each row formed with ITS strategy.  > 0: h0 is
+                                    [n_slots][n_envs][ld], block s at s * h0_group_stride formed with strategy s, and the row of env e
+                                    in tile t reads block tile_slot[t] at row e                                                        */
+  int32_t  ld;                   /* row pitch of h0 in floats                                                                          */
+  int32_t  Hp;                   /* width of pi_fc1, 1 .. 256 (learned master; not read with an expert master: the h0 row then starts
+                                    with the skills' logits)                                                                           */
+  int32_t  n_slots;              /* 1 .. CG_HMARL_POP_MAX                                                                              */
+  int32_t  n_tiles;              /* q->n = 16 * n_tiles                                                                                */
+} cygym_hmarl_pop;
+
+/* Host only, touches no GPU: validate the n configs with the table rules of cygym_hmarl_decode (the same code), check that role, master,
+ * n_skills, n_logits and n_types agree across them, and write the n records of `out` (host memory).  The pointers, n, and the
+ * outputs of the configs are not read.  `h` may be NULL.  CYGYM_EINVAL: NULL cfgs / out, n outside 1 .. CG_HMARL_POP_MAX, a config that
+ * breaks a rule or disagrees with config 0 -- cygym_last_error names the slot; nothing of `out` is to be used then.  The only producer
+ * of the slot table. */
+int cygym_hmarl_pack_slots(cygym_handle* h /* may be NULL */, const cygym_hmarl* cfgs, int32_t n, cygym_hmarl_slot* out);
+
+/* cygym_hmarl_decode for a population of strategies in ONE launch: source row r -- skill, type, ordered targets, float64 cost batches,
+ * fanout, groups, cuts, CG_DECODE_TRUNCATED, every draw -- is decided exactly as cygym_hmarl_decode decides it with the tables of slot
+ * s = pop->tile_slot[r / 16] and, for a learned master, the master logits  pi_b2[s][k] + sum_c relu(h0[c]) pi_w2[s][k][c]  formed on
+ * chip in the arithmetic of cygym_hmarl_sample_decode (lane j adds its columns j, j + 64, ... in ascending order with fmaf, the xor
+ * butterfly 32 .. 1, then the bias); the skill's logits are columns Hp + skill * n_logits .. of the h0 row.  So a learned population's
+ * turn is ONE batched GEMM of the caller plus ONE launch.  The work shape is cygym_hmarl_decode's: one wave per source row, 4 rows per
+ * workgroup up to 1600 devices, else 2 (both divide 16: a workgroup's rows lie in one tile), no workgroup barrier, no atomics, no draw
+ * of its own; a row's bits do not depend on what shares its tile.
+ * `q` describes the population: role, master, n_skills, n_logits, n_types; net_mask = the UNION of the slots' masks (a slot's bit
+ * outside it is ignored); skill_out / type_out (optional, [16 n_tiles] by source row), status, and the MANDATORY tiled row list
+ * rows [16 n_tiles] (-1 = no row, skipped like a row >= n_envs) with q->n = 16 n_tiles -- the layout cygym_mixture_draw writes.  Its
+ * tables are checked as cygym_hmarl_decode checks them (they are slot 0's) but the kernel reads the slots' records; master_logits and
+ * sub_logits are not read.  A tile whose slot is negative or >= n_slots writes NOTHING: no action row, no optional output, no status bit.
+ * CYGYM_EUNSUPPORTED: n_slots outside 1 .. CG_HMARL_POP_MAX; Hp outside 1 .. 256 with a learned master.  CYGYM_EINVAL: NULL pop,
+ * tile_slot, slots or q->rows; NULL h0 when the master is learned or q->net_mask != 0; NULL pi_w2 / pi_b2 with a learned master; a
+ * non-NULL h0 with an expert master and q->net_mask == 0; ld < Hp + n_skills * n_logits (ld < Hp when q->net_mask == 0; Hp counts only with a learned master); q->n != 16 n_tiles;
+ * h0_group_stride < 0, or > 0 and smaller than one block, (n_envs - 1) ld + that width.  Every other check, limit and message
+ * convention is that of cygym_hmarl_decode.  Nothing is launched and nothing is written on a refusal.
+ * Out of scope: the sampled (training) decision for a population; populations of committee strategies; mixed expert and learned
+ * masters in one population; building the observation on chip. */
+int cygym_hmarl_decode_pop(cygym_handle* h, const cygym_hmarl* q /* slot 0 */, const cygym_hmarl_pop* pop, const cygym_actions* dst,
+                           void* stream);
+
 /* A MetaDOAR strategy (meta_hierarchical_br.py: MetaHierarchicalBestResponse, type_mapping["meta"]) and the role's DDPG critic in the
  * pieces the decode below reads, all fp32.  DEVICE pointers.  With id_dim, embed_dim = ED, proj_dim = P the controller is
  *   X_i   = [struct_feats.id_emb[i] (id_dim), degn_i, known_i, owned_i]                      (:150-185; Not_yet_added is no feature)
@@ -1540,8 +1613,8 @@ typedef struct cygym_meta_pop {
  * h0_group_stride < 0, or > 0 and smaller than one block, (n_envs - 1) h0_stride + Hp + H1.  CYGYM_ENOTBOUND only when the flags are
  * needed (flags_fixeds == NULL) and the handle is not bound.  Every other check, limit and message convention is that of
  * cygym_meta_decode.  Nothing is launched and nothing is written on a refusal.
- * Out of scope: the sampled or observer decision (cygym_meta_select) for a population; populations of H-MARL and committee
- * strategies; staging the critic once per tile with several rows per wave; building h0 on chip; M > 1000. */
+ * Out of scope: the sampled or observer decision (cygym_meta_select) for a population; populations of committee strategies
+ * (H-MARL strategies: cygym_hmarl_decode_pop); staging the critic once per tile with several rows per wave; building h0 on chip; M > 1000. */
 int cygym_meta_decode_pop(cygym_handle* h, const cygym_meta* q /* slot 0 */, const cygym_meta_pop* pop, const cygym_actions* dst,
                           void* stream);
 

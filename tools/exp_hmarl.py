@@ -5,7 +5,14 @@ one process, HIP events after warm-up:
   (b) HMARLPolicy.write: the addmm plus cygym_hmarl_decode, per role and master; the launch also alone, and with one forced type per
       launch (13: one device per group; 11: batches of 29; the defender's type 1: the float64 walk; the attacker's type 1: the shuffle)
   (c) beside it one cygym_step of the same batch
-One JSON line per measurement: median and min..max over --reps repetitions."""
+One JSON line per measurement: median and min..max over --reps repetitions.
+--pop: the population leg alone, 256 devices, the reference's widths (master hidden 128, 8 logits per skill), the defender's view, both
+masters, S = 2, 4, 8, 16, 32 same-key strategies with 8, 64 and 512 rows each, the two legs alternating inside every repetition:
+  grid form     S HMARLPolicy.write calls over the members' own rows (the ungrouped path) against the gather of the padded tile order
+                plus ONE HMARLPolicyGroup.write (one baddbmm + cygym_hmarl_decode_pop), as simulate_grid's tick runs them
+  mixture form  a MixturePolicy of the S members with equal weights on a batch of S x rows envs, members one by one (tiled=False: every
+                member's launch walks all envs' masked rows) against the population launch with h0 for every (member, env)
+and a last line with the smallest S from which the grouped median is below the other at every row count, per form."""
 import argparse
 import json
 import os
@@ -27,20 +34,93 @@ ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--host-rows", type=int, default=256)
 ap.add_argument("--label", default="")
+ap.add_argument("--pop", action="store_true")
 args = ap.parse_args()
 
 M, N = args.devices, args.envs
 dev = "cuda:0"
 topo, init, ck = make_topology(M, 1, seed=0, max_extra=0)
 cfg = abi.EnvConfig(seed=0, lambda_events=0.0, auto_reset=1, **ck)
-env1 = BatchedCyberDefenseEnv(topo, cfg, N, init, device=dev, max_groups=1, max_devs=M)
-env1.randomize()
-for t in range(6):      # a few ticks of the synthetic script: compromised, owned and reachable devices in every env
-    env1.gen_actions(t)
-    env1.step()
-st = env1.state_numpy()
-env1.close()
-env = BatchedCyberDefenseEnv(topo, cfg, N, st, device=dev, max_groups=M, max_devs=M)
+
+
+def played_batch(n):
+    """A batch of n envs a few ticks into the synthetic script: compromised, owned and reachable devices in every env."""
+    env1 = BatchedCyberDefenseEnv(topo, cfg, n, init, device=dev, max_groups=1, max_devs=M)
+    env1.randomize()
+    for t in range(6):
+        env1.gen_actions(t)
+        env1.step()
+    st = env1.state_numpy()
+    env1.close()
+    return BatchedCyberDefenseEnv(topo, cfg, n, st, device=dev, max_groups=M, max_devs=M), st
+
+
+if args.pop:
+    from cygym_amd import policies as P
+    from cygym_amd.rollout_grid import _rows_tiled
+    P.HMARLPolicyGroup.MIN_MEMBERS_MIXTURE = 2      # (measure the grouped mixture whatever the shipped threshold says)
+    SIZES, ROWS, role = (2, 4, 8, 16, 32), (8, 64, 512), "defender"
+    sd = 6 * M
+
+    def member(learned, seed):
+        torch.manual_seed(seed)
+        nets = [_HMARLSkillNet(sd, 8).to(dev) for _ in range(3)]
+        pol = HMARLPolicy(role, _HMARLMaster(sd, 3).to(dev) if learned else {"global_prob": 0.1}, nets)
+        pol._packed(torch.device(dev))
+        return pol
+
+    def measure(legs):
+        """The legs one after the other inside every repetition, HIP events around each: {leg: (median, min, max)}."""
+        ms = {k: [] for k in legs}
+        for rep in range(args.warmup + args.reps):
+            for k, fn in legs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); fn(); e1.record()
+                e1.synchronize()
+                if rep >= args.warmup:
+                    ms[k].append(e0.elapsed_time(e1))
+        return {k: (sorted(v)[len(v) // 2], min(v), max(v)) for k, v in ms.items()}
+
+    batches = {}
+    wins = {}      # (form, master) -> {S: grouped below one by one at every row count}
+    for learned in (False, True):
+        master = "learned" if learned else "expert"
+        pols = [member(learned, 1 + s) for s in range(max(SIZES))]
+        for S_ in SIZES:
+            for rows in ROWS:
+                n = S_ * rows
+                if n not in batches:
+                    b = played_batch(n)[0]
+                    batches[n] = (b, b.observe(1))
+                env, obs = batches[n]
+                chunk = [(pols[s], torch.arange(s * rows, (s + 1) * rows, device=dev)) for s in range(S_)]
+                grp, r64, r32, sl = _rows_tiled(P.HMARLPolicyGroup, chunk)
+                each = [(p, r.to(torch.int32), slice(int(r[0]), int(r[-1]) + 1)) for p, r in chunk]
+                mixes = {tiled: P.MixturePolicy(pols[:S_], [1.0 / S_] * S_, role, tiled=tiled) for tiled in (False, True)}
+                forms = {"grid": {"one by one": lambda each=each, env=env, obs=obs: [p.write(env, None, r, obs[s]) for p, r, s in each],
+                                  "grouped": lambda g=grp, env=env, obs=obs, r64=r64, r32=r32, sl=sl:
+                                      g.write(env, None, r32, obs[sl] if sl is not None else obs.index_select(0, r64))},
+                         "mixture": {"one by one": lambda m=mixes[False], env=env, obs=obs: m.write(env, env.act, None, obs),
+                                     "grouped": lambda m=mixes[True], env=env, obs=obs: m.write(env, env.act, None, obs)}}
+                for form, legs in forms.items():
+                    res = measure(legs)
+                    for leg, (med, lo, hi) in res.items():
+                        print(json.dumps({"what": f"{form} turn, {leg}", "label": args.label, "master": master, "S": S_, "rows_per_member": rows, "envs": n,
+                                          "devices": M, "ms": round(med, 4), "ms_min_max": [round(lo, 4), round(hi, 4)], "reps": args.reps}), flush=True)
+                    ok = wins.setdefault((form, master), {})
+                    ok[S_] = ok.get(S_, True) and res["grouped"][0] < res["one by one"][0]
+                assert mixes[True]._st["hmarl"] is not None and mixes[False]._st["hmarl"] is None
+    for env, _ in batches.values():
+        assert env.take_status() & abi.DECODE_TRUNCATED == 0
+    for form in ("grid", "mixture"):
+        least = {}
+        for master in ("expert", "learned"):
+            ok = wins[(form, master)]
+            least[master] = next((S_ for S_ in SIZES if all(ok[T_] for T_ in SIZES if T_ >= S_)), 33)
+        print(json.dumps({"what": f"smallest S from which grouping wins at every row count, {form} form", **least, "both": max(least.values())}))
+    sys.exit(0)
+
+env, st = played_batch(N)
 base = {"label": args.label, "envs": N, "devices": M, "compromised_share": round(float(((st["flags"] & S.F_COMP) != 0).mean()), 4),
         "owned_share": round(float(((st["flags"] & S.F_OWNED) != 0).mean()), 4)}
 
